@@ -2,7 +2,9 @@
 """Headline benchmark: functional bootstraps per second (batched), N=1024 -- BASELINE.json configs[1].
 
     python bench.py [--gpus N] [--steps K] [--warmup W]                      # the headline (workload "batch")
+    python bench.py --full [--gpus N] ...                                    # ... and every leg beside it (see below)
     python bench.py --workload circuit --mode gate|sample [--gpus N] ...     # BASELINE configs[3] stand-in
+    python bench.py ... --dump-outputs DIR                                   # + the last step's outputs as DIR/*.npy
 
 A "step" is one pass of the hot path (key switch + modulus switch + blind rotation + sample extraction)
   batch:   over one synthetic batch of `--batch` independent ciphertexts per GPU (weak scaling: keys replicated,
@@ -20,11 +22,16 @@ and exits with the child's code.  With WORLD_SIZE set (the driver's own torchrun
 
 Prints ONE JSON line (rank 0): the contract fields; `roofline` for the dominant kernel (blind rotation, timed live with HIP
 events on its own stream through libfbsexec's profile hooks: `frac` = ALGORITHMIC work over time over the FP64 issue peak,
-`valu_frac` = executed instructions from the offline PMC record of profiles/r03/, refused when taken on other kernel sources);
-at N = 1 `cpu_baseline` (the scalar CPU oracle on a bounded sample of the same batch, and `tuned`: the AVX-512 IFMA baseline,
-both checked bit for bit against the GPU's ciphertexts), `secure` (the same batch at the 128-bit parameter sets) and
-`shared_rotations`; at N > 1 `sharded`: one mapped circuit cut over the ranks three ways (gate groups with one RCCL all-gather
-per level, sample groups, and the layout distributed.choose_sharding picks), strong scaling, next to the weak-scaling headline.
+`valu_frac` = executed instructions from the offline PMC record of profiles/r03/, refused when taken on other kernel sources).
+With --full, the legs that take runs of their own: at N = 1 `cpu_baseline` (the scalar CPU oracle on a bounded sample of the
+same batch, and `tuned`: the AVX-512 IFMA baseline, both checked bit for bit against the GPU's ciphertexts), `secure` (the same
+batch at the 128-bit parameter sets) and `shared_rotations`; at N > 1 `sharded`: one mapped circuit cut over the ranks three
+ways (gate groups with one RCCL all-gather per level, sample groups, and the layout distributed.choose_sharding picks), strong
+scaling, next to the weak-scaling headline.  Without --full a run sets up, warms up, times its steps and prints the line.
+
+--dump-outputs DIR: rank 0 writes what the last timed step computed -- its output ciphertexts (ciphertexts.npy, one row per
+ciphertext), their decryptions (messages.npy) and the row indices (rows.npy; a fixed seeded sample past 64 MB), all float64.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -93,6 +100,11 @@ def parse_args(argv=None):
     ap.add_argument("--secure", action="store_true",
                     help="circuit: the 128-bit parameter set choose_params returns for the program's (p, norm2) instead of the "
                          "reduced-noise benchmark set")
+    ap.add_argument("--full", action="store_true",
+                    help="batch: also the legs beside the headline (cpu_baseline, secure, shared_rotations at --gpus 1; the "
+                         "sharded circuit legs at --gpus > 1); a plain run sets up, times its steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; rank 0)")
     args = ap.parse_args(argv)
     if args.steps is None:
         args.steps = 20 if args.workload == "batch" else 2
@@ -163,7 +175,7 @@ def worker(args):
         if dist is not None:
             dist.destroy_process_group()
         return 3
-    if args.workload == "batch" and world > 1 and not args.no_sharded_legs:
+    if args.workload == "batch" and world > 1 and args.full and not args.no_sharded_legs:
         sharded = sharded_legs(rank, world, local, dist, args.sharded_circuit, args.sharded_samples, args.sharded_reduced_noise)   # every rank takes part; rank 0 holds the record
         if rank == 0:
             result["sharded"] = sharded
@@ -199,6 +211,27 @@ def all_ok(ok, dist):
     flag = torch.tensor([1 if ok else 0], device="cuda")
     dist.all_reduce(flag, op=dist.ReduceOp.MIN)
     return bool(flag.item())
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(path, cts, msgs):
+    """--dump-outputs: the output ciphertexts of the last timed step (one row of ct_words words each; words are residues
+    below the 46-bit modulus, exact in float64) and what they decrypt to.  Past DUMP_BYTES, a fixed seeded sample of rows;
+    rows.npy holds their indices either way."""
+    import numpy as np
+    cts = cts.reshape(-1, cts.shape[-1])
+    msgs = np.asarray(msgs).reshape(-1)
+    assert len(msgs) == len(cts) and int(cts.max(initial=0)) < 1 << 53
+    rows = np.arange(len(cts))
+    per_row = (cts.shape[1] + 2) * 8
+    if len(rows) * per_row > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(len(cts), DUMP_BYTES // per_row, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "ciphertexts.npy"), cts[rows].astype(np.float64))
+    np.save(os.path.join(path, "messages.npy"), msgs[rows].astype(np.float64))
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
 
 
 def params_record(prm):
@@ -370,6 +403,8 @@ def run_batch(args, rank, world, local, dist):
     ok = all_ok(ok, dist)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, ctx.decrypt(out))
     value = world * B * args.steps / elapsed
     result = dict(metric="functional bootstraps/sec (batched), N=1024", value=value, unit="FBS/s", n_gpus=world,
                   steps=args.steps, warmup=args.warmup, ms_per_step=elapsed / args.steps * 1e3,
@@ -382,10 +417,10 @@ def run_batch(args, rank, world, local, dist):
                               batch_per_gpu=B, parallelism="replicas of the batch per GPU, keys replicated, no collective",
                               device=ctx.device_info, params=params_record(prm)),
                   decrypt_ok=ok, roofline=roofline_record(prm, prof, prof["kernels"], B, args.steps, ctx.stat("cu_count")))
-    if world == 1 and args.cpu_sample != 0:
+    if world == 1 and args.full and args.cpu_sample != 0:
         result["cpu_baseline"] = cpu_baseline(prm, tables, cts, ids, out, args.cpu_sample)
     ctx.close()
-    if world == 1 and not args.no_secure:
+    if world == 1 and args.full and not args.no_secure:
         sec = result["secure"] = secure_leg(B, local, max(3, args.steps // 2), args.oracle_sample)
         # the deployable number beside the benchmark shape: the same batch at the 128-bit set for p = 15, norm2 70 (N = 1024, k = 2).
         # `value` stays on BASELINE's P1024 configuration.
@@ -736,6 +771,8 @@ def run_circuit(args, rank, world, local, dist):
     ok = all_ok(ok, dist)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out.cpu().numpy().view(np.uint64), got)
     fbs_per_eval = prog.n_bootstrap * T * (world if args.mode == "sample" else 1)
     value = fbs_per_eval * args.steps / elapsed
     return dict(metric="functional bootstraps/sec (batched), N=1024", value=value, unit="FBS/s", n_gpus=world, steps=args.steps,

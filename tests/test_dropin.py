@@ -1,17 +1,47 @@
-"""Drop-in checks on the CPU: the module-name shim, and -- where the reference is present (build container only) --
-the REFERENCE's own mappers building their programs into this package's LutExecEnv, byte-identical to what they
-build into the reference's."""
+"""Drop-in checks on the CPU: the module-name shim, and the REFERENCE's own mappers building their programs into this
+package's LutExecEnv, byte-identical to what they build into the reference's.
+
+The mappers' side is recorded data (tests/golden/_dropin_traces.json.gz): the reference's map_to_fbs was run with this
+package's fbs_exec_env shadowing its own, and every call it made on the LutExecEnv (input / const / linear / bootstrap /
+output; a node argument as the index of the call that returned it, a numpy scalar with its dtype) was kept in order -- and, with the search
+swapped in, every call of MapToFBSHeur._find_lincomb_coefs_search with what the reference's own method answers.  The
+tests replay those calls into the env imported under the reference's module name."""
+import gzip
 import io
+import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
-from tests.helpers import load_fixture
+from tests.helpers import GOLDEN, load_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/fbs_mapper"
+
+
+def traces():
+    with gzip.open(os.path.join(GOLDEN, "_dropin_traces.json.gz"), "rb") as f:
+        return json.loads(f.read().decode())
+
+
+def replay(calls):
+    """The recorded mapper calls on a fresh LutExecEnv of the shim module; -> the program text the mapper's caller prints."""
+    from fbs_exec_env import LutExecEnv
+    env, made = LutExecEnv(), []
+
+    def arg(v):
+        if isinstance(v, dict):
+            return made[v["node"]] if "node" in v else np.dtype(v["np"]).type(v["v"])
+        return [arg(x) for x in v] if isinstance(v, list) else v
+    for name, args, kw in calls:
+        made.append(getattr(env, name)(*[arg(a) for a in args], **{k: arg(v) for k, v in kw.items()}))
+    assert "tfhe_fbs_map_amd" in type(env).__module__
+    env.remove_dangling_nodes()
+    s = io.StringIO()
+    env.print(os=s, show_outputs=True)
+    return s.getvalue()
 
 
 def test_module_name_shim():
@@ -23,66 +53,40 @@ def test_module_name_shim():
     assert out == "m1 = 1 * a + 2 * b \nm2 = Bootstrap(m1, [0, 1, 1, 0])\nOutput o = m2\n"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("mapper,p,fixture", [("search", 7, "full_adder__search_p7"), ("naive", 7, "aoi21__naive_p7"),
                                               ("search", 15, "aes_sbox__search_p15"), ("basic", 2, "ascon_lut__basic_p2")])
 def test_reference_mappers_build_into_this_env(mapper, p, fixture):
-    """Run the reference's map_to_fbs (imported read-only, in a subprocess) with OUR fbs_exec_env shadowing
-    theirs: the mapped program text must equal the fixture the reference produced with its own class."""
-    circuit = fixture.split("__")[0]
-    gen = {"full_adder": "full_adder_bench", "aoi21": "aoi21_bench", "aes_sbox": "aes_sbox", "ascon_lut": "ascon_lut"}[circuit]
-    code = f"""
-import sys, io, logging
-sys.dont_write_bytecode = True
-sys.argv = ['x']
-sys.path.insert(0, '/root/reference'); sys.path.insert(0, '/root/reference/experiments'); sys.path.insert(0, {REF!r})
-sys.path.insert(0, {ROOT!r})                      # our fbs_exec_env shadows fbs_mapper/fbs_exec_env.py
-import fbs_exec_env
-assert 'tfhe_fbs_map_amd' in fbs_exec_env.LutExecEnv.__module__
-import bit_exec_env, map_to_fbs, generate_benchmarks as gb
-logging.disable(logging.CRITICAL)
-env = bit_exec_env.BitExecEnv(); gb.Bit.set_env(env); gb.{gen}(); env.remove_dangling_nodes()
-m = map_to_fbs.MapToFBSBasic() if {mapper!r} == 'basic' else map_to_fbs.MapToFBSHeur(fbs_size={p}, max_fbs_size={2 * p}, max_truth_table_size=16, cone_merger={mapper!r})
-lut = m.map(env); lut.remove_dangling_nodes()
-assert type(lut).__module__.startswith('tfhe_fbs_map_amd')
-s = io.StringIO(); lut.print(os=s, show_outputs=True); sys.stdout.write(s.getvalue())
-"""
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True,
-                         env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1")).stdout
-    assert out == load_fixture(fixture)["fbs"]
+    """The reference's map_to_fbs building into OUR fbs_exec_env (its recorded calls, replayed): the mapped program text
+    must equal the fixture the reference produced with its own class."""
+    rec = traces()["mappers"][fixture]
+    assert (rec["mapper"], rec["p"]) == (mapper, p) and rec["calls"]
+    assert replay(rec["calls"]) == load_fixture(fixture)["fbs"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("p,fixture", [(7, "full_adder__search_p7"), (15, "aes_sbox__search_p15")])
-def test_reference_mapper_with_the_search_swapped_in(p, fixture):
-    """`mapper_search.install(MapToFBSHeur)` on the REFERENCE's own class: the mapper must walk through the replaced
-    method and map to the same program.  There is no GPU in the build container, so here the function behind the
-    binding is stood in for by the test oracle (same arguments, same return value); on the GPU box
-    tests/test_mapper_search.py holds the kernel itself against the recorded reference results."""
-    circuit = fixture.split("__")[0]
-    gen = {"full_adder": "full_adder_bench", "aes_sbox": "aes_sbox"}[circuit]
-    code = f"""
-import sys, io, logging
-sys.dont_write_bytecode = True
-sys.argv = ['x']
-sys.path.insert(0, '/root/reference'); sys.path.insert(0, '/root/reference/experiments'); sys.path.insert(0, {REF!r})
-sys.path.insert(0, {ROOT!r})
-import bit_exec_env, map_to_fbs, generate_benchmarks as gb
-from tfhe_fbs_map_amd import mapper_search
-from oracle import mapper_search_oracle as mso
-calls = []
-def stand_in(xy_mvt, r_tt, fbs_size, max_fbs_size, device=0):
-    calls.append(len(r_tt))
-    return mso.find_lincomb_coefs_search(xy_mvt[:, 0], xy_mvt[:, 1], r_tt, fbs_size, max_fbs_size)
-mapper_search.find_lincomb_coefs_search = stand_in
-mapper_search.install(map_to_fbs.MapToFBSHeur)
-logging.disable(logging.CRITICAL)
-env = bit_exec_env.BitExecEnv(); gb.Bit.set_env(env); gb.{gen}(); env.remove_dangling_nodes()
-m = map_to_fbs.MapToFBSHeur(fbs_size={p}, max_fbs_size={2 * p}, max_truth_table_size=16, cone_merger='search')
-lut = m.map(env); lut.remove_dangling_nodes()
-assert calls, 'the replaced method was never reached'
-s = io.StringIO(); lut.print(os=s, show_outputs=True); sys.stdout.write(s.getvalue())
-"""
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True,
-                         env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1")).stdout
-    assert out == load_fixture(fixture)["fbs"]
+def test_reference_mapper_with_the_search_swapped_in(p, fixture, monkeypatch):
+    """`mapper_search.install(MapToFBSHeur)`: the installed method, on every call the reference's mapper made of it, must
+    give what the reference's own method gave, and the mapper's calls on the env then map to the same program.  There is
+    no GPU here, so the function behind the binding is stood in for by the test oracle (same arguments, same return value);
+    on the GPU box tests/test_mapper_search.py holds the kernel itself against the recorded reference results."""
+    from tfhe_fbs_map_amd import mapper_search
+    from oracle import mapper_search_oracle as mso
+    rec = traces()["search"][fixture]
+    calls = []
+
+    def stand_in(xy_mvt, r_tt, fbs_size, max_fbs_size, device=0):
+        calls.append(len(r_tt))
+        return mso.find_lincomb_coefs_search(xy_mvt[:, 0], xy_mvt[:, 1], r_tt, fbs_size, max_fbs_size)
+
+    class MapToFBSHeur:                     # what the installed method reads of the reference's mapper object
+        fbs_size, max_fbs_size = p, 2 * p
+    monkeypatch.setattr(mapper_search, "find_lincomb_coefs_search", stand_in)
+    m = mapper_search.install(MapToFBSHeur)()
+    for c in rec["searches"]:
+        ab, mvt = m._find_lincomb_coefs_search(np.asarray(c["xy"], np.int64), np.asarray(c["tt"], np.int64))
+        if c["ab"] is None:
+            assert ab is None and mvt is None
+        else:
+            assert list(ab) == c["ab"] and np.asarray(mvt).tolist() == c["mvt"]
+    assert calls and len(calls) == len(rec["searches"]), 'the replaced method was never reached'
+    assert replay(rec["calls"]) == load_fixture(fixture)["fbs"]

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +21,7 @@ def run_bench(*args):
 
 
 def test_headline_line_has_the_contract_fields():
-    d = run_bench("--steps", "3", "--warmup", "1", "--batch", "256", "--cpu-sample", "8")
+    d = run_bench("--steps", "3", "--warmup", "1", "--batch", "256", "--cpu-sample", "8", "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "secure"):
         assert key in d, key
@@ -58,14 +59,38 @@ def test_headline_line_has_the_contract_fields():
     assert f["fused"]["params"]["security_bits_estimate"] >= 127.9 and f["fused"]["margin_sigmas_at_its_norm2"] >= 5.9
 
 
+def test_plain_line_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """Without --full a run sets up, times its steps and prints the line -- none of the legs beside the headline; with
+    --dump-outputs it writes what the last timed step computed, float64, and the same again on a second run."""
+    args = ("--steps", "2", "--warmup", "1", "--batch", "128")
+    d = run_bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in d, key
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["decrypt_ok"]
+    assert not {"cpu_baseline", "secure", "value_secure", "shared_rotations", "sharded"} & set(d)
+    assert abs(d["value"] - 128 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+    run_bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["ciphertexts.npy", "messages.npy", "rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["ciphertexts.npy"].shape == (128, 1025) and a["rows.npy"].tolist() == list(range(128))
+    assert set(a["messages.npy"].tolist()) <= {0, 1} and 0 < a["ciphertexts.npy"].max() < 2 ** 46
+    for f in files:
+        assert np.array_equal(a[f], np.load(tmp_path / "b" / f)), f
+
+
 @pytest.mark.parametrize("mode", ["gate", "sample"])
-def test_circuit_workload(mode):
+def test_circuit_workload(mode, tmp_path):
     d = run_bench("--workload", "circuit", "--mode", mode, "--circuit", "adder8__search_p15", "--samples", "8",
-                  "--steps", "1", "--warmup", "1")
+                  "--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path))
     assert d["decrypt_ok"] and d["config"]["mode"] == mode and d["config"]["rccl_ranks"] == 1
     assert d["scaling"] == ("strong" if mode == "gate" else "weak")
     assert d["config"]["wire_slots"] < d["config"]["wires"]
     assert d["value"] > 0 and set(d["kernels_ms_per_step"]) == {"keyswitch", "blind_rotate", "lincomb"}
+    cts, msgs = np.load(tmp_path / "ciphertexts.npy"), np.load(tmp_path / "messages.npy")
+    assert cts.dtype == msgs.dtype == np.float64 and len(cts) == len(msgs) and len(msgs) % 8 == 0
 
 
 def test_circuit_workload_at_the_secure_set():
@@ -84,7 +109,7 @@ def test_two_rank_line_carries_the_sharded_legs():
     sock = socket.socket(); sock.bind(("127.0.0.1", 0)); port = sock.getsockname()[1]; sock.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "128",
-           "--sharded-circuit", "adder8__search_p15", "--sharded-samples", "6"]
+           "--full", "--sharded-circuit", "adder8__search_p15", "--sharded-samples", "6"]
     rc = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, FBS_BENCH_SHARE_GPU="1"))
     assert rc.returncode == 0, rc.stderr[-3000:]
     lines = [ln for ln in rc.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]

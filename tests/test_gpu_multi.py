@@ -71,8 +71,8 @@ def test_sharded_runners_on_rccl_bit_identical(tmp_path, name, T, flavour):
 
 @needs_two
 def test_bench_two_gpus_reports_rccl_legs():
-    """`python bench.py --gpus 2 --steps 2` exactly as the driver calls it (no WORLD_SIZE: bench.py starts its own ranks)."""
-    rc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    """`python bench.py --gpus 2 --steps 2 --full` as the driver calls it (no WORLD_SIZE: bench.py starts its own ranks)."""
+    rc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
                          "--sharded-circuit", "adder8__search_p15", "--sharded-samples", "16"],
                         capture_output=True, text=True, timeout=1200,
                         env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")})
