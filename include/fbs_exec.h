@@ -110,13 +110,14 @@ void fbs_ctx_destroy(fbs_ctx *ctx);
  * Zero leaves a buffer as it is.  After it, the only blocking case left is a call that exceeds what was reserved. */
 int fbs_ctx_reserve(fbs_ctx *ctx, size_t max_keyswitches, size_t max_shared_rows, size_t wire_words);
 /* Launcher knobs -- which kernel shape a launch takes.  The defaults are the measured choices; tests set them to reach
- * every launcher branch in one process, tools/ to time one shape against another.  Results never depend on them.
- *   "ks_gemm_min" (1)  key switches per launch from which the int8 GEMM on the matrix cores is used
- *   "ks_mfma" (1), "ks_fp" (1), "ks_cols_major" (1), "ks_split" (0 = automatic)   key-switch fallbacks / grid order
- *   "br_whole_cu" (1)       whole rounds of a launch as one four-bootstrap workgroup per CU
- *   "br_cu_kernel" (1)      launches that leave most of the chip empty as ONE bootstrap per CU (eight waves)
- *   "br_cu_max_per_cu" (2)  ... up to this many bootstraps per CU
- *   "br_cu_lean" (1)        ... and between one and two per CU as two 128-register workgroups per CU (2: always, 0: never) */
+ * every kernel instantiation at small sizes.  Results never depend on them.
+ *   "ks_mfma" (1)           0: no int8 GEMM on the matrix cores for the key switch
+ *   "ks_fp" (1)             0: ... and the integer kernels instead of the FP64 one
+ *   "br_cu_kernel" (1)      launches of up to two bootstraps per CU as ONE bootstrap per CU (eight or twelve waves)
+ *   "br_cu_lean" (1)        ... and between one and two per CU as two 128-register workgroups per CU (2: always, 0: never)
+ *   "br_k2_shape" (0)       GLWE dimension 2: 0 by launch size, 3 always three waves per bootstrap, 12 always twelve
+ *   "br_glwe_fpw" (0)       other GLWE dimensions >= 2: bootstraps per workgroup, 0 by launch size; 1, 2; larger: the
+ *                           throughput shape */
 int fbs_ctx_tune(fbs_ctx *ctx, const char *knob, int64_t value);
 /* counters: "scratch_growths" (how often a call (re)allocated scratch, i.e. blocked), "ms_capacity", "acc_capacity",
  * "wires_capacity", "next_nonce", "cu_count" */

@@ -1,11 +1,16 @@
 // Sanitizer harness for the HOST side of libfbsexec ("race detection / sanitizers" -- on the CPU build only; the
 // GPU pool has no AddressSanitizer).  Built by tests/c/Makefile with g++ -fsanitize=address,undefined from the product's own
-// sources -- csrc/fbs_plan.cpp (the program loader's scheduling, slot reuse and level-index construction) and csrc/fbs_host.cpp
-// (key generation, encryption, decryption, test vectors) -- and driven by tests/test_sanitizers.py.  No GPU, no HIP call.
+// sources -- csrc/fbs_plan.cpp (the program loader's scheduling, slot reuse and level-index construction), csrc/fbs_host.cpp
+// (key generation, encryption, decryption, test vectors) and csrc/fbs_select.cpp (parameter admission, kernel selection) -- and
+// driven by tests/test_sanitizers.py and tests/test_select.py.  No GPU, no HIP call.
 //
 //   host_harness plan  < description        the plan of a program (plain and with shared rotations), EXECUTED in the clear on
 //                                           wire slots exactly as the level kernels index them; prints the outputs
 //   host_harness crypto                     keygen / encrypt / decrypt / test vectors at toy parameter sets, checked
+//   host_harness select < cases             per line "n log_n k l beta t gamma p group cu_count count [knob=value ...]": the
+//                                           launches a key switch and a blind rotation of `count` make, one per line
+//                                           ("ks" or "br", kernel name, first bootstrap, count, tab-separated), or "error" and the
+//                                           code fbs_ctx_create refuses the set with; a blank line after each case
 //
 // description (text, whitespace separated): n_inputs n_instr n_terms n_outputs n_tables T
 //   kind[n_instr] arg0[n_instr] arg1[n_instr] const[n_instr] term_coef[n_terms] term_src[n_terms] out_wire[n_outputs]
@@ -14,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -206,9 +212,49 @@ static int mode_crypto() {
     return 0;
 }
 
+static int mode_select() {
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        if (line.find_first_not_of(" \t") == std::string::npos) continue;
+        std::istringstream in(line);
+        fbs_params p{};
+        long long cus = 0, count = 0;
+        if (!(in >> p.n >> p.log_n_poly >> p.k >> p.l_bsk >> p.beta_bsk >> p.t_ksk >> p.gamma_ksk >> p.p_msg >> p.bsk_group >> cus >> count) ||
+            cus < 1 || count < 0) {
+            fprintf(stderr, "bad case: %s\n", line.c_str());
+            return 2;
+        }
+        p.sigma_lwe = 1 << 8, p.sigma_glwe = 1 << 4;
+        fbs_ctx ctx;
+        int rc = host_ctx_init(&ctx, &p, 1, nullptr);
+        if (rc == FBS_OK) rc = check_kernel_built(&ctx);   // (what fbs_ctx_create refuses)
+        if (rc != FBS_OK) {
+            printf("error\t%d\n\n", rc);
+            continue;
+        }
+        ctx.cu_count = (int)cus;
+        for (std::string kv; in >> kv;) {
+            const size_t eq = kv.find('=');
+            int64_t *slot = eq == std::string::npos ? nullptr : tune_knob(ctx.tune, kv.substr(0, eq));
+            if (!slot) {
+                fprintf(stderr, "bad knob: %s\n", kv.c_str());
+                return 2;
+            }
+            *slot = atoll(kv.c_str() + eq + 1);
+        }
+        for (const Launch &l : select_keyswitch(&ctx, (size_t)count))
+            printf("ks\t%s\t%zu\t%zu\n", kernel_name(l.kernel).c_str(), l.first, l.count);
+        for (const Launch &l : select_blind_rotate(&ctx, (size_t)count))
+            printf("br\t%s\t%zu\t%zu\n", kernel_name(l.kernel).c_str(), l.first, l.count);
+        printf("\n");
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "plan")) return mode_plan();
     if (argc >= 2 && !strcmp(argv[1], "crypto")) return mode_crypto();
-    fprintf(stderr, "usage: host_harness plan|crypto\n");
+    if (argc >= 2 && !strcmp(argv[1], "select")) return mode_select();
+    fprintf(stderr, "usage: host_harness plan|crypto|select\n");
     return 2;
 }

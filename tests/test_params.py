@@ -146,11 +146,11 @@ def test_glwe_dimension_three_at_n512_for_small_plaintext_moduli():
     assert choose_params(31, 325, glwe_dims=DEFAULT_GLWE_DIMS) == choose_params(31, 325)
     for k in (2, 3, 4, 5):
         for log_n in (8, 9, 10, 11):
-            assert glwe_shape_built(k, log_n) == ((k <= 4 and log_n <= 9) or (k <= 3 and log_n == 10))
+            assert glwe_shape_built(log_n, k) == ((k <= 4 and log_n <= 9) or (k <= 3 and log_n == 10))
     for dims in ((1, 2, 3, 4, 5), (4, 5)):
         for p, norm2 in ((2, 1), (4, 2)):
             s = choose_params(p, norm2, glwe_dims=dims, poly_sizes=(8, 9, 10, 11, 12))
-            assert s.k == 1 or glwe_shape_built(s.k, s.log_n_poly)
+            assert s.k == 1 or glwe_shape_built(s.log_n_poly, s.k)
     prm = choose_params(4, 2, glwe_dims=DEFAULT_GLWE_DIMS)
     assert abs(glwe_instructions(prm) - 307 * 512 * 4 * (2 * 4.0 * 9 + 7.0 * 4 * 4 + 2 + 12) / 64.0) < 1e-6
 

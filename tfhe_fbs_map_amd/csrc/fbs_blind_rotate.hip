@@ -565,17 +565,13 @@ static int upload_keys_t(fbs_ctx *ctx) {
                            polys);
         e = hipGetLastError();
         constexpr int LLS = lanes_log2_for_small_launch(LOGN);
-        if constexpr (LLS != LL) {
-            // (two key bits per step: a second copy of the 1.5 times larger key only where a kernel reads it -- N = 2048, l <= 2)
-            // (... and N = 1024 at GLWE dimension 2: the whole-workgroup latency shape of fbs_blind_rotate_k2.hip)
-            if (ctx->group == 1 || (LOGN == 11 && ctx->p.l_bsk <= 2) || (LOGN == 10 && ctx->p.k == 2)) {
-                if (e == hipSuccess && !ctx->d_bsk_hat_small) e = hipMalloc(&ctx->d_bsk_hat_small, polys * N * 8);
-                if (e == hipSuccess) {
-                    hipLaunchKernelGGL((k_bsk_transform<LOGN, LLS>), dim3(grid), dim3(1 << LLS), 0, ctx->stream, d_src,
-                                       reinterpret_cast<double *>(ctx->d_bsk_hat_small), reinterpret_cast<const double *>(ctx->d_tw_fwd),
-                                       n_inv, polys);
-                    e = hipGetLastError();
-                }
+        if (small_key_needed(ctx)) {
+            if (e == hipSuccess && !ctx->d_bsk_hat_small) e = hipMalloc(&ctx->d_bsk_hat_small, polys * N * 8);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL((k_bsk_transform<LOGN, LLS>), dim3(grid), dim3(1 << LLS), 0, ctx->stream, d_src,
+                                   reinterpret_cast<double *>(ctx->d_bsk_hat_small), reinterpret_cast<const double *>(ctx->d_tw_fwd),
+                                   n_inv, polys);
+                e = hipGetLastError();
             }
         }
     }
@@ -646,34 +642,38 @@ int dev_upload_keys(fbs_ctx *ctx) {
     return set_error(ctx, FBS_E_INVALID, "unsupported N");
 }
 
-// One workgroup per CU -- ALL the waves a CU holds in one barrier domain.  The two waves that share a SIMD then advance
-// in lockstep; as separate workgroups the SIMD's oldest-first arbitration lets one of them run ahead (measured per
-// workgroup with the wall clock, P1024: 6.0 ms for the favoured ones, 10.7 ms for the others, every XCD alike), and once
-// the favoured half has left, the rest runs with one wave per SIMD and nothing to cover its stalls: 10.7 ms per 1024-batch
-// against 10.0 ms in lockstep.  It pays when the launch fills whole rounds (a round = what the chip holds at once: 600
-// bootstraps take 9.1 ms as small workgroups, 10.05 ms as whole-CU ones); beyond a few rounds the hardware refills freed
-// slots anyway.  Measured and NOT adopted for the other shapes: two-level sets at N = 1024 (slower with the priority hand-over below:
-// 152.5 against 155.5 k FBS/s at p = 2, 124 against 131 k at p = 4), N = 2048 with
-// two bootstraps per workgroup (pairs 10.13 against 9.94 ms, l = 2 23.1 against 21.7 ms; with the priority hand-over as
-// well: 10.34 against 9.87 ms at 1024 bootstraps, 82.4 against 73.7 ms at 8192 -- the transforms' own barriers then span
-// eight waves).
-// How many bootstraps of a launch of `count` go to whole-CU workgroups: all of them when the last round is (nearly) full,
-// else the whole rounds only -- the rest follows as a launch of its own in the shape that suits its size (a partly
-// filled round is faster as small workgroups: 768 bootstraps 8.2 ms against 9.3).
-static size_t whole_cu_share(const fbs_ctx *ctx, size_t count, size_t per_round) {
-    if (!ctx->tune.br_whole_cu) return 0;   // (A/B switch)
-    const size_t r = count % per_round;
-    return (r == 0 || 8 * r >= 7 * per_round) ? count : count - r;
+// the instantiation of a k_blind_rotate or k_blind_rotate_pairs descriptor (fbs_select.hpp); false for any other
+static bool launch_blind_rotate_main(const Kernel &k, const BrArgs &a, hipStream_t stream) {
+    if (k.family == Family::BLIND_ROTATE) {
+#define X(L, LL, DIG, FPW, TURNS)                                                                                               \
+    if (k.t[0] == L && k.t[1] == (LL) && k.t[2] == DIG && k.t[3] == FPW && k.alt == !(TURNS)) {                                 \
+        hipLaunchKernelGGL((k_blind_rotate<L, LL, DIG, FPW, TURNS>), dim3((unsigned)((a.count + FPW - 1) / FPW)),              \
+                           dim3((2 << (LL)) * FPW), 0, stream, a);                                                              \
+        return true;                                                                                                            \
+    }
+        FBS_BR_KERNELS(X)
+#undef X
+    }
+    if (k.family == Family::PAIRS) {
+#define X(L, DIG)                                                                                                               \
+    if (k.t[0] == L && k.t[1] == lanes_log2_for(L) && k.t[2] == DIG) {                                                          \
+        hipLaunchKernelGGL((k_blind_rotate_pairs<L, lanes_log2_for(L), DIG>), dim3((unsigned)a.count), dim3(2 << lanes_log2_for(L)), \
+                           0, stream, a);                                                                                       \
+        return true;                                                                                                            \
+    }
+        FBS_PAIRS_KERNELS(X)
+#undef X
+    }
+    return false;
 }
 
 int dev_blind_rotate(fbs_ctx *ctx, const fbs_tvset *tv, const GateView &gv, const uint32_t *d_ms, hipStream_t stream) {
     const fbs_params &p = ctx->p;
     BrArgs a{};
-    a.gv = gv;
     a.ms = d_ms;
-    a.bsk_hat = reinterpret_cast<const double *>(ctx->d_bsk_hat);
     a.tw_fwd = reinterpret_cast<const double *>(ctx->d_tw_fwd);
     a.tw_inv = reinterpret_cast<const double *>(ctx->d_tw_inv);
+    a.psi_pow = reinterpret_cast<const double *>(ctx->d_psi_pow);
     a.tvs = tv->d_tvs;
     a.post = tv->d_post;
     a.n = p.n;
@@ -682,226 +682,25 @@ int dev_blind_rotate(fbs_ctx *ctx, const fbs_tvset *tv, const GateView &gv, cons
     a.ct_words = ctx->D + 1;
     // (entry n_tables of the set is TV_0: selectable only by the rotations of a fused program, whose ids the host wrote)
     a.n_tables = (gv.acc_rows || gv.row_words) ? tv->n_tables + 1 : std::max(1u, tv->n_tables);
-    const size_t count = gv.count;
-    if (count == 0) return FBS_OK;
-    if (count > 0x7FFFFFFFull) return set_error(ctx, FBS_E_INVALID, "batch too large for one launch");
-    a.count = count;
-    // Two bootstraps per workgroup exactly where two-wave workgroups would double up on half of the SIMDs: between one
-    // and two bootstraps per CU (measured per 1024-coefficient launch: 6.5 ms against 9.8).  Up to one per CU the
-    // two-wave form is faster (5.7 against 6.5 ms), beyond two per CU too (9.8-11.1 against 11.1).
-    const bool pair = lanes_log2_for((int)p.log_n_poly) == 6 && count > (size_t)ctx->cu_count && count <= 2 * (size_t)ctx->cu_count;
-    dim3 grid((unsigned)(pair ? (count + 1) / 2 : count));
-    if (p.k >= 2 && !(p.k == 2 && p.log_n_poly == 10 && ctx->group == 2 && p.l_bsk == 1)) {
-        // every (k >= 2, N, l, key bits per step) but the one with kernels of its own: k + 1 waves per bootstrap (fbs_blind_rotate_glwe.hip).
-        // Bootstraps per workgroup by launch size: one up to one bootstrap per CU, two up to two, the throughput shape beyond; a launch
-        // longer than a round of the throughput shape whose last round would be at most two bootstraps per CU: whole rounds first, the
-        // rest as a launch of its own (k = 3, N = 512: 1 024 = 768 + 256 bootstraps in 4.1 + 1.8 ms against two rounds' 7.4)
-        a.psi_pow = reinterpret_cast<const double *>(ctx->d_psi_pow);
-        const size_t cus = (size_t)ctx->cu_count;
-        const int full = glwe_full_fpw(p.log_n_poly, p.k);
-        const size_t per_round = (size_t)full * cus, rest_n = per_round ? count % per_round : 0;
-        const bool small_ok = ctx->tune.br_cu_max_per_cu >= 1 && ctx->tune.br_glwe_fpw == 0;
-        const bool cut = small_ok && ctx->tune.br_whole_cu && count > per_round && rest_n != 0 && rest_n <= (full > 2 ? 2 : 1) * cus;
-        if (cut) {
-            a.count = count - rest_n;
-            a.gv.count = a.count;
-        }
-        int fpw = (int)ctx->tune.br_glwe_fpw;
-        if (fpw == 0) fpw = !small_ok ? full : a.count <= cus ? 1 : (a.count <= 2 * cus && full > 2) ? 2 : full;
-        hipEvent_t c0, c1;
-        prof_begin(ctx, 1, stream, &c0, &c1);
-        if (!launch_blind_rotate_glwe(ctx, a, fpw, stream, &ctx->prof.kernel[1])) {
-            if (c0) ctx->prof.pool.push_back({c0, c1});
-            return set_error(ctx, FBS_E_INVALID, "no blind-rotation kernel for this GLWE dimension and polynomial size");
-        }
-        prof_end(ctx, 1, stream, c0, c1);
-        FBS_HIP(ctx, hipGetLastError());
-        if (!cut) return FBS_OK;
-        GateView rest = gv;
-        rest.f_begin += count - rest_n;
-        rest.count = rest_n;
-        if (rest.out_rows) rest.out_rows += (count - rest_n) * (size_t)(rest.row_words ? rest.row_words : ctx->D + 1);
-        return dev_blind_rotate(ctx, tv, rest, d_ms, stream);
-    }
-    if (p.k == 2) {   // GLWE dimension 2 at N = 1024, two key bits per step, one level: the shape the selector picks for p <= 15
-        a.psi_pow = reinterpret_cast<const double *>(ctx->d_psi_pow);
-        // a launch longer than a round of four-bootstrap workgroups whose last round would be (far) from full: whole rounds first,
-        // the rest as a launch of its own in the twelve-wave shape (1 124 = 1 024 + 100: 7.3 + 2.1 ms against two rounds' 14.5)
-        const size_t per_round = 4 * (size_t)ctx->cu_count, rest_n = count % per_round;
-        const bool cut = count > per_round && rest_n != 0 && rest_n <= K2_CU_ROUNDS * (size_t)ctx->cu_count && ctx->tune.br_whole_cu &&
-                         ctx->tune.br_k2_shape == 0 && ctx->tune.br_cu_kernel && ctx->tune.br_cu_max_per_cu >= 1;
-        if (cut) {
-            a.count = count - rest_n;
-            a.gv.count = a.count;
-        }
-        hipEvent_t c0, c1;
-        prof_begin(ctx, 1, stream, &c0, &c1);
-        if (!launch_blind_rotate_k2(ctx, a, stream, &ctx->prof.kernel[1])) {
-            if (c0) ctx->prof.pool.push_back({c0, c1});   // (the event pair goes back: nothing was recorded between them)
-            return set_error(ctx, FBS_E_INVALID, "no blind-rotation kernel for this k = 2 shape");
-        }
-        prof_end(ctx, 1, stream, c0, c1);
-        FBS_HIP(ctx, hipGetLastError());
-        if (!cut) return FBS_OK;
-        GateView rest = gv;
-        rest.f_begin += count - rest_n;
-        rest.count = rest_n;
-        if (rest.out_rows) rest.out_rows += (count - rest_n) * (size_t)(rest.row_words ? rest.row_words : ctx->D + 1);
-        return dev_blind_rotate(ctx, tv, rest, d_ms, stream);
-    }
-    if (ctx->group == 2) {
-        a.psi_pow = reinterpret_cast<const double *>(ctx->d_psi_pow);
-        // launches of at most one bootstrap per CU: the whole-CU shape (2.65-2.9 ms per bootstrap against 3.3-3.4; two rounds of
-        // it are no faster than two bootstraps side by side in the four-wave kernel: 5.44 against 5.35 ms per 512)
-        // Two gadget levels (the 128-bit sets for p = 31): the whole-CU shape for every launch, round after round -- the
-        // two-waves-per-polynomial kernel spills 100 registers there (22.7 ms per 1024 bootstraps against 17.1)
-        if ((count <= (size_t)ctx->cu_count || p.l_bsk == 2) && ctx->tune.br_cu_max_per_cu >= 1) {
-            hipEvent_t c0, c1;
-            prof_begin(ctx, 1, stream, &c0, &c1);
-            if (launch_blind_rotate_cu_pairs(ctx, a, stream, &ctx->prof.kernel[1])) {
-                prof_end(ctx, 1, stream, c0, c1);
-                FBS_HIP(ctx, hipGetLastError());
-                return FBS_OK;
-            }
-            if (c0) ctx->prof.pool.push_back({c0, c1});
-        }
-        const int dig2 = p.l_bsk == 1 ? 4 : p.beta_bsk <= 7 ? 3 : 0;
+    if (gv.count > 0x7FFFFFFFull) return set_error(ctx, FBS_E_INVALID, "batch too large for one launch");
+    for (const Launch &l : select_blind_rotate(ctx, gv.count)) {
+        a.gv = gv;
+        a.gv.f_begin += l.first;
+        a.gv.count = a.count = l.count;
+        if (a.gv.out_rows) a.gv.out_rows += l.first * (size_t)(gv.row_words ? gv.row_words : ctx->D + 1);
+        a.bsk_hat = reinterpret_cast<const double *>(reads_small_key(l.kernel) ? ctx->d_bsk_hat_small : ctx->d_bsk_hat);
+        ctx->prof.kernel[1] = kernel_name(l.kernel);
         hipEvent_t e0, e1;
         prof_begin(ctx, 1, stream, &e0, &e1);
-#define LAUNCH_PAIRS(L, DIG)                                                                                          \
-    do {                                                                                                               \
-        ctx->prof.kernel[1] = "k_blind_rotate_pairs<" #L "," + std::to_string(lanes_log2_for(L)) + "," #DIG ">";        \
-        hipLaunchKernelGGL((k_blind_rotate_pairs<L, lanes_log2_for(L), DIG>), dim3((unsigned)count),                   \
-                           dim3(2 << lanes_log2_for(L)), 0, stream, a);                                                \
-    } while (0)
-#define PAIRS_FOR(L)                                                                                                   \
-    case L:                                                                                                            \
-        if (dig2 == 4) LAUNCH_PAIRS(L, 4);                                                                             \
-        else if (dig2 == 3) LAUNCH_PAIRS(L, 3);                                                                        \
-        else LAUNCH_PAIRS(L, 0);                                                                                       \
-        break;
-        switch (p.log_n_poly) {
-            PAIRS_FOR(10)
-            PAIRS_FOR(11)
-            PAIRS_FOR(12)
-            default: return set_error(ctx, FBS_E_INVALID, "two key bits per step: N = 1024, 2048 or 4096 only");
+        if (!launch_blind_rotate_main(l.kernel, a, stream) && !launch_blind_rotate_cu(l.kernel, a, stream) &&
+            !launch_blind_rotate_k2(l.kernel, a, stream) && !launch_blind_rotate_glwe(l.kernel, a, stream)) {
+            if (e0) ctx->prof.pool.push_back({e0, e1});   // (the event pair goes back: nothing was recorded between them)
+            return set_error(ctx, FBS_E_INVALID, "no instantiation of " + ctx->prof.kernel[1]);
         }
-#undef PAIRS_FOR
-#undef LAUNCH_PAIRS
         prof_end(ctx, 1, stream, e0, e1);
         FBS_HIP(ctx, hipGetLastError());
-        return FBS_OK;
     }
-    const int by_beta = p.beta_bsk <= 7 ? 3 : p.beta_bsk <= 9 ? 2 : 1;
-    const int dig = p.l_bsk > 5 ? 0 : p.l_bsk == 1 ? 4 : p.l_bsk == 2 ? 4 + by_beta : by_beta;
-    // at most one bootstrap per CU: the shape with twice the waves per bootstrap, where there is one (fbs_ntt.hpp)
-    const bool small_launch = ctx->d_bsk_hat_small != nullptr && count <= (size_t)ctx->cu_count;
-    hipEvent_t e0, e1;
-    prof_begin(ctx, 1, stream, &e0, &e1);
-    {
-        // launches that leave most of the chip empty: one bootstrap on the eight waves of a CU (fbs_blind_rotate_cu.hip)
-        // Up to TWO bootstraps per CU: the second round of workgroups follows the first CU by CU (512 bootstraps: 5.9 ms against
-        // 6.5 ms for two bootstraps side by side in the two-waves-per-bootstrap kernel; 384: 6.0 against 6.5).  Beyond that
-        // the small workgroups of k_blind_rotate win (768: 8.3 ms against three rounds of 2.95).
-        if (ctx->d_bsk_hat_small && count <= (size_t)ctx->cu_count * (size_t)ctx->tune.br_cu_max_per_cu &&
-            launch_blind_rotate_cu(ctx, a, stream, &ctx->prof.kernel[1])) {
-            prof_end(ctx, 1, stream, e0, e1);
-            FBS_HIP(ctx, hipGetLastError());
-            return FBS_OK;
-        }
-    }
-    const size_t whole = (p.log_n_poly == 10 && dig == 3) ? whole_cu_share(ctx, count, 4 * (size_t)ctx->cu_count) : 0;
-    if (whole) {
-        // the benchmark shape: four bootstraps = the eight waves of a CU in one workgroup
-        a.count = whole;
-        a.gv.count = whole;
-        ctx->prof.kernel[1] = "k_blind_rotate<10,6,3,4>";
-        hipLaunchKernelGGL((k_blind_rotate<10, 6, 3, 4>), dim3((unsigned)((whole + 3) / 4)), dim3((2 << 6) * 4), 0, stream, a);
-        prof_end(ctx, 1, stream, e0, e1);
-        FBS_HIP(ctx, hipGetLastError());
-        if (whole == count) return FBS_OK;
-        GateView rest = gv;                       // what did not fill a round: its own launch, in the shape its size asks for
-        rest.f_begin += whole;
-        rest.count = count - whole;
-        if (rest.out_rows) rest.out_rows += whole * (size_t)(rest.row_words ? rest.row_words : ctx->D + 1);
-        return dev_blind_rotate(ctx, tv, rest, d_ms, stream);
-    } else if (p.log_n_poly == 10 && (dig == 6 || dig == 7) && count > 8 * (size_t)ctx->cu_count) {
-        // the two-level 128-bit sets at N = 1024 in launches of more than two rounds: no taking turns (see TURNS)
-        if (dig == 6) {
-            ctx->prof.kernel[1] = "k_blind_rotate<10,6,6,1,false>";
-            hipLaunchKernelGGL((k_blind_rotate<10, 6, 6, 1, false>), grid, dim3(2 << 6), 0, stream, a);
-        } else {
-            ctx->prof.kernel[1] = "k_blind_rotate<10,6,7,1,false>";
-            hipLaunchKernelGGL((k_blind_rotate<10, 6, 7, 1, false>), grid, dim3(2 << 6), 0, stream, a);
-        }
-    } else
-    switch (p.log_n_poly) {
-#define LAUNCH_LL(L, LL_, DIG, FPW)                                                                                    \
-    do {                                                                                                               \
-        ctx->prof.kernel[1] = "k_blind_rotate<" #L "," + std::to_string(LL_) + "," #DIG "," #FPW ">";                   \
-        hipLaunchKernelGGL((k_blind_rotate<L, LL_, DIG, FPW>), grid, dim3((2 << (LL_)) * FPW), 0, stream, a);          \
-    } while (0)
-#define LAUNCH_DIG(L, LL_, FPW)                                                                                        \
-    do {                                                                                                               \
-        if (dig == 4) LAUNCH_LL(L, LL_, 4, FPW);                                                                       \
-        else if (dig == 5) LAUNCH_LL(L, LL_, 5, FPW);                                                                  \
-        else if (dig == 6) LAUNCH_LL(L, LL_, 6, FPW);                                                                  \
-        else if (dig == 7) LAUNCH_LL(L, LL_, 7, FPW);                                                                  \
-        else if (dig == 3) LAUNCH_LL(L, LL_, 3, FPW);                                                                  \
-        else if (dig == 2) LAUNCH_LL(L, LL_, 2, FPW);                                                                  \
-        else if (dig == 1) LAUNCH_LL(L, LL_, 1, FPW);                                                                  \
-        else LAUNCH_LL(L, LL_, 0, FPW);                                                                                \
-    } while (0)
-#define X(L)                                                                                                           \
-    case L:                                                                                                            \
-        if constexpr (lanes_log2_for_small_launch(L) != lanes_log2_for(L)) {                                           \
-            if (small_launch) {                                                                                        \
-                a.bsk_hat = reinterpret_cast<const double *>(ctx->d_bsk_hat_small);                                    \
-                LAUNCH_DIG(L, lanes_log2_for_small_launch(L), 1);                                                      \
-                break;                                                                                                 \
-            }                                                                                                          \
-        }                                                                                                              \
-        if constexpr (lanes_log2_for(L) == 6) {                                                                        \
-            if (pair) LAUNCH_DIG(L, lanes_log2_for(L), 2);                                                             \
-            else LAUNCH_DIG(L, lanes_log2_for(L), 1);                                                                  \
-        } else {                                                                                                       \
-            LAUNCH_DIG(L, lanes_log2_for(L), 1);                                                                       \
-        }                                                                                                              \
-        break;
-        FBS_FOR_EACH_SHAPE(X)
-#undef X
-#undef LAUNCH_DIG
-#undef LAUNCH_LL
-        default: return set_error(ctx, FBS_E_INVALID, "unsupported N");
-    }
-    prof_end(ctx, 1, stream, e0, e1);
-    FBS_HIP(ctx, hipGetLastError());
     return FBS_OK;
-}
-
-// Every blind-rotation instantiation dev_blind_rotate can pick, by the rules of the dispatch above (fbs_kernel_catalog;
-// tests/test_gpu_dispatch.py drives each one and checks it against the oracle)
-void blind_rotate_catalog(std::vector<std::string> *out) {
-    auto name = [](int L, int ll, int dig, int fpw) {
-        return "k_blind_rotate<" + std::to_string(L) + "," + std::to_string(ll) + "," + std::to_string(dig) + "," + std::to_string(fpw) + ">";
-    };
-    for (int L : {8, 9, 10, 11, 12}) {
-        const int ll = lanes_log2_for(L), small = lanes_log2_for_small_launch(L);
-        for (int dig = 0; dig < 8; dig++) {
-            out->push_back(name(L, ll, dig, 1));
-            if (ll == 6) out->push_back(name(L, ll, dig, 2));
-            if (small != ll) out->push_back(name(L, small, dig, 1));
-        }
-    }
-    out->push_back("k_blind_rotate<10,6,3,4>");
-    out->push_back("k_blind_rotate<10,6,6,1,false>");
-    out->push_back("k_blind_rotate<10,6,7,1,false>");
-    for (int L : {10, 11, 12})
-        for (int dig : {0, 3, 4})
-            out->push_back("k_blind_rotate_pairs<" + std::to_string(L) + "," + std::to_string(lanes_log2_for(L)) + "," + std::to_string(dig) + ">");
-    blind_rotate_cu_catalog(out);
-    blind_rotate_k2_catalog(out);
-    blind_rotate_glwe_catalog(out);
 }
 
 int dev_polymul(fbs_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_c, hipStream_t stream) {

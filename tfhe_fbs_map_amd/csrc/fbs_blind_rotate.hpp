@@ -77,23 +77,12 @@ struct KeyRows {
     }
 };
 
-// fbs_blind_rotate_cu.hip: one bootstrap on the eight waves of a CU (N = 1024, at most four gadget levels).  Returns false when
-// there is no instantiation for the context's parameters (the caller then takes the generic kernel); *kernel = its name.
-bool launch_blind_rotate_cu(fbs_ctx *ctx, const BrArgs &a, hipStream_t stream, std::string *kernel);
-// ... with two key bits per step (N = 2048, one gadget level)
-bool launch_blind_rotate_cu_pairs(fbs_ctx *ctx, const BrArgs &a, hipStream_t stream, std::string *kernel);
-void blind_rotate_cu_catalog(std::vector<std::string> *out);
-// fbs_blind_rotate_k2.hip: GLWE dimension k = 2 at N = 1024 (two key bits per step, one gadget level): three waves per bootstrap and
-// one / two / four bootstraps per workgroup, or one bootstrap on the twelve waves of a workgroup (launches that leave most of the
-// chip empty).  Returns false when the context is not of that shape.
-constexpr size_t K2_CU_ROUNDS = 3;   // bootstraps per CU up to which a k = 2 launch takes the twelve-wave shape, round after round
-bool launch_blind_rotate_k2(fbs_ctx *ctx, const BrArgs &a, hipStream_t stream, std::string *kernel);
-void blind_rotate_k2_catalog(std::vector<std::string> *out);
-// fbs_blind_rotate_glwe.hip: every other (k >= 2, N <= 1024, l, key bits per step): k + 1 waves per bootstrap, one wave per polynomial.
-// Returns false when no instantiation is built for the context's (N, k).
-// fpw: bootstraps per workgroup -- 1, 2, or anything else for the throughput shape (glwe_full_fpw of them)
-bool launch_blind_rotate_glwe(fbs_ctx *ctx, const BrArgs &a, int fpw, hipStream_t stream, std::string *kernel);
-int glwe_full_fpw(uint32_t log_n, uint32_t k);
-void blind_rotate_glwe_catalog(std::vector<std::string> *out);
+// the launch of one descriptor (fbs_select.hpp) in each launch file: false when the descriptor is not of its families
+// fbs_blind_rotate_cu.hip: one bootstrap on the eight waves of a CU (k = 1)
+bool launch_blind_rotate_cu(const Kernel &k, const BrArgs &a, hipStream_t stream);
+// fbs_blind_rotate_k2.hip: GLWE dimension k = 2 at N = 1024, two key bits per step, one gadget level
+bool launch_blind_rotate_k2(const Kernel &k, const BrArgs &a, hipStream_t stream);
+// fbs_blind_rotate_glwe.hip: every other k >= 2: k + 1 waves per bootstrap, one wave per polynomial
+bool launch_blind_rotate_glwe(const Kernel &k, const BrArgs &a, hipStream_t stream);
 
 }  // namespace fbs

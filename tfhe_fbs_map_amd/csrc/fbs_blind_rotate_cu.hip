@@ -22,35 +22,15 @@
 // 128-register workgroups per CU) 5.4 ms for 512.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <type_traits>
 
 #include "fbs_blind_rotate_cu.hpp"
 
 namespace fbs {
 
-// -DFBS_CU_TRACE (experiments only, tools/variant builds): cycles per phase of a step, per wave of workgroup 0, summed over the
-// rotation and printed by the launcher -- where a step's time goes when the instruction count says it should be shorter
-#ifdef FBS_CU_TRACE
-__device__ unsigned long long g_cu_trace[8 * 16];
-#define FBS_TRACE_INIT unsigned long long tr_t = __builtin_readcyclecounter(), tr_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define FBS_TRACE(k)                                              \
-    {                                                             \
-        const unsigned long long now = __builtin_readcyclecounter(); \
-        tr_acc[k] += now - tr_t;                                  \
-        tr_t = now;                                               \
-    }
-#define FBS_TRACE_FLUSH                                           \
-    if (blockIdx.x == 0 && (threadIdx.x & 63u) == 0)              \
-        for (int k = 0; k < 12; k++) g_cu_trace[(threadIdx.x >> 6) * 16 + k] = tr_acc[k];
-#else
-#define FBS_TRACE_INIT
-#define FBS_TRACE(k)
-#define FBS_TRACE_FLUSH
-#endif
 // Issue priority between the two waves of a SIMD (wave w of component 0 and wave w of component 1).  Left alone the SIMD issues
 // the OLDER wave first whenever both are ready: component 0 runs every stretch between two barriers at full speed, waits at
-// the barrier, and component 1 finishes it ALONE, with nobody to fill its stalls (traced with -DFBS_CU_TRACE at P1024: of a
+// the barrier, and component 1 finishes it ALONE, with nobody to fill its stalls (traced with cycle stamps at P1024: of a
 // 7.0 M-cycle rotation component 0 spends 2.9 M waiting at barriers while component 1 issues at 54 % of the rate the pair
 // reaches together).  favour() flips the lead in the middle of a stretch -- component 1 leads the first half, component 0
 // the second -- so both arrive at the barrier together.  FBS_CU_PRIO: 0 off, 1 the long stretch only (forward transforms |
@@ -161,7 +141,6 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
         }
     };
     if constexpr (PREFETCH) request_keys(0);
-    FBS_TRACE_INIT
     for (uint32_t i = 0; i < a.n; i++) {
         const uint32_t r = __builtin_amdgcn_readfirstlane(r_next);
         r_next = ms[i + 1];     // ms has n+1 entries; the last one (the body) is read here and ignored
@@ -170,7 +149,6 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
             if constexpr (PREFETCH) request_keys(i_next);
             continue;
         }
-        FBS_TRACE(0)
 
         // key words of this step: this thread's four evaluations of the 2 NL polynomials of its component's rows.  Requested
         // now, used after the forward transforms: a step's 96 KB come out of L2 while the transforms run.
@@ -191,7 +169,6 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
                 digits[m] = (uint32_t)__builtin_fma(d, round_scale, round_offset) ^ sign_bits;
             }
         }
-        FBS_TRACE(1)
 
         // ---- all levels: digits -> the two cross stages -> re-deal -> private transforms, together ------------------------
         double x[NL][E];
@@ -216,9 +193,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
 #pragma unroll
                 for (int r = 0; r < EP; r++) region[q * M + t + (uint32_t)LANES * r] = x[lv][q * EP + r];
         }
-        FBS_TRACE(2)
         __syncthreads();
-        FBS_TRACE(3)
         if constexpr (!LEAN) favour<1>(second);
         double *bufs[NL];
 #pragma unroll
@@ -228,7 +203,6 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
             for (int m = 0; m < E; m++) x[lv][m] = bufs[lv][ln + 64u * m];
         }
         tw.template forward<NL>(x, bufs, ln);
-        FBS_TRACE(4)
         if constexpr (!LEAN) favour<1>(!second);
         if constexpr (LEAN) {   // what the forward transforms had no registers for
 #pragma unroll
@@ -263,9 +237,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
             // ---- hand the partner its half (through the accumulator words: every rotation has read them by now) ---------
 #pragma unroll
             for (int m = 0; m < E; m++) accbuf_partner[(uint32_t)LANES * m + t] = other[m];
-            FBS_TRACE(5)
             __syncthreads();
-            FBS_TRACE(6)
             if constexpr (!LEAN) favour<2>(second);
 #pragma unroll
             for (int m = 0; m < E; m++) own[m] += accbuf[(uint32_t)LANES * m + t];
@@ -277,9 +249,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
             Part::sync();
 #pragma unroll
             for (int m = 0; m < E; m++) bufs[0][ln + 64u * m] = own[m];
-            FBS_TRACE(7)
             __syncthreads();
-            FBS_TRACE(8)
 #pragma unroll
             for (int q = 0; q < 4; q++)
 #pragma unroll
@@ -304,11 +274,8 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
             acc[m] = fp_center(acc[m] + own[m]);
             accbuf[t + (uint32_t)LANES * m] = acc[m];
         }
-        FBS_TRACE(9)
         __syncthreads();
-        FBS_TRACE(10)
     }
-    FBS_TRACE_FLUSH
 
     // ---- sample extraction of coefficient 0, plus the table's constant -----------------------------
     if (!live) return;
@@ -466,7 +433,6 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
     const uint32_t ahead_off = threadIdx.x < slice_lines && ahead_line < ROW_LINES ? ahead_line * 128u : 0x7FFFFFF0u;
     uint32_t ahead_word = 0;
 #endif
-    FBS_TRACE_INIT
     for (uint32_t i = 0; i < n_pairs; i++) {
         uint32_t e[3];
         e[0] = __builtin_amdgcn_readfirstlane(e0_next);
@@ -482,7 +448,6 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
             continue;
         }
         e[2] = (e[0] + e[1]) & (2u * N - 1u);
-        FBS_TRACE(0)
 
         // ---- what memory has to bring: psi^(e o_lane) for the three exponents, and the key words -----------------------------
         double A[3];
@@ -532,9 +497,7 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
                     for (int r = 0; r < EP; r++) region[q * M + t + (uint32_t)LANES * r] = x[lv][q * EP + r];
             }
         }
-        FBS_TRACE(1)
         __syncthreads();
-        FBS_TRACE(2)
         double *bufs[NL];
 #pragma unroll
         for (int lv = 0; lv < NL; lv++) {
@@ -543,7 +506,6 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
             for (int m = 0; m < E; m++) x[lv][m] = bufs[lv][ln + 64u * m];
         }
         tw.template forward<NL>(x, bufs, ln);
-        FBS_TRACE(3)
 
         // ---- the monomial factors ----------------------------------------------------------------------------------------
         // zeta_m^e = psi^(e o_lane) omega^(e k_m), k_m = r1 + 2 r0 + 4 r2 for register m = (r2 r1 r0); omega^(t + 4) = -omega^t.
@@ -629,9 +591,7 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
         // ---- hand the partner its half, private inverse, re-deal back, the two joining stages, accumulate ------------------------
 #pragma unroll
         for (int m = 0; m < E; m++) hand_partner[64u * m + ln] = other[m];
-        FBS_TRACE(4)
         __syncthreads();
-        FBS_TRACE(5)
 #if FBS_CU_PAIRS_L2_AHEAD
         {   // (no branch: a thread without a line asks beyond the resource's end, which touches no memory)
             const uint32_t far_step = i + FBS_CU_PAIRS_L2_AHEAD < n_pairs ? i + FBS_CU_PAIRS_L2_AHEAD : n_pairs - 1;
@@ -662,9 +622,7 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
         Part::sync();
 #pragma unroll
         for (int m = 0; m < E; m++) hand_mine[ln + 64u * m] = own[m];
-        FBS_TRACE(6)
         __syncthreads();
-        FBS_TRACE(7)
 #pragma unroll
         for (int q = 0; q < 4; q++)
 #pragma unroll
@@ -684,9 +642,7 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
         }
 #pragma unroll
         for (int m = 0; m < E; m++) acc[m] = fp_center(acc[m] + own[m]);
-        FBS_TRACE(8)
     }
-    FBS_TRACE_FLUSH
 #if FBS_CU_PAIRS_L2_AHEAD
     asm volatile("" ::"v"(ahead_word));   // (never looked at; this keeps the loads)
 #endif
@@ -711,94 +667,27 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
     }
 }
 
-#ifdef FBS_CU_TRACE
-void cu_trace_dump(const char *kernel);
-#define FBS_TRACE_DUMP(k) cu_trace_dump(k)
-#else
-#define FBS_TRACE_DUMP(k)
-#endif
-
-bool launch_blind_rotate_cu_pairs(fbs_ctx *ctx, const BrArgs &a, hipStream_t stream, std::string *kernel) {
-    const fbs_params &p = ctx->p;
-    if (ctx->group != 2 || !ctx->d_bsk_hat_small || p.log_n_poly != 11 || p.l_bsk > 2 || !ctx->tune.br_cu_kernel) return false;
-    BrArgs b = a;
-    b.bsk_hat = reinterpret_cast<const double *>(ctx->d_bsk_hat_small);
-    if (p.l_bsk == 1) {
-        *kernel = "k_blind_rotate_cu_pairs<11,1>";
-        hipLaunchKernelGGL((k_blind_rotate_cu_pairs<11, 1>), dim3((unsigned)a.count), dim3(512), 0, stream, b);
-        FBS_TRACE_DUMP(kernel->c_str());
-    } else {
-        *kernel = "k_blind_rotate_cu_pairs<11,2>";
-        hipLaunchKernelGGL((k_blind_rotate_cu_pairs<11, 2>), dim3((unsigned)a.count), dim3(512), 0, stream, b);
-        FBS_TRACE_DUMP(kernel->c_str());
+// the instantiation of a k_blind_rotate_cu or k_blind_rotate_cu_pairs descriptor (fbs_select.hpp); false for any other
+bool launch_blind_rotate_cu(const Kernel &k, const BrArgs &a, hipStream_t stream) {
+    if (k.family == Family::CU) {
+#define X(L, NL, FIRST, LEAN)                                                                                          \
+    if (k.t[0] == L && k.t[1] == NL && k.t[2] == FIRST && k.alt == LEAN) {                                            \
+        hipLaunchKernelGGL((k_blind_rotate_cu<L, NL, FIRST, LEAN>), dim3((unsigned)a.count), dim3(512), 0, stream, a); \
+        return true;                                                                                                   \
     }
-    return true;
-}
-
-bool launch_blind_rotate_cu(fbs_ctx *ctx, const BrArgs &a, hipStream_t stream, std::string *kernel) {
-    const fbs_params &p = ctx->p;
-    // N = 1024 with up to four gadget levels, N = 2048 with up to two (LDS: 2 N + 2 l N words + the inverse twiddles)
-    if (ctx->group != 1 || !ctx->d_bsk_hat_small) return false;
-    if (!((p.log_n_poly == 10 && p.l_bsk <= 4) || (p.log_n_poly == 11 && p.l_bsk <= 2))) return false;
-    if (!ctx->tune.br_cu_kernel) return false;   // (A/B switch: the generic kernel on the four-wave transform)
-    const int first = p.beta_bsk <= 7 ? 2 : p.beta_bsk <= 9 ? 1 : 0;
-    BrArgs b = a;
-    b.bsk_hat = reinterpret_cast<const double *>(ctx->d_bsk_hat_small);
-    const dim3 grid((unsigned)a.count), block(512);
-    // more than one bootstrap per CU: the two-workgroups-per-CU variant where there is one (N = 1024, up to three levels)
-    // (512 bootstraps at P1024: 6.07 ms as two rounds of the 162-register kernel, 5.40 ms with two workgroups per CU; 1 536 =
-    // 1 024 + 512: 99.7 -> 105.3 k FBS/s)
-    const bool lean = p.log_n_poly == 10 && p.l_bsk <= 3 &&
-                      (ctx->tune.br_cu_lean == 2 || (ctx->tune.br_cu_lean == 1 && a.count > (size_t)ctx->cu_count));
-#define CU_CASE(L, NL, FIRST)                                                                    \
-    if (p.log_n_poly == L && p.l_bsk == NL && first == FIRST) {                                  \
-        if constexpr (L == 10 && NL <= 3) {                                                      \
-            if (lean) {                                                                          \
-                *kernel = "k_blind_rotate_cu<" #L "," #NL "," #FIRST ",lean>";                   \
-                hipLaunchKernelGGL((k_blind_rotate_cu<L, NL, FIRST, true>), grid, block, 0, stream, b); \
-                FBS_TRACE_DUMP(kernel->c_str());                                                 \
-                return true;                                                                     \
-            }                                                                                    \
-        }                                                                                        \
-        *kernel = "k_blind_rotate_cu<" #L "," #NL "," #FIRST ">";                                \
-        hipLaunchKernelGGL((k_blind_rotate_cu<L, NL, FIRST>), grid, block, 0, stream, b);        \
-        FBS_TRACE_DUMP(kernel->c_str());                                                         \
-        return true;                                                                             \
+        FBS_CU_KERNELS(X)
+#undef X
     }
-    CU_CASE(10, 1, 0) CU_CASE(10, 1, 1) CU_CASE(10, 1, 2)
-    CU_CASE(10, 2, 0) CU_CASE(10, 2, 1) CU_CASE(10, 2, 2)
-    CU_CASE(10, 3, 0) CU_CASE(10, 3, 1) CU_CASE(10, 3, 2)
-    CU_CASE(10, 4, 2)   // (l * beta <= 30: four levels have at most 7 bits each)
-    CU_CASE(11, 1, 0) CU_CASE(11, 1, 1) CU_CASE(11, 1, 2)
-    CU_CASE(11, 2, 0) CU_CASE(11, 2, 1) CU_CASE(11, 2, 2)
-#undef CU_CASE
+    if (k.family == Family::CU_PAIRS) {
+#define X(L, NL)                                                                                                    \
+    if (k.t[0] == L && k.t[1] == NL) {                                                                              \
+        hipLaunchKernelGGL((k_blind_rotate_cu_pairs<L, NL>), dim3((unsigned)a.count), dim3(512), 0, stream, a);     \
+        return true;                                                                                                \
+    }
+        FBS_CU_PAIRS_KERNELS(X)
+#undef X
+    }
     return false;
-}
-
-#ifdef FBS_CU_TRACE
-void cu_trace_dump(const char *kernel) {
-    unsigned long long h[8 * 16];
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_cu_trace), sizeof h) != hipSuccess) return;
-    fprintf(stderr, "trace %s (cycles per phase, workgroup 0, whole rotation):\n", kernel);
-    for (int w = 0; w < 8; w++) {
-        fprintf(stderr, "  wave %d:", w);
-        for (int k = 0; k < 12; k++) fprintf(stderr, " %9llu", h[w * 16 + k]);
-        fprintf(stderr, "\n");
-    }
-}
-#endif
-
-void blind_rotate_cu_catalog(std::vector<std::string> *out) {
-    for (int nl = 1; nl <= 4; nl++)
-        for (int first = nl == 4 ? 2 : 0; first < 3; first++) {
-            out->push_back("k_blind_rotate_cu<10," + std::to_string(nl) + "," + std::to_string(first) + ">");
-            if (nl <= 3) out->push_back("k_blind_rotate_cu<10," + std::to_string(nl) + "," + std::to_string(first) + ",lean>");
-        }
-    for (int nl = 1; nl <= 2; nl++)
-        for (int first = 0; first < 3; first++)
-            out->push_back("k_blind_rotate_cu<11," + std::to_string(nl) + "," + std::to_string(first) + ">");
-    out->push_back("k_blind_rotate_cu_pairs<11,1>");
-    out->push_back("k_blind_rotate_cu_pairs<11,2>");
 }
 
 }  // namespace fbs

@@ -342,84 +342,31 @@ __global__ __launch_bounds__(64 * K1 * FPW) void k_blind_rotate_glwe(BrArgs a) {
     }
 }
 
-// Bootstraps per workgroup.  The THROUGHPUT shape fills a CU: twelve waves where the registers allow three waves per SIMD (N <= 512:
-// 4, 3, 2 bootstraps at k = 2, 3, 4), six to eight at N = 1024.  Launches that leave most of the chip empty take ONE bootstrap per
-// workgroup up to one per CU (every wave alone on its SIMD: a step is one wave's instruction chain, not three waves' sharing an issue
-// port) and two up to two per CU.  Measured at k = 3, N = 512, n = 614 (the 128-bit set for p <= 4), ms per launch: 64 / 256 bootstraps
-// 1.55 / 1.81 with one per workgroup against 3.32 / 3.37 with three; 512: 2.90 with two against 3.61; 768: 4.06 with three.  (FOUR per workgroup
-// there -- sixteen waves at 128 registers with 196 bytes spilled, one set of landing words -- 6.99 against 5.43 ms per 1 024, 20.6 against 14.5 per 3 072.)
-template <int LOGN, int K1>
-constexpr int glwe_fpw() {
-#ifdef FBS_EXP_GLWE_FPW       // (experiments: every shape)
-    return FBS_EXP_GLWE_FPW;
-#elif defined(FBS_EXP_GLWE_FPW_K3N512)   // (experiments: k = 3 at N = 512 only)
-    return LOGN == 9 && K1 == 4 ? FBS_EXP_GLWE_FPW_K3N512 : LOGN >= 10 ? 2 : 12 / K1;
-#else
-    return LOGN >= 10 ? 2 : 12 / K1;
-#endif
-}
-
+// the instantiation of a k_blind_rotate_glwe descriptor (fbs_select.hpp); false for any other.  Bootstraps per workgroup: 1, 2
+// and the throughput shape's (glwe_full_fpw)
 template <int LOGN, int K1, int GROUP, int FPW>
-static void launch_fpw(const BrArgs &a, hipStream_t stream, std::string *kernel) {
-    *kernel = "k_blind_rotate_glwe<" + std::to_string(LOGN) + "," + std::to_string(K1) + "," + std::to_string(GROUP) + "," + std::to_string(FPW) + ">";
+static bool launch_fpw(const BrArgs &a, hipStream_t stream) {
     hipLaunchKernelGGL((k_blind_rotate_glwe<LOGN, K1, GROUP, FPW>), dim3((unsigned)((a.count + FPW - 1) / FPW)), dim3(64 * K1 * FPW), 0, stream, a);
+    return true;
 }
 
 template <int LOGN, int K1, int GROUP>
-static void launch_one(int fpw, const BrArgs &a, hipStream_t stream, std::string *kernel) {
-    constexpr int FULL = glwe_fpw<LOGN, K1>();
-    if (fpw == 1) launch_fpw<LOGN, K1, GROUP, 1>(a, stream, kernel);
-    else if (fpw == 2) launch_fpw<LOGN, K1, GROUP, (FULL < 2 ? FULL : 2)>(a, stream, kernel);
-    else launch_fpw<LOGN, K1, GROUP, FULL>(a, stream, kernel);
+static bool launch_group(int fpw, const BrArgs &a, hipStream_t stream) {
+    constexpr int FULL = glwe_full_fpw(LOGN, K1 - 1);
+    return fpw == 1      ? launch_fpw<LOGN, K1, GROUP, 1>(a, stream)
+           : fpw == 2    ? launch_fpw<LOGN, K1, GROUP, 2>(a, stream)
+           : fpw == FULL ? launch_fpw<LOGN, K1, GROUP, FULL>(a, stream)
+                         : false;
 }
 
-// the shapes built: k = 2, 3, 4 at N = 256 and 512, k = 2, 3 at N = 1024; one or two key bits per step
-#define FBS_GLWE_SHAPES(X) X(8, 3) X(8, 4) X(8, 5) X(9, 3) X(9, 4) X(9, 5) X(10, 3) X(10, 4)
-
-bool glwe_shape_built(uint32_t log_n, uint32_t k) {
-#define X(L, K) \
-    if (log_n == L && k + 1 == K) return true;
+bool launch_blind_rotate_glwe(const Kernel &k, const BrArgs &a, hipStream_t stream) {
+    if (k.family != Family::GLWE) return false;
+#define X(L, K1)                                                                                                          \
+    if (k.t[0] == L && k.t[1] == K1)                                                                                      \
+        return k.t[2] == 1 ? launch_group<L, K1, 1>(k.t[3], a, stream) : k.t[2] == 2 && launch_group<L, K1, 2>(k.t[3], a, stream);
     FBS_GLWE_SHAPES(X)
 #undef X
     return false;
-}
-
-// bootstraps per workgroup of the throughput shape (what a full round is made of: glwe_full_fpw x CUs)
-int glwe_full_fpw(uint32_t log_n, uint32_t k) {
-#define X(L, K) \
-    if (log_n == L && k + 1 == K) return glwe_fpw<L, K>();
-    FBS_GLWE_SHAPES(X)
-#undef X
-    return 0;
-}
-
-// fpw: bootstraps per workgroup (1, 2, or anything else for the throughput shape)
-bool launch_blind_rotate_glwe(fbs_ctx *ctx, const BrArgs &a, int fpw, hipStream_t stream, std::string *kernel) {
-    const fbs_params &p = ctx->p;
-    if (p.k < 2 || !glwe_shape_built(p.log_n_poly, p.k)) return false;
-#define X(L, K)                                                           \
-    if (p.log_n_poly == L && p.k + 1 == K) {                              \
-        if (ctx->group == 2) launch_one<L, K, 2>(fpw, a, stream, kernel); \
-        else launch_one<L, K, 1>(fpw, a, stream, kernel);                 \
-        return true;                                                      \
-    }
-    FBS_GLWE_SHAPES(X)
-#undef X
-    return false;
-}
-
-void blind_rotate_glwe_catalog(std::vector<std::string> *out) {
-    std::vector<std::string> names;
-#define X(L, K)                                  \
-    for (int g = 1; g <= 2; g++)                 \
-        for (int fpw : {1, 2, glwe_fpw<L, K>()}) \
-            names.push_back("k_blind_rotate_glwe<" + std::to_string(L) + "," + std::to_string(K) + "," + std::to_string(g) + "," + std::to_string(fpw) + ">");
-    FBS_GLWE_SHAPES(X)
-#undef X
-    // (a shape whose throughput form holds two bootstraps per workgroup lists "2" once)
-    std::sort(names.begin(), names.end());
-    names.erase(std::unique(names.begin(), names.end()), names.end());
-    out->insert(out->end(), names.begin(), names.end());
 }
 
 }  // namespace fbs

@@ -37,7 +37,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
 #include <type_traits>
 
 #include "fbs_blind_rotate_cu.hpp"
@@ -219,24 +218,6 @@ __global__ __launch_bounds__(192 * FPW) void k_blind_rotate_pairs_k2(BrArgs a) {
     }
 }
 
-// -DFBS_CU_TRACE (experiments only, tools/trace_k2.sh): cycles per phase of a step, per wave of workgroup 0, summed over the rotation
-#ifdef FBS_CU_TRACE
-__device__ unsigned long long g_k2_trace[12 * 16];
-#define K2_TRACE_INIT unsigned long long tr_t = __builtin_readcyclecounter(), tr_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#define K2_TRACE(k)                                                  \
-    {                                                                \
-        const unsigned long long now = __builtin_readcyclecounter(); \
-        tr_acc[k] += now - tr_t;                                     \
-        tr_t = now;                                                  \
-    }
-#define K2_TRACE_FLUSH                                               \
-    if (blockIdx.x == 0 && (threadIdx.x & 63u) == 0)                 \
-        for (int k = 0; k < 10; k++) g_k2_trace[(threadIdx.x >> 6) * 16 + k] = tr_acc[k];
-#else
-#define K2_TRACE_INIT
-#define K2_TRACE(k)
-#define K2_TRACE_FLUSH
-#endif
 // ---------------------------------------------------------------------------------------------
 // The LATENCY shape: ONE k = 2 bootstrap on the twelve waves of a workgroup -- what a launch that leaves most of the chip empty
 // wants (a rank's slice of a level of a sharded circuit, a narrow level, the leftovers of a round): a bootstrap is n / 2 dependent
@@ -272,7 +253,7 @@ __device__ unsigned long long g_k2_trace[12 * 16];
 // LOWEST bits of P, the two HIGHEST of its bit reversal, so 2 bitrev(P) + 1 = o_lane + 512 k_m with k_m = j1 + 2 j0, and
 // psi^512 = R is a primitive FOURTH root of unity: zeta_m^e = psi^(e o_lane) R^(e k_m).  ONE table look-up per lane and exponent;
 // R^e is wave-uniform (picked among 1, R, -1, -R by scalar instructions) and multiplied in once.
-// WHERE A STEP'S TIME GOES (-DFBS_CU_TRACE, tools/trace_k2.sh, profiles/r04/k2_cu_phase_trace.txt; cycle stamps per wave of workgroup 0): of
+// WHERE A STEP'S TIME GOES (profiles/r04/k2_cu_phase_trace.txt; cycle stamps per wave of workgroup 0): of
 // ~17 k cycles per step the forward transform takes 5.7 k, the products 4.5 k, the inverse 4.4 k for the wave that finishes last; the three
 // waves of a SIMD (component 0, 1, 2: oldest first) do NOT advance together -- component 0 is issued first whenever it is ready and waits
 // 2.1 M of a rotation's 6.2 M cycles at the barriers, component 2 never waits.  Handing the lead over in the middle of every stretch
@@ -364,7 +345,6 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
     double2 kw0[3][K1], kw1[3][K1];
     request(0, Pair0{}, kw0);
     uint32_t e0_next = ms[0], e1_next = ms[1];
-    K2_TRACE_INIT
     for (uint32_t i = 0; i < n_pairs; i++) {
         uint32_t e[3];
         e[0] = __builtin_amdgcn_readfirstlane(e0_next);
@@ -377,7 +357,6 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
                 continue;
         }
         e[2] = (e[0] + e[1]) & (2u * N - 1u);
-        K2_TRACE(0)
 
         // ---- psi^(e o_lane) for the three exponents: one look-up each (psi^(x + N) = -psi^x) -------------------------------------
         double A[3];
@@ -400,9 +379,7 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
         }
 #pragma unroll
         for (int q = 0; q < PARTS; q++) xf[q * M + t] = x[0][q];
-        K2_TRACE(1)
         __syncthreads();
-        K2_TRACE(2)
         double *bufs[1] = {xf + w * M};   // the words only this wave reads: its private exchange buffer from here on
 #pragma unroll
         for (int m = 0; m < E; m++) x[0][m] = bufs[0][ln + 64u * m];
@@ -454,7 +431,6 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
         // transform, ahead of its last four stages, and both pairs' with the second pair's key words asked for a step ahead as well:
         // 2.06 / 2.35 -> 2.30 / 2.50 and 2.25 / 2.45 ms per launch of 64 / 256, same box, twice.  profiles/r04/k2_cu_bundle_in_transform_ab.txt)
         LaneNtt256::forward_multi<1, 0>(x, bufs, ln, tw.f, [&] { request(i, Pair1{}, kw1); });
-        K2_TRACE(3)
         root_powers();
         bundle(Pair0{}, kw0, w0);
         finish(Pair0{}, w0);
@@ -467,9 +443,7 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
             to_c1[64u * m + ln] = prod[1][m];
             to_c2[64u * m + ln] = prod[2][m];
         }
-        K2_TRACE(4)
         __syncthreads();
-        K2_TRACE(5)
         double own[E];
 #pragma unroll
         for (int m = 0; m < E; m++) own[m] = prod[0][m] + mine[64u * m + ln] + mine2[64u * m + ln];
@@ -478,9 +452,7 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
         Part::sync();
 #pragma unroll
         for (int m = 0; m < E; m++) mine[ln + 64u * m] = own[m];
-        K2_TRACE(6)
         __syncthreads();
-        K2_TRACE(7)
 #pragma unroll
         for (int q = 0; q < PARTS; q++) own[q] = back[q * M + t];
 #pragma unroll
@@ -497,9 +469,7 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
         }
 #pragma unroll
         for (int m = 0; m < E; m++) acc[m] = fp_center(acc[m] + own[m]);
-        K2_TRACE(8)
     }
-    K2_TRACE_FLUSH
 
     // ---- sample extraction of coefficient 0 (two mask polynomials, the body), plus the table's constant -----------------
     if (!live) return;
@@ -522,57 +492,23 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
     }
 }
 
-// k = 2: N = 1024, two key bits per step, one gadget level (what dev_supported admits).  Returns false when the context is not
-// of that shape.
-bool launch_blind_rotate_k2(fbs_ctx *ctx, const BrArgs &a, hipStream_t stream, std::string *kernel) {
-    const fbs_params &p = ctx->p;
-    if (p.k != 2 || p.log_n_poly != 10 || ctx->group != 2 || p.l_bsk != 1) return false;
-    const size_t cus = (size_t)ctx->cu_count;
-    // tune.br_k2_shape: 0 = by launch size (below); 3 = always the three-waves-per-bootstrap kernels; 12 = always the twelve-wave
-    // whole-workgroup shape (A/B measurements, dispatch tests)
-    const int64_t shape = ctx->tune.br_k2_shape;
-    const bool small = a.count <= cus * K2_CU_ROUNDS && ctx->tune.br_cu_kernel && ctx->tune.br_cu_max_per_cu >= 1;
-    if ((shape == 12 || (shape == 0 && small)) && ctx->d_bsk_hat_small) {
-        // launches of up to three bootstraps per CU: one bootstrap on twelve waves, round after round (n = 734, one box: 2.06 ms at
-        // 64, 2.36 at 256, 4.43 at 512, 6.37 at 768 bootstraps against 3.33 / 3.49 / 4.92 / 6.79 on three waves per bootstrap;
-        // from 769 on a round of four-bootstrap workgroups is ahead: 6.8-7.2 ms up to 1 024)
-        BrArgs b = a;
-        b.bsk_hat = reinterpret_cast<const double *>(ctx->d_bsk_hat_small);
-        *kernel = "k_blind_rotate_cu_k2";
-        hipLaunchKernelGGL(k_blind_rotate_cu_k2, dim3((unsigned)a.count), dim3(768), 0, stream, b);
-#ifdef FBS_CU_TRACE
-        {
-            unsigned long long h[12 * 16];
-            if (hipDeviceSynchronize() == hipSuccess && hipMemcpyFromSymbol(h, HIP_SYMBOL(g_k2_trace), sizeof h) == hipSuccess) {
-                fprintf(stderr, "trace k_blind_rotate_cu_k2 (cycles per phase, workgroup 0, whole rotation; wave = 4 component + part):\n");
-                for (int w = 0; w < 12; w++) {
-                    fprintf(stderr, "  wave %2d:", w);
-                    for (int k = 0; k < 9; k++) fprintf(stderr, " %9llu", h[w * 16 + k]);
-                    fprintf(stderr, "\n");
-                }
-            }
-        }
-#endif
+// the instantiation of a k_blind_rotate_pairs_k2 or k_blind_rotate_cu_k2 descriptor (fbs_select.hpp); false for any other
+bool launch_blind_rotate_k2(const Kernel &k, const BrArgs &a, hipStream_t stream) {
+    if (k.family == Family::CU_K2) {
+        hipLaunchKernelGGL(k_blind_rotate_cu_k2, dim3((unsigned)a.count), dim3(768), 0, stream, a);
         return true;
     }
-    // the three-waves-per-bootstrap kernel: up to one bootstrap per CU one per workgroup; up to two: two; beyond: four
-    // (measured per launch: tools/k2_check.py)
-    if (a.count <= cus && ctx->tune.br_cu_max_per_cu >= 1) {
-        *kernel = "k_blind_rotate_pairs_k2<10,1>";
-        hipLaunchKernelGGL((k_blind_rotate_pairs_k2<10, 1>), dim3((unsigned)a.count), dim3(192), 0, stream, a);
-    } else if (a.count <= 2 * cus && ctx->tune.br_cu_max_per_cu >= 1) {
-        *kernel = "k_blind_rotate_pairs_k2<10,2>";
-        hipLaunchKernelGGL((k_blind_rotate_pairs_k2<10, 2>), dim3((unsigned)((a.count + 1) / 2)), dim3(384), 0, stream, a);
-    } else {
-        *kernel = "k_blind_rotate_pairs_k2<10,4>";
-        hipLaunchKernelGGL((k_blind_rotate_pairs_k2<10, 4>), dim3((unsigned)((a.count + 3) / 4)), dim3(768), 0, stream, a);
+    if (k.family == Family::PAIRS_K2) {
+#define X(L, FPW)                                                                                                           \
+    if (k.t[0] == L && k.t[1] == FPW) {                                                                                     \
+        hipLaunchKernelGGL((k_blind_rotate_pairs_k2<L, FPW>), dim3((unsigned)((a.count + FPW - 1) / FPW)), dim3(192 * FPW), 0, \
+                           stream, a);                                                                                      \
+        return true;                                                                                                        \
     }
-    return true;
-}
-
-void blind_rotate_k2_catalog(std::vector<std::string> *out) {
-    for (const char *name : {"k_blind_rotate_pairs_k2<10,1>", "k_blind_rotate_pairs_k2<10,2>", "k_blind_rotate_pairs_k2<10,4>", "k_blind_rotate_cu_k2"})
-        out->push_back(name);
+        FBS_PAIRS_K2_KERNELS(X)
+#undef X
+    }
+    return false;
 }
 
 }  // namespace fbs

@@ -187,34 +187,17 @@ int fbs_poly_size_check(uint32_t poly_size) try {
     return FBS_OK;
 } FBS_API_CATCH(nullptr)
 
-static int64_t env_knob(const char *name, int64_t dflt) {
-    const char *e = getenv(name);
-    return e && *e ? atoll(e) : dflt;
-}
-
 static int ctx_create(const fbs_params *params, uint64_t seed, const uint8_t *seed32, int device, fbs_ctx **out) {
     if (!params || !out) return set_error(nullptr, FBS_E_INVALID, "null argument");
     *out = nullptr;
     std::unique_ptr<fbs_ctx> ctx(new fbs_ctx);
     // everything that is arithmetic on the parameter set (ranges, derived sizes, Delta, gadget factors, the random key): host code
-    // with no device in it (fbs_host.cpp: the sanitizer harness of tests/c/ runs the same function)
+    // with no device in it (fbs_host.cpp), then whether a kernel is built for the set (fbs_select.cpp): the sanitizer harness of
+    // tests/c/ runs the same functions
     int rc = host_ctx_init(ctx.get(), params, seed, seed32);
+    if (rc == FBS_OK) rc = check_kernel_built(ctx.get());
     if (rc != FBS_OK) return set_error(nullptr, rc, ctx->err);
     ctx->device = device;
-    // A/B switches of the launchers, settable per context with fbs_ctx_tune; the environment gives the defaults of a process
-    ctx->tune.ks_gemm_min = env_knob("FBS_KS_GEMM_MIN", ctx->tune.ks_gemm_min);
-    ctx->tune.ks_mfma = env_knob("FBS_KS_NO_MFMA", 0) ? 0 : 1;
-    ctx->tune.ks_fp = env_knob("FBS_KS_INTEGER", 0) ? 0 : 1;
-    ctx->tune.ks_cols_major = env_knob("FBS_KS_TILES_MAJOR", 0) ? 0 : 1;
-    ctx->tune.ks_split = env_knob("FBS_KS_SPLIT", 0);
-    ctx->tune.br_whole_cu = getenv("FBS_BR_SMALL_WORKGROUPS") ? 0 : 1;
-    ctx->tune.br_cu_kernel = getenv("FBS_BR_NO_CU_KERNEL") ? 0 : 1;
-    ctx->tune.br_cu_max_per_cu = env_knob("FBS_BR_CU_MAX_PER_CU", ctx->tune.br_cu_max_per_cu);
-    ctx->tune.br_cu_lean = env_knob("FBS_BR_CU_LEAN", ctx->tune.br_cu_lean);
-    ctx->tune.br_k2_shape = env_knob("FBS_BR_K2_SHAPE", ctx->tune.br_k2_shape);
-    ctx->tune.br_glwe_fpw = env_knob("FBS_BR_GLWE_FPW", ctx->tune.br_glwe_fpw);
-    rc = dev_supported(ctx.get());   // (is there a kernel instantiation for this shape?)
-    if (rc != FBS_OK) return set_error(nullptr, rc, ctx->err);
 
     int n_dev = 0;
     hipError_t e = hipGetDeviceCount(&n_dev);
@@ -255,11 +238,7 @@ int fbs_ctx_create_seeded(const fbs_params *params, const uint8_t seed[32], int 
 int fbs_ctx_tune(fbs_ctx *ctx, const char *knob, int64_t value) try {
     if (!ctx || !knob) return FBS_E_INVALID;
     const std::string k(knob);
-    Tune &t = ctx->tune;
-    int64_t *slot = k == "ks_gemm_min" ? &t.ks_gemm_min : k == "ks_mfma" ? &t.ks_mfma : k == "ks_fp" ? &t.ks_fp :
-                    k == "ks_cols_major" ? &t.ks_cols_major : k == "ks_split" ? &t.ks_split : k == "br_whole_cu" ? &t.br_whole_cu :
-                    k == "br_cu_kernel" ? &t.br_cu_kernel : k == "br_cu_max_per_cu" ? &t.br_cu_max_per_cu : k == "br_cu_lean" ? &t.br_cu_lean :
-                    k == "br_k2_shape" ? &t.br_k2_shape : k == "br_glwe_fpw" ? &t.br_glwe_fpw : nullptr;
+    int64_t *slot = tune_knob(ctx->tune, k);
     if (!slot) return set_error(ctx, FBS_E_INVALID, "unknown knob '" + k + "'");
     if (value < 0) return set_error(ctx, FBS_E_INVALID, "knob values are non-negative");
     *slot = value;
@@ -1061,8 +1040,7 @@ const char *fbs_profile_kernel(const fbs_ctx *ctx, int which) try {
 const char *fbs_kernel_catalog(void) try {
     static const std::string text = [] {
         std::vector<std::string> names;
-        keyswitch_catalog(&names);
-        blind_rotate_catalog(&names);
+        kernel_catalog(&names);
         std::string t;
         for (const std::string &n : names) t += n + "\n";
         return t;

@@ -143,6 +143,7 @@ int host_ctx_init(fbs_ctx *ctx, const fbs_params *params, uint64_t seed, const u
     ctx->n_ggsw = ctx->group == 2 ? (size_t)p.n / 2 * 3 : p.n;
     ctx->ksk_stride = ((p.n + 1 + 255) / 256) * 256;
     ctx->delta_half = (uint64_t)(((unsigned __int128)FQ + 2ull * p.p_msg) / (4ull * p.p_msg));
+    if (const char *why = params_out_of_range(p, ctx->D)) return set_error(ctx, FBS_E_INVALID, why);   // (before the shifts below)
     auto round_div = [](uint32_t e) {
         unsigned __int128 d = (unsigned __int128)1 << e;
         return (uint64_t)(((unsigned __int128)FQ + d / 2) / d);

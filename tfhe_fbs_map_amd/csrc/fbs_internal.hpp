@@ -13,6 +13,7 @@
 
 #include "../../include/fbs_exec.h"
 #include "fbs_field.hpp"
+#include "fbs_select.hpp"
 
 namespace fbs {
 
@@ -32,17 +33,12 @@ RandKey rand_key_derive(const uint8_t seed[32], const fbs_params &p);
 void rand_words(const RandKey &key, uint64_t stream, uint64_t idx0, uint64_t *dst, size_t count);
 int64_t noise_sample(const RandKey &key, uint64_t stream, uint64_t idx, uint64_t sigma);
 
-// launcher knobs (fbs_ctx_tune): which kernel shape a launch takes.  Defaults are the measured choices; tests use them to reach
-// every launcher branch in one process, tools/ to measure one against another.
+// launcher knobs (fbs_ctx_tune): which kernel shape a launch takes (fbs_select.cpp).  Defaults are the measured choices; tests
+// use them to reach every instantiation at small sizes.
 struct Tune {
-    int64_t ks_gemm_min = 1;        // key switches per launch from which the int8 GEMM on the matrix cores is used
     int64_t ks_mfma = 1;            // 0: never the GEMM
     int64_t ks_fp = 1;              // 0: integer kernels instead of the FP64 one (fallback path)
-    int64_t ks_cols_major = 1;      // 0: round-1 grid order of the vector key-switch kernels
-    int64_t ks_split = 0;           // > 0: k slices of the GEMM
-    int64_t br_whole_cu = 1;        // 0: no whole-CU workgroups (four bootstraps per workgroup) in the blind rotation
     int64_t br_cu_kernel = 1;       // 0: no one-bootstrap-per-CU kernel (the generic kernel on the four-wave transform instead)
-    int64_t br_cu_max_per_cu = 2;   // bootstraps per CU up to which a launch takes the one-bootstrap-per-CU kernel
     int64_t br_cu_lean = 1;         // 1: between one and two per CU, its 128-register variant (two workgroups per CU); 2: always; 0: never
     int64_t br_k2_shape = 0;        // k = 2: 0 by launch size; 3 always three waves per bootstrap; 12 always the twelve-wave latency shape
     int64_t br_glwe_fpw = 0;        // k_blind_rotate_glwe: bootstraps per workgroup -- 0 by launch size; 1, 2; anything larger = the throughput shape
@@ -122,7 +118,7 @@ struct fbs_ctx {
     std::vector<uint64_t> sk_lwe, sk_glwe, bsk, ksk;   // host copies, standard layout
 
     uint64_t *d_bsk_hat = nullptr;   // [n][rows][k+1][N]  NTT domain, lane-interleaved, x N^-1
-    uint64_t *d_bsk_hat_small = nullptr;   // the same in the evaluation order of the small-launch shape (fbs_ntt.hpp), or null
+    uint64_t *d_bsk_hat_small = nullptr;   // the same in the evaluation order of the small-launch shape (fbs_ntt.hpp), where small_key_needed
     uint64_t *d_ksk = nullptr;       // [D*t][ksk_stride]
     uint64_t *d_ksk_f = nullptr;     // the same key as centred doubles (bit patterns), for the FP64 key-switch kernel
     int8_t *d_ks_b = nullptr;        // the key as balanced base-256 limbs in MFMA fragment order (k_ks_gemm, fbs_kernels.hip)
@@ -229,8 +225,6 @@ int host_build_tv_diff(const fbs_ctx *ctx, const int32_t *table, uint32_t len, u
 void host_twiddles(uint32_t log_n, std::vector<uint64_t> &fwd, std::vector<uint64_t> &inv);
 
 // device side (fbs_kernels.hip); all asynchronous on `stream`
-int dev_supported(const fbs_ctx *ctx);   // FBS_OK or error if no kernel instance for the params
-bool glwe_shape_built(uint32_t log_n, uint32_t k);   // fbs_blind_rotate_glwe.hip: is there a kernel for GLWE dimension k >= 2 at N = 2^log_n?
 int dev_upload_keys(fbs_ctx *ctx);       // BSK -> NTT domain, KSK padded
 int dev_keyswitch_gemm_setup(fbs_ctx *ctx);   // limb fragments of the key-switching key for the int8 MFMA key switch
 int dev_keyswitch(fbs_ctx *ctx, const GateView &gv, uint32_t *d_ms, hipStream_t stream);
@@ -253,9 +247,6 @@ int dev_copy_out(fbs_ctx *ctx, const uint64_t *d_wires, size_t T, size_t s_begin
 int dev_multi_extract(fbs_ctx *ctx, const fbs_tvset *tv, const uint64_t *d_acc_rows, uint64_t *d_wires, size_t T, size_t s_begin,
                       size_t s_count, uint32_t n_extract, const uint32_t *d_x_row, const uint32_t *d_x_table,
                       const uint32_t *d_x_dst, hipStream_t stream);
-// names of every kernel instantiation the launchers can pick (fbs_kernel_catalog)
-void blind_rotate_catalog(std::vector<std::string> *out);
-void keyswitch_catalog(std::vector<std::string> *out);
 int dev_polymul(fbs_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_c, hipStream_t stream);
 
 // profiling helpers

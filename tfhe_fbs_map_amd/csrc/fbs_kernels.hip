@@ -44,7 +44,7 @@ struct KsArgs {
     uint64_t *body_raw;        // [count]
     uint32_t offs;         // B/2 at every digit position
     uint32_t n, D, t, gamma, stride, ct_words, log2_2n;
-    uint32_t cols_major;   // 1: blockIdx.x walks the column blocks (see dev_keyswitch), 0: the ciphertext tiles
+    uint32_t cols_major;   // 1: blockIdx.x walks the column blocks (what launch_keyswitch sets), 0: the ciphertext tiles
     size_t row0;           // first key switch of this launch (launches are split when a grid dimension would overflow)
     size_t count;          // key switches in all (gv.ks_count)
 };
@@ -647,29 +647,6 @@ void prof_end(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t e0, hipEvent_t 
     ctx->prof.pending[which].push_back({e0, e1, ctx->prof.kernel[which]});
 }
 
-int dev_supported(const fbs_ctx *ctx) {
-    const fbs_params &p = ctx->p;
-    if (p.k >= 2 && !glwe_shape_built(p.log_n_poly, p.k))
-        return set_error(ctx, FBS_E_INVALID, "GLWE dimensions k >= 2 are built for k = 2, 3, 4 at N = 256 and 512 and k = 2, 3 at N = 1024");
-    if (p.k < 1) return set_error(ctx, FBS_E_INVALID, "need k >= 1");
-    if (p.log_n_poly < 8 || p.log_n_poly > 12)
-        return set_error(ctx, FBS_E_INVALID, "supported polynomial sizes are N = 256, 512, 1024, 2048, 4096");
-    if (p.l_bsk < 1 || p.beta_bsk < 1 || p.l_bsk * p.beta_bsk > 30 || p.l_bsk * p.beta_bsk > FQ_BITS - 2)
-        return set_error(ctx, FBS_E_INVALID, "need 1 <= l*beta <= 30");
-    if (p.t_ksk < 1 || p.gamma_ksk < 1 || p.t_ksk * p.gamma_ksk > 31 || p.t_ksk * p.gamma_ksk > FQ_BITS - 2)
-        return set_error(ctx, FBS_E_INVALID, "need 1 <= t*gamma <= 31");
-    if (p.n < 1 || p.n > 4096) return set_error(ctx, FBS_E_INVALID, "need 1 <= n <= 4096");
-    if (p.bsk_group == 2 && p.k == 1 && (p.log_n_poly < 10 || p.l_bsk > 5))
-        return set_error(ctx, FBS_E_INVALID, "two key bits per step (bsk_group = 2) at k = 1 is built for N = 1024, 2048 and 4096, l <= 5");
-    // lazy FP64 ranges (fbs_field.hpp): partial external products stay below 2^50 while (k+1)*l <= 20
-    if ((p.k + 1) * p.l_bsk > 20) return set_error(ctx, FBS_E_INVALID, "need (k+1)*l <= 20");
-    // 64-bit key-switch accumulators: D*t digits < 2^gamma times words < 2^46
-    double bits = FQ_BITS + p.gamma_ksk + std::log2((double)p.t_ksk * ctx->D);
-    if (bits > 63.9 || bits - 32.0 > 31.9)   // whole sum in 64 bits; the high-word partial sums in 32
-        return set_error(ctx, FBS_E_INVALID, "key-switch accumulator would overflow");
-    return FBS_OK;
-}
-
 static KsGemm gemm_shape(const fbs_ctx *ctx) {
     KsGemm g{};
     g.D = ctx->D;
@@ -699,13 +676,8 @@ int dev_keyswitch_gemm_setup(fbs_ctx *ctx) {
 // digits -> GEMM -> recombination + modulus switch, in passes of at most 8192 ciphertexts (the scratch stays bounded)
 constexpr size_t KS_GEMM_PASS = 8192;
 
-static bool keyswitch_gemm_exact(const fbs_ctx *ctx) {
-    // int8 GEMM on the matrix cores: exact while 2^(gamma-1) * 2^7 * kN t stays below 2^31
-    return ctx->d_ks_b && std::ldexp((double)ctx->D * ctx->p.t_ksk, (int)ctx->p.gamma_ksk + 6) < 2147483648.0;
-}
-
 int dev_keyswitch_reserve(fbs_ctx *ctx, size_t count) {
-    if (!keyswitch_gemm_exact(ctx)) return FBS_OK;
+    if (!ctx->d_ks_b || !ks_gemm_exact(ctx)) return FBS_OK;
     const KsGemm g = gemm_shape(ctx);
     const size_t want = std::min<size_t>(KS_GEMM_PASS, (count + 127) / 128 * 128);
     if (ctx->ks_rows_capacity >= want) return FBS_OK;
@@ -735,7 +707,6 @@ static int keyswitch_gemm(fbs_ctx *ctx, KsArgs &a, hipStream_t stream) {
     constexpr size_t PASS = KS_GEMM_PASS;
     const uint32_t ldc = 6 * g.cols_pad;
     if (int rc = dev_keyswitch_reserve(ctx, a.count)) return rc;   // (a no-op after ensure_ms / fbs_ctx_reserve)
-    ctx->prof.kernel[0] = "k_ks_gemm<2,2> (int8 MFMA)";
     for (size_t f0 = 0; f0 < a.count; f0 += PASS) {
         const size_t rows = std::min(PASS, a.count - f0);
         const unsigned m_blocks = (unsigned)((rows + 127) / 128), n_blocks = ldc / 128;
@@ -743,8 +714,7 @@ static int keyswitch_gemm(fbs_ctx *ctx, KsArgs &a, hipStream_t stream) {
         // enough workgroups to keep every CU busy: the k range is cut where the (m, n) grid alone is too small.  (2 x 4 tiles
         // per wave halve the fragment traffic but leave one wave per SIMD: 186 against 135 us at N = 2048, t = 7.)
         const unsigned want_split = (2u * (unsigned)ctx->cu_count + m_blocks * n_blocks - 1) / (m_blocks * n_blocks);
-        unsigned split = std::max(1u, std::min({want_split, 16u, g.ksteps / 16u}));
-        if (ctx->tune.ks_split > 0) split = (unsigned)ctx->tune.ks_split;   // (tuning)
+        const unsigned split = std::max(1u, std::min({want_split, 16u, g.ksteps / 16u}));
         const uint32_t klen = (g.ksteps + split - 1) / split;
         hipLaunchKernelGGL((k_ks_gemm<2, 2>), dim3(n_blocks, m_blocks, (g.ksteps + klen - 1) / klen), dim3(256), 0, stream,
                            reinterpret_cast<const v4i *>(ctx->d_ks_a), reinterpret_cast<const v4i *>(ctx->d_ks_b), ctx->d_ks_c, g.ksteps, klen,
@@ -755,9 +725,60 @@ static int keyswitch_gemm(fbs_ctx *ctx, KsArgs &a, hipStream_t stream) {
     return FBS_OK;
 }
 
-void keyswitch_catalog(std::vector<std::string> *out) {
-    for (const char *k : {"k_ks_gemm<2,2> (int8 MFMA)", "k_keyswitch_fp<8,2,8>", "k_keyswitch_lanes<8,2,8>", "k_keyswitch_lanes<8,1,4>", "k_keyswitch<8>"})
-        out->push_back(k);
+// the instantiation of a key-switch descriptor (fbs_select.hpp)
+static int launch_keyswitch(fbs_ctx *ctx, const Kernel &k, KsArgs &a, hipStream_t stream) {
+    const fbs_params &p = ctx->p;
+    // Workgroups are dealt to the 8 XCDs round-robin by linear id.  With the column blocks on grid.x, padded to a multiple of 16
+    // and dealt in adjacent pairs, XCD x only ever sees column blocks 2x, 2x+1 (mod 16): each key line is fetched by ONE XCD's L2
+    // instead of all eight (the 50 MB key does not fit any L2), and what every XCD re-reads is the 8 times smaller ciphertext batch.
+    constexpr int COLS = 8;
+    const unsigned cols_padded = ((p.n + 1 + COLS - 1) / COLS + 15u) / 16u * 16u;
+    const size_t tiles = (a.count + 127) / 128;   // (the 128-ciphertext tiles sit on grid.y)
+    switch (k.family) {
+    case Family::KS_GEMM:
+        return keyswitch_gemm(ctx, a, stream);
+    case Family::KS_FP: {   // (8, 2, 8)
+        a.cols_major = 1u;
+        // FP64 form: as many mask words per exact fold as the doubles' room allows
+        const double per_word = (double)p.t_ksk * std::ldexp(1.0, 44 + (int)p.gamma_ksk);
+        const double room = std::ldexp(1.0, 53) - std::ldexp(1.0, 45);
+        const uint32_t words_per_fold = (uint32_t)std::min(1024.0, std::floor(room / per_word));
+        for (size_t t0 = 0; t0 < tiles; t0 += 65535) {
+            a.row0 = t0 * 128;
+            // measured per 1024-batch: 8 columns x 128 ciphertexts x 8 waves 0.48 ms; 16 columns 0.77 (8 waves) / 0.67 (4 waves);
+            // 8 columns x 4 waves 0.60; 256 ciphertexts 0.57
+            hipLaunchKernelGGL((k_keyswitch_fp<COLS, 2, 8>), dim3(cols_padded, (unsigned)std::min<size_t>(65535, tiles - t0)), dim3(512),
+                               0, stream, a, reinterpret_cast<const double *>(ctx->d_ksk_f), words_per_fold);
+        }
+        return FBS_OK;
+    }
+    case Family::KS_LANES:
+        // measured per 1024-batch: 64 ciphertexts x 4 waves 0.91 ms, 128 x 4 waves 0.81, 64 x 8 waves 1.10, 128 x 8 waves 0.65,
+        // 256 x 8 waves 1.32, 128 x 16 waves 0.86, 256 x 16 waves 1.80
+        a.cols_major = 1u;
+        if (k.t[1] == 2 && k.t[2] == 8) {
+            for (size_t t0 = 0; t0 < tiles; t0 += 65535) {
+                a.row0 = t0 * 128;
+                hipLaunchKernelGGL((k_keyswitch_lanes<COLS, 2, 8>), dim3(cols_padded, (unsigned)std::min<size_t>(65535, tiles - t0)),
+                                   dim3(512), 0, stream, a);
+            }
+            return FBS_OK;
+        }
+        if (k.t[1] == 1 && k.t[2] == 4) {   // (at most 64 ciphertexts)
+            hipLaunchKernelGGL((k_keyswitch_lanes<COLS, 1, 4>), dim3(cols_padded, 1), dim3(256), 0, stream, a);
+            return FBS_OK;
+        }
+        break;
+    case Family::KS_INT: {
+        constexpr int FB = 8;
+        dim3 grid((unsigned)((a.count + FB - 1) / FB), ctx->ksk_stride / 256);
+        size_t shmem = (size_t)FB * ctx->D * sizeof(uint32_t);
+        hipLaunchKernelGGL(k_keyswitch<FB>, grid, dim3(256), shmem, stream, a);
+        return FBS_OK;
+    }
+    default: break;
+    }
+    return set_error(ctx, FBS_E_INVALID, "no instantiation of " + kernel_name(k));
 }
 
 int dev_keyswitch(fbs_ctx *ctx, const GateView &gv, uint32_t *d_ms, hipStream_t stream) {
@@ -778,71 +799,20 @@ int dev_keyswitch(fbs_ctx *ctx, const GateView &gv, uint32_t *d_ms, hipStream_t 
     a.ct_words = ctx->D + 1;
     a.log2_2n = p.log_n_poly + 1;
     a.count = gv.ks_count;
-    if (a.count == 0) return FBS_OK;
-    hipEvent_t e0, e1;
-    prof_begin(ctx, 0, stream, &e0, &e1);
-    // The int8 GEMM on the matrix cores serves every batch size (round 2 used it above 64 ciphertexts only; below, the integer
-    // kernels took 0.54 ms for 32-64 ciphertexts and 2.7 ms for 1-16, the GEMM takes 0.04-0.06 ms: its cost is streaming the
-    // key's 31 MB of limb fragments, whatever the number of rows).
-    const size_t gemm_min = (size_t)ctx->tune.ks_gemm_min;
-    const bool gemm_ok = ctx->tune.ks_mfma && keyswitch_gemm_exact(ctx);
-    if (a.count >= gemm_min && gemm_ok) {
-        const int rc = keyswitch_gemm(ctx, a, stream);
-        if (rc != FBS_OK) return rc;
-    } else if (a.count >= 32) {
-        // lanes = ciphertexts: pays once a wave is at least half full
-        constexpr int COLS = 8;
-        // measured per 1024-batch: 64 ciphertexts x 4 waves 0.91 ms, 128 x 4 waves 0.81, 64 x 8 waves 1.10, 128 x 8 waves 0.65,
-        // 256 x 8 waves 1.32, 128 x 16 waves 0.86, 256 x 16 waves 1.80
-        // Workgroups are dealt to the 8 XCDs round-robin by linear id.  With the column blocks on grid.x, padded to a
-        // multiple of 16 and dealt in adjacent pairs, XCD x only ever sees column blocks 2x, 2x+1 (mod 16): each key line is fetched by ONE XCD's L2
-        // instead of all eight (the 50 MB key does not fit any L2), and what every XCD re-reads is the 8 times
-        // smaller ciphertext batch.
-        const bool cols_major = ctx->tune.ks_cols_major != 0;
-        a.cols_major = cols_major ? 1u : 0u;
-        const unsigned cols = (p.n + 1 + COLS - 1) / COLS;
-        const unsigned cols_padded = cols_major ? (cols + 15u) / 16u * 16u : cols;
-        // FP64 form: needs the centred-double copy of the key and room to accumulate at least one mask word exactly
-        const double per_word = (double)p.t_ksk * std::ldexp(1.0, 44 + (int)p.gamma_ksk);
-        const double room = std::ldexp(1.0, 53) - std::ldexp(1.0, 45);
-        const bool allow_fp = ctx->tune.ks_fp != 0;
-        if (a.count > 64 && cols_major && allow_fp && ctx->d_ksk_f && per_word <= room) {
-            const uint32_t words_per_fold = (uint32_t)std::min(1024.0, std::floor(room / per_word));
-            const size_t tiles = (a.count + 127) / 128;
-            for (size_t t0 = 0; t0 < tiles; t0 += 65535) {
-                const unsigned nt = (unsigned)std::min<size_t>(65535, tiles - t0);
-                a.row0 = t0 * 128;
-                // measured per 1024-batch: 8 columns x 128 ciphertexts x 8 waves 0.48 ms; 16 columns 0.77 (8 waves) / 0.67 (4 waves);
-                // 8 columns x 4 waves 0.60; 256 ciphertexts 0.57
-                ctx->prof.kernel[0] = "k_keyswitch_fp<8,2,8>";
-                hipLaunchKernelGGL((k_keyswitch_fp<COLS, 2, 8>), dim3(cols_padded, nt), dim3(512), 0, stream, a,
-                                   reinterpret_cast<const double *>(ctx->d_ksk_f), words_per_fold);
-            }
-        } else if (a.count > 64) {
-            const size_t tiles = (a.count + 127) / 128;
-            const size_t per_launch = cols_major ? 65535 : 0x7FFFFFFF;     // tiles sit on grid.y in the column-major form
-            for (size_t t0 = 0; t0 < tiles; t0 += per_launch) {
-                const unsigned nt = (unsigned)std::min(per_launch, tiles - t0);
-                a.row0 = t0 * 128;
-                ctx->prof.kernel[0] = "k_keyswitch_lanes<8,2,8>";
-                hipLaunchKernelGGL((k_keyswitch_lanes<COLS, 2, 8>), cols_major ? dim3(cols_padded, nt) : dim3(nt, cols), dim3(512), 0,
-                                   stream, a);
-            }
-        } else {
-            ctx->prof.kernel[0] = "k_keyswitch_lanes<8,1,4>";
-            hipLaunchKernelGGL((k_keyswitch_lanes<COLS, 1, 4>), cols_major ? dim3(cols_padded, 1) : dim3(1, cols), dim3(256), 0, stream, a);
+    // (one launch: select_keyswitch never cuts a key switch; the modulus switch of the bodies follows it)
+    for (const Launch &l : select_keyswitch(ctx, a.count)) {
+        ctx->prof.kernel[0] = kernel_name(l.kernel);
+        hipEvent_t e0, e1;
+        prof_begin(ctx, 0, stream, &e0, &e1);
+        if (int rc = launch_keyswitch(ctx, l.kernel, a, stream)) {
+            if (e0) ctx->prof.pool.push_back({e0, e1});
+            return rc;
         }
-    } else {
-        constexpr int FB = 8;
-        dim3 grid((unsigned)((a.count + FB - 1) / FB), ctx->ksk_stride / 256);
-        size_t shmem = (size_t)FB * ctx->D * sizeof(uint32_t);
-        ctx->prof.kernel[0] = "k_keyswitch<8>";
-        hipLaunchKernelGGL(k_keyswitch<FB>, grid, dim3(256), shmem, stream, a);
+        hipLaunchKernelGGL(k_ms_body, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0, stream, d_ms, a.eps, a.body_raw, p.n,
+                           a.log2_2n, a.count);
+        prof_end(ctx, 0, stream, e0, e1);
+        FBS_HIP(ctx, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_ms_body, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0, stream, d_ms, a.eps, a.body_raw, p.n,
-                       a.log2_2n, a.count);
-    prof_end(ctx, 0, stream, e0, e1);
-    FBS_HIP(ctx, hipGetLastError());
     return FBS_OK;
 }
 

@@ -153,8 +153,8 @@ def bootstrap_cost(prm: Params) -> float:
     return 0.988 * pairs * blind(n, l, N, prm.log_n_poly) / blind(630, 3, 1024, 10, 1) + 0.012 * (k * N * t * (n + 1)) / (1024 * 8 * 631.0)
 
 
-def glwe_shape_built(k: int, log_n: int) -> bool:
-    """Is there a blind-rotation kernel for GLWE dimension k >= 2 at N = 2^log_n (csrc/fbs_blind_rotate_glwe.hip: FBS_GLWE_SHAPES)?"""
+def glwe_shape_built(log_n: int, k: int) -> bool:
+    """Is there a blind-rotation kernel for GLWE dimension k >= 2 at N = 2^log_n (csrc/fbs_select.hpp: FBS_GLWE_SHAPES)?"""
     return (k in (2, 3, 4) and log_n in (8, 9)) or (k in (2, 3) and log_n == 10)
 
 
@@ -229,7 +229,7 @@ def choose_params(p: int, norm2: float = 1.0, min_margin: float = 6.0, security:
     need = (1.0 / (4.0 * p) / min_margin) ** 2              # largest admissible variance
     best = None
     for k, log_n in [(k_, ln) for k_ in glwe_dims for ln in poly_sizes]:
-        if k >= 2 and not glwe_shape_built(k, log_n):
+        if k >= 2 and not glwe_shape_built(log_n, k):
             continue                                        # no kernel for this (k, N)
         N = 1 << log_n
         s_glwe = (sigma_min(k * N, security) if security is not None else (sigma if sigma is not None else REDUCED_SIGMA)) / q

@@ -1,5 +1,5 @@
 #!/bin/bash
-# fabric traffic of the key-switch kernel (FETCH_SIZE / WRITE_SIZE, separate passes) for the grid order in $FBS_KS_TILES_MAJOR
+# fabric traffic of the key-switch and blind-rotation kernels (FETCH_SIZE / WRITE_SIZE, separate passes); $1 names the output
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/pmc_ks_${1:-default}
 rm -rf $OUT && mkdir -p $OUT
