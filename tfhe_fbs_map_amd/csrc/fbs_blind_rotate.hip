@@ -62,10 +62,11 @@ __global__ __launch_bounds__(1 << LL) void k_polymul(const uint64_t *a, const ui
 // ---------------------------------------------------------------------------------------------
 // DIG: what the launcher knows about the gadget --
 //   0  nothing;
-//   1  l <= 5: the 2l lazy products (each below 0.8 q) that enter the inverse transform stay below 8 q (its first centring
-//      pass is spared);
+//   1  l <= 5: the 2l lazy products (each below 0.8 q; below 1.2 q after the fused opening of 3) that enter the inverse
+//      transform stay below 16 q (its first centring pass is spared);
 //   2  also beta <= 9: a balanced digit (|d| <= 2^8) times a twiddle (|w| <= 2^45) is exact in a double;
-//   3  also beta <= 7: the first butterfly stage of the forward transforms is two exact FMAs (first_butterfly, fbs_ntt.hpp)
+//   3  also beta <= 7: the first butterfly stage of the forward transforms is two exact FMAs (first_butterfly, fbs_ntt.hpp);
+//      where a wave holds a whole polynomial (SplitNtt) the first TWO stages are exact three-term sums (first_two_stages)
 //   4  l = 1 (one wide digit, any beta: the shape the 128-bit parameter sets take at N = 2048): as 1, without the loop
 //      over further levels -- and without the registers the compiler keeps alive for it
 //   5, 6, 7  l = 2 (the 128-bit sets for p <= 4 at N = 1024 and for p = 31, 63): as 1, 2, 3 with the two levels written out
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(1 << LL) void k_polymul(const uint64_t *a, const ui
 template <int LOGN, int LL, int DIG, int FPW, bool TURNS = true>
 __global__ __launch_bounds__((2 << LL) * FPW) __attribute__((amdgpu_waves_per_eu(2))) void k_blind_rotate(BrArgs a) {
     using W = typename NttFor<LOGN, LL>::type;
-    constexpr int FIRST = (DIG == 3 || DIG == 7) ? 2 : (DIG == 2 || DIG == 6) ? 1 : 0;
+    constexpr int FIRST = (DIG == 3 || DIG == 7) ? (has_fused_opening<W>::value ? 3 : 2) : (DIG == 2 || DIG == 6) ? 1 : 0;
     constexpr bool BOUNDED = DIG >= 1;
     constexpr bool ONE_LEVEL = DIG == 4, TWO_LEVELS = DIG >= 5;
 #ifndef FBS_PEEL_MAX_LL
@@ -164,13 +165,12 @@ __global__ __launch_bounds__((2 << LL) * FPW) __attribute__((amdgpu_waves_per_eu
         lead_if<PRIO>(PRIO == 7 ? 2u * i : i, slot);
         const uint32_t r = __builtin_amdgcn_readfirstlane(r_next);
         r_next = ms[i + 1];     // ms has n+1 entries; the last one (the body) is read here and ignored
-        if (r == 0) {           // X^0 * ACC - ACC = 0: nothing to add (uniform over the two waves of a bootstrap)
-            if constexpr (FPW > 1) {   // the other bootstrap of the workgroup still meets its two barriers of this step
-                __syncthreads();
-                __syncthreads();
-            }
-            continue;
-        }
+        // X^0 * ACC - ACC = 0: nothing to add (uniform over the two waves of a bootstrap).  Workgroups of several bootstraps run
+        // such a step through instead: its digits are all zero, so is every product, and ACC comes out of fp_center unchanged.
+        // A skip that still met the other bootstraps' two barriers was a second path into the loop latch, and the compiler
+        // carried ACC across it in a second set of registers: 16 v_mov_b64 on every step (one step in 2N takes r = 0).
+        if constexpr (FPW == 1)
+            if (r == 0) continue;
 
         // ---- (X^r - 1) * ACC_c, centred, rounded to the closest multiple of q / B^l ---------------
         uint32_t digits[E];
@@ -586,16 +586,17 @@ int dev_upload_keys(fbs_ctx *ctx) {
     const uint32_t N = ctx->N;
     std::vector<uint64_t> fwd, inv;
     host_twiddles(p.log_n_poly, fwd, inv);
-    std::vector<double> fwd_c(3 * (size_t)N), inv_c(3 * (size_t)N);   // the table, its two half-size and four quarter-size subtrees
-    for (uint32_t i = 0; i < 3 * N; i++) {
+    // the table, its two half-size and four quarter-size subtrees, the fused opening's two products (tw_table_words)
+    std::vector<double> fwd_c(tw_table_words(N)), inv_c(tw_table_words(N));
+    for (uint32_t i = 0; i < tw_table_words(N); i++) {
         fwd_c[i] = fq_centered(fwd[i]);
         inv_c[i] = fq_centered(inv[i]);
     }
     const size_t bsk_words = ctx->n_ggsw * ctx->rows * (p.k + 1) * N;
     const size_t ksk_rows = (size_t)ctx->D * p.t_ksk;
     if (!ctx->d_tw_fwd) {
-        FBS_HIP(ctx, hipMalloc(&ctx->d_tw_fwd, 3 * (size_t)N * 8));
-        FBS_HIP(ctx, hipMalloc(&ctx->d_tw_inv, 3 * (size_t)N * 8));
+        FBS_HIP(ctx, hipMalloc(&ctx->d_tw_fwd, (size_t)tw_table_words(N) * 8));
+        FBS_HIP(ctx, hipMalloc(&ctx->d_tw_inv, (size_t)tw_table_words(N) * 8));
         FBS_HIP(ctx, hipMalloc(&ctx->d_bsk_hat, bsk_words * 8));
         FBS_HIP(ctx, hipMalloc(&ctx->d_ksk, ksk_rows * ctx->ksk_stride * 8));
         FBS_HIP(ctx, hipMalloc(&ctx->d_ksk_f, ksk_rows * ctx->ksk_stride * 8));

@@ -60,6 +60,12 @@ inline uint64_t fq_inv(uint64_t a) { return fq_pow(a, FQ - 2); }
 // centred representative in (-q/2, q/2] as a double (how twiddles and key polynomials are stored for the kernels)
 inline double fq_centered(uint64_t a) { return a > FQ / 2 ? -(double)(FQ - a) : (double)a; }
 
+// Layout of an uploaded twiddle table of size N (host_twiddles, fbs_host.cpp): [N: the whole tree][N: its two half-size
+// subtrees][N: its four quarter-size subtrees], then the two products tw[1] tw[2], tw[1] tw[3] (mod q) that the fused first two
+// stages of a whole-polynomial forward transform take (SplitNtt::first_two_stages, fbs_ntt_split.hpp)
+constexpr uint32_t tw_fused_word(uint32_t n) { return 3 * n; }
+constexpr uint32_t tw_table_words(uint32_t n) { return 3 * n + 2; }
+
 // ---- device-side exact FP64 arithmetic ---------------------------------------------------------------------
 #if defined(__HIPCC__)
 constexpr double FP_Q = 70368743669761.0;            // q, exactly representable
@@ -70,6 +76,14 @@ constexpr double FP_MAGIC = 4503599627370496.0;      // 2^52: x + 2^52 exposes t
 // Up to |x| < 2^52 the result is still the exact residue (h - qh*q is an integer below 2^47, so the FMA cannot round;
 // l is the exact low part by construction); only the quotient estimate loosens (error <= |qh| * 2^-52 < 0.3), so the
 // result lies in (-0.8q, 0.8q).
+// Up to |x| < 2^53 (integer x, |w| <= (q-1)/2), still exact, below 1.24 q:
+//   h = fl(x w) is an integer (|x w| >= 2^53 rounds to a multiple of ulp >= 2), |h| < 2^98, so |l| = |x w - h| <= ulp(h)/2
+//   <= 2^44 < 0.2501 q and l is exact (the FMA's remainder of a product of integers);
+//   |h / q| < 2^52: fl(h * QINV) differs from h / q by at most |h / q| * |QINV q - 1| (QINV q - 1 = -2^-54.09 for this q:
+//   < 0.235) plus half an ulp (<= 0.25), and rint adds at most 0.5: |h / q - qh| < 0.985;
+//   so h - qh q is an integer below 0.985 q < 2^47 (the FMA that forms it cannot round), r = h - qh q + l below 1.236 q
+//   (the add cannot round either), and r = x w - qh q exactly.
+// tests/test_fused_opening.py checks these bounds (worst cases) and replays the transforms that rely on them.
 FBS_D double fp_mulmod(double x, double w) {
     const double h = x * w;
     const double l = __builtin_fma(x, w, -h);

@@ -336,6 +336,8 @@ int host_build_tv_diff(const fbs_ctx *ctx, const int32_t *table, uint32_t len, u
 // Entries [N, 2N) repeat the two half-size subtrees (nodes 2 and 3 of the twiddle tree) as tables of their own, N/2
 // entries each: entry i of half h = entry ((2 + h) << d) + (i - 2^d), d = floor(log2 i); entries [2N, 3N) the four
 // quarter-size subtrees (nodes 4 .. 7) likewise -- what the multi-wave transforms (WavesNtt, fbs_ntt_split.hpp) gather from.
+// Two more forward entries follow (tw_table_words, fbs_field.hpp): tw[1] tw[2] and tw[1] tw[3], for the fused opening of the
+// digit transforms (SplitNtt::first_two_stages).
 // ---------------------------------------------------------------------------------------------
 void host_twiddles(uint32_t log_n, std::vector<uint64_t> &fwd, std::vector<uint64_t> &inv) {
     const uint32_t N = 1u << log_n;
@@ -359,6 +361,10 @@ void host_twiddles(uint32_t log_n, std::vector<uint64_t> &fwd, std::vector<uint6
                 fwd[base + h * (N / parts) + i] = fwd[big];
                 inv[base + h * (N / parts) + i] = inv[big];
             }
+    fwd.resize(tw_table_words(N), 1);   // the fused opening's products (tw_fused_word); the inverse table keeps the same size
+    inv.resize(tw_table_words(N), 1);
+    fwd[tw_fused_word(N)] = fq_mul(fwd[1], fwd[2]);
+    fwd[tw_fused_word(N) + 1] = fq_mul(fwd[1], fwd[3]);
 }
 
 }  // namespace fbs

@@ -126,8 +126,8 @@ struct fbs_ctx {
     int *d_ks_c = nullptr;           // scratch: limb sums [rows][6][cols_pad], zero between launches
     size_t ks_rows_capacity = 0;
     uint64_t *d_ks_corr = nullptr;   // [ksk_stride]  (B/2) * sum of all key-switching-key rows: balanced digits from unsigned fields
-    uint64_t *d_tw_fwd = nullptr;    // [N]  psi^bitrev(i)
-    uint64_t *d_tw_inv = nullptr;    // [N]  psi^-bitrev(i)
+    uint64_t *d_tw_fwd = nullptr;    // [tw_table_words(N)]  psi^bitrev(i), centred doubles (layout: fbs_field.hpp)
+    uint64_t *d_tw_inv = nullptr;    // [tw_table_words(N)]  psi^-bitrev(i)
     uint64_t *d_psi_pow = nullptr;    // [N] psi^x, centred doubles: what the transforms of the monomials X^e - 1 are made from (group 2)
     uint32_t *d_ms = nullptr;        // scratch: mod-switched small ciphertexts [capacity][n+1]
     size_t ms_capacity = 0;

@@ -46,9 +46,11 @@ struct Twiddles {
 //              UNREDUCED -- 2 instructions.  Every later butterfly reduces only the operand it multiplies, so all values of
 //              the transform then sit near 2^51 and grow by less than 0.8 q a stage: below 2^51.2 after eleven stages,
 //              inside the 2^52 that fp_mulmod (butterflies and key products alike) accepts, and every sum exact.
+//   FIRST = 3  as 2, with the first TWO stages fused into exact three-term sums (SplitNtt::first_two_stages, fbs_ntt_split.hpp;
+//              whole polynomials on one wave only, has_fused_opening); a single butterfly treats it as 2.
 template <int FIRST>
 __device__ __forceinline__ void first_butterfly(double &a, double &b, double w) {
-    if constexpr (FIRST == 2) {
+    if constexpr (FIRST >= 2) {
         const double u = a, d = b;
         a = __builtin_fma(d, w, u);
         b = __builtin_fma(-d, w, u);

@@ -107,11 +107,12 @@ struct SplitNtt {
             }
         }
     }
-    template <int G, int H>
+    // K0: the first stage of the group to run (1 where first_two_stages has done stage 0 of group 0)
+    template <int G, int H, int K0 = 0>
     __device__ static __forceinline__ void fwd_group(double (&x)[E], const GroupTw &g) {
         constexpr int lo = lo_of(G), OFF = H * EH;
 #pragma unroll
-        for (int k = 0; k < LOGEH; k++) {
+        for (int k = K0; k < LOGEH; k++) {
             const int bit = LOGM - 1 - (G * LOGEH + k) - lo, hm = 1 << bit;
 #pragma unroll
             for (int r = 0; r < EH; r++) {
@@ -123,9 +124,10 @@ struct SplitNtt {
             }
         }
     }
-    // CENTRE = false: the caller promises |x| <= 8 q on entry.  Three Gentleman-Sande stages then feed fp_mulmod at most
-    // 8 * 8 q = 2^52 * (q / 2^46) < 2^52, inside the bound under which it stays exact (fbs_field.hpp; its result is then
-    // below 0.8 q rather than 0.75 q), and leave sums below 64 q < 2^52, which the next group's centring accepts.
+    // CENTRE = false: the caller promises |x| < 16 q on entry.  Three Gentleman-Sande stages then feed fp_mulmod at most
+    // 8 * 16 q = 128 q < 2^53, inside the bound under which it stays exact (fbs_field.hpp; its result is then below 1.24 q),
+    // and leave sums below 128 q < 2^53, exact integers, which the next group's centring accepts (its quotient estimate is
+    // off by far less than 2^-40 there).
     template <int G, int H, bool CENTRE = true>
     __device__ static __forceinline__ void inv_group(double (&x)[E], const GroupTw &g) {
         constexpr int lo = lo_of(G), OFF = H * EH;
@@ -162,12 +164,43 @@ struct SplitNtt {
         __device__ __forceinline__ void operator()() const {}
     };
 
-    // FIRST: what is known about the inputs (first_butterfly, fbs_ntt.hpp)
+    // The first two Cooley-Tukey stages of a whole polynomial (R = 1) whose inputs are balanced digits, |d| <= 2^6 (FIRST = 3).
+    // Both stages pair registers of one lane under wave-uniform twiddles: stage 0 pairs m with m + 8 under w1 = tw[1], stage 1
+    // pairs m with m + 4 under w2 = tw[2] (registers 0..7) and w3 = tw[3] (8..15).  Per four registers (a, b, c, d) = (r, r + 4,
+    // r + 8, r + 12) the two stages compute
+    //     r      a + w1 c + w2 b + w1w2 d          r + 8    a - w1 c + w3 b - w1w3 d
+    //     r + 4  a + w1 c - w2 b - w1w2 d          r + 12   a - w1 c - w3 b + w1w3 d
+    // with w1w2, w1w3 the centred products mod q (tw_fused_word, fbs_field.hpp).  Every coefficient is at most (q-1)/2 and
+    // every digit at most 64, so every partial sum is an integer below 64 + 96 (q-1) < 96 q < 1.5 * 2^52: each FMA is exact and
+    // the results, left unreduced, are the same residues the two stages give (10 instructions per four registers, against 4 + 16).
+    // Ranges after this opening (worst cases, tests/test_fused_opening.py): each of the eight remaining stages adds a product
+    // below 1.2 q (fp_mulmod, fbs_field.hpp), so the transform ends below 105.5 q < 2^52.73 < 2^53, where fp_mulmod is still
+    // exact -- every later butterfly reduces only the operand it multiplies, so the sums are exact integers too.  The key
+    // products then stay below 1.2 q each.
+    __device__ static __forceinline__ void first_two_stages(double (&x)[E], const Twiddles &tw) {
+        const double w1 = tw.uniform[1], w2 = tw.uniform[2], w3 = tw.uniform[3];
+        const double w12 = tw.uniform[tw_fused_word(N)], w13 = tw.uniform[tw_fused_word(N) + 1];
+        constexpr int Q = EH / 2;
+#pragma unroll
+        for (int r = 0; r < Q; r++) {
+            const double a = x[r], b = x[r + Q], c = x[r + EH], d = x[r + EH + Q];
+            const double s = __builtin_fma(c, w1, a), u = __builtin_fma(-c, w1, a);
+            x[r] = __builtin_fma(d, w12, __builtin_fma(b, w2, s));
+            x[r + Q] = __builtin_fma(-d, w12, __builtin_fma(-b, w2, s));
+            x[r + EH] = __builtin_fma(-d, w13, __builtin_fma(b, w3, u));
+            x[r + EH + Q] = __builtin_fma(d, w13, __builtin_fma(-b, w3, u));
+        }
+    }
+
+    // FIRST: what is known about the inputs (first_butterfly, fbs_ntt.hpp); FIRST = 3 (first_two_stages) needs R = 1
     template <int FIRST, class Hook>
     __device__ static __forceinline__ void forward(double (&x)[E], Xchg &xc, uint32_t t, const Twiddles &tw, Hook &&before_last,
                                                    uint32_t R = 1) {
         double *half0 = xc.next(), *half1 = half0 + N / 2;
-        {
+        constexpr int K0 = FIRST == 3 ? 1 : 0;   // stage 0 of the halves' first group done by first_two_stages
+        if constexpr (FIRST == 3) {
+            first_two_stages(x, tw);
+        } else {
             const double w0 = tw.uniform[R];
 #pragma unroll
             for (int r = 0; r < EH; r++) first_butterfly<FIRST>(x[r], x[r + EH], w0);
@@ -176,11 +209,11 @@ struct SplitNtt {
         GroupTw ta, tb;
         load_twiddles<0, 0>(t, tw, ta, R);
         load_twiddles<0, 1>(t, tw, tb, R);
-        fwd_group<0, 0>(x, ta);
+        fwd_group<0, 0, K0>(x, ta);
         exchange<0, 1, 0>(x, half0, t);
         load_twiddles<1, 0>(t, tw, ta, R);
         pin();
-        fwd_group<0, 1>(x, tb);
+        fwd_group<0, 1, K0>(x, tb);
         exchange<0, 1, 1>(x, half1, t);
         load_twiddles<1, 1>(t, tw, tb, R);
         pin();
@@ -199,7 +232,7 @@ struct SplitNtt {
     __device__ static __forceinline__ void forward(double (&x)[E], Xchg &xc, uint32_t t, const Twiddles &tw) {
         forward<0>(x, xc, t, tw, NoHook{});
     }
-    // evaluations (|x| < 2^52; BOUNDED: |x| <= 8 q, which spares the first centring pass) -> N * coefficients (|x| <= 8 q)
+    // evaluations (|x| < 2^52; BOUNDED: |x| < 16 q, which spares the first centring pass) -> N * coefficients (|x| <= 8 q)
     // The wave-uniform twiddles of the inverse (last group of each half + the joining stage).  Scalar loads share the
     // LDS counter and return out of order, so whoever waits for one waits for everything in flight: a caller with slack
     // ahead of the transform (a barrier, say) requests them there with inverse_uniform() and passes them in.
@@ -413,6 +446,12 @@ struct WavesNtt {
 };
 template <int LOGN>
 using PairNtt = WavesNtt<LOGN, 1>;
+
+// transforms that take FIRST = 3 (SplitNtt::first_two_stages)
+template <class W>
+struct has_fused_opening : std::false_type {};
+template <int LOGN, int LL>
+struct has_fused_opening<SplitNtt<LOGN, LL>> : std::true_type {};
 
 // the transform used for a shape: the split schedule where a wave holds a whole polynomial at 16 coefficients per lane,
 // two or four wave-private split transforms behind one or two cross stages where two or four waves hold a larger one
