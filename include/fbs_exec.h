@@ -130,7 +130,9 @@ const char *fbs_device_info(const fbs_ctx *ctx);
 /* ---- keys ----------------------------------------------------------------
  * Secret keys stay on the host; the bootstrapping key (n GGSW samples) is
  * uploaded, transformed to the NTT domain on the GPU and kept resident, as is
- * the key-switching key. */
+ * the key-switching key.  The GLWE secret key (the big key ciphertexts are
+ * encrypted under) also lives in device memory, as packed bits, for the life
+ * of the context: the device encryption and decryption below read it. */
 int fbs_keygen(fbs_ctx *ctx);
 /* word counts of { sk_lwe, sk_glwe, bsk, ksk } in the standard (coefficient) layout:
  *   sk_lwe[n], sk_glwe[k][N] (bit c N + j = coefficient j of key polynomial S_c; read flat it is the key of the
@@ -167,6 +169,13 @@ int fbs_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t 
 int fbs_encrypt_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *cts, uint64_t *nonce0);
 /* msgs[i] = round(phase * 2p / q) mod 2p */
 int fbs_decrypt(const fbs_ctx *ctx, const uint64_t *cts, size_t count, int64_t *msgs);
+/* The same three on device buffers, asynchronous on `stream` (NULL = the context's own stream), word-identical to
+ * fbs_encrypt / fbs_encrypt_fresh / fbs_decrypt: the same streams, checks, error codes and nonce rules (a refused call writes
+ * nothing and leaves the stream counter where it was; count = 0 does nothing).  d_msgs [count] int64, d_cts [count][D+1].
+ * They use no per-context scratch. */
+int fbs_encrypt_dev(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_cts, void *stream);
+int fbs_encrypt_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t *d_cts, uint64_t *nonce0, void *stream);
+int fbs_decrypt_dev(const fbs_ctx *ctx, const uint64_t *d_cts, size_t count, int64_t *d_msgs, void *stream);
 
 /* ---- tables -> test vectors ----------------------------------------------
  * One entry per distinct `Bootstrap.table` (fbs_exec_env.py:51-61).  Table t is
@@ -255,6 +264,15 @@ int fbs_program_info(const fbs_prog *prog, uint32_t *n_levels, uint32_t *max_wid
 int fbs_eval(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *in_cts, size_t T, uint64_t *out_cts);
 /* the same on device-resident buffers, asynchronous on `stream` */
 int fbs_eval_dev(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *d_in, size_t T, uint64_t *d_out, void *stream);
+/* Messages in, messages out: fbs_eval with the inputs encrypted on the device straight into their wire slots and the output
+ * slots decrypted there, so only int64 messages cross the bus.  msgs: host [n_inputs][T]; out_msgs: host [n_outputs][T].
+ * Input i, sample s takes stream nonce0 + i*T + s (the order fbs_encrypt gives a [n_inputs][T] array).  fresh != 0:
+ * n_inputs*T streams are reserved from the context's counter (as fbs_encrypt_fresh) and the first is written to *nonce0
+ * (may be NULL); fresh == 0: *nonce0 is read, under fbs_encrypt's range rule.  The results are those of fbs_decrypt applied
+ * to fbs_eval of fbs_encrypt's ciphertexts; a constant output reads back as fbs_decrypt of the trivial ciphertext fbs_eval
+ * returns for it.  T = 0 does nothing.  Blocks until the messages are back. */
+int fbs_eval_messages(fbs_ctx *ctx, fbs_prog *prog, const int64_t *msgs, size_t T, int fresh, uint64_t *nonce0,
+                      int64_t *out_msgs);
 
 /* ---- a loaded program, one level at a time (multi-GPU hosts) -----------------
  * The two independent axes of the reference's eval loop (fbs_exec_env.py:211-223) are the gates

@@ -147,6 +147,9 @@ def _load():
         "fbs_encrypt": (i32, [vp, vp, sz, u64, vp]),
         "fbs_encrypt_fresh": (i32, [vp, vp, sz, vp, C.POINTER(u64)]),
         "fbs_decrypt": (i32, [vp, vp, sz, vp]),
+        "fbs_encrypt_dev": (i32, [vp, vp, sz, u64, vp, vp]),
+        "fbs_encrypt_fresh_dev": (i32, [vp, vp, sz, vp, C.POINTER(u64), vp]),
+        "fbs_decrypt_dev": (i32, [vp, vp, sz, vp, vp]),
         "fbs_tvset_create": (i32, [vp, vp, vp, u32, C.POINTER(vp)]),
         "fbs_tvset_destroy": (None, [vp]),
         "fbs_bootstrap_batch": (i32, [vp, vp, vp, vp, sz, vp]),
@@ -160,6 +163,7 @@ def _load():
         "fbs_program_info": (i32, [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
         "fbs_eval": (i32, [vp, vp, vp, sz, vp]),
         "fbs_eval_dev": (i32, [vp, vp, vp, sz, vp, vp]),
+        "fbs_eval_messages": (i32, [vp, vp, vp, sz, i32, C.POINTER(u64), vp]),
         "fbs_program_layout": (i32, [vp, C.POINTER(_Layout)]),
         "fbs_program_level": (i32, [vp, u32, C.POINTER(u32), C.POINTER(u32)]),
         "fbs_program_io_slots": (i32, [vp, vp, vp]),
@@ -190,12 +194,13 @@ def _load():
 EXPORTED_SYMBOLS = (
     "fbs_poly_size_check", "fbs_ctx_create", "fbs_ctx_create_seeded", "fbs_ctx_reserve", "fbs_ctx_tune", "fbs_ctx_stat",
     "fbs_import_keys", "fbs_encrypt_fresh", "fbs_ctx_destroy", "fbs_last_error", "fbs_device_info", "fbs_keygen",
-    "fbs_key_sizes", "fbs_export_keys", "fbs_encrypt", "fbs_decrypt", "fbs_tvset_create",
+    "fbs_key_sizes", "fbs_export_keys", "fbs_encrypt", "fbs_decrypt", "fbs_encrypt_dev", "fbs_encrypt_fresh_dev",
+    "fbs_decrypt_dev", "fbs_tvset_create",
     "fbs_tvset_destroy", "fbs_bootstrap_batch", "fbs_bootstrap_batch_dev", "fbs_lincomb_dev",
     "fbs_bootstrap_wires_dev", "fbs_program_load", "fbs_program_load_ex", "fbs_table_fusion_norms", "fbs_program_destroy",
     "fbs_program_info",
     "fbs_searcher_create", "fbs_searcher_destroy", "fbs_searcher_last_error", "fbs_searcher_last_kernel_ms",
-    "fbs_search_lincomb_coefs", "fbs_eval", "fbs_eval_dev", "fbs_program_layout", "fbs_program_level", "fbs_program_io_slots",
+    "fbs_search_lincomb_coefs", "fbs_eval", "fbs_eval_dev", "fbs_eval_messages", "fbs_program_layout", "fbs_program_level", "fbs_program_io_slots",
     "fbs_level_lincomb_dev", "fbs_level_bootstrap_dev", "fbs_level_scatter_dev", "fbs_profile_enable", "fbs_profile_kernel", "fbs_kernel_catalog", "fbs_profile_kernels", "fbs_profile_read", "fbs_sync", "fbs_debug_polymul", "fbs_debug_raise",
 )
 
@@ -276,6 +281,18 @@ class Program:
         in_cts = _c(in_cts, np.uint64).reshape(self.n_inputs, T, ctw)
         out = np.empty((self.n_outputs, T, ctw), np.uint64)
         self.ctx._check(lib.fbs_eval(self.ctx._h, self._h, _ptr(in_cts), T, _ptr(out)))
+        return out
+
+    def eval_messages(self, msgs, nonce0=None):
+        """Messages in, messages out (fbs_eval_messages): msgs [n_inputs][T] -> np.ndarray [n_outputs][T], with the inputs
+        encrypted and the outputs decrypted on the GPU.  The same as ctx.decrypt(self.eval(ctx.encrypt(msgs, nonce0), T)):
+        nonce0=None takes n_inputs * T streams nobody has used, an int pins input i, sample s to stream nonce0 + i*T + s."""
+        msgs = _c(msgs, np.int64)
+        T = msgs.shape[-1] if msgs.ndim else 1
+        msgs = msgs.reshape(self.n_inputs, T)
+        out = np.empty((self.n_outputs, T), np.int64)
+        first = C.c_uint64(0 if nonce0 is None else int(nonce0))
+        self.ctx._check(lib.fbs_eval_messages(self.ctx._h, self._h, _ptr(msgs), T, int(nonce0 is None), C.byref(first), _ptr(out)))
         return out
 
     # device-pointer entry points (ints from torch.Tensor.data_ptr()); asynchronous on `stream`, no host copies
@@ -410,6 +427,20 @@ class Context:
         return out
 
     # device-pointer entry points (ints from torch.Tensor.data_ptr()); asynchronous on `stream`
+    def encrypt_dev(self, d_msgs, count, d_cts, nonce0=None, stream=0):
+        """fbs_encrypt_dev / fbs_encrypt_fresh_dev: `count` int64 messages at d_msgs -> [count][D+1] ciphertexts at d_cts,
+        word-identical to `encrypt`.  Returns the first stream taken (nonce0, or the first fresh one when nonce0 is None)."""
+        if nonce0 is None:
+            first = C.c_uint64()
+            self._check(lib.fbs_encrypt_fresh_dev(self._h, d_msgs or None, count, d_cts or None, C.byref(first), stream or None))
+            return first.value
+        self._check(lib.fbs_encrypt_dev(self._h, d_msgs or None, count, int(nonce0), d_cts or None, stream or None))
+        return int(nonce0)
+
+    def decrypt_dev(self, d_cts, count, d_msgs, stream=0):
+        """fbs_decrypt_dev: [count][D+1] ciphertexts at d_cts -> `count` int64 messages at d_msgs, what `decrypt` returns."""
+        self._check(lib.fbs_decrypt_dev(self._h, d_cts or None, count, d_msgs or None, stream or None))
+
     def bootstrap_batch_dev(self, tvset, d_in, d_table_ids, count, d_out, stream=0):
         self._check(lib.fbs_bootstrap_batch_dev(self._h, tvset._h, d_in, d_table_ids or None, count, d_out,
                                                 stream or None))

@@ -57,6 +57,8 @@ struct fbs_prog {
     bool fused = false;
     std::vector<uint32_t> in_slot;    // [n_inputs]
     std::vector<int64_t> out_slot;    // [n_outputs]  slot, or -1-c for the constant c
+    uint32_t *d_in_slot = nullptr;    // [n_inputs]   the same on the device (fbs_eval_messages)
+    uint32_t *d_out_slot = nullptr;   // [n_outputs]  slot, or 0xFFFFFFFF for a constant
     // schedule: for level L = 0..depth: lincomb stages (dependency order), then the bootstraps of level L+1
     std::vector<std::vector<LincombStage>> lin;   // [depth+1][sub]
     std::vector<BootStage> boot;                  // [depth]  (boot[L] = bootstraps of level L+1)
@@ -274,7 +276,7 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->scratch_used) (void)hipStreamSynchronize(ctx->scratch_stream);
     for (void *p : {(void *)ctx->d_bsk_hat, (void *)ctx->d_bsk_hat_small, (void *)ctx->d_ksk, (void *)ctx->d_ksk_f, (void *)ctx->d_ks_corr, (void *)ctx->d_ks_a, (void *)ctx->d_ks_b, (void *)ctx->d_ks_c, (void *)ctx->d_tw_fwd, (void *)ctx->d_tw_inv, (void *)ctx->d_psi_pow, (void *)ctx->d_ms, (void *)ctx->d_ms_eps, (void *)ctx->d_ms_body, (void *)ctx->d_acc, (void *)ctx->d_stage_in, (void *)ctx->d_stage_out, (void *)ctx->d_stage_ids,
-                    (void *)ctx->d_idx, (void *)ctx->d_wires})
+                    (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_io_msgs})
         if (p) (void)hipFree(p);
     if (ctx->scratch_event) (void)hipEventDestroy(ctx->scratch_event);
     for (auto &v : ctx->prof.pending)
@@ -300,6 +302,7 @@ int fbs_keygen(fbs_ctx *ctx) try {
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     host_keygen(ctx);
     int rc = dev_upload_keys(ctx);
+    if (rc == FBS_OK) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
     ctx->have_keys = true;
     return FBS_OK;
@@ -397,20 +400,34 @@ int fbs_import_keys(fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glw
     ctx->ksk.assign(ksk, ksk + sizes[3]);
     ctx->have_keys = false;
     int rc = dev_upload_keys(ctx);
+    if (rc == FBS_OK) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
     ctx->have_keys = true;
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
-int fbs_encrypt_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *cts, uint64_t *nonce0) try {
-    if (!ctx || (count && (!msgs || !cts))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    // the range [first, first + count) is reserved atomically: two threads encrypting on one context never share a stream (the
-    // bound is checked BEFORE the counter moves, so a refused call leaves it where it was)
+// Streams [first, first + count) of [2^55, 2^56) that nobody has used, for every entry that takes fresh streams.  The range is
+// reserved atomically: two threads encrypting on one context never share a stream (the bound is checked BEFORE the counter
+// moves, so a refused call leaves it where it was).
+static int reserve_fresh(fbs_ctx *ctx, size_t count, uint64_t *first_out) {
     uint64_t first = ctx->next_nonce.load(std::memory_order_relaxed);
     do {
         if (count > (1ull << 56) || first + count > (1ull << 56)) return set_error(ctx, FBS_E_STATE, "encryption streams of this context are used up");
     } while (!ctx->next_nonce.compare_exchange_weak(first, first + count, std::memory_order_relaxed));
+    *first_out = first;
+    return FBS_OK;
+}
+// streams [2^55, 2^56) belong to the fresh entries: an explicit nonce can never repeat one the context handed out itself
+static int check_nonces(const fbs_ctx *ctx, uint64_t nonce0, size_t count) {
+    if (nonce0 >= (1ull << 55) || count > (1ull << 55) - nonce0) return set_error(ctx, FBS_E_INVALID, "nonce0 + count must stay below 2^55");
+    return FBS_OK;
+}
+
+int fbs_encrypt_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *cts, uint64_t *nonce0) try {
+    if (!ctx || (count && (!msgs || !cts))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    uint64_t first = 0;
+    if (int rc = reserve_fresh(ctx, count, &first)) return rc;
     if (nonce0) *nonce0 = first;
     host_encrypt(ctx, msgs, count, first, cts);
     return FBS_OK;
@@ -419,8 +436,7 @@ int fbs_encrypt_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t 
 int fbs_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *cts) try {
     if (!ctx || (count && (!msgs || !cts))) return FBS_E_INVALID;
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    // streams [2^55, 2^56) belong to fbs_encrypt_fresh: an explicit nonce can never repeat one the context handed out itself
-    if (nonce0 >= (1ull << 55) || count > (1ull << 55) - nonce0) return set_error(ctx, FBS_E_INVALID, "nonce0 + count must stay below 2^55");
+    if (int rc = check_nonces(ctx, nonce0, count)) return rc;
     host_encrypt(ctx, msgs, count, nonce0, cts);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
@@ -430,6 +446,54 @@ int fbs_decrypt(const fbs_ctx *ctx, const uint64_t *cts, size_t count, int64_t *
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
     host_decrypt(ctx, cts, count, msgs);
     return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+// ---- the same on device buffers --------------------------------------------------------------
+// count ciphertexts of D + 1 words: more than fit in a size_t is refused before anything is launched
+static int check_ct_words(const fbs_ctx *ctx, size_t count) {
+    if (count > SIZE_MAX / 8 / (ctx->D + 1)) return set_error(ctx, FBS_E_INVALID, "count * (D + 1) words overflow");
+    return FBS_OK;
+}
+static IoView plain_rows(const int64_t *msgs, const uint64_t *cts, size_t count) {
+    IoView v{};
+    v.msgs = const_cast<int64_t *>(msgs);
+    v.msg_stride = count;
+    v.cts = const_cast<uint64_t *>(cts);
+    v.ct_stride = count;
+    v.rows = 1;
+    v.per_row = count;
+    return v;
+}
+
+int fbs_encrypt_dev(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_cts, void *stream) try {
+    if (!ctx || (count && (!d_msgs || !d_cts))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    int rc;
+    if ((rc = check_nonces(ctx, nonce0, count)) || (rc = check_ct_words(ctx, count))) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_encrypt(ctx, plain_rows(d_msgs, d_cts, count), nonce0, 0, stream ? (hipStream_t)stream : ctx->stream);
+} FBS_API_CATCH(ctx)
+
+int fbs_encrypt_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t *d_cts, uint64_t *nonce0, void *stream) try {
+    if (!ctx || (count && (!d_msgs || !d_cts))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    int rc;
+    uint64_t first = 0;
+    if ((rc = check_ct_words(ctx, count)) || (rc = reserve_fresh(ctx, count, &first))) return rc;
+    if (nonce0) *nonce0 = first;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_encrypt(ctx, plain_rows(d_msgs, d_cts, count), first, 0, pick(ctx, stream));
+} FBS_API_CATCH(ctx)
+
+int fbs_decrypt_dev(const fbs_ctx *ctx, const uint64_t *d_cts, size_t count, int64_t *d_msgs, void *stream) try {
+    if (!ctx || (count && (!d_msgs || !d_cts))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (int rc = check_ct_words(ctx, count)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_decrypt(ctx, plain_rows(d_msgs, d_cts, count), stream ? (hipStream_t)stream : ctx->stream);
 } FBS_API_CATCH(ctx)
 
 // ---------------------------------------------------------------------------------------------
@@ -701,6 +765,12 @@ int fbs_program_load_ex(fbs_ctx *ctx, const fbs_program_desc *d, const fbs_tvset
     prog->n_rotations = plan.n_rotations;
     prog->in_slot = plan.in_slot;
     prog->out_slot = plan.out_slot;
+    {
+        std::vector<uint32_t> out_slot(plan.out_slot.size());
+        for (size_t o = 0; o < out_slot.size(); o++) out_slot[o] = plan.out_slot[o] >= 0 ? (uint32_t)plan.out_slot[o] : 0xFFFFFFFFu;
+        if ((rc = to_device(ctx, prog.get(), plan.in_slot, &prog->d_in_slot)) || (rc = to_device(ctx, prog.get(), out_slot, &prog->d_out_slot)))
+            return rc;
+    }
     // ---- upload the stage tables (coefficients and constants mapped into the field) ----------------------------------
     prog->lin.resize(plan.depth + 1);
     prog->boot.resize(plan.depth);
@@ -971,6 +1041,73 @@ int fbs_eval(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *in_cts, size_t T, uin
             }
         }
         FBS_HIP(ctx, hipStreamSynchronize(s));
+    }
+    return scratch_done(ctx, s);
+} FBS_API_CATCH(ctx)
+
+// Messages in, messages out: fbs_eval with the inputs encrypted on the device straight into their wire slots and the output
+// slots decrypted there (the same chunks, scratch ordering and checks); only int64 messages cross the bus.
+static int ensure_io_msgs(fbs_ctx *ctx, size_t words) {
+    if (words <= ctx->io_msgs_capacity) return FBS_OK;
+    ctx->scratch_growths++;
+    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));
+    if (ctx->d_io_msgs) (void)hipFree(ctx->d_io_msgs);
+    ctx->d_io_msgs = nullptr;
+    ctx->io_msgs_capacity = 0;
+    FBS_HIP(ctx, hipMalloc(&ctx->d_io_msgs, words * 8));
+    ctx->io_msgs_capacity = words;
+    return FBS_OK;
+}
+
+int fbs_eval_messages(fbs_ctx *ctx, fbs_prog *prog, const int64_t *msgs, size_t T, int fresh, uint64_t *nonce0, int64_t *out_msgs) try {
+    int rc = check_ready(ctx, prog ? prog->tv : nullptr);
+    if (rc != FBS_OK) return rc;
+    if (!prog || prog->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "program belongs to another context");
+    if ((prog->n_inputs && T && !msgs) || (prog->n_outputs && T && !out_msgs) || (!fresh && !nonce0))
+        return set_error(ctx, FBS_E_INVALID, "null argument");
+    if (T == 0) return FBS_OK;
+    const size_t n_in = prog->n_inputs, n_out = prog->n_outputs;
+    if (T > SIZE_MAX / 8 / std::max<size_t>(1, n_in + n_out) || (rc = check_ct_words(ctx, T * std::max<size_t>(1, n_in))))
+        return set_error(ctx, FBS_E_INVALID, "n_inputs * T ciphertexts overflow");
+    const size_t streams = n_in * T;
+    if (!fresh && (rc = check_nonces(ctx, *nonce0, streams))) return rc;
+    hipStream_t s = ctx->stream;
+    size_t Tc = 0;
+    if ((rc = reserve_wires(ctx, prog, T, &Tc)) != FBS_OK) return rc;
+    if ((rc = ensure_io_msgs(ctx, (n_in + n_out) * Tc)) != FBS_OK) return rc;
+    uint64_t first = fresh ? 0 : *nonce0;
+    if (fresh) {
+        if ((rc = reserve_fresh(ctx, streams, &first))) return rc;
+        if (nonce0) *nonce0 = first;
+    }
+    // what fbs_decrypt makes of the trivial ciphertext fbs_eval returns for a constant output
+    std::vector<int64_t> const_msg(n_out, 0);
+    {
+        std::vector<uint64_t> triv(ctx->D + 1, 0);
+        for (size_t o = 0; o < n_out; o++)
+            if (prog->out_slot[o] < 0) {
+                triv[ctx->D] = trivial_body(ctx, prog->out_slot[o]);
+                host_decrypt(ctx, triv.data(), 1, &const_msg[o]);
+            }
+    }
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    int64_t *d_in_msgs = ctx->d_io_msgs, *d_out_msgs = ctx->d_io_msgs + n_in * Tc;
+    for (size_t s0 = 0; s0 < T; s0 += Tc) {
+        const size_t tc = std::min(Tc, T - s0);
+        if (n_in) {
+            FBS_HIP(ctx, hipMemcpy2DAsync(d_in_msgs, Tc * 8, msgs + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
+            IoView in{d_in_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc};
+            if ((rc = dev_encrypt(ctx, in, first + s0, T, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+        }
+        if ((rc = run_levels(ctx, prog, ctx->d_wires, Tc, tc, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+        if (n_out) {
+            IoView out{d_out_msgs, Tc, ctx->d_wires, prog->d_out_slot, Tc, n_out, tc};
+            if ((rc = dev_decrypt(ctx, out, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+            FBS_HIP(ctx, hipMemcpy2DAsync(out_msgs + s0, T * 8, d_out_msgs, Tc * 8, tc * 8, n_out, hipMemcpyDeviceToHost, s));
+        }
+        FBS_HIP(ctx, hipStreamSynchronize(s));
+        for (size_t o = 0; o < n_out; o++)
+            if (prog->out_slot[o] < 0) std::fill(out_msgs + o * T + s0, out_msgs + o * T + s0 + tc, const_msg[o]);
     }
     return scratch_done(ctx, s);
 } FBS_API_CATCH(ctx)

@@ -8,45 +8,14 @@
 #include <thread>
 
 #include "fbs_internal.hpp"
+#include "fbs_chacha.hpp"
 
 namespace fbs {
 
 // ---------------------------------------------------------------------------------------------
-// ChaCha20, original 64-bit-counter layout.  key = seed || fixed tail, nonce = stream id.
+// ChaCha20 (fbs_chacha.hpp, the same code the device encryption runs): original 64-bit-counter layout, key = seed || fixed
+// tail, stream id in the nonce words.
 // ---------------------------------------------------------------------------------------------
-namespace {
-struct ChaCha {
-    uint32_t in[16];
-    ChaCha(const RandKey &key, uint64_t stream) {
-        static const uint32_t sigma[4] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
-        for (int i = 0; i < 4; i++) in[i] = sigma[i];
-        for (int i = 0; i < 8; i++) in[4 + i] = key.w[i];
-        in[12] = in[13] = 0;
-        in[14] = (uint32_t)stream;
-        in[15] = (uint32_t)(stream >> 32);
-    }
-    static uint32_t rol(uint32_t v, int s) { return (v << s) | (v >> (32 - s)); }
-    static void quarter(uint32_t *x, int a, int b, int c, int d) {
-        x[a] += x[b]; x[d] = rol(x[d] ^ x[a], 16);
-        x[c] += x[d]; x[b] = rol(x[b] ^ x[c], 12);
-        x[a] += x[b]; x[d] = rol(x[d] ^ x[a], 8);
-        x[c] += x[d]; x[b] = rol(x[b] ^ x[c], 7);
-    }
-    void block(uint64_t counter, uint64_t out[8]) {
-        uint32_t x[16];
-        in[12] = (uint32_t)counter;
-        in[13] = (uint32_t)(counter >> 32);
-        std::memcpy(x, in, sizeof x);
-        for (int round = 0; round < 20; round += 2) {
-            quarter(x, 0, 4, 8, 12); quarter(x, 1, 5, 9, 13); quarter(x, 2, 6, 10, 14); quarter(x, 3, 7, 11, 15);
-            quarter(x, 0, 5, 10, 15); quarter(x, 1, 6, 11, 12); quarter(x, 2, 7, 8, 13); quarter(x, 3, 4, 9, 14);
-        }
-        for (int i = 0; i < 8; i++)
-            out[i] = (uint64_t)(x[2 * i] + in[2 * i]) | ((uint64_t)(x[2 * i + 1] + in[2 * i + 1]) << 32);
-    }
-};
-}  // namespace
-
 RandKey rand_key_from_seed64(uint64_t seed) {
     // key words 2..7 spell "fbs-exec-amd-gfx950-key1"
     static const uint32_t tail[6] = {0x2d736266u, 0x63657865u, 0x646d612du, 0x7866672du, 0x2d303539u, 0x3179656bu};
@@ -71,37 +40,32 @@ RandKey rand_key_derive(const uint8_t seed[32], const fbs_params &p) {
             h ^= (f >> (8 * b)) & 0xff;
             h *= 0x100000001b3ull;
         }
-    ChaCha c(master, (0xFFull << 56) | (h & 0x00FFFFFFFFFFFFFFull));
     uint64_t blk[8];
-    c.block(0, blk);
+    chacha_block(master.w, (0xFFull << 56) | (h & 0x00FFFFFFFFFFFFFFull), 0, blk);
     RandKey k;
     std::memcpy(k.w, blk, 32);
     return k;
 }
 
 void rand_words(const RandKey &seed, uint64_t stream, uint64_t idx0, uint64_t *dst, size_t count) {
-    ChaCha c(seed, stream);
     uint64_t blk[8];
     uint64_t have = ~0ull;
     for (size_t i = 0; i < count; i++) {
         uint64_t idx = idx0 + i;
         if ((idx >> 3) != have) {
             have = idx >> 3;
-            c.block(have, blk);
+            chacha_block(seed.w, stream, have, blk);
         }
         dst[i] = blk[idx & 7];
     }
 }
 
-// Integer-only Gaussian stand-in (Irwin-Hall, 12 uniform 32-bit terms, variance 2^64), scaled by
-// sigma / 2^32 and rounded half-up.  Bounded at 6 sigma; fine for tests, not a production sampler.
+// sample idx of a stream: irwin_hall_sample (fbs_chacha.hpp) of its words 6 idx .. 6 idx + 5; no draw when sigma is 0
 int64_t noise_sample(const RandKey &seed, uint64_t stream, uint64_t idx, uint64_t sigma) {
     if (!sigma) return 0;
     uint64_t w[6];
     rand_words(seed, stream, idx * 6, w, 6);
-    __int128 s = -(__int128)6 * 0xFFFFFFFFll;
-    for (uint64_t v : w) s += (__int128)(uint32_t)v + (__int128)(v >> 32);
-    return (int64_t)((s * (__int128)sigma + ((__int128)1 << 31)) >> 32);
+    return irwin_hall_sample(w, sigma);
 }
 
 static void parallel_for(size_t n, const std::function<void(size_t, size_t)> &body) {

@@ -22,7 +22,7 @@ enum Domain : uint64_t {
     DOM_SK_LWE = 1, DOM_SK_GLWE = 2, DOM_BSK_MASK = 3, DOM_BSK_NOISE = 4,
     DOM_KSK_MASK = 5, DOM_KSK_NOISE = 6, DOM_ENC_MASK = 7, DOM_ENC_NOISE = 8
 };
-inline uint64_t stream_id(Domain d, uint64_t sub) { return ((uint64_t)d << 56) | (sub & 0x00FFFFFFFFFFFFFFull); }
+FBS_HD uint64_t stream_id(Domain d, uint64_t sub) { return ((uint64_t)d << 56) | (sub & 0x00FFFFFFFFFFFFFFull); }
 // the 256-bit ChaCha key of a context: a 64-bit seed followed by a fixed tail (fbs_ctx_create: reproducible, test-grade), or
 // derived from 32 caller-supplied bytes and the parameter set (fbs_ctx_create_seeded)
 struct RandKey {
@@ -71,6 +71,18 @@ struct GateView {
     size_t ks_begin, ks_count;  // key switches of this launch, flattened the same way over [n_sources][s_count];
                                 // row r of the modulus-switched scratch holds flattened source index ks_begin + r
     uint32_t n_gates;
+};
+
+// Rows of ciphertexts for the device encryption and decryption (fbs_io.hip): ciphertext (r, s), r < rows, s < per_row, lives at
+// cts + (slot * ct_stride + s) * (D + 1) with slot = row_slot[r] (row_slot null: slot = r; for decryption 0xFFFFFFFF = a row
+// nobody touches), its message at msgs[r * msg_stride + s].
+struct IoView {
+    int64_t *msgs;   // (read by the encryption)
+    size_t msg_stride;
+    uint64_t *cts;   // (read by the decryption)
+    const uint32_t *row_slot;
+    size_t ct_stride;
+    size_t rows, per_row;
 };
 
 struct Profile {
@@ -140,6 +152,9 @@ struct fbs_ctx {
     size_t stage_capacity = 0;       // in ciphertexts
     uint32_t *d_idx = nullptr;       // scratch for index arrays of the host-index wires API
     size_t idx_capacity = 0;
+    uint32_t *d_sk_bits = nullptr;   // [ceil(D / 32)] the GLWE secret key as packed bits (device encryption / decryption, fbs_io.hip)
+    int64_t *d_io_msgs = nullptr;    // scratch: messages of fbs_eval_messages, [n_inputs + n_outputs][chunk]
+    size_t io_msgs_capacity = 0;     // in words
     uint64_t *d_wires = nullptr;     // wire slots of fbs_eval, shared by every program of the context
     size_t wires_capacity = 0;       // in words
     // The scratch buffers above are shared by every call on the context.  Calls on ONE stream are ordered by the
@@ -248,6 +263,12 @@ int dev_multi_extract(fbs_ctx *ctx, const fbs_tvset *tv, const uint64_t *d_acc_r
                       size_t s_count, uint32_t n_extract, const uint32_t *d_x_row, const uint32_t *d_x_table,
                       const uint32_t *d_x_dst, hipStream_t stream);
 int dev_polymul(fbs_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_c, hipStream_t stream);
+
+// device encryption / decryption under the big key (fbs_io.hip), word for word host_encrypt / host_decrypt; asynchronous on `stream`
+int dev_upload_secret(fbs_ctx *ctx);     // sk_glwe -> d_sk_bits (after keygen or import)
+// ciphertext (r, s) of `v` takes stream nonce0 + r * nonce_stride + s
+int dev_encrypt(const fbs_ctx *ctx, const IoView &v, uint64_t nonce0, uint64_t nonce_stride, hipStream_t stream);
+int dev_decrypt(const fbs_ctx *ctx, const IoView &v, hipStream_t stream);
 
 // profiling helpers
 void prof_begin(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t *e0, hipEvent_t *e1);

@@ -1,0 +1,157 @@
+// Encryption and decryption under the big key on the device (fbs_encrypt_dev, fbs_decrypt_dev, fbs_eval_messages), gfx950:
+//
+//   k_encrypt   word for word what host_encrypt (fbs_host.cpp) writes: the same ChaCha20 streams (fbs_chacha.hpp), the same
+//               folds, the same body
+//   k_decrypt   round(phase * 2p / q) mod 2p, what host_decrypt returns
+//
+// One wave per ciphertext.  A lane makes one 64-byte ChaCha block of the mask (8 words) per iteration and stores it with
+// 16-byte stores, consecutive lanes on consecutive blocks; its key-selected words go into a 64-bit sum (D folded words stay
+// below D 2^46 <= 2^58), which the wave adds up and reduces once.  These kernels are not blind-rotation or key-switch
+// launches: they are not in fbs_kernel_catalog and the profile does not count them.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "fbs_chacha.hpp"
+#include "fbs_internal.hpp"
+
+namespace fbs {
+
+constexpr uint32_t IO_WAVES = 4;              // waves (ciphertexts in flight) per workgroup
+constexpr uint32_t IO_MAX_BLOCKS = 1u << 16;  // grid cap; the waves stride over the rest
+constexpr uint32_t IO_NO_SLOT = 0xFFFFFFFFu;
+
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+
+struct EncArgs {
+    IoView v;
+    uint64_t nonce0, nonce_stride;   // ciphertext (r, s) takes stream nonce0 + r nonce_stride + s
+    RandKey key;
+    const uint32_t *sk;              // GLWE secret key, packed bits
+    uint32_t D;
+    uint64_t delta, sigma;
+};
+
+struct DecArgs {
+    IoView v;
+    const uint32_t *sk;
+    uint32_t D;
+    uint64_t two_p;
+};
+
+__device__ __forceinline__ uint64_t wave_sum(uint64_t x) {
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
+    return x;
+}
+
+__global__ __launch_bounds__(64 * IO_WAVES) void k_encrypt(EncArgs a) {
+    const uint32_t lane = threadIdx.x & 63u, D = a.D, blocks = (D + 7) / 8;
+    const size_t total = a.v.rows * a.v.per_row;
+    for (size_t c = (size_t)blockIdx.x * IO_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * IO_WAVES) {   // wave-uniform
+        const size_t r = c / a.v.per_row, s = c - r * a.v.per_row;
+        const size_t slot = a.v.row_slot ? a.v.row_slot[r] : r;
+        uint64_t *ct = a.v.cts + (slot * a.v.ct_stride + s) * (D + 1);
+        const uint64_t nonce = a.nonce0 + r * a.nonce_stride + s;
+        const uint64_t stream = stream_id(DOM_ENC_MASK, nonce);
+        uint64_t sum = 0;
+        for (uint32_t b = lane; b < blocks; b += 64) {
+            uint64_t w[8];
+            chacha_block(a.key.w, stream, b, w);                     // mask words 8b .. 8b + 7
+            const uint32_t bits = (a.sk[b >> 2] >> (8 * (b & 3))) & 0xFFu;
+            for (int i = 0; i < 8; i++) {
+                w[i] = fq_fold(w[i]);
+                sum += ((bits >> i) & 1u) ? w[i] : 0;
+            }
+            uint64_t *p = ct + 8 * (size_t)b;
+            if (8 * b + 8 <= D) {
+                // D + 1 is odd: every other ciphertext starts on an odd word, and so do all of its blocks (the branch is uniform)
+                if (((uintptr_t)p & 15u) == 0) {
+                    for (int i = 0; i < 8; i += 2) *reinterpret_cast<u64x2 *>(p + i) = u64x2{w[i], w[i + 1]};
+                } else {
+                    p[0] = w[0];
+                    for (int i = 1; i < 7; i += 2) *reinterpret_cast<u64x2 *>(p + i) = u64x2{w[i], w[i + 1]};
+                    p[7] = w[7];
+                }
+            } else {
+                for (uint32_t i = 0; 8 * b + i < D; i++) p[i] = w[i];   // D % 8 != 0: the last, partial block
+            }
+        }
+        sum = wave_sum(sum);
+        if (lane == 63) {   // (the lane with the least mask work when the blocks do not fill the last round)
+            uint64_t body = sum % FQ;
+            if (a.sigma) {
+                uint64_t w[8];
+                chacha_block(a.key.w, stream_id(DOM_ENC_NOISE, nonce), 0, w);   // noise_sample(.., idx 0, ..): words 0 .. 5
+                body = fq_add(body, fq_from_i64(irwin_hall_sample(w, a.sigma)));
+            }
+            const int64_t m = a.v.msgs[r * a.v.msg_stride + s];
+            ct[D] = fq_add(body, fq_mul(fq_from_i64(m), a.delta));
+        }
+    }
+}
+
+__global__ __launch_bounds__(64 * IO_WAVES) void k_decrypt(DecArgs a) {
+    const uint32_t lane = threadIdx.x & 63u, D = a.D;
+    const size_t total = a.v.rows * a.v.per_row;
+    for (size_t c = (size_t)blockIdx.x * IO_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * IO_WAVES) {   // wave-uniform
+        const size_t r = c / a.v.per_row, s = c - r * a.v.per_row;
+        const uint32_t slot = a.v.row_slot ? a.v.row_slot[r] : (uint32_t)r;
+        if (a.v.row_slot && slot == IO_NO_SLOT) continue;   // a constant output: the host fills it in
+        const uint64_t *ct = a.v.cts + ((size_t)slot * a.v.ct_stride + s) * (D + 1);
+        uint64_t sum = 0;
+        for (uint32_t j = lane; j < D; j += 64) {
+            const uint64_t w = ct[j];
+            sum += ((a.sk[j >> 5] >> (j & 31u)) & 1u) ? w : 0;
+        }
+        sum = wave_sum(sum);
+        if (lane == 0) {
+            const uint64_t phase = fq_sub(ct[D], sum % FQ);
+            const uint64_t v = phase * a.two_p + FQ / 2;   // < 2^46 * 2^13 + 2^45: no overflow
+            a.v.msgs[r * a.v.msg_stride + s] = (int64_t)((v / FQ) % a.two_p);
+        }
+    }
+}
+
+static dim3 io_grid(size_t total) { return dim3((unsigned)std::min<size_t>((total + IO_WAVES - 1) / IO_WAVES, IO_MAX_BLOCKS)); }
+
+int dev_upload_secret(fbs_ctx *ctx) {
+    const uint32_t D = ctx->D, words = (D + 31) / 32;
+    std::vector<uint32_t> bits(words, 0);
+    for (uint32_t j = 0; j < D; j++)
+        if (ctx->sk_glwe[j]) bits[j >> 5] |= 1u << (j & 31);
+    if (!ctx->d_sk_bits) FBS_HIP(ctx, hipMalloc(&ctx->d_sk_bits, (size_t)words * 4));
+    FBS_HIP(ctx, hipMemcpy(ctx->d_sk_bits, bits.data(), (size_t)words * 4, hipMemcpyHostToDevice));
+    return FBS_OK;
+}
+
+int dev_encrypt(const fbs_ctx *ctx, const IoView &v, uint64_t nonce0, uint64_t nonce_stride, hipStream_t stream) {
+    const size_t total = v.rows * v.per_row;
+    if (total == 0) return FBS_OK;
+    EncArgs a{};
+    a.v = v;
+    a.nonce0 = nonce0;
+    a.nonce_stride = nonce_stride;
+    a.key = ctx->rkey;
+    a.sk = ctx->d_sk_bits;
+    a.D = ctx->D;
+    a.delta = 2 * ctx->delta_half;
+    a.sigma = ctx->p.sigma_glwe;
+    hipLaunchKernelGGL(k_encrypt, io_grid(total), dim3(64 * IO_WAVES), 0, stream, a);
+    FBS_HIP(ctx, hipGetLastError());
+    return FBS_OK;
+}
+
+int dev_decrypt(const fbs_ctx *ctx, const IoView &v, hipStream_t stream) {
+    const size_t total = v.rows * v.per_row;
+    if (total == 0) return FBS_OK;
+    DecArgs a{};
+    a.v = v;
+    a.sk = ctx->d_sk_bits;
+    a.D = ctx->D;
+    a.two_p = 2ull * ctx->p.p_msg;
+    hipLaunchKernelGGL(k_decrypt, io_grid(total), dim3(64 * IO_WAVES), 0, stream, a);
+    FBS_HIP(ctx, hipGetLastError());
+    return FBS_OK;
+}
+
+}  // namespace fbs

@@ -124,6 +124,9 @@ class ExecConfig:
     # FBS/s in full rounds where the k = 2 sets give 151-164 k, 1.5-1.9 ms per launch of up to one bootstrap per CU where they take 2.0-2.4.
     glwe_dims: tuple = (1, 2, 3)          # (= params.DEFAULT_GLWE_DIMS)
     max_programs: int = 8                 # loaded programs kept per ExecConfig (least recently used evicted)
+    # True: `eval` encrypts the inputs and decrypts the outputs on the GPU (Program.eval_messages), only messages cross the bus;
+    # False: on the host (ctx.encrypt, Program.eval, ctx.decrypt).  The same results and the same streams either way.
+    device_io: bool = True
     _contexts: dict = field(default_factory=dict, repr=False)
     _programs: "OrderedDict" = field(default_factory=OrderedDict, repr=False)
     last_choice: dict | None = field(default=None, repr=False)   # what `choose` decided for the most recent program
@@ -507,8 +510,11 @@ class LutExecEnv:
         assert bits.size == 0 or (bits.min() >= 0 and bits.max() <= 1), "inputs are bits"
 
         program = cfg.program_for(ctx, low, fuse)
-        cts = ctx.encrypt(bits, nonce0=cfg.take_nonces(bits.size))
-        out = ctx.decrypt(program.eval(cts, T))
+        if cfg.device_io:
+            out = program.eval_messages(bits, nonce0=cfg.take_nonces(bits.size))
+        else:
+            cts = ctx.encrypt(bits, nonce0=cfg.take_nonces(bits.size))
+            out = ctx.decrypt(program.eval(cts, T))
         result = {}
         for k, name in enumerate(low["out_names"]):
             w = low["out_wire"][k]
