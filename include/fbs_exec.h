@@ -120,7 +120,8 @@ int fbs_ctx_reserve(fbs_ctx *ctx, size_t max_keyswitches, size_t max_shared_rows
  *                           throughput shape */
 int fbs_ctx_tune(fbs_ctx *ctx, const char *knob, int64_t value);
 /* counters: "scratch_growths" (how often a call (re)allocated scratch, i.e. blocked), "ms_capacity", "acc_capacity",
- * "wires_capacity", "next_nonce", "cu_count" */
+ * "wires_capacity", "next_nonce", "cu_count"; "has_secret" (1: the context holds secret keys), "seeded_keys" (1: its keys
+ * came from fbs_keygen_seeded or fbs_import_seeded_keys) */
 int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value);
 /* text of the last failure on `ctx` (or of the last failed fbs_ctx_create when ctx == NULL) */
 const char *fbs_last_error(const fbs_ctx *ctx);
@@ -176,6 +177,46 @@ int fbs_decrypt(const fbs_ctx *ctx, const uint64_t *cts, size_t count, int64_t *
 int fbs_encrypt_dev(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_cts, void *stream);
 int fbs_encrypt_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t *d_cts, uint64_t *nonce0, void *stream);
 int fbs_decrypt_dev(const fbs_ctx *ctx, const uint64_t *d_cts, size_t count, int64_t *d_msgs, void *stream);
+
+/* ---- seeded keys and inputs: evaluation without the secret key --------------
+ * A client holds the secret; a server evaluates with the evaluation keys only.  Every mask of this path is drawn from
+ * ChaCha20 under a PUBLIC 32-byte mask key (the first 32 bytes of a ChaCha20 block under the context's key, which that
+ * block does not reveal), so a server regenerates the masks and only bodies travel: a bootstrapping-key row shrinks from
+ * (k+1) N words to N, a key-switching row from n + 1 words to one, an input ciphertext from D + 1 words to one.  Noise and secrets
+ * come from the context's key, on streams of their own: no noise stream is shared with fbs_keygen
+ * or fbs_encrypt.  The secrets are drawn as fbs_keygen draws them, so a client may mix seeded and full calls.
+ *
+ * fbs_keygen_seeded: as fbs_keygen, with the seeded streams.  The keys it uploads are full keys in the layout of
+ * fbs_key_sizes (fbs_export_keys reads them); a mask row of a GGSW sample carries its message in the body
+ * (-bit g_lv S_comp), which is the phase -- and the distribution -- of fbs_keygen's rows. */
+int fbs_keygen_seeded(fbs_ctx *ctx);
+/* word counts of the bodies: sizes[0] = G (k+1) l N (bsk_bodies[G][(k+1) l][N], column k of every bootstrapping-key
+ * row), sizes[1] = k N t (ksk_bodies[k N][t], word n of every key-switching row) */
+int fbs_seeded_key_sizes(const fbs_ctx *ctx, size_t sizes[2]);
+/* the server key: mask key and bodies.  FBS_E_STATE unless the keys came from fbs_keygen_seeded on this context. */
+int fbs_export_seeded_keys(const fbs_ctx *ctx, uint8_t mask_key[32], uint64_t *bsk_bodies, uint64_t *ksk_bodies);
+/* The mirror, on the server: expands (mask key, bodies) into full keys on the host and uploads them.  Every body word must
+ * be a canonical residue (FBS_E_INVALID otherwise).  The phases cannot be checked, because there is no secret: keys
+ * made for another parameter set or mask key are accepted and bootstrap to garbage.  A refused call leaves the previous
+ * keys in place and usable.  Afterwards the context is EVALUATION-ONLY: its secret keys are gone from host and device,
+ * and every entry that needs them (fbs_encrypt*, fbs_decrypt*, fbs_eval_messages, fbs_encrypt_seeded*,
+ * fbs_export_seeded_keys, fbs_export_keys with sk_lwe or sk_glwe non-NULL) returns FBS_E_STATE; everything else works
+ * as after fbs_keygen.  fbs_keygen / fbs_import_keys / fbs_keygen_seeded make it a full context again. */
+int fbs_import_seeded_keys(fbs_ctx *ctx, const uint8_t mask_key[32], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies);
+/* Seeded encryption: bodies[count] only.  Ciphertext i takes stream nonce0 + i (mask and noise), under fbs_encrypt's nonce
+ * rules: explicit nonces below 2^55, fresh ones from the counter fbs_encrypt_fresh uses. */
+int fbs_encrypt_seeded(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *bodies);
+int fbs_encrypt_seeded_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *bodies, uint64_t *nonce0);
+/* the same two on device buffers, asynchronous on `stream` (NULL = the context's own), word-identical to the host entries */
+int fbs_encrypt_seeded_dev(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_bodies,
+                           void *stream);
+int fbs_encrypt_seeded_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t *d_bodies, uint64_t *nonce0,
+                                 void *stream);
+/* bodies[count] of streams nonce0 .. nonce0 + count - 1 (below 2^56) -> full ciphertexts cts [count][D+1] under the
+ * context's mask key; needs no secret.  fbs_expand_seeded runs on the host and is the reference the device entry is held to. */
+int fbs_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count, uint64_t nonce0, uint64_t *cts);
+int fbs_expand_seeded_dev(const fbs_ctx *ctx, const uint64_t *d_bodies, size_t count, uint64_t nonce0, uint64_t *d_cts,
+                          void *stream);
 
 /* ---- tables -> test vectors ----------------------------------------------
  * One entry per distinct `Bootstrap.table` (fbs_exec_env.py:51-61).  Table t is
@@ -273,6 +314,11 @@ int fbs_eval_dev(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *d_in, size_t T, u
  * returns for it.  T = 0 does nothing.  Blocks until the messages are back. */
 int fbs_eval_messages(fbs_ctx *ctx, fbs_prog *prog, const int64_t *msgs, size_t T, int fresh, uint64_t *nonce0,
                       int64_t *out_msgs);
+/* Seeded inputs, full outputs: bodies host [n_inputs][T] (fbs_encrypt_seeded of a [n_inputs][T] array: input i, sample s
+ * on stream nonce0 + i*T + s), out_cts host [n_outputs][T][D+1] as fbs_eval returns them (constant outputs as trivial
+ * ciphertexts).  Only the bodies cross the bus on the way in; they are expanded on the device straight into the input
+ * wire slots.  The same chunks as fbs_eval; needs no secret.  T = 0 does nothing.  Blocks until the outputs are back. */
+int fbs_eval_seeded(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t T, uint64_t nonce0, uint64_t *out_cts);
 
 /* ---- a loaded program, one level at a time (multi-GPU hosts) -----------------
  * The two independent axes of the reference's eval loop (fbs_exec_env.py:211-223) are the gates

@@ -150,6 +150,17 @@ def _load():
         "fbs_encrypt_dev": (i32, [vp, vp, sz, u64, vp, vp]),
         "fbs_encrypt_fresh_dev": (i32, [vp, vp, sz, vp, C.POINTER(u64), vp]),
         "fbs_decrypt_dev": (i32, [vp, vp, sz, vp, vp]),
+        "fbs_keygen_seeded": (i32, [vp]),
+        "fbs_seeded_key_sizes": (i32, [vp, C.POINTER(sz * 2)]),
+        "fbs_export_seeded_keys": (i32, [vp, vp, vp, vp]),
+        "fbs_import_seeded_keys": (i32, [vp, vp, vp, vp]),
+        "fbs_encrypt_seeded": (i32, [vp, vp, sz, u64, vp]),
+        "fbs_encrypt_seeded_fresh": (i32, [vp, vp, sz, vp, C.POINTER(u64)]),
+        "fbs_encrypt_seeded_dev": (i32, [vp, vp, sz, u64, vp, vp]),
+        "fbs_encrypt_seeded_fresh_dev": (i32, [vp, vp, sz, vp, C.POINTER(u64), vp]),
+        "fbs_expand_seeded": (i32, [vp, vp, sz, u64, vp]),
+        "fbs_expand_seeded_dev": (i32, [vp, vp, sz, u64, vp, vp]),
+        "fbs_eval_seeded": (i32, [vp, vp, vp, sz, u64, vp]),
         "fbs_tvset_create": (i32, [vp, vp, vp, u32, C.POINTER(vp)]),
         "fbs_tvset_destroy": (None, [vp]),
         "fbs_bootstrap_batch": (i32, [vp, vp, vp, vp, sz, vp]),
@@ -202,6 +213,9 @@ EXPORTED_SYMBOLS = (
     "fbs_searcher_create", "fbs_searcher_destroy", "fbs_searcher_last_error", "fbs_searcher_last_kernel_ms",
     "fbs_search_lincomb_coefs", "fbs_eval", "fbs_eval_dev", "fbs_eval_messages", "fbs_program_layout", "fbs_program_level", "fbs_program_io_slots",
     "fbs_level_lincomb_dev", "fbs_level_bootstrap_dev", "fbs_level_scatter_dev", "fbs_profile_enable", "fbs_profile_kernel", "fbs_kernel_catalog", "fbs_profile_kernels", "fbs_profile_read", "fbs_sync", "fbs_debug_polymul", "fbs_debug_raise",
+    "fbs_keygen_seeded", "fbs_seeded_key_sizes", "fbs_export_seeded_keys", "fbs_import_seeded_keys", "fbs_encrypt_seeded",
+    "fbs_encrypt_seeded_fresh", "fbs_encrypt_seeded_dev", "fbs_encrypt_seeded_fresh_dev", "fbs_expand_seeded",
+    "fbs_expand_seeded_dev", "fbs_eval_seeded",
 )
 
 lib = _load()
@@ -295,6 +309,15 @@ class Program:
         self.ctx._check(lib.fbs_eval_messages(self.ctx._h, self._h, _ptr(msgs), T, int(nonce0 is None), C.byref(first), _ptr(out)))
         return out
 
+    def eval_seeded(self, bodies, T, nonce0):
+        """Seeded inputs, full outputs (fbs_eval_seeded): bodies [n_inputs][T] from `Context.encrypt_seeded` of a [n_inputs][T]
+        array whose first stream is nonce0 -> output ciphertexts [n_outputs][T][D+1], as `eval` returns them.  Needs no
+        secret: an evaluation-only context (`Context.evaluation_only`) runs it."""
+        bodies = _c(bodies, np.uint64).reshape(self.n_inputs, T)
+        out = np.empty((self.n_outputs, T, self.ctx.params.ct_words), np.uint64)
+        self.ctx._check(lib.fbs_eval_seeded(self.ctx._h, self._h, _ptr(bodies), T, int(nonce0), _ptr(out)))
+        return out
+
     # device-pointer entry points (ints from torch.Tensor.data_ptr()); asynchronous on `stream`, no host copies
     def eval_dev(self, d_in, T, d_out, stream=0):
         self.ctx._check(lib.fbs_eval_dev(self.ctx._h, self._h, d_in or None, T, d_out or None, stream or None))
@@ -333,6 +356,7 @@ class Context:
         `import_keys`)."""
         self.params = params
         self.seed = seed
+        self.device = device
         self._h = C.c_void_p()
         cp = params.to_c()
         if isinstance(seed, int):
@@ -383,6 +407,84 @@ class Context:
             if a.size != want:
                 raise ValueError(f"{name} has {a.size} words, the parameter set needs {want}")
         self._check(lib.fbs_import_keys(self._h, *[_ptr(a) for a in arrs]))
+
+    # ---- seeded path: masks under a public key, only bodies travel (include/fbs_exec.h) ----
+    def keygen_seeded(self):
+        """fbs_keygen_seeded: keys whose masks a server regenerates from the public mask key (`export_seeded_keys`)."""
+        self._check(lib.fbs_keygen_seeded(self._h))
+
+    def seeded_key_sizes(self):
+        sizes = (C.c_size_t * 2)()
+        self._check(lib.fbs_seeded_key_sizes(self._h, C.byref(sizes)))
+        return int(sizes[0]), int(sizes[1])
+
+    def export_seeded_keys(self):
+        """The server key: dict(mask_key=32 bytes, bsk_bodies, ksk_bodies).  Holds no secret."""
+        nb, nk = self.seeded_key_sizes()
+        mk = np.zeros(32, np.uint8)
+        bsk, ksk = np.empty(nb, np.uint64), np.empty(nk, np.uint64)
+        self._check(lib.fbs_export_seeded_keys(self._h, _ptr(mk), _ptr(bsk), _ptr(ksk)))
+        return dict(mask_key=mk.tobytes(), bsk_bodies=bsk, ksk_bodies=ksk)
+
+    def import_seeded_keys(self, mask_key, bsk_bodies, ksk_bodies):
+        """fbs_import_seeded_keys: expands the server key and leaves the context evaluation-only."""
+        mk = np.frombuffer(bytes(mask_key), np.uint8).copy()
+        if mk.size != 32:
+            raise ValueError("a mask key has 32 bytes")
+        bsk, ksk = _c(bsk_bodies, np.uint64).ravel(), _c(ksk_bodies, np.uint64).ravel()
+        for a, want, name in zip((bsk, ksk), self.seeded_key_sizes(), ("bsk_bodies", "ksk_bodies")):
+            if a.size != want:
+                raise ValueError(f"{name} has {a.size} words, the parameter set needs {want}")
+        self._check(lib.fbs_import_seeded_keys(self._h, _ptr(mk), _ptr(bsk), _ptr(ksk)))
+
+    @classmethod
+    def evaluation_only(cls, params: Params, mask_key, bsk_bodies, ksk_bodies, device: int = 0):
+        """A context that holds the evaluation keys of a server key and no secret: it evaluates (`Program.eval_seeded`,
+        `Program.eval`, the batch and level entries) and refuses to encrypt or decrypt."""
+        ctx = cls(params, seed=None, device=device, keygen=False)
+        ctx.import_seeded_keys(mask_key, bsk_bodies, ksk_bodies)
+        return ctx
+
+    def encrypt_seeded(self, msgs, nonce0=None, device=True):
+        """Seeded encryption: (bodies with the shape of msgs, first stream).  Ciphertext i takes stream nonce0 + i; None = streams
+        nobody has used (the counter of `encrypt`).  device=True (default): on the GPU (fbs_encrypt_seeded_dev), False: on the
+        host -- the same words."""
+        msgs = _c(msgs, np.int64)
+        if not device:
+            bodies = np.empty(msgs.shape, np.uint64)
+            if nonce0 is None:
+                first = C.c_uint64()
+                self._check(lib.fbs_encrypt_seeded_fresh(self._h, _ptr(msgs), msgs.size, _ptr(bodies), C.byref(first)))
+                return bodies, first.value
+            self._check(lib.fbs_encrypt_seeded(self._h, _ptr(msgs), msgs.size, int(nonce0), _ptr(bodies)))
+            return bodies, int(nonce0)
+        import torch
+        d_m = torch.from_numpy(msgs.reshape(-1)).to("cuda:%d" % self.device)
+        d_b = torch.empty(max(1, msgs.size), dtype=torch.int64, device=d_m.device)
+        torch.cuda.synchronize(d_m.device)
+        first = self.encrypt_seeded_dev(d_m.data_ptr(), msgs.size, d_b.data_ptr(), nonce0=nonce0)
+        self.sync()
+        return d_b[:msgs.size].cpu().numpy().view(np.uint64).reshape(msgs.shape), first
+
+    def encrypt_seeded_dev(self, d_msgs, count, d_bodies, nonce0=None, stream=0):
+        """fbs_encrypt_seeded_dev / fbs_encrypt_seeded_fresh_dev; returns the first stream taken"""
+        if nonce0 is None:
+            first = C.c_uint64()
+            self._check(lib.fbs_encrypt_seeded_fresh_dev(self._h, d_msgs or None, count, d_bodies or None, C.byref(first),
+                                                         stream or None))
+            return first.value
+        self._check(lib.fbs_encrypt_seeded_dev(self._h, d_msgs or None, count, int(nonce0), d_bodies or None, stream or None))
+        return int(nonce0)
+
+    def expand_seeded(self, bodies, nonce0):
+        """fbs_expand_seeded (host): bodies of streams nonce0, nonce0 + 1, .. -> full ciphertexts [..][D+1]"""
+        bodies = _c(bodies, np.uint64)
+        cts = np.empty(bodies.shape + (self.params.ct_words,), np.uint64)
+        self._check(lib.fbs_expand_seeded(self._h, _ptr(bodies), bodies.size, int(nonce0), _ptr(cts)))
+        return cts
+
+    def expand_seeded_dev(self, d_bodies, count, nonce0, d_cts, stream=0):
+        self._check(lib.fbs_expand_seeded_dev(self._h, d_bodies or None, count, int(nonce0), d_cts or None, stream or None))
 
     def reserve(self, max_keyswitches=0, max_shared_rows=0, wire_words=0):
         """Size the scratch up front so that no later `*_dev` call has to grow it (growing blocks): include/fbs_exec.h."""

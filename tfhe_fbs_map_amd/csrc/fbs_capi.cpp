@@ -14,6 +14,8 @@
 using namespace fbs;
 
 static thread_local std::string g_create_error;
+// what every entry that needs the secret keys says on a context made by fbs_import_seeded_keys
+static const char *const EVAL_ONLY = "this context holds evaluation keys only";
 
 namespace fbs {
 int set_error(const fbs_ctx *ctx, int code, const std::string &msg) {
@@ -256,6 +258,8 @@ int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value) try {
     else if (k == "wires_capacity") *value = (int64_t)ctx->wires_capacity;
     else if (k == "next_nonce") *value = (int64_t)ctx->next_nonce.load();
     else if (k == "cu_count") *value = ctx->cu_count;
+    else if (k == "has_secret") *value = ctx->have_keys && !ctx->eval_only;
+    else if (k == "seeded_keys") *value = ctx->have_keys && ctx->seeded_keys;
     else return set_error(ctx, FBS_E_INVALID, "unknown statistic '" + k + "'");
     return FBS_OK;
 } FBS_API_CATCH(ctx)
@@ -301,6 +305,8 @@ int fbs_keygen(fbs_ctx *ctx) try {
     if (!ctx) return FBS_E_INVALID;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     host_keygen(ctx);
+    ctx->mask_key = mask_key_of(ctx->rkey);
+    ctx->seeded_keys = ctx->eval_only = false;
     int rc = dev_upload_keys(ctx);
     if (rc == FBS_OK) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
@@ -320,6 +326,7 @@ int fbs_key_sizes(const fbs_ctx *ctx, size_t sizes[4]) try {
 int fbs_export_keys(const fbs_ctx *ctx, uint64_t *sk_lwe, uint64_t *sk_glwe, uint64_t *bsk, uint64_t *ksk) try {
     if (!ctx) return FBS_E_INVALID;
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if ((sk_lwe || sk_glwe) && ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     if (sk_lwe) std::memcpy(sk_lwe, ctx->sk_lwe.data(), ctx->sk_lwe.size() * 8);
     if (sk_glwe) std::memcpy(sk_glwe, ctx->sk_glwe.data(), ctx->sk_glwe.size() * 8);
     if (bsk) std::memcpy(bsk, ctx->bsk.data(), ctx->bsk.size() * 8);
@@ -399,6 +406,8 @@ int fbs_import_keys(fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glw
     ctx->bsk.assign(bsk, bsk + sizes[2]);
     ctx->ksk.assign(ksk, ksk + sizes[3]);
     ctx->have_keys = false;
+    ctx->mask_key = mask_key_of(ctx->rkey);
+    ctx->seeded_keys = ctx->eval_only = false;
     int rc = dev_upload_keys(ctx);
     if (rc == FBS_OK) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
@@ -426,6 +435,7 @@ static int check_nonces(const fbs_ctx *ctx, uint64_t nonce0, size_t count) {
 int fbs_encrypt_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *cts, uint64_t *nonce0) try {
     if (!ctx || (count && (!msgs || !cts))) return FBS_E_INVALID;
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     uint64_t first = 0;
     if (int rc = reserve_fresh(ctx, count, &first)) return rc;
     if (nonce0) *nonce0 = first;
@@ -436,6 +446,7 @@ int fbs_encrypt_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t 
 int fbs_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *cts) try {
     if (!ctx || (count && (!msgs || !cts))) return FBS_E_INVALID;
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     if (int rc = check_nonces(ctx, nonce0, count)) return rc;
     host_encrypt(ctx, msgs, count, nonce0, cts);
     return FBS_OK;
@@ -444,6 +455,7 @@ int fbs_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t 
 int fbs_decrypt(const fbs_ctx *ctx, const uint64_t *cts, size_t count, int64_t *msgs) try {
     if (!ctx || (count && (!msgs || !cts))) return FBS_E_INVALID;
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     host_decrypt(ctx, cts, count, msgs);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
@@ -468,6 +480,7 @@ static IoView plain_rows(const int64_t *msgs, const uint64_t *cts, size_t count)
 int fbs_encrypt_dev(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_cts, void *stream) try {
     if (!ctx || (count && (!d_msgs || !d_cts))) return FBS_E_INVALID;
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     int rc;
     if ((rc = check_nonces(ctx, nonce0, count)) || (rc = check_ct_words(ctx, count))) return rc;
     if (count == 0) return FBS_OK;
@@ -478,6 +491,7 @@ int fbs_encrypt_dev(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uin
 int fbs_encrypt_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t *d_cts, uint64_t *nonce0, void *stream) try {
     if (!ctx || (count && (!d_msgs || !d_cts))) return FBS_E_INVALID;
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     int rc;
     uint64_t first = 0;
     if ((rc = check_ct_words(ctx, count)) || (rc = reserve_fresh(ctx, count, &first))) return rc;
@@ -490,10 +504,154 @@ int fbs_encrypt_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uin
 int fbs_decrypt_dev(const fbs_ctx *ctx, const uint64_t *d_cts, size_t count, int64_t *d_msgs, void *stream) try {
     if (!ctx || (count && (!d_msgs || !d_cts))) return FBS_E_INVALID;
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     if (int rc = check_ct_words(ctx, count)) return rc;
     if (count == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     return dev_decrypt(ctx, plain_rows(d_msgs, d_cts, count), stream ? (hipStream_t)stream : ctx->stream);
+} FBS_API_CATCH(ctx)
+
+// ---- seeded keys and inputs: masks under a public key, only bodies travel ----------------------
+int fbs_keygen_seeded(fbs_ctx *ctx) try {
+    if (!ctx) return FBS_E_INVALID;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    host_keygen_seeded(ctx);
+    ctx->seeded_keys = true;
+    ctx->eval_only = false;
+    int rc = dev_upload_keys(ctx);
+    if (rc == FBS_OK) rc = dev_upload_secret(ctx);
+    if (rc != FBS_OK) return rc;
+    ctx->have_keys = true;
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_seeded_key_sizes(const fbs_ctx *ctx, size_t sizes[2]) try {
+    if (!ctx || !sizes) return FBS_E_INVALID;
+    sizes[0] = ctx->n_ggsw * ctx->rows * ctx->N;
+    sizes[1] = (size_t)ctx->D * ctx->p.t_ksk;
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_export_seeded_keys(const fbs_ctx *ctx, uint8_t mask_key[32], uint64_t *bsk_bodies, uint64_t *ksk_bodies) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (!mask_key || !bsk_bodies || !ksk_bodies) return set_error(ctx, FBS_E_INVALID, "null argument");
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "the keys of this context did not come from fbs_keygen_seeded");
+    const uint32_t N = ctx->N, n = ctx->p.n, k = ctx->p.k;
+    const size_t bsk_rows = ctx->n_ggsw * ctx->rows, ksk_rows = (size_t)ctx->D * ctx->p.t_ksk;
+    for (int i = 0; i < 8; i++)
+        for (int b = 0; b < 4; b++) mask_key[4 * i + b] = (uint8_t)(ctx->mask_key.w[i] >> (8 * b));
+    for (size_t r = 0; r < bsk_rows; r++)
+        std::memcpy(bsk_bodies + r * N, ctx->bsk.data() + (r * (k + 1) + k) * (size_t)N, (size_t)N * 8);
+    for (size_t r = 0; r < ksk_rows; r++) ksk_bodies[r] = ctx->ksk[r * (n + 1) + n];
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_import_seeded_keys(fbs_ctx *ctx, const uint8_t mask_key[32], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (!mask_key || !bsk_bodies || !ksk_bodies) return set_error(ctx, FBS_E_INVALID, "null argument");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    size_t sizes[2];
+    fbs_seeded_key_sizes(ctx, sizes);
+    for (size_t i = 0; i < sizes[0]; i++)
+        if (bsk_bodies[i] >= FQ) return set_error(ctx, FBS_E_INVALID, "bootstrapping-key body word is not a canonical residue");
+    for (size_t i = 0; i < sizes[1]; i++)
+        if (ksk_bodies[i] >= FQ) return set_error(ctx, FBS_E_INVALID, "key-switching-key body word is not a canonical residue");
+    RandKey mk;
+    for (int i = 0; i < 8; i++)
+        mk.w[i] = (uint32_t)mask_key[4 * i] | ((uint32_t)mask_key[4 * i + 1] << 8) | ((uint32_t)mask_key[4 * i + 2] << 16) |
+                  ((uint32_t)mask_key[4 * i + 3] << 24);
+    std::vector<uint64_t> bsk, ksk;
+    host_expand_seeded_keys(ctx, mk, bsk_bodies, ksk_bodies, bsk, ksk);   // (the previous keys stay until this has succeeded)
+    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));   // kernels may still read the old keys
+    if (ctx->stream) FBS_HIP(ctx, hipStreamSynchronize(ctx->stream));               // ... or the old secret
+    ctx->bsk.swap(bsk);
+    ctx->ksk.swap(ksk);
+    std::fill(ctx->sk_lwe.begin(), ctx->sk_lwe.end(), 0);
+    std::fill(ctx->sk_glwe.begin(), ctx->sk_glwe.end(), 0);
+    std::vector<uint64_t>().swap(ctx->sk_lwe);
+    std::vector<uint64_t>().swap(ctx->sk_glwe);
+    if (ctx->d_sk_bits) {
+        (void)hipFree(ctx->d_sk_bits);
+        ctx->d_sk_bits = nullptr;
+    }
+    ctx->mask_key = mk;
+    ctx->have_keys = false;
+    ctx->seeded_keys = true;
+    ctx->eval_only = true;
+    if (int rc = dev_upload_keys(ctx)) return rc;
+    ctx->have_keys = true;
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+// seeded streams may be any the full entries may take, fresh ones included
+static int check_seeded_streams(const fbs_ctx *ctx, uint64_t nonce0, size_t count) {
+    if (nonce0 >= (1ull << 56) || count > (1ull << 56) - nonce0) return set_error(ctx, FBS_E_INVALID, "nonce0 + count must stay below 2^56");
+    return FBS_OK;
+}
+
+int fbs_encrypt_seeded(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *bodies) try {
+    if (!ctx || (count && (!msgs || !bodies))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    if (int rc = check_nonces(ctx, nonce0, count)) return rc;
+    host_encrypt_seeded(ctx, msgs, count, nonce0, bodies);
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_encrypt_seeded_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *bodies, uint64_t *nonce0) try {
+    if (!ctx || (count && (!msgs || !bodies))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    uint64_t first = 0;
+    if (int rc = reserve_fresh(ctx, count, &first)) return rc;
+    if (nonce0) *nonce0 = first;
+    host_encrypt_seeded(ctx, msgs, count, first, bodies);
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_encrypt_seeded_dev(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_bodies, void *stream) try {
+    if (!ctx || (count && (!d_msgs || !d_bodies))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    if (int rc = check_nonces(ctx, nonce0, count)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_encrypt_seeded(ctx, d_msgs, count, nonce0, d_bodies, stream ? (hipStream_t)stream : ctx->stream);
+} FBS_API_CATCH(ctx)
+
+int fbs_encrypt_seeded_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t *d_bodies, uint64_t *nonce0, void *stream) try {
+    if (!ctx || (count && (!d_msgs || !d_bodies))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    uint64_t first = 0;
+    if (int rc = reserve_fresh(ctx, count, &first)) return rc;
+    if (nonce0) *nonce0 = first;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_encrypt_seeded(ctx, d_msgs, count, first, d_bodies, pick(ctx, stream));
+} FBS_API_CATCH(ctx)
+
+int fbs_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count, uint64_t nonce0, uint64_t *cts) try {
+    if (!ctx || (count && (!bodies || !cts))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    int rc;
+    if ((rc = check_seeded_streams(ctx, nonce0, count)) || (rc = check_ct_words(ctx, count))) return rc;
+    host_expand_seeded(ctx, bodies, count, nonce0, cts);
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_expand_seeded_dev(const fbs_ctx *ctx, const uint64_t *d_bodies, size_t count, uint64_t nonce0, uint64_t *d_cts, void *stream) try {
+    if (!ctx || (count && (!d_bodies || !d_cts))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    int rc;
+    if ((rc = check_seeded_streams(ctx, nonce0, count)) || (rc = check_ct_words(ctx, count))) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    IoView v = plain_rows(nullptr, d_cts, count);
+    v.msgs = reinterpret_cast<int64_t *>(const_cast<uint64_t *>(d_bodies));
+    return dev_expand_seeded(ctx, v, nonce0, 0, stream ? (hipStream_t)stream : ctx->stream);
 } FBS_API_CATCH(ctx)
 
 // ---------------------------------------------------------------------------------------------
@@ -1065,6 +1223,7 @@ int fbs_eval_messages(fbs_ctx *ctx, fbs_prog *prog, const int64_t *msgs, size_t 
     if (!prog || prog->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "program belongs to another context");
     if ((prog->n_inputs && T && !msgs) || (prog->n_outputs && T && !out_msgs) || (!fresh && !nonce0))
         return set_error(ctx, FBS_E_INVALID, "null argument");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     if (T == 0) return FBS_OK;
     const size_t n_in = prog->n_inputs, n_out = prog->n_outputs;
     if (T > SIZE_MAX / 8 / std::max<size_t>(1, n_in + n_out) || (rc = check_ct_words(ctx, T * std::max<size_t>(1, n_in))))
@@ -1108,6 +1267,50 @@ int fbs_eval_messages(fbs_ctx *ctx, fbs_prog *prog, const int64_t *msgs, size_t 
         FBS_HIP(ctx, hipStreamSynchronize(s));
         for (size_t o = 0; o < n_out; o++)
             if (prog->out_slot[o] < 0) std::fill(out_msgs + o * T + s0, out_msgs + o * T + s0 + tc, const_msg[o]);
+    }
+    return scratch_done(ctx, s);
+} FBS_API_CATCH(ctx)
+
+// Seeded inputs: fbs_eval with the bodies copied to the device and expanded there straight into their wire slots (the chunks,
+// scratch ordering and outputs of fbs_eval); needs no secret.  The bodies use fbs_eval_messages's message scratch.
+int fbs_eval_seeded(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t T, uint64_t nonce0, uint64_t *out_cts) try {
+    int rc = check_ready(ctx, prog ? prog->tv : nullptr);
+    if (rc != FBS_OK) return rc;
+    if (!prog || prog->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "program belongs to another context");
+    if ((prog->n_inputs && T && !bodies) || (prog->n_outputs && T && !out_cts)) return set_error(ctx, FBS_E_INVALID, "null argument");
+    if (T == 0) return FBS_OK;
+    const size_t n_in = prog->n_inputs, n_out = prog->n_outputs, ctw = ctx->D + 1;
+    if (T > SIZE_MAX / 8 / std::max<size_t>(1, std::max(n_in, n_out)) / ctw)
+        return set_error(ctx, FBS_E_INVALID, "n_inputs * T ciphertexts overflow");
+    if ((rc = check_seeded_streams(ctx, nonce0, n_in * T))) return rc;
+    hipStream_t s = ctx->stream;
+    size_t Tc = 0;
+    if ((rc = reserve_wires(ctx, prog, T, &Tc)) != FBS_OK) return rc;
+    if ((rc = ensure_io_msgs(ctx, std::max<size_t>(1, n_in) * Tc)) != FBS_OK) return rc;
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    uint64_t *d_bodies = reinterpret_cast<uint64_t *>(ctx->d_io_msgs);
+    for (size_t s0 = 0; s0 < T; s0 += Tc) {
+        const size_t tc = std::min(Tc, T - s0);
+        if (n_in) {
+            FBS_HIP(ctx, hipMemcpy2DAsync(d_bodies, Tc * 8, bodies + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
+            IoView in{ctx->d_io_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc};
+            if ((rc = dev_expand_seeded(ctx, in, nonce0 + s0, T, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+        }
+        if ((rc = run_levels(ctx, prog, ctx->d_wires, Tc, tc, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+        for (uint32_t o = 0; o < n_out; o++) {
+            uint64_t *dst = out_cts + ((size_t)o * T + s0) * ctw;
+            const int64_t w = prog->out_slot[o];
+            if (w >= 0) {
+                FBS_HIP(ctx, hipMemcpyAsync(dst, ctx->d_wires + (size_t)w * Tc * ctw, tc * ctw * 8, hipMemcpyDeviceToHost, s));
+            } else {
+                const uint64_t body = trivial_body(ctx, w);   // trivial ciphertext of the constant, as fbs_eval
+                for (size_t q = 0; q < tc; q++) {
+                    std::memset(dst + q * ctw, 0, ctx->D * 8);
+                    dst[q * ctw + ctx->D] = body;
+                }
+            }
+        }
+        FBS_HIP(ctx, hipStreamSynchronize(s));
     }
     return scratch_done(ctx, s);
 } FBS_API_CATCH(ctx)

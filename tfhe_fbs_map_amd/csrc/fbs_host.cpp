@@ -94,6 +94,7 @@ int host_ctx_init(fbs_ctx *ctx, const fbs_params *params, uint64_t seed, const u
     ctx->p = *params;
     ctx->seed = seed;
     ctx->rkey = seed32 ? rand_key_derive(seed32, *params) : rand_key_from_seed64(seed);
+    ctx->mask_key = mask_key_of(ctx->rkey);
     const fbs_params &p = ctx->p;
     if (p.log_n_poly < 2 || p.log_n_poly > 14 || p.k < 1 || p.k > 4 || p.p_msg < 1 || p.p_msg > 4096 || p.l_bsk > 16 ||
         p.t_ksk > 64)
@@ -117,30 +118,47 @@ int host_ctx_init(fbs_ctx *ctx, const fbs_params *params, uint64_t seed, const u
     return FBS_OK;
 }
 
+// the secret keys of fbs_keygen and fbs_keygen_seeded alike (DOM_SK_LWE, DOM_SK_GLWE)
+static void draw_secrets(fbs_ctx *ctx) {
+    const uint32_t n = ctx->p.n, D = ctx->D;
+    ctx->sk_lwe.assign(n, 0);
+    ctx->sk_glwe.assign(D, 0);
+    std::vector<uint64_t> w(std::max(n, D));
+    rand_words(ctx->rkey, stream_id(DOM_SK_LWE, 0), 0, w.data(), n);
+    for (uint32_t i = 0; i < n; i++) ctx->sk_lwe[i] = w[i] & 1;
+    rand_words(ctx->rkey, stream_id(DOM_SK_GLWE, 0), 0, w.data(), D);
+    for (uint32_t i = 0; i < D; i++) ctx->sk_glwe[i] = w[i] & 1;
+}
+
+// support of each GLWE key polynomial (binary key => A*S is a signed sum of shifted copies of A)
+static std::vector<std::vector<uint32_t>> glwe_support(const fbs_ctx *ctx) {
+    std::vector<std::vector<uint32_t>> support(ctx->p.k);
+    for (uint32_t c = 0; c < ctx->p.k; c++)
+        for (uint32_t i = 0; i < ctx->N; i++)
+            if (ctx->sk_glwe[(size_t)c * ctx->N + i]) support[c].push_back(i);
+    return support;
+}
+
+// the bit GGSW sample g encrypts: key bit g, or for pairs (s0, s1) of key bits the products s0(1-s1), (1-s0)s1, s0 s1
+static uint64_t ggsw_bit(const fbs_ctx *ctx, size_t g) {
+    if (ctx->group != 2) return ctx->sk_lwe[g];
+    const uint64_t s0 = ctx->sk_lwe[2 * (g / 3)], s1 = ctx->sk_lwe[2 * (g / 3) + 1];
+    return g % 3 == 0 ? (s0 & (1 - s1)) : g % 3 == 1 ? ((1 - s0) & s1) : (s0 & s1);
+}
+
+// acc += a * S (negacyclic, binary S given by its support)
+static void add_times_key(uint64_t *acc, const uint64_t *a, const std::vector<uint32_t> &support, uint32_t N) {
+    for (uint32_t sh : support) {
+        for (uint32_t j = 0; j < N - sh; j++) acc[j + sh] = fq_add(acc[j + sh], a[j]);
+        for (uint32_t j = N - sh; j < N; j++) acc[j + sh - N] = fq_sub(acc[j + sh - N], a[j]);
+    }
+}
+
 void host_keygen(fbs_ctx *ctx) {
     const fbs_params &p = ctx->p;
     const uint32_t N = ctx->N, D = ctx->D, n = p.n, k = p.k, l = p.l_bsk, t = p.t_ksk, rows = ctx->rows;
-    ctx->sk_lwe.assign(n, 0);
-    ctx->sk_glwe.assign(D, 0);
-    {
-        std::vector<uint64_t> w(std::max(n, D));
-        rand_words(ctx->rkey, stream_id(DOM_SK_LWE, 0), 0, w.data(), n);
-        for (uint32_t i = 0; i < n; i++) ctx->sk_lwe[i] = w[i] & 1;
-        rand_words(ctx->rkey, stream_id(DOM_SK_GLWE, 0), 0, w.data(), D);
-        for (uint32_t i = 0; i < D; i++) ctx->sk_glwe[i] = w[i] & 1;
-    }
-    // support of each GLWE key polynomial (binary key => A*S is a signed sum of shifted copies of A)
-    std::vector<std::vector<uint32_t>> support(k);
-    for (uint32_t c = 0; c < k; c++)
-        for (uint32_t i = 0; i < N; i++)
-            if (ctx->sk_glwe[(size_t)c * N + i]) support[c].push_back(i);
-
-    // the bit GGSW sample g encrypts: key bit g, or for pairs (s0, s1) of key bits the products s0(1-s1), (1-s0)s1, s0 s1
-    auto ggsw_bit = [&](size_t g) -> uint64_t {
-        if (ctx->group != 2) return ctx->sk_lwe[g];
-        const uint64_t s0 = ctx->sk_lwe[2 * (g / 3)], s1 = ctx->sk_lwe[2 * (g / 3) + 1];
-        return g % 3 == 0 ? (s0 & (1 - s1)) : g % 3 == 1 ? ((1 - s0) & s1) : (s0 & s1);
-    };
+    draw_secrets(ctx);
+    const std::vector<std::vector<uint32_t>> support = glwe_support(ctx);
     const size_t row_words = (size_t)(k + 1) * N;
     ctx->bsk.assign(ctx->n_ggsw * rows * row_words, 0);
     parallel_for(ctx->n_ggsw * rows, [&](size_t r0, size_t r1) {
@@ -164,7 +182,7 @@ void host_keygen(fbs_ctx *ctx) {
                 }
                 for (uint32_t j = 0; j < N; j++) body[j] = fq_add(body[j], prod[j]);
             }
-            if (ggsw_bit(i)) row[(size_t)comp * N] = fq_add(row[(size_t)comp * N], ctx->g[lv]);
+            if (ggsw_bit(ctx, i)) row[(size_t)comp * N] = fq_add(row[(size_t)comp * N], ctx->g[lv]);
         }
     });
 
@@ -181,6 +199,120 @@ void host_keygen(fbs_ctx *ctx) {
             }
             if (ctx->sk_glwe[j]) b = fq_add(b, ctx->h[v]);
             row[n] = b;
+        }
+    });
+}
+
+// ---------------------------------------------------------------------------------------------
+// seeded keys: every mask under the public mask key, so that only the bodies travel
+// ---------------------------------------------------------------------------------------------
+RandKey mask_key_of(const RandKey &key) {
+    uint64_t blk[8];
+    chacha_block(key.w, stream_id(DOM_MASK_KEY, 0), 0, blk);
+    RandKey m;
+    for (int i = 0; i < 4; i++) {
+        m.w[2 * i] = (uint32_t)blk[i];
+        m.w[2 * i + 1] = (uint32_t)(blk[i] >> 32);
+    }
+    return m;
+}
+
+// Row r of the bootstrapping key, r = g (k+1) l + comp l + lv: mask A_c = fold(words c N .. c N + N - 1 of stream
+// (DOM_SBSK_MASK, r)) under the mask key, body = e + sum_c A_c S_c + the message, e on stream (DOM_SBSK_NOISE, r) under the
+// context key.  The message sits in the body whatever the component: bit g_lv at X^0 for comp = k, -bit g_lv S_comp for a mask
+// row.  That is the phase fbs_keygen's rows have (its g_lv sits on A_comp), and the same distribution --
+// the server, which regenerates the masks, needs no secret bit.  Key-switching row r = (j, v): mask = fold(stream
+// (DOM_SKSK_MASK, r)), body = e + <a, sk_lwe> + sk_glwe[j] h_v.
+void host_keygen_seeded(fbs_ctx *ctx) {
+    const fbs_params &p = ctx->p;
+    const uint32_t N = ctx->N, D = ctx->D, n = p.n, k = p.k, l = p.l_bsk, t = p.t_ksk, rows = ctx->rows;
+    draw_secrets(ctx);
+    ctx->mask_key = mask_key_of(ctx->rkey);
+    const std::vector<std::vector<uint32_t>> support = glwe_support(ctx);
+    std::vector<uint64_t> bsk_bodies(ctx->n_ggsw * rows * N), ksk_bodies((size_t)D * t);
+    parallel_for(ctx->n_ggsw * rows, [&](size_t r0, size_t r1) {
+        std::vector<uint64_t> a(N);
+        for (size_t r = r0; r < r1; r++) {
+            const size_t g = r / rows;
+            const uint32_t rr = (uint32_t)(r % rows), comp = rr / l, lv = rr % l;
+            uint64_t *body = bsk_bodies.data() + r * N;
+            for (uint32_t j = 0; j < N; j++)
+                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SBSK_NOISE, r), j, p.sigma_glwe));
+            for (uint32_t c = 0; c < k; c++) {
+                rand_words(ctx->mask_key, stream_id(DOM_SBSK_MASK, r), (uint64_t)c * N, a.data(), N);
+                for (uint32_t j = 0; j < N; j++) a[j] = fq_fold(a[j]);
+                add_times_key(body, a.data(), support[c], N);
+            }
+            if (!ggsw_bit(ctx, g)) continue;
+            if (comp == k) {
+                body[0] = fq_add(body[0], ctx->g[lv]);
+            } else {
+                for (uint32_t j : support[comp]) body[j] = fq_sub(body[j], ctx->g[lv]);
+            }
+        }
+    });
+    parallel_for((size_t)D * t, [&](size_t r0, size_t r1) {
+        std::vector<uint64_t> a(n);
+        for (size_t r = r0; r < r1; r++) {
+            const uint32_t j = (uint32_t)(r / t), v = (uint32_t)(r % t);
+            rand_words(ctx->mask_key, stream_id(DOM_SKSK_MASK, r), 0, a.data(), n);
+            uint64_t b = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SKSK_NOISE, r), 0, p.sigma_lwe));
+            for (uint32_t i = 0; i < n; i++)
+                if (ctx->sk_lwe[i]) b = fq_add(b, fq_fold(a[i]));
+            if (ctx->sk_glwe[j]) b = fq_add(b, ctx->h[v]);
+            ksk_bodies[r] = b;
+        }
+    });
+    host_expand_seeded_keys(ctx, ctx->mask_key, bsk_bodies.data(), ksk_bodies.data(), ctx->bsk, ctx->ksk);
+}
+
+void host_expand_seeded_keys(const fbs_ctx *ctx, const RandKey &mask_key, const uint64_t *bsk_bodies, const uint64_t *ksk_bodies,
+                             std::vector<uint64_t> &bsk, std::vector<uint64_t> &ksk) {
+    const uint32_t N = ctx->N, D = ctx->D, n = ctx->p.n, k = ctx->p.k, t = ctx->p.t_ksk, rows = ctx->rows;
+    const size_t row_words = (size_t)(k + 1) * N;
+    bsk.assign(ctx->n_ggsw * rows * row_words, 0);
+    parallel_for(ctx->n_ggsw * rows, [&](size_t r0, size_t r1) {
+        for (size_t r = r0; r < r1; r++) {
+            uint64_t *row = bsk.data() + r * row_words;
+            rand_words(mask_key, stream_id(DOM_SBSK_MASK, r), 0, row, (size_t)k * N);
+            for (size_t j = 0; j < (size_t)k * N; j++) row[j] = fq_fold(row[j]);
+            std::memcpy(row + (size_t)k * N, bsk_bodies + r * N, (size_t)N * 8);
+        }
+    });
+    ksk.assign((size_t)D * t * (n + 1), 0);
+    parallel_for((size_t)D * t, [&](size_t r0, size_t r1) {
+        for (size_t r = r0; r < r1; r++) {
+            uint64_t *row = ksk.data() + r * (n + 1);
+            rand_words(mask_key, stream_id(DOM_SKSK_MASK, r), 0, row, n);
+            for (uint32_t i = 0; i < n; i++) row[i] = fq_fold(row[i]);
+            row[n] = ksk_bodies[r];
+        }
+    });
+}
+
+void host_encrypt_seeded(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *bodies) {
+    const uint32_t D = ctx->D;
+    const uint64_t delta = 2 * ctx->delta_half;
+    parallel_for(count, [&](size_t a, size_t b) {
+        std::vector<uint64_t> mask(D);
+        for (size_t i = a; i < b; i++) {
+            rand_words(ctx->mask_key, stream_id(DOM_SENC_MASK, nonce0 + i), 0, mask.data(), D);
+            uint64_t body = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SENC_NOISE, nonce0 + i), 0, ctx->p.sigma_glwe));
+            for (uint32_t j = 0; j < D; j++)
+                if (ctx->sk_glwe[j]) body = fq_add(body, fq_fold(mask[j]));
+            bodies[i] = fq_add(body, fq_mul(fq_from_i64(msgs[i]), delta));
+        }
+    });
+}
+
+void host_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count, uint64_t nonce0, uint64_t *cts) {
+    const uint32_t D = ctx->D;
+    parallel_for(count, [&](size_t a, size_t b) {
+        for (size_t i = a; i < b; i++) {
+            uint64_t *ct = cts + i * (D + 1);
+            rand_words(ctx->mask_key, stream_id(DOM_SENC_MASK, nonce0 + i), 0, ct, D);
+            for (uint32_t j = 0; j < D; j++) ct[j] = fq_fold(ct[j]);
+            ct[D] = bodies[i];
         }
     });
 }

@@ -18,9 +18,18 @@
 namespace fbs {
 
 // ---- randomness: ChaCha20 keyed by the context seed (spec in DESIGN.md) -----------------------
+// Domains 9 and up are the seeded path's (fbs_keygen_seeded, fbs_encrypt_seeded): its masks are drawn under the public mask
+// key (mask_key_of), its noise and secrets under the context's key.  No (key, stream) pair of the seeded path may equal one that
+// fbs_keygen or fbs_encrypt uses, above all for noise: two key sets under one secret and one noise stream have bodies that differ
+// by exactly (A - A') S, which gives the secret away.  The secret keys themselves are shared (DOM_SK_*), so that one client
+// context can mix seeded and full calls.
 enum Domain : uint64_t {
     DOM_SK_LWE = 1, DOM_SK_GLWE = 2, DOM_BSK_MASK = 3, DOM_BSK_NOISE = 4,
-    DOM_KSK_MASK = 5, DOM_KSK_NOISE = 6, DOM_ENC_MASK = 7, DOM_ENC_NOISE = 8
+    DOM_KSK_MASK = 5, DOM_KSK_NOISE = 6, DOM_ENC_MASK = 7, DOM_ENC_NOISE = 8,
+    DOM_MASK_KEY = 9,                                   // under the context's key: block 0 of stream 0 -> the public mask key
+    DOM_SBSK_MASK = 10, DOM_SBSK_NOISE = 11,            // seeded bootstrapping key: mask (mask key), noise (context key)
+    DOM_SKSK_MASK = 12, DOM_SKSK_NOISE = 13,            // seeded key-switching key
+    DOM_SENC_MASK = 14, DOM_SENC_NOISE = 15             // seeded encryption
 };
 FBS_HD uint64_t stream_id(Domain d, uint64_t sub) { return ((uint64_t)d << 56) | (sub & 0x00FFFFFFFFFFFFFFull); }
 // the 256-bit ChaCha key of a context: a 64-bit seed followed by a fixed tail (fbs_ctx_create: reproducible, test-grade), or
@@ -32,6 +41,9 @@ RandKey rand_key_from_seed64(uint64_t seed);
 RandKey rand_key_derive(const uint8_t seed[32], const fbs_params &p);
 void rand_words(const RandKey &key, uint64_t stream, uint64_t idx0, uint64_t *dst, size_t count);
 int64_t noise_sample(const RandKey &key, uint64_t stream, uint64_t idx, uint64_t sigma);
+// the public mask key of the seeded path: the first four 64-bit words of chacha_block(key, stream_id(DOM_MASK_KEY, 0), 0),
+// little-endian (ChaCha20 is a PRF keyed by `key`: publishing this block reveals nothing about it)
+RandKey mask_key_of(const RandKey &key);
 
 // launcher knobs (fbs_ctx_tune): which kernel shape a launch takes (fbs_select.cpp).  Defaults are the measured choices; tests
 // use them to reach every instantiation at small sizes.
@@ -77,7 +89,7 @@ struct GateView {
 // cts + (slot * ct_stride + s) * (D + 1) with slot = row_slot[r] (row_slot null: slot = r; for decryption 0xFFFFFFFF = a row
 // nobody touches), its message at msgs[r * msg_stride + s].
 struct IoView {
-    int64_t *msgs;   // (read by the encryption)
+    int64_t *msgs;   // (read by the encryption; the seeded expansion reads its bodies here, as uint64 words)
     size_t msg_stride;
     uint64_t *cts;   // (read by the decryption)
     const uint32_t *row_slot;
@@ -128,6 +140,11 @@ struct fbs_ctx {
 
     bool have_keys = false;
     std::vector<uint64_t> sk_lwe, sk_glwe, bsk, ksk;   // host copies, standard layout
+    // Seeded path: masks are drawn under `mask_key` (mask_key_of(rkey), or the one fbs_import_seeded_keys received).
+    // seeded_keys: the evaluation keys came from fbs_keygen_seeded or fbs_import_seeded_keys; eval_only: they came from
+    // fbs_import_seeded_keys, and the context holds no secret (sk_lwe, sk_glwe empty, d_sk_bits freed).
+    fbs::RandKey mask_key{};
+    bool seeded_keys = false, eval_only = false;
 
     uint64_t *d_bsk_hat = nullptr;   // [n][rows][k+1][N]  NTT domain, lane-interleaved, x N^-1
     uint64_t *d_bsk_hat_small = nullptr;   // the same in the evaluation order of the small-launch shape (fbs_ntt.hpp), where small_key_needed
@@ -232,6 +249,16 @@ int host_ctx_init(fbs_ctx *ctx, const fbs_params *params, uint64_t seed, const u
 void host_keygen(fbs_ctx *ctx);
 void host_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *cts);
 void host_decrypt(const fbs_ctx *ctx, const uint64_t *cts, size_t count, int64_t *msgs);
+// seeded path (DOM_S*): host_keygen row for row with masks under ctx->mask_key (= mask_key_of(rkey)) and noise on the seeded
+// streams; the secrets are host_keygen's.  The bodies are computed, then expanded by host_expand_seeded_keys like any import.
+void host_keygen_seeded(fbs_ctx *ctx);
+// (mask key, bodies) -> full keys in the fbs_key_sizes layout.  bsk_bodies [G][(k+1) l][N], ksk_bodies [k N][t]
+void host_expand_seeded_keys(const fbs_ctx *ctx, const RandKey &mask_key, const uint64_t *bsk_bodies, const uint64_t *ksk_bodies,
+                             std::vector<uint64_t> &bsk, std::vector<uint64_t> &ksk);
+// ciphertext i takes stream nonce0 + i in both DOM_SENC_MASK (under ctx->mask_key) and DOM_SENC_NOISE; bodies[count]
+void host_encrypt_seeded(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *bodies);
+// bodies[count] -> cts [count][D+1]: the mask of stream nonce0 + i under ctx->mask_key, then the body
+void host_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count, uint64_t nonce0, uint64_t *cts);
 int host_build_tv(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint64_t *tv, uint64_t *post_add);
 // D_F with TV_F = TV_0 * D_F as (position, value) pairs of its non-zero coefficients, at most p + 1 of them (`pos`, `val`
 // sized for that); *norm2 = |D_F|^2, *g_norm2 = |G_F|^2 (TV_F = delta_half G_F), *abs_sum = sum |d|.  Errors as host_build_tv.
@@ -269,6 +296,10 @@ int dev_upload_secret(fbs_ctx *ctx);     // sk_glwe -> d_sk_bits (after keygen o
 // ciphertext (r, s) of `v` takes stream nonce0 + r * nonce_stride + s
 int dev_encrypt(const fbs_ctx *ctx, const IoView &v, uint64_t nonce0, uint64_t nonce_stride, hipStream_t stream);
 int dev_decrypt(const fbs_ctx *ctx, const IoView &v, hipStream_t stream);
+// seeded path, word for word host_encrypt_seeded / host_expand_seeded.  dev_encrypt_seeded: d_msgs [count] -> d_bodies [count];
+// dev_expand_seeded: the bodies at v.msgs (read as uint64 words) -> ciphertexts, (r, s) on stream nonce0 + r nonce_stride + s
+int dev_encrypt_seeded(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_bodies, hipStream_t stream);
+int dev_expand_seeded(const fbs_ctx *ctx, const IoView &v, uint64_t nonce0, uint64_t nonce_stride, hipStream_t stream);
 
 // profiling helpers
 void prof_begin(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t *e0, hipEvent_t *e1);

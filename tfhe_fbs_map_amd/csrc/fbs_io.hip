@@ -3,6 +3,10 @@
 //   k_encrypt   word for word what host_encrypt (fbs_host.cpp) writes: the same ChaCha20 streams (fbs_chacha.hpp), the same
 //               folds, the same body
 //   k_decrypt   round(phase * 2p / q) mod 2p, what host_decrypt returns
+//   k_encrypt_seeded   the body of host_encrypt_seeded: k_encrypt's sum over the mask of the seeded stream under the public mask
+//               key, noise and message; only the body is stored
+//   k_expand_seeded    host_expand_seeded: the mask of the seeded stream under the mask key, then the given body.  No key-selected
+//               sum: the kernel needs no secret, and is what an evaluation-only context runs on its inputs
 //
 // One wave per ciphertext.  A lane makes one 64-byte ChaCha block of the mask (8 words) per iteration and stores it with
 // 16-byte stores, consecutive lanes on consecutive blocks; its key-selected words go into a 64-bit sum (D folded words stay
@@ -112,6 +116,80 @@ __global__ __launch_bounds__(64 * IO_WAVES) void k_decrypt(DecArgs a) {
     }
 }
 
+struct SeededEncArgs {
+    const int64_t *msgs;
+    uint64_t *bodies;
+    size_t count;
+    uint64_t nonce0;                 // ciphertext i takes stream nonce0 + i
+    RandKey mask_key, key;           // masks under the public mask key, noise under the context's key
+    const uint32_t *sk;
+    uint32_t D;
+    uint64_t delta, sigma;
+};
+
+struct ExpandArgs {
+    IoView v;                        // v.msgs: the bodies, as uint64 words
+    uint64_t nonce0, nonce_stride;   // ciphertext (r, s) takes stream nonce0 + r nonce_stride + s
+    RandKey mask_key;
+    uint32_t D;
+};
+
+__global__ __launch_bounds__(64 * IO_WAVES) void k_encrypt_seeded(SeededEncArgs a) {
+    const uint32_t lane = threadIdx.x & 63u, D = a.D, blocks = (D + 7) / 8;
+    for (size_t c = (size_t)blockIdx.x * IO_WAVES + threadIdx.x / 64; c < a.count; c += (size_t)gridDim.x * IO_WAVES) {   // wave-uniform
+        const uint64_t nonce = a.nonce0 + c;
+        const uint64_t stream = stream_id(DOM_SENC_MASK, nonce);
+        uint64_t sum = 0;
+        for (uint32_t b = lane; b < blocks; b += 64) {
+            uint64_t w[8];
+            chacha_block(a.mask_key.w, stream, b, w);                // mask words 8b .. 8b + 7
+            const uint32_t bits = (a.sk[b >> 2] >> (8 * (b & 3))) & 0xFFu;   // (bits past D are zero in the packed key)
+            for (int i = 0; i < 8; i++) sum += ((bits >> i) & 1u) ? fq_fold(w[i]) : 0;
+        }
+        sum = wave_sum(sum);
+        if (lane == 63) {
+            uint64_t body = sum % FQ;
+            if (a.sigma) {
+                uint64_t w[8];
+                chacha_block(a.key.w, stream_id(DOM_SENC_NOISE, nonce), 0, w);
+                body = fq_add(body, fq_from_i64(irwin_hall_sample(w, a.sigma)));
+            }
+            a.bodies[c] = fq_add(body, fq_mul(fq_from_i64(a.msgs[c]), a.delta));
+        }
+    }
+}
+
+__global__ __launch_bounds__(64 * IO_WAVES) void k_expand_seeded(ExpandArgs a) {
+    const uint32_t lane = threadIdx.x & 63u, D = a.D, blocks = (D + 7) / 8;
+    const size_t total = a.v.rows * a.v.per_row;
+    const uint64_t *bodies = reinterpret_cast<const uint64_t *>(a.v.msgs);
+    for (size_t c = (size_t)blockIdx.x * IO_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * IO_WAVES) {   // wave-uniform
+        const size_t r = c / a.v.per_row, s = c - r * a.v.per_row;
+        const size_t slot = a.v.row_slot ? a.v.row_slot[r] : r;
+        uint64_t *ct = a.v.cts + (slot * a.v.ct_stride + s) * (D + 1);
+        const uint64_t stream = stream_id(DOM_SENC_MASK, a.nonce0 + r * a.nonce_stride + s);
+        for (uint32_t b = lane; b < blocks; b += 64) {
+            uint64_t w[8];
+            chacha_block(a.mask_key.w, stream, b, w);
+            for (int i = 0; i < 8; i++) w[i] = fq_fold(w[i]);
+            uint64_t *p = ct + 8 * (size_t)b;
+            if (8 * b + 8 <= D) {
+                // D + 1 is odd: every other ciphertext starts on an odd word, and so do all of its blocks (the branch is uniform)
+                if (((uintptr_t)p & 15u) == 0) {
+                    for (int i = 0; i < 8; i += 2) *reinterpret_cast<u64x2 *>(p + i) = u64x2{w[i], w[i + 1]};
+                } else {
+                    p[0] = w[0];
+                    for (int i = 1; i < 7; i += 2) *reinterpret_cast<u64x2 *>(p + i) = u64x2{w[i], w[i + 1]};
+                    p[7] = w[7];
+                }
+            } else {
+                for (uint32_t i = 0; 8 * b + i < D; i++) p[i] = w[i];   // D % 8 != 0: the last, partial block
+            }
+        }
+        if (lane == 63) ct[D] = bodies[r * a.v.msg_stride + s];
+    }
+}
+
 static dim3 io_grid(size_t total) { return dim3((unsigned)std::min<size_t>((total + IO_WAVES - 1) / IO_WAVES, IO_MAX_BLOCKS)); }
 
 int dev_upload_secret(fbs_ctx *ctx) {
@@ -150,6 +228,38 @@ int dev_decrypt(const fbs_ctx *ctx, const IoView &v, hipStream_t stream) {
     a.D = ctx->D;
     a.two_p = 2ull * ctx->p.p_msg;
     hipLaunchKernelGGL(k_decrypt, io_grid(total), dim3(64 * IO_WAVES), 0, stream, a);
+    FBS_HIP(ctx, hipGetLastError());
+    return FBS_OK;
+}
+
+int dev_encrypt_seeded(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_bodies, hipStream_t stream) {
+    if (count == 0) return FBS_OK;
+    SeededEncArgs a{};
+    a.msgs = d_msgs;
+    a.bodies = d_bodies;
+    a.count = count;
+    a.nonce0 = nonce0;
+    a.mask_key = ctx->mask_key;
+    a.key = ctx->rkey;
+    a.sk = ctx->d_sk_bits;
+    a.D = ctx->D;
+    a.delta = 2 * ctx->delta_half;
+    a.sigma = ctx->p.sigma_glwe;
+    hipLaunchKernelGGL(k_encrypt_seeded, io_grid(count), dim3(64 * IO_WAVES), 0, stream, a);
+    FBS_HIP(ctx, hipGetLastError());
+    return FBS_OK;
+}
+
+int dev_expand_seeded(const fbs_ctx *ctx, const IoView &v, uint64_t nonce0, uint64_t nonce_stride, hipStream_t stream) {
+    const size_t total = v.rows * v.per_row;
+    if (total == 0) return FBS_OK;
+    ExpandArgs a{};
+    a.v = v;
+    a.nonce0 = nonce0;
+    a.nonce_stride = nonce_stride;
+    a.mask_key = ctx->mask_key;
+    a.D = ctx->D;
+    hipLaunchKernelGGL(k_expand_seeded, io_grid(total), dim3(64 * IO_WAVES), 0, stream, a);
     FBS_HIP(ctx, hipGetLastError());
     return FBS_OK;
 }

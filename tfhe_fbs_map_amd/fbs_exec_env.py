@@ -171,6 +171,12 @@ class ExecConfig:
         to be evaluated on, over how many GPUs -- recorded in `last_choice` with the launch sizes they imply; they do not move
         the parameter set (see `glwe_dims`: k = 2 is ahead at every launch size, so one GPU and every rank of a sharded run take
         the same set).  Leaves in `last_choice` the margin the program got and the failure probability that goes with it."""
+        prm, fuse = self.choose_params_fuse(env, p, samples, ranks)
+        return self.context_of(prm), fuse
+
+    def choose_params_fuse(self, env, p, samples=None, ranks=1):
+        """The pure part of `choose`: (parameter set, fuse) with `last_choice` recorded, and no context made (split.Client keys
+        its own context)."""
         from .params import bootstrap_cost
         stats = env.stats()
         fstats = env.fusion_stats(p) if self.fuse_tables is not False else None
@@ -192,7 +198,7 @@ class ExecConfig:
                                 p_error_per_bootstrap=per_bootstrap,
                                 p_error_per_sample=-math.expm1(nb_bootstrap * math.log1p(-min(per_bootstrap, 0.5))),
                                 relaxed=self.params is None and not self.reduced_noise and margin < self.min_margin - 1e-9)
-        return self.context_of(prm), fuse
+        return prm, fuse
 
     def program_for(self, ctx, low, fuse=False):
         """The loaded (device-resident) form of a lowered program, cached; the cache is bounded because every entry

@@ -1,0 +1,250 @@
+"""Client / server split: evaluate a program on a GPU that never holds the secret key.
+
+The `Client` picks the parameter set for a program exactly as `ExecConfig.choose` does, keys a context with
+`Context.keygen_seeded` and hands out a `ServerKey`: the public mask key and the bodies of the evaluation keys (include/
+fbs_exec.h, "seeded keys and inputs").  It encrypts inputs to bodies only (`EncryptedInputs`) and decrypts what comes back.
+The `Server` builds an evaluation-only context from the server key, lowers the program itself, expands the input bodies on
+the GPU and returns full output ciphertexts (`EncryptedOutputs`).  All three objects save to and load from `.npz` files with
+`allow_pickle=False`; none of them holds secret material.
+
+    client = Client(env, ExecConfig())
+    client.server_key().save("server_key.npz")             # -> the server, once
+    client.encrypt(inputs).save("inputs.npz")              # -> the server, per evaluation
+    server = Server(ServerKey.load("server_key.npz"))
+    server.run(env, EncryptedInputs.load("inputs.npz")).save("outputs.npz")
+    client.decrypt(EncryptedOutputs.load("outputs.npz"))  # == env.eval(inputs)
+"""
+from __future__ import annotations
+
+import hashlib
+from dataclasses import asdict, dataclass
+
+import numpy as np
+
+from .fbs_exec_env import ExecConfig, min_fbs_size, table_is_valid
+
+__all__ = ["ServerKey", "EncryptedInputs", "EncryptedOutputs", "Client", "Server", "FORMAT_VERSION", "mask_key_fingerprint",
+           "seeded_key_sizes"]
+
+FORMAT_VERSION = 1
+_PARAM_FIELDS = ("n", "log_n_poly", "k", "l_bsk", "beta_bsk", "t_ksk", "gamma_ksk", "p_msg", "sigma_lwe", "sigma_glwe",
+                 "bsk_group")
+
+
+def mask_key_fingerprint(mask_key: bytes) -> bytes:
+    """8 bytes that name a server key: what inputs and outputs carry so that nobody mixes key sets"""
+    return hashlib.sha256(b"tfhe_fbs_map_amd seeded mask key" + bytes(mask_key)).digest()[:8]
+
+
+def seeded_key_sizes(prm):
+    """(bootstrapping-key bodies, key-switching-key bodies) in words for a parameter set: fbs_seeded_key_sizes without a GPU"""
+    g = prm.n // 2 * 3 if prm.bsk_group == 2 else prm.n
+    return g * (prm.k + 1) * prm.l_bsk * prm.N, prm.k * prm.N * prm.t_ksk
+
+
+def _load_npz(path, kind):
+    with np.load(path, allow_pickle=False) as z:
+        d = {k: z[k] for k in z.files}
+    if str(d.get("kind", "")) != kind:
+        raise ValueError(f"{path} is not a saved {kind}")
+    if int(d.get("format_version", -1)) != FORMAT_VERSION:
+        raise ValueError(f"{path}: format version {d.get('format_version')} (this library reads {FORMAT_VERSION})")
+    return d
+
+
+def _fingerprint_of(d):
+    fp = np.asarray(d["fingerprint"], np.uint8)
+    if fp.shape != (8,):
+        raise ValueError("a fingerprint has 8 bytes")
+    return fp.tobytes()
+
+
+@dataclass
+class ServerKey:
+    """What a server needs to evaluate: the parameter set, whether programs load with shared rotations (`fuse_tables`), the
+    public mask key and the key bodies.  No secret."""
+    params: object
+    fuse_tables: bool
+    mask_key: bytes
+    bsk_bodies: np.ndarray
+    ksk_bodies: np.ndarray
+
+    def __post_init__(self):
+        self.mask_key = bytes(self.mask_key)
+        if len(self.mask_key) != 32:
+            raise ValueError("a mask key has 32 bytes")
+        self.bsk_bodies = np.ascontiguousarray(self.bsk_bodies, np.uint64).reshape(-1)
+        self.ksk_bodies = np.ascontiguousarray(self.ksk_bodies, np.uint64).reshape(-1)
+        want = seeded_key_sizes(self.params)
+        for a, w, name in zip((self.bsk_bodies, self.ksk_bodies), want, ("bsk_bodies", "ksk_bodies")):
+            if a.size != w:
+                raise ValueError(f"{name} has {a.size} words, the parameter set needs {w}")
+
+    @property
+    def fingerprint(self) -> bytes:
+        return mask_key_fingerprint(self.mask_key)
+
+    def save(self, path):
+        prm = asdict(self.params)
+        np.savez(path, kind=np.array("server_key"), format_version=np.array(FORMAT_VERSION),
+                 params=np.array([int(prm[f]) for f in _PARAM_FIELDS], np.int64), fuse_tables=np.array(bool(self.fuse_tables)),
+                 mask_key=np.frombuffer(self.mask_key, np.uint8), fingerprint=np.frombuffer(self.fingerprint, np.uint8),
+                 bsk_bodies=self.bsk_bodies, ksk_bodies=self.ksk_bodies)
+
+    @classmethod
+    def load(cls, path):
+        from ._native import Params
+        d = _load_npz(path, "server_key")
+        vals = np.asarray(d["params"], np.int64)
+        if vals.shape != (len(_PARAM_FIELDS),):
+            raise ValueError("parameter record has the wrong length")
+        prm = Params(**{f: int(v) for f, v in zip(_PARAM_FIELDS, vals)})
+        if d["bsk_bodies"].dtype != np.uint64 or d["ksk_bodies"].dtype != np.uint64:
+            raise ValueError("key bodies are uint64 words")
+        key = cls(prm, bool(d["fuse_tables"]), np.asarray(d["mask_key"], np.uint8).tobytes(), d["bsk_bodies"], d["ksk_bodies"])
+        if _fingerprint_of(d) != key.fingerprint:
+            raise ValueError("the saved fingerprint is not the mask key's")
+        return key
+
+
+@dataclass
+class EncryptedInputs:
+    """Seeded input ciphertexts of one evaluation: bodies [n_inputs][T]; input i, sample s on stream nonce0 + i*T + s."""
+    input_names: list
+    T: int
+    nonce0: int
+    bodies: np.ndarray
+    fingerprint: bytes
+
+    def save(self, path):
+        np.savez(path, kind=np.array("encrypted_inputs"), format_version=np.array(FORMAT_VERSION),
+                 input_names=np.array(list(self.input_names), dtype=str), T=np.array(self.T, np.int64),
+                 nonce0=np.array(self.nonce0, np.uint64), bodies=np.ascontiguousarray(self.bodies, np.uint64),
+                 fingerprint=np.frombuffer(self.fingerprint, np.uint8))
+
+    @classmethod
+    def load(cls, path):
+        d = _load_npz(path, "encrypted_inputs")
+        names = [str(n) for n in np.asarray(d["input_names"]).reshape(-1)]
+        T = int(d["T"])
+        bodies = np.asarray(d["bodies"])
+        if bodies.dtype != np.uint64 or bodies.shape != (len(names), T):
+            raise ValueError(f"bodies of shape {bodies.shape} for {len(names)} inputs of {T} samples")
+        return cls(names, T, int(d["nonce0"]), bodies, _fingerprint_of(d))
+
+
+@dataclass
+class EncryptedOutputs:
+    """Output ciphertexts of one evaluation: [n_outputs][T][D+1], as `Program.eval` returns them."""
+    output_names: list
+    T: int
+    cts: np.ndarray
+    fingerprint: bytes
+
+    def save(self, path):
+        np.savez(path, kind=np.array("encrypted_outputs"), format_version=np.array(FORMAT_VERSION),
+                 output_names=np.array(list(self.output_names), dtype=str), T=np.array(self.T, np.int64),
+                 cts=np.ascontiguousarray(self.cts, np.uint64), fingerprint=np.frombuffer(self.fingerprint, np.uint8))
+
+    @classmethod
+    def load(cls, path):
+        d = _load_npz(path, "encrypted_outputs")
+        names = [str(n) for n in np.asarray(d["output_names"]).reshape(-1)]
+        T = int(d["T"])
+        cts = np.asarray(d["cts"])
+        if cts.dtype != np.uint64 or cts.ndim != 3 or cts.shape[:2] != (len(names), T):
+            raise ValueError(f"ciphertexts of shape {cts.shape} for {len(names)} outputs of {T} samples")
+        return cls(names, T, cts, _fingerprint_of(d))
+
+
+class Client:
+    """Holds the secret.  Chooses (parameter set, fuse) for `env` with the rules of `ExecConfig.choose`, keys a context with
+    `keygen_seeded`, encrypts inputs to bodies and decrypts outputs."""
+
+    def __init__(self, env, config: ExecConfig | None = None):
+        from ._native import Context
+        self.env = env
+        self.config = cfg = config or ExecConfig()
+        self._low = low = env.lower()
+        p = cfg.fbs_size or min_fbs_size(low["tables"])
+        for t in low["tables"]:
+            if not table_is_valid(t, p):
+                raise ValueError("table %s cannot be evaluated by one bootstrap at fbs_size %d" % (t, p))
+        self.params, self.fuse_tables = cfg.choose_params_fuse(env, p)
+        self.ctx = Context(self.params, seed=cfg.key_seed(), device=cfg.device, keygen=False)
+        self.ctx.keygen_seeded()
+        self._server_key = None
+
+    def server_key(self) -> ServerKey:
+        if self._server_key is None:
+            self._server_key = ServerKey(self.params, self.fuse_tables, **self.ctx.export_seeded_keys())
+        return self._server_key
+
+    @property
+    def fingerprint(self) -> bytes:
+        return self.server_key().fingerprint
+
+    def encrypt(self, input_values, nonce0=None) -> EncryptedInputs:
+        """{input name: array-like of bits} (the contract of `LutExecEnv.eval`) -> seeded ciphertexts.  nonce0: the first
+        stream (None: the config's `nonce0`, or streams nobody has used)."""
+        names = self._low["input_names"]
+        cols = [np.asarray(input_values[n]).reshape(-1) for n in names]
+        T = max((len(c) for c in cols), default=1)
+        bits = np.stack([np.broadcast_to(c, (T,)) for c in cols]).astype(np.int64) if cols else np.zeros((0, T), np.int64)
+        assert bits.size == 0 or (bits.min() >= 0 and bits.max() <= 1), "inputs are bits"
+        bodies, first = self.ctx.encrypt_seeded(bits, nonce0=self.config.nonce0 if nonce0 is None else nonce0)
+        return EncryptedInputs(list(names), T, first, bodies.reshape(len(names), T), self.fingerprint)
+
+    def decrypt(self, outputs: EncryptedOutputs):
+        """-> exactly what `LutExecEnv.eval` returns: {output name: np.ndarray of ints}, constant outputs as python ints"""
+        low = self._low
+        if outputs.fingerprint != self.fingerprint:
+            raise ValueError("outputs were computed under another server key")
+        if list(outputs.output_names) != list(low["out_names"]):
+            raise ValueError("outputs belong to another program")
+        out = self.ctx.decrypt(outputs.cts) if outputs.cts.size else np.zeros(outputs.cts.shape[:2], np.int64)
+        result = {}
+        for k, name in enumerate(low["out_names"]):
+            w = low["out_wire"][k]
+            result[name] = (-1 - w) if w < 0 else out[k].astype(int)
+        return result
+
+
+class Server:
+    """Holds evaluation keys only (`Context.evaluation_only`).  Lowers each program itself and evaluates seeded inputs."""
+
+    def __init__(self, server_key: ServerKey, device: int = 0, max_programs: int = 8):
+        from ._native import Context
+        self.key = server_key
+        self.ctx = Context.evaluation_only(server_key.params, server_key.mask_key, server_key.bsk_bodies, server_key.ksk_bodies,
+                                           device=device)
+        self.max_programs = max_programs
+        self._programs = {}
+
+    def program_for(self, env):
+        from ._native import Program
+        low = env.lower()
+        hit = self._programs.get(id(low))
+        if hit is not None and hit[1] is low:
+            return hit[0], low
+        p = self.key.params.p_msg
+        for t in low["tables"]:
+            if not table_is_valid(t, p):
+                raise ValueError("table %s cannot be evaluated by one bootstrap at the server key's p = %d" % (t, p))
+        tv = self.ctx.tvset(low["tables"])
+        prog = Program(self.ctx, tv, len(low["input_names"]), low["kind"], low["arg0"], low["arg1"], low["const_coef"],
+                       low["term_coef"], low["term_src"], low["out_wire"], fuse_tables=self.key.fuse_tables)
+        prog._tv = tv
+        if len(self._programs) >= max(1, self.max_programs):
+            self._programs.pop(next(iter(self._programs)))[0].close()
+        self._programs[id(low)] = (prog, low)
+        return prog, low
+
+    def run(self, env, inputs: EncryptedInputs) -> EncryptedOutputs:
+        if inputs.fingerprint != self.key.fingerprint:
+            raise ValueError("inputs were encrypted for another server key")
+        prog, low = self.program_for(env)
+        if list(inputs.input_names) != list(low["input_names"]):
+            raise ValueError("inputs belong to another program")
+        cts = prog.eval_seeded(inputs.bodies, inputs.T, inputs.nonce0)
+        return EncryptedOutputs(list(low["out_names"]), inputs.T, cts, self.key.fingerprint)
