@@ -75,6 +75,8 @@ def test_crypto_host_code_and_the_oracle_under_the_sanitizers(harness):
         r = subprocess.run(cmd, capture_output=True, text=True, env=ENV, timeout=600)
         assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stdout[-500:] + r.stderr[-3000:]
         assert r.stdout.count(" ok") >= 3
+        if cmd[0] == host:   # fbs_import_keys's check on a secret of exactly n words at two key bits per step (k = 1, l = 1)
+            assert "import check n=12 N=256 k=1 l=1 group=2 ok" in r.stdout, r.stdout
 
 
 def test_the_loader_plan_on_every_fixture_under_the_sanitizers(harness):

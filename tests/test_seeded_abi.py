@@ -1,6 +1,6 @@
 """The seeded path without a GPU: the new entries of include/fbs_exec.h are declared, exported and bound; the seeded streams
 have domains of their own; the split's files round-trip, refuse what does not fit their parameters and hold no secret; and the
-host code of the seeded keys and inputs passes tests/c_seeded/seeded_harness.cpp under AddressSanitizer and UBSan."""
+host code of the seeded keys and inputs passes the seeded mode of tests/c/host_harness.cpp under AddressSanitizer and UBSan."""
 import ctypes
 import os
 import re
@@ -14,7 +14,6 @@ CSRC = os.path.join(ROOT, "tfhe_fbs_map_amd", "csrc")
 ENTRIES = ("fbs_keygen_seeded", "fbs_seeded_key_sizes", "fbs_export_seeded_keys", "fbs_import_seeded_keys", "fbs_encrypt_seeded",
            "fbs_encrypt_seeded_fresh", "fbs_encrypt_seeded_dev", "fbs_encrypt_seeded_fresh_dev", "fbs_expand_seeded",
            "fbs_expand_seeded_dev", "fbs_eval_seeded")
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]   # tests/c/Makefile
 ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
 
 
@@ -138,13 +137,10 @@ def test_encrypted_inputs_and_outputs_round_trip(tmp_path):
         EncryptedOutputs.load(p_in)
 
 
-def test_seeded_host_code_under_the_sanitizers(tmp_path):
-    exe = str(tmp_path / "seeded_harness")
-    srcs = [os.path.join(ROOT, "tests", "c_seeded", "seeded_harness.cpp")] + \
-           [os.path.join(CSRC, f) for f in ("fbs_plan.cpp", "fbs_host.cpp", "fbs_select.cpp")]
-    subprocess.check_call(["g++", "-std=c++17", *SAN, "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-pthread", "-o", exe,
-                           *srcs], timeout=600)
-    r = subprocess.run([exe], capture_output=True, text=True, env=ENV, timeout=600)
+def test_seeded_host_code_under_the_sanitizers():
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "c"), "asan"], timeout=600)
+    r = subprocess.run([os.path.join(ROOT, "tests", "c", "build", "host_harness"), "seeded"], capture_output=True, text=True, env=ENV,
+                       timeout=600)
     assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stdout[-2000:] + r.stderr[-3000:]
     ok = [ln for ln in r.stdout.splitlines() if ln.endswith(" ok")]
     assert len(ok) == 6, r.stdout

@@ -13,17 +13,8 @@
 
 using namespace fbs;
 
-static thread_local std::string g_create_error;
 // what every entry that needs the secret keys says on a context made by fbs_import_seeded_keys
 static const char *const EVAL_ONLY = "this context holds evaluation keys only";
-
-namespace fbs {
-int set_error(const fbs_ctx *ctx, int code, const std::string &msg) {
-    if (ctx) ctx->err = msg;
-    else g_create_error = msg;
-    return code;
-}
-}  // namespace fbs
 
 // ---------------------------------------------------------------------------------------------
 // program representation
@@ -87,7 +78,7 @@ static uint64_t coef_bits(int64_t c) {
     return u;
 }
 
-static hipStream_t pick(fbs_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+static hipStream_t pick(const fbs_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 
 // Scratch is grown on demand, and growing it BLOCKS (the old buffers may still be read by queued kernels): a host that wants
 // its *_dev calls to be nothing but kernel launches sizes everything up front with fbs_ctx_reserve.
@@ -111,29 +102,24 @@ static int ensure_ms(fbs_ctx *ctx, size_t count) {
     return FBS_OK;
 }
 
-static int ensure_acc(fbs_ctx *ctx, size_t rows) {
-    if (rows <= ctx->acc_capacity) return FBS_OK;
-    ctx->scratch_growths++;
-    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));
-    if (ctx->d_acc) (void)hipFree(ctx->d_acc);
-    ctx->d_acc = nullptr;
-    ctx->acc_capacity = 0;
-    FBS_HIP(ctx, hipMalloc(&ctx->d_acc, rows * (size_t)(ctx->p.k + 1) * ctx->N * 8));   // a row = a whole GLWE accumulator
-    ctx->acc_capacity = rows;
+// one scratch buffer of `count` elements of `bytes` each; `counted`: a growth shows in scratch_growths
+template <typename T>
+static int grow(fbs_ctx *ctx, T *&buf, size_t &capacity, size_t count, size_t bytes, bool counted) {
+    if (count <= capacity) return FBS_OK;
+    if (counted) ctx->scratch_growths++;
+    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));   // kernels may still read the old buffer
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    capacity = 0;
+    FBS_HIP(ctx, hipMalloc(&buf, count * bytes));
+    capacity = count;
     return FBS_OK;
 }
-
-static int ensure_wires(fbs_ctx *ctx, size_t words) {
-    if (words <= ctx->wires_capacity) return FBS_OK;
-    ctx->scratch_growths++;
-    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));
-    if (ctx->d_wires) (void)hipFree(ctx->d_wires);
-    ctx->d_wires = nullptr;
-    ctx->wires_capacity = 0;
-    FBS_HIP(ctx, hipMalloc(&ctx->d_wires, words * 8));
-    ctx->wires_capacity = words;
-    return FBS_OK;
+static int ensure_acc(fbs_ctx *ctx, size_t rows) {   // a row = a whole GLWE accumulator
+    return grow(ctx, ctx->d_acc, ctx->acc_capacity, rows, (size_t)(ctx->p.k + 1) * ctx->N * 8, true);
 }
+static int ensure_wires(fbs_ctx *ctx, size_t words) { return grow(ctx, ctx->d_wires, ctx->wires_capacity, words, 8, true); }
+static int ensure_io_msgs(fbs_ctx *ctx, size_t words) { return grow(ctx, ctx->d_io_msgs, ctx->io_msgs_capacity, words, 8, true); }
 
 // Cross-stream ordering of the per-context scratch (d_ms, d_idx, d_wires): a call on stream `s` first waits for the last
 // call that used the scratch on ANOTHER stream; calls on one stream are ordered by the stream itself.
@@ -297,7 +283,7 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
 } catch (...) {   // (nothing here allocates; the promise of the ABI is kept anyway)
 }
 
-const char *fbs_last_error(const fbs_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
+const char *fbs_last_error(const fbs_ctx *ctx) { return ctx ? ctx->err.c_str() : create_error(); }
 const char *fbs_device_info(const fbs_ctx *ctx) { return ctx ? ctx->devinfo.c_str() : ""; }
 
 // ---------------------------------------------------------------------------------------------
@@ -334,57 +320,6 @@ int fbs_export_keys(const fbs_ctx *ctx, uint64_t *sk_lwe, uint64_t *sk_glwe, uin
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
-// Do the evaluation keys decrypt under the secrets they came with?  A handful of GGSW samples (every row) and key-switching rows,
-// each phase compared with what the layout of fbs_key_sizes says it encrypts: a key in another sample / row / column order has
-// uniform phases and fails here instead of bootstrapping to garbage.  Tolerance: 16 standard deviations of the set's noise.
-static const char *imported_keys_mismatch(const fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glwe, const uint64_t *bsk,
-                                          const uint64_t *ksk) {
-    const fbs_params &p = ctx->p;
-    const uint32_t N = ctx->N, D = ctx->D, n = p.n, k = p.k, l = p.l_bsk, t = p.t_ksk, rows = ctx->rows;
-    auto far = [](uint64_t got, uint64_t want, double tol) { return std::fabs(fq_centered(fq_sub(got, want))) > tol; };
-    const double tol_glwe = 1024.0 + 16.0 * (double)p.sigma_glwe, tol_lwe = 1024.0 + 16.0 * (double)p.sigma_lwe;
-    std::vector<size_t> samples = {0, 1, 2, ctx->n_ggsw / 2, ctx->n_ggsw - 1};
-    std::vector<uint64_t> phase(N);
-    for (size_t g : samples) {
-        if (g >= ctx->n_ggsw) continue;
-        uint64_t bit = sk_lwe[g];
-        if (ctx->group == 2) {
-            const uint64_t s0 = sk_lwe[2 * (g / 3)], s1 = sk_lwe[2 * (g / 3) + 1];
-            bit = g % 3 == 0 ? (s0 & (1 - s1)) : g % 3 == 1 ? ((1 - s0) & s1) : (s0 & s1);
-        }
-        for (uint32_t rr = 0; rr < rows; rr++) {
-            const uint32_t comp = rr / l, lv = rr % l;
-            const uint64_t *row = bsk + (g * rows + rr) * (size_t)(k + 1) * N;
-            for (uint32_t j = 0; j < N; j++) phase[j] = row[(size_t)k * N + j];
-            for (uint32_t c = 0; c < k; c++)                            // phase -= A_c * S_c (negacyclic, binary S)
-                for (uint32_t sh = 0; sh < N; sh++) {
-                    if (!sk_glwe[(size_t)c * N + sh]) continue;
-                    const uint64_t *a = row + (size_t)c * N;
-                    for (uint32_t j = 0; j < N - sh; j++) phase[j + sh] = fq_sub(phase[j + sh], a[j]);
-                    for (uint32_t j = N - sh; j < N; j++) phase[j + sh - N] = fq_add(phase[j + sh - N], a[j]);
-                }
-            // row (comp, lv) = GLWE(0) + bit g_lv on component comp: the phase is bit g_lv at X^0 (body row), -bit g_lv S_comp (mask rows)
-            for (uint32_t j = 0; j < N; j++) {
-                uint64_t want = 0;
-                if (bit && comp == k && j == 0) want = ctx->g[lv];
-                if (bit && comp < k && sk_glwe[(size_t)comp * N + j]) want = fq_sub(0, ctx->g[lv]);
-                if (far(phase[j], want, tol_glwe)) return "bootstrapping key does not decrypt under the supplied secrets (sample / row / column order of fbs_key_sizes?)";
-            }
-        }
-    }
-    const size_t ksk_rows = (size_t)D * t;
-    for (size_t r : {(size_t)0, (size_t)1, (size_t)2, (size_t)3, ksk_rows / 2, ksk_rows - 4, ksk_rows - 3, ksk_rows - 2, ksk_rows - 1}) {
-        if (r >= ksk_rows) continue;
-        const uint32_t j = (uint32_t)(r / t), v = (uint32_t)(r % t);
-        const uint64_t *row = ksk + r * (size_t)(n + 1);
-        uint64_t ph = row[n];
-        for (uint32_t i = 0; i < n; i++)
-            if (sk_lwe[i]) ph = fq_sub(ph, row[i]);
-        if (far(ph, sk_glwe[j] ? ctx->h[v] : 0, tol_lwe)) return "key-switching key does not decrypt under the supplied secrets (row order [kN][t][n+1]?)";
-    }
-    return nullptr;
-}
-
 int fbs_import_keys(fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glwe, const uint64_t *bsk, const uint64_t *ksk) try {
     if (!ctx) return FBS_E_INVALID;
     if (!sk_lwe || !sk_glwe || !bsk || !ksk) return set_error(ctx, FBS_E_INVALID, "null argument");
@@ -418,7 +353,7 @@ int fbs_import_keys(fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glw
 // Streams [first, first + count) of [2^55, 2^56) that nobody has used, for every entry that takes fresh streams.  The range is
 // reserved atomically: two threads encrypting on one context never share a stream (the bound is checked BEFORE the counter
 // moves, so a refused call leaves it where it was).
-static int reserve_fresh(fbs_ctx *ctx, size_t count, uint64_t *first_out) {
+static int reserve_fresh(const fbs_ctx *ctx, size_t count, uint64_t *first_out) {
     uint64_t first = ctx->next_nonce.load(std::memory_order_relaxed);
     do {
         if (count > (1ull << 56) || first + count > (1ull << 56)) return set_error(ctx, FBS_E_STATE, "encryption streams of this context are used up");
@@ -431,41 +366,55 @@ static int check_nonces(const fbs_ctx *ctx, uint64_t nonce0, size_t count) {
     if (nonce0 >= (1ull << 55) || count > (1ull << 55) - nonce0) return set_error(ctx, FBS_E_INVALID, "nonce0 + count must stay below 2^55");
     return FBS_OK;
 }
+// seeded streams may be any the full entries may take, fresh ones included
+static int check_seeded_streams(const fbs_ctx *ctx, uint64_t nonce0, size_t count) {
+    if (nonce0 >= (1ull << 56) || count > (1ull << 56) - nonce0) return set_error(ctx, FBS_E_INVALID, "nonce0 + count must stay below 2^56");
+    return FBS_OK;
+}
+// count ciphertexts of D + 1 words: more than fit in a size_t is refused before anything is launched
+static int check_ct_words(const fbs_ctx *ctx, size_t count) {
+    if (count > SIZE_MAX / 8 / (ctx->D + 1)) return set_error(ctx, FBS_E_INVALID, "count * (D + 1) words overflow");
+    return FBS_OK;
+}
+
+// What the encrypt / decrypt / expand entries check, in this order: the buffers (a null one with count > 0 is FBS_E_INVALID
+// without a message), the keys, the secret (IO_SECRET), the explicit streams [*first, *first + count) (IO_BELOW_2_55 or
+// IO_BELOW_2_56), count * (D + 1) words (IO_CT_WORDS), and last a fresh range (IO_FRESH: reserved into *first), so that a
+// refused call never moves next_nonce.
+enum : unsigned { IO_SECRET = 1, IO_BELOW_2_55 = 2, IO_BELOW_2_56 = 4, IO_FRESH = 8, IO_CT_WORDS = 16 };
+static int io_prologue(const fbs_ctx *ctx, const void *src, const void *dst, size_t count, unsigned checks, uint64_t *first) {
+    if (!ctx || (count && (!src || !dst))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if ((checks & IO_SECRET) && ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    int rc = FBS_OK;
+    if ((checks & IO_BELOW_2_55) && (rc = check_nonces(ctx, *first, count))) return rc;
+    if ((checks & IO_BELOW_2_56) && (rc = check_seeded_streams(ctx, *first, count))) return rc;
+    if ((checks & IO_CT_WORDS) && (rc = check_ct_words(ctx, count))) return rc;
+    if (checks & IO_FRESH) rc = reserve_fresh(ctx, count, first);
+    return rc;
+}
 
 int fbs_encrypt_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *cts, uint64_t *nonce0) try {
-    if (!ctx || (count && (!msgs || !cts))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     uint64_t first = 0;
-    if (int rc = reserve_fresh(ctx, count, &first)) return rc;
+    if (int rc = io_prologue(ctx, msgs, cts, count, IO_SECRET | IO_FRESH, &first)) return rc;
     if (nonce0) *nonce0 = first;
     host_encrypt(ctx, msgs, count, first, cts);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 int fbs_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *cts) try {
-    if (!ctx || (count && (!msgs || !cts))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    if (int rc = check_nonces(ctx, nonce0, count)) return rc;
+    if (int rc = io_prologue(ctx, msgs, cts, count, IO_SECRET | IO_BELOW_2_55, &nonce0)) return rc;
     host_encrypt(ctx, msgs, count, nonce0, cts);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 int fbs_decrypt(const fbs_ctx *ctx, const uint64_t *cts, size_t count, int64_t *msgs) try {
-    if (!ctx || (count && (!msgs || !cts))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    if (int rc = io_prologue(ctx, cts, msgs, count, IO_SECRET, nullptr)) return rc;
     host_decrypt(ctx, cts, count, msgs);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 // ---- the same on device buffers --------------------------------------------------------------
-// count ciphertexts of D + 1 words: more than fit in a size_t is refused before anything is launched
-static int check_ct_words(const fbs_ctx *ctx, size_t count) {
-    if (count > SIZE_MAX / 8 / (ctx->D + 1)) return set_error(ctx, FBS_E_INVALID, "count * (D + 1) words overflow");
-    return FBS_OK;
-}
 static IoView plain_rows(const int64_t *msgs, const uint64_t *cts, size_t count) {
     IoView v{};
     v.msgs = const_cast<int64_t *>(msgs);
@@ -478,23 +427,15 @@ static IoView plain_rows(const int64_t *msgs, const uint64_t *cts, size_t count)
 }
 
 int fbs_encrypt_dev(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_cts, void *stream) try {
-    if (!ctx || (count && (!d_msgs || !d_cts))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    int rc;
-    if ((rc = check_nonces(ctx, nonce0, count)) || (rc = check_ct_words(ctx, count))) return rc;
+    if (int rc = io_prologue(ctx, d_msgs, d_cts, count, IO_SECRET | IO_BELOW_2_55 | IO_CT_WORDS, &nonce0)) return rc;
     if (count == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
-    return dev_encrypt(ctx, plain_rows(d_msgs, d_cts, count), nonce0, 0, stream ? (hipStream_t)stream : ctx->stream);
+    return dev_encrypt(ctx, plain_rows(d_msgs, d_cts, count), nonce0, 0, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
 int fbs_encrypt_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t *d_cts, uint64_t *nonce0, void *stream) try {
-    if (!ctx || (count && (!d_msgs || !d_cts))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    int rc;
     uint64_t first = 0;
-    if ((rc = check_ct_words(ctx, count)) || (rc = reserve_fresh(ctx, count, &first))) return rc;
+    if (int rc = io_prologue(ctx, d_msgs, d_cts, count, IO_SECRET | IO_CT_WORDS | IO_FRESH, &first)) return rc;
     if (nonce0) *nonce0 = first;
     if (count == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
@@ -502,13 +443,10 @@ int fbs_encrypt_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uin
 } FBS_API_CATCH(ctx)
 
 int fbs_decrypt_dev(const fbs_ctx *ctx, const uint64_t *d_cts, size_t count, int64_t *d_msgs, void *stream) try {
-    if (!ctx || (count && (!d_msgs || !d_cts))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    if (int rc = check_ct_words(ctx, count)) return rc;
+    if (int rc = io_prologue(ctx, d_cts, d_msgs, count, IO_SECRET | IO_CT_WORDS, nullptr)) return rc;
     if (count == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
-    return dev_decrypt(ctx, plain_rows(d_msgs, d_cts, count), stream ? (hipStream_t)stream : ctx->stream);
+    return dev_decrypt(ctx, plain_rows(d_msgs, d_cts, count), pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
 // ---- seeded keys and inputs: masks under a public key, only bodies travel ----------------------
@@ -585,73 +523,50 @@ int fbs_import_seeded_keys(fbs_ctx *ctx, const uint8_t mask_key[32], const uint6
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
-// seeded streams may be any the full entries may take, fresh ones included
-static int check_seeded_streams(const fbs_ctx *ctx, uint64_t nonce0, size_t count) {
-    if (nonce0 >= (1ull << 56) || count > (1ull << 56) - nonce0) return set_error(ctx, FBS_E_INVALID, "nonce0 + count must stay below 2^56");
-    return FBS_OK;
-}
-
 int fbs_encrypt_seeded(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *bodies) try {
-    if (!ctx || (count && (!msgs || !bodies))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    if (int rc = check_nonces(ctx, nonce0, count)) return rc;
+    if (int rc = io_prologue(ctx, msgs, bodies, count, IO_SECRET | IO_BELOW_2_55, &nonce0)) return rc;
     host_encrypt_seeded(ctx, msgs, count, nonce0, bodies);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 int fbs_encrypt_seeded_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *bodies, uint64_t *nonce0) try {
-    if (!ctx || (count && (!msgs || !bodies))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     uint64_t first = 0;
-    if (int rc = reserve_fresh(ctx, count, &first)) return rc;
+    if (int rc = io_prologue(ctx, msgs, bodies, count, IO_SECRET | IO_FRESH, &first)) return rc;
     if (nonce0) *nonce0 = first;
     host_encrypt_seeded(ctx, msgs, count, first, bodies);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 int fbs_encrypt_seeded_dev(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_bodies, void *stream) try {
-    if (!ctx || (count && (!d_msgs || !d_bodies))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    if (int rc = check_nonces(ctx, nonce0, count)) return rc;
+    if (int rc = io_prologue(ctx, d_msgs, d_bodies, count, IO_SECRET | IO_BELOW_2_55, &nonce0)) return rc;
     if (count == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
-    return dev_encrypt_seeded(ctx, d_msgs, count, nonce0, d_bodies, stream ? (hipStream_t)stream : ctx->stream);
+    return dev_encrypt_seeded(ctx, d_msgs, count, nonce0, d_bodies, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
 int fbs_encrypt_seeded_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t *d_bodies, uint64_t *nonce0, void *stream) try {
-    if (!ctx || (count && (!d_msgs || !d_bodies))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     uint64_t first = 0;
-    if (int rc = reserve_fresh(ctx, count, &first)) return rc;
+    if (int rc = io_prologue(ctx, d_msgs, d_bodies, count, IO_SECRET | IO_FRESH, &first)) return rc;
     if (nonce0) *nonce0 = first;
     if (count == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     return dev_encrypt_seeded(ctx, d_msgs, count, first, d_bodies, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
+// (no secret needed: these run on evaluation-only contexts)
 int fbs_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count, uint64_t nonce0, uint64_t *cts) try {
-    if (!ctx || (count && (!bodies || !cts))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    int rc;
-    if ((rc = check_seeded_streams(ctx, nonce0, count)) || (rc = check_ct_words(ctx, count))) return rc;
+    if (int rc = io_prologue(ctx, bodies, cts, count, IO_BELOW_2_56 | IO_CT_WORDS, &nonce0)) return rc;
     host_expand_seeded(ctx, bodies, count, nonce0, cts);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 int fbs_expand_seeded_dev(const fbs_ctx *ctx, const uint64_t *d_bodies, size_t count, uint64_t nonce0, uint64_t *d_cts, void *stream) try {
-    if (!ctx || (count && (!d_bodies || !d_cts))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    int rc;
-    if ((rc = check_seeded_streams(ctx, nonce0, count)) || (rc = check_ct_words(ctx, count))) return rc;
+    if (int rc = io_prologue(ctx, d_bodies, d_cts, count, IO_BELOW_2_56 | IO_CT_WORDS, &nonce0)) return rc;
     if (count == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     IoView v = plain_rows(nullptr, d_cts, count);
     v.msgs = reinterpret_cast<int64_t *>(const_cast<uint64_t *>(d_bodies));
-    return dev_expand_seeded(ctx, v, nonce0, 0, stream ? (hipStream_t)stream : ctx->stream);
+    return dev_expand_seeded(ctx, v, nonce0, 0, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
 // ---------------------------------------------------------------------------------------------
@@ -797,16 +712,8 @@ int fbs_bootstrap_batch(fbs_ctx *ctx, const fbs_tvset *tv, const uint64_t *cts_i
 // per-context buffer and waits for the copy; hosts that step a loaded program use the fbs_level_* calls below,
 // whose index arrays were uploaded once by fbs_program_load)
 // ---------------------------------------------------------------------------------------------
-static int ensure_idx(fbs_ctx *ctx, size_t words) {
-    if (words <= ctx->idx_capacity) return FBS_OK;
-    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));
-    if (ctx->d_idx) (void)hipFree(ctx->d_idx);
-    ctx->d_idx = nullptr;
-    ctx->idx_capacity = 0;
-    size_t cap = std::max<size_t>(words, 1 << 16);
-    FBS_HIP(ctx, hipMalloc(&ctx->d_idx, cap * 4));
-    ctx->idx_capacity = cap;
-    return FBS_OK;
+static int ensure_idx(fbs_ctx *ctx, size_t words) {   // (not counted in scratch_growths)
+    return words <= ctx->idx_capacity ? FBS_OK : grow(ctx, ctx->d_idx, ctx->idx_capacity, std::max<size_t>(words, 1 << 16), 4, false);
 }
 
 int fbs_lincomb_dev(fbs_ctx *ctx, uint64_t *d_wires, size_t T, uint32_t n_out, const uint32_t *dst, const uint32_t *term_off,
@@ -1013,10 +920,14 @@ int fbs_program_io_slots(const fbs_prog *prog, uint32_t *in_slot, int64_t *out_s
 } FBS_API_CATCH(prog ? prog->ctx : nullptr)
 
 // ---- one level at a time, device-resident wires, nothing but kernel launches on `stream` ------------------------
-static int check_level_call(fbs_ctx *ctx, const fbs_prog *prog, const uint64_t *d_wires, size_t T, size_t s_begin, size_t s_count) {
+static int check_prog(fbs_ctx *ctx, const fbs_prog *prog) {
     int rc = check_ready(ctx, prog ? prog->tv : nullptr);
     if (rc != FBS_OK) return rc;
     if (!prog || prog->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "program belongs to another context");
+    return FBS_OK;
+}
+static int check_level_call(fbs_ctx *ctx, const fbs_prog *prog, const uint64_t *d_wires, size_t T, size_t s_begin, size_t s_count) {
+    if (int rc = check_prog(ctx, prog)) return rc;
     if (!d_wires) return set_error(ctx, FBS_E_INVALID, "null argument");
     if (s_begin + s_count > T) return set_error(ctx, FBS_E_INVALID, "bad sample range");
     return FBS_OK;
@@ -1142,87 +1053,100 @@ static int reserve_wires(fbs_ctx *ctx, const fbs_prog *prog, size_t T, size_t *c
 
 static uint64_t trivial_body(const fbs_ctx *ctx, int64_t out_slot) { return fq_mul(fq_from_i64(-1 - out_slot), 2 * ctx->delta_half); }
 
-int fbs_eval_dev(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *d_in, size_t T, uint64_t *d_out, void *stream) try {
-    int rc = check_ready(ctx, prog ? prog->tv : nullptr);
-    if (rc != FBS_OK) return rc;
-    if (!prog || prog->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "program belongs to another context");
-    if (T == 0) return FBS_OK;
-    if ((prog->n_inputs && !d_in) || (prog->n_outputs && !d_out)) return set_error(ctx, FBS_E_INVALID, "null argument");
+// ---- the four program evaluations: one chunk loop, each entry its checks, its scratch and its two stages -------------------
+// what every evaluation checks first: the keys, the program's owner, the buffers of a call with samples
+static int check_eval(fbs_ctx *ctx, const fbs_prog *prog, const void *in, size_t T, const void *out) {
+    if (int rc = check_prog(ctx, prog)) return rc;
+    if (T && ((prog->n_inputs && !in) || (prog->n_outputs && !out))) return set_error(ctx, FBS_E_INVALID, "null argument");
+    return FBS_OK;
+}
+
+static int sync_stream(fbs_ctx *ctx, hipStream_t s) {
+    FBS_HIP(ctx, hipStreamSynchronize(s));
+    return FBS_OK;
+}
+
+// samples [s0, s0 + tc) of the chunk: put the inputs into their wire slots, or take the outputs out of theirs
+using ChunkStage = std::function<int(size_t s0, size_t tc)>;
+
+// Chunks of Tc samples (reserve_wires) on stream `s`: load, run_levels, store.  `sync`: the host-facing entries wait for each
+// chunk (pageable memory), then run `post` on it when given; fbs_eval_dev only launches.  A failure inside the loop puts the
+// scratch back (scratch_fail).
+static int eval_chunks(fbs_ctx *ctx, const fbs_prog *prog, size_t T, size_t Tc, hipStream_t s, bool sync, const ChunkStage &load,
+                       const ChunkStage &store, const ChunkStage &post = nullptr) {
+    int rc;
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    for (size_t s0 = 0; s0 < T; s0 += Tc) {
+        const size_t tc = std::min(Tc, T - s0);
+        if ((rc = load(s0, tc)) || (rc = run_levels(ctx, prog, ctx->d_wires, Tc, tc, s)) || (rc = store(s0, tc))) return scratch_fail(ctx, s, rc);
+        if (sync && ((rc = sync_stream(ctx, s)) || (post && (rc = post(s0, tc))))) return scratch_fail(ctx, s, rc);
+    }
+    return scratch_done(ctx, s);
+}
+
+// ciphertexts [n_inputs][T][D + 1] -> the input slots (`kind`: from the host or the device)
+static int load_cts(fbs_ctx *ctx, const fbs_prog *prog, const uint64_t *in, size_t T, size_t Tc, size_t s0, size_t tc, hipMemcpyKind kind,
+                    hipStream_t s) {
     const size_t ctw = ctx->D + 1;
+    for (uint32_t i = 0; i < prog->n_inputs; i++)
+        FBS_HIP(ctx, hipMemcpyAsync(ctx->d_wires + (size_t)prog->in_slot[i] * Tc * ctw, in + ((size_t)i * T + s0) * ctw, tc * ctw * 8, kind, s));
+    return FBS_OK;
+}
+
+// the output slots -> host ciphertexts [n_outputs][T][D + 1]; a constant output as its trivial ciphertext
+static int store_host_cts(fbs_ctx *ctx, const fbs_prog *prog, uint64_t *out, size_t T, size_t Tc, size_t s0, size_t tc, hipStream_t s) {
+    const size_t ctw = ctx->D + 1;
+    for (uint32_t o = 0; o < prog->n_outputs; o++) {
+        uint64_t *dst = out + ((size_t)o * T + s0) * ctw;
+        const int64_t w = prog->out_slot[o];
+        if (w >= 0) {
+            FBS_HIP(ctx, hipMemcpyAsync(dst, ctx->d_wires + (size_t)w * Tc * ctw, tc * ctw * 8, hipMemcpyDeviceToHost, s));
+        } else {
+            const uint64_t body = trivial_body(ctx, w);
+            for (size_t q = 0; q < tc; q++) {
+                std::memset(dst + q * ctw, 0, ctx->D * 8);
+                dst[q * ctw + ctx->D] = body;
+            }
+        }
+    }
+    return FBS_OK;
+}
+
+int fbs_eval_dev(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *d_in, size_t T, uint64_t *d_out, void *stream) try {
+    int rc = check_eval(ctx, prog, d_in, T, d_out);
+    if (rc != FBS_OK || T == 0) return rc;
     hipStream_t s = pick(ctx, stream);
     size_t Tc = 0;
     if ((rc = reserve_wires(ctx, prog, T, &Tc)) != FBS_OK) return rc;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    for (size_t s0 = 0; s0 < T; s0 += Tc) {
-        const size_t tc = std::min(Tc, T - s0);
-        for (uint32_t i = 0; i < prog->n_inputs; i++)
-            FBS_HIP(ctx, hipMemcpyAsync(ctx->d_wires + (size_t)prog->in_slot[i] * Tc * ctw, d_in + ((size_t)i * T + s0) * ctw, tc * ctw * 8,
-                                        hipMemcpyDeviceToDevice, s));
-        if ((rc = run_levels(ctx, prog, ctx->d_wires, Tc, tc, s)) != FBS_OK) return rc;
+    auto load = [&](size_t s0, size_t tc) { return load_cts(ctx, prog, d_in, T, Tc, s0, tc, hipMemcpyDeviceToDevice, s); };
+    auto store = [&](size_t s0, size_t tc) {
         for (uint32_t o = 0; o < prog->n_outputs; o++) {
             const int64_t w = prog->out_slot[o];
-            rc = dev_copy_out(ctx, ctx->d_wires, Tc, 0, tc, w, w < 0 ? trivial_body(ctx, w) : 0, d_out + ((size_t)o * T + s0) * ctw, s);
-            if (rc != FBS_OK) return rc;
+            uint64_t *dst = d_out + ((size_t)o * T + s0) * (ctx->D + 1);
+            if (int rc = dev_copy_out(ctx, ctx->d_wires, Tc, 0, tc, w, w < 0 ? trivial_body(ctx, w) : 0, dst, s)) return rc;
         }
-    }
-    return scratch_done(ctx, s);
+        return FBS_OK;
+    };
+    return eval_chunks(ctx, prog, T, Tc, s, false, load, store);
 } FBS_API_CATCH(ctx)
 
 int fbs_eval(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *in_cts, size_t T, uint64_t *out_cts) try {
-    int rc = check_ready(ctx, prog ? prog->tv : nullptr);
-    if (rc != FBS_OK) return rc;
-    if (!prog || prog->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "program belongs to another context");
-    if (T == 0) return FBS_OK;
-    if ((prog->n_inputs && !in_cts) || (prog->n_outputs && !out_cts)) return set_error(ctx, FBS_E_INVALID, "null argument");
-    const size_t ctw = ctx->D + 1;
+    int rc = check_eval(ctx, prog, in_cts, T, out_cts);
+    if (rc != FBS_OK || T == 0) return rc;
     hipStream_t s = ctx->stream;
     size_t Tc = 0;
     if ((rc = reserve_wires(ctx, prog, T, &Tc)) != FBS_OK) return rc;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    for (size_t s0 = 0; s0 < T; s0 += Tc) {
-        const size_t tc = std::min(Tc, T - s0);
-        for (uint32_t i = 0; i < prog->n_inputs; i++)
-            FBS_HIP(ctx, hipMemcpyAsync(ctx->d_wires + (size_t)prog->in_slot[i] * Tc * ctw, in_cts + ((size_t)i * T + s0) * ctw, tc * ctw * 8,
-                                        hipMemcpyHostToDevice, s));
-        if ((rc = run_levels(ctx, prog, ctx->d_wires, Tc, tc, s)) != FBS_OK) return rc;
-        for (uint32_t o = 0; o < prog->n_outputs; o++) {
-            uint64_t *dst = out_cts + ((size_t)o * T + s0) * ctw;
-            const int64_t w = prog->out_slot[o];
-            if (w >= 0) {
-                FBS_HIP(ctx, hipMemcpyAsync(dst, ctx->d_wires + (size_t)w * Tc * ctw, tc * ctw * 8, hipMemcpyDeviceToHost, s));
-            } else {
-                const uint64_t body = trivial_body(ctx, w);   // trivial ciphertext of the constant
-                for (size_t q = 0; q < tc; q++) {
-                    std::memset(dst + q * ctw, 0, ctx->D * 8);
-                    dst[q * ctw + ctx->D] = body;
-                }
-            }
-        }
-        FBS_HIP(ctx, hipStreamSynchronize(s));
-    }
-    return scratch_done(ctx, s);
+    auto load = [&](size_t s0, size_t tc) { return load_cts(ctx, prog, in_cts, T, Tc, s0, tc, hipMemcpyHostToDevice, s); };
+    auto store = [&](size_t s0, size_t tc) { return store_host_cts(ctx, prog, out_cts, T, Tc, s0, tc, s); };
+    return eval_chunks(ctx, prog, T, Tc, s, true, load, store);
 } FBS_API_CATCH(ctx)
 
 // Messages in, messages out: fbs_eval with the inputs encrypted on the device straight into their wire slots and the output
 // slots decrypted there (the same chunks, scratch ordering and checks); only int64 messages cross the bus.
-static int ensure_io_msgs(fbs_ctx *ctx, size_t words) {
-    if (words <= ctx->io_msgs_capacity) return FBS_OK;
-    ctx->scratch_growths++;
-    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));
-    if (ctx->d_io_msgs) (void)hipFree(ctx->d_io_msgs);
-    ctx->d_io_msgs = nullptr;
-    ctx->io_msgs_capacity = 0;
-    FBS_HIP(ctx, hipMalloc(&ctx->d_io_msgs, words * 8));
-    ctx->io_msgs_capacity = words;
-    return FBS_OK;
-}
-
 int fbs_eval_messages(fbs_ctx *ctx, fbs_prog *prog, const int64_t *msgs, size_t T, int fresh, uint64_t *nonce0, int64_t *out_msgs) try {
-    int rc = check_ready(ctx, prog ? prog->tv : nullptr);
+    int rc = check_eval(ctx, prog, msgs, T, out_msgs);
     if (rc != FBS_OK) return rc;
-    if (!prog || prog->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "program belongs to another context");
-    if ((prog->n_inputs && T && !msgs) || (prog->n_outputs && T && !out_msgs) || (!fresh && !nonce0))
-        return set_error(ctx, FBS_E_INVALID, "null argument");
+    if (!fresh && !nonce0) return set_error(ctx, FBS_E_INVALID, "null argument");
     if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
     if (T == 0) return FBS_OK;
     const size_t n_in = prog->n_inputs, n_out = prog->n_outputs;
@@ -1249,36 +1173,31 @@ int fbs_eval_messages(fbs_ctx *ctx, fbs_prog *prog, const int64_t *msgs, size_t 
                 host_decrypt(ctx, triv.data(), 1, &const_msg[o]);
             }
     }
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
     int64_t *d_in_msgs = ctx->d_io_msgs, *d_out_msgs = ctx->d_io_msgs + n_in * Tc;
-    for (size_t s0 = 0; s0 < T; s0 += Tc) {
-        const size_t tc = std::min(Tc, T - s0);
-        if (n_in) {
-            FBS_HIP(ctx, hipMemcpy2DAsync(d_in_msgs, Tc * 8, msgs + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
-            IoView in{d_in_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc};
-            if ((rc = dev_encrypt(ctx, in, first + s0, T, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-        }
-        if ((rc = run_levels(ctx, prog, ctx->d_wires, Tc, tc, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-        if (n_out) {
-            IoView out{d_out_msgs, Tc, ctx->d_wires, prog->d_out_slot, Tc, n_out, tc};
-            if ((rc = dev_decrypt(ctx, out, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-            FBS_HIP(ctx, hipMemcpy2DAsync(out_msgs + s0, T * 8, d_out_msgs, Tc * 8, tc * 8, n_out, hipMemcpyDeviceToHost, s));
-        }
-        FBS_HIP(ctx, hipStreamSynchronize(s));
+    auto load = [&](size_t s0, size_t tc) {
+        if (!n_in) return FBS_OK;
+        FBS_HIP(ctx, hipMemcpy2DAsync(d_in_msgs, Tc * 8, msgs + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
+        return dev_encrypt(ctx, IoView{d_in_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc}, first + s0, T, s);
+    };
+    auto store = [&](size_t s0, size_t tc) {
+        if (!n_out) return FBS_OK;
+        if (int rc = dev_decrypt(ctx, IoView{d_out_msgs, Tc, ctx->d_wires, prog->d_out_slot, Tc, n_out, tc}, s)) return rc;
+        FBS_HIP(ctx, hipMemcpy2DAsync(out_msgs + s0, T * 8, d_out_msgs, Tc * 8, tc * 8, n_out, hipMemcpyDeviceToHost, s));
+        return FBS_OK;
+    };
+    auto post = [&](size_t s0, size_t tc) {
         for (size_t o = 0; o < n_out; o++)
             if (prog->out_slot[o] < 0) std::fill(out_msgs + o * T + s0, out_msgs + o * T + s0 + tc, const_msg[o]);
-    }
-    return scratch_done(ctx, s);
+        return FBS_OK;
+    };
+    return eval_chunks(ctx, prog, T, Tc, s, true, load, store, post);
 } FBS_API_CATCH(ctx)
 
 // Seeded inputs: fbs_eval with the bodies copied to the device and expanded there straight into their wire slots (the chunks,
 // scratch ordering and outputs of fbs_eval); needs no secret.  The bodies use fbs_eval_messages's message scratch.
 int fbs_eval_seeded(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t T, uint64_t nonce0, uint64_t *out_cts) try {
-    int rc = check_ready(ctx, prog ? prog->tv : nullptr);
-    if (rc != FBS_OK) return rc;
-    if (!prog || prog->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "program belongs to another context");
-    if ((prog->n_inputs && T && !bodies) || (prog->n_outputs && T && !out_cts)) return set_error(ctx, FBS_E_INVALID, "null argument");
-    if (T == 0) return FBS_OK;
+    int rc = check_eval(ctx, prog, bodies, T, out_cts);
+    if (rc != FBS_OK || T == 0) return rc;
     const size_t n_in = prog->n_inputs, n_out = prog->n_outputs, ctw = ctx->D + 1;
     if (T > SIZE_MAX / 8 / std::max<size_t>(1, std::max(n_in, n_out)) / ctw)
         return set_error(ctx, FBS_E_INVALID, "n_inputs * T ciphertexts overflow");
@@ -1287,32 +1206,13 @@ int fbs_eval_seeded(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t
     size_t Tc = 0;
     if ((rc = reserve_wires(ctx, prog, T, &Tc)) != FBS_OK) return rc;
     if ((rc = ensure_io_msgs(ctx, std::max<size_t>(1, n_in) * Tc)) != FBS_OK) return rc;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    uint64_t *d_bodies = reinterpret_cast<uint64_t *>(ctx->d_io_msgs);
-    for (size_t s0 = 0; s0 < T; s0 += Tc) {
-        const size_t tc = std::min(Tc, T - s0);
-        if (n_in) {
-            FBS_HIP(ctx, hipMemcpy2DAsync(d_bodies, Tc * 8, bodies + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
-            IoView in{ctx->d_io_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc};
-            if ((rc = dev_expand_seeded(ctx, in, nonce0 + s0, T, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-        }
-        if ((rc = run_levels(ctx, prog, ctx->d_wires, Tc, tc, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-        for (uint32_t o = 0; o < n_out; o++) {
-            uint64_t *dst = out_cts + ((size_t)o * T + s0) * ctw;
-            const int64_t w = prog->out_slot[o];
-            if (w >= 0) {
-                FBS_HIP(ctx, hipMemcpyAsync(dst, ctx->d_wires + (size_t)w * Tc * ctw, tc * ctw * 8, hipMemcpyDeviceToHost, s));
-            } else {
-                const uint64_t body = trivial_body(ctx, w);   // trivial ciphertext of the constant, as fbs_eval
-                for (size_t q = 0; q < tc; q++) {
-                    std::memset(dst + q * ctw, 0, ctx->D * 8);
-                    dst[q * ctw + ctx->D] = body;
-                }
-            }
-        }
-        FBS_HIP(ctx, hipStreamSynchronize(s));
-    }
-    return scratch_done(ctx, s);
+    auto load = [&](size_t s0, size_t tc) {
+        if (!n_in) return FBS_OK;
+        FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_io_msgs, Tc * 8, bodies + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
+        return dev_expand_seeded(ctx, IoView{ctx->d_io_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc}, nonce0 + s0, T, s);
+    };
+    auto store = [&](size_t s0, size_t tc) { return store_host_cts(ctx, prog, out_cts, T, Tc, s0, tc, s); };
+    return eval_chunks(ctx, prog, T, Tc, s, true, load, store);
 } FBS_API_CATCH(ctx)
 
 // ---------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 // (reference fbs_mapper/fbs_exec_env.py:208-229) can take cleartext bits in and hand cleartext
 // values back, as the reference's harness (fbs_mapper/map_circuit.py:137-180) expects.
 #include <algorithm>
+#include <cmath>
 #include <functional>
 #include <cstring>
 #include <thread>
@@ -315,6 +316,59 @@ void host_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count
             ct[D] = bodies[i];
         }
     });
+}
+
+// Do the evaluation keys decrypt under the secrets they came with?  A handful of GGSW samples (every row) and key-switching rows,
+// each phase compared with what the layout of fbs_key_sizes says it encrypts: a key in another sample / row / column order has
+// uniform phases and fails here instead of bootstrapping to garbage.  Tolerance: 16 standard deviations of the set's noise.
+const char *imported_keys_mismatch(const fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glwe, const uint64_t *bsk,
+                                   const uint64_t *ksk) {
+    const fbs_params &p = ctx->p;
+    const uint32_t N = ctx->N, D = ctx->D, n = p.n, k = p.k, l = p.l_bsk, t = p.t_ksk, rows = ctx->rows;
+    auto far = [](uint64_t got, uint64_t want, double tol) { return std::fabs(fq_centered(fq_sub(got, want))) > tol; };
+    const double tol_glwe = 1024.0 + 16.0 * (double)p.sigma_glwe, tol_lwe = 1024.0 + 16.0 * (double)p.sigma_lwe;
+    std::vector<size_t> samples = {0, 1, 2, ctx->n_ggsw / 2, ctx->n_ggsw - 1};
+    std::vector<uint64_t> phase(N);
+    for (size_t g : samples) {
+        if (g >= ctx->n_ggsw) continue;
+        uint64_t bit;
+        if (ctx->group == 2) {   // sample g of 3n/2 encrypts a product of the key bits 2 (g / 3) and 2 (g / 3) + 1
+            const uint64_t s0 = sk_lwe[2 * (g / 3)], s1 = sk_lwe[2 * (g / 3) + 1];
+            bit = g % 3 == 0 ? (s0 & (1 - s1)) : g % 3 == 1 ? ((1 - s0) & s1) : (s0 & s1);
+        } else {
+            bit = sk_lwe[g];
+        }
+        for (uint32_t rr = 0; rr < rows; rr++) {
+            const uint32_t comp = rr / l, lv = rr % l;
+            const uint64_t *row = bsk + (g * rows + rr) * (size_t)(k + 1) * N;
+            for (uint32_t j = 0; j < N; j++) phase[j] = row[(size_t)k * N + j];
+            for (uint32_t c = 0; c < k; c++)                            // phase -= A_c * S_c (negacyclic, binary S)
+                for (uint32_t sh = 0; sh < N; sh++) {
+                    if (!sk_glwe[(size_t)c * N + sh]) continue;
+                    const uint64_t *a = row + (size_t)c * N;
+                    for (uint32_t j = 0; j < N - sh; j++) phase[j + sh] = fq_sub(phase[j + sh], a[j]);
+                    for (uint32_t j = N - sh; j < N; j++) phase[j + sh - N] = fq_add(phase[j + sh - N], a[j]);
+                }
+            // row (comp, lv) = GLWE(0) + bit g_lv on component comp: the phase is bit g_lv at X^0 (body row), -bit g_lv S_comp (mask rows)
+            for (uint32_t j = 0; j < N; j++) {
+                uint64_t want = 0;
+                if (bit && comp == k && j == 0) want = ctx->g[lv];
+                if (bit && comp < k && sk_glwe[(size_t)comp * N + j]) want = fq_sub(0, ctx->g[lv]);
+                if (far(phase[j], want, tol_glwe)) return "bootstrapping key does not decrypt under the supplied secrets (sample / row / column order of fbs_key_sizes?)";
+            }
+        }
+    }
+    const size_t ksk_rows = (size_t)D * t;
+    for (size_t r : {(size_t)0, (size_t)1, (size_t)2, (size_t)3, ksk_rows / 2, ksk_rows - 4, ksk_rows - 3, ksk_rows - 2, ksk_rows - 1}) {
+        if (r >= ksk_rows) continue;
+        const uint32_t j = (uint32_t)(r / t), v = (uint32_t)(r % t);
+        const uint64_t *row = ksk + r * (size_t)(n + 1);
+        uint64_t ph = row[n];
+        for (uint32_t i = 0; i < n; i++)
+            if (sk_lwe[i]) ph = fq_sub(ph, row[i]);
+        if (far(ph, sk_glwe[j] ? ctx->h[v] : 0, tol_lwe)) return "key-switching key does not decrypt under the supplied secrets (row order [kN][t][n+1]?)";
+    }
+    return nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------

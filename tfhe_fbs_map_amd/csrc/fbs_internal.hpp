@@ -122,7 +122,7 @@ struct fbs_ctx {
     fbs_params p{};
     uint64_t seed = 0;
     fbs::RandKey rkey{};               // what all randomness of the context is expanded from
-    std::atomic<uint64_t> next_nonce{1ull << 55};  // fbs_encrypt_fresh: first unused encryption stream of [2^55, 2^56); reserved by compare-exchange
+    mutable std::atomic<uint64_t> next_nonce{1ull << 55};  // fbs_encrypt_fresh: first unused encryption stream of [2^55, 2^56); reserved by compare-exchange
     fbs::Tune tune;
     int64_t scratch_growths = 0;       // how often a call had to (re)allocate scratch, i.e. blocked (fbs_ctx_stat)
     int device = 0;
@@ -201,7 +201,10 @@ struct fbs_tvset {
 
 namespace fbs {
 
+// the error text of a call (fbs_error.cpp): into ctx->err, or (ctx null: fbs_ctx_create and its kin) into a thread-local that
+// create_error reads
 int set_error(const fbs_ctx *ctx, int code, const std::string &msg);
+const char *create_error();
 #define FBS_HIP(ctx, call)                                                                       \
     do {                                                                                         \
         hipError_t e__ = (call);                                                                 \
@@ -265,6 +268,10 @@ int host_build_tv(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint64
 int host_build_tv_diff(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint32_t *pos, int32_t *val, uint32_t *count,
                        uint64_t *norm2, uint64_t *g_norm2, uint64_t *abs_sum);
 void host_twiddles(uint32_t log_n, std::vector<uint64_t> &fwd, std::vector<uint64_t> &inv);
+// fbs_import_keys: null if sampled rows of bsk and ksk decrypt under sk_lwe [n] and sk_glwe [D] as the fbs_key_sizes layout says,
+// else why not
+const char *imported_keys_mismatch(const fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glwe, const uint64_t *bsk,
+                                   const uint64_t *ksk);
 
 // device side (fbs_kernels.hip); all asynchronous on `stream`
 int dev_upload_keys(fbs_ctx *ctx);       // BSK -> NTT domain, KSK padded
