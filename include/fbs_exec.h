@@ -320,6 +320,33 @@ int fbs_eval_messages(fbs_ctx *ctx, fbs_prog *prog, const int64_t *msgs, size_t 
  * wire slots.  The same chunks as fbs_eval; needs no secret.  T = 0 does nothing.  Blocks until the outputs are back. */
 int fbs_eval_seeded(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t T, uint64_t nonce0, uint64_t *out_cts);
 
+/* ---- compact outputs: what a server returns in place of big-key ciphertexts ----------------------------------------------
+ * A compact ciphertext at width `bits` = w, log2(2N) <= w <= 31, is the big-key ciphertext key-switched to the small LWE key
+ * (dimension n) with the key-switching key, which gives x in Z_q^(n+1) (mask first, body last), then rounded to Z_(2^w) exactly
+ * as the modulus switch rounds to Z_2N before every blind rotation, with q treated as 2^46:
+ *     sh = 46 - w;   m_i = ((x_i >> (sh-1)) + 1) >> 1  (i < n);   eps = sum_i (x_i - (m_i << sh))  (signed);
+ *     body' = (x_n - floor(eps / 2)) mod q;   m_n = ((body' >> (sh-1)) + 1) >> 1;   every field mod 2^w.
+ * At w = log2(2N) the fields are, word for word, what the blind rotation reads.  PACKING: a ciphertext is
+ * W = ceil((n+1) w / 64) uint64 words; field j occupies bits [j w, j w + w) of the ciphertext's bit stream, stream bit b being
+ * bit b mod 64 of word b / 64; bits past the last field are zero; a batch is [count][W].  DECODE under the small key s:
+ *     phase = (m_n - sum_i m_i s_i) mod 2^w;   msg = ((phase 2p + 2^(w-1)) >> w) mod 2p.
+ * The compaction of a constant output is that of its trivial ciphertext: zero mask fields and the rounded body.  The noise it
+ * carries is at most that of a bootstrap input at w = log2(2N) (params.compact_output_variance).
+ * Every entry returns FBS_E_INVALID for a w outside [log2(2N), 31] and writes nothing when it fails. */
+int fbs_compact_words(const fbs_ctx *ctx, uint32_t bits, size_t *words);
+/* d_cts [count][D+1] (any big-key ciphertexts, device) -> d_words [count][W], asynchronous on `stream`; needs no secret.  Runs in
+ * passes of the context's modulus-switch scratch (of at least 8192 ciphertexts): it does not grow scratch with count. */
+int fbs_compact_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_words, void *stream);
+/* fbs_eval_seeded with compact outputs: out_words host [n_outputs][T][W], and only those words cross the bus on the way back.
+ * Equal to fbs_compact_dev of fbs_eval_seeded's outputs (constant outputs as above).  Needs no secret.  T = 0 does nothing.
+ * Blocks until the outputs are back. */
+int fbs_eval_seeded_compact(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t T, uint64_t nonce0, uint32_t bits,
+                            uint64_t *out_words);
+/* the decode, words [count][W] -> msgs[count]; host and device give the same messages.  FBS_E_STATE on an evaluation-only
+ * context (as fbs_decrypt). */
+int fbs_decrypt_compact(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs);
+int fbs_decrypt_compact_dev(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, int64_t *d_msgs, void *stream);
+
 /* ---- a loaded program, one level at a time (multi-GPU hosts) -----------------
  * The two independent axes of the reference's eval loop (fbs_exec_env.py:211-223) are the gates
  * of a bootstrap level and the samples.  A host that shards the GATES of a level over several

@@ -161,6 +161,11 @@ def _load():
         "fbs_expand_seeded": (i32, [vp, vp, sz, u64, vp]),
         "fbs_expand_seeded_dev": (i32, [vp, vp, sz, u64, vp, vp]),
         "fbs_eval_seeded": (i32, [vp, vp, vp, sz, u64, vp]),
+        "fbs_compact_words": (i32, [vp, u32, C.POINTER(sz)]),
+        "fbs_compact_dev": (i32, [vp, vp, sz, u32, vp, vp]),
+        "fbs_eval_seeded_compact": (i32, [vp, vp, vp, sz, u64, u32, vp]),
+        "fbs_decrypt_compact": (i32, [vp, vp, sz, u32, vp]),
+        "fbs_decrypt_compact_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_tvset_create": (i32, [vp, vp, vp, u32, C.POINTER(vp)]),
         "fbs_tvset_destroy": (None, [vp]),
         "fbs_bootstrap_batch": (i32, [vp, vp, vp, vp, sz, vp]),
@@ -216,6 +221,7 @@ EXPORTED_SYMBOLS = (
     "fbs_keygen_seeded", "fbs_seeded_key_sizes", "fbs_export_seeded_keys", "fbs_import_seeded_keys", "fbs_encrypt_seeded",
     "fbs_encrypt_seeded_fresh", "fbs_encrypt_seeded_dev", "fbs_encrypt_seeded_fresh_dev", "fbs_expand_seeded",
     "fbs_expand_seeded_dev", "fbs_eval_seeded",
+    "fbs_compact_words", "fbs_compact_dev", "fbs_eval_seeded_compact", "fbs_decrypt_compact", "fbs_decrypt_compact_dev",
 )
 
 lib = _load()
@@ -316,6 +322,16 @@ class Program:
         bodies = _c(bodies, np.uint64).reshape(self.n_inputs, T)
         out = np.empty((self.n_outputs, T, self.ctx.params.ct_words), np.uint64)
         self.ctx._check(lib.fbs_eval_seeded(self.ctx._h, self._h, _ptr(bodies), T, int(nonce0), _ptr(out)))
+        return out
+
+    def eval_seeded_compact(self, bodies, T, nonce0, bits=None):
+        """Seeded inputs, compact outputs (fbs_eval_seeded_compact): as `eval_seeded`, but each output comes back key-switched to
+        the small key, rounded to `bits` bits a field (None: log2(2N)) and packed -> words [n_outputs][T][W]
+        (`Context.compact_words`).  Needs no secret; `Context.decrypt_compact` reads the words."""
+        bits = self.ctx.default_compact_bits if bits is None else int(bits)
+        bodies = _c(bodies, np.uint64).reshape(self.n_inputs, T)
+        out = np.empty((self.n_outputs, T, self.ctx.compact_words(bits)), np.uint64)
+        self.ctx._check(lib.fbs_eval_seeded_compact(self.ctx._h, self._h, _ptr(bodies), T, int(nonce0), bits, _ptr(out)))
         return out
 
     # device-pointer entry points (ints from torch.Tensor.data_ptr()); asynchronous on `stream`, no host copies
@@ -519,6 +535,50 @@ class Context:
 
     def tvset(self, tables):
         return TvSet(self, tables)
+
+    # ---- compact outputs: key-switched to the small key, rounded to `bits` bits a field, bit-packed (include/fbs_exec.h) ----
+    @property
+    def default_compact_bits(self):
+        """log2(2N): the width the blind rotation reads, and the narrowest compact width"""
+        return self.params.log_n_poly + 1
+
+    def compact_words(self, bits=None):
+        """W, the uint64 words of one compact ciphertext at width `bits` (None: log2(2N)); FbsError(FBS_E_INVALID) outside
+        [log2(2N), 31]"""
+        w = C.c_size_t()
+        self._check(lib.fbs_compact_words(self._h, self.default_compact_bits if bits is None else int(bits), C.byref(w)))
+        return int(w.value)
+
+    def compact_dev(self, d_cts, count, d_words, bits=None, stream=0):
+        """fbs_compact_dev: `count` big-key ciphertexts at d_cts -> [count][W] words at d_words, asynchronous on `stream`; needs
+        no secret"""
+        self._check(lib.fbs_compact_dev(self._h, d_cts or None, count, self.default_compact_bits if bits is None else int(bits),
+                                        d_words or None, stream or None))
+
+    def decrypt_compact(self, words, bits=None, device=True):
+        """Compact ciphertexts [..][W] -> messages [..].  device=True: on the GPU (fbs_decrypt_compact_dev), False: on the host
+        (fbs_decrypt_compact) -- the same messages."""
+        bits = self.default_compact_bits if bits is None else int(bits)
+        words = _c(words, np.uint64)
+        W = words.shape[-1] if words.ndim else 0
+        out = np.empty(words.shape[:-1], np.int64)
+        if out.size and W != self.compact_words(bits):
+            raise ValueError(f"compact ciphertexts of {W} words at {bits} bits (the parameter set needs {self.compact_words(bits)})")
+        if not device:
+            self._check(lib.fbs_decrypt_compact(self._h, _ptr(words), out.size, bits, _ptr(out)))
+            return out
+        import torch
+        d_w = torch.from_numpy(words.reshape(-1).view(np.int64)).to("cuda:%d" % self.device) if words.size else None
+        d_m = torch.empty(max(1, out.size), dtype=torch.int64, device="cuda:%d" % self.device)
+        torch.cuda.synchronize(d_m.device)
+        self._check(lib.fbs_decrypt_compact_dev(self._h, d_w.data_ptr() if d_w is not None else None, out.size, bits, d_m.data_ptr(),
+                                                None))
+        self.sync()
+        return d_m[:out.size].cpu().numpy().reshape(out.shape)
+
+    def decrypt_compact_dev(self, d_words, count, d_msgs, bits=None, stream=0):
+        self._check(lib.fbs_decrypt_compact_dev(self._h, d_words or None, count, self.default_compact_bits if bits is None else int(bits),
+                                                d_msgs or None, stream or None))
 
     def bootstrap_batch(self, tvset, cts, table_ids=None):
         cts = _c(cts, np.uint64)

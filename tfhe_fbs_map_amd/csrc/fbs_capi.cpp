@@ -8,6 +8,7 @@
 #include <functional>
 #include <memory>
 
+#include "fbs_compact.hpp"
 #include "fbs_internal.hpp"
 #include "fbs_plan.hpp"
 
@@ -52,6 +53,8 @@ struct fbs_prog {
     std::vector<int64_t> out_slot;    // [n_outputs]  slot, or -1-c for the constant c
     uint32_t *d_in_slot = nullptr;    // [n_inputs]   the same on the device (fbs_eval_messages)
     uint32_t *d_out_slot = nullptr;   // [n_outputs]  slot, or 0xFFFFFFFF for a constant
+    std::vector<uint32_t> live_out;   // the outputs that are wires, not constants, in output order
+    uint32_t *d_live_slot = nullptr;  // [live_out.size()] their slots (the key switches of fbs_eval_seeded_compact read them)
     // schedule: for level L = 0..depth: lincomb stages (dependency order), then the bootstraps of level L+1
     std::vector<std::vector<LincombStage>> lin;   // [depth+1][sub]
     std::vector<BootStage> boot;                  // [depth]  (boot[L] = bootstraps of level L+1)
@@ -266,7 +269,8 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->scratch_used) (void)hipStreamSynchronize(ctx->scratch_stream);
     for (void *p : {(void *)ctx->d_bsk_hat, (void *)ctx->d_bsk_hat_small, (void *)ctx->d_ksk, (void *)ctx->d_ksk_f, (void *)ctx->d_ks_corr, (void *)ctx->d_ks_a, (void *)ctx->d_ks_b, (void *)ctx->d_ks_c, (void *)ctx->d_tw_fwd, (void *)ctx->d_tw_inv, (void *)ctx->d_psi_pow, (void *)ctx->d_ms, (void *)ctx->d_ms_eps, (void *)ctx->d_ms_body, (void *)ctx->d_acc, (void *)ctx->d_stage_in, (void *)ctx->d_stage_out, (void *)ctx->d_stage_ids,
-                    (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_io_msgs})
+                    (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_sk_lwe_bits, (void *)ctx->d_io_msgs,
+                    (void *)ctx->d_compact})
         if (p) (void)hipFree(p);
     if (ctx->scratch_event) (void)hipEventDestroy(ctx->scratch_event);
     for (auto &v : ctx->prof.pending)
@@ -510,10 +514,11 @@ int fbs_import_seeded_keys(fbs_ctx *ctx, const uint8_t mask_key[32], const uint6
     std::fill(ctx->sk_glwe.begin(), ctx->sk_glwe.end(), 0);
     std::vector<uint64_t>().swap(ctx->sk_lwe);
     std::vector<uint64_t>().swap(ctx->sk_glwe);
-    if (ctx->d_sk_bits) {
-        (void)hipFree(ctx->d_sk_bits);
-        ctx->d_sk_bits = nullptr;
-    }
+    for (uint32_t **bits : {&ctx->d_sk_bits, &ctx->d_sk_lwe_bits})
+        if (*bits) {
+            (void)hipFree(*bits);
+            *bits = nullptr;
+        }
     ctx->mask_key = mk;
     ctx->have_keys = false;
     ctx->seeded_keys = true;
@@ -663,7 +668,7 @@ int fbs_bootstrap_batch_dev(fbs_ctx *ctx, const fbs_tvset *tv, const uint64_t *d
     const GateView gv = batch_view(d_cts_in, d_cts_out, d_table_ids, count);
     hipStream_t s = pick(ctx, stream);
     if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    rc = dev_keyswitch(ctx, gv, ctx->d_ms, s);
+    rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s);
     if (rc != FBS_OK) return scratch_fail(ctx, s, rc);
     rc = dev_blind_rotate(ctx, tv, gv, ctx->d_ms, s);
     if (rc != FBS_OK) return scratch_fail(ctx, s, rc);
@@ -785,7 +790,7 @@ int fbs_bootstrap_wires_dev(fbs_ctx *ctx, const fbs_tvset *tv, uint64_t *d_wires
     gv.ks_begin = 0;
     gv.ks_count = count;
     gv.n_gates = n_gates;
-    rc = dev_keyswitch(ctx, gv, ctx->d_ms, s);
+    rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s);
     if (rc != FBS_OK) return rc;
     rc = dev_blind_rotate(ctx, tv, gv, ctx->d_ms, s);
     if (rc != FBS_OK) return rc;
@@ -835,6 +840,13 @@ int fbs_program_load_ex(fbs_ctx *ctx, const fbs_program_desc *d, const fbs_tvset
         for (size_t o = 0; o < out_slot.size(); o++) out_slot[o] = plan.out_slot[o] >= 0 ? (uint32_t)plan.out_slot[o] : 0xFFFFFFFFu;
         if ((rc = to_device(ctx, prog.get(), plan.in_slot, &prog->d_in_slot)) || (rc = to_device(ctx, prog.get(), out_slot, &prog->d_out_slot)))
             return rc;
+        std::vector<uint32_t> live_slot;
+        for (size_t o = 0; o < out_slot.size(); o++)
+            if (plan.out_slot[o] >= 0) {
+                prog->live_out.push_back((uint32_t)o);
+                live_slot.push_back(out_slot[o]);
+            }
+        if ((rc = to_device(ctx, prog.get(), live_slot, &prog->d_live_slot))) return rc;
     }
     // ---- upload the stage tables (coefficients and constants mapped into the field) ----------------------------------
     prog->lin.resize(plan.depth + 1);
@@ -993,7 +1005,7 @@ int fbs_level_bootstrap_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, 
     }
     hipStream_t s = pick(ctx, stream);
     if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    if ((rc = dev_keyswitch(ctx, gv, ctx->d_ms, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+    if ((rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
     if ((rc = dev_blind_rotate(ctx, prog->tv, gv, ctx->d_ms, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
     if (b.n_shared && !d_rows &&
         (rc = dev_multi_extract(ctx, prog->tv, ctx->d_acc, d_wires, T, s_begin, s_count, b.n_extract, b.d_x_row, b.d_x_table, b.d_x_dst, s)) != FBS_OK)
@@ -1031,13 +1043,15 @@ static int run_levels(fbs_ctx *ctx, const fbs_prog *prog, uint64_t *d_wires, siz
 
 // Samples are independent through the whole program: evaluate in chunks whose wire slots fit in HBM.  The wire buffer
 // belongs to the context and is shared by all of its programs (it only ever grows).
-static int reserve_wires(fbs_ctx *ctx, const fbs_prog *prog, size_t T, size_t *chunk) {
+// `extra_per_sample`: bytes per sample of a further buffer the caller sizes by the chunk (the packed staging of compact outputs)
+static int reserve_wires(fbs_ctx *ctx, const fbs_prog *prog, size_t T, size_t *chunk, size_t extra_per_sample = 0) {
     const size_t ctw = ctx->D + 1;
     const size_t per_sample = (size_t)prog->n_slots * ctw * 8 + (size_t)std::max(1u, prog->max_sources) * (ctx->p.n + 1) * 4 +
-                              (size_t)prog->max_shared * (ctx->p.k + 1) * ctx->N * 8;
+                              (size_t)prog->max_shared * (ctx->p.k + 1) * ctx->N * 8 + extra_per_sample;
     size_t free_b = 0, total_b = 0;
     FBS_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
     size_t have = free_b + ctx->wires_capacity * 8 + ctx->ms_capacity * (ctx->p.n + 1) * 4 + ctx->acc_capacity * (size_t)(ctx->p.k + 1) * ctx->N * 8;
+    if (extra_per_sample) have += ctx->compact_capacity * 8;   // (the compact path reuses its packed staging; no other call does)
     // test hook: FBS_WIRE_BUDGET_MB caps what the wire slots may take, so that the chunked path runs at small sizes
     if (const char *cap = getenv("FBS_WIRE_BUDGET_MB")) have = std::min<size_t>(have, (size_t)std::max(1, atoi(cap)) << 20);
     const size_t Tc = std::min<size_t>(T, std::max<size_t>(1, (size_t)(0.6 * (double)have) / per_sample));
@@ -1213,6 +1227,118 @@ int fbs_eval_seeded(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t
     };
     auto store = [&](size_t s0, size_t tc) { return store_host_cts(ctx, prog, out_cts, T, Tc, s0, tc, s); };
     return eval_chunks(ctx, prog, T, Tc, s, true, load, store);
+} FBS_API_CATCH(ctx)
+
+// ---- compact outputs: key switch to the small key, rounding to Z_(2^bits), bit packing (fbs_compact.hpp) --------------------
+static int check_bits(const fbs_ctx *ctx, uint32_t bits) {
+    if (bits < ctx->p.log_n_poly + 1 || bits > 31) return set_error(ctx, FBS_E_INVALID, "compact width must lie in [log2(2N), 31]");
+    return FBS_OK;
+}
+static int check_compact_words(const fbs_ctx *ctx, size_t count, uint32_t bits) {
+    if (count > SIZE_MAX / 8 / compact_words(ctx->p.n, bits)) return set_error(ctx, FBS_E_INVALID, "count * W words overflow");
+    return FBS_OK;
+}
+// fbs_compact_dev runs in passes of the modulus-switch scratch the context has, or of this many ciphertexts when it has less
+constexpr size_t COMPACT_PASS = 8192;
+
+int fbs_compact_words(const fbs_ctx *ctx, uint32_t bits, size_t *words) try {
+    if (!ctx || !words) return FBS_E_INVALID;
+    if (int rc = check_bits(ctx, bits)) return rc;
+    *words = compact_words(ctx->p.n, bits);
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+// (no secret needed: runs on evaluation-only contexts)
+int fbs_compact_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_words, void *stream) try {
+    if (int rc = io_prologue(ctx, d_cts, d_words, count, IO_CT_WORDS, nullptr)) return rc;
+    if (int rc = check_bits(ctx, bits)) return rc;
+    if (int rc = check_compact_words(ctx, count, bits)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t pass = std::min(count, std::max(ctx->ms_capacity, COMPACT_PASS)), ctw = ctx->D + 1, W = compact_words(ctx->p.n, bits);
+    int rc = ensure_ms(ctx, pass);
+    if (rc != FBS_OK) return rc;
+    hipStream_t s = pick(ctx, stream);
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    for (size_t f0 = 0; f0 < count; f0 += pass) {
+        const size_t rows = std::min(pass, count - f0);
+        const GateView gv = batch_view(d_cts + f0 * ctw, nullptr, nullptr, rows);
+        if ((rc = dev_keyswitch(ctx, gv, ctx->d_ms, bits, s)) || (rc = dev_compact_pack(ctx, ctx->d_ms, rows, bits, d_words + f0 * W, s)))
+            return scratch_fail(ctx, s, rc);
+    }
+    return scratch_done(ctx, s);
+} FBS_API_CATCH(ctx)
+
+// fbs_eval_seeded with another store stage: the output slots of a chunk are key-switched and packed on the device in groups of
+// outputs whose rows fit the modulus-switch scratch reserve_wires sized (max_sources x Tc rows), and only the packed words are
+// copied back.  The packed staging of a group is counted in the chunk's budget.
+int fbs_eval_seeded_compact(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t T, uint64_t nonce0, uint32_t bits,
+                            uint64_t *out_words) try {
+    int rc = check_eval(ctx, prog, bodies, T, out_words);
+    if (rc != FBS_OK) return rc;
+    if ((rc = check_bits(ctx, bits)) != FBS_OK || T == 0) return rc;
+    const size_t n_in = prog->n_inputs, n_out = prog->n_outputs, ctw = ctx->D + 1, W = compact_words(ctx->p.n, bits);
+    if (T > SIZE_MAX / 8 / std::max<size_t>(1, std::max(n_in, n_out)) / std::max(ctw, W))
+        return set_error(ctx, FBS_E_INVALID, "n_inputs * T ciphertexts overflow");
+    if ((rc = check_seeded_streams(ctx, nonce0, n_in * T))) return rc;
+    hipStream_t s = ctx->stream;
+    const size_t rows_per_sample = std::max(1u, prog->max_sources);
+    size_t Tc = 0;
+    if ((rc = reserve_wires(ctx, prog, T, &Tc, rows_per_sample * W * 8)) != FBS_OK) return rc;
+    if ((rc = ensure_io_msgs(ctx, std::max<size_t>(1, n_in) * Tc)) != FBS_OK) return rc;
+    const size_t cap_rows = rows_per_sample * Tc;   // (ensure_ms has made d_ms at least this long)
+    if ((rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, cap_rows * W, 8, true)) != FBS_OK) return rc;
+    // a constant output: the compaction of the trivial ciphertext fbs_eval_seeded returns for it
+    std::vector<uint64_t> constant((size_t)n_out * W, 0);
+    for (size_t o = 0; o < n_out; o++)
+        if (prog->out_slot[o] < 0) host_compact_trivial(ctx, trivial_body(ctx, prog->out_slot[o]), bits, constant.data() + o * W);
+    auto load = [&](size_t s0, size_t tc) {
+        if (!n_in) return FBS_OK;
+        FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_io_msgs, Tc * 8, bodies + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
+        return dev_expand_seeded(ctx, IoView{ctx->d_io_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc}, nonce0 + s0, T, s);
+    };
+    auto store = [&](size_t s0, size_t tc) {
+        const size_t n_live = prog->live_out.size(), group = std::max<size_t>(1, cap_rows / tc);
+        for (size_t g0 = 0; g0 < n_live; g0 += group) {
+            const size_t ng = std::min(group, n_live - g0), rows = ng * tc;
+            GateView gv{};
+            gv.in_base = ctx->d_wires;
+            gv.src_slot = prog->d_live_slot + g0;
+            gv.T = Tc;
+            gv.s_begin = 0;
+            gv.s_count = tc;
+            gv.count = rows;
+            gv.ks_count = rows;
+            gv.n_gates = (uint32_t)ng;
+            if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, bits, s)) return rc;
+            if (int rc = dev_compact_pack(ctx, ctx->d_ms, rows, bits, ctx->d_compact, s)) return rc;
+            for (size_t i = 0; i < ng; i++)
+                FBS_HIP(ctx, hipMemcpyAsync(out_words + ((size_t)prog->live_out[g0 + i] * T + s0) * W, ctx->d_compact + i * tc * W, tc * W * 8,
+                                            hipMemcpyDeviceToHost, s));
+        }
+        for (size_t o = 0; o < n_out; o++)
+            if (prog->out_slot[o] < 0)
+                for (size_t q = 0; q < tc; q++) std::memcpy(out_words + (o * T + s0 + q) * W, constant.data() + o * W, W * 8);
+        return FBS_OK;
+    };
+    return eval_chunks(ctx, prog, T, Tc, s, true, load, store);
+} FBS_API_CATCH(ctx)
+
+int fbs_decrypt_compact(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs) try {
+    if (int rc = io_prologue(ctx, words, msgs, count, IO_SECRET, nullptr)) return rc;
+    if (int rc = check_bits(ctx, bits)) return rc;
+    if (int rc = check_compact_words(ctx, count, bits)) return rc;
+    host_decrypt_compact(ctx, words, count, bits, msgs);
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_decrypt_compact_dev(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, int64_t *d_msgs, void *stream) try {
+    if (int rc = io_prologue(ctx, d_words, d_msgs, count, IO_SECRET, nullptr)) return rc;
+    if (int rc = check_bits(ctx, bits)) return rc;
+    if (int rc = check_compact_words(ctx, count, bits)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_decrypt_compact(ctx, d_words, count, bits, d_msgs, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
 // ---------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 
 #include "fbs_internal.hpp"
 #include "fbs_chacha.hpp"
+#include "fbs_compact.hpp"
 
 namespace fbs {
 
@@ -404,6 +405,26 @@ void host_decrypt(const fbs_ctx *ctx, const uint64_t *cts, size_t count, int64_t
             msgs[i] = (int64_t)((uint64_t)(v / FQ) % two_p);
         }
     });
+}
+
+// Compact outputs (fbs_compact.hpp): the phase of the packed fields under the small key, rounded to a message
+void host_decrypt_compact(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs) {
+    const uint32_t n = ctx->p.n, W = compact_words(n, bits);
+    const uint64_t two_p = 2ull * ctx->p.p_msg;
+    parallel_for(count, [&](size_t a, size_t b) {
+        for (size_t c = a; c < b; c++) {
+            const uint64_t *ct = words + c * W;
+            uint32_t sum = 0;
+            for (uint32_t i = 0; i < n; i++)
+                if (ctx->sk_lwe[i]) sum += compact_field(ct, i, bits);
+            msgs[c] = compact_decode(compact_field(ct, n, bits), sum, bits, two_p);
+        }
+    });
+}
+
+void host_compact_trivial(const fbs_ctx *ctx, uint64_t body, uint32_t bits, uint64_t *words) {
+    const uint32_t n = ctx->p.n, W = compact_words(n, bits), m_n = compact_round(body, bits);
+    for (uint32_t j = 0; j < W; j++) words[j] = compact_word(j, n + 1, bits, [&](uint32_t f) { return f == n ? m_n : 0u; });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -170,6 +170,9 @@ struct fbs_ctx {
     uint32_t *d_idx = nullptr;       // scratch for index arrays of the host-index wires API
     size_t idx_capacity = 0;
     uint32_t *d_sk_bits = nullptr;   // [ceil(D / 32)] the GLWE secret key as packed bits (device encryption / decryption, fbs_io.hip)
+    uint32_t *d_sk_lwe_bits = nullptr;   // [ceil(n / 32)] the small LWE key as packed bits (decryption of compact outputs)
+    uint64_t *d_compact = nullptr;   // scratch: packed compact ciphertexts of fbs_eval_seeded_compact's output groups
+    size_t compact_capacity = 0;     // in words
     int64_t *d_io_msgs = nullptr;    // scratch: messages of fbs_eval_messages, [n_inputs + n_outputs][chunk]
     size_t io_msgs_capacity = 0;     // in words
     uint64_t *d_wires = nullptr;     // wire slots of fbs_eval, shared by every program of the context
@@ -252,6 +255,10 @@ int host_ctx_init(fbs_ctx *ctx, const fbs_params *params, uint64_t seed, const u
 void host_keygen(fbs_ctx *ctx);
 void host_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *cts);
 void host_decrypt(const fbs_ctx *ctx, const uint64_t *cts, size_t count, int64_t *msgs);
+// compact outputs (fbs_compact.hpp): words [count][compact_words(n, bits)] -> msgs[count] under sk_lwe; the device decode is held to it
+void host_decrypt_compact(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs);
+// the compaction of the trivial ciphertext (0, .., 0, body): zero mask fields, the rounded body -> words[compact_words(n, bits)]
+void host_compact_trivial(const fbs_ctx *ctx, uint64_t body, uint32_t bits, uint64_t *words);
 // seeded path (DOM_S*): host_keygen row for row with masks under ctx->mask_key (= mask_key_of(rkey)) and noise on the seeded
 // streams; the secrets are host_keygen's.  The bodies are computed, then expanded by host_expand_seeded_keys like any import.
 void host_keygen_seeded(fbs_ctx *ctx);
@@ -276,7 +283,9 @@ const char *imported_keys_mismatch(const fbs_ctx *ctx, const uint64_t *sk_lwe, c
 // device side (fbs_kernels.hip); all asynchronous on `stream`
 int dev_upload_keys(fbs_ctx *ctx);       // BSK -> NTT domain, KSK padded
 int dev_keyswitch_gemm_setup(fbs_ctx *ctx);   // limb fragments of the key-switching key for the int8 MFMA key switch
-int dev_keyswitch(fbs_ctx *ctx, const GateView &gv, uint32_t *d_ms, hipStream_t stream);
+// the key switch kN -> n and the rounding of every word to Z_(2^log2_mod) (log2(2N): what the blind rotation reads; up to 31: the
+// fields of compact outputs), into d_ms [gv.ks_count][n + 1]
+int dev_keyswitch(fbs_ctx *ctx, const GateView &gv, uint32_t *d_ms, uint32_t log2_mod, hipStream_t stream);
 int dev_keyswitch_reserve(fbs_ctx *ctx, size_t count);          // scratch of the GEMM key switch for launches of `count` (blocks when it grows)
 int dev_keyswitch_rezero(fbs_ctx *ctx, hipStream_t stream);     // puts its "zero between launches" scratch back after a failed call
 int dev_blind_rotate(fbs_ctx *ctx, const fbs_tvset *tv, const GateView &gv, const uint32_t *d_ms, hipStream_t stream);
@@ -307,6 +316,11 @@ int dev_decrypt(const fbs_ctx *ctx, const IoView &v, hipStream_t stream);
 // dev_expand_seeded: the bodies at v.msgs (read as uint64 words) -> ciphertexts, (r, s) on stream nonce0 + r nonce_stride + s
 int dev_encrypt_seeded(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, uint64_t nonce0, uint64_t *d_bodies, hipStream_t stream);
 int dev_expand_seeded(const fbs_ctx *ctx, const IoView &v, uint64_t nonce0, uint64_t nonce_stride, hipStream_t stream);
+
+// compact outputs (fbs_compact.hip): the switched fields d_ms [count][n + 1] -> packed words d_words [count][W]; and the decode of
+// packed words under the small key (d_sk_lwe_bits), word for word host_decrypt_compact
+int dev_compact_pack(const fbs_ctx *ctx, const uint32_t *d_ms, size_t count, uint32_t bits, uint64_t *d_words, hipStream_t stream);
+int dev_decrypt_compact(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, int64_t *d_msgs, hipStream_t stream);
 
 // profiling helpers
 void prof_begin(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t *e0, hipEvent_t *e1);

@@ -192,13 +192,20 @@ __global__ __launch_bounds__(64 * IO_WAVES) void k_expand_seeded(ExpandArgs a) {
 
 static dim3 io_grid(size_t total) { return dim3((unsigned)std::min<size_t>((total + IO_WAVES - 1) / IO_WAVES, IO_MAX_BLOCKS)); }
 
-int dev_upload_secret(fbs_ctx *ctx) {
+int dev_upload_secret(fbs_ctx *ctx) {   // (both secret keys, as packed bits)
     const uint32_t D = ctx->D, words = (D + 31) / 32;
     std::vector<uint32_t> bits(words, 0);
     for (uint32_t j = 0; j < D; j++)
         if (ctx->sk_glwe[j]) bits[j >> 5] |= 1u << (j & 31);
     if (!ctx->d_sk_bits) FBS_HIP(ctx, hipMalloc(&ctx->d_sk_bits, (size_t)words * 4));
     FBS_HIP(ctx, hipMemcpy(ctx->d_sk_bits, bits.data(), (size_t)words * 4, hipMemcpyHostToDevice));
+    // the small LWE key too: what compact outputs are decrypted under (fbs_decrypt_compact_dev)
+    const uint32_t n = ctx->p.n, small_words = std::max(1u, (n + 31) / 32);
+    std::vector<uint32_t> small(small_words, 0);
+    for (uint32_t i = 0; i < n; i++)
+        if (ctx->sk_lwe[i]) small[i >> 5] |= 1u << (i & 31);
+    if (!ctx->d_sk_lwe_bits) FBS_HIP(ctx, hipMalloc(&ctx->d_sk_lwe_bits, (size_t)small_words * 4));
+    FBS_HIP(ctx, hipMemcpy(ctx->d_sk_lwe_bits, small.data(), (size_t)small_words * 4, hipMemcpyHostToDevice));
     return FBS_OK;
 }
 

@@ -43,7 +43,8 @@ struct KsArgs {
     unsigned long long *eps;   // [count]  two's complement sums, zero on entry
     uint64_t *body_raw;        // [count]
     uint32_t offs;         // B/2 at every digit position
-    uint32_t n, D, t, gamma, stride, ct_words, log2_2n;
+    uint32_t n, D, t, gamma, stride, ct_words;
+    uint32_t log2_2n;      // the words are rounded to Z_(2^log2_2n): 2N for the blind rotation, 2^w for compact outputs (w <= 31)
     uint32_t cols_major;   // 1: blockIdx.x walks the column blocks (what launch_keyswitch sets), 0: the ciphertext tiles
     size_t row0;           // first key switch of this launch (launches are split when a grid dimension would overflow)
     size_t count;          // key switches in all (gv.ks_count)
@@ -781,7 +782,7 @@ static int launch_keyswitch(fbs_ctx *ctx, const Kernel &k, KsArgs &a, hipStream_
     return set_error(ctx, FBS_E_INVALID, "no instantiation of " + kernel_name(k));
 }
 
-int dev_keyswitch(fbs_ctx *ctx, const GateView &gv, uint32_t *d_ms, hipStream_t stream) {
+int dev_keyswitch(fbs_ctx *ctx, const GateView &gv, uint32_t *d_ms, uint32_t log2_mod, hipStream_t stream) {
     const fbs_params &p = ctx->p;
     KsArgs a{};
     a.gv = gv;
@@ -797,7 +798,7 @@ int dev_keyswitch(fbs_ctx *ctx, const GateView &gv, uint32_t *d_ms, hipStream_t 
     a.gamma = p.gamma_ksk;
     a.stride = ctx->ksk_stride;
     a.ct_words = ctx->D + 1;
-    a.log2_2n = p.log_n_poly + 1;
+    a.log2_2n = log2_mod;   // (log2(2N) for the blind rotation; ms_store's mask (1u << log2_mod) - 1 is defined up to 31)
     a.count = gv.ks_count;
     // (one launch: select_keyswitch never cuts a key switch; the modulus switch of the bodies follows it)
     for (const Launch &l : select_keyswitch(ctx, a.count)) {

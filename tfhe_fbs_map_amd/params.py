@@ -109,6 +109,43 @@ def margin_sigmas(prm: Params, norm2: float = 1.0) -> float:
     return (1.0 / (4.0 * prm.p_msg)) / sigma
 
 
+# ---- compact outputs (include/fbs_exec.h, "compact outputs") ----------------------------------------------------------------
+def compact_output_variance(prm: Params, bits: int, out_norm2: float = 1.0) -> float:
+    """Phase variance of a compact output at width `bits`: the output's own noise (out_norm2 times a blind rotation's: 1 for a
+    bootstrap output, its coefficients' squared norm for a linear combination of bootstrap outputs, |D_F|^2 for a table cut from a
+    shared rotation, about 0 for inputs and constants), the key switch to the small key, and the mean-compensated rounding of the
+    n + 1 fields to Z_(2^bits) -- the modulus switch of `variances` at 2^bits in place of 2N."""
+    v_br, v_ks, _ = variances(prm)
+    return out_norm2 * v_br + v_ks + (1 + prm.n / 4.0) / (12.0 * 2.0 ** (2 * bits))
+
+
+def compact_output_skew(prm: Params) -> float:
+    """Bound on the deterministic shift of the phase (torus units) that rounding with q treated as 2^46 leaves: each of the
+    n + 1 fields is off by at most (2^46 - q) / 2^46 of the torus, whatever the width."""
+    return (prm.n + 1) * float((1 << MODULUS_BITS) - MODULUS) / float(1 << MODULUS_BITS)
+
+
+def compact_output_margin(prm: Params, bits: int, out_norm2: float = 1.0) -> float:
+    """Standard deviations between a compact output's phase and the edge of its box: (q/(4p) - skew) / sigma, the counterpart
+    of `margin_sigmas` for what a client decodes."""
+    return (1.0 / (4.0 * prm.p_msg) - compact_output_skew(prm)) / math.sqrt(compact_output_variance(prm, bits, out_norm2))
+
+
+def compact_output_bits(prm: Params, norm2: float = 1.0, out_norm2: float = 1.0) -> int:
+    """The narrowest width w >= log2(2N) at which a compact output decodes with at least the margin the parameter set was chosen
+    for: `margin_sigmas(prm, norm2)` with the same skew counted on both sides (a deliberate departure from comparing against
+    `margin_sigmas` as it stands, DESIGN.md section 4 "Compact outputs").  The modulus switch in front of every blind rotation
+    rounds with q treated as 2^46 too, so the inputs the selector admitted carry that skew; `margin_sigmas` leaves it out, and
+    comparing a skew-counted margin against it would ask for a wider field where nothing got worse (p = 31, N = 2048: 5.9986
+    against 6.0017 at log2(2N)).  With out_norm2 <= norm2 -- every bootstrap output of a plain program -- the answer is log2(2N):
+    such an output is no noisier than what the next bootstrap would have read.  31 when no width reaches the margin."""
+    need = margin_sigmas(prm, norm2) * (1.0 - 4.0 * prm.p_msg * compact_output_skew(prm))
+    for bits in range(prm.log_n_poly + 1, 32):
+        if compact_output_margin(prm, bits, out_norm2) >= need * (1.0 - 1e-12):   # (equal variances: w = log2(2N))
+            return bits
+    return 31
+
+
 def p_error(margin: float) -> float:
     """Probability that a Gaussian leaves +-margin standard deviations (one bootstrap)."""
     return math.erfc(margin / math.sqrt(2.0))

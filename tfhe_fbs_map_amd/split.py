@@ -4,15 +4,17 @@ The `Client` picks the parameter set for a program exactly as `ExecConfig.choose
 `Context.keygen_seeded` and hands out a `ServerKey`: the public mask key and the bodies of the evaluation keys (include/
 fbs_exec.h, "seeded keys and inputs").  It encrypts inputs to bodies only (`EncryptedInputs`) and decrypts what comes back.
 The `Server` builds an evaluation-only context from the server key, lowers the program itself, expands the input bodies on
-the GPU and returns full output ciphertexts (`EncryptedOutputs`).  All three objects save to and load from `.npz` files with
-`allow_pickle=False`; none of them holds secret material.
+the GPU and returns either full output ciphertexts (`run` -> `EncryptedOutputs`, kN + 1 words each) or compact ones
+(`run_compact` -> `CompactOutputs`: key-switched to the small key, rounded to a few bits a field and packed, n + 1 fields --
+include/fbs_exec.h, "compact outputs").  All four objects save to and load from `.npz` files with `allow_pickle=False`; none of
+them holds secret material.
 
     client = Client(env, ExecConfig())
     client.server_key().save("server_key.npz")             # -> the server, once
     client.encrypt(inputs).save("inputs.npz")              # -> the server, per evaluation
     server = Server(ServerKey.load("server_key.npz"))
-    server.run(env, EncryptedInputs.load("inputs.npz")).save("outputs.npz")
-    client.decrypt(EncryptedOutputs.load("outputs.npz"))  # == env.eval(inputs)
+    server.run_compact(env, EncryptedInputs.load("inputs.npz")).save("outputs.npz")
+    client.decrypt(CompactOutputs.load("outputs.npz"))    # == env.eval(inputs)
 """
 from __future__ import annotations
 
@@ -21,10 +23,10 @@ from dataclasses import asdict, dataclass
 
 import numpy as np
 
-from .fbs_exec_env import ExecConfig, min_fbs_size, table_is_valid
+from .fbs_exec_env import ExecConfig, min_fbs_size, table_fusion_factor, table_is_valid
 
-__all__ = ["ServerKey", "EncryptedInputs", "EncryptedOutputs", "Client", "Server", "FORMAT_VERSION", "mask_key_fingerprint",
-           "seeded_key_sizes"]
+__all__ = ["ServerKey", "EncryptedInputs", "EncryptedOutputs", "CompactOutputs", "Client", "Server", "FORMAT_VERSION",
+           "mask_key_fingerprint", "seeded_key_sizes", "compact_words", "output_noise_factor"]
 
 FORMAT_VERSION = 1
 _PARAM_FIELDS = ("n", "log_n_poly", "k", "l_bsk", "beta_bsk", "t_ksk", "gamma_ksk", "p_msg", "sigma_lwe", "sigma_glwe",
@@ -40,6 +42,30 @@ def seeded_key_sizes(prm):
     """(bootstrapping-key bodies, key-switching-key bodies) in words for a parameter set: fbs_seeded_key_sizes without a GPU"""
     g = prm.n // 2 * 3 if prm.bsk_group == 2 else prm.n
     return g * (prm.k + 1) * prm.l_bsk * prm.N, prm.k * prm.N * prm.t_ksk
+
+
+def compact_words(prm, bits):
+    """W, the words of one compact ciphertext at width `bits`: fbs_compact_words without a GPU"""
+    return ((prm.n + 1) * int(bits) + 63) // 64
+
+
+def output_noise_factor(low, p, fused=False):
+    """out_norm2 of `params.compact_output_bits`: the worst output's noise in units of one blind rotation's -- 1 for a bootstrap
+    output, `table_fusion_factor` for one cut from a shared rotation (fused programs), the squared norm of the coefficients for a
+    linear combination (over its sources' factors), 0 for inputs and constants (fresh or trivial ciphertexts)."""
+    n_in = len(low["input_names"])
+    readers = {}
+    for kind, a0 in zip(low["kind"], low["arg0"]):
+        if kind == 1:
+            readers[int(a0)] = readers.get(int(a0), 0) + 1
+    noise = [0.0] * n_in
+    for i, kind in enumerate(low["kind"]):
+        a0, a1 = int(low["arg0"][i]), int(low["arg1"][i])
+        if kind == 1:
+            noise.append(float(table_fusion_factor(low["tables"][a1], p)) if fused and readers[a0] >= 2 else 1.0)
+        else:
+            noise.append(sum(float(low["term_coef"][t]) ** 2 * noise[int(low["term_src"][t])] for t in range(a0, a0 + a1)))
+    return max((noise[int(w)] for w in low["out_wire"] if w >= 0), default=0.0)
 
 
 def _load_npz(path, kind):
@@ -157,6 +183,35 @@ class EncryptedOutputs:
         return cls(names, T, cts, _fingerprint_of(d))
 
 
+@dataclass
+class CompactOutputs:
+    """Compact output ciphertexts of one evaluation (`Server.run_compact`): words [n_outputs][T][W], each ciphertext the output
+    key-switched to the small key, rounded to `bits` bits a field and packed (include/fbs_exec.h, "compact outputs")."""
+    output_names: list
+    T: int
+    bits: int
+    words: np.ndarray
+    fingerprint: bytes
+
+    def save(self, path):
+        np.savez(path, kind=np.array("compact_outputs"), format_version=np.array(FORMAT_VERSION),
+                 output_names=np.array(list(self.output_names), dtype=str), T=np.array(self.T, np.int64),
+                 bits=np.array(self.bits, np.int64), words=np.ascontiguousarray(self.words, np.uint64),
+                 fingerprint=np.frombuffer(self.fingerprint, np.uint8))
+
+    @classmethod
+    def load(cls, path):
+        d = _load_npz(path, "compact_outputs")
+        names = [str(n) for n in np.asarray(d["output_names"]).reshape(-1)]
+        T, bits = int(d["T"]), int(d["bits"])
+        words = np.asarray(d["words"])
+        if not 1 <= bits <= 31:
+            raise ValueError(f"a compact width of {bits} bits")
+        if words.dtype != np.uint64 or words.ndim != 3 or words.shape[:2] != (len(names), T):
+            raise ValueError(f"compact ciphertexts of shape {words.shape} for {len(names)} outputs of {T} samples")
+        return cls(names, T, bits, words, _fingerprint_of(d))
+
+
 class Client:
     """Holds the secret.  Chooses (parameter set, fuse) for `env` with the rules of `ExecConfig.choose`, keys a context with
     `keygen_seeded`, encrypts inputs to bodies and decrypts outputs."""
@@ -195,14 +250,21 @@ class Client:
         bodies, first = self.ctx.encrypt_seeded(bits, nonce0=self.config.nonce0 if nonce0 is None else nonce0)
         return EncryptedInputs(list(names), T, first, bodies.reshape(len(names), T), self.fingerprint)
 
-    def decrypt(self, outputs: EncryptedOutputs):
-        """-> exactly what `LutExecEnv.eval` returns: {output name: np.ndarray of ints}, constant outputs as python ints"""
+    def decrypt(self, outputs):
+        """EncryptedOutputs or CompactOutputs -> exactly what `LutExecEnv.eval` returns: {output name: np.ndarray of ints},
+        constant outputs as python ints"""
         low = self._low
         if outputs.fingerprint != self.fingerprint:
             raise ValueError("outputs were computed under another server key")
         if list(outputs.output_names) != list(low["out_names"]):
             raise ValueError("outputs belong to another program")
-        out = self.ctx.decrypt(outputs.cts) if outputs.cts.size else np.zeros(outputs.cts.shape[:2], np.int64)
+        if isinstance(outputs, CompactOutputs):
+            bits, words = int(outputs.bits), outputs.words
+            if not self.params.log_n_poly + 1 <= bits <= 31 or words.shape[-1] != compact_words(self.params, bits):
+                raise ValueError(f"compact ciphertexts of {words.shape[-1]} words at {bits} bits do not fit this parameter set")
+            out = self.ctx.decrypt_compact(words, bits) if words.size else np.zeros(words.shape[:2], np.int64)
+        else:
+            out = self.ctx.decrypt(outputs.cts) if outputs.cts.size else np.zeros(outputs.cts.shape[:2], np.int64)
         result = {}
         for k, name in enumerate(low["out_names"]):
             w = low["out_wire"][k]
@@ -248,3 +310,24 @@ class Server:
             raise ValueError("inputs belong to another program")
         cts = prog.eval_seeded(inputs.bodies, inputs.T, inputs.nonce0)
         return EncryptedOutputs(list(low["out_names"]), inputs.T, cts, self.key.fingerprint)
+
+    def compact_bits(self, env):
+        """The width `run_compact` uses by default: `params.compact_output_bits` for the server key's parameter set, the program's
+        norm2 (the statistic its parameter set was chosen for: `stats`, or `fusion_stats` when tables share rotations) and its
+        worst output's noise (`output_noise_factor`)."""
+        from .params import compact_output_bits
+        prm, low = self.key.params, env.lower()
+        norm2 = (env.fusion_stats(prm.p_msg) if self.key.fuse_tables else env.stats())["norm2_linprod"]
+        return compact_output_bits(prm, norm2, output_noise_factor(low, prm.p_msg, self.key.fuse_tables))
+
+    def run_compact(self, env, inputs: EncryptedInputs, bits=None) -> CompactOutputs:
+        """`run` with compact outputs (fbs_eval_seeded_compact): [n_outputs][T][W] words instead of [n_outputs][T][kN + 1];
+        bits=None: `compact_bits(env)`."""
+        if inputs.fingerprint != self.key.fingerprint:
+            raise ValueError("inputs were encrypted for another server key")
+        prog, low = self.program_for(env)
+        if list(inputs.input_names) != list(low["input_names"]):
+            raise ValueError("inputs belong to another program")
+        bits = self.compact_bits(env) if bits is None else int(bits)
+        words = prog.eval_seeded_compact(inputs.bodies, inputs.T, inputs.nonce0, bits)
+        return CompactOutputs(list(low["out_names"]), inputs.T, bits, words, self.key.fingerprint)
