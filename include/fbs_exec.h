@@ -347,6 +347,39 @@ int fbs_eval_seeded_compact(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies
 int fbs_decrypt_compact(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs);
 int fbs_decrypt_compact_dev(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, int64_t *d_msgs, void *stream);
 
+/* ---- chained evaluation: one program's outputs as the next one's inputs, under the same evaluation keys ------------------
+ * A compact ciphertext goes back into a program through a REFRESH: its fields are unpacked to b = log2(2N) bits into the rows
+ * the blind rotation reads -- at w = b word for word what the modulus switch would have left, at w > b re-rounded by the header
+ * formula above with 2^w in place of 2^46 (sh = w - b; round the mask fields, eps = sum of their signed errors in 64 bits,
+ * body' = (m_n - floor(eps / 2)) mod 2^w, round the body) -- and one blind rotation through the identity table [0, 1, .., p - 1]
+ * writes a fresh big-key ciphertext of the same value (every value in [0, p); program inputs are bits).  It costs one bootstrap
+ * per ciphertext and carries that bootstrap's noise, whatever the link's.  None of these entries needs a secret. */
+/* d_words [count][W] at width `bits` -> the fields d_fields [count][n + 1] (uint32, < 2^log2(2N)), asynchronous on `stream` */
+int fbs_compact_fields_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint32_t *d_fields, void *stream);
+/* d_words [count][W] -> refreshed big-key ciphertexts d_cts [count][D+1], asynchronous on `stream`.  At bits = log2(2N) equal
+ * to fbs_bootstrap_batch_dev of the ciphertexts fbs_compact_dev packed, through the identity table.  In passes of the
+ * modulus-switch scratch (of at least 8192 ciphertexts), like fbs_compact_dev. */
+int fbs_refresh_compact_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint64_t *d_cts, void *stream);
+
+#define FBS_SRC_SEEDED 0u    /* the client's seeded inputs: data = [T] bodies of streams nonce0 + s */
+#define FBS_SRC_FULL 1u      /* full ciphertexts of an earlier evaluation: data = [T][D+1] */
+#define FBS_SRC_COMPACT 2u   /* compact ciphertexts of an earlier evaluation: data = [T][W] at width `bits` */
+typedef struct fbs_input_src {
+    uint32_t kind;        /* FBS_SRC_* */
+    uint32_t bits;        /* COMPACT: its width w */
+    uint32_t refresh;     /* FULL: 1 = bootstrap through the identity table before use (COMPACT: always; SEEDED: never) */
+    uint64_t nonce0;      /* SEEDED: sample s on stream nonce0 + s */
+    const uint64_t *data; /* host memory */
+} fbs_input_src;
+/* One evaluation whose input i comes from src[i], any mix of the three kinds.  out_bits = 0: full outputs out [n_outputs][T][D+1]
+ * (as fbs_eval_seeded); else compact outputs out [n_outputs][T][W] at that width (as fbs_eval_seeded_compact).  The same chunks
+ * as fbs_eval; full inputs marked `refresh` go through the ordinary key switch and modulus switch, then the identity rotation.
+ * With every source seeded at nonce0 + i T the outputs are word for word those of fbs_eval_seeded (out_bits = 0) and of
+ * fbs_eval_seeded_compact (out_bits = w).  Refused with FBS_E_INVALID, nothing written: an unknown kind, null data, a compact
+ * width outside [log2(2N), 31], streams past 2^56, T * words overflowing.  Repeated calls of one shape do not grow scratch.
+ * T = 0 does nothing.  Blocks until the outputs are back. */
+int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, size_t T, uint32_t out_bits, uint64_t *out);
+
 /* ---- a loaded program, one level at a time (multi-GPU hosts) -----------------
  * The two independent axes of the reference's eval loop (fbs_exec_env.py:211-223) are the gates
  * of a bootstrap level and the samples.  A host that shards the GATES of a level over several

@@ -47,6 +47,14 @@ class _ProgramDesc(C.Structure):
                 ("out_wire", C.c_void_p)]
 
 
+class _InputSrc(C.Structure):   # fbs_input_src (include/fbs_exec.h, "chained evaluation")
+    _fields_ = [("kind", C.c_uint32), ("bits", C.c_uint32), ("refresh", C.c_uint32), ("nonce0", C.c_uint64),
+                ("data", C.c_void_p)]
+
+
+SRC_SEEDED, SRC_FULL, SRC_COMPACT = 0, 1, 2   # FBS_SRC_*
+
+
 @dataclass(frozen=True)
 class Params:
     """Cryptographic parameter set.  The shape defaults to BASELINE.md's synthetic set (n=630 N=1024 k=1 l=3 beta=7
@@ -166,6 +174,9 @@ def _load():
         "fbs_eval_seeded_compact": (i32, [vp, vp, vp, sz, u64, u32, vp]),
         "fbs_decrypt_compact": (i32, [vp, vp, sz, u32, vp]),
         "fbs_decrypt_compact_dev": (i32, [vp, vp, sz, u32, vp, vp]),
+        "fbs_compact_fields_dev": (i32, [vp, vp, sz, u32, vp, vp]),
+        "fbs_refresh_compact_dev": (i32, [vp, vp, sz, u32, vp, vp]),
+        "fbs_eval_sources": (i32, [vp, vp, vp, sz, u32, vp]),
         "fbs_tvset_create": (i32, [vp, vp, vp, u32, C.POINTER(vp)]),
         "fbs_tvset_destroy": (None, [vp]),
         "fbs_bootstrap_batch": (i32, [vp, vp, vp, vp, sz, vp]),
@@ -222,6 +233,7 @@ EXPORTED_SYMBOLS = (
     "fbs_encrypt_seeded_fresh", "fbs_encrypt_seeded_dev", "fbs_encrypt_seeded_fresh_dev", "fbs_expand_seeded",
     "fbs_expand_seeded_dev", "fbs_eval_seeded",
     "fbs_compact_words", "fbs_compact_dev", "fbs_eval_seeded_compact", "fbs_decrypt_compact", "fbs_decrypt_compact_dev",
+    "fbs_compact_fields_dev", "fbs_refresh_compact_dev", "fbs_eval_sources",
 )
 
 lib = _load()
@@ -332,6 +344,36 @@ class Program:
         bodies = _c(bodies, np.uint64).reshape(self.n_inputs, T)
         out = np.empty((self.n_outputs, T, self.ctx.compact_words(bits)), np.uint64)
         self.ctx._check(lib.fbs_eval_seeded_compact(self.ctx._h, self._h, _ptr(bodies), T, int(nonce0), bits, _ptr(out)))
+        return out
+
+    def eval_sources(self, sources, T, bits=0):
+        """Inputs from any mix of sources (fbs_eval_sources), one per input in input order:
+            ("seeded", bodies [T], nonce0)     -- sample s on stream nonce0 + s (`Context.encrypt_seeded`)
+            ("full", cts [T][D+1], refresh)    -- outputs of an earlier evaluation; refresh=True: through the identity table first
+            ("compact", words [T][W], bits)    -- compact outputs of an earlier evaluation, always refreshed
+        bits = 0: full outputs [n_outputs][T][D+1] (as `eval_seeded`); else compact [n_outputs][T][W] at that width (as
+        `eval_seeded_compact`).  Needs no secret."""
+        if len(sources) != self.n_inputs:
+            raise ValueError(f"{len(sources)} sources for {self.n_inputs} inputs")
+        arr, keep = (_InputSrc * max(1, self.n_inputs))(), []
+        ctw = self.ctx.params.ct_words
+        for i, (kind, data, arg) in enumerate(sources):
+            if kind == "seeded":
+                a = _c(data, np.uint64).reshape(T)
+                arr[i] = _InputSrc(SRC_SEEDED, 0, 0, int(arg), a.ctypes.data)
+            elif kind == "full":
+                a = _c(data, np.uint64).reshape(T, ctw)
+                arr[i] = _InputSrc(SRC_FULL, 0, int(bool(arg)), 0, a.ctypes.data)
+            elif kind == "compact":
+                a = _c(data, np.uint64).reshape(T, -1)
+                arr[i] = _InputSrc(SRC_COMPACT, int(arg), 1, 0, a.ctypes.data)
+            else:
+                raise ValueError(f"unknown source kind {kind!r}")
+            keep.append(a)
+        bits = int(bits)
+        shape = (self.n_outputs, T, self.ctx.compact_words(bits) if bits else ctw)
+        out = np.empty(shape, np.uint64)
+        self.ctx._check(lib.fbs_eval_sources(self.ctx._h, self._h, C.byref(arr), T, bits, _ptr(out)))
         return out
 
     # device-pointer entry points (ints from torch.Tensor.data_ptr()); asynchronous on `stream`, no host copies
@@ -575,6 +617,18 @@ class Context:
                                                 None))
         self.sync()
         return d_m[:out.size].cpu().numpy().reshape(out.shape)
+
+    def compact_fields_dev(self, d_words, count, d_fields, bits=None, stream=0):
+        """fbs_compact_fields_dev: [count][W] words at width `bits` -> uint32 fields [count][n + 1] at log2(2N) bits (what the
+        blind rotation reads), asynchronous on `stream`"""
+        self._check(lib.fbs_compact_fields_dev(self._h, d_words or None, count, self.default_compact_bits if bits is None else int(bits),
+                                               d_fields or None, stream or None))
+
+    def refresh_compact_dev(self, d_words, count, d_cts, bits=None, stream=0):
+        """fbs_refresh_compact_dev: [count][W] words -> fresh big-key ciphertexts [count][D+1] (one bootstrap through the identity
+        table each), asynchronous on `stream`; needs no secret"""
+        self._check(lib.fbs_refresh_compact_dev(self._h, d_words or None, count, self.default_compact_bits if bits is None else int(bits),
+                                                d_cts or None, stream or None))
 
     def decrypt_compact_dev(self, d_words, count, d_msgs, bits=None, stream=0):
         self._check(lib.fbs_decrypt_compact_dev(self._h, d_words or None, count, self.default_compact_bits if bits is None else int(bits),

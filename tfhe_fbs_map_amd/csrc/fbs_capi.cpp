@@ -272,6 +272,7 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
                     (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_sk_lwe_bits, (void *)ctx->d_io_msgs,
                     (void *)ctx->d_compact})
         if (p) (void)hipFree(p);
+    fbs_tvset_destroy(ctx->tv_identity);
     if (ctx->scratch_event) (void)hipEventDestroy(ctx->scratch_event);
     for (auto &v : ctx->prof.pending)
         for (auto &pr : v) {
@@ -1269,9 +1270,52 @@ int fbs_compact_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t 
     return scratch_done(ctx, s);
 } FBS_API_CATCH(ctx)
 
-// fbs_eval_seeded with another store stage: the output slots of a chunk are key-switched and packed on the device in groups of
-// outputs whose rows fit the modulus-switch scratch reserve_wires sized (max_sources x Tc rows), and only the packed words are
-// copied back.  The packed staging of a group is counted in the chunk's budget.
+// The compact store stage (fbs_eval_seeded_compact, fbs_eval_sources): the output slots of a chunk are key-switched and packed on
+// the device in groups of outputs whose rows fit the modulus-switch scratch reserve_wires sized (max_sources x Tc rows), and only
+// the packed words are copied back; a constant output is the compaction of the trivial ciphertext fbs_eval_seeded returns for it.
+// The caller counts the packed staging (cap_rows x W words) in the chunk's budget and grows d_compact to it.
+struct CompactStore {
+    uint32_t bits = 0;
+    size_t W = 0, cap_rows = 0;
+    std::vector<uint64_t> constant;   // [n_outputs][W]
+};
+static CompactStore compact_store_for(const fbs_ctx *ctx, const fbs_prog *prog, uint32_t bits, size_t Tc) {
+    CompactStore cs;
+    cs.bits = bits;
+    cs.W = compact_words(ctx->p.n, bits);
+    cs.cap_rows = (size_t)std::max(1u, prog->max_sources) * Tc;   // (ensure_ms has made d_ms at least this long)
+    cs.constant.assign((size_t)prog->n_outputs * cs.W, 0);
+    for (size_t o = 0; o < prog->n_outputs; o++)
+        if (prog->out_slot[o] < 0) host_compact_trivial(ctx, trivial_body(ctx, prog->out_slot[o]), bits, cs.constant.data() + o * cs.W);
+    return cs;
+}
+static int store_compact(fbs_ctx *ctx, const fbs_prog *prog, const CompactStore &cs, uint64_t *out_words, size_t T, size_t Tc,
+                         size_t s0, size_t tc, hipStream_t s) {
+    const size_t W = cs.W, n_live = prog->live_out.size(), group = std::max<size_t>(1, cs.cap_rows / tc);
+    for (size_t g0 = 0; g0 < n_live; g0 += group) {
+        const size_t ng = std::min(group, n_live - g0), rows = ng * tc;
+        GateView gv{};
+        gv.in_base = ctx->d_wires;
+        gv.src_slot = prog->d_live_slot + g0;
+        gv.T = Tc;
+        gv.s_begin = 0;
+        gv.s_count = tc;
+        gv.count = rows;
+        gv.ks_count = rows;
+        gv.n_gates = (uint32_t)ng;
+        if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, cs.bits, s)) return rc;
+        if (int rc = dev_compact_pack(ctx, ctx->d_ms, rows, cs.bits, ctx->d_compact, s)) return rc;
+        for (size_t i = 0; i < ng; i++)
+            FBS_HIP(ctx, hipMemcpyAsync(out_words + ((size_t)prog->live_out[g0 + i] * T + s0) * W, ctx->d_compact + i * tc * W, tc * W * 8,
+                                        hipMemcpyDeviceToHost, s));
+    }
+    for (size_t o = 0; o < prog->n_outputs; o++)
+        if (prog->out_slot[o] < 0)
+            for (size_t q = 0; q < tc; q++) std::memcpy(out_words + (o * T + s0 + q) * W, cs.constant.data() + o * W, W * 8);
+    return FBS_OK;
+}
+
+// fbs_eval_seeded with the compact store stage
 int fbs_eval_seeded_compact(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t T, uint64_t nonce0, uint32_t bits,
                             uint64_t *out_words) try {
     int rc = check_eval(ctx, prog, bodies, T, out_words);
@@ -1286,41 +1330,14 @@ int fbs_eval_seeded_compact(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies
     size_t Tc = 0;
     if ((rc = reserve_wires(ctx, prog, T, &Tc, rows_per_sample * W * 8)) != FBS_OK) return rc;
     if ((rc = ensure_io_msgs(ctx, std::max<size_t>(1, n_in) * Tc)) != FBS_OK) return rc;
-    const size_t cap_rows = rows_per_sample * Tc;   // (ensure_ms has made d_ms at least this long)
-    if ((rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, cap_rows * W, 8, true)) != FBS_OK) return rc;
-    // a constant output: the compaction of the trivial ciphertext fbs_eval_seeded returns for it
-    std::vector<uint64_t> constant((size_t)n_out * W, 0);
-    for (size_t o = 0; o < n_out; o++)
-        if (prog->out_slot[o] < 0) host_compact_trivial(ctx, trivial_body(ctx, prog->out_slot[o]), bits, constant.data() + o * W);
+    const CompactStore cs = compact_store_for(ctx, prog, bits, Tc);
+    if ((rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, cs.cap_rows * W, 8, true)) != FBS_OK) return rc;
     auto load = [&](size_t s0, size_t tc) {
         if (!n_in) return FBS_OK;
         FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_io_msgs, Tc * 8, bodies + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
         return dev_expand_seeded(ctx, IoView{ctx->d_io_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc}, nonce0 + s0, T, s);
     };
-    auto store = [&](size_t s0, size_t tc) {
-        const size_t n_live = prog->live_out.size(), group = std::max<size_t>(1, cap_rows / tc);
-        for (size_t g0 = 0; g0 < n_live; g0 += group) {
-            const size_t ng = std::min(group, n_live - g0), rows = ng * tc;
-            GateView gv{};
-            gv.in_base = ctx->d_wires;
-            gv.src_slot = prog->d_live_slot + g0;
-            gv.T = Tc;
-            gv.s_begin = 0;
-            gv.s_count = tc;
-            gv.count = rows;
-            gv.ks_count = rows;
-            gv.n_gates = (uint32_t)ng;
-            if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, bits, s)) return rc;
-            if (int rc = dev_compact_pack(ctx, ctx->d_ms, rows, bits, ctx->d_compact, s)) return rc;
-            for (size_t i = 0; i < ng; i++)
-                FBS_HIP(ctx, hipMemcpyAsync(out_words + ((size_t)prog->live_out[g0 + i] * T + s0) * W, ctx->d_compact + i * tc * W, tc * W * 8,
-                                            hipMemcpyDeviceToHost, s));
-        }
-        for (size_t o = 0; o < n_out; o++)
-            if (prog->out_slot[o] < 0)
-                for (size_t q = 0; q < tc; q++) std::memcpy(out_words + (o * T + s0 + q) * W, constant.data() + o * W, W * 8);
-        return FBS_OK;
-    };
+    auto store = [&](size_t s0, size_t tc) { return store_compact(ctx, prog, cs, out_words, T, Tc, s0, tc, s); };
     return eval_chunks(ctx, prog, T, Tc, s, true, load, store);
 } FBS_API_CATCH(ctx)
 
@@ -1339,6 +1356,187 @@ int fbs_decrypt_compact_dev(const fbs_ctx *ctx, const uint64_t *d_words, size_t 
     if (count == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     return dev_decrypt_compact(ctx, d_words, count, bits, d_msgs, pick(ctx, stream));
+} FBS_API_CATCH(ctx)
+
+// ---- chained evaluation: compact ciphertexts back into the blind rotation, and programs over mixed input sources ------------
+// the context's identity table [0, 1, .., p - 1], made on first use: a blind rotation through it is a refresh
+static int identity_tv(fbs_ctx *ctx, fbs_tvset **out) {
+    if (!ctx->tv_identity) {
+        std::vector<int32_t> vals(ctx->p.p_msg);
+        for (uint32_t v = 0; v < ctx->p.p_msg; v++) vals[v] = (int32_t)v;
+        const uint32_t off[2] = {0, ctx->p.p_msg};
+        if (int rc = fbs_tvset_create(ctx, vals.data(), off, 1, &ctx->tv_identity)) return rc;
+    }
+    *out = ctx->tv_identity;
+    return FBS_OK;
+}
+
+// (no secret needed; no scratch: the fields go straight to the caller's buffer)
+int fbs_compact_fields_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint32_t *d_fields, void *stream) try {
+    if (int rc = io_prologue(ctx, d_words, d_fields, count, 0, nullptr)) return rc;
+    if (int rc = check_bits(ctx, bits)) return rc;
+    if (int rc = check_compact_words(ctx, count, bits)) return rc;
+    if (count > SIZE_MAX / 4 / (ctx->p.n + 1)) return set_error(ctx, FBS_E_INVALID, "count * (n + 1) fields overflow");
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_compact_unpack(ctx, d_words, count, bits, d_fields, pick(ctx, stream));
+} FBS_API_CATCH(ctx)
+
+// unpack into the modulus-switch scratch, then one blind rotation through the identity table: in passes like fbs_compact_dev
+int fbs_refresh_compact_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint64_t *d_cts, void *stream) try {
+    if (int rc = io_prologue(ctx, d_words, d_cts, count, IO_CT_WORDS, nullptr)) return rc;
+    if (int rc = check_bits(ctx, bits)) return rc;
+    if (int rc = check_compact_words(ctx, count, bits)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    fbs_tvset *tv = nullptr;
+    int rc = identity_tv(ctx, &tv);
+    if (rc != FBS_OK) return rc;
+    const size_t pass = std::min(count, std::max(ctx->ms_capacity, COMPACT_PASS)), ctw = ctx->D + 1, W = compact_words(ctx->p.n, bits);
+    if ((rc = ensure_ms(ctx, pass)) != FBS_OK) return rc;
+    hipStream_t s = pick(ctx, stream);
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    for (size_t f0 = 0; f0 < count; f0 += pass) {
+        const size_t rows = std::min(pass, count - f0);
+        if ((rc = dev_compact_unpack(ctx, d_words + f0 * W, rows, bits, ctx->d_ms, s)) ||
+            (rc = dev_blind_rotate(ctx, tv, batch_view(nullptr, d_cts + f0 * ctw, nullptr, rows), ctx->d_ms, s)))
+            return scratch_fail(ctx, s, rc);
+    }
+    return scratch_done(ctx, s);
+} FBS_API_CATCH(ctx)
+
+// the refresh of `ng` input slots (d_slot [ng], device) of a chunk whose rows d_ms [ng][tc][n + 1] hold already: a blind rotation
+// through the identity table written back into the same slots
+static int refresh_slots(fbs_ctx *ctx, const fbs_tvset *tv, const uint32_t *d_slot, size_t ng, size_t Tc, size_t tc, hipStream_t s) {
+    GateView gv{};
+    gv.in_base = ctx->d_wires;
+    gv.out_base = ctx->d_wires;
+    gv.src_slot = d_slot;
+    gv.dst_slot = d_slot;
+    gv.T = Tc;
+    gv.s_begin = 0;
+    gv.s_count = tc;
+    gv.f_begin = 0;
+    gv.count = ng * tc;
+    gv.ks_begin = 0;
+    gv.ks_count = ng * tc;
+    gv.n_gates = (uint32_t)ng;
+    return dev_blind_rotate(ctx, tv, gv, ctx->d_ms, s);
+}
+
+// One more pair of stages on eval_chunks.  Load: the full inputs are copied into their slots; runs of seeded inputs whose streams
+// step by T (and whose bodies lie T words apart) are expanded by one dev_expand_seeded each; compact inputs are staged in the packed
+// buffer, unpacked into the modulus-switch scratch and refreshed, and full inputs marked `refresh` are key-switched, modulus-switched
+// and refreshed in place -- both in groups whose rows fit the scratch reserve_wires sized (max_sources x Tc rows).  Store: that of
+// fbs_eval_seeded (out_bits = 0) or fbs_eval_seeded_compact.
+int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, size_t T, uint32_t out_bits, uint64_t *out) try {
+    int rc = check_eval(ctx, prog, src, T, out);
+    if (rc != FBS_OK) return rc;
+    if (out_bits && (rc = check_bits(ctx, out_bits)) != FBS_OK) return rc;
+    if (T == 0) return FBS_OK;
+    const size_t n_in = prog->n_inputs, n_out = prog->n_outputs, ctw = ctx->D + 1, W_out = out_bits ? compact_words(ctx->p.n, out_bits) : 0;
+    // every source is checked before anything is reserved, copied or launched
+    size_t W_in = 0;
+    std::vector<uint32_t> compact_in, full_refresh;   // input indices
+    bool any_seeded = false;
+    for (size_t i = 0; i < n_in; i++) {
+        const fbs_input_src &x = src[i];
+        const std::string who = "input " + std::to_string(i) + ": ";
+        if (x.kind > FBS_SRC_COMPACT) return set_error(ctx, FBS_E_INVALID, who + "unknown source kind " + std::to_string(x.kind));
+        if (!x.data) return set_error(ctx, FBS_E_INVALID, who + "null data");
+        size_t words = x.kind == FBS_SRC_SEEDED ? 1 : ctw;
+        if (x.kind == FBS_SRC_COMPACT) {
+            if ((rc = check_bits(ctx, x.bits)) != FBS_OK) return rc;
+            words = compact_words(ctx->p.n, x.bits);
+            W_in = std::max(W_in, words);
+            compact_in.push_back((uint32_t)i);
+        }
+        if (x.kind == FBS_SRC_SEEDED) {
+            if ((rc = check_seeded_streams(ctx, x.nonce0, T)) != FBS_OK) return rc;
+            any_seeded = true;
+        }
+        if (x.kind == FBS_SRC_FULL && x.refresh) full_refresh.push_back((uint32_t)i);
+        if (T > SIZE_MAX / 8 / words) return set_error(ctx, FBS_E_INVALID, who + "T * words overflow");
+    }
+    if (T > SIZE_MAX / 8 / std::max<size_t>(1, n_out) / std::max(ctw, W_out)) return set_error(ctx, FBS_E_INVALID, "n_outputs * T words overflow");
+    hipStream_t s = ctx->stream;
+    const size_t W_stage = std::max(W_in, W_out), rows_per_sample = std::max(1u, prog->max_sources);
+    size_t Tc = 0;
+    if ((rc = reserve_wires(ctx, prog, T, &Tc, rows_per_sample * W_stage * 8)) != FBS_OK) return rc;
+    if (any_seeded && (rc = ensure_io_msgs(ctx, n_in * Tc)) != FBS_OK) return rc;
+    const size_t cap_rows = rows_per_sample * Tc;   // (ensure_ms has made d_ms at least this long)
+    if (W_stage && (rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, cap_rows * W_stage, 8, true)) != FBS_OK) return rc;
+    // the slots to refresh, compact inputs first: uploaded with the first chunk (after eval_chunks's scratch_wait)
+    std::vector<uint32_t> refresh_slot;
+    for (uint32_t i : compact_in) refresh_slot.push_back(prog->in_slot[i]);
+    for (uint32_t i : full_refresh) refresh_slot.push_back(prog->in_slot[i]);
+    const fbs_tvset *tv = nullptr;
+    if (!refresh_slot.empty()) {
+        fbs_tvset *made = nullptr;
+        if ((rc = identity_tv(ctx, &made)) != FBS_OK || (rc = ensure_idx(ctx, refresh_slot.size())) != FBS_OK) return rc;
+        tv = made;
+    }
+    CompactStore cs;
+    if (out_bits) cs = compact_store_for(ctx, prog, out_bits, Tc);
+    const size_t n1 = ctx->p.n + 1;
+    auto load = [&](size_t s0, size_t tc) {
+        if (s0 == 0 && !refresh_slot.empty())
+            FBS_HIP(ctx, hipMemcpyAsync(ctx->d_idx, refresh_slot.data(), refresh_slot.size() * 4, hipMemcpyHostToDevice, s));
+        for (size_t i = 0; i < n_in; i++)
+            if (src[i].kind == FBS_SRC_FULL)
+                FBS_HIP(ctx, hipMemcpyAsync(ctx->d_wires + (size_t)prog->in_slot[i] * Tc * ctw, src[i].data + s0 * ctw, tc * ctw * 8,
+                                            hipMemcpyHostToDevice, s));
+        for (size_t i0 = 0; i0 < n_in;) {   // seeded runs: streams nonce0 + r T + s over the run's rows r
+            if (src[i0].kind != FBS_SRC_SEEDED) {
+                i0++;
+                continue;
+            }
+            size_t i1 = i0 + 1;
+            while (i1 < n_in && src[i1].kind == FBS_SRC_SEEDED && src[i1].nonce0 == src[i1 - 1].nonce0 + T) i1++;
+            for (size_t j0 = i0; j0 < i1;) {   // the bodies: one 2D copy per stretch whose rows lie T words apart
+                size_t j1 = j0 + 1;
+                while (j1 < i1 && src[j1].data == src[j1 - 1].data + T) j1++;
+                FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_io_msgs + j0 * Tc, Tc * 8, src[j0].data + s0, T * 8, tc * 8, j1 - j0, hipMemcpyHostToDevice, s));
+                j0 = j1;
+            }
+            IoView v{ctx->d_io_msgs + i0 * Tc, Tc, ctx->d_wires, prog->d_in_slot + i0, Tc, i1 - i0, tc};
+            if (int rc = dev_expand_seeded(ctx, v, src[i0].nonce0 + s0, T, s)) return rc;
+            i0 = i1;
+        }
+        const size_t group = std::max<size_t>(1, cap_rows / tc);
+        for (size_t g0 = 0; g0 < compact_in.size(); g0 += group) {
+            const size_t ng = std::min(group, compact_in.size() - g0);
+            size_t staged = 0;
+            for (size_t j = 0; j < ng; j++) {
+                const fbs_input_src &x = src[compact_in[g0 + j]];
+                const size_t W = compact_words(ctx->p.n, x.bits);
+                FBS_HIP(ctx, hipMemcpyAsync(ctx->d_compact + staged, x.data + s0 * W, tc * W * 8, hipMemcpyHostToDevice, s));
+                if (int rc = dev_compact_unpack(ctx, ctx->d_compact + staged, tc, x.bits, ctx->d_ms + j * tc * n1, s)) return rc;
+                staged += tc * W;
+            }
+            if (int rc = refresh_slots(ctx, tv, ctx->d_idx + g0, ng, Tc, tc, s)) return rc;
+        }
+        for (size_t g0 = 0; g0 < full_refresh.size(); g0 += group) {
+            const size_t ng = std::min(group, full_refresh.size() - g0);
+            const uint32_t *d_slot = ctx->d_idx + compact_in.size() + g0;
+            GateView gv{};
+            gv.in_base = ctx->d_wires;
+            gv.src_slot = d_slot;
+            gv.T = Tc;
+            gv.s_begin = 0;
+            gv.s_count = tc;
+            gv.count = ng * tc;
+            gv.ks_count = ng * tc;
+            gv.n_gates = (uint32_t)ng;
+            if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) return rc;
+            if (int rc = refresh_slots(ctx, tv, d_slot, ng, Tc, tc, s)) return rc;
+        }
+        return FBS_OK;
+    };
+    auto store = [&](size_t s0, size_t tc) {
+        return out_bits ? store_compact(ctx, prog, cs, out, T, Tc, s0, tc, s) : store_host_cts(ctx, prog, out, T, Tc, s0, tc, s);
+    };
+    return eval_chunks(ctx, prog, T, Tc, s, true, load, store);
 } FBS_API_CATCH(ctx)
 
 // ---------------------------------------------------------------------------------------------

@@ -22,6 +22,15 @@ FBS_HD uint32_t compact_round(uint64_t x, uint32_t bits) {
     return (uint32_t)(((x >> (sh - 1)) + 1) >> 1) & ((1u << bits) - 1u);
 }
 
+// the modulus switch from 2^w down to 2^b (sh = w - b >= 1): a mask field x < 2^w -> round(x / 2^sh), not yet reduced mod 2^b
+FBS_HD uint32_t compact_reround(uint32_t x, uint32_t sh) { return ((x >> (sh - 1)) + 1) >> 1; }
+// the body of that switch: body' = (x_n - floor(eps / 2)) mod 2^w with eps the sum of the mask fields' signed errors
+// x_i - (round(x_i / 2^sh) << sh), then rounded like a mask field (reduce mod 2^b after)
+FBS_HD uint32_t compact_reround_body(uint32_t body, int64_t eps, uint32_t bits, uint32_t sh) {
+    const uint32_t b2 = (uint32_t)((int64_t)body - (eps >> 1)) & ((1u << bits) - 1u);   // (>> floors)
+    return compact_reround(b2, sh);
+}
+
 // field i of a packed ciphertext (fields never straddle more than two words: bits <= 31)
 FBS_HD uint32_t compact_field(const uint64_t *ct, uint32_t i, uint32_t bits) {
     const uint64_t b = (uint64_t)i * bits;

@@ -172,7 +172,8 @@ struct fbs_ctx {
     uint32_t *d_sk_bits = nullptr;   // [ceil(D / 32)] the GLWE secret key as packed bits (device encryption / decryption, fbs_io.hip)
     uint32_t *d_sk_lwe_bits = nullptr;   // [ceil(n / 32)] the small LWE key as packed bits (decryption of compact outputs)
     uint64_t *d_compact = nullptr;   // scratch: packed compact ciphertexts of fbs_eval_seeded_compact's output groups
-    size_t compact_capacity = 0;     // in words
+    size_t compact_capacity = 0;     // in words (also the staging of compact inputs, fbs_eval_sources)
+    fbs_tvset *tv_identity = nullptr;   // the identity table [0, 1, .., p - 1], made on first use: what refreshes a compact input
     int64_t *d_io_msgs = nullptr;    // scratch: messages of fbs_eval_messages, [n_inputs + n_outputs][chunk]
     size_t io_msgs_capacity = 0;     // in words
     uint64_t *d_wires = nullptr;     // wire slots of fbs_eval, shared by every program of the context
@@ -321,6 +322,9 @@ int dev_expand_seeded(const fbs_ctx *ctx, const IoView &v, uint64_t nonce0, uint
 // packed words under the small key (d_sk_lwe_bits), word for word host_decrypt_compact
 int dev_compact_pack(const fbs_ctx *ctx, const uint32_t *d_ms, size_t count, uint32_t bits, uint64_t *d_words, hipStream_t stream);
 int dev_decrypt_compact(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, int64_t *d_msgs, hipStream_t stream);
+// and back: packed words [count][W] at width `bits` -> the fields at log2(2N) bits, d_ms [count][n + 1] as the blind rotation reads them
+// (re-rounded as the modulus switch rounds when bits > log2(2N))
+int dev_compact_unpack(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint32_t *d_ms, hipStream_t stream);
 
 // profiling helpers
 void prof_begin(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t *e0, hipEvent_t *e1);

@@ -146,6 +146,31 @@ def compact_output_bits(prm: Params, norm2: float = 1.0, out_norm2: float = 1.0)
     return 31
 
 
+# ---- chained evaluation (include/fbs_exec.h, "chained evaluation") -------------------------------------------------------------
+def refresh_input_variance(prm: Params, bits: int | None = None, out_norm2: float = 1.0) -> float:
+    """Phase variance of what the refresh of a linked input rotates by.  A compact link (`bits` = its width w): the compact
+    output's own variance (`compact_output_variance`), plus the modulus switch from 2^w down to 2N when w > log2(2N) (at w =
+    log2(2N) the fields are already what the blind rotation reads).  A full link (bits=None): the ordinary bootstrap input at
+    norm2 = out_norm2 -- its producer's noise, the key switch and the modulus switch."""
+    v_br, v_ks, v_ms = variances(prm)
+    if bits is None:
+        return out_norm2 * v_br + v_ks + v_ms
+    return compact_output_variance(prm, bits, out_norm2) + (v_ms if bits > prm.log_n_poly + 1 else 0.0)
+
+
+def refresh_margin(prm: Params, bits: int | None = None, out_norm2: float = 1.0) -> float:
+    """Standard deviations between the phase a refresh reads and the edge of its box, (q/(4p) - skew) / sigma with the 2^46 rounding
+    skew (`compact_output_skew`) counted as `compact_output_bits` counts it.  A link is admitted when this is at least
+    `refresh_margin_needed(prm, norm2)` of the consuming program: the refresh is then no likelier to fail than the program's own
+    bootstraps.  At w = log2(2N) and out_norm2 = 1 it equals margin_sigmas(prm, 1) (1 - 4 p skew)."""
+    return (1.0 / (4.0 * prm.p_msg) - compact_output_skew(prm)) / math.sqrt(refresh_input_variance(prm, bits, out_norm2))
+
+
+def refresh_margin_needed(prm: Params, norm2: float = 1.0) -> float:
+    """`margin_sigmas(prm, norm2)` of the consuming program with the same skew counted on its side (`compact_output_bits`)"""
+    return margin_sigmas(prm, norm2) * (1.0 - 4.0 * prm.p_msg * compact_output_skew(prm))
+
+
 def p_error(margin: float) -> float:
     """Probability that a Gaussian leaves +-margin standard deviations (one bootstrap)."""
     return math.erfc(margin / math.sqrt(2.0))

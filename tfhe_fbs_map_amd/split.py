@@ -15,6 +15,21 @@ them holds secret material.
     server = Server(ServerKey.load("server_key.npz"))
     server.run_compact(env, EncryptedInputs.load("inputs.npz")).save("outputs.npz")
     client.decrypt(CompactOutputs.load("outputs.npz"))    # == env.eval(inputs)
+
+Chains.  `Server.run_chain` evaluates a program whose inputs come from any mix of the client's seeded inputs and the full or
+compact outputs of earlier evaluations under the same server key, found by name (`rename` maps an input to another source name).
+A compact input is refreshed on the GPU -- unpacked and bootstrapped through the identity table, one bootstrap per input and
+sample -- and so is a full input whose producer was noisier than a bootstrap output (`out_norm2` > 1).  Every link is held to the
+consuming program's margin (`plan_chain`).  One client key serves every program of a chain: `Client(env, config, programs=...)`.
+
+    client = Client(adder8, ExecConfig(), programs=[adder8])
+    server = Server(client.server_key())
+    acc = server.run_compact(adder8, client.encrypt(first))            # first: {a0..a7, b0..b7: bits}
+    a_from_s = {f"a{i}": f"s{i}" for i in range(8)}
+    for b in stream:                                                   # acc <- acc + b; the state stays on the server
+        fresh = client.encrypt(b, names=[f"b{i}" for i in range(8)])
+        acc = server.run_chain(adder8, [acc, fresh], rename=a_from_s, compact=True)
+    client.decrypt(acc)
 """
 from __future__ import annotations
 
@@ -26,7 +41,8 @@ import numpy as np
 from .fbs_exec_env import ExecConfig, min_fbs_size, table_fusion_factor, table_is_valid
 
 __all__ = ["ServerKey", "EncryptedInputs", "EncryptedOutputs", "CompactOutputs", "Client", "Server", "FORMAT_VERSION",
-           "mask_key_fingerprint", "seeded_key_sizes", "compact_words", "output_noise_factor"]
+           "mask_key_fingerprint", "seeded_key_sizes", "compact_words", "output_noise_factor", "output_noise_factors",
+           "plan_chain", "ChainLink", "client_choice"]
 
 FORMAT_VERSION = 1
 _PARAM_FIELDS = ("n", "log_n_poly", "k", "l_bsk", "beta_bsk", "t_ksk", "gamma_ksk", "p_msg", "sigma_lwe", "sigma_glwe",
@@ -53,19 +69,26 @@ def output_noise_factor(low, p, fused=False):
     """out_norm2 of `params.compact_output_bits`: the worst output's noise in units of one blind rotation's -- 1 for a bootstrap
     output, `table_fusion_factor` for one cut from a shared rotation (fused programs), the squared norm of the coefficients for a
     linear combination (over its sources' factors), 0 for inputs and constants (fresh or trivial ciphertexts)."""
+    return max(output_noise_factors(low, p, fused), default=0.0)
+
+
+def output_noise_factors(low, p, fused=False, input_noise=None):
+    """`output_noise_factor` for each output in output order (a constant: 0).  input_noise: the factor of each input (None: 0, fresh
+    ciphertexts; a chained evaluation passes 1 for an input that was refreshed, its producer's factor for a full link)."""
     n_in = len(low["input_names"])
     readers = {}
     for kind, a0 in zip(low["kind"], low["arg0"]):
         if kind == 1:
             readers[int(a0)] = readers.get(int(a0), 0) + 1
-    noise = [0.0] * n_in
+    noise = [0.0] * n_in if input_noise is None else [float(x) for x in input_noise]
+    assert len(noise) == n_in
     for i, kind in enumerate(low["kind"]):
         a0, a1 = int(low["arg0"][i]), int(low["arg1"][i])
         if kind == 1:
             noise.append(float(table_fusion_factor(low["tables"][a1], p)) if fused and readers[a0] >= 2 else 1.0)
         else:
             noise.append(sum(float(low["term_coef"][t]) ** 2 * noise[int(low["term_src"][t])] for t in range(a0, a0 + a1)))
-    return max((noise[int(w)] for w in low["out_wire"] if w >= 0), default=0.0)
+    return [noise[int(w)] if w >= 0 else 0.0 for w in low["out_wire"]]
 
 
 def _load_npz(path, kind):
@@ -83,6 +106,20 @@ def _fingerprint_of(d):
     if fp.shape != (8,):
         raise ValueError("a fingerprint has 8 bytes")
     return fp.tobytes()
+
+
+def _norm2_fields(outputs):
+    """the optional out_norm2 record of a saved output set (files written before it existed have none)"""
+    return {} if outputs.out_norm2 is None else dict(out_norm2=np.asarray(outputs.out_norm2, np.float64).reshape(-1))
+
+
+def _norm2_of(d, n_outputs):
+    if "out_norm2" not in d:
+        return None
+    v = np.asarray(d["out_norm2"], np.float64).reshape(-1)
+    if v.shape != (n_outputs,) or not np.isfinite(v).all() or (v < 0).any():
+        raise ValueError(f"out_norm2 of shape {v.shape} for {n_outputs} outputs")
+    return v
 
 
 @dataclass
@@ -166,11 +203,13 @@ class EncryptedOutputs:
     T: int
     cts: np.ndarray
     fingerprint: bytes
+    out_norm2: np.ndarray | None = None   # [n_outputs] each output's noise factor (output_noise_factors); None: not recorded
 
     def save(self, path):
         np.savez(path, kind=np.array("encrypted_outputs"), format_version=np.array(FORMAT_VERSION),
                  output_names=np.array(list(self.output_names), dtype=str), T=np.array(self.T, np.int64),
-                 cts=np.ascontiguousarray(self.cts, np.uint64), fingerprint=np.frombuffer(self.fingerprint, np.uint8))
+                 cts=np.ascontiguousarray(self.cts, np.uint64), fingerprint=np.frombuffer(self.fingerprint, np.uint8),
+                 **_norm2_fields(self))
 
     @classmethod
     def load(cls, path):
@@ -180,7 +219,7 @@ class EncryptedOutputs:
         cts = np.asarray(d["cts"])
         if cts.dtype != np.uint64 or cts.ndim != 3 or cts.shape[:2] != (len(names), T):
             raise ValueError(f"ciphertexts of shape {cts.shape} for {len(names)} outputs of {T} samples")
-        return cls(names, T, cts, _fingerprint_of(d))
+        return cls(names, T, cts, _fingerprint_of(d), _norm2_of(d, len(names)))
 
 
 @dataclass
@@ -192,12 +231,13 @@ class CompactOutputs:
     bits: int
     words: np.ndarray
     fingerprint: bytes
+    out_norm2: np.ndarray | None = None   # as EncryptedOutputs.out_norm2
 
     def save(self, path):
         np.savez(path, kind=np.array("compact_outputs"), format_version=np.array(FORMAT_VERSION),
                  output_names=np.array(list(self.output_names), dtype=str), T=np.array(self.T, np.int64),
                  bits=np.array(self.bits, np.int64), words=np.ascontiguousarray(self.words, np.uint64),
-                 fingerprint=np.frombuffer(self.fingerprint, np.uint8))
+                 fingerprint=np.frombuffer(self.fingerprint, np.uint8), **_norm2_fields(self))
 
     @classmethod
     def load(cls, path):
@@ -209,23 +249,41 @@ class CompactOutputs:
             raise ValueError(f"a compact width of {bits} bits")
         if words.dtype != np.uint64 or words.ndim != 3 or words.shape[:2] != (len(names), T):
             raise ValueError(f"compact ciphertexts of shape {words.shape} for {len(names)} outputs of {T} samples")
-        return cls(names, T, bits, words, _fingerprint_of(d))
+        return cls(names, T, bits, words, _fingerprint_of(d), _norm2_of(d, len(names)))
+
+
+def client_choice(env, config: ExecConfig, programs=()):
+    """The pure part of `Client`: (parameter set, fuse) of the server key.  programs=(): `config.choose_params_fuse` for env at the
+    smallest p its tables need.  Otherwise one key for env and every program: p the largest any of them needs (or `fbs_size`),
+    `config.params_choice(p, max norm2)`, and shared rotations only when `config.fuse_tables is True`."""
+    everything = [env] + [e for e in programs if e is not env]
+    lows = [e.lower() for e in everything]
+    p = config.fbs_size or max(min_fbs_size(low["tables"]) for low in lows)
+    for low in lows:
+        for t in low["tables"]:
+            if not table_is_valid(t, p):
+                raise ValueError("table %s cannot be evaluated by one bootstrap at fbs_size %d" % (t, p))
+    if not len(programs):
+        return config.choose_params_fuse(env, p)
+    fuse = config.fuse_tables is True
+    norm2 = max((e.fusion_stats(p) if fuse else e.stats())["norm2_linprod"] for e in everything)
+    return config.params_choice(p, norm2), fuse
 
 
 class Client:
     """Holds the secret.  Chooses (parameter set, fuse) for `env` with the rules of `ExecConfig.choose`, keys a context with
-    `keygen_seeded`, encrypts inputs to bodies and decrypts outputs."""
+    `keygen_seeded`, encrypts inputs to bodies and decrypts outputs.
 
-    def __init__(self, env, config: ExecConfig | None = None):
+    programs: further programs the same server key has to evaluate (a chain, `Server.run_chain`).  The key then takes the largest
+    p any of them needs and the set `config.params_choice(p, max norm2)` over all of them; tables share rotations only when
+    `config.fuse_tables is True`.  With programs=() the choice is `env`'s alone, as before."""
+
+    def __init__(self, env, config: ExecConfig | None = None, programs=()):
         from ._native import Context
         self.env = env
         self.config = cfg = config or ExecConfig()
-        self._low = low = env.lower()
-        p = cfg.fbs_size or min_fbs_size(low["tables"])
-        for t in low["tables"]:
-            if not table_is_valid(t, p):
-                raise ValueError("table %s cannot be evaluated by one bootstrap at fbs_size %d" % (t, p))
-        self.params, self.fuse_tables = cfg.choose_params_fuse(env, p)
+        self._low = env.lower()
+        self.params, self.fuse_tables = client_choice(env, cfg, programs)
         self.ctx = Context(self.params, seed=cfg.key_seed(), device=cfg.device, keygen=False)
         self.ctx.keygen_seeded()
         self._server_key = None
@@ -239,10 +297,11 @@ class Client:
     def fingerprint(self) -> bytes:
         return self.server_key().fingerprint
 
-    def encrypt(self, input_values, nonce0=None) -> EncryptedInputs:
+    def encrypt(self, input_values, nonce0=None, names=None) -> EncryptedInputs:
         """{input name: array-like of bits} (the contract of `LutExecEnv.eval`) -> seeded ciphertexts.  nonce0: the first
-        stream (None: the config's `nonce0`, or streams nobody has used)."""
-        names = self._low["input_names"]
+        stream (None: the config's `nonce0`, or streams nobody has used).  names: the inputs to encrypt, in this order (None: every
+        input of the client's program) -- a chain feeds some inputs of a program from earlier outputs (`Server.run_chain`)."""
+        names = self._low["input_names"] if names is None else [str(n) for n in names]
         cols = [np.asarray(input_values[n]).reshape(-1) for n in names]
         T = max((len(c) for c in cols), default=1)
         bits = np.stack([np.broadcast_to(c, (T,)) for c in cols]).astype(np.int64) if cols else np.zeros((0, T), np.int64)
@@ -250,10 +309,10 @@ class Client:
         bodies, first = self.ctx.encrypt_seeded(bits, nonce0=self.config.nonce0 if nonce0 is None else nonce0)
         return EncryptedInputs(list(names), T, first, bodies.reshape(len(names), T), self.fingerprint)
 
-    def decrypt(self, outputs):
+    def decrypt(self, outputs, env=None):
         """EncryptedOutputs or CompactOutputs -> exactly what `LutExecEnv.eval` returns: {output name: np.ndarray of ints},
-        constant outputs as python ints"""
-        low = self._low
+        constant outputs as python ints.  env: the program that computed them (None: the client's own; any program of a chain)."""
+        low = self._low if env is None else env.lower()
         if outputs.fingerprint != self.fingerprint:
             raise ValueError("outputs were computed under another server key")
         if list(outputs.output_names) != list(low["out_names"]):
@@ -309,7 +368,7 @@ class Server:
         if list(inputs.input_names) != list(low["input_names"]):
             raise ValueError("inputs belong to another program")
         cts = prog.eval_seeded(inputs.bodies, inputs.T, inputs.nonce0)
-        return EncryptedOutputs(list(low["out_names"]), inputs.T, cts, self.key.fingerprint)
+        return EncryptedOutputs(list(low["out_names"]), inputs.T, cts, self.key.fingerprint, self._out_norm2(low))
 
     def compact_bits(self, env):
         """The width `run_compact` uses by default: `params.compact_output_bits` for the server key's parameter set, the program's
@@ -330,4 +389,129 @@ class Server:
             raise ValueError("inputs belong to another program")
         bits = self.compact_bits(env) if bits is None else int(bits)
         words = prog.eval_seeded_compact(inputs.bodies, inputs.T, inputs.nonce0, bits)
-        return CompactOutputs(list(low["out_names"]), inputs.T, bits, words, self.key.fingerprint)
+        return CompactOutputs(list(low["out_names"]), inputs.T, bits, words, self.key.fingerprint, self._out_norm2(low))
+
+    def _out_norm2(self, low, input_noise=None):
+        return np.asarray(output_noise_factors(low, self.key.params.p_msg, self.key.fuse_tables, input_noise), np.float64)
+
+    def run_chain(self, env, sources, rename=None, compact=False, bits=None):
+        """Evaluate `env` with each input taken by name from one of `sources`: the client's `EncryptedInputs` (seeded) and the
+        `EncryptedOutputs` / `CompactOutputs` of earlier evaluations under this server key (fbs_eval_sources).  rename: {input name:
+        source name} for an input whose source carries another name.  Compact links, and full links whose producer was noisier
+        than a bootstrap output, are refreshed on the GPU: one bootstrap each per sample.  compact=True: compact outputs at `bits`
+        (None: the width `compact_bits` would pick for the noise these outputs carry).  `plan_chain` says what is refused."""
+        from .params import compact_output_bits
+        prm, fuse = self.key.params, self.key.fuse_tables
+        sources = [sources] if isinstance(sources, (EncryptedInputs, EncryptedOutputs, CompactOutputs)) else list(sources)
+        links, T = plan_chain(prm, fuse, self.key.fingerprint, env, sources, rename)
+        prog, low = self.program_for(env)
+        feed = []
+        for ln in links:
+            src = sources[ln.source]
+            if ln.kind == "seeded":
+                feed.append(("seeded", src.bodies[ln.index], src.nonce0 + ln.index * src.T))
+            elif ln.kind == "full":
+                feed.append(("full", src.cts[ln.index], ln.refresh))
+            else:
+                feed.append(("compact", src.words[ln.index], int(src.bits)))
+        out_norm2 = self._out_norm2(low, [ln.noise for ln in links])
+        names = list(low["out_names"])
+        if not compact:
+            return EncryptedOutputs(names, T, prog.eval_sources(feed, T, 0), self.key.fingerprint, out_norm2)
+        if bits is None:
+            norm2 = (env.fusion_stats(prm.p_msg) if fuse else env.stats())["norm2_linprod"]
+            bits = compact_output_bits(prm, norm2, float(out_norm2.max(initial=0.0)))
+        bits = int(bits)
+        return CompactOutputs(names, T, bits, prog.eval_sources(feed, T, bits), self.key.fingerprint, out_norm2)
+
+
+@dataclass
+class ChainLink:
+    """How one input of a chained evaluation is fed (`plan_chain`)."""
+    name: str                     # the program's input
+    source: int                   # which of the sources
+    index: int                    # its row there (input or output position)
+    kind: str                     # "seeded", "full" or "compact"
+    refresh: bool                 # bootstrapped through the identity table before use
+    noise: float                  # its noise factor going in: 0 fresh, 1 refreshed, the producer's out_norm2 for a plain full link
+    margin: float | None = None   # params.refresh_margin of a refreshed link
+
+
+def _names_of(src):
+    return list(src.input_names if isinstance(src, EncryptedInputs) else src.output_names)
+
+
+def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_margin=None):
+    """The pure part of `Server.run_chain`: -> ([ChainLink per input of env], T), or ValueError saying why not.
+
+    Refused: a program whose own margin at `params` (`margin_sigmas` at its norm2: `fusion_stats` when tables share rotations) is
+    below `min_margin` (None: `ExecConfig().min_margin`) or whose tables are invalid at the key's p; a source of another server
+    key or another T; an input that no source, or more than one, names; an output set saved without `out_norm2`; a link whose
+    refresh margin (`params.refresh_margin`) is below `params.refresh_margin_needed` at the program's norm2.  A full link whose
+    producer's factor is at most 1 (a bootstrap output or a constant) goes in as it is: the program's parameter set assumes
+    inputs no noisier than that.  Every other full link and every compact link is refreshed."""
+    from .params import margin_sigmas, refresh_margin, refresh_margin_needed
+    low = env.lower()
+    p = params.p_msg
+    for t in low["tables"]:
+        if not table_is_valid(t, p):
+            raise ValueError("table %s cannot be evaluated by one bootstrap at the server key's p = %d" % (t, p))
+    norm2 = (env.fusion_stats(p) if fuse_tables else env.stats())["norm2_linprod"]
+    floor = ExecConfig().min_margin if min_margin is None else float(min_margin)
+    own = margin_sigmas(params, norm2)
+    if own < floor - 1e-9:
+        raise ValueError("the program's own margin at the server key's parameter set is %.2f sigma (norm2 %g), below %.2f: "
+                         "key the chain for it (Client(..., programs=[...]))" % (own, norm2, floor))
+    sources = list(sources)
+    if not sources and low["input_names"]:
+        raise ValueError("no sources for a program with inputs")
+    T = None
+    for k, src in enumerate(sources):
+        if not isinstance(src, (EncryptedInputs, EncryptedOutputs, CompactOutputs)):
+            raise TypeError("source %d is a %s, not EncryptedInputs, EncryptedOutputs or CompactOutputs" % (k, type(src).__name__))
+        if src.fingerprint != fingerprint:
+            raise ValueError("source %d was computed under another server key" % k)
+        if T is not None and src.T != T:
+            raise ValueError("source %d has T = %d samples where the others have %d" % (k, src.T, T))
+        T = src.T
+    rename = {str(a): str(b) for a, b in (rename or {}).items()}
+    unknown = sorted(set(rename) - set(low["input_names"]))
+    if unknown:
+        raise ValueError("rename names %s, which are not inputs of the program" % unknown)
+    need = refresh_margin_needed(params, norm2)
+    links = []
+    for name in low["input_names"]:
+        want = rename.get(name, name)
+        hits = [(k, j) for k, src in enumerate(sources) for j, n in enumerate(_names_of(src)) if n == want]
+        via = name if want == name else "%s (as %s)" % (name, want)
+        if not hits:
+            raise ValueError("input %s: no source holds it" % via)
+        if len(hits) > 1:
+            raise ValueError("input %s: ambiguous, held by sources %s" % (via, sorted({k for k, _ in hits})))
+        k, j = hits[0]
+        src = sources[k]
+        if isinstance(src, EncryptedInputs):
+            links.append(ChainLink(name, k, j, "seeded", False, 0.0))
+            continue
+        if src.out_norm2 is None:
+            raise ValueError("input %s: source %d was saved without out_norm2 (before chains existed), so the noise it carries is "
+                             "unknown and it cannot be linked; it still decrypts" % (via, k))
+        o2 = float(np.asarray(src.out_norm2).reshape(-1)[j])
+        if isinstance(src, CompactOutputs):
+            bits = int(src.bits)
+            if not params.log_n_poly + 1 <= bits <= 31 or src.words.shape[-1] != compact_words(params, bits):
+                raise ValueError("input %s: compact ciphertexts of %d words at %d bits do not fit the server key's parameter set"
+                                 % (via, src.words.shape[-1], bits))
+            link = ChainLink(name, k, j, "compact", True, 1.0, refresh_margin(params, bits, o2))
+        else:
+            if src.cts.shape[-1] != params.ct_words:
+                raise ValueError("input %s: ciphertexts of %d words, the server key's set has %d" % (via, src.cts.shape[-1], params.ct_words))
+            if o2 <= 1.0:
+                links.append(ChainLink(name, k, j, "full", False, o2))
+                continue
+            link = ChainLink(name, k, j, "full", True, 1.0, refresh_margin(params, None, o2))
+        if link.margin < need * (1.0 - 1e-12):
+            raise ValueError("input %s: its refresh would keep %.3f sigma (out_norm2 %g), below the %.3f the program's bootstraps keep"
+                             % (via, link.margin, o2, need))
+        links.append(link)
+    return links, (T if T is not None else 0)
