@@ -457,6 +457,23 @@ int fbs_search_lincomb_coefs(fbs_searcher *s, const int32_t *x, const int32_t *y
 
 /* ---- debug hook: negacyclic product of two polynomials on the device NTT ---- */
 int fbs_debug_polymul(fbs_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64_t *c);
+/* ---- test hooks: the device's FP64 field primitives and its transforms in isolation (tests/test_gpu_transforms.py) ----
+ * fbs_debug_field: element-wise over `count` int64 words holding integers |x| < 2^53 (w: the second operand of op 0 and 1, else
+ * NULL); out[i] is the RAW result as an integer -- the exact representative, not its residue.  op: 0 fp_mulmod(x, w),
+ * 1 fp_mulmod_exact(x, w), 2 fp_center(x), 3 fp_canon(x), 4 fp_canon_near(x), 5 fp_to_u64(fp_from_u64(x)) (0 <= x < 2^52). */
+int fbs_debug_field(fbs_ctx *ctx, int op, const int64_t *x, const int64_t *w, size_t count, int64_t *out);
+/* Static text, no GPU needed: one line per transform variant some blind-rotation kernel instantiates, made from the lists the
+ * kernels are instantiated from:
+ *   "class=<PolyNtt|SplitNtt|WavesNtt|LaneNtt256|LaneNtt512> logn=<log2 N> lanes=<threads per polynomial> dir=forward first=<FIRST>[ np=<NP>]"
+ *   "class=... logn=... lanes=... dir=inverse bounded=<0|1>"
+ * (np: the polynomials LaneNtt*::forward_multi takes side by side; logn of a lane transform: the polynomial its four parts make). */
+const char *fbs_debug_transform_list(void);
+/* One workgroup per polynomial (per np polynomials) runs the call the kernels make, on a line of the list above; the context
+ * must be of the variant's N (FBS_E_INVALID otherwise; the twiddle tables depend on N alone, so any k serves), polys a multiple of np.
+ * int64 in and out, not reduced.  Coefficient side: natural order (a lane transform: its four parts back to back, each in natural
+ * order).  Evaluation side: register order, word t*E + m = register m of thread t, E = N / lanes -- what forward leaves in a word
+ * is what inverse takes from it; which evaluation point a word holds is found by transforming the monomial X. */
+int fbs_debug_transform(fbs_ctx *ctx, const char *variant, const int64_t *in, int64_t *out, size_t polys);
 /* ---- test hook: raises a C++ exception INSIDE the library (kind 0 std::bad_alloc, 1 std::length_error, 2 std::runtime_error,
  * 3 a non-standard one; else nothing) to show that none crosses this boundary: returns FBS_E_NOMEM, FBS_E_NOMEM,
  * FBS_E_INVALID, FBS_E_INVALID, FBS_OK, with the text in fbs_last_error(ctx) (ctx may be NULL: no device is touched). */

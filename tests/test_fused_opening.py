@@ -19,176 +19,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "tfhe_fbs_map_amd", "csrc")
 
-Q = 0x3FFFFFF84001
-QINV = 1.0 / Q
-LOGN, N = 10, 1024
-TWO53 = 1 << 53
-HALF = (Q - 1) // 2
-
-
-# ---- the device's FP64 instructions on integer-valued doubles --------------------------------------------------------
-def rnd(v):
-    """round an exact integer to the nearest double (ties to even), as the FP64 unit does"""
-    return float(v)
-
-
-def exact(v):
-    f = float(v)
-    assert int(f) == v, "inexact: %d" % v
-    return f
-
-
-def fma(a, b, c):
-    return rnd(int(a) * int(b) + int(c))
-
-
-def fp_mulmod(x, w):
-    h = rnd(int(x) * int(w))
-    l = exact(int(x) * int(w) - int(h))              # fma(x, w, -h): the exact remainder
-    qh = round(h * QINV)                              # rint(h * QINV), ties to even
-    r0 = exact(int(h) - qh * Q)                       # fma(-qh, q, h)
-    return exact(int(r0) + int(l))                    # r0 + l
-
-
-def fp_center(x):
-    return exact(int(x) - round(x * QINV) * Q)
-
-
-def centred(v):
-    v %= Q
-    return v - Q if v > Q // 2 else v
-
-
-# ---- twiddles as host_twiddles makes them (fbs_host.cpp), centred as uploaded ----------------------------------------
-def bitrev(i, bits):
-    return int(format(i, "0%db" % bits)[::-1], 2)
-
-
-PSI = pow(7, (Q - 1) // (2 * N), Q)
-TW = [centred(pow(PSI, bitrev(i, LOGN), Q)) for i in range(N)]
-TWI = [centred(pow(pow(PSI, Q - 2, Q), bitrev(i, LOGN), Q)) for i in range(N)]
-W12, W13 = centred(TW[1] * TW[2]), centred(TW[1] * TW[3])   # tw_fused_word(N), tw_fused_word(N) + 1
-
-
-# ---- worst-case bounds (the proofs in the headers, evaluated exactly) ------------------------------------------------
-EPS1 = abs(Fraction(QINV) * Q - 1)
-
-
-def half_ulp(x):
-    """half an ulp of a double of magnitude at most x"""
-    e = math.floor(math.log2(x))
-    if Fraction(2) ** (e + 1) <= x:
-        e += 1
-    return Fraction(2) ** (e - 53)
-
-
-def rho(x_max):
-    """bound on |fp_mulmod(x, w)| for |x| <= x_max < 2^53 and |w| <= (q-1)/2"""
-    assert x_max < TWO53
-    h = Fraction(x_max) * HALF
-    h += half_ulp(h)
-    z = h / Q * (1 + EPS1)
-    z += half_ulp(z)
-    return Q * (Fraction(1, 2) + h / Q * EPS1 + half_ulp(z)) + half_ulp(h)
-
-
-OPENING = 64 + 96 * (Q - 1)          # |a + al c + be b + ga d|, |digit| <= 64, |coefficient| <= (q-1)/2
-FWD_BOUNDS = [Fraction(OPENING)]      # after the opening and after each of the 8 remaining stages
-for _ in range(8):
-    FWD_BOUNDS.append(FWD_BOUNDS[-1] + rho(FWD_BOUNDS[-1]))
-PRODUCT = rho(FWD_BOUNDS[-1])         # one key product
-
-
-# ---- the transforms ------------------------------------------------------------------------------------------------
-def first_two_stages(x):
-    """SplitNtt::first_two_stages: registers (r, r+4, r+8, r+12) of a lane are coefficients j, j+256, j+512, j+768"""
-    y = list(x)
-    w1, w2, w3 = TW[1], TW[2], TW[3]
-    for j in range(N // 4):
-        a, b, c, d = x[j], x[j + 256], x[j + 512], x[j + 768]
-        s, u = fma(c, w1, a), fma(-c, w1, a)
-        y[j] = fma(d, W12, fma(b, w2, s))
-        y[j + 256] = fma(-d, W12, fma(-b, w2, s))
-        y[j + 512] = fma(-d, W13, fma(b, w3, u))
-        y[j + 768] = fma(d, W13, fma(-b, w3, u))
-    return y
-
-
-def ct_stage(x, s):
-    """Cooley-Tukey stage s: blocks of N >> s, twiddle tw[2^s + block]; only the multiplied operand is reduced"""
-    half = N >> (s + 1)
-    for blk in range(1 << s):
-        w = TW[(1 << s) + blk]
-        for i in range(blk * 2 * half, blk * 2 * half + half):
-            u, v = x[i], fp_mulmod(x[i + half], w)
-            x[i], x[i + half] = exact(int(u) + int(v)), exact(int(u) - int(v))
-
-
-def forward_fused(digits, bounds=None):
-    x = first_two_stages([float(d) for d in digits])
-    seen = [max(abs(v) for v in x)]
-    for s in range(2, LOGN):
-        ct_stage(x, s)
-        seen.append(max(abs(v) for v in x))
-    if bounds is not None:
-        for got, lim in zip(seen, bounds):
-            assert got <= lim < TWO53
-    return x
-
-
-def forward_int(coefs):
-    x = [c % Q for c in coefs]
-    for s in range(LOGN):
-        half = N >> (s + 1)
-        for blk in range(1 << s):
-            w = TW[(1 << s) + blk]
-            for i in range(blk * 2 * half, blk * 2 * half + half):
-                u, v = x[i], x[i + half] * w
-                x[i], x[i + half] = (u + v) % Q, (u - v) % Q
-    return x
-
-
-def inverse_bounded(x):
-    """SplitNtt::inverse<true>: GS stages 9..7 uncentred (entry promise |x| < 16 q), centring before 6..4 and 3..1, then the
-    joining stage 0; returns N * coefficients"""
-    x = list(x)
-    assert max(abs(v) for v in x) < 16 * Q
-    for stages, centre in (((9, 8, 7), False), ((6, 5, 4), True), ((3, 2, 1), True), ((0,), False)):
-        if centre:
-            x = [fp_center(v) for v in x]
-        for s in stages:
-            half = N >> (s + 1)
-            for blk in range(1 << s):
-                w = TWI[(1 << s) + blk]
-                for i in range(blk * 2 * half, blk * 2 * half + half):
-                    u, v = x[i], x[i + half]
-                    x[i] = exact(int(u) + int(v))
-                    x[i + half] = fp_mulmod(exact(int(u) - int(v)), w)
-            assert max(abs(v) for v in x) < 128 * Q < TWO53
-    return x
-
-
-def inverse_int(x):
-    x = [v % Q for v in x]
-    for s in range(LOGN - 1, -1, -1):
-        half = N >> (s + 1)
-        for blk in range(1 << s):
-            w = TWI[(1 << s) + blk]
-            for i in range(blk * 2 * half, blk * 2 * half + half):
-                u, v = x[i], x[i + half]
-                x[i], x[i + half] = (u + v) % Q, (u - v) * w % Q
-    return x
-
-
-def digit_cases():
-    rng = random.Random(7)
-    yield "random", [rng.randrange(-64, 64) for _ in range(N)]
-    yield "all -64", [-64] * N
-    yield "alternating +-64", [64 if i % 2 else -64 for i in range(N)]
-    # the largest opening each output class can reach: every digit at 64 with the sign of its coefficient
-    for cls, coef in enumerate(((1, TW[1], TW[2], W12), (1, TW[1], -TW[2], -W12), (1, -TW[1], TW[3], -W13), (1, -TW[1], -TW[3], W13))):
-        sgn = [64 if c >= 0 else -64 for c in coef]   # (a, c, b, d) of the class
-        yield "extreme class %d" % cls, [sgn[0]] * 256 + [sgn[2]] * 256 + [sgn[1]] * 256 + [sgn[3]] * 256
+# the device's FP64 instructions on integer-valued doubles, the twiddles, the worst-case bounds and the replayed transforms:
+# tests/helpers.py (shared with tests/test_gpu_transforms.py, which holds them against the device)
+from tests.helpers import (Q, QINV, LOGN, N, TWO53, HALF, rnd, exact, fma, fp_mulmod, fp_center, centred, bitrev, PSI, TW, TWI, W12, W13, EPS1, half_ulp, rho,
+                           OPENING, FWD_BOUNDS, PRODUCT, first_two_stages, ct_stage, forward_fused, forward_int, inverse_bounded, inverse_int,
+                           digit_cases)  # noqa: E402,F401
 
 
 # ---- the tests -----------------------------------------------------------------------------------------------------

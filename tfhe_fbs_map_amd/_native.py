@@ -205,6 +205,9 @@ def _load():
         "fbs_sync": (i32, [vp, vp]),
         "fbs_debug_polymul": (i32, [vp, vp, vp, vp]),
         "fbs_debug_raise": (i32, [vp, i32]),
+        "fbs_debug_field": (i32, [vp, i32, vp, vp, sz, vp]),
+        "fbs_debug_transform_list": (C.c_char_p, []),
+        "fbs_debug_transform": (i32, [vp, C.c_char_p, vp, vp, sz]),
         "fbs_searcher_create": (i32, [i32, C.POINTER(vp)]),
         "fbs_searcher_destroy": (None, [vp]),
         "fbs_searcher_last_error": (C.c_char_p, [vp]),
@@ -229,6 +232,7 @@ EXPORTED_SYMBOLS = (
     "fbs_searcher_create", "fbs_searcher_destroy", "fbs_searcher_last_error", "fbs_searcher_last_kernel_ms",
     "fbs_search_lincomb_coefs", "fbs_eval", "fbs_eval_dev", "fbs_eval_messages", "fbs_program_layout", "fbs_program_level", "fbs_program_io_slots",
     "fbs_level_lincomb_dev", "fbs_level_bootstrap_dev", "fbs_level_scatter_dev", "fbs_profile_enable", "fbs_profile_kernel", "fbs_kernel_catalog", "fbs_profile_kernels", "fbs_profile_read", "fbs_sync", "fbs_debug_polymul", "fbs_debug_raise",
+    "fbs_debug_field", "fbs_debug_transform_list", "fbs_debug_transform",
     "fbs_keygen_seeded", "fbs_seeded_key_sizes", "fbs_export_seeded_keys", "fbs_import_seeded_keys", "fbs_encrypt_seeded",
     "fbs_encrypt_seeded_fresh", "fbs_encrypt_seeded_dev", "fbs_encrypt_seeded_fresh_dev", "fbs_expand_seeded",
     "fbs_expand_seeded_dev", "fbs_eval_seeded",
@@ -250,6 +254,11 @@ def _c(a, dtype):
 def kernel_catalog():
     """Names of every kernel instantiation the launchers can pick (fbs_kernel_catalog)."""
     return [n for n in lib.fbs_kernel_catalog().decode().split("\n") if n]
+
+
+def debug_transform_list():
+    """One line per transform variant the blind-rotation kernels instantiate (fbs_debug_transform_list); needs no GPU."""
+    return [n for n in lib.fbs_debug_transform_list().decode().split("\n") if n]
 
 
 class TvSet:
@@ -704,3 +713,20 @@ class Context:
         c = np.empty_like(a)
         self._check(lib.fbs_debug_polymul(self._h, _ptr(a), _ptr(b), _ptr(c)))
         return c
+
+    DEBUG_FIELD_OPS = ("fp_mulmod", "fp_mulmod_exact", "fp_center", "fp_canon", "fp_canon_near", "fp_u64_round_trip")
+
+    def debug_field(self, op, x, w=None):
+        """The device's raw result of a field primitive (DEBUG_FIELD_OPS) on int64 arrays, element by element."""
+        x = _c(x, np.int64)
+        w = None if w is None else _c(w, np.int64)
+        out = np.empty_like(x)
+        self._check(lib.fbs_debug_field(self._h, self.DEBUG_FIELD_OPS.index(op), _ptr(x), _ptr(w), x.size, _ptr(out)))
+        return out
+
+    def debug_transform(self, variant, values):
+        """One transform variant (a line of debug_transform_list) on [polys][N] int64 values, unreduced in and out."""
+        values = _c(values, np.int64).reshape(-1, 1 << self.params.log_n_poly)
+        out = np.empty_like(values)
+        self._check(lib.fbs_debug_transform(self._h, variant.encode(), _ptr(values), _ptr(out), values.shape[0]))
+        return out

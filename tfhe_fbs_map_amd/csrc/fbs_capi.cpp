@@ -1638,6 +1638,22 @@ int fbs_debug_polymul(fbs_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
+int fbs_debug_field(fbs_ctx *ctx, int op, const int64_t *x, const int64_t *w, size_t count, int64_t *out) try {
+    int rc = check_ready(ctx, nullptr);
+    if (rc != FBS_OK) return rc;
+    return dev_debug_field(ctx, op, x, w, count, out);
+} FBS_API_CATCH(ctx)
+
+const char *fbs_debug_transform_list(void) try {
+    return debug_transform_list();
+} catch (...) { return ""; }
+
+int fbs_debug_transform(fbs_ctx *ctx, const char *variant, const int64_t *in, int64_t *out, size_t polys) try {
+    int rc = check_ready(ctx, nullptr);
+    if (rc != FBS_OK) return rc;
+    return dev_debug_transform(ctx, variant, in, out, polys);
+} FBS_API_CATCH(ctx)
+
 // test hook: raise inside an entry point what a host allocation or a library call could raise, to show the barrier holds
 // (kind 0: std::bad_alloc, 1: std::length_error, 2: std::runtime_error, 3: a non-standard exception; anything else: no throw)
 int fbs_debug_raise(fbs_ctx *ctx, int kind) try {

@@ -307,6 +307,10 @@ int dev_multi_extract(fbs_ctx *ctx, const fbs_tvset *tv, const uint64_t *d_acc_r
                       size_t s_count, uint32_t n_extract, const uint32_t *d_x_row, const uint32_t *d_x_table,
                       const uint32_t *d_x_dst, hipStream_t stream);
 int dev_polymul(fbs_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_c, hipStream_t stream);
+// test hooks (fbs_debug_transform.hip): host arrays in and out, synchronous
+int dev_debug_field(fbs_ctx *ctx, int op, const int64_t *x, const int64_t *w, size_t count, int64_t *out);
+const char *debug_transform_list();
+int dev_debug_transform(fbs_ctx *ctx, const char *variant, const int64_t *in, int64_t *out, size_t polys);
 
 // device encryption / decryption under the big key (fbs_io.hip), word for word host_encrypt / host_decrypt; asynchronous on `stream`
 int dev_upload_secret(fbs_ctx *ctx);     // sk_glwe -> d_sk_bits (after keygen or import)

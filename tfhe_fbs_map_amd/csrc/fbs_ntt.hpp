@@ -44,8 +44,8 @@ struct Twiddles {
 //   FIRST = 1  |b| <= 2^8 (gadget digits, beta <= 9): b * w is exact in a double, 6 instructions;
 //   FIRST = 2  |a|, |b| <= 2^6 (beta <= 7): a +- w b is an integer below 2^51 + 2^6, EXACT in one FMA each and left
 //              UNREDUCED -- 2 instructions.  Every later butterfly reduces only the operand it multiplies, so all values of
-//              the transform then sit near 2^51 and grow by less than 0.8 q a stage: below 2^51.2 after eleven stages,
-//              inside the 2^52 that fp_mulmod (butterflies and key products alike) accepts, and every sum exact.
+//              the transform then sit near 2^51 and grow by less than 0.8 q a stage: below 64 + 32 (q - 1) + 11 * 0.8 q < 40.9 q <
+//              2^51.4 after eleven more stages, inside the 2^52 that fp_mulmod (butterflies and key products alike) accepts, and every sum exact.
 //   FIRST = 3  as 2, with the first TWO stages fused into exact three-term sums (SplitNtt::first_two_stages, fbs_ntt_split.hpp;
 //              whole polynomials on one wave only, has_fused_opening); a single butterfly treats it as 2.
 template <int FIRST>

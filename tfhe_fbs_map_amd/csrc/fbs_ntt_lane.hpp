@@ -117,6 +117,9 @@ struct LaneNtt256 {
     };
     // NP polynomials side by side (same twiddles, one 256-word exchange buffer each): layout A in, layout D out.
     // FIRST: what is known about the inputs (first_butterfly); `before_last` runs ahead of the last four stages.
+    // Entry promise (FIRST = 0, from the callers -- the two cross stages of WavesNtt and of the whole-CU kernels, at most an unreduced
+    // first butterfly on digits |d| <= 64 plus one product): |x| <= 64 + 32 (q - 1) + 0.8 q < 32.9 q.  Every stage adds a product below
+    // 0.8 q: the eight stages end below 39.3 q < 2^52.
     template <int NP, int FIRST, class Hook>
     __device__ static __forceinline__ void forward_multi(double (&x)[NP][E], double *const (&bufs)[NP], uint32_t ln, const Tw &w,
                                                          Hook &&before_last) {
@@ -329,6 +332,7 @@ struct LaneNtt512 {
     struct NoHook {
         __device__ __forceinline__ void operator()() const {}
     };
+    // entry promise as LaneNtt256::forward_multi, |x| <= 64 + 32 (q - 1) + 0.8 q; the nine stages end below 40.1 q < 2^52
     template <int NP, int FIRST, class Hook>
     __device__ static __forceinline__ void forward_multi(double (&x)[NP][E], double *const (&bufs)[NP], uint32_t ln, const Uniform &u,
                                                          const TwLane &w, Hook &&before_last) {

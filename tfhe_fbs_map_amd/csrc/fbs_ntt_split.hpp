@@ -362,6 +362,7 @@ struct WavesNtt {
     struct NoHook {
         __device__ __forceinline__ void operator()() const {}
     };
+    // entry promise: as PolyNtt -- |x| <= q for FIRST = 0, digits |d| <= 2^8 for FIRST = 1, |d| <= 2^6 for FIRST = 2; ranges: first_butterfly
     template <int FIRST, class Hook>
     __device__ static __forceinline__ void forward(double (&x)[E], Xchg &xc, uint32_t t, const Twiddles &tw, Hook &&before_last) {
         const uint32_t w = wave_of(t), l = t & 63u;
