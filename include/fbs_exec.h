@@ -121,7 +121,8 @@ int fbs_ctx_reserve(fbs_ctx *ctx, size_t max_keyswitches, size_t max_shared_rows
 int fbs_ctx_tune(fbs_ctx *ctx, const char *knob, int64_t value);
 /* counters: "scratch_growths" (how often a call (re)allocated scratch, i.e. blocked), "ms_capacity", "acc_capacity",
  * "wires_capacity", "next_nonce", "cu_count"; "has_secret" (1: the context holds secret keys), "seeded_keys" (1: its keys
- * came from fbs_keygen_seeded or fbs_import_seeded_keys) */
+ * came from fbs_keygen_seeded or fbs_import_seeded_keys); "states_alive", "state_bytes" (resident state: fbs_state blocks not
+ * yet destroyed, and the device bytes they hold) */
 int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value);
 /* text of the last failure on `ctx` (or of the last failed fbs_ctx_create when ctx == NULL) */
 const char *fbs_last_error(const fbs_ctx *ctx);
@@ -379,6 +380,48 @@ typedef struct fbs_input_src {
  * width outside [log2(2N), 31], streams past 2^56, T * words overflowing.  Repeated calls of one shape do not grow scratch.
  * T = 0 does nothing.  Blocks until the outputs are back. */
 int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, size_t T, uint32_t out_bits, uint64_t *out);
+
+/* ---- resident state: chained ciphertexts that stay on the GPU between evaluations ------------------------------------------
+ * A server whose state only its own later evaluations read keeps it in device memory: an fbs_state is a context-owned block of
+ * big-key ciphertexts laid out [rows][T][D+1].  It is not part of the scratch: it never moves or shrinks while alive, and a
+ * growing scratch leaves it alone.  An evaluation writes its outputs into a state (fbs_eval_resident) and a later one reads its
+ * inputs from state rows, with no copy to the host and no refresh in between; the state leaves the card only when asked
+ * (fbs_state_fetch), full or compact.  Every entry works on the context's own stream, in call order.  None needs a secret. */
+typedef struct fbs_state fbs_state;
+/* rows, T >= 1; rows <= FBS_MAX_WIRES, and rows * T * (D+1) words must not overflow (FBS_E_INVALID, checked before anything is
+ * sized).  A device that cannot hold it: FBS_E_DEVICE, and the context stays usable.  The words are not initialised. */
+int fbs_state_create(fbs_ctx *ctx, size_t rows, size_t T, fbs_state **out);
+/* Waits for the work queued on the context, then frees.  NULL is allowed.  fbs_ctx_destroy frees the states still alive: a
+ * state must not be destroyed after its context. */
+void fbs_state_destroy(fbs_state *st);
+int fbs_state_info(const fbs_state *st, size_t *rows, size_t *T);   /* (either pointer may be NULL) */
+
+typedef struct fbs_resident_src {
+    const fbs_state *state;   /* NULL: input i comes from src[i], as in fbs_eval_sources */
+    uint32_t row;             /* input i = row `row` of `state`, all T samples */
+    uint32_t refresh;         /* as fbs_input_src.refresh of FBS_SRC_FULL: 1 = key switch, modulus switch and identity rotation first */
+} fbs_resident_src;
+/* fbs_eval_sources with two additions.  (1) res (may be NULL: no resident input) has one entry per input; where res[i].state is
+ * non-NULL input i is that state row and src[i] is not read (src may be NULL when every input is resident).  (2) Exactly one of
+ * out_host and out_state is given.  out_host: as `out` of fbs_eval_sources, at out_bits.  out_state (then out_bits must be 0): a
+ * state of n_outputs rows whose row o becomes output o for all T samples, a constant output as the trivial ciphertext fbs_eval
+ * writes.  The same chunks as fbs_eval: chunk [s0, s0 + tc) reads samples s0 onwards of each state row and writes samples s0
+ * onwards of out_state, one gather launch and one scatter launch per chunk.  With out_state and every input resident or seeded
+ * the call queues its work on the context's stream and returns without waiting for it (the caller's arrays are read before it
+ * returns; a later call on the context, fbs_state_fetch included, is ordered behind it); otherwise it blocks as
+ * fbs_eval_sources does.  Refused with FBS_E_INVALID, nothing written: what fbs_eval_sources refuses; a state of another
+ * context; a row past the state's rows; a state whose T differs from the call's; an out_state with rows != n_outputs; an
+ * out_state that is also an input state (no in-place hops); both or neither of out_host and out_state; out_bits != 0 with
+ * out_state.  Repeated calls of one shape do not grow scratch.  T = 0 does nothing. */
+int fbs_eval_resident(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res, size_t T, uint32_t out_bits,
+                      uint64_t *out_host, fbs_state *out_state);
+/* Rows [row0, row0 + rows) to the host.  bits = 0: the full ciphertexts, out [rows][T][D+1].  Else compact words out [rows][T][W]
+ * at that width: compacted on the device as fbs_compact_dev does it (word for word fbs_compact_dev of the full fetch), in passes of
+ * the modulus-switch scratch, and only the packed words cross the bus.  Blocks until the data is back. */
+int fbs_state_fetch(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint32_t bits, uint64_t *out);
+/* The way back (state saved to disk by a full fetch): cts [rows][T][D+1] into rows [row0, row0 + rows).  Every word must be a
+ * canonical residue (FBS_E_INVALID otherwise, nothing written).  Blocks until the words are on the device. */
+int fbs_state_put(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *cts);
 
 /* ---- a loaded program, one level at a time (multi-GPU hosts) -----------------
  * The two independent axes of the reference's eval loop (fbs_exec_env.py:211-223) are the gates

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 from dataclasses import dataclass, asdict
 
 import numpy as np
@@ -50,6 +51,10 @@ class _ProgramDesc(C.Structure):
 class _InputSrc(C.Structure):   # fbs_input_src (include/fbs_exec.h, "chained evaluation")
     _fields_ = [("kind", C.c_uint32), ("bits", C.c_uint32), ("refresh", C.c_uint32), ("nonce0", C.c_uint64),
                 ("data", C.c_void_p)]
+
+
+class _ResidentSrc(C.Structure):   # fbs_resident_src (include/fbs_exec.h, "resident state")
+    _fields_ = [("state", C.c_void_p), ("row", C.c_uint32), ("refresh", C.c_uint32)]
 
 
 SRC_SEEDED, SRC_FULL, SRC_COMPACT = 0, 1, 2   # FBS_SRC_*
@@ -177,6 +182,12 @@ def _load():
         "fbs_compact_fields_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_refresh_compact_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_eval_sources": (i32, [vp, vp, vp, sz, u32, vp]),
+        "fbs_state_create": (i32, [vp, sz, sz, C.POINTER(vp)]),
+        "fbs_state_destroy": (None, [vp]),
+        "fbs_state_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz)]),
+        "fbs_eval_resident": (i32, [vp, vp, vp, vp, sz, u32, vp, vp]),
+        "fbs_state_fetch": (i32, [vp, vp, sz, sz, u32, vp]),
+        "fbs_state_put": (i32, [vp, vp, sz, sz, vp]),
         "fbs_tvset_create": (i32, [vp, vp, vp, u32, C.POINTER(vp)]),
         "fbs_tvset_destroy": (None, [vp]),
         "fbs_bootstrap_batch": (i32, [vp, vp, vp, vp, sz, vp]),
@@ -238,6 +249,7 @@ EXPORTED_SYMBOLS = (
     "fbs_expand_seeded_dev", "fbs_eval_seeded",
     "fbs_compact_words", "fbs_compact_dev", "fbs_eval_seeded_compact", "fbs_decrypt_compact", "fbs_decrypt_compact_dev",
     "fbs_compact_fields_dev", "fbs_refresh_compact_dev", "fbs_eval_sources",
+    "fbs_state_create", "fbs_state_destroy", "fbs_state_info", "fbs_eval_resident", "fbs_state_fetch", "fbs_state_put",
 )
 
 lib = _load()
@@ -385,6 +397,48 @@ class Program:
         self.ctx._check(lib.fbs_eval_sources(self.ctx._h, self._h, C.byref(arr), T, bits, _ptr(out)))
         return out
 
+    def eval_resident(self, sources, T, out_bits=0, out_state=None):
+        """`eval_sources` with resident state (fbs_eval_resident).  A source may also be
+            ("state", state, row, refresh)     -- row `row` of a `DeviceState`; refresh=True: through the identity table first
+        out_state=None: returns the outputs as `eval_sources` does at `out_bits`.  out_state: a `DeviceState` of n_outputs rows and
+        T samples a row that takes the full outputs, row o = output o; returns it.  With out_state and only state and seeded
+        sources the call does not wait for the evaluation: whatever reads the state next is queued behind it."""
+        if len(sources) != self.n_inputs:
+            raise ValueError(f"{len(sources)} sources for {self.n_inputs} inputs")
+        arr, res, keep = (_InputSrc * max(1, self.n_inputs))(), (_ResidentSrc * max(1, self.n_inputs))(), []
+        ctw = self.ctx.params.ct_words
+        for i, source in enumerate(sources):
+            kind = source[0]
+            if kind == "state":
+                _, state, row, refresh = source
+                if not isinstance(state, DeviceState) or state.closed:
+                    raise ValueError(f"input {i}: a closed state")
+                res[i] = _ResidentSrc(state._h.value, int(row), int(bool(refresh)))
+                keep.append(state)
+                continue
+            _, data, arg = source
+            if kind == "seeded":
+                a = _c(data, np.uint64).reshape(T)
+                arr[i] = _InputSrc(SRC_SEEDED, 0, 0, int(arg), a.ctypes.data)
+            elif kind == "full":
+                a = _c(data, np.uint64).reshape(T, ctw)
+                arr[i] = _InputSrc(SRC_FULL, 0, int(bool(arg)), 0, a.ctypes.data)
+            elif kind == "compact":
+                a = _c(data, np.uint64).reshape(T, -1)
+                arr[i] = _InputSrc(SRC_COMPACT, int(arg), 1, 0, a.ctypes.data)
+            else:
+                raise ValueError(f"unknown source kind {kind!r}")
+            keep.append(a)
+        bits = int(out_bits)
+        if out_state is not None:
+            if not isinstance(out_state, DeviceState) or out_state.closed:
+                raise ValueError("out_state is a closed state")
+            self.ctx._check(lib.fbs_eval_resident(self.ctx._h, self._h, C.byref(arr), C.byref(res), T, bits, None, out_state._h))
+            return out_state
+        out = np.empty((self.n_outputs, T, self.ctx.compact_words(bits) if bits else ctw), np.uint64)
+        self.ctx._check(lib.fbs_eval_resident(self.ctx._h, self._h, C.byref(arr), C.byref(res), T, bits, _ptr(out), None))
+        return out
+
     # device-pointer entry points (ints from torch.Tensor.data_ptr()); asynchronous on `stream`, no host copies
     def eval_dev(self, d_in, T, d_out, stream=0):
         self.ctx._check(lib.fbs_eval_dev(self.ctx._h, self._h, d_in or None, T, d_out or None, stream or None))
@@ -409,6 +463,59 @@ class Program:
         self.close()
 
 
+class DeviceState:
+    """Resident state (fbs_state, include/fbs_exec.h): [rows][T][D+1] big-key ciphertexts that stay in the context's device
+    memory between evaluations.  `Program.eval_resident` writes its outputs into one and reads inputs from its rows; `fetch`
+    brings rows to the host, full or compact, and `put` takes full ones back.  `close()` frees it (also as a context manager);
+    closing the context closes its states."""
+
+    def __init__(self, ctx, rows, T):
+        self.ctx, self.rows, self.T = ctx, int(rows), int(T)
+        self._h = None
+        h = C.c_void_p()
+        ctx._check(lib.fbs_state_create(ctx._h, self.rows, self.T, C.byref(h)))
+        self._h = h
+        ctx._states.add(self)
+
+    @property
+    def closed(self):
+        return self._h is None or not self.ctx._h
+
+    def _live(self):
+        if self.closed:
+            raise ValueError("the state is closed")
+        return self._h
+
+    def fetch(self, row0=0, rows=None, bits=0):
+        """rows [row0, row0 + rows) -> np.ndarray: bits=0 the full ciphertexts [rows][T][D+1]; else compact words [rows][T][W] at
+        that width, compacted on the GPU (fbs_state_fetch).  Waits for the evaluations queued before it."""
+        rows = self.rows - int(row0) if rows is None else int(rows)
+        bits = int(bits)
+        out = np.empty((max(0, rows), self.T, self.ctx.compact_words(bits) if bits else self.ctx.params.ct_words), np.uint64)
+        self.ctx._check(lib.fbs_state_fetch(self.ctx._h, self._live(), int(row0), rows, bits, _ptr(out)))
+        return out
+
+    def put(self, cts, row0=0):
+        """full ciphertexts [rows][T][D+1] (canonical words) -> rows row0 onwards (fbs_state_put)"""
+        cts = _c(cts, np.uint64).reshape(-1, self.T, self.ctx.params.ct_words)
+        self.ctx._check(lib.fbs_state_put(self.ctx._h, self._live(), int(row0), cts.shape[0], _ptr(cts)))
+        return self
+
+    def close(self):
+        if not self.closed and lib is not None:
+            lib.fbs_state_destroy(self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
 class Context:
     """One GPU, one parameter set, one key set."""
 
@@ -424,6 +531,7 @@ class Context:
         self.params = params
         self.seed = seed
         self.device = device
+        self._states = weakref.WeakSet()   # its DeviceStates: closed with it
         self._h = C.c_void_p()
         cp = params.to_c()
         if isinstance(seed, int):
@@ -445,6 +553,8 @@ class Context:
 
     def close(self):
         if getattr(self, "_h", None) and lib is not None:      # `lib` is None while the interpreter shuts down
+            for st in list(getattr(self, "_states", ())):      # fbs_ctx_destroy frees the states still alive
+                st._h = None
             lib.fbs_ctx_destroy(self._h)
             self._h = None
 
@@ -586,6 +696,10 @@ class Context:
 
     def tvset(self, tables):
         return TvSet(self, tables)
+
+    def state(self, rows, T):
+        """A `DeviceState` of [rows][T][D+1] ciphertexts in this context's device memory (fbs_state_create)."""
+        return DeviceState(self, rows, T)
 
     # ---- compact outputs: key-switched to the small key, rounded to `bits` bits a field, bit-packed (include/fbs_exec.h) ----
     @property

@@ -249,6 +249,8 @@ int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value) try {
     else if (k == "cu_count") *value = ctx->cu_count;
     else if (k == "has_secret") *value = ctx->have_keys && !ctx->eval_only;
     else if (k == "seeded_keys") *value = ctx->have_keys && ctx->seeded_keys;
+    else if (k == "states_alive") *value = (int64_t)ctx->states.size();
+    else if (k == "state_bytes") *value = (int64_t)ctx->state_bytes;
     else return set_error(ctx, FBS_E_INVALID, "unknown statistic '" + k + "'");
     return FBS_OK;
 } FBS_API_CATCH(ctx)
@@ -270,8 +272,13 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     if (ctx->scratch_used) (void)hipStreamSynchronize(ctx->scratch_stream);
     for (void *p : {(void *)ctx->d_bsk_hat, (void *)ctx->d_bsk_hat_small, (void *)ctx->d_ksk, (void *)ctx->d_ksk_f, (void *)ctx->d_ks_corr, (void *)ctx->d_ks_a, (void *)ctx->d_ks_b, (void *)ctx->d_ks_c, (void *)ctx->d_tw_fwd, (void *)ctx->d_tw_inv, (void *)ctx->d_psi_pow, (void *)ctx->d_ms, (void *)ctx->d_ms_eps, (void *)ctx->d_ms_body, (void *)ctx->d_acc, (void *)ctx->d_stage_in, (void *)ctx->d_stage_out, (void *)ctx->d_stage_ids,
                     (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_sk_lwe_bits, (void *)ctx->d_io_msgs,
-                    (void *)ctx->d_compact})
+                    (void *)ctx->d_compact, (void *)ctx->d_links})
         if (p) (void)hipFree(p);
+    for (fbs_state *st : ctx->states) {   // the states still alive
+        (void)hipFree(st->d);
+        delete st;
+    }
+    if (ctx->inputs_event) (void)hipEventDestroy(ctx->inputs_event);
     fbs_tvset_destroy(ctx->tv_identity);
     if (ctx->scratch_event) (void)hipEventDestroy(ctx->scratch_event);
     for (auto &v : ctx->prof.pending)
@@ -1429,17 +1436,56 @@ static int refresh_slots(fbs_ctx *ctx, const fbs_tvset *tv, const uint32_t *d_sl
 // buffer, unpacked into the modulus-switch scratch and refreshed, and full inputs marked `refresh` are key-switched, modulus-switched
 // and refreshed in place -- both in groups whose rows fit the scratch reserve_wires sized (max_sources x Tc rows).  Store: that of
 // fbs_eval_seeded (out_bits = 0) or fbs_eval_seeded_compact.
-int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, size_t T, uint32_t out_bits, uint64_t *out) try {
-    int rc = check_eval(ctx, prog, src, T, out);
+//
+// fbs_eval_resident adds: inputs that are rows of states (res), gathered into their slots by one launch per chunk before the
+// refreshes (a resident input marked `refresh` joins the full ones), and out_state in place of the host buffer, filled by one scatter
+// launch per chunk.  With out_state and no full or compact host input nothing has to come back: the chunks are queued without
+// waiting, and the call returns once the arrays it was given have been read (`inputs_event`, after the last chunk's load).
+static bool state_of(const fbs_ctx *ctx, const fbs_state *st) {   // (by address: a foreign or stale pointer is never dereferenced)
+    return st && std::find(ctx->states.begin(), ctx->states.end(), st) != ctx->states.end();
+}
+
+static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res, size_t T, uint32_t out_bits,
+                        uint64_t *out, fbs_state *out_state) {
+    int rc = check_prog(ctx, prog);
     if (rc != FBS_OK) return rc;
     if (out_bits && (rc = check_bits(ctx, out_bits)) != FBS_OK) return rc;
+    if (out_state) {
+        if (!state_of(ctx, out_state)) return set_error(ctx, FBS_E_INVALID, "the output state is not a live state of this context");
+        if (out_bits) return set_error(ctx, FBS_E_INVALID, "outputs into a state are full ciphertexts: out_bits must be 0");
+        if (out_state->rows != prog->n_outputs)
+            return set_error(ctx, FBS_E_INVALID, "the output state has " + std::to_string(out_state->rows) + " rows for " +
+                                                     std::to_string(prog->n_outputs) + " outputs");
+        if (out_state->T != T) return set_error(ctx, FBS_E_INVALID, "the output state holds " + std::to_string(out_state->T) + " samples a row, the call has " + std::to_string(T));
+    }
+    for (size_t i = 0; res && i < prog->n_inputs; i++) {
+        const fbs_state *st = res[i].state;
+        if (!st) continue;
+        const std::string who = "input " + std::to_string(i) + ": ";
+        if (!state_of(ctx, st)) return set_error(ctx, FBS_E_INVALID, who + "not a live state of this context");
+        if (st == out_state) return set_error(ctx, FBS_E_INVALID, who + "the output state is also an input state (no in-place hops)");
+        if (res[i].row >= st->rows) return set_error(ctx, FBS_E_INVALID, who + "row " + std::to_string(res[i].row) + " of a state of " + std::to_string(st->rows) + " rows");
+        if (st->T != T) return set_error(ctx, FBS_E_INVALID, who + "its state holds " + std::to_string(st->T) + " samples a row, the call has " + std::to_string(T));
+    }
+    auto resident = [&](size_t i) { return res && res[i].state; };
+    if (T) {
+        bool from_src = false;
+        for (size_t i = 0; i < prog->n_inputs; i++) from_src |= !resident(i);
+        if ((from_src && !src) || (prog->n_outputs && !out && !out_state)) return set_error(ctx, FBS_E_INVALID, "null argument");
+    }
     if (T == 0) return FBS_OK;
     const size_t n_in = prog->n_inputs, n_out = prog->n_outputs, ctw = ctx->D + 1, W_out = out_bits ? compact_words(ctx->p.n, out_bits) : 0;
     // every source is checked before anything is reserved, copied or launched
     size_t W_in = 0;
     std::vector<uint32_t> compact_in, full_refresh;   // input indices
-    bool any_seeded = false;
+    std::vector<StateLink> links;                     // the gather list, then the scatter list
+    bool any_seeded = false, host_cts = false;        // host_cts: some input is ciphertexts in host memory
     for (size_t i = 0; i < n_in; i++) {
+        if (resident(i)) {
+            links.push_back(StateLink{res[i].state->d + (size_t)res[i].row * T * ctw, prog->in_slot[i]});
+            if (res[i].refresh) full_refresh.push_back((uint32_t)i);
+            continue;
+        }
         const fbs_input_src &x = src[i];
         const std::string who = "input " + std::to_string(i) + ": ";
         if (x.kind > FBS_SRC_COMPACT) return set_error(ctx, FBS_E_INVALID, who + "unknown source kind " + std::to_string(x.kind));
@@ -1456,6 +1502,7 @@ int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, siz
             any_seeded = true;
         }
         if (x.kind == FBS_SRC_FULL && x.refresh) full_refresh.push_back((uint32_t)i);
+        host_cts |= x.kind != FBS_SRC_SEEDED;
         if (T > SIZE_MAX / 8 / words) return set_error(ctx, FBS_E_INVALID, who + "T * words overflow");
     }
     if (T > SIZE_MAX / 8 / std::max<size_t>(1, n_out) / std::max(ctw, W_out)) return set_error(ctx, FBS_E_INVALID, "n_outputs * T words overflow");
@@ -1478,21 +1525,34 @@ int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, siz
     }
     CompactStore cs;
     if (out_bits) cs = compact_store_for(ctx, prog, out_bits, Tc);
+    const size_t n_gather = links.size();
+    for (size_t o = 0; out_state && o < n_out; o++) {
+        const int64_t w = prog->out_slot[o];
+        links.push_back(StateLink{out_state->d + o * T * ctw, w >= 0 ? (uint64_t)w : STATE_LINK_CONST | trivial_body(ctx, w)});
+    }
+    if (!links.empty() && (rc = grow(ctx, ctx->d_links, ctx->links_capacity, std::max<size_t>(links.size(), 1 << 12), sizeof(StateLink), false)) != FBS_OK)
+        return rc;
+    const bool wait = !out_state || host_cts;   // results or pageable ciphertexts cross the bus: chunk by chunk, as fbs_eval_sources
+    if (!wait && !ctx->inputs_event) FBS_HIP(ctx, hipEventCreateWithFlags(&ctx->inputs_event, hipEventDisableTiming));
     const size_t n1 = ctx->p.n + 1;
     auto load = [&](size_t s0, size_t tc) {
         if (s0 == 0 && !refresh_slot.empty())
             FBS_HIP(ctx, hipMemcpyAsync(ctx->d_idx, refresh_slot.data(), refresh_slot.size() * 4, hipMemcpyHostToDevice, s));
+        if (s0 == 0 && !links.empty())
+            FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links, links.data(), links.size() * sizeof(StateLink), hipMemcpyHostToDevice, s));
+        if (int rc = dev_state_gather(ctx, StateCopy{ctx->d_links, n_gather, ctx->d_wires, Tc, s0, tc, ctx->D}, s)) return rc;
         for (size_t i = 0; i < n_in; i++)
-            if (src[i].kind == FBS_SRC_FULL)
+            if (!resident(i) && src[i].kind == FBS_SRC_FULL)
                 FBS_HIP(ctx, hipMemcpyAsync(ctx->d_wires + (size_t)prog->in_slot[i] * Tc * ctw, src[i].data + s0 * ctw, tc * ctw * 8,
                                             hipMemcpyHostToDevice, s));
+        auto seeded = [&](size_t i) { return !resident(i) && src[i].kind == FBS_SRC_SEEDED; };
         for (size_t i0 = 0; i0 < n_in;) {   // seeded runs: streams nonce0 + r T + s over the run's rows r
-            if (src[i0].kind != FBS_SRC_SEEDED) {
+            if (!seeded(i0)) {
                 i0++;
                 continue;
             }
             size_t i1 = i0 + 1;
-            while (i1 < n_in && src[i1].kind == FBS_SRC_SEEDED && src[i1].nonce0 == src[i1 - 1].nonce0 + T) i1++;
+            while (i1 < n_in && seeded(i1) && src[i1].nonce0 == src[i1 - 1].nonce0 + T) i1++;
             for (size_t j0 = i0; j0 < i1;) {   // the bodies: one 2D copy per stretch whose rows lie T words apart
                 size_t j1 = j0 + 1;
                 while (j1 < i1 && src[j1].data == src[j1 - 1].data + T) j1++;
@@ -1531,12 +1591,129 @@ int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, siz
             if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) return rc;
             if (int rc = refresh_slots(ctx, tv, d_slot, ng, Tc, tc, s)) return rc;
         }
+        if (!wait && s0 + tc == T) FBS_HIP(ctx, hipEventRecord(ctx->inputs_event, s));   // every array of the caller has been queued
         return FBS_OK;
     };
     auto store = [&](size_t s0, size_t tc) {
+        if (out_state) return dev_state_scatter(ctx, StateCopy{ctx->d_links + n_gather, n_out, ctx->d_wires, Tc, s0, tc, ctx->D}, s);
         return out_bits ? store_compact(ctx, prog, cs, out, T, Tc, s0, tc, s) : store_host_cts(ctx, prog, out, T, Tc, s0, tc, s);
     };
-    return eval_chunks(ctx, prog, T, Tc, s, true, load, store);
+    rc = eval_chunks(ctx, prog, T, Tc, s, wait, load, store);
+    // the link lists, refresh slots and seeded bodies live in pageable memory of this call or its caller: read before it returns.
+    // A call that failed part way may have queued copies from them without reaching the event: it waits for the stream instead.
+    if (!wait && rc == FBS_OK) FBS_HIP(ctx, hipEventSynchronize(ctx->inputs_event));
+    if (!wait && rc != FBS_OK) (void)hipStreamSynchronize(s);
+    return rc;
+}
+
+int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, size_t T, uint32_t out_bits, uint64_t *out) try {
+    if (int rc = check_eval(ctx, prog, src, T, out)) return rc;
+    return eval_sources(ctx, prog, src, nullptr, T, out_bits, out, nullptr);
+} FBS_API_CATCH(ctx)
+
+// ---- resident state: device blocks of ciphertexts that stay on the card between evaluations (fbs_state.hip) -----------------
+int fbs_state_create(fbs_ctx *ctx, size_t rows, size_t T, fbs_state **out) try {
+    if (!ctx || !out) return FBS_E_INVALID;
+    *out = nullptr;
+    if (rows == 0 || T == 0) return set_error(ctx, FBS_E_INVALID, "a state has at least one row and one sample");
+    if (rows > FBS_MAX_WIRES) return set_error(ctx, FBS_E_INVALID, "state too large: rows exceed FBS_MAX_WIRES");
+    if (T > SIZE_MAX / 8 / rows / (ctx->D + 1)) return set_error(ctx, FBS_E_INVALID, "rows * T * (D + 1) words overflow");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = rows * T * (ctx->D + 1) * 8;
+    std::unique_ptr<fbs_state> st(new fbs_state);
+    ctx->states.reserve(ctx->states.size() + 1);
+    const hipError_t e = hipMalloc(&st->d, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();   // (an allocation that fails leaves the device, and so the context, as it was)
+        return set_error(ctx, FBS_E_DEVICE, "a state of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+    }
+    st->ctx = ctx;
+    st->rows = rows;
+    st->T = T;
+    ctx->states.push_back(st.get());
+    ctx->state_bytes += bytes;
+    *out = st.release();
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+void fbs_state_destroy(fbs_state *st) try {
+    if (!st) return;
+    fbs_ctx *ctx = st->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);   // queued evaluations may still read or write it
+    if (ctx->scratch_used) (void)hipStreamSynchronize(ctx->scratch_stream);
+    ctx->states.erase(std::remove(ctx->states.begin(), ctx->states.end(), st), ctx->states.end());
+    ctx->state_bytes -= st->rows * st->T * (ctx->D + 1) * 8;
+    (void)hipFree(st->d);
+    delete st;
+} catch (...) {
+}
+
+int fbs_state_info(const fbs_state *st, size_t *rows, size_t *T) try {
+    if (!st) return FBS_E_INVALID;
+    if (rows) *rows = st->rows;
+    if (T) *T = st->T;
+    return FBS_OK;
+} FBS_API_CATCH(st ? st->ctx : nullptr)
+
+int fbs_eval_resident(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res, size_t T, uint32_t out_bits,
+                      uint64_t *out_host, fbs_state *out_state) try {
+    if (!ctx) return FBS_E_INVALID;
+    if ((out_host != nullptr) == (out_state != nullptr))
+        return set_error(ctx, FBS_E_INVALID, "exactly one of out_host and out_state takes the outputs");
+    return eval_sources(ctx, prog, src, res, T, out_bits, out_host, out_state);
+} FBS_API_CATCH(ctx)
+
+// what fetch and put check: the state is this context's, the rows are its rows
+static int check_state_rows(const fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, const void *host) {
+    if (!state_of(ctx, st)) return set_error(ctx, FBS_E_INVALID, "not a live state of this context");
+    if (row0 > st->rows || rows > st->rows - row0) return set_error(ctx, FBS_E_INVALID, "rows past the end of the state");
+    if (rows && !host) return set_error(ctx, FBS_E_INVALID, "null argument");
+    return FBS_OK;
+}
+
+int fbs_state_fetch(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint32_t bits, uint64_t *out) try {
+    if (!ctx) return FBS_E_INVALID;
+    int rc = check_state_rows(ctx, st, row0, rows, out);
+    if (rc != FBS_OK) return rc;
+    if (bits && (rc = check_bits(ctx, bits)) != FBS_OK) return rc;
+    if (rows == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t ctw = ctx->D + 1, count = rows * st->T;
+    const uint64_t *d_cts = st->d + row0 * st->T * ctw;
+    if (!bits) {
+        FBS_HIP(ctx, hipMemcpyAsync(out, d_cts, count * ctw * 8, hipMemcpyDeviceToHost, s));
+        return sync_stream(ctx, s);
+    }
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    // fbs_compact_dev's passes, each packed into the staging of the compact outputs and copied back from there
+    const size_t pass = std::min(count, std::max(ctx->ms_capacity, COMPACT_PASS)), W = compact_words(ctx->p.n, bits);
+    if ((rc = ensure_ms(ctx, pass)) != FBS_OK) return rc;
+    if ((rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, pass * W, 8, true)) != FBS_OK) return rc;
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    for (size_t f0 = 0; f0 < count; f0 += pass) {
+        const size_t n = std::min(pass, count - f0);
+        const GateView gv = batch_view(d_cts + f0 * ctw, nullptr, nullptr, n);
+        if ((rc = dev_keyswitch(ctx, gv, ctx->d_ms, bits, s)) || (rc = dev_compact_pack(ctx, ctx->d_ms, n, bits, ctx->d_compact, s)))
+            return scratch_fail(ctx, s, rc);
+        if (hipMemcpyAsync(out + f0 * W, ctx->d_compact, n * W * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+            return scratch_fail(ctx, s, set_error(ctx, FBS_E_DEVICE, "copying compact words to the host failed"));
+    }
+    if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
+    return sync_stream(ctx, s);
+} FBS_API_CATCH(ctx)
+
+int fbs_state_put(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *cts) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (int rc = check_state_rows(ctx, st, row0, rows, cts)) return rc;
+    if (rows == 0) return FBS_OK;
+    const size_t ctw = ctx->D + 1, words = rows * st->T * ctw;
+    for (size_t i = 0; i < words; i++)
+        if (cts[i] >= FQ) return set_error(ctx, FBS_E_INVALID, "word " + std::to_string(i) + " is not a canonical residue");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    FBS_HIP(ctx, hipMemcpyAsync(st->d + row0 * st->T * ctw, cts, words * 8, hipMemcpyHostToDevice, ctx->stream));
+    return sync_stream(ctx, ctx->stream);
 } FBS_API_CATCH(ctx)
 
 // ---------------------------------------------------------------------------------------------

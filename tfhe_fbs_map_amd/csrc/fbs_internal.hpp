@@ -97,6 +97,23 @@ struct IoView {
     size_t rows, per_row;
 };
 
+// Resident state (fbs_state.hip): link e of a launch joins a state row and a wire slot.  `row` points at sample 0 of the row
+// ([T][D + 1] words of a state block); `slot` is the wire slot, or -- for the scatter -- STATE_LINK_CONST | body: the row takes
+// the trivial ciphertext of that body (a constant output; bodies are residues below 2^46).
+constexpr uint64_t STATE_LINK_CONST = 1ull << 63;
+struct StateLink {
+    uint64_t *row;
+    uint64_t slot;
+};
+struct StateCopy {
+    const StateLink *links;   // [n_links], device
+    size_t n_links;
+    uint64_t *wires;          // wire slots [n_slots][Tc][D + 1]
+    size_t Tc;                // samples per slot in the wire buffer (stride)
+    size_t s0, tc;            // sample q < tc of a slot is sample s0 + q of a row
+    uint32_t D;
+};
+
 struct Profile {
     struct Pending {
         hipEvent_t begin, end;
@@ -184,7 +201,22 @@ struct fbs_ctx {
     hipEvent_t scratch_event = nullptr;
     bool scratch_used = false;
 
+    // Resident state: the blocks fbs_state_create made and nobody destroyed yet (fbs_ctx_destroy frees them), and the link lists
+    // of the current fbs_eval_resident (gather list, then scatter list), uploaded with its first chunk
+    std::vector<fbs_state *> states;
+    size_t state_bytes = 0;
+    fbs::StateLink *d_links = nullptr;
+    size_t links_capacity = 0;
+    hipEvent_t inputs_event = nullptr;   // an fbs_eval_resident that does not wait for its results: its host arrays have been read
+
     fbs::Profile prof;
+};
+
+// a context-owned device block of big-key ciphertexts [rows][T][D + 1]; not part of the scratch: it never moves while alive
+struct fbs_state {
+    fbs_ctx *ctx = nullptr;
+    uint64_t *d = nullptr;
+    size_t rows = 0, T = 0;
 };
 
 struct fbs_tvset {
@@ -329,6 +361,10 @@ int dev_decrypt_compact(const fbs_ctx *ctx, const uint64_t *d_words, size_t coun
 // and back: packed words [count][W] at width `bits` -> the fields at log2(2N) bits, d_ms [count][n + 1] as the blind rotation reads them
 // (re-rounded as the modulus switch rounds when bits > log2(2N))
 int dev_compact_unpack(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint32_t *d_ms, hipStream_t stream);
+
+// resident state (fbs_state.hip): the links of `a` between state rows and wire slots, one launch each
+int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);
+int dev_state_scatter(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);
 
 // profiling helpers
 void prof_begin(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t *e0, hipEvent_t *e1);

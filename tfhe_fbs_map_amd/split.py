@@ -30,6 +30,19 @@ consuming program's margin (`plan_chain`).  One client key serves every program 
         fresh = client.encrypt(b, names=[f"b{i}" for i in range(8)])
         acc = server.run_chain(adder8, [acc, fresh], rename=a_from_s, compact=True)
     client.decrypt(acc)
+
+Resident state.  With `resident=True`, `run` and `run_chain` leave the full outputs in the server's device memory and return a
+`ResidentOutputs`; it links into the next `run_chain` like an `EncryptedOutputs` (a bootstrap output goes in untouched), with no
+copy through the host and no refresh.  The state leaves the card only when asked: `fetch()` -> `EncryptedOutputs`,
+`fetch(compact=True)` -> `CompactOutputs` (compacted on the GPU; only the packed words cross the bus); `Server.restore` puts a
+fetched `EncryptedOutputs` back.
+
+    acc = server.run(adder8, client.encrypt(first), resident=True)
+    for b in stream:
+        nxt = server.run_chain(adder8, [acc, client.encrypt(b, names=b_names)], rename=a_from_s, resident=True)
+        acc.close()
+        acc = nxt
+    client.decrypt(acc.fetch(compact=True))
 """
 from __future__ import annotations
 
@@ -40,7 +53,7 @@ import numpy as np
 
 from .fbs_exec_env import ExecConfig, min_fbs_size, table_fusion_factor, table_is_valid
 
-__all__ = ["ServerKey", "EncryptedInputs", "EncryptedOutputs", "CompactOutputs", "Client", "Server", "FORMAT_VERSION",
+__all__ = ["ServerKey", "EncryptedInputs", "EncryptedOutputs", "CompactOutputs", "ResidentOutputs", "Client", "Server", "FORMAT_VERSION",
            "mask_key_fingerprint", "seeded_key_sizes", "compact_words", "output_noise_factor", "output_noise_factors",
            "plan_chain", "ChainLink", "client_choice"]
 
@@ -252,6 +265,44 @@ class CompactOutputs:
         return cls(names, T, bits, words, _fingerprint_of(d), _norm2_of(d, len(names)))
 
 
+class ResidentOutputs:
+    """Full output ciphertexts of one evaluation that stayed on the server's GPU (`Server.run` / `Server.run_chain` with
+    `resident=True`): row o of `state` (a `DeviceState`, [n_outputs][T][D+1]) is output o.  A source of `Server.run_chain` on the
+    server that made it, under the link rule of `EncryptedOutputs`; `fetch` brings it to the host, `close()` frees the state."""
+
+    def __init__(self, output_names, T, fingerprint, out_norm2, state, server=None, compact_bits=None):
+        self.output_names, self.T, self.fingerprint = list(output_names), int(T), bytes(fingerprint)
+        self.out_norm2 = None if out_norm2 is None else np.asarray(out_norm2, np.float64).reshape(-1)
+        self.state, self.server = state, server
+        self.compact_bits = compact_bits   # the width fetch(compact=True) takes by default: the producer's `Server.compact_bits`
+
+    @property
+    def closed(self):
+        return self.state is None or bool(self.state.closed)
+
+    def fetch(self, compact=False, bits=None):
+        """-> `EncryptedOutputs`, or with compact=True `CompactOutputs` at `bits` (None: the width `Server.compact_bits` picks for
+        the program that computed them, or for their noise after a chain); both as `run` / `run_compact` return them."""
+        if self.closed:
+            raise ValueError("the resident outputs are closed")
+        if not compact:
+            return EncryptedOutputs(list(self.output_names), self.T, self.state.fetch(), self.fingerprint, self.out_norm2)
+        bits = self.compact_bits if bits is None else int(bits)
+        if bits is None:
+            raise ValueError("no default compact width is recorded for these outputs: pass bits")
+        return CompactOutputs(list(self.output_names), self.T, int(bits), self.state.fetch(bits=int(bits)), self.fingerprint, self.out_norm2)
+
+    def close(self):
+        if self.state is not None:
+            self.state.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def client_choice(env, config: ExecConfig, programs=()):
     """The pure part of `Client`: (parameter set, fuse) of the server key.  programs=(): `config.choose_params_fuse` for env at the
     smallest p its tables need.  Otherwise one key for env and every program: p the largest any of them needs (or `fbs_size`),
@@ -361,12 +412,16 @@ class Server:
         self._programs[id(low)] = (prog, low)
         return prog, low
 
-    def run(self, env, inputs: EncryptedInputs) -> EncryptedOutputs:
+    def run(self, env, inputs: EncryptedInputs, resident=False):
+        """-> `EncryptedOutputs`; resident=True: the outputs stay on the GPU (fbs_eval_resident) -> `ResidentOutputs`."""
         if inputs.fingerprint != self.key.fingerprint:
             raise ValueError("inputs were encrypted for another server key")
         prog, low = self.program_for(env)
         if list(inputs.input_names) != list(low["input_names"]):
             raise ValueError("inputs belong to another program")
+        if resident:
+            feed = [("seeded", inputs.bodies[i], inputs.nonce0 + i * inputs.T) for i in range(len(low["input_names"]))]
+            return self._resident(env, prog, low, feed, inputs.T, self._out_norm2(low))
         cts = prog.eval_seeded(inputs.bodies, inputs.T, inputs.nonce0)
         return EncryptedOutputs(list(low["out_names"]), inputs.T, cts, self.key.fingerprint, self._out_norm2(low))
 
@@ -394,15 +449,53 @@ class Server:
     def _out_norm2(self, low, input_noise=None):
         return np.asarray(output_noise_factors(low, self.key.params.p_msg, self.key.fuse_tables, input_noise), np.float64)
 
-    def run_chain(self, env, sources, rename=None, compact=False, bits=None):
+    def _resident(self, env, prog, low, feed, T, out_norm2):
+        from .params import compact_output_bits
+        prm = self.key.params
+        norm2 = (env.fusion_stats(prm.p_msg) if self.key.fuse_tables else env.stats())["norm2_linprod"]
+        bits = compact_output_bits(prm, norm2, float(np.asarray(out_norm2).max(initial=0.0)))
+        if T < 1 or not len(low["out_names"]):
+            raise ValueError("resident outputs need at least one output and one sample")
+        state = self.ctx.state(len(low["out_names"]), T)
+        try:
+            prog.eval_resident(feed, T, 0, state)
+        except Exception:
+            state.close()
+            raise
+        return ResidentOutputs(list(low["out_names"]), T, self.key.fingerprint, out_norm2, state, self, bits)
+
+    def restore(self, outputs: EncryptedOutputs, compact_bits=None) -> "ResidentOutputs":
+        """An `EncryptedOutputs` (a `ResidentOutputs.fetch()`, possibly saved and loaded) back into device memory
+        (fbs_state_put).  compact_bits: the default width of a later fetch(compact=True) (None: it has to be passed then)."""
+        if outputs.fingerprint != self.key.fingerprint:
+            raise ValueError("outputs were computed under another server key")
+        cts = np.ascontiguousarray(outputs.cts, np.uint64)
+        if cts.ndim != 3 or cts.shape[:2] != (len(outputs.output_names), outputs.T) or cts.shape[2] != self.key.params.ct_words or not cts.size:
+            raise ValueError(f"ciphertexts of shape {cts.shape} do not fit the server key's parameter set")
+        state = self.ctx.state(cts.shape[0], cts.shape[1])
+        try:
+            state.put(cts)
+        except Exception:
+            state.close()
+            raise
+        return ResidentOutputs(list(outputs.output_names), outputs.T, self.key.fingerprint, outputs.out_norm2, state, self, compact_bits)
+
+    def run_chain(self, env, sources, rename=None, compact=False, bits=None, resident=False):
         """Evaluate `env` with each input taken by name from one of `sources`: the client's `EncryptedInputs` (seeded) and the
         `EncryptedOutputs` / `CompactOutputs` of earlier evaluations under this server key (fbs_eval_sources).  rename: {input name:
         source name} for an input whose source carries another name.  Compact links, and full links whose producer was noisier
         than a bootstrap output, are refreshed on the GPU: one bootstrap each per sample.  compact=True: compact outputs at `bits`
-        (None: the width `compact_bits` would pick for the noise these outputs carry).  `plan_chain` says what is refused."""
+        (None: the width `compact_bits` would pick for the noise these outputs carry).  `plan_chain` says what is refused.
+        A source may also be a `ResidentOutputs` of this server (a closed one, or another server's, is refused): its rows are read
+        on the GPU.  resident=True: the outputs stay there too -> `ResidentOutputs` (not with compact=True)."""
         from .params import compact_output_bits
+        if resident and compact:
+            raise ValueError("resident outputs are full ciphertexts: fetch(compact=True) compacts them when they leave the GPU")
         prm, fuse = self.key.params, self.key.fuse_tables
-        sources = [sources] if isinstance(sources, (EncryptedInputs, EncryptedOutputs, CompactOutputs)) else list(sources)
+        sources = [sources] if isinstance(sources, _SOURCE_TYPES) else list(sources)
+        for k, src in enumerate(sources):
+            if isinstance(src, ResidentOutputs) and not src.closed and (src.server is not self or src.state.ctx is not self.ctx):
+                raise ValueError("source %d is resident on another server" % k)
         links, T = plan_chain(prm, fuse, self.key.fingerprint, env, sources, rename)
         prog, low = self.program_for(env)
         feed = []
@@ -412,17 +505,22 @@ class Server:
                 feed.append(("seeded", src.bodies[ln.index], src.nonce0 + ln.index * src.T))
             elif ln.kind == "full":
                 feed.append(("full", src.cts[ln.index], ln.refresh))
+            elif ln.kind == "state":
+                feed.append(("state", src.state, ln.index, ln.refresh))
             else:
                 feed.append(("compact", src.words[ln.index], int(src.bits)))
         out_norm2 = self._out_norm2(low, [ln.noise for ln in links])
         names = list(low["out_names"])
+        run = prog.eval_resident if any(ln.kind == "state" for ln in links) else prog.eval_sources
+        if resident:
+            return self._resident(env, prog, low, feed, T, out_norm2)
         if not compact:
-            return EncryptedOutputs(names, T, prog.eval_sources(feed, T, 0), self.key.fingerprint, out_norm2)
+            return EncryptedOutputs(names, T, run(feed, T, 0), self.key.fingerprint, out_norm2)
         if bits is None:
             norm2 = (env.fusion_stats(prm.p_msg) if fuse else env.stats())["norm2_linprod"]
             bits = compact_output_bits(prm, norm2, float(out_norm2.max(initial=0.0)))
         bits = int(bits)
-        return CompactOutputs(names, T, bits, prog.eval_sources(feed, T, bits), self.key.fingerprint, out_norm2)
+        return CompactOutputs(names, T, bits, run(feed, T, bits), self.key.fingerprint, out_norm2)
 
 
 @dataclass
@@ -431,10 +529,13 @@ class ChainLink:
     name: str                     # the program's input
     source: int                   # which of the sources
     index: int                    # its row there (input or output position)
-    kind: str                     # "seeded", "full" or "compact"
+    kind: str                     # "seeded", "full", "compact" or "state" (a row of a ResidentOutputs: full ciphertexts on the GPU)
     refresh: bool                 # bootstrapped through the identity table before use
     noise: float                  # its noise factor going in: 0 fresh, 1 refreshed, the producer's out_norm2 for a plain full link
     margin: float | None = None   # params.refresh_margin of a refreshed link
+
+
+_SOURCE_TYPES = (EncryptedInputs, EncryptedOutputs, CompactOutputs, ResidentOutputs)
 
 
 def _names_of(src):
@@ -449,7 +550,8 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
     key or another T; an input that no source, or more than one, names; an output set saved without `out_norm2`; a link whose
     refresh margin (`params.refresh_margin`) is below `params.refresh_margin_needed` at the program's norm2.  A full link whose
     producer's factor is at most 1 (a bootstrap output or a constant) goes in as it is: the program's parameter set assumes
-    inputs no noisier than that.  Every other full link and every compact link is refreshed."""
+    inputs no noisier than that.  Every other full link and every compact link is refreshed.  A `ResidentOutputs` is a full link
+    whose ciphertexts are on the GPU (kind "state"), under the same rule; a closed one is refused."""
     from .params import margin_sigmas, refresh_margin, refresh_margin_needed
     low = env.lower()
     p = params.p_msg
@@ -467,8 +569,10 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
         raise ValueError("no sources for a program with inputs")
     T = None
     for k, src in enumerate(sources):
-        if not isinstance(src, (EncryptedInputs, EncryptedOutputs, CompactOutputs)):
-            raise TypeError("source %d is a %s, not EncryptedInputs, EncryptedOutputs or CompactOutputs" % (k, type(src).__name__))
+        if not isinstance(src, _SOURCE_TYPES):
+            raise TypeError("source %d is a %s, not EncryptedInputs, EncryptedOutputs, CompactOutputs or ResidentOutputs" % (k, type(src).__name__))
+        if isinstance(src, ResidentOutputs) and src.closed:
+            raise ValueError("source %d is resident state that has been closed" % k)
         if src.fingerprint != fingerprint:
             raise ValueError("source %d was computed under another server key" % k)
         if T is not None and src.T != T:
@@ -504,12 +608,13 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
                                  % (via, src.words.shape[-1], bits))
             link = ChainLink(name, k, j, "compact", True, 1.0, refresh_margin(params, bits, o2))
         else:
-            if src.cts.shape[-1] != params.ct_words:
+            kind = "state" if isinstance(src, ResidentOutputs) else "full"
+            if kind == "full" and src.cts.shape[-1] != params.ct_words:
                 raise ValueError("input %s: ciphertexts of %d words, the server key's set has %d" % (via, src.cts.shape[-1], params.ct_words))
             if o2 <= 1.0:
-                links.append(ChainLink(name, k, j, "full", False, o2))
+                links.append(ChainLink(name, k, j, kind, False, o2))
                 continue
-            link = ChainLink(name, k, j, "full", True, 1.0, refresh_margin(params, None, o2))
+            link = ChainLink(name, k, j, kind, True, 1.0, refresh_margin(params, None, o2))
         if link.margin < need * (1.0 - 1e-12):
             raise ValueError("input %s: its refresh would keep %.3f sigma (out_norm2 %g), below the %.3f the program's bootstraps keep"
                              % (via, link.margin, o2, need))

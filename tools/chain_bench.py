@@ -1,11 +1,14 @@
 """Chained evaluation (`Server.run_chain`, `fbs_eval_sources`): what keeping state on the server between programs costs.
 
 (a) An accumulator: adder8__search_p15 with a <- the previous sum (s0..s7) and b <- fresh client inputs, over --hops hops at T
-    samples, once with full links (`EncryptedOutputs`, kN + 1 words a bit) and once with compact links (`CompactOutputs`, refreshed
-    on the GPU).  Per link kind, one JSON line: bytes of state per hop, fresh-input bytes per hop, server seconds per hop (median of
+    samples, once with full links (`EncryptedOutputs`, kN + 1 words a bit), once with compact links (`CompactOutputs`, refreshed
+    on the GPU) and once with resident links (`ResidentOutputs`: the state stays in device memory, nothing crosses the bus but
+    the fresh inputs; the clock stops after the last hop has finished on the GPU).  Per link kind, one JSON line: bytes of state per hop, fresh-input bytes per hop, server seconds per hop (median of
     --reps chains, each the mean of its hops), and that the client decrypts the running sum after the last hop.
 (b) One adder128__search_p15 hop through compact links (a <- s of an earlier `run_compact`, b fresh) next to the same program's
     own `run_compact` on fresh inputs: the refresh overhead (medians of --reps).
+(c) adder128__search_p15 on fresh inputs three ways: `run` (full outputs to the host), `run_compact`, and `run(resident=True)` --
+    timed to the end of the evaluation on the GPU -- followed by one `fetch(compact=True)`, timed on its own.
 
 Both at the default 128-bit sets (`ExecConfig()`, one key for the chain: `Client(env, programs=[env])`).
 
@@ -73,21 +76,28 @@ def accumulator(T, hops, reps):
     for x in stream:
         clear = lut_oracle.eval_fbs_text(rec["fbs"], {**{f"a{i}": np.broadcast_to(clear[f"s{i}"], (T,)) for i in range(8)}, **x})
     lines = []
-    for link in ("full", "compact"):
-        compact = link == "compact"
+    for link in ("full", "compact", "resident"):
+        compact, resident = link == "compact", link == "resident"
         start = client.encrypt(first)
-        warm = server.run_chain(env, [server.run_compact(env, start) if compact else server.run(env, start), fresh[0]], rename=rename,
-                                compact=compact)   # warm-up: program load, scratch, identity table
+
+        def begin():
+            return server.run_compact(env, start) if compact else server.run(env, start, resident=resident)
+        warm = server.run_chain(env, [begin(), fresh[0]], rename=rename, compact=compact, resident=resident)   # warm-up: program load, scratch, identity table
         per_hop, state_bytes = [], 0
         for _ in range(reps):
-            acc = server.run_compact(env, start) if compact else server.run(env, start)
+            acc = begin()
+            server.ctx.sync()
             t0 = time.perf_counter()
             for f in fresh:
-                acc = server.run_chain(env, [acc, f], rename=rename, compact=compact)
+                nxt = server.run_chain(env, [acc, f], rename=rename, compact=compact, resident=resident)
+                if resident:
+                    acc.close()          # (waits for the hop that reads it)
+                acc = nxt
+            server.ctx.sync()
             per_hop.append((time.perf_counter() - t0) / hops)
-            data = acc.words if compact else acc.cts
-            state_bytes = int(data[:8].nbytes)              # what a hop carries over: the eight sum bits
-        got = client.decrypt(acc)
+            # what crosses the bus per hop for the eight sum bits
+            state_bytes = 0 if resident else int((acc.words if compact else acc.cts)[:8].nbytes)
+        got = client.decrypt(acc.fetch() if resident else acc)
         ok = all(np.array_equal(np.broadcast_to(got[k], (T,)), np.broadcast_to(clear[k], (T,))) for k in clear)
         line = dict(bench="adder8_accumulator", link=link, T=T, hops=hops, k=prm.k, N=prm.N, n=prm.n, p=prm.p_msg,
                     bits=getattr(warm, "bits", None), state_bytes_per_hop=state_bytes,
@@ -135,12 +145,49 @@ def adder128_hop(T, reps):
     return [line]
 
 
+def adder128_outputs(T, reps):
+    from tfhe_fbs_map_amd import Client, ExecConfig, Server
+    rec, env = _env("adder128__search_p15")
+    client = Client(env, ExecConfig(seed=1), programs=[env])
+    server = Server(client.server_key())
+    prm = client.params
+    rng = np.random.default_rng(0)
+    start = client.encrypt({n: rng.integers(0, 2, T) for n in env.lower()["input_names"]})
+    want = client.decrypt(server.run_compact(env, start))   # (warm-up too)
+    server.run(env, start)
+    with server.run(env, start, resident=True) as warm:
+        got = client.decrypt(warm.fetch(compact=True))
+    ok = all(np.array_equal(got[k], want[k]) for k in want)
+    t = dict(run=[], run_compact=[], resident=[], fetch_compact=[])
+    for _ in range(reps):
+        for name, call in (("run", lambda: server.run(env, start)), ("run_compact", lambda: server.run_compact(env, start))):
+            t0 = time.perf_counter()
+            call()
+            t[name].append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        out = server.run(env, start, resident=True)
+        server.ctx.sync()
+        t["resident"].append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        words = out.fetch(compact=True)
+        t["fetch_compact"].append(time.perf_counter() - t0)
+        out.close()
+    line = dict(bench="adder128_outputs", T=T, k=prm.k, N=prm.N, n=prm.n, p=prm.p_msg, bits=words.bits,
+                full_output_bytes=len(words.output_names) * T * prm.ct_words * 8, compact_output_bytes=int(words.words.nbytes),
+                resident_then_fetch_compact_decrypts_as_run_compact=bool(ok),
+                **{k + "_s_median": float(np.median(v)) for k, v in t.items()}, **{k + "_all": [round(x, 4) for x in v] for k, v in t.items()})
+    print(json.dumps(line), flush=True)
+    server.ctx.close()
+    client.ctx.close()
+    return [line]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--hops", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--only", choices=("accumulator", "adder128"), default=None)
+    ap.add_argument("--only", choices=("accumulator", "adder128", "outputs"), default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace", default=None, help="summarise this rocprofv3 kernel_trace.csv instead of running")
     args = ap.parse_args()
@@ -152,6 +199,8 @@ def main():
         lines += accumulator(args.T, args.hops, args.reps)
     if args.only in (None, "adder128"):
         lines += adder128_hop(args.T, args.reps)
+    if args.only in (None, "outputs"):
+        lines += adder128_outputs(args.T, args.reps)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
