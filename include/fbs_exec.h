@@ -117,12 +117,14 @@ int fbs_ctx_reserve(fbs_ctx *ctx, size_t max_keyswitches, size_t max_shared_rows
  *   "br_cu_lean" (1)        ... and between one and two per CU as two 128-register workgroups per CU (2: always, 0: never)
  *   "br_k2_shape" (0)       GLWE dimension 2: 0 by launch size, 3 always three waves per bootstrap, 12 always twelve
  *   "br_glwe_fpw" (0)       other GLWE dimensions >= 2: bootstraps per workgroup, 0 by launch size; 1, 2; larger: the
- *                           throughput shape */
+ *                           throughput shape
+ *   "pack_slices" (0)       packed outputs: slices the i-sum of one packed sample is cut into, 0 by launch size (at most 32) */
 int fbs_ctx_tune(fbs_ctx *ctx, const char *knob, int64_t value);
 /* counters: "scratch_growths" (how often a call (re)allocated scratch, i.e. blocked), "ms_capacity", "acc_capacity",
  * "wires_capacity", "next_nonce", "cu_count"; "has_secret" (1: the context holds secret keys), "seeded_keys" (1: its keys
  * came from fbs_keygen_seeded or fbs_import_seeded_keys); "states_alive", "state_bytes" (resident state: fbs_state blocks not
- * yet destroyed, and the device bytes they hold) */
+ * yet destroyed, and the device bytes they hold); "packing_key" (1: the context holds a packing key), "packing_levels" and
+ * "packing_base_bits" (its t_p and gamma_p, 0 without one) */
 int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value);
 /* text of the last failure on `ctx` (or of the last failed fbs_ctx_create when ctx == NULL) */
 const char *fbs_last_error(const fbs_ctx *ctx);
@@ -422,6 +424,64 @@ int fbs_state_fetch(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows,
 /* The way back (state saved to disk by a full fetch): cts [rows][T][D+1] into rows [row0, row0 + rows).  Every word must be a
  * canonical residue (FBS_E_INVALID otherwise, nothing written).  Blocks until the words are on the device. */
 int fbs_state_put(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *cts);
+
+/* ---- packed outputs: up to N output bits in one GLWE ciphertext under the key the client already holds ------------------------
+ * A compact ciphertext costs (n + 1) w bits per output.  A PACKING KEY SWITCH writes up to N of them into the N coefficients of one
+ * GLWE sample under the big key (S_0 .. S_(k-1)), (k + 1) N w bits for N outputs.
+ *
+ * PACKING KEY, parameters (t_p, gamma_p), 1 <= t_p, 1 <= gamma_p, t_p gamma_p <= 31.  (The packing kernel transforms its digits
+ * with the general forward transform -- "first=0" in fbs_debug_transform_list, inputs |x| <= q -- so gamma_p has no further bound.)
+ * Rows (i, v), i < n, v < t_p, layout [n][t_p][k+1][N]: row (i, v) is a GLWE encryption of the constant polynomial s_i h_v,
+ * s = sk_lwe, h_v = round(q / 2^(gamma_p (v+1))): polynomials A_0 .. A_(k-1), then B = sum_c A_c S_c + e + s_i h_v (e: sigma_glwe).
+ * The masks come from ChaCha20 under the context's public mask key, the noise from the context's key, both on streams no other
+ * key or ciphertext uses ("Randomness"); only the bodies [n][t_p][N] travel.  Every (k, N) a context can be
+ * created with is served.  The key belongs to the evaluation keys it was made beside: fbs_keygen, fbs_import_keys,
+ * fbs_keygen_seeded and fbs_import_seeded_keys drop it.
+ *
+ * PACKING.  Input: `count` big-key ciphertexts, in order; ciphertext j goes to coefficient j mod N of sample g = j / N; the last
+ * sample may be partly filled (fill f_g <= N).
+ *   1. key switch to the small key at width 31, exactly as fbs_compact_dev(bits = 31): fields m_0 .. m_n in Z_(2^31);
+ *   2. mask fields to t_p gamma_p bits: r = 31 - t_p gamma_p; r > 0: a' = ((m_i >> (r-1)) + 1) >> 1 mod 2^(t_p gamma_p); r = 0: a' = m_i;
+ *   3. a' into t_p BALANCED digits d_v in [-2^(gamma_p - 1), 2^(gamma_p - 1)), v = 0 the most significant: from the least
+ *      significant up, u = field + carry; u >= 2^(gamma_p - 1): d = u - 2^gamma_p, carry 1; else d = u, carry 0; the carry out of
+ *      the top is dropped (the key switch's own convention);
+ *   4. body lifted to Z_q: B_j = (m_n q + 2^30) >> 31, an exact integer;
+ *   5. D_(i,v)(X) = sum_j d_v(a' of ciphertext j, field i) X^j;  ACC_c = - sum_(i,v) D_(i,v) A_c^(i,v)  (c < k),
+ *      ACC_k = sum_j B_j X^j - sum_(i,v) D_(i,v) B^(i,v);  negacyclic, mod q.
+ * Every quantity is an exact residue: the result does not depend on summation order, launch shape or "pack_slices".
+ *
+ * TRANSPORT.  Width w, log2(2N) <= w <= 31.  Every coefficient x is rounded as the compact format rounds, q treated as 2^46:
+ * ((x >> (45 - w)) + 1) >> 1 mod 2^w (no mean compensation).  A sample is its k N mask fields, component-major, then the f_g body
+ * fields of coefficients j < f_g; fields of w bits, bit-packed as compact ciphertexts are (stream bit b = bit b mod 64 of word
+ * b / 64, zero padding); every sample starts on a word boundary; a batch is its samples back to back: fbs_packed_words.
+ * DECODE.  phase_j = body_j - sum_c (A_c S_c)_j mod 2^w;  msg = ((phase 2p + 2^(w-1)) >> w) mod 2p.
+ * Noise: params.packed_output_variance.  Every entry returns FBS_E_INVALID for a w outside [log2(2N), 31] and writes nothing when
+ * it fails. */
+/* Makes the packing key on the host and uploads it in the transform domain.  FBS_E_STATE unless the context's keys came from
+ * fbs_keygen_seeded on this context (the masks are the mask key's); FBS_E_INVALID for parameters outside the range above. */
+int fbs_packing_keygen(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p);
+/* word counts for t_p levels (0: the context's own key; FBS_E_STATE without one): sizes[0] = n t_p N (bodies), sizes[1] = n t_p (k+1) N */
+int fbs_packing_key_sizes(const fbs_ctx *ctx, uint32_t t_p, size_t sizes[2]);
+/* bodies [n][t_p][N] (what a server needs beside the mask key).  full (may be NULL) is a test hook: the whole key
+ * [n][t_p][k+1][N] in the coefficient domain, as fbs_export_keys returns the others.  Either pointer may be NULL. */
+int fbs_export_packing_key(const fbs_ctx *ctx, uint64_t *bodies, uint64_t *full);
+/* The mirror: expands the masks from the context's mask key and uploads.  Works on evaluation-only contexts (after
+ * fbs_import_seeded_keys).  Every body word must be a canonical residue (FBS_E_INVALID); a refused call leaves the previous
+ * packing key in place. */
+int fbs_import_packing_key(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, const uint64_t *bodies);
+/* words of a batch of `count` outputs at width `bits`: (count / N) full samples of (k + 1) N w / 64 words, and for a rest
+ * f = count mod N > 0 one of k N w / 64 + ceil(f w / 64) */
+int fbs_packed_words(const fbs_ctx *ctx, size_t count, uint32_t bits, size_t *words);
+/* d_cts [count][D+1] (any big-key ciphertexts, device) -> d_words [fbs_packed_words], asynchronous on `stream`; needs no secret;
+ * FBS_E_STATE without a packing key.  Runs in passes of the modulus-switch scratch (whole samples of at least 8192 ciphertexts);
+ * its own scratch (the transposed fields of a pass, partial accumulators) grows like any other: repeated calls of one shape do
+ * not grow it. */
+int fbs_pack_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_words, void *stream);
+/* Rows [row0, row0 + rows) of a resident state, flattened [row][sample] in that order, packed on the device as fbs_pack_dev packs
+ * them (word for word fbs_pack_dev of fbs_state_fetch(bits = 0)); only the packed words cross the bus.  Blocks until they are back. */
+int fbs_state_fetch_packed(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint32_t bits, uint64_t *out);
+/* the decode on the host, words [fbs_packed_words(count)] -> msgs[count].  FBS_E_STATE on an evaluation-only context. */
+int fbs_decrypt_packed(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs);
 
 /* ---- a loaded program, one level at a time (multi-GPU hosts) -----------------
  * The two independent axes of the reference's eval loop (fbs_exec_env.py:211-223) are the gates

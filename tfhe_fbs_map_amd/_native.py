@@ -182,6 +182,14 @@ def _load():
         "fbs_compact_fields_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_refresh_compact_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_eval_sources": (i32, [vp, vp, vp, sz, u32, vp]),
+        "fbs_packing_keygen": (i32, [vp, u32, u32]),
+        "fbs_packing_key_sizes": (i32, [vp, u32, C.POINTER(sz * 2)]),
+        "fbs_export_packing_key": (i32, [vp, vp, vp]),
+        "fbs_import_packing_key": (i32, [vp, u32, u32, vp]),
+        "fbs_packed_words": (i32, [vp, sz, u32, C.POINTER(sz)]),
+        "fbs_pack_dev": (i32, [vp, vp, sz, u32, vp, vp]),
+        "fbs_state_fetch_packed": (i32, [vp, vp, sz, sz, u32, vp]),
+        "fbs_decrypt_packed": (i32, [vp, vp, sz, u32, vp]),
         "fbs_state_create": (i32, [vp, sz, sz, C.POINTER(vp)]),
         "fbs_state_destroy": (None, [vp]),
         "fbs_state_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz)]),
@@ -250,6 +258,8 @@ EXPORTED_SYMBOLS = (
     "fbs_compact_words", "fbs_compact_dev", "fbs_eval_seeded_compact", "fbs_decrypt_compact", "fbs_decrypt_compact_dev",
     "fbs_compact_fields_dev", "fbs_refresh_compact_dev", "fbs_eval_sources",
     "fbs_state_create", "fbs_state_destroy", "fbs_state_info", "fbs_eval_resident", "fbs_state_fetch", "fbs_state_put",
+    "fbs_packing_keygen", "fbs_packing_key_sizes", "fbs_export_packing_key", "fbs_import_packing_key", "fbs_packed_words",
+    "fbs_pack_dev", "fbs_state_fetch_packed", "fbs_decrypt_packed",
 )
 
 lib = _load()
@@ -493,6 +503,14 @@ class DeviceState:
         bits = int(bits)
         out = np.empty((max(0, rows), self.T, self.ctx.compact_words(bits) if bits else self.ctx.params.ct_words), np.uint64)
         self.ctx._check(lib.fbs_state_fetch(self.ctx._h, self._live(), int(row0), rows, bits, _ptr(out)))
+        return out
+
+    def fetch_packed(self, bits, row0=0, rows=None):
+        """rows [row0, row0 + rows), flattened [row][sample], packed on the GPU into GLWE samples at width `bits`
+        (fbs_state_fetch_packed) -> the packed words, `Context.packed_words(rows * T, bits)` of them"""
+        rows = self.rows - int(row0) if rows is None else int(rows)
+        out = np.empty(self.ctx.packed_words(max(0, rows) * self.T, bits), np.uint64)
+        self.ctx._check(lib.fbs_state_fetch_packed(self.ctx._h, self._live(), int(row0), rows, int(bits), _ptr(out)))
         return out
 
     def put(self, cts, row0=0):
@@ -756,6 +774,68 @@ class Context:
     def decrypt_compact_dev(self, d_words, count, d_msgs, bits=None, stream=0):
         self._check(lib.fbs_decrypt_compact_dev(self._h, d_words or None, count, self.default_compact_bits if bits is None else int(bits),
                                                 d_msgs or None, stream or None))
+
+    # ---- packed outputs: up to N outputs in one GLWE sample under the big key (include/fbs_exec.h, "packed outputs") ----
+    def packing_keygen(self, t_p, gamma_p):
+        """fbs_packing_keygen: the packing key (t_p levels of gamma_p bits) beside the keys of `keygen_seeded`"""
+        self._check(lib.fbs_packing_keygen(self._h, int(t_p), int(gamma_p)))
+
+    def packing_key_sizes(self, t_p=0):
+        """(bodies, whole key) in words for t_p levels (0: the context's own key)"""
+        sizes = (C.c_size_t * 2)()
+        self._check(lib.fbs_packing_key_sizes(self._h, int(t_p), C.byref(sizes)))
+        return int(sizes[0]), int(sizes[1])
+
+    def export_packing_key(self, full=False):
+        """dict(packing_levels, packing_base_bits, packing_bodies [n][t_p][N]); full=True adds `full`, the whole key
+        [n][t_p][k+1][N] in the coefficient domain (a test hook)"""
+        nb, nf = self.packing_key_sizes()
+        bodies = np.empty(nb, np.uint64)
+        whole = np.empty(nf, np.uint64) if full else None
+        self._check(lib.fbs_export_packing_key(self._h, _ptr(bodies), _ptr(whole)))
+        out = dict(packing_levels=self.stat("packing_levels"), packing_base_bits=self.stat("packing_base_bits"), packing_bodies=bodies)
+        if full:
+            prm = self.params
+            out["full"] = whole.reshape(prm.n, out["packing_levels"], prm.k + 1, prm.N)
+        return out
+
+    def import_packing_key(self, t_p, gamma_p, bodies):
+        """fbs_import_packing_key: the masks come from the context's mask key; works on evaluation-only contexts"""
+        bodies = _c(bodies, np.uint64).ravel()
+        if 1 <= int(t_p) <= 31 and bodies.size != self.packing_key_sizes(t_p)[0]:
+            raise ValueError(f"packing_bodies has {bodies.size} words, the parameter set needs {self.packing_key_sizes(t_p)[0]}")
+        self._check(lib.fbs_import_packing_key(self._h, int(t_p), int(gamma_p), _ptr(bodies)))
+
+    def packed_words(self, count, bits):
+        """uint64 words of `count` outputs packed at width `bits` (fbs_packed_words)"""
+        w = C.c_size_t()
+        self._check(lib.fbs_packed_words(self._h, int(count), int(bits), C.byref(w)))
+        return int(w.value)
+
+    def pack_dev(self, d_cts, count, d_words, bits, stream=0):
+        """fbs_pack_dev: `count` big-key ciphertexts at d_cts -> packed words at d_words, asynchronous on `stream`; no secret"""
+        self._check(lib.fbs_pack_dev(self._h, d_cts or None, int(count), int(bits), d_words or None, stream or None))
+
+    def pack(self, cts, bits):
+        """Host ciphertexts [..][D+1] -> packed words (through `pack_dev`); for tests and one-off calls"""
+        import torch
+        cts = _c(cts, np.uint64).reshape(-1, self.params.ct_words)
+        count = cts.shape[0]
+        d_c = torch.from_numpy(cts.view(np.int64)).to("cuda:%d" % self.device)
+        d_w = torch.zeros(max(1, self.packed_words(count, bits)), dtype=torch.int64, device=d_c.device)
+        torch.cuda.synchronize(d_c.device)
+        self.pack_dev(d_c.data_ptr(), count, d_w.data_ptr(), bits)
+        self.sync()
+        return d_w[:self.packed_words(count, bits)].cpu().numpy().view(np.uint64)
+
+    def decrypt_packed(self, words, count, bits):
+        """Packed words of `count` outputs -> messages [count] (fbs_decrypt_packed, on the host)"""
+        words = _c(words, np.uint64).ravel()
+        if words.size != self.packed_words(count, bits):
+            raise ValueError(f"{words.size} packed words for {count} outputs at {bits} bits (the parameter set needs {self.packed_words(count, bits)})")
+        out = np.empty(int(count), np.int64)
+        self._check(lib.fbs_decrypt_packed(self._h, _ptr(words), int(count), int(bits), _ptr(out)))
+        return out
 
     def bootstrap_batch(self, tvset, cts, table_ids=None):
         cts = _c(cts, np.uint64)

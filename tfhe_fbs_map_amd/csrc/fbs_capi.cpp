@@ -10,6 +10,7 @@
 
 #include "fbs_compact.hpp"
 #include "fbs_internal.hpp"
+#include "fbs_pack.hpp"
 #include "fbs_plan.hpp"
 
 using namespace fbs;
@@ -251,6 +252,9 @@ int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value) try {
     else if (k == "seeded_keys") *value = ctx->have_keys && ctx->seeded_keys;
     else if (k == "states_alive") *value = (int64_t)ctx->states.size();
     else if (k == "state_bytes") *value = (int64_t)ctx->state_bytes;
+    else if (k == "packing_key") *value = ctx->have_pack;
+    else if (k == "packing_levels") *value = ctx->have_pack ? ctx->pack_t : 0;
+    else if (k == "packing_base_bits") *value = ctx->have_pack ? ctx->pack_gamma : 0;
     else return set_error(ctx, FBS_E_INVALID, "unknown statistic '" + k + "'");
     return FBS_OK;
 } FBS_API_CATCH(ctx)
@@ -272,7 +276,8 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     if (ctx->scratch_used) (void)hipStreamSynchronize(ctx->scratch_stream);
     for (void *p : {(void *)ctx->d_bsk_hat, (void *)ctx->d_bsk_hat_small, (void *)ctx->d_ksk, (void *)ctx->d_ksk_f, (void *)ctx->d_ks_corr, (void *)ctx->d_ks_a, (void *)ctx->d_ks_b, (void *)ctx->d_ks_c, (void *)ctx->d_tw_fwd, (void *)ctx->d_tw_inv, (void *)ctx->d_psi_pow, (void *)ctx->d_ms, (void *)ctx->d_ms_eps, (void *)ctx->d_ms_body, (void *)ctx->d_acc, (void *)ctx->d_stage_in, (void *)ctx->d_stage_out, (void *)ctx->d_stage_ids,
                     (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_sk_lwe_bits, (void *)ctx->d_io_msgs,
-                    (void *)ctx->d_compact, (void *)ctx->d_links})
+                    (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_key, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc,
+                    (void *)ctx->d_packed})
         if (p) (void)hipFree(p);
     for (fbs_state *st : ctx->states) {   // the states still alive
         (void)hipFree(st->d);
@@ -309,6 +314,7 @@ int fbs_keygen(fbs_ctx *ctx) try {
     if (rc == FBS_OK) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
     ctx->have_keys = true;
+    ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
@@ -359,6 +365,7 @@ int fbs_import_keys(fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glw
     if (rc == FBS_OK) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
     ctx->have_keys = true;
+    ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
@@ -472,6 +479,7 @@ int fbs_keygen_seeded(fbs_ctx *ctx) try {
     if (rc == FBS_OK) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
     ctx->have_keys = true;
+    ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
@@ -533,6 +541,7 @@ int fbs_import_seeded_keys(fbs_ctx *ctx, const uint8_t mask_key[32], const uint6
     ctx->eval_only = true;
     if (int rc = dev_upload_keys(ctx)) return rc;
     ctx->have_keys = true;
+    ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
@@ -1714,6 +1723,178 @@ int fbs_state_put(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const u
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     FBS_HIP(ctx, hipMemcpyAsync(st->d + row0 * st->T * ctw, cts, words * 8, hipMemcpyHostToDevice, ctx->stream));
     return sync_stream(ctx, ctx->stream);
+} FBS_API_CATCH(ctx)
+
+// ---- packed outputs: up to N outputs in one GLWE sample under the big key (fbs_pack.hpp, fbs_pack.hip) -----------------------
+static int check_packing_params(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) {
+    if (const char *why = packing_params_refused(t_p, gamma_p)) return set_error(ctx, FBS_E_INVALID, why);
+    if (!pack_shape_built(ctx->p.log_n_poly, ctx->p.k)) return set_error(ctx, FBS_E_INVALID, "no packing kernel for this (k, N)");
+    return FBS_OK;
+}
+static int check_packed_words(const fbs_ctx *ctx, size_t count, uint32_t bits) {
+    if (count / ctx->N + 1 > SIZE_MAX / 8 / packed_sample_words(ctx->p.k, ctx->N, ctx->N, bits))
+        return set_error(ctx, FBS_E_INVALID, "packed words overflow");
+    return FBS_OK;
+}
+// installs (t_p, gamma_p, bodies) as the context's packing key: expands the masks, transforms on the device; the previous key
+// stays until this has succeeded
+static int install_packing_key(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies) {
+    std::vector<uint64_t> full;
+    host_expand_packing_key(ctx, ctx->mask_key, t_p, bodies.data(), full);
+    const bool had = ctx->have_pack;
+    ctx->have_pack = false;
+    if (int rc = dev_upload_packing_key(ctx, full, t_p)) {
+        // (the device copy may be half written: re-install the previous key, or leave the context without one)
+        if (had) {
+            host_expand_packing_key(ctx, ctx->mask_key, ctx->pack_t, ctx->pack_bodies.data(), full);
+            const std::string text = ctx->err;
+            ctx->have_pack = dev_upload_packing_key(ctx, full, ctx->pack_t) == FBS_OK;
+            ctx->err = text;
+        }
+        return rc;
+    }
+    ctx->pack_bodies.swap(bodies);
+    ctx->pack_t = t_p;
+    ctx->pack_gamma = gamma_p;
+    ctx->have_pack = true;
+    return FBS_OK;
+}
+
+int fbs_packing_keygen(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "a packing key goes with seeded keys (fbs_keygen_seeded)");
+    if (int rc = check_packing_params(ctx, t_p, gamma_p)) return rc;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> bodies;
+    host_packing_keygen(ctx, t_p, gamma_p, bodies);
+    return install_packing_key(ctx, t_p, gamma_p, bodies);
+} FBS_API_CATCH(ctx)
+
+int fbs_packing_key_sizes(const fbs_ctx *ctx, uint32_t t_p, size_t sizes[2]) try {
+    if (!ctx || !sizes) return FBS_E_INVALID;
+    if (t_p == 0) {
+        if (!ctx->have_pack) return set_error(ctx, FBS_E_STATE, "the context has no packing key");
+        t_p = ctx->pack_t;
+    }
+    if (t_p > 31) return set_error(ctx, FBS_E_INVALID, "packing key needs 1 <= t_p <= 31");
+    sizes[0] = (size_t)ctx->p.n * t_p * ctx->N;
+    sizes[1] = sizes[0] * (ctx->p.k + 1);
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_export_packing_key(const fbs_ctx *ctx, uint64_t *bodies, uint64_t *full) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (!ctx->have_pack) return set_error(ctx, FBS_E_STATE, "the context has no packing key");
+    if (bodies) std::memcpy(bodies, ctx->pack_bodies.data(), ctx->pack_bodies.size() * 8);
+    if (full) {
+        std::vector<uint64_t> key;
+        host_expand_packing_key(ctx, ctx->mask_key, ctx->pack_t, ctx->pack_bodies.data(), key);
+        std::memcpy(full, key.data(), key.size() * 8);
+    }
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_import_packing_key(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, const uint64_t *bodies) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (!bodies) return set_error(ctx, FBS_E_INVALID, "null argument");
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "a packing key goes with seeded keys (fbs_import_seeded_keys)");
+    if (int rc = check_packing_params(ctx, t_p, gamma_p)) return rc;
+    const size_t words = (size_t)ctx->p.n * t_p * ctx->N;
+    for (size_t i = 0; i < words; i++)
+        if (bodies[i] >= FQ) return set_error(ctx, FBS_E_INVALID, "packing-key body word is not a canonical residue");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> copy(bodies, bodies + words);
+    return install_packing_key(ctx, t_p, gamma_p, copy);
+} FBS_API_CATCH(ctx)
+
+int fbs_packed_words(const fbs_ctx *ctx, size_t count, uint32_t bits, size_t *words) try {
+    if (!ctx || !words) return FBS_E_INVALID;
+    if (int rc = check_bits(ctx, bits)) return rc;
+    if (int rc = check_packed_words(ctx, count, bits)) return rc;
+    *words = packed_words(ctx->p.k, ctx->N, count, bits);
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+// Ciphertexts per pass: what the modulus-switch scratch holds (at least COMPACT_PASS), cut down to whole samples -- and the
+// packing scratch for a pass of that size (transposed fields, partial accumulators), grown like any other scratch
+static int pack_reserve(fbs_ctx *ctx, size_t count, size_t *pass_out) {
+    const size_t N = ctx->N, whole = std::max(ctx->ms_capacity, COMPACT_PASS) / N * N;
+    const size_t pass = std::min((count + N - 1) / N * N, whole), samples = pass / N;
+    if (int rc = ensure_ms(ctx, std::min(count, pass))) return rc;
+    if (int rc = grow(ctx, ctx->d_pack_fields, ctx->pack_fields_capacity, (size_t)(ctx->p.n + 1) * pass, 4, true)) return rc;
+    // (slices x samples is largest for the whole pass or for a single sample, whichever the launch rule favours)
+    size_t rows = 0;
+    for (size_t g = 1; g <= samples; g++) rows = std::max(rows, g * pack_slices_for(ctx, g));
+    if (int rc = grow(ctx, ctx->d_pack_acc, ctx->pack_acc_capacity, rows * (ctx->p.k + 1) * N, 8, true)) return rc;
+    *pass_out = pass;
+    return FBS_OK;
+}
+static int pack_prologue(const fbs_ctx *ctx, size_t count, uint32_t bits) {
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (!ctx->have_pack) return set_error(ctx, FBS_E_STATE, "the context has no packing key (fbs_packing_keygen / fbs_import_packing_key)");
+    if (int rc = check_bits(ctx, bits)) return rc;
+    return check_packed_words(ctx, count, bits);
+}
+// the passes of fbs_pack_dev; `staging` non-null: each pass is packed there and copied to the host array `out`
+static int pack_passes(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_words, uint64_t *out, size_t pass,
+                       hipStream_t s) {
+    const size_t ctw = ctx->D + 1, per_pass = packed_words(ctx->p.k, ctx->N, pass, bits);
+    for (size_t f0 = 0; f0 < count; f0 += pass) {
+        const size_t rows = std::min(pass, count - f0), w0 = f0 / pass * per_pass;
+        const GateView gv = batch_view(d_cts + f0 * ctw, nullptr, nullptr, rows);
+        uint64_t *dst = out ? d_words : d_words + w0;
+        int rc = dev_keyswitch(ctx, gv, ctx->d_ms, 31, s);
+        if (rc == FBS_OK) rc = dev_pack(ctx, ctx->d_ms, rows, bits, dst, s);
+        if (rc != FBS_OK) return rc;
+        if (out && hipMemcpyAsync(out + w0, dst, packed_words(ctx->p.k, ctx->N, rows, bits) * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+            return set_error(ctx, FBS_E_DEVICE, "copying packed words to the host failed");
+    }
+    return FBS_OK;
+}
+
+// (no secret needed: runs on evaluation-only contexts)
+int fbs_pack_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_words, void *stream) try {
+    if (int rc = io_prologue(ctx, d_cts, d_words, count, IO_CT_WORDS, nullptr)) return rc;
+    if (int rc = pack_prologue(ctx, count, bits)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    size_t pass = 0;
+    int rc = pack_reserve(ctx, count, &pass);
+    if (rc != FBS_OK) return rc;
+    hipStream_t s = pick(ctx, stream);
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    if ((rc = pack_passes(ctx, d_cts, count, bits, d_words, nullptr, pass, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+    return scratch_done(ctx, s);
+} FBS_API_CATCH(ctx)
+
+int fbs_state_fetch_packed(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint32_t bits, uint64_t *out) try {
+    if (!ctx) return FBS_E_INVALID;
+    int rc = check_state_rows(ctx, st, row0, rows, out);
+    if (rc != FBS_OK) return rc;
+    const size_t count = rows * st->T;   // (a state's rows * T * (D + 1) words fit a size_t)
+    if ((rc = pack_prologue(ctx, count, bits)) != FBS_OK) return rc;
+    if (rows == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    size_t pass = 0;
+    if ((rc = pack_reserve(ctx, count, &pass)) != FBS_OK) return rc;
+    if ((rc = grow(ctx, ctx->d_packed, ctx->packed_capacity, packed_words(ctx->p.k, ctx->N, pass, bits), 8, true)) != FBS_OK) return rc;
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    if ((rc = pack_passes(ctx, st->d + row0 * st->T * (ctx->D + 1), count, bits, ctx->d_packed, out, pass, s)) != FBS_OK)
+        return scratch_fail(ctx, s, rc);
+    if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
+    return sync_stream(ctx, s);
+} FBS_API_CATCH(ctx)
+
+int fbs_decrypt_packed(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs) try {
+    if (int rc = io_prologue(ctx, words, msgs, count, IO_SECRET, nullptr)) return rc;
+    if (int rc = check_bits(ctx, bits)) return rc;
+    if (int rc = check_packed_words(ctx, count, bits)) return rc;
+    host_decrypt_packed(ctx, words, count, bits, msgs);
+    return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 // ---------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@
 #include "fbs_internal.hpp"
 #include "fbs_chacha.hpp"
 #include "fbs_compact.hpp"
+#include "fbs_pack.hpp"
 
 namespace fbs {
 
@@ -425,6 +426,72 @@ void host_decrypt_compact(const fbs_ctx *ctx, const uint64_t *words, size_t coun
 void host_compact_trivial(const fbs_ctx *ctx, uint64_t body, uint32_t bits, uint64_t *words) {
     const uint32_t n = ctx->p.n, W = compact_words(n, bits), m_n = compact_round(body, bits);
     for (uint32_t j = 0; j < W; j++) words[j] = compact_word(j, n + 1, bits, [&](uint32_t f) { return f == n ? m_n : 0u; });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Packed outputs (fbs_pack.hpp; include/fbs_exec.h, "packed outputs").  The packing key: n t_p GLWE encryptions under the big key of
+// the constants sk_lwe[i] h_v, masks under the public mask key on streams of their own (DOM_PACK_MASK), noise under the context's
+// key (DOM_PACK_NOISE) -- made only when asked for, so that nothing else a context derives changes.
+// ---------------------------------------------------------------------------------------------
+void host_packing_keygen(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies) {
+    const uint32_t N = ctx->N, n = ctx->p.n, k = ctx->p.k;
+    const std::vector<std::vector<uint32_t>> support = glwe_support(ctx);
+    bodies.assign((size_t)n * t_p * N, 0);
+    parallel_for((size_t)n * t_p, [&](size_t r0, size_t r1) {
+        std::vector<uint64_t> a(N);
+        for (size_t r = r0; r < r1; r++) {
+            const uint32_t i = (uint32_t)(r / t_p), v = (uint32_t)(r % t_p);
+            uint64_t *body = bodies.data() + r * N;
+            for (uint32_t j = 0; j < N; j++)
+                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_PACK_NOISE, r), j, ctx->p.sigma_glwe));
+            for (uint32_t c = 0; c < k; c++) {
+                rand_words(ctx->mask_key, stream_id(DOM_PACK_MASK, r), (uint64_t)c * N, a.data(), N);
+                for (uint32_t j = 0; j < N; j++) a[j] = fq_fold(a[j]);
+                add_times_key(body, a.data(), support[c], N);
+            }
+            if (ctx->sk_lwe[i]) body[0] = fq_add(body[0], pack_gadget(gamma_p, v));
+        }
+    });
+}
+
+void host_expand_packing_key(const fbs_ctx *ctx, const RandKey &mask_key, uint32_t t_p, const uint64_t *bodies, std::vector<uint64_t> &full) {
+    const uint32_t N = ctx->N, n = ctx->p.n, k = ctx->p.k;
+    const size_t row_words = (size_t)(k + 1) * N;
+    full.assign((size_t)n * t_p * row_words, 0);
+    parallel_for((size_t)n * t_p, [&](size_t r0, size_t r1) {
+        for (size_t r = r0; r < r1; r++) {
+            uint64_t *row = full.data() + r * row_words;
+            rand_words(mask_key, stream_id(DOM_PACK_MASK, r), 0, row, (size_t)k * N);
+            for (size_t j = 0; j < (size_t)k * N; j++) row[j] = fq_fold(row[j]);
+            std::memcpy(row + (size_t)k * N, bodies + r * N, (size_t)N * 8);
+        }
+    });
+}
+
+// The decode: phase_j = body_j - sum_c (A_c S_c)_j mod 2^w over the fields of each sample (32-bit wrapping sums are exact mod 2^w),
+// msg = round(phase 2p / 2^w) mod 2p.  Sample g holds outputs g N .. g N + fill - 1 in its first `fill` coefficients.
+void host_decrypt_packed(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs) {
+    const uint32_t N = ctx->N, k = ctx->p.k;
+    const uint64_t two_p = 2ull * ctx->p.p_msg;
+    const size_t samples = (count + N - 1) / N, full_words = packed_sample_words(k, N, N, bits);
+    const std::vector<std::vector<uint32_t>> support = glwe_support(ctx);
+    parallel_for(samples, [&](size_t g0, size_t g1) {
+        std::vector<uint32_t> sum(N), a(N);
+        for (size_t g = g0; g < g1; g++) {
+            const uint64_t *sample = words + g * full_words;
+            const uint32_t fill = (uint32_t)std::min<size_t>(N, count - g * N);
+            std::fill(sum.begin(), sum.end(), 0u);
+            for (uint32_t c = 0; c < k; c++) {
+                for (uint32_t j = 0; j < N; j++) a[j] = compact_field(sample, c * N + j, bits);
+                for (uint32_t sh : support[c]) {   // sum += X^sh A_c
+                    for (uint32_t j = 0; j < N - sh; j++) sum[j + sh] += a[j];
+                    for (uint32_t j = N - sh; j < N; j++) sum[j + sh - N] -= a[j];
+                }
+            }
+            for (uint32_t j = 0; j < fill; j++)
+                msgs[g * N + j] = compact_decode(compact_field(sample, k * N + j, bits), sum[j], bits, two_p);
+        }
+    });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -29,7 +29,8 @@ enum Domain : uint64_t {
     DOM_MASK_KEY = 9,                                   // under the context's key: block 0 of stream 0 -> the public mask key
     DOM_SBSK_MASK = 10, DOM_SBSK_NOISE = 11,            // seeded bootstrapping key: mask (mask key), noise (context key)
     DOM_SKSK_MASK = 12, DOM_SKSK_NOISE = 13,            // seeded key-switching key
-    DOM_SENC_MASK = 14, DOM_SENC_NOISE = 15             // seeded encryption
+    DOM_SENC_MASK = 14, DOM_SENC_NOISE = 15,            // seeded encryption
+    DOM_PACK_MASK = 16, DOM_PACK_NOISE = 17             // packing key (packed outputs): mask (mask key), noise (context key)
 };
 FBS_HD uint64_t stream_id(Domain d, uint64_t sub) { return ((uint64_t)d << 56) | (sub & 0x00FFFFFFFFFFFFFFull); }
 // the 256-bit ChaCha key of a context: a 64-bit seed followed by a fixed tail (fbs_ctx_create: reproducible, test-grade), or
@@ -54,6 +55,7 @@ struct Tune {
     int64_t br_cu_lean = 1;         // 1: between one and two per CU, its 128-register variant (two workgroups per CU); 2: always; 0: never
     int64_t br_k2_shape = 0;        // k = 2: 0 by launch size; 3 always three waves per bootstrap; 12 always the twelve-wave latency shape
     int64_t br_glwe_fpw = 0;        // k_blind_rotate_glwe: bootstraps per workgroup -- 0 by launch size; 1, 2; anything larger = the throughput shape
+    int64_t pack_slices = 0;        // packed outputs: slices the i-sum of one packed sample is cut into -- 0 by launch size (fbs_pack.hip)
 };
 
 // ---- launch descriptors ------------------------------------------------------------------------
@@ -190,6 +192,20 @@ struct fbs_ctx {
     uint32_t *d_sk_lwe_bits = nullptr;   // [ceil(n / 32)] the small LWE key as packed bits (decryption of compact outputs)
     uint64_t *d_compact = nullptr;   // scratch: packed compact ciphertexts of fbs_eval_seeded_compact's output groups
     size_t compact_capacity = 0;     // in words (also the staging of compact inputs, fbs_eval_sources)
+    // Packed outputs (fbs_pack.hip): the packing key's parameters and bodies [n][t_p][N] (the masks come from mask_key), the key
+    // in the transform domain [n][t_p][k+1][N] (centred doubles, x N^-1, key_word order), and the packing scratch: the rounded
+    // mask fields and the raw body fields of a pass transposed to [n+1][samples N], partial accumulators [samples][slices][k+1][N]
+    bool have_pack = false;
+    uint32_t pack_t = 0, pack_gamma = 0;
+    std::vector<uint64_t> pack_bodies;
+    double *d_pack_key = nullptr;
+    size_t pack_key_capacity = 0;    // in words
+    uint32_t *d_pack_fields = nullptr;
+    size_t pack_fields_capacity = 0; // in words
+    double *d_pack_acc = nullptr;
+    size_t pack_acc_capacity = 0;    // in words
+    uint64_t *d_packed = nullptr;    // staging of fbs_state_fetch_packed's words
+    size_t packed_capacity = 0;      // in words
     fbs_tvset *tv_identity = nullptr;   // the identity table [0, 1, .., p - 1], made on first use: what refreshes a compact input
     int64_t *d_io_msgs = nullptr;    // scratch: messages of fbs_eval_messages, [n_inputs + n_outputs][chunk]
     size_t io_msgs_capacity = 0;     // in words
@@ -302,6 +318,13 @@ void host_expand_seeded_keys(const fbs_ctx *ctx, const RandKey &mask_key, const 
 void host_encrypt_seeded(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *bodies);
 // bodies[count] -> cts [count][D+1]: the mask of stream nonce0 + i under ctx->mask_key, then the body
 void host_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count, uint64_t nonce0, uint64_t *cts);
+// Packed outputs (fbs_pack.hpp).  Row r = i t_p + v of the packing key: masks A_c = fold(words c N .. of stream (DOM_PACK_MASK, r))
+// under the mask key, body = e + sum_c A_c S_c + sk_lwe[i] h_v at X^0, e on stream (DOM_PACK_NOISE, r) under the context's key.
+// host_packing_keygen -> bodies [n][t_p][N]; host_expand_packing_key: (mask key, bodies) -> the whole key [n][t_p][k+1][N]
+void host_packing_keygen(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies);
+void host_expand_packing_key(const fbs_ctx *ctx, const RandKey &mask_key, uint32_t t_p, const uint64_t *bodies, std::vector<uint64_t> &full);
+// packed words of `count` outputs at width `bits` -> msgs[count] under sk_glwe
+void host_decrypt_packed(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs);
 int host_build_tv(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint64_t *tv, uint64_t *post_add);
 // D_F with TV_F = TV_0 * D_F as (position, value) pairs of its non-zero coefficients, at most p + 1 of them (`pos`, `val`
 // sized for that); *norm2 = |D_F|^2, *g_norm2 = |G_F|^2 (TV_F = delta_half G_F), *abs_sum = sum |d|.  Errors as host_build_tv.
@@ -361,6 +384,14 @@ int dev_decrypt_compact(const fbs_ctx *ctx, const uint64_t *d_words, size_t coun
 // and back: packed words [count][W] at width `bits` -> the fields at log2(2N) bits, d_ms [count][n + 1] as the blind rotation reads them
 // (re-rounded as the modulus switch rounds when bits > log2(2N))
 int dev_compact_unpack(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint32_t *d_ms, hipStream_t stream);
+
+// packed outputs (fbs_pack.hip).  dev_upload_packing_key: the whole key in the coefficient domain -> d_pack_key (transformed on
+// the device; blocks).  pack_slices_for: slices per sample of a launch of `samples` packed samples.  dev_pack: the switched
+// 31-bit fields d_ms [count][n + 1] of ciphertexts that start a packed sample -> packed words at width `bits`; uses d_pack_fields
+// ((n + 1) * samples * N words) and d_pack_acc (samples * slices * (k + 1) * N words), which the caller has sized
+int dev_upload_packing_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_p);
+uint32_t pack_slices_for(const fbs_ctx *ctx, size_t samples);
+int dev_pack(fbs_ctx *ctx, const uint32_t *d_ms, size_t count, uint32_t bits, uint64_t *d_words, hipStream_t stream);
 
 // resident state (fbs_state.hip): the links of `a` between state rows and wire slots, one launch each
 int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);

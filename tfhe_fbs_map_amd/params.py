@@ -146,6 +146,55 @@ def compact_output_bits(prm: Params, norm2: float = 1.0, out_norm2: float = 1.0)
     return 31
 
 
+# ---- packed outputs (include/fbs_exec.h, "packed outputs") -------------------------------------------------------------------
+def packed_output_variance(prm: Params, t_p: int, gamma_p: int, bits: int, out_norm2: float = 1.0) -> float:
+    """Phase variance of one output inside a packed GLWE sample at transport width `bits`, the sum of four terms: the compact
+    output at 31 bits (what the packing key switch starts from); the packing key's noise, n t_p N balanced digits of variance
+    (2^(2 gamma_p) + 2) / 12 against sigma_glwe; the rounding of the n mask fields to t_p gamma_p bits seen through a binary key;
+    and the transport rounding of the body and of the k N mask coefficients (through a binary key) to 2^bits, without mean
+    compensation."""
+    s_glwe = prm.sigma_glwe / float(MODULUS)
+    v_key = prm.n * t_p * prm.N * (2.0 ** (2 * gamma_p) + 2.0) / 12.0 * s_glwe ** 2
+    v_digit = (prm.n / 2.0) * 2.0 ** (-2 * t_p * gamma_p) / 12.0
+    v_transport = (1 + prm.k * prm.N / 2.0) / (12.0 * 2.0 ** (2 * bits))
+    return compact_output_variance(prm, 31, out_norm2) + v_key + v_digit + v_transport
+
+
+def packed_output_skew(prm: Params) -> float:
+    """`compact_output_skew` for a packed output: the k N + 1 transport fields its phase is made of, plus the n + 1 fields of the
+    31-bit stage, each off by at most (2^46 - q) / 2^46 of the torus."""
+    return (prm.k * prm.N + 1 + prm.n + 1) * float((1 << MODULUS_BITS) - MODULUS) / float(1 << MODULUS_BITS)
+
+
+def packed_output_margin(prm: Params, t_p: int, gamma_p: int, bits: int, out_norm2: float = 1.0) -> float:
+    """Standard deviations between a packed output's phase and the edge of its box, skew counted as `compact_output_margin` does"""
+    return (1.0 / (4.0 * prm.p_msg) - packed_output_skew(prm)) / math.sqrt(packed_output_variance(prm, t_p, gamma_p, bits, out_norm2))
+
+
+def packed_margin_needed(prm: Params, norm2: float = 1.0) -> float:
+    """`margin_sigmas(prm, norm2)` with the packed skew counted on its side too (as `compact_output_bits` does with its own)"""
+    return margin_sigmas(prm, norm2) * (1.0 - 4.0 * prm.p_msg * packed_output_skew(prm))
+
+
+def packing_choice(prm: Params, norm2: float = 1.0, out_norm2: float = 1.0):
+    """(t_p, gamma_p, bits) of the packing key and the transport width for a program: among the choices whose
+    `packed_output_margin` reaches `packed_margin_needed(prm, norm2)`, the smallest key -- the fewest levels t_p, then the widest
+    digit gamma_p (t_p gamma_p <= 31) -- and then the narrowest width.  When nothing reaches it: (t_p, gamma_p) of the largest
+    margin at 31 bits, the last resort `compact_output_bits` takes too."""
+    need = packed_margin_needed(prm, norm2) * (1.0 - 1e-12)
+    best = None
+    for t_p in range(1, 32):
+        for gamma_p in range(31 // t_p, 0, -1):
+            if packed_output_margin(prm, t_p, gamma_p, 31, out_norm2) < need:
+                if best is None or packed_output_margin(prm, t_p, gamma_p, 31, out_norm2) > 1.01 * packed_output_margin(prm, *best, out_norm2):
+                    best = (t_p, gamma_p, 31)
+                continue
+            for bits in range(prm.log_n_poly + 1, 32):
+                if packed_output_margin(prm, t_p, gamma_p, bits, out_norm2) >= need:
+                    return t_p, gamma_p, bits
+    return best
+
+
 # ---- chained evaluation (include/fbs_exec.h, "chained evaluation") -------------------------------------------------------------
 def refresh_input_variance(prm: Params, bits: int | None = None, out_norm2: float = 1.0) -> float:
     """Phase variance of what the refresh of a linked input rotates by.  A compact link (`bits` = its width w): the compact

@@ -53,7 +53,7 @@ import numpy as np
 
 from .fbs_exec_env import ExecConfig, min_fbs_size, table_fusion_factor, table_is_valid
 
-__all__ = ["ServerKey", "EncryptedInputs", "EncryptedOutputs", "CompactOutputs", "ResidentOutputs", "Client", "Server", "FORMAT_VERSION",
+__all__ = ["ServerKey", "EncryptedInputs", "EncryptedOutputs", "CompactOutputs", "PackedOutputs", "ResidentOutputs", "packed_words", "Client", "Server", "FORMAT_VERSION",
            "mask_key_fingerprint", "seeded_key_sizes", "compact_words", "output_noise_factor", "output_noise_factors",
            "plan_chain", "ChainLink", "client_choice"]
 
@@ -76,6 +76,16 @@ def seeded_key_sizes(prm):
 def compact_words(prm, bits):
     """W, the words of one compact ciphertext at width `bits`: fbs_compact_words without a GPU"""
     return ((prm.n + 1) * int(bits) + 63) // 64
+
+
+def packed_words(prm, count, bits):
+    """Words of `count` outputs packed at width `bits` (include/fbs_exec.h, "packed outputs"): fbs_packed_words without a GPU.  A
+    full sample is its (k + 1) N fields, a partly filled last one its k N mask fields and `count mod N` body fields; every sample
+    starts on a word boundary (k N bits is a multiple of 64)."""
+    N, bits = prm.N, int(bits)
+    full, rest = divmod(int(count), N)
+    mask_words = prm.k * N * bits // 64
+    return full * (mask_words + (N * bits + 63) // 64) + ((mask_words + (rest * bits + 63) // 64) if rest else 0)
 
 
 def output_noise_factor(low, p, fused=False):
@@ -144,6 +154,9 @@ class ServerKey:
     mask_key: bytes
     bsk_bodies: np.ndarray
     ksk_bodies: np.ndarray
+    packing_bodies: np.ndarray | None = None   # [n][t_p][N] bodies of the packing key (packed outputs); None: the key has none
+    packing_levels: int = 0                    # t_p
+    packing_base_bits: int = 0                 # gamma_p
 
     def __post_init__(self):
         self.mask_key = bytes(self.mask_key)
@@ -155,6 +168,16 @@ class ServerKey:
         for a, w, name in zip((self.bsk_bodies, self.ksk_bodies), want, ("bsk_bodies", "ksk_bodies")):
             if a.size != w:
                 raise ValueError(f"{name} has {a.size} words, the parameter set needs {w}")
+        if self.packing_bodies is None:
+            self.packing_levels = self.packing_base_bits = 0
+        else:
+            t, g = int(self.packing_levels), int(self.packing_base_bits)
+            self.packing_levels, self.packing_base_bits = t, g
+            self.packing_bodies = np.ascontiguousarray(self.packing_bodies, np.uint64).reshape(-1)
+            if t < 1 or g < 1 or t * g > 31:
+                raise ValueError(f"a packing key of {t} levels of {g} bits")
+            if self.packing_bodies.size != self.params.n * t * self.params.N:
+                raise ValueError(f"packing_bodies has {self.packing_bodies.size} words, the parameter set needs {self.params.n * t * self.params.N}")
 
     @property
     def fingerprint(self) -> bytes:
@@ -165,7 +188,14 @@ class ServerKey:
         np.savez(path, kind=np.array("server_key"), format_version=np.array(FORMAT_VERSION),
                  params=np.array([int(prm[f]) for f in _PARAM_FIELDS], np.int64), fuse_tables=np.array(bool(self.fuse_tables)),
                  mask_key=np.frombuffer(self.mask_key, np.uint8), fingerprint=np.frombuffer(self.fingerprint, np.uint8),
-                 bsk_bodies=self.bsk_bodies, ksk_bodies=self.ksk_bodies)
+                 bsk_bodies=self.bsk_bodies, ksk_bodies=self.ksk_bodies, **self._packing_fields())
+
+    def _packing_fields(self):
+        """the optional packing key of a saved server key (a key without one is written exactly as before)"""
+        if self.packing_bodies is None:
+            return {}
+        return dict(packing_bodies=self.packing_bodies, packing_levels=np.array(self.packing_levels, np.int64),
+                    packing_base_bits=np.array(self.packing_base_bits, np.int64))
 
     @classmethod
     def load(cls, path):
@@ -177,7 +207,13 @@ class ServerKey:
         prm = Params(**{f: int(v) for f, v in zip(_PARAM_FIELDS, vals)})
         if d["bsk_bodies"].dtype != np.uint64 or d["ksk_bodies"].dtype != np.uint64:
             raise ValueError("key bodies are uint64 words")
-        key = cls(prm, bool(d["fuse_tables"]), np.asarray(d["mask_key"], np.uint8).tobytes(), d["bsk_bodies"], d["ksk_bodies"])
+        packing = {}
+        if "packing_bodies" in d:
+            if d["packing_bodies"].dtype != np.uint64:
+                raise ValueError("key bodies are uint64 words")
+            packing = dict(packing_bodies=d["packing_bodies"], packing_levels=int(d["packing_levels"]),
+                           packing_base_bits=int(d["packing_base_bits"]))
+        key = cls(prm, bool(d["fuse_tables"]), np.asarray(d["mask_key"], np.uint8).tobytes(), d["bsk_bodies"], d["ksk_bodies"], **packing)
         if _fingerprint_of(d) != key.fingerprint:
             raise ValueError("the saved fingerprint is not the mask key's")
         return key
@@ -265,6 +301,38 @@ class CompactOutputs:
         return cls(names, T, bits, words, _fingerprint_of(d), _norm2_of(d, len(names)))
 
 
+@dataclass
+class PackedOutputs:
+    """Packed output ciphertexts of one evaluation (`Server.run_packed`): the n_outputs * T outputs, flattened [output][sample],
+    written N at a time into GLWE samples under the client's big key, rounded to `bits` bits a coefficient and bit-packed
+    (include/fbs_exec.h, "packed outputs"); `words` is the flat array `packed_words(params, n_outputs * T, bits)` long.  For the
+    client only: a packed result is no source of a chain."""
+    output_names: list
+    T: int
+    bits: int
+    words: np.ndarray
+    fingerprint: bytes
+    out_norm2: np.ndarray | None = None   # as EncryptedOutputs.out_norm2
+
+    def save(self, path):
+        np.savez(path, kind=np.array("packed_outputs"), format_version=np.array(FORMAT_VERSION),
+                 output_names=np.array(list(self.output_names), dtype=str), T=np.array(self.T, np.int64),
+                 bits=np.array(self.bits, np.int64), words=np.ascontiguousarray(self.words, np.uint64),
+                 fingerprint=np.frombuffer(self.fingerprint, np.uint8), **_norm2_fields(self))
+
+    @classmethod
+    def load(cls, path):
+        d = _load_npz(path, "packed_outputs")
+        names = [str(n) for n in np.asarray(d["output_names"]).reshape(-1)]
+        T, bits = int(d["T"]), int(d["bits"])
+        words = np.asarray(d["words"])
+        if not 1 <= bits <= 31 or T < 0:
+            raise ValueError(f"a packed width of {bits} bits, {T} samples")
+        if words.dtype != np.uint64 or words.ndim != 1:
+            raise ValueError(f"packed words of shape {words.shape} and type {words.dtype}")
+        return cls(names, T, bits, words, _fingerprint_of(d), _norm2_of(d, len(names)))
+
+
 class ResidentOutputs:
     """Full output ciphertexts of one evaluation that stayed on the server's GPU (`Server.run` / `Server.run_chain` with
     `resident=True`): row o of `state` (a `DeviceState`, [n_outputs][T][D+1]) is output o.  A source of `Server.run_chain` on the
@@ -275,16 +343,28 @@ class ResidentOutputs:
         self.out_norm2 = None if out_norm2 is None else np.asarray(out_norm2, np.float64).reshape(-1)
         self.state, self.server = state, server
         self.compact_bits = compact_bits   # the width fetch(compact=True) takes by default: the producer's `Server.compact_bits`
+        self.packed_bits = None            # the width fetch(packed=True) takes by default (`Server.packed_bits`)
 
     @property
     def closed(self):
         return self.state is None or bool(self.state.closed)
 
-    def fetch(self, compact=False, bits=None):
+    def fetch(self, compact=False, bits=None, packed=False):
         """-> `EncryptedOutputs`, or with compact=True `CompactOutputs` at `bits` (None: the width `Server.compact_bits` picks for
-        the program that computed them, or for their noise after a chain); both as `run` / `run_compact` return them."""
+        the program that computed them, or for their noise after a chain); both as `run` / `run_compact` return them.
+        packed=True: `PackedOutputs` at `bits` (None: the width `params.packing_choice` gave for them), packed on the GPU with the
+        server key's packing key; only the packed words cross the bus."""
         if self.closed:
             raise ValueError("the resident outputs are closed")
+        if packed:
+            if compact:
+                raise ValueError("packed or compact, not both")
+            if self.server is None or self.server.key.packing_bodies is None:
+                raise ValueError("the server key holds no packing key (Client(..., packing=True))")
+            bits = self.packed_bits if bits is None else int(bits)
+            if bits is None:
+                raise ValueError("no default packed width is recorded for these outputs: pass bits")
+            return PackedOutputs(list(self.output_names), self.T, int(bits), self.state.fetch_packed(int(bits)), self.fingerprint, self.out_norm2)
         if not compact:
             return EncryptedOutputs(list(self.output_names), self.T, self.state.fetch(), self.fingerprint, self.out_norm2)
         bits = self.compact_bits if bits is None else int(bits)
@@ -329,7 +409,10 @@ class Client:
     p any of them needs and the set `config.params_choice(p, max norm2)` over all of them; tables share rotations only when
     `config.fuse_tables is True`.  With programs=() the choice is `env`'s alone, as before."""
 
-    def __init__(self, env, config: ExecConfig | None = None, programs=()):
+    def __init__(self, env, config: ExecConfig | None = None, programs=(), packing=False):
+        """packing=True: the server key also carries a packing key (`Server.run_packed`, `PackedOutputs`), at the parameters
+        `params.packing_choice` gives for the noisiest output of env and of every program; False (default): keys and files are
+        what they were without it."""
         from ._native import Context
         self.env = env
         self.config = cfg = config or ExecConfig()
@@ -337,11 +420,23 @@ class Client:
         self.params, self.fuse_tables = client_choice(env, cfg, programs)
         self.ctx = Context(self.params, seed=cfg.key_seed(), device=cfg.device, keygen=False)
         self.ctx.keygen_seeded()
+        self.packing = None
+        if packing:
+            from .params import packing_choice
+            everything = [env] + [e for e in programs if e is not env]
+            p = self.params.p_msg
+            norm2 = min((e.fusion_stats(p) if self.fuse_tables else e.stats())["norm2_linprod"] for e in everything)
+            worst = max(output_noise_factor(e.lower(), p, self.fuse_tables) for e in everything)
+            self.packing = packing_choice(self.params, norm2, max(worst, 1.0))
+            self.ctx.packing_keygen(*self.packing[:2])
         self._server_key = None
 
     def server_key(self) -> ServerKey:
         if self._server_key is None:
-            self._server_key = ServerKey(self.params, self.fuse_tables, **self.ctx.export_seeded_keys())
+            packing = {}
+            if self.packing:
+                packing = {k: v for k, v in self.ctx.export_packing_key().items() if k.startswith("packing_")}
+            self._server_key = ServerKey(self.params, self.fuse_tables, **self.ctx.export_seeded_keys(), **packing)
         return self._server_key
 
     @property
@@ -361,14 +456,20 @@ class Client:
         return EncryptedInputs(list(names), T, first, bodies.reshape(len(names), T), self.fingerprint)
 
     def decrypt(self, outputs, env=None):
-        """EncryptedOutputs or CompactOutputs -> exactly what `LutExecEnv.eval` returns: {output name: np.ndarray of ints},
+        """EncryptedOutputs, CompactOutputs or PackedOutputs -> exactly what `LutExecEnv.eval` returns: {output name: np.ndarray of ints},
         constant outputs as python ints.  env: the program that computed them (None: the client's own; any program of a chain)."""
         low = self._low if env is None else env.lower()
         if outputs.fingerprint != self.fingerprint:
             raise ValueError("outputs were computed under another server key")
         if list(outputs.output_names) != list(low["out_names"]):
             raise ValueError("outputs belong to another program")
-        if isinstance(outputs, CompactOutputs):
+        if isinstance(outputs, PackedOutputs):
+            bits, count = int(outputs.bits), len(low["out_names"]) * int(outputs.T)
+            words = np.ascontiguousarray(outputs.words, np.uint64).reshape(-1)
+            if not self.params.log_n_poly + 1 <= bits <= 31 or words.size != packed_words(self.params, count, bits):
+                raise ValueError(f"{words.size} packed words at {bits} bits do not fit this parameter set and {count} outputs")
+            out = (self.ctx.decrypt_packed(words, count, bits) if count else np.zeros(0, np.int64)).reshape(len(low["out_names"]), int(outputs.T))
+        elif isinstance(outputs, CompactOutputs):
             bits, words = int(outputs.bits), outputs.words
             if not self.params.log_n_poly + 1 <= bits <= 31 or words.shape[-1] != compact_words(self.params, bits):
                 raise ValueError(f"compact ciphertexts of {words.shape[-1]} words at {bits} bits do not fit this parameter set")
@@ -390,6 +491,8 @@ class Server:
         self.key = server_key
         self.ctx = Context.evaluation_only(server_key.params, server_key.mask_key, server_key.bsk_bodies, server_key.ksk_bodies,
                                            device=device)
+        if server_key.packing_bodies is not None:
+            self.ctx.import_packing_key(server_key.packing_levels, server_key.packing_base_bits, server_key.packing_bodies)
         self.max_programs = max_programs
         self._programs = {}
 
@@ -446,6 +549,32 @@ class Server:
         words = prog.eval_seeded_compact(inputs.bodies, inputs.T, inputs.nonce0, bits)
         return CompactOutputs(list(low["out_names"]), inputs.T, bits, words, self.key.fingerprint, self._out_norm2(low))
 
+    def packed_bits(self, env, out_norm2=None):
+        """The transport width `run_packed` uses by default: the narrowest at which `params.packed_output_margin`, at the server
+        key's packing parameters and the outputs' worst noise factor, reaches `params.packed_margin_needed` for the program's
+        norm2 (31 when none does)."""
+        from .params import packed_margin_needed, packed_output_margin
+        prm, low = self.key.params, env.lower()
+        if self.key.packing_bodies is None:
+            raise ValueError("the server key holds no packing key (Client(..., packing=True))")
+        norm2 = (env.fusion_stats(prm.p_msg) if self.key.fuse_tables else env.stats())["norm2_linprod"]
+        worst = output_noise_factor(low, prm.p_msg, self.key.fuse_tables) if out_norm2 is None else float(np.asarray(out_norm2).max(initial=0.0))
+        need = packed_margin_needed(prm, norm2) * (1.0 - 1e-12)
+        for bits in range(prm.log_n_poly + 1, 32):
+            if packed_output_margin(prm, self.key.packing_levels, self.key.packing_base_bits, bits, worst) >= need:
+                return bits
+        return 31
+
+    def run_packed(self, env, inputs: EncryptedInputs, bits=None) -> PackedOutputs:
+        """`run` with packed outputs: evaluated resident (the outputs never leave the GPU as ciphertexts), then packed into GLWE
+        samples under the client's key (fbs_state_fetch_packed); bits=None: `packed_bits(env)`.  A constant output travels as the
+        packing of its trivial ciphertext."""
+        if self.key.packing_bodies is None:
+            raise ValueError("the server key holds no packing key (Client(..., packing=True))")
+        bits = self.packed_bits(env) if bits is None else int(bits)
+        with self.run(env, inputs, resident=True) as res:
+            return res.fetch(packed=True, bits=bits)
+
     def _out_norm2(self, low, input_noise=None):
         return np.asarray(output_noise_factors(low, self.key.params.p_msg, self.key.fuse_tables, input_noise), np.float64)
 
@@ -462,7 +591,10 @@ class Server:
         except Exception:
             state.close()
             raise
-        return ResidentOutputs(list(low["out_names"]), T, self.key.fingerprint, out_norm2, state, self, bits)
+        res = ResidentOutputs(list(low["out_names"]), T, self.key.fingerprint, out_norm2, state, self, bits)
+        if self.key.packing_bodies is not None:
+            res.packed_bits = self.packed_bits(env, out_norm2)
+        return res
 
     def restore(self, outputs: EncryptedOutputs, compact_bits=None) -> "ResidentOutputs":
         """An `EncryptedOutputs` (a `ResidentOutputs.fetch()`, possibly saved and loaded) back into device memory
@@ -569,6 +701,9 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
         raise ValueError("no sources for a program with inputs")
     T = None
     for k, src in enumerate(sources):
+        if isinstance(src, PackedOutputs):
+            raise ValueError("source %d is a PackedOutputs: a packed result is under the client's big key in GLWE form, for the client "
+                             "only; link the EncryptedOutputs, CompactOutputs or ResidentOutputs of that evaluation instead" % k)
         if not isinstance(src, _SOURCE_TYPES):
             raise TypeError("source %d is a %s, not EncryptedInputs, EncryptedOutputs, CompactOutputs or ResidentOutputs" % (k, type(src).__name__))
         if isinstance(src, ResidentOutputs) and src.closed:
