@@ -504,3 +504,258 @@ def key_product_sums(name, x):
         key = [rng.choice((HALF, -HALF, rng.randrange(-HALF, HALF + 1))) for _ in range(N)]
         own = [exact(int(o) + int(fp_mulmod(v, float(k)))) for o, v, k in zip(own, x, key)]
     return own
+
+
+# ==== the key switch on worst-case keys and digits (tests/test_keyswitch_reference.py, tests/test_gpu_keyswitch.py) =====================
+# A key-switching-key row is (mask[0..n), body) with body = sum_i s_i mask_i + sk_glwe[j] h_v + e: the MASK can be anything, so a key
+# whose mask columns hold the words that drive each kernel's accumulators to their stated bounds is a valid key for fbs_import_keys.
+# Everything below is Python integers (numpy arrays of dtype object where an array is handy): no fixed-width word anywhere.
+QBITS = 46
+# name -> the parameter set: the smallest at which each bound of the key-switch kernels is tight (l, beta, p only make it a set a
+# blind-rotation kernel is built for)
+KS_SETS = {
+    "g9": dict(n=20, log_n_poly=8, k=1, l_bsk=2, beta_bsk=10, t_ksk=1, gamma_ksk=9),       # 9-bit digits: no int8 GEMM
+    "g8_t1": dict(n=20, log_n_poly=8, k=1, l_bsk=2, beta_bsk=10, t_ksk=1, gamma_ksk=8),    # digit -128 in the GEMM; FP64 folds every word
+    "g8_t2": dict(n=20, log_n_poly=8, k=1, l_bsk=2, beta_bsk=10, t_ksk=2, gamma_ksk=8),    # 63.0 bits; no room for FP64
+    "n4096": dict(n=20, log_n_poly=12, k=1, l_bsk=2, beta_bsk=10, t_ksk=7, gamma_ksk=3),   # 63.8 of 63.9 bits; FP64 folds every 9 words
+    "k3": dict(n=77, log_n_poly=9, k=3, l_bsk=2, beta_bsk=8, t_ksk=4, gamma_ksk=5),        # D = 1536, a second 64-column block
+    "shipped": dict(n=130, log_n_poly=10, k=1, l_bsk=3, beta_bsk=7, t_ksk=8, gamma_ksk=2), # the everyday gadget, three 64-column blocks
+}
+KS_SIGMA = 1 << 8
+
+
+def ks_set(name):
+    """the full parameter dict of a KS_SETS entry (what Oracle and Params take)"""
+    return dict(KS_SETS[name], p_msg=7, sigma_lwe=KS_SIGMA, sigma_glwe=4, bsk_group=1)
+
+
+def ks_shape(prm):
+    """-> (n, D, t, gamma) of a parameter dict"""
+    return prm["n"], prm["k"] << prm["log_n_poly"], prm["t_ksk"], prm["gamma_ksk"]
+
+
+def _limb_word(low_limb):
+    """the word whose balanced base-256 limbs are `low_limb` in planes 0..4 and, in plane 5, the limb of the OTHER sign that is
+    largest in magnitude while |x| < q/2 (so that the word is the centred value the limb kernel decomposes back to these limbs)"""
+    low = sum(low_limb << (8 * b) for b in range(5))
+    top = next(m for m in range(127, 0, -1) if abs(low + (-m if low_limb > 0 else m) * 256 ** 5) <= HALF)
+    return (low + (-top if low_limb > 0 else top) * 256 ** 5) % Q
+
+
+def balanced_limbs(word):
+    """the six balanced base-256 limbs of the centred value of a canonical word (k_ks_limbs)"""
+    x, out = centred(word), []
+    for _ in range(6):
+        limb = ((x + 128) & 255) - 128
+        out.append(limb)
+        x = (x - limb) >> 8
+    assert x == 0
+    return out
+
+
+KS_WORDS = {"qm1": Q - 1, "half+": (Q - 1) // 2, "half-": (Q + 1) // 2, "limb-": _limb_word(-128), "limb+": _limb_word(127)}
+KS_MIRROR = {"qm1": "qm1", "half+": "half-", "half-": "half+", "limb-": "limb+", "limb+": "limb-", "alt": "alt'", "rand": "rand'"}
+
+
+def ks_column_plan(n, mirrored=False):
+    """pattern name per mask column.  Every pattern within the first 8-column block; columns 8 and 16 (the second and third 8-column
+    blocks: grid indices 8 and 1 of the XCD-paired column order of k_keyswitch_lanes / _fp) on the FP64 worst cases; column n - 1 and,
+    where the key has them, columns 63 and 64 (the last of a 64-column block of the GEMM and the first of the next) on stress patterns
+    too.  mirrored: the second key -- every pattern swapped for the one of the other sign."""
+    cycle = ("qm1", "half+", "half-", "limb-", "limb+", "alt", "rand")
+    plan = [cycle[i % 7] for i in range(n)]
+    plan[n - 1] = "half+"
+    if n > 64:
+        plan[63], plan[64] = "limb-", "half-"
+    assert plan[0] == "qm1" and plan[8] == "half+" and plan[16] == "half-"
+    return [KS_MIRROR[p] for p in plan] if mirrored else plan
+
+
+def ks_listed_columns(n):
+    """the columns the issue names: 0, n - 1, one in each of the next two 8-column blocks, 63 and 64 where they exist"""
+    return [0, n - 1, 8, 16] + ([63, 64] if n > 64 else [])
+
+
+def ks_gadget(prm):
+    """h_v = round(q / 2^(gamma (v + 1)))"""
+    _, _, t, gamma = ks_shape(prm)
+    return [(Q + (1 << (gamma * (v + 1) - 1))) >> (gamma * (v + 1)) for v in range(t)]
+
+
+def ks_digits(word, t, gamma):
+    """balanced digits (most significant first) in [-B/2, B/2), carries propagated, of abar = round(w 2^(t gamma) / 2^46) mod 2^(t gamma)"""
+    tg, B = t * gamma, 1 << gamma
+    abar = (((word << tg) + (1 << (QBITS - 1))) >> QBITS) % (1 << tg)
+    digs = [0] * t
+    for v in range(t - 1, -1, -1):
+        d = abar % B
+        abar //= B
+        if d >= B // 2:
+            d -= B
+            abar += 1
+        digs[v] = d
+    return digs
+
+
+def ks_word_for_digits(digs, gamma):
+    """a canonical word that ks_digits maps to `digs` (most significant first): w = abar << (46 - t gamma).  Where that is not
+    below q (only patterns whose top bits are all ones, from t gamma = 28 on) the nearest pattern below that has a preimage is taken;
+    none of the rows below needs it, the assertion in planted_rows says so."""
+    t = len(digs)
+    tg = t * gamma
+    abar = sum(d << (gamma * (t - 1 - v)) for v, d in enumerate(digs)) % (1 << tg)
+    while (abar << (QBITS - tg)) >= Q:
+        abar -= 1
+    return abar << (QBITS - tg)
+
+
+def ks_body(mask_row, j, v, r, sk_lwe, sk_glwe, h):
+    """body of key row r = (j, v): sum_i s_i mask_i + sk_glwe[j] h_v + e, e deterministic with |e| <= sigma_lwe"""
+    e = (r * 2654435761 + 12345) % (2 * KS_SIGMA + 1) - KS_SIGMA
+    return (sum(int(m) for m, s in zip(mask_row, sk_lwe) if s) + (h[v] if sk_glwe[j] else 0) + e) % Q
+
+
+def ks_switch(rows, ksk, prm):
+    """THE DEFINITION on Python integers: rows [R][D + 1], ksk [D t][n + 1] (object) -> [R][n + 1] (object),
+    out = (0, .., 0, body) - sum_(j, v) digit_v(a_j) K[(j, v)] mod q"""
+    n, D, t, gamma = ks_shape(prm)
+    digs = np.array([[d for w in row[:D] for d in ks_digits(int(w), t, gamma)] for row in rows], dtype=object)
+    out = -digs.dot(ksk)
+    out[:, n] += np.array([int(row[D]) for row in rows], dtype=object)
+    return out % Q
+
+
+def planted_keys(keys, prm, mirrored=False):
+    """keys: dict(sk_lwe, sk_glwe, bsk, ksk) of a normally keyed context or oracle (export_keys / keys).  -> (the same dict with the
+    key-switching key's masks planted by ks_column_plan and every body recomputed, tuned), tuned = [(row pattern 0 | 1, column, key
+    row, target low bits)]: in each of eight-plus columns per stress row one key word is moved so that the switched word of that
+    row in that column ends in 0x4000 (rounds up at 31 bits, one less rounds down) or 0x3FFF (rounds down, one more rounds up).
+    Stress rows 0 and 1 both have uniform digits, so one column cannot be tuned for both (the two conditions on it are
+    proportional): the listed columns are dealt to the two rows alternately, and the mirrored key deals them the other way round."""
+    n, D, t, gamma = ks_shape(prm)
+    rows = D * t
+    sk_lwe, sk_glwe = [int(x) for x in keys["sk_lwe"]], [int(x) for x in keys["sk_glwe"]]
+    h = ks_gadget(prm)
+    rng = random.Random("planted key %d %d %d %d %d" % (n, D, t, gamma, mirrored))
+    ksk = np.empty((rows, n + 1), dtype=object)
+    for i, pat in enumerate(ks_column_plan(n, mirrored)):
+        if pat in KS_WORDS:
+            ksk[:, i] = KS_WORDS[pat]
+        elif pat.startswith("alt"):                                   # the FP64 worst case with the sign alternating by row parity
+            a, b = ("half+", "half-") if pat == "alt" else ("half-", "half+")
+            ksk[0::2, i], ksk[1::2, i] = KS_WORDS[a], KS_WORDS[b]
+        else:
+            ksk[:, i] = [rng.randrange(Q) for _ in range(rows)]
+    # the tuned words
+    B = 1 << gamma
+    listed = ks_listed_columns(n)
+    others = [i for i in range(n) if i not in listed]
+    cols = listed + others[:max(0, 16 - len(listed))]                 # sixteen columns (all of the listed ones), eight per stress row
+    if mirrored:
+        cols = cols[1:] + cols[:1]
+    tuned = []
+    for idx, col in enumerate(cols):
+        which = idx & 1                                               # stress row 0: every digit -B/2; 1: every digit B/2 - 1
+        d0 = -(B // 2) if which == 0 else B // 2 - 1
+        r = (-d0 * sum(int(x) for x in ksk[:, col])) % Q              # the switched word of that row in a mask column
+        low = 0x4000 if (idx >> 1) & 1 == 0 else 0x3FFF
+        target = (r & ~0x7FFF) | low
+        kr = ((idx % 8) * (D // 8) + 5 * idx + 1) % D * t + idx % t   # one key row in every eighth of the mask words, every level
+        ksk[kr, col] = (int(ksk[kr, col]) + (r - target) * pow(d0, Q - 2, Q)) % Q
+        tuned.append((which, col, kr, low))
+    for r in range(rows):
+        ksk[r, n] = ks_body(ksk[r, :n], r // t, r % t, r, sk_lwe, sk_glwe, h)
+    out = dict(keys)
+    out["ksk"] = np.array(ksk.reshape(-1), dtype=np.uint64)           # (the transport format of import_keys / set_keys)
+    return out, tuned
+
+
+def planted_rows(prm, count, honest, seed=1):
+    """[count][D + 1] canonical words, the six row patterns in turn (row i has pattern i % 6) with bodies 0, q - 1 and random in turn
+    ((i + i // 6) % 3: every pattern meets every body within eighteen rows): 0 every balanced digit -B/2; 1 every digit B/2 - 1; 2 those two alternating by word; 3 words 0 and q - 1
+    alternating (q - 1 rounds up past the top digit: the carry is dropped); 4 uniform random; 5 the next row of `honest` (encryptions
+    under the context's key, body and all)"""
+    n, D, t, gamma = ks_shape(prm)
+    B = 1 << gamma
+    lo, hi = ks_word_for_digits([-(B // 2)] * t, gamma), ks_word_for_digits([B // 2 - 1] * t, gamma)
+    assert ks_digits(lo, t, gamma) == [-(B // 2)] * t and ks_digits(hi, t, gamma) == [B // 2 - 1] * t   # both have a preimage
+    assert ks_digits(Q - 1, t, gamma) == [0] * t and ((Q - 1) >> (QBITS - 1 - t * gamma)) + 1 == 2 << (t * gamma)   # the carry
+    rng = random.Random("planted rows %d %d" % (D, seed))
+    out = np.zeros((count, D + 1), dtype=np.uint64)
+    for i in range(count):
+        pat = i % 6
+        if pat == 5:
+            out[i] = honest[(i // 6) % len(honest)]
+            continue
+        mask = {0: [lo] * D, 1: [hi] * D, 2: [lo, hi] * (D // 2), 3: [0, Q - 1] * (D // 2)}.get(pat) or [rng.randrange(Q) for _ in range(D)]
+        out[i, :D] = mask
+        out[i, D] = (0, Q - 1, rng.randrange(Q))[(i + i // 6) % 3]
+    return out
+
+
+# ---- what the planted inputs make each kernel family hold, against the bound its code states ----------------------------------
+def ks_fp_words_per_fold(prm):
+    """launch_keyswitch's formula; 0: the FP64 kernel is refused (select_keyswitch)"""
+    _, _, t, gamma = ks_shape(prm)
+    return min(1024, ((1 << 53) - (1 << 45)) // (t << (44 + gamma)))
+
+
+def ks_gemm_admitted(prm):
+    """ks_gemm_exact: int8 digits and int32 sums"""
+    _, D, t, gamma = ks_shape(prm)
+    return gamma <= 8 and (D * t) << (gamma + 6) < 1 << 31
+
+
+def ks_stated_bounds(prm):
+    """family -> the bound its code states, evaluated at the set (None: the family never runs there)"""
+    _, D, t, gamma = ks_shape(prm)
+    wpf = ks_fp_words_per_fold(prm)
+    return {"gemm_int32": (D * t) << (gamma - 1 + 7) if ks_gemm_admitted(prm) else None,      # 2^(gamma-1) 2^7 kN t  (< 2^31)
+            "fp64": (1 << 45) + wpf * (t << (44 + gamma)) if wpf else None,                    # 2^45 + words t 2^(44+gamma)  (<= 2^53)
+            "u64_sum": (D * t) << (46 + gamma),                                                # 2^(46+gamma) t D  (<= 2^63.9)
+            "lanes_hi": (D * t) << (14 + gamma)}                                               # its high part  (<= 2^31.9)
+
+
+def ks_reached(prm, ksk, rows):
+    """family -> the largest magnitude that family's accumulators hold on these inputs.  ksk [D t][n + 1], rows [R][D + 1].
+    gemm_int32: running sums over kappa = v D + j of digit x limb per plane; fp64: per wave of k_keyswitch_fp<8,2,8> (an eighth of the
+    mask words each), the running sum of digit x centred word from a centred start, folded every words_per_fold words; u64_sum: the whole
+    sum of field x word (k_keyswitch; the lanes kernels after their waves met); lanes_hi: the whole sum of field x (word >> 32), and
+    lanes_hi_wave: the fullest 32-bit register of one wave, which sums 1 / WAVES of the mask words (an eighth in <8,2,8>, a quarter in
+    <8,1,4>), times WAVES -- its fill against its equal share of the stated bound."""
+    n, D, t, gamma = ks_shape(prm)
+    B = 1 << gamma
+    K = np.array(ksk, dtype=object).reshape(D, t, n + 1)
+    Kc = np.vectorize(centred, otypes=[object])(K)
+    digs = [np.array([ks_digits(int(w), t, gamma) for w in row[:D]], dtype=object) for row in rows]      # [D][t] each
+    reached = dict.fromkeys(("gemm_int32", "fp64", "u64_sum", "lanes_hi", "lanes_hi_wave"), 0)
+    x, planes = Kc.astype(np.int64), []                               # (what k_ks_limbs does, on machine words as it does)
+    for _ in range(6):
+        planes.append(((x + 128) & 255) - 128)
+        x = (x - planes[-1]) >> 8
+    limbs = np.stack(planes, axis=-1)                                                                      # [D][t][n + 1][6]
+    wpf = ks_fp_words_per_fold(prm)
+    for d in digs:
+        if ks_gemm_admitted(prm):
+            terms = d.astype(np.int64).T[:, :, None, None] * limbs.transpose(1, 0, 2, 3)                  # [t][D][n + 1][6], kappa order
+            run = np.cumsum(terms.reshape(D * t, n + 1, 6), axis=0)
+            reached["gemm_int32"] = max(reached["gemm_int32"], int(np.abs(run).max()))
+        if wpf:
+            slice_len = -(-D // 8)
+            for wave in range(8):
+                acc = np.zeros(n + 1, dtype=object)
+                for at, j in enumerate(range(wave * slice_len, min(D, (wave + 1) * slice_len))):
+                    for v in range(t):
+                        acc = acc + d[j, v] * Kc[j, v]
+                        reached["fp64"] = max(reached["fp64"], max(abs(x) for x in acc))
+                    if (at + 1) % wpf == 0:
+                        acc = np.array([centred(x) for x in acc], dtype=object)
+        u = d + B // 2                                                                                     # the fields the integer kernels see
+        reached["u64_sum"] = max(reached["u64_sum"], max((u[:, :, None] * K).sum(axis=(0, 1))))
+        hi = u[:, :, None] * (K >> 32)
+        reached["lanes_hi"] = max(reached["lanes_hi"], max(hi.sum(axis=(0, 1))))
+        for waves in (4, 8):
+            slice_len = -(-D // waves)
+            share = max(max(hi[w * slice_len:(w + 1) * slice_len].sum(axis=(0, 1))) for w in range(waves))
+            reached["lanes_hi_wave"] = max(reached["lanes_hi_wave"], share * waves)                        # as a fraction of the whole bound
+    return reached

@@ -225,6 +225,15 @@ BOUNDARIES = [
         1: 'k_keyswitch<8>', 31: 'k_keyswitch<8>', 32: 'k_keyswitch_lanes<8,1,4>', 64: 'k_keyswitch_lanes<8,1,4>',
         65: 'k_keyswitch_lanes<8,2,8>', 256: 'k_keyswitch_lanes<8,2,8>', 2108: 'k_keyswitch_lanes<8,2,8>',
     }),
+    # 9-bit key-switch digits do not fit the GEMM's int8 operand (ks_gemm_exact), whatever the int32 sums allow; FP64 has no room either
+    ('gamma=9 ks', '12 8 1 2 10 1 9 7 1', '', 'ks', {
+        1: 'k_keyswitch<8>', 31: 'k_keyswitch<8>', 32: 'k_keyswitch_lanes<8,1,4>', 64: 'k_keyswitch_lanes<8,1,4>',
+        65: 'k_keyswitch_lanes<8,2,8>', 256: 'k_keyswitch_lanes<8,2,8>',
+    }),
+    ('gamma=8 ks', '12 8 1 2 10 1 8 7 1', '', 'ks', {
+        1: 'k_ks_gemm<2,2> (int8 MFMA)', 31: 'k_ks_gemm<2,2> (int8 MFMA)', 32: 'k_ks_gemm<2,2> (int8 MFMA)',
+        64: 'k_ks_gemm<2,2> (int8 MFMA)', 65: 'k_ks_gemm<2,2> (int8 MFMA)', 256: 'k_ks_gemm<2,2> (int8 MFMA)',
+    }),
 ]
 
 

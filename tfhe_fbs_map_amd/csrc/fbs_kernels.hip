@@ -381,9 +381,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_keyswitch_fp(KsArgs a, const dou
 // is a [ciphertexts] x [kN t] by [kN t] x [n + 1] product.  The balanced digits are tiny (|d| <= 2^(gamma-1)); a centred key
 // word (|K| < 2^45) is cut into SIX balanced base-256 limbs, K = sum_b limb_b 256^b with limb_b in [-128, 128), so that
 //     C[f][b][col] = sum_kappa digit[f][kappa] * limb_b[kappa][col]
-// is an int8 x int8 -> int32 GEMM with N = 6 (n + 1) columns, EXACT (|C| <= 2^(gamma-1) 2^7 kN t < 2^31, checked by the
-// launcher), and out = body - sum_b C_b 256^b mod q is recombined by the finishing kernel, which also does the modulus
-// switch.  Same integers as the other key-switch kernels, so the same ciphertexts.  Per 1024 bootstraps at P1024 this is
+// is an int8 x int8 -> int32 GEMM with N = 6 (n + 1) columns, EXACT under two conditions that ks_gemm_exact checks for the
+// launcher: the digits fit the int8 operand (gamma <= 8: a 9-bit digit in [-256, 256) would be cut to its low byte by
+// k_ks_digits) and the sums fit the int32 accumulator (|C| <= 2^(gamma-1) 2^7 kN t < 2^31).  out = body - sum_b C_b 256^b
+// mod q is recombined by the finishing kernel, which also does the modulus switch.  Same integers as the other key-switch kernels, so the same ciphertexts.  Per 1024 bootstraps at P1024 this is
 // 6.4e10 int8 multiply-adds x 2 -- 13 us at the dense int8 rate -- where the FP64 form spends 8.3e7 wave-FMAs on the vector
 // pipe (0.47 ms measured); the key shrinks from 8 to 6 bytes per word.
 //
@@ -665,6 +666,7 @@ int dev_keyswitch_gemm_setup(fbs_ctx *ctx) {
     const size_t bytes = (size_t)g.ksteps * 32 * 6 * g.cols_pad;
     if (ctx->d_ks_b) (void)hipFree(ctx->d_ks_b);
     ctx->d_ks_b = nullptr;
+    if (!ks_gemm_exact(ctx)) return FBS_OK;   // the selection never picks the GEMM at this set: no fragments, no scratch (dev_keyswitch_reserve)
     FBS_HIP(ctx, hipMalloc(&ctx->d_ks_b, bytes));
     const size_t threads = (size_t)g.D * g.t * g.cols_pad;
     hipLaunchKernelGGL(k_ks_limbs, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_ksk, ctx->ksk_stride, g,

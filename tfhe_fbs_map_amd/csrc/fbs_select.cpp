@@ -163,7 +163,9 @@ std::vector<Launch> select_blind_rotate(const fbs_ctx *ctx, size_t count) {
 }
 
 bool ks_gemm_exact(const fbs_ctx *ctx) {
-    return std::ldexp((double)ctx->D * ctx->p.t_ksk, (int)ctx->p.gamma_ksk + 6) < 2147483648.0;
+    // the operands: balanced digits in [-2^(gamma-1), 2^(gamma-1)) are stored as int8 (k_ks_digits), which holds them up to gamma = 8;
+    // the sums: |digit| * |limb| * kN t <= 2^(gamma-1) 2^7 kN t in an int32
+    return ctx->p.gamma_ksk <= 8 && std::ldexp((double)ctx->D * ctx->p.t_ksk, (int)ctx->p.gamma_ksk + 6) < 2147483648.0;
 }
 
 std::vector<Launch> select_keyswitch(const fbs_ctx *ctx, size_t count) {

@@ -118,7 +118,8 @@ void kernel_catalog(std::vector<std::string> *out);
 bool reads_small_key(const Kernel &k);
 // does the context need that copy?  (key upload makes it exactly when this says so)
 bool small_key_needed(const fbs_ctx *ctx);
-// int8 GEMM key switch on the matrix cores: exact while 2^(gamma-1) * 2^7 * kN t stays below 2^31
+// int8 GEMM key switch on the matrix cores: exact while the balanced digits fit an int8 (gamma <= 8) and the int32 sums
+// 2^(gamma-1) * 2^7 * kN t stay below 2^31
 bool ks_gemm_exact(const fbs_ctx *ctx);
 // Parameter admission, in two parts.  The arithmetic limits: null, or why the set is refused.  host_ctx_init asks before it computes
 // anything from the gadget parameters (q / 2^(beta (lv + 1)), q / 2^(gamma (v + 1))); D = k N.
