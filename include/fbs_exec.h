@@ -356,7 +356,14 @@ int fbs_decrypt_compact_dev(const fbs_ctx *ctx, const uint64_t *d_words, size_t 
  * formula above with 2^w in place of 2^46 (sh = w - b; round the mask fields, eps = sum of their signed errors in 64 bits,
  * body' = (m_n - floor(eps / 2)) mod 2^w, round the body) -- and one blind rotation through the identity table [0, 1, .., p - 1]
  * writes a fresh big-key ciphertext of the same value (every value in [0, p); program inputs are bits).  It costs one bootstrap
- * per ciphertext and carries that bootstrap's noise, whatever the link's.  None of these entries needs a secret. */
+ * per ciphertext and carries that bootstrap's noise, whatever the link's.  None of these entries needs a secret.
+ *
+ * PLAINTEXT INPUTS.  A server brings data of its own (a table row, a round key, a counter) as cleartext messages: a source of kind
+ * FBS_SRC_PLAIN holds int64 messages in [0, 2p), the range fbs_encrypt accepts, and the ciphertext of message m is word for word
+ * the trivial ciphertext fbs_eval writes for a constant output m: D zero mask words, then m * Delta mod q, Delta = 2*round(q/4p).
+ * It is written on the device straight into the input's wire slots: 8 bytes a sample cross the bus, or nothing for a broadcast
+ * message.  A trivial ciphertext carries no noise and hides nothing: the messages are public.  The program still pays its
+ * bootstraps for such an input; nothing is folded. */
 /* d_words [count][W] at width `bits` -> the fields d_fields [count][n + 1] (uint32, < 2^log2(2N)), asynchronous on `stream` */
 int fbs_compact_fields_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint32_t *d_fields, void *stream);
 /* d_words [count][W] -> refreshed big-key ciphertexts d_cts [count][D+1], asynchronous on `stream`.  At bits = log2(2N) equal
@@ -367,19 +374,21 @@ int fbs_refresh_compact_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count,
 #define FBS_SRC_SEEDED 0u    /* the client's seeded inputs: data = [T] bodies of streams nonce0 + s */
 #define FBS_SRC_FULL 1u      /* full ciphertexts of an earlier evaluation: data = [T][D+1] */
 #define FBS_SRC_COMPACT 2u   /* compact ciphertexts of an earlier evaluation: data = [T][W] at width `bits` */
+#define FBS_SRC_PLAIN 3u     /* the server's cleartext messages: data = host int64 [T] (bits = 0) or one message for all T samples (bits = 1) */
 typedef struct fbs_input_src {
     uint32_t kind;        /* FBS_SRC_* */
-    uint32_t bits;        /* COMPACT: its width w */
-    uint32_t refresh;     /* FULL: 1 = bootstrap through the identity table before use (COMPACT: always; SEEDED: never) */
-    uint64_t nonce0;      /* SEEDED: sample s on stream nonce0 + s */
-    const uint64_t *data; /* host memory */
+    uint32_t bits;        /* COMPACT: its width w.  PLAIN: 0 = sample s takes data[s], 1 = broadcast, data[0] serves every sample */
+    uint32_t refresh;     /* FULL: 1 = bootstrap through the identity table before use (COMPACT: always; SEEDED: never; PLAIN: must be 0) */
+    uint64_t nonce0;      /* SEEDED: sample s on stream nonce0 + s (PLAIN: not read) */
+    const uint64_t *data; /* host memory (PLAIN: int64 messages behind this pointer) */
 } fbs_input_src;
-/* One evaluation whose input i comes from src[i], any mix of the three kinds.  out_bits = 0: full outputs out [n_outputs][T][D+1]
+/* One evaluation whose input i comes from src[i], any mix of the four kinds.  out_bits = 0: full outputs out [n_outputs][T][D+1]
  * (as fbs_eval_seeded); else compact outputs out [n_outputs][T][W] at that width (as fbs_eval_seeded_compact).  The same chunks
  * as fbs_eval; full inputs marked `refresh` go through the ordinary key switch and modulus switch, then the identity rotation.
  * With every source seeded at nonce0 + i T the outputs are word for word those of fbs_eval_seeded (out_bits = 0) and of
  * fbs_eval_seeded_compact (out_bits = w).  Refused with FBS_E_INVALID, nothing written: an unknown kind, null data, a compact
- * width outside [log2(2N), 31], streams past 2^56, T * words overflowing.  Repeated calls of one shape do not grow scratch.
+ * width outside [log2(2N), 31], streams past 2^56, T * words overflowing, a plaintext message outside [0, 2p) (every message is checked
+ * before anything is queued), a plaintext source with refresh != 0 or bits > 1.  Repeated calls of one shape do not grow scratch.
  * T = 0 does nothing.  Blocks until the outputs are back. */
 int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, size_t T, uint32_t out_bits, uint64_t *out);
 
@@ -408,8 +417,8 @@ typedef struct fbs_resident_src {
  * out_host and out_state is given.  out_host: as `out` of fbs_eval_sources, at out_bits.  out_state (then out_bits must be 0): a
  * state of n_outputs rows whose row o becomes output o for all T samples, a constant output as the trivial ciphertext fbs_eval
  * writes.  The same chunks as fbs_eval: chunk [s0, s0 + tc) reads samples s0 onwards of each state row and writes samples s0
- * onwards of out_state, one gather launch and one scatter launch per chunk.  With out_state and every input resident or seeded
- * the call queues its work on the context's stream and returns without waiting for it (the caller's arrays are read before it
+ * onwards of out_state, one gather launch and one scatter launch per chunk.  With out_state and every input resident, seeded
+ * or plaintext (FBS_SRC_PLAIN mixes with state rows like the other kinds) the call queues its work on the context's stream and returns without waiting for it (the caller's arrays are read before it
  * returns; a later call on the context, fbs_state_fetch included, is ordered behind it); otherwise it blocks as
  * fbs_eval_sources does.  Refused with FBS_E_INVALID, nothing written: what fbs_eval_sources refuses; a state of another
  * context; a row past the state's rows; a state whose T differs from the call's; an out_state with rows != n_outputs; an

@@ -10,9 +10,9 @@ from ._native import MODULUS, MODULUS_BITS, Context, FbsError, Params, Program, 
 from .fbs_exec_env import ExecConfig, FbsExecEnv, LutExecEnv, min_fbs_size, parse_fbs, parse_lbf, table_is_valid
 from .netlist import BitExecEnv, map_basic, parse_blif, parse_bristol
 from .params import P1024, P2048, bootstrap_cost, choose_params, margin_sigmas, params_for, security_bits, sigma_min
-from .split import Client, EncryptedInputs, EncryptedOutputs, Server, ServerKey
+from .split import Client, EncryptedInputs, EncryptedOutputs, PlainInputs, Server, ServerKey
 
 __all__ = ["Context", "FbsError", "Params", "Program", "TvSet", "ExecConfig", "FbsExecEnv", "LutExecEnv",
            "min_fbs_size", "parse_fbs", "parse_lbf", "table_is_valid", "P1024", "P2048", "margin_sigmas",
            "params_for", "bootstrap_cost", "choose_params", "security_bits", "sigma_min", "BitExecEnv", "map_basic", "parse_blif", "parse_bristol",
-           "Client", "Server", "ServerKey", "EncryptedInputs", "EncryptedOutputs"]
+           "Client", "Server", "ServerKey", "EncryptedInputs", "EncryptedOutputs", "PlainInputs"]

@@ -6,6 +6,11 @@ FILE is a mapped program the reference wrote (`.fbs` from `--output`, `.lbf` fro
 `--mapper basic`).  Inputs are the harness's: `np.random.seed(42)`, one `randint(0, 2, T)` draw per input in program
 order (map_circuit.py:137-139).  For netlists the decrypted outputs are compared with the netlist's own cleartext
 evaluation -- the reference's self-check (:174-180) with ciphertexts in the middle.  One JSON line is printed.
+
+`--plain NAME=BITS` (repeatable) gives input NAME to the server in the clear instead of encrypting it (`split.PlainInputs`): BITS = 0
+or 1 is that value for every sample, BITS = samples the harness's own draws for NAME.  The run then goes through the client / server
+split -- the client encrypts the other inputs, the server evaluates without the secret, the client decrypts -- and the self-check
+covers the mixed run.
 """
 import argparse
 import json
@@ -34,6 +39,28 @@ def load(path, kind, inputs):
     return map_basic(bits), bits, kind
 
 
+def split_run(env, cfg, values, plain, order):
+    """the evaluation with some inputs in the clear: -> (a callable that runs it, a callable that lists the loaded programs).
+    Client and server are made by the first run, as `LutExecEnv.eval` makes its context."""
+    from .split import Client, PlainInputs, Server
+    made = {}
+
+    def evaluate():
+        if not made:
+            made["client"] = Client(env, cfg)
+            made["server"] = Server(made["client"].server_key(), device=cfg.device)
+        client, server = made["client"], made["server"]
+        T = len(next(iter(values.values())))
+        rows = {n: int(plain[n]) if plain[n] != "samples" else np.asarray(values[n], np.int64) for n in order if n in plain}
+        sources = [PlainInputs(list(rows), T, rows)]
+        secret = [n for n in order if n not in plain]
+        if secret:
+            sources.insert(0, client.encrypt(values, names=secret))
+        return client.decrypt(server.run_chain(env, sources))
+
+    return evaluate, lambda: [prog for prog, _ in made["server"]._programs.values()]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m tfhe_fbs_map_amd", description=__doc__.split("\n\n")[0])
     ap.add_argument("filename")
@@ -47,6 +74,8 @@ def main(argv=None):
                     help="benchmark parameter set with reduced noise (NOT secure) instead of the 128-bit selector")
     ap.add_argument("--no-shared-rotations", action="store_true",
                     help="give every table a blind rotation of its own, even where several read one linear combination")
+    ap.add_argument("--plain", action="append", default=[], metavar="NAME=BITS",
+                    help="give input NAME to the server in the clear: BITS = 0 or 1 for every sample, or 'samples' for the harness's draws")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
 
@@ -60,12 +89,24 @@ def main(argv=None):
 
     cfg = ExecConfig(fbs_size=args.fbs_size, seed=args.seed, device=args.device, reduced_noise=args.reduced_noise,
                      fuse_tables=False if args.no_shared_rotations else None)
+    plain = {}
+    for item in args.plain:
+        name, sep, what = item.partition("=")
+        if not sep or name not in values or name in plain or what not in ("0", "1", "samples"):
+            ap.error("--plain %s: NAME=BITS with NAME an input, once, and BITS 0, 1 or samples" % item)
+        plain[name] = what
+        if what != "samples":
+            values[name] = np.full(args.samples, int(what))
     stats = env.stats()
+    if plain:
+        evaluate, programs = split_run(env, cfg, values, plain, order)
+    else:
+        evaluate, programs = (lambda: env.eval(values, config=cfg)), (lambda: [prog for prog, _ in cfg._programs.values()])
     t0 = time.perf_counter()
-    out = env.eval(values, config=cfg)          # first call: key generation + upload + program load + run
+    out = evaluate()          # first call: key generation + upload + program load + run
     first = time.perf_counter() - t0
     t0 = time.perf_counter()
-    out = env.eval(values, config=cfg)
+    out = evaluate()
     steady = time.perf_counter() - t0
     result = dict(file=args.filename, type=kind, samples=args.samples, stats=stats,
                   first_eval_s=round(first, 3), eval_s=round(steady, 3),
@@ -73,7 +114,9 @@ def main(argv=None):
                   outputs={str(k): (int(v) if np.ndim(v) == 0 else int(np.asarray(v).sum())) for k, v in out.items()})
     from dataclasses import asdict
     from .params import margin_sigmas, security_bits
-    for prog, _ in cfg._programs.values():
+    if plain:
+        result["plain_inputs"] = plain
+    for prog in programs():
         ctx = prog.ctx
         norm2 = env.fusion_stats(ctx.params.p_msg)["norm2_linprod"] if prog.fused else stats["norm2_linprod"]
         result["params"] = asdict(ctx.params)

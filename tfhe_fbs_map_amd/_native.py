@@ -7,6 +7,7 @@ loaded, importing this module raises, and if no gfx950 GPU is present
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 import weakref
 from dataclasses import dataclass, asdict
@@ -57,7 +58,30 @@ class _ResidentSrc(C.Structure):   # fbs_resident_src (include/fbs_exec.h, "resi
     _fields_ = [("state", C.c_void_p), ("row", C.c_uint32), ("refresh", C.c_uint32)]
 
 
-SRC_SEEDED, SRC_FULL, SRC_COMPACT = 0, 1, 2   # FBS_SRC_*
+SRC_SEEDED, SRC_FULL, SRC_COMPACT, SRC_PLAIN = 0, 1, 2, 3   # FBS_SRC_*
+
+
+def _input_src(source, T, ctw):
+    """one feed tuple of `Program.eval_sources` -> (fbs_input_src, the array it points into)"""
+    kind = source[0]
+    if kind == "plain":
+        _, data = source
+        if np.ndim(data) == 0:   # one message for every sample
+            a = np.array([operator.index(data)], np.int64)
+            return _InputSrc(SRC_PLAIN, 1, 0, 0, a.ctypes.data), a
+        a = _c(data, np.int64).reshape(T)
+        return _InputSrc(SRC_PLAIN, 0, 0, 0, a.ctypes.data), a
+    _, data, arg = source
+    if kind == "seeded":
+        a = _c(data, np.uint64).reshape(T)
+        return _InputSrc(SRC_SEEDED, 0, 0, int(arg), a.ctypes.data), a
+    if kind == "full":
+        a = _c(data, np.uint64).reshape(T, ctw)
+        return _InputSrc(SRC_FULL, 0, int(bool(arg)), 0, a.ctypes.data), a
+    if kind == "compact":
+        a = _c(data, np.uint64).reshape(T, -1)
+        return _InputSrc(SRC_COMPACT, int(arg), 1, 0, a.ctypes.data), a
+    raise ValueError(f"unknown source kind {kind!r}")
 
 
 @dataclass(frozen=True)
@@ -382,24 +406,16 @@ class Program:
             ("seeded", bodies [T], nonce0)     -- sample s on stream nonce0 + s (`Context.encrypt_seeded`)
             ("full", cts [T][D+1], refresh)    -- outputs of an earlier evaluation; refresh=True: through the identity table first
             ("compact", words [T][W], bits)    -- compact outputs of an earlier evaluation, always refreshed
+            ("plain", msgs int64 [T])          -- the server's own cleartext messages in [0, 2p), written on the GPU as trivial
+            ("plain", int)                        ciphertexts (zero mask, body m * Delta); an int serves every sample
         bits = 0: full outputs [n_outputs][T][D+1] (as `eval_seeded`); else compact [n_outputs][T][W] at that width (as
         `eval_seeded_compact`).  Needs no secret."""
         if len(sources) != self.n_inputs:
             raise ValueError(f"{len(sources)} sources for {self.n_inputs} inputs")
         arr, keep = (_InputSrc * max(1, self.n_inputs))(), []
         ctw = self.ctx.params.ct_words
-        for i, (kind, data, arg) in enumerate(sources):
-            if kind == "seeded":
-                a = _c(data, np.uint64).reshape(T)
-                arr[i] = _InputSrc(SRC_SEEDED, 0, 0, int(arg), a.ctypes.data)
-            elif kind == "full":
-                a = _c(data, np.uint64).reshape(T, ctw)
-                arr[i] = _InputSrc(SRC_FULL, 0, int(bool(arg)), 0, a.ctypes.data)
-            elif kind == "compact":
-                a = _c(data, np.uint64).reshape(T, -1)
-                arr[i] = _InputSrc(SRC_COMPACT, int(arg), 1, 0, a.ctypes.data)
-            else:
-                raise ValueError(f"unknown source kind {kind!r}")
+        for i, source in enumerate(sources):
+            arr[i], a = _input_src(source, T, ctw)
             keep.append(a)
         bits = int(bits)
         shape = (self.n_outputs, T, self.ctx.compact_words(bits) if bits else ctw)
@@ -412,7 +428,7 @@ class Program:
             ("state", state, row, refresh)     -- row `row` of a `DeviceState`; refresh=True: through the identity table first
         out_state=None: returns the outputs as `eval_sources` does at `out_bits`.  out_state: a `DeviceState` of n_outputs rows and
         T samples a row that takes the full outputs, row o = output o; returns it.  With out_state and only state and seeded
-        sources the call does not wait for the evaluation: whatever reads the state next is queued behind it."""
+        sources (and plain ones) the call does not wait for the evaluation: whatever reads the state next is queued behind it."""
         if len(sources) != self.n_inputs:
             raise ValueError(f"{len(sources)} sources for {self.n_inputs} inputs")
         arr, res, keep = (_InputSrc * max(1, self.n_inputs))(), (_ResidentSrc * max(1, self.n_inputs))(), []
@@ -426,18 +442,7 @@ class Program:
                 res[i] = _ResidentSrc(state._h.value, int(row), int(bool(refresh)))
                 keep.append(state)
                 continue
-            _, data, arg = source
-            if kind == "seeded":
-                a = _c(data, np.uint64).reshape(T)
-                arr[i] = _InputSrc(SRC_SEEDED, 0, 0, int(arg), a.ctypes.data)
-            elif kind == "full":
-                a = _c(data, np.uint64).reshape(T, ctw)
-                arr[i] = _InputSrc(SRC_FULL, 0, int(bool(arg)), 0, a.ctypes.data)
-            elif kind == "compact":
-                a = _c(data, np.uint64).reshape(T, -1)
-                arr[i] = _InputSrc(SRC_COMPACT, int(arg), 1, 0, a.ctypes.data)
-            else:
-                raise ValueError(f"unknown source kind {kind!r}")
+            arr[i], a = _input_src(source, T, ctw)
             keep.append(a)
         bits = int(out_bits)
         if out_state is not None:

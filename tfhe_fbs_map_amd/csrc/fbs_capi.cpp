@@ -1441,14 +1441,15 @@ static int refresh_slots(fbs_ctx *ctx, const fbs_tvset *tv, const uint32_t *d_sl
 }
 
 // One more pair of stages on eval_chunks.  Load: the full inputs are copied into their slots; runs of seeded inputs whose streams
-// step by T (and whose bodies lie T words apart) are expanded by one dev_expand_seeded each; compact inputs are staged in the packed
+// step by T (and whose bodies lie T words apart) are expanded by one dev_expand_seeded each; plaintext inputs (FBS_SRC_PLAIN) send the
+// chunk's messages, 8 bytes a sample or nothing for a broadcast, and one launch writes all their trivial ciphertexts (dev_fill_plain); compact inputs are staged in the packed
 // buffer, unpacked into the modulus-switch scratch and refreshed, and full inputs marked `refresh` are key-switched, modulus-switched
 // and refreshed in place -- both in groups whose rows fit the scratch reserve_wires sized (max_sources x Tc rows).  Store: that of
 // fbs_eval_seeded (out_bits = 0) or fbs_eval_seeded_compact.
 //
 // fbs_eval_resident adds: inputs that are rows of states (res), gathered into their slots by one launch per chunk before the
 // refreshes (a resident input marked `refresh` joins the full ones), and out_state in place of the host buffer, filled by one scatter
-// launch per chunk.  With out_state and no full or compact host input nothing has to come back: the chunks are queued without
+// launch per chunk.  With out_state and no full or compact host input (plaintext messages are none) nothing has to come back: the chunks are queued without
 // waiting, and the call returns once the arrays it was given have been read (`inputs_event`, after the last chunk's load).
 static bool state_of(const fbs_ctx *ctx, const fbs_state *st) {   // (by address: a foreign or stale pointer is never dereferenced)
     return st && std::find(ctx->states.begin(), ctx->states.end(), st) != ctx->states.end();
@@ -1488,7 +1489,9 @@ static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, 
     size_t W_in = 0;
     std::vector<uint32_t> compact_in, full_refresh;   // input indices
     std::vector<StateLink> links;                     // the gather list, then the scatter list
+    std::vector<uint32_t> plain_in;                   // input indices of the plaintext inputs
     bool any_seeded = false, host_cts = false;        // host_cts: some input is ciphertexts in host memory
+    bool plain_msgs = false;                          // some plaintext input brings a message per sample
     for (size_t i = 0; i < n_in; i++) {
         if (resident(i)) {
             links.push_back(StateLink{res[i].state->d + (size_t)res[i].row * T * ctw, prog->in_slot[i]});
@@ -1497,8 +1500,20 @@ static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, 
         }
         const fbs_input_src &x = src[i];
         const std::string who = "input " + std::to_string(i) + ": ";
-        if (x.kind > FBS_SRC_COMPACT) return set_error(ctx, FBS_E_INVALID, who + "unknown source kind " + std::to_string(x.kind));
+        if (x.kind > FBS_SRC_PLAIN) return set_error(ctx, FBS_E_INVALID, who + "unknown source kind " + std::to_string(x.kind));
         if (!x.data) return set_error(ctx, FBS_E_INVALID, who + "null data");
+        if (x.kind == FBS_SRC_PLAIN) {   // cleartext messages: [T], or one for every sample (bits = 1)
+            if (x.refresh) return set_error(ctx, FBS_E_INVALID, who + "a plaintext input is not refreshed");
+            if (x.bits > 1) return set_error(ctx, FBS_E_INVALID, who + "bits of a plaintext input is 0 ([T] messages) or 1 (one message for all)");
+            if (T > SIZE_MAX / 8) return set_error(ctx, FBS_E_INVALID, who + "T * words overflow");
+            const int64_t *m = reinterpret_cast<const int64_t *>(x.data);
+            for (size_t q = 0, count = x.bits ? 1 : T; q < count; q++)
+                if (m[q] < 0 || m[q] >= 2 * (int64_t)ctx->p.p_msg)
+                    return set_error(ctx, FBS_E_INVALID, who + "message " + std::to_string(m[q]) + " outside [0, 2p)");
+            plain_in.push_back((uint32_t)i);
+            plain_msgs |= !x.bits;
+            continue;
+        }
         size_t words = x.kind == FBS_SRC_SEEDED ? 1 : ctw;
         if (x.kind == FBS_SRC_COMPACT) {
             if ((rc = check_bits(ctx, x.bits)) != FBS_OK) return rc;
@@ -1519,7 +1534,7 @@ static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, 
     const size_t W_stage = std::max(W_in, W_out), rows_per_sample = std::max(1u, prog->max_sources);
     size_t Tc = 0;
     if ((rc = reserve_wires(ctx, prog, T, &Tc, rows_per_sample * W_stage * 8)) != FBS_OK) return rc;
-    if (any_seeded && (rc = ensure_io_msgs(ctx, n_in * Tc)) != FBS_OK) return rc;
+    if ((any_seeded || plain_msgs) && (rc = ensure_io_msgs(ctx, n_in * Tc)) != FBS_OK) return rc;
     const size_t cap_rows = rows_per_sample * Tc;   // (ensure_ms has made d_ms at least this long)
     if (W_stage && (rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, cap_rows * W_stage, 8, true)) != FBS_OK) return rc;
     // the slots to refresh, compact inputs first: uploaded with the first chunk (after eval_chunks's scratch_wait)
@@ -1539,8 +1554,16 @@ static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, 
         const int64_t w = prog->out_slot[o];
         links.push_back(StateLink{out_state->d + o * T * ctw, w >= 0 ? (uint64_t)w : STATE_LINK_CONST | trivial_body(ctx, w)});
     }
-    if (!links.empty() && (rc = grow(ctx, ctx->d_links, ctx->links_capacity, std::max<size_t>(links.size(), 1 << 12), sizeof(StateLink), false)) != FBS_OK)
+    // the fill list of the plaintext inputs, behind the links in the same buffer: the messages of input i lie where its bodies would
+    std::vector<PlainLink> plain;
+    for (uint32_t i : plain_in) {
+        const int64_t *m = reinterpret_cast<const int64_t *>(src[i].data);
+        plain.push_back(src[i].bits ? PlainLink{nullptr, m[0], prog->in_slot[i]} : PlainLink{ctx->d_io_msgs + (size_t)i * Tc, 0, prog->in_slot[i]});
+    }
+    const size_t link_units = links.size() + (plain.size() * sizeof(PlainLink) + sizeof(StateLink) - 1) / sizeof(StateLink);
+    if (link_units && (rc = grow(ctx, ctx->d_links, ctx->links_capacity, std::max<size_t>(link_units, 1 << 12), sizeof(StateLink), false)) != FBS_OK)
         return rc;
+    const PlainLink *d_plain = reinterpret_cast<const PlainLink *>(ctx->d_links + links.size());
     const bool wait = !out_state || host_cts;   // results or pageable ciphertexts cross the bus: chunk by chunk, as fbs_eval_sources
     if (!wait && !ctx->inputs_event) FBS_HIP(ctx, hipEventCreateWithFlags(&ctx->inputs_event, hipEventDisableTiming));
     const size_t n1 = ctx->p.n + 1;
@@ -1549,7 +1572,21 @@ static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, 
             FBS_HIP(ctx, hipMemcpyAsync(ctx->d_idx, refresh_slot.data(), refresh_slot.size() * 4, hipMemcpyHostToDevice, s));
         if (s0 == 0 && !links.empty())
             FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links, links.data(), links.size() * sizeof(StateLink), hipMemcpyHostToDevice, s));
+        if (s0 == 0 && !plain.empty())
+            FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links + links.size(), plain.data(), plain.size() * sizeof(PlainLink), hipMemcpyHostToDevice, s));
         if (int rc = dev_state_gather(ctx, StateCopy{ctx->d_links, n_gather, ctx->d_wires, Tc, s0, tc, ctx->D}, s)) return rc;
+        auto per_sample = [&](size_t i) { return !resident(i) && src[i].kind == FBS_SRC_PLAIN && !src[i].bits; };
+        for (size_t j0 = 0; j0 < n_in;) {   // the messages of the chunk: one 2D copy per stretch of inputs whose rows lie T words apart
+            if (!per_sample(j0)) {
+                j0++;
+                continue;
+            }
+            size_t j1 = j0 + 1;
+            while (j1 < n_in && per_sample(j1) && src[j1].data == src[j1 - 1].data + T) j1++;
+            FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_io_msgs + j0 * Tc, Tc * 8, src[j0].data + s0, T * 8, tc * 8, j1 - j0, hipMemcpyHostToDevice, s));
+            j0 = j1;
+        }
+        if (int rc = dev_fill_plain(ctx, PlainFill{d_plain, plain.size(), ctx->d_wires, Tc, tc, ctx->D, 2 * ctx->delta_half}, s)) return rc;
         for (size_t i = 0; i < n_in; i++)
             if (!resident(i) && src[i].kind == FBS_SRC_FULL)
                 FBS_HIP(ctx, hipMemcpyAsync(ctx->d_wires + (size_t)prog->in_slot[i] * Tc * ctw, src[i].data + s0 * ctw, tc * ctw * 8,
@@ -1608,7 +1645,7 @@ static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, 
         return out_bits ? store_compact(ctx, prog, cs, out, T, Tc, s0, tc, s) : store_host_cts(ctx, prog, out, T, Tc, s0, tc, s);
     };
     rc = eval_chunks(ctx, prog, T, Tc, s, wait, load, store);
-    // the link lists, refresh slots and seeded bodies live in pageable memory of this call or its caller: read before it returns.
+    // the link lists, refresh slots, seeded bodies and plaintext messages live in pageable memory of this call or its caller: read before it returns.
     // A call that failed part way may have queued copies from them without reaching the event: it waits for the stream instead.
     if (!wait && rc == FBS_OK) FBS_HIP(ctx, hipEventSynchronize(ctx->inputs_event));
     if (!wait && rc != FBS_OK) (void)hipStreamSynchronize(s);

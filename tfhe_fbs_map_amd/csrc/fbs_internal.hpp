@@ -116,6 +116,22 @@ struct StateCopy {
     uint32_t D;
 };
 
+// Plaintext inputs (FBS_SRC_PLAIN, fbs_state.hip): entry e of a launch fills wire slot `slot`, samples q < tc, with the trivial
+// ciphertexts of msgs[q] (the chunk's messages on the device) or, msgs null, of the one message `value` (a broadcast input)
+struct PlainLink {
+    const int64_t *msgs;
+    int64_t value;
+    uint64_t slot;
+};
+struct PlainFill {
+    const PlainLink *links;   // [n_links], device
+    size_t n_links;
+    uint64_t *wires;          // wire slots [n_slots][Tc][D + 1]
+    size_t Tc, tc;
+    uint32_t D;
+    uint64_t delta;           // 2 round(q / 4p): a message m in [0, 2p) is the body m delta mod q
+};
+
 struct Profile {
     struct Pending {
         hipEvent_t begin, end;
@@ -396,6 +412,8 @@ int dev_pack(fbs_ctx *ctx, const uint32_t *d_ms, size_t count, uint32_t bits, ui
 // resident state (fbs_state.hip): the links of `a` between state rows and wire slots, one launch each
 int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);
 int dev_state_scatter(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);
+// plaintext inputs: the trivial ciphertexts of the links of `a` into their wire slots, one launch
+int dev_fill_plain(const fbs_ctx *ctx, const PlainFill &a, hipStream_t stream);
 
 // profiling helpers
 void prof_begin(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t *e0, hipEvent_t *e1);

@@ -1,9 +1,11 @@
 // Resident state (fbs_state, fbs_eval_resident), gfx950: ciphertexts between the rows of state blocks [rows][T][D + 1] and the wire
-// slots [n_slots][Tc][D + 1] of a chunk.
+// slots [n_slots][Tc][D + 1] of a chunk; and the plaintext inputs of a chunk (FBS_SRC_PLAIN), written into the same slots.
 //
 //   k_state_gather    wire slot of link e, sample q  <-  row of link e, sample s0 + q     (the resident inputs of a chunk)
 //   k_state_scatter   row of link e, sample s0 + q   <-  wire slot of link e, sample q    (its outputs; a constant output is
 //                     written as the trivial ciphertext fbs_eval returns for it)
+//   k_fill_plain      wire slot of link e, sample q  <-  the trivial ciphertext of the link's message for sample q (the plaintext
+//                     inputs of a chunk, FBS_SRC_PLAIN: D zero words, then m Delta mod q)
 //
 // One launch moves every link of the chunk: the (link, sample) grid is dealt to waves, one ciphertext per wave at a time.  A
 // ciphertext is D + 1 words, an odd number, so one at an odd index starts 8 bytes off a 16-byte line.  Where source and
@@ -80,6 +82,20 @@ __global__ __launch_bounds__(64 * ST_WAVES) void k_state_scatter(StateCopy a) {
     }
 }
 
+// A pure streaming write: the wave stores 16 bytes a lane, aligned to the destination (wave_fill_trivial), and the body -- the only
+// non-zero word -- is computed once per ciphertext, wave-uniform.  m < 2p (checked by the host) and Delta <= q / 2p + 1, so
+// m Delta < q + 2p fits 64 bits and one 64-bit remainder is the residue fbs_eval's trivial_body computes.
+__global__ __launch_bounds__(64 * ST_WAVES) void k_fill_plain(PlainFill a) {
+    const uint32_t lane = threadIdx.x & 63u, words = a.D + 1;
+    const size_t total = a.n_links * a.tc;
+    for (size_t c = (size_t)blockIdx.x * ST_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * ST_WAVES) {   // wave-uniform
+        const size_t e = c / a.tc, q = c - e * a.tc;
+        const PlainLink ln = a.links[e];
+        const uint64_t m = (uint64_t)(ln.msgs ? ln.msgs[q] : ln.value);
+        wave_fill_trivial(a.wires + ((size_t)ln.slot * a.Tc + q) * words, m * a.delta % FQ, words, lane);
+    }
+}
+
 static dim3 st_grid(size_t total) { return dim3((unsigned)std::min<size_t>((total + ST_WAVES - 1) / ST_WAVES, ST_MAX_BLOCKS)); }
 
 int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream) {
@@ -92,6 +108,13 @@ int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream)
 int dev_state_scatter(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream) {
     if (a.n_links * a.tc == 0) return FBS_OK;
     hipLaunchKernelGGL(k_state_scatter, st_grid(a.n_links * a.tc), dim3(64 * ST_WAVES), 0, stream, a);
+    FBS_HIP(ctx, hipGetLastError());
+    return FBS_OK;
+}
+
+int dev_fill_plain(const fbs_ctx *ctx, const PlainFill &a, hipStream_t stream) {
+    if (a.n_links * a.tc == 0) return FBS_OK;
+    hipLaunchKernelGGL(k_fill_plain, st_grid(a.n_links * a.tc), dim3(64 * ST_WAVES), 0, stream, a);
     FBS_HIP(ctx, hipGetLastError());
     return FBS_OK;
 }

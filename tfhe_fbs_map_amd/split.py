@@ -43,6 +43,13 @@ fetched `EncryptedOutputs` back.
         acc.close()
         acc = nxt
     client.decrypt(acc.fetch(compact=True))
+
+Plaintext inputs.  The server's own data -- a table row, a round key, a counter -- joins a chain as a `PlainInputs`: cleartext bits by
+input name, a row per sample or one value for every sample.  They are written on the GPU as trivial ciphertexts (zero mask, body
+m * Delta: include/fbs_exec.h, "chained evaluation"), carry no noise and belong to no key; the client never sees them.
+
+    round_key = PlainInputs(b_names, None, {f"b{i}": (k >> i) & 1 for i in range(8)})    # one value for all samples
+    server.run(adder8, client.encrypt(query, names=a_names), plain=round_key)
 """
 from __future__ import annotations
 
@@ -53,7 +60,7 @@ import numpy as np
 
 from .fbs_exec_env import ExecConfig, min_fbs_size, table_fusion_factor, table_is_valid
 
-__all__ = ["ServerKey", "EncryptedInputs", "EncryptedOutputs", "CompactOutputs", "PackedOutputs", "ResidentOutputs", "packed_words", "Client", "Server", "FORMAT_VERSION",
+__all__ = ["ServerKey", "EncryptedInputs", "PlainInputs", "EncryptedOutputs", "CompactOutputs", "PackedOutputs", "ResidentOutputs", "packed_words", "Client", "Server", "FORMAT_VERSION",
            "mask_key_fingerprint", "seeded_key_sizes", "compact_words", "output_noise_factor", "output_noise_factors",
            "plan_chain", "ChainLink", "client_choice"]
 
@@ -243,6 +250,90 @@ class EncryptedInputs:
         if bodies.dtype != np.uint64 or bodies.shape != (len(names), T):
             raise ValueError(f"bodies of shape {bodies.shape} for {len(names)} inputs of {T} samples")
         return cls(names, T, int(d["nonce0"]), bodies, _fingerprint_of(d))
+
+
+@dataclass
+class PlainInputs:
+    """Cleartext inputs the server supplies itself (`Server.run_chain`): bits by input name, written on the GPU as trivial
+    ciphertexts.  values: int64 [n_inputs][T], or [n_inputs] when every input has one value for all samples (T may then be None: the
+    chain's T), or a mapping {name: array [T] or int} that may mix the two.  Public data: no fingerprint, no key.  Held to what
+    `Client.encrypt` admits for inputs: bits."""
+    input_names: list
+    T: int | None
+    values: object
+    broadcast: np.ndarray | None = None   # [n_inputs] bool: the row is one value for all samples (None: by the shape of `values`)
+
+    def __post_init__(self):
+        self.input_names = [str(n) for n in self.input_names]
+        n = len(self.input_names)
+        if len(set(self.input_names)) != n:
+            raise ValueError("plain inputs name an input twice")
+        self.T = None if self.T is None else int(self.T)
+        if self.T is not None and self.T < 1:
+            raise ValueError(f"plain inputs of T = {self.T} samples")
+        v = self.values
+        if hasattr(v, "keys"):
+            if sorted(str(k) for k in v.keys()) != sorted(self.input_names):
+                raise ValueError("the values name other inputs than input_names")
+            v = {str(k): x for k, x in v.items()}
+            rows = [self._int64(v[name]) for name in self.input_names]
+            self.broadcast = np.array([r.ndim == 0 for r in rows], bool)
+            if self.broadcast.all():
+                v = np.array([int(r) for r in rows], np.int64).reshape(n)
+            else:
+                if self.T is None:
+                    raise ValueError("plain inputs with a value per sample need T")
+                for name, r in zip(self.input_names, rows):
+                    if r.ndim and r.shape != (self.T,):
+                        raise ValueError(f"plain input {name}: values of shape {r.shape} for {self.T} samples")
+                v = np.stack([np.broadcast_to(r, (self.T,)) for r in rows]).astype(np.int64)
+        else:
+            v = self._int64(v)
+            if self.broadcast is None:
+                self.broadcast = np.full(n, v.ndim == 1, bool)
+        self.broadcast = np.asarray(self.broadcast)
+        if self.broadcast.dtype != bool or self.broadcast.shape != (n,):
+            raise ValueError(f"a broadcast mask of shape {self.broadcast.shape} and type {self.broadcast.dtype} for {n} plain inputs")
+        if v.ndim == 1:
+            if v.shape != (n,) or not self.broadcast.all():
+                raise ValueError(f"plain values of shape {v.shape} for {n} inputs with one value each")
+        elif self.T is None or v.shape != (n, self.T):
+            raise ValueError(f"plain values of shape {v.shape} for {n} inputs of {self.T} samples")
+        elif (v[self.broadcast] != v[self.broadcast][:, :1]).any():
+            raise ValueError("a plain input marked as one value for all samples holds several")
+        if v.size and (v.min() < 0 or v.max() > 1):
+            raise ValueError("plain inputs are bits, as the inputs a client encrypts")
+        self.values = np.ascontiguousarray(v, np.int64)
+
+    @staticmethod
+    def _int64(x):
+        a = np.asarray(x)
+        if a.dtype == bool:
+            a = a.astype(np.int64)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"plain values of type {a.dtype}: they are integers")
+        return a.astype(np.int64)
+
+    def row(self, j):
+        """what feeds input j: a python int (one value for all samples) or an int64 array [T]"""
+        if self.values.ndim == 1:
+            return int(self.values[j])
+        return int(self.values[j, 0]) if self.broadcast[j] else self.values[j]
+
+    def save(self, path):
+        np.savez(path, kind=np.array("plain_inputs"), format_version=np.array(FORMAT_VERSION),
+                 input_names=np.array(list(self.input_names), dtype=str), T=np.array(-1 if self.T is None else self.T, np.int64),
+                 values=self.values, broadcast=self.broadcast)
+
+    @classmethod
+    def load(cls, path):
+        d = _load_npz(path, "plain_inputs")
+        names = [str(n) for n in np.asarray(d["input_names"]).reshape(-1)]
+        T = int(d["T"])
+        values, broadcast = np.asarray(d["values"]), np.asarray(d["broadcast"])
+        if values.dtype != np.int64 or values.ndim not in (1, 2) or broadcast.dtype != bool:
+            raise ValueError(f"plain values of shape {values.shape} and type {values.dtype}, a mask of type {broadcast.dtype}")
+        return cls(names, None if T < 0 else T, values, broadcast)
 
 
 @dataclass
@@ -515,8 +606,11 @@ class Server:
         self._programs[id(low)] = (prog, low)
         return prog, low
 
-    def run(self, env, inputs: EncryptedInputs, resident=False):
-        """-> `EncryptedOutputs`; resident=True: the outputs stay on the GPU (fbs_eval_resident) -> `ResidentOutputs`."""
+    def run(self, env, inputs: EncryptedInputs, resident=False, plain=None):
+        """-> `EncryptedOutputs`; resident=True: the outputs stay on the GPU (fbs_eval_resident) -> `ResidentOutputs`.
+        plain: a `PlainInputs` with the inputs the server supplies in the clear; then `run_chain(env, [inputs, plain])`."""
+        if plain is not None:
+            return self.run_chain(env, [inputs, plain], resident=resident)
         if inputs.fingerprint != self.key.fingerprint:
             raise ValueError("inputs were encrypted for another server key")
         prog, low = self.program_for(env)
@@ -613,8 +707,9 @@ class Server:
         return ResidentOutputs(list(outputs.output_names), outputs.T, self.key.fingerprint, outputs.out_norm2, state, self, compact_bits)
 
     def run_chain(self, env, sources, rename=None, compact=False, bits=None, resident=False):
-        """Evaluate `env` with each input taken by name from one of `sources`: the client's `EncryptedInputs` (seeded) and the
-        `EncryptedOutputs` / `CompactOutputs` of earlier evaluations under this server key (fbs_eval_sources).  rename: {input name:
+        """Evaluate `env` with each input taken by name from one of `sources`: the client's `EncryptedInputs` (seeded), the
+        `EncryptedOutputs` / `CompactOutputs` of earlier evaluations under this server key, and the server's own `PlainInputs`
+        (cleartext bits, written on the GPU as trivial ciphertexts: noise-free, no key) (fbs_eval_sources).  rename: {input name:
         source name} for an input whose source carries another name.  Compact links, and full links whose producer was noisier
         than a bootstrap output, are refreshed on the GPU: one bootstrap each per sample.  compact=True: compact outputs at `bits`
         (None: the width `compact_bits` would pick for the noise these outputs carry).  `plan_chain` says what is refused.
@@ -639,6 +734,8 @@ class Server:
                 feed.append(("full", src.cts[ln.index], ln.refresh))
             elif ln.kind == "state":
                 feed.append(("state", src.state, ln.index, ln.refresh))
+            elif ln.kind == "plain":
+                feed.append(("plain", src.row(ln.index)))
             else:
                 feed.append(("compact", src.words[ln.index], int(src.bits)))
         out_norm2 = self._out_norm2(low, [ln.noise for ln in links])
@@ -661,17 +758,17 @@ class ChainLink:
     name: str                     # the program's input
     source: int                   # which of the sources
     index: int                    # its row there (input or output position)
-    kind: str                     # "seeded", "full", "compact" or "state" (a row of a ResidentOutputs: full ciphertexts on the GPU)
+    kind: str                     # "seeded", "full", "compact", "state" (a row of a ResidentOutputs: full ciphertexts on the GPU) or "plain"
     refresh: bool                 # bootstrapped through the identity table before use
-    noise: float                  # its noise factor going in: 0 fresh, 1 refreshed, the producer's out_norm2 for a plain full link
+    noise: float                  # its noise factor going in: 0 fresh or plain, 1 refreshed, the producer's out_norm2 for a plain full link
     margin: float | None = None   # params.refresh_margin of a refreshed link
 
 
-_SOURCE_TYPES = (EncryptedInputs, EncryptedOutputs, CompactOutputs, ResidentOutputs)
+_SOURCE_TYPES = (EncryptedInputs, EncryptedOutputs, CompactOutputs, ResidentOutputs, PlainInputs)
 
 
 def _names_of(src):
-    return list(src.input_names if isinstance(src, EncryptedInputs) else src.output_names)
+    return list(src.input_names if isinstance(src, (EncryptedInputs, PlainInputs)) else src.output_names)
 
 
 def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_margin=None):
@@ -683,7 +780,9 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
     refresh margin (`params.refresh_margin`) is below `params.refresh_margin_needed` at the program's norm2.  A full link whose
     producer's factor is at most 1 (a bootstrap output or a constant) goes in as it is: the program's parameter set assumes
     inputs no noisier than that.  Every other full link and every compact link is refreshed.  A `ResidentOutputs` is a full link
-    whose ciphertexts are on the GPU (kind "state"), under the same rule; a closed one is refused."""
+    whose ciphertexts are on the GPU (kind "state"), under the same rule; a closed one is refused.
+    A `PlainInputs` is public and belongs to no key: no fingerprint is asked of it, its link is noise-free (kind "plain", noise 0)
+    and never refreshed; one without T takes the chain's, and a program fed by such sources alone has no T and is refused."""
     from .params import margin_sigmas, refresh_margin, refresh_margin_needed
     low = env.lower()
     p = params.p_msg
@@ -705,14 +804,18 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
             raise ValueError("source %d is a PackedOutputs: a packed result is under the client's big key in GLWE form, for the client "
                              "only; link the EncryptedOutputs, CompactOutputs or ResidentOutputs of that evaluation instead" % k)
         if not isinstance(src, _SOURCE_TYPES):
-            raise TypeError("source %d is a %s, not EncryptedInputs, EncryptedOutputs, CompactOutputs or ResidentOutputs" % (k, type(src).__name__))
+            raise TypeError("source %d is a %s, not EncryptedInputs, EncryptedOutputs, CompactOutputs or ResidentOutputs, or PlainInputs" % (k, type(src).__name__))
         if isinstance(src, ResidentOutputs) and src.closed:
             raise ValueError("source %d is resident state that has been closed" % k)
-        if src.fingerprint != fingerprint:
+        if not isinstance(src, PlainInputs) and src.fingerprint != fingerprint:
             raise ValueError("source %d was computed under another server key" % k)
+        if src.T is None:   # (a PlainInputs of one value per input: the chain's T)
+            continue
         if T is not None and src.T != T:
             raise ValueError("source %d has T = %d samples where the others have %d" % (k, src.T, T))
         T = src.T
+    if T is None and sources and low["input_names"]:
+        raise ValueError("every source is a PlainInputs without T (one value for all samples): the chain has no T; give one of them T")
     rename = {str(a): str(b) for a, b in (rename or {}).items()}
     unknown = sorted(set(rename) - set(low["input_names"]))
     if unknown:
@@ -731,6 +834,9 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
         src = sources[k]
         if isinstance(src, EncryptedInputs):
             links.append(ChainLink(name, k, j, "seeded", False, 0.0))
+            continue
+        if isinstance(src, PlainInputs):
+            links.append(ChainLink(name, k, j, "plain", False, 0.0))
             continue
         if src.out_norm2 is None:
             raise ValueError("input %s: source %d was saved without out_norm2 (before chains existed), so the noise it carries is "
