@@ -97,6 +97,7 @@ typedef struct fbs_prog fbs_prog;
  * share no key material.  In BOTH forms the noise sampler is an integer
  * Irwin-Hall(12) stand-in for a discrete Gaussian (bounded at 6 sigma): test-grade.
  * A deployment that needs more brings its own keys with fbs_import_keys. */
+#define FBS_DEVICE_NONE (-1)   /* `device` of a context of the client library (below); libfbsexec.so refuses it like any ordinal it has no GPU for */
 int fbs_ctx_create(const fbs_params *params, uint64_t seed, int device, fbs_ctx **out);
 int fbs_ctx_create_seeded(const fbs_params *params, const uint8_t seed[32], int device, fbs_ctx **out);
 void fbs_ctx_destroy(fbs_ctx *ctx);
@@ -220,6 +221,33 @@ int fbs_encrypt_seeded_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t cou
 int fbs_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count, uint64_t nonce0, uint64_t *cts);
 int fbs_expand_seeded_dev(const fbs_ctx *ctx, const uint64_t *d_bodies, size_t count, uint64_t nonce0, uint64_t *d_cts,
                           void *stream);
+
+/* ---- client library: libfbsclient.so, the secret-key holder's part of this header on a machine with no GPU ------------------------
+ * The party that makes the keys, encrypts the inputs and reads the results is not the party with the GPU.  libfbsclient.so is
+ * built from the host sources alone (make -C tfhe_fbs_map_amd/csrc client: a C++17 compiler, no ROCm, no HIP runtime among its
+ * dependencies) and exports a SUBSET of the entries declared here, with the signatures, checks, error codes and nonce rules
+ * given above -- the two libraries compile the same code for them:
+ *     poly_size_check, ctx_create, ctx_create_seeded, ctx_destroy, ctx_stat, last_error, device_info,
+ *     keygen, key_sizes, export_keys,   keygen_seeded, seeded_key_sizes, export_seeded_keys,
+ *     encrypt, encrypt_fresh, decrypt,   encrypt_seeded, encrypt_seeded_fresh, expand_seeded,
+ *     compact_words, decrypt_compact,   packing_keygen, packing_key_sizes, export_packing_key, packed_words, decrypt_packed,
+ *     debug_raise                                                                      (each with the fbs_ prefix).
+ * Every other entry is ABSENT from that library, not stubbed: a program that needs one links libfbsexec.so.  Every entry is an
+ * exception barrier, as there.
+ * THE CONTRACT.  For the same fbs_params and the same seed, in either seed form, every word the client library writes -- secret
+ * keys, full keys, the mask key, key bodies, packing-key bodies, ciphertexts, seeded bodies, the streams fresh calls take -- is the
+ * word libfbsexec.so writes, and every message it decodes is the message libfbsexec.so decodes.  A server key exported by one opens
+ * in the other.
+ * DIFFERENCES from libfbsexec.so:
+ *   - `device` must be FBS_DEVICE_NONE.  Any other value returns FBS_E_DEVICE, with a text that names libfbsexec.so as the library
+ *     for contexts on a GPU.  The sentence at the top of this header stays true of libfbsexec.so: it has no CPU fallback, and
+ *     FBS_DEVICE_NONE does not give it one.
+ *   - the device-info entry returns "host".
+ *   - the statistics served are "has_secret", "seeded_keys", "next_nonce", "packing_key", "packing_levels" and "packing_base_bits";
+ *     any other name returns FBS_E_INVALID.
+ *   - parameter admission is the same: the range rules, then whether libfbsexec.so has kernels for the set (a set it refuses is
+ *     refused here with the same code, since no server could evaluate under such keys).
+ *   - a context is host memory only, so nothing is uploaded: the packing keygen entry keeps the bodies, the export entries read them. */
 
 /* ---- tables -> test vectors ----------------------------------------------
  * One entry per distinct `Bootstrap.table` (fbs_exec_env.py:51-61).  Table t is

@@ -10,7 +10,6 @@ import ctypes as C
 import operator
 import os
 import weakref
-from dataclasses import dataclass, asdict
 
 import numpy as np
 
@@ -18,22 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FBS_LIB") or os.path.join(_HERE, "libfbsexec.so")   # FBS_LIB: kernel-variant experiments
 
 from .security import MODULUS, MODULUS_BITS, sigma_min      # noqa: E402,F401
-
-
-RANDOMNESS_GRADE = ("test-grade: ChaCha20 streams keyed by the context seed; noise = integer Irwin-Hall(12) stand-in for a discrete "
-                    "Gaussian, bounded at 6 sigma.  Bring keys made with a production sampler through Context.import_keys")
-
-
-class FbsError(RuntimeError):
-    def __init__(self, code, text):
-        super().__init__(f"libfbsexec error {code}: {text}")
-        self.code = code
-
-
-class _Params(C.Structure):
-    _fields_ = [(f, C.c_uint32) for f in
-                ("n", "log_n_poly", "k", "l_bsk", "beta_bsk", "t_ksk", "gamma_ksk", "p_msg")] + \
-               [("sigma_lwe", C.c_uint64), ("sigma_glwe", C.c_uint64), ("bsk_group", C.c_uint32), ("reserved", C.c_uint32)]
+# what a client shares with this module lives in `_client_native`, which needs neither this library nor a GPU
+from ._client_native import RANDOMNESS_GRADE, FbsError, Params, _Params, _c, _ptr, gpu_library_missing      # noqa: E402,F401
 
 
 class _Layout(C.Structure):
@@ -84,81 +69,9 @@ def _input_src(source, T, ctw):
     raise ValueError(f"unknown source kind {kind!r}")
 
 
-@dataclass(frozen=True)
-class Params:
-    """Cryptographic parameter set.  The shape defaults to BASELINE.md's synthetic set (n=630 N=1024 k=1 l=3 beta=7
-    t=8 gamma=2).  A noise left at None becomes the smallest standard deviation that is 128-bit secure at its
-    dimension (`security.sigma_min`); anything lower is an explicit choice -- `reduced_noise()` is the benchmark
-    setting (2^-40 q, NOT secure), `params.P1024` the benchmark set built with it, `params.choose_params` the
-    selector that returns secure AND correct sets."""
-    n: int = 630
-    log_n_poly: int = 10
-    k: int = 1
-    l_bsk: int = 3
-    beta_bsk: int = 7
-    t_ksk: int = 8
-    gamma_ksk: int = 2
-    p_msg: int = 15
-    sigma_lwe: int | None = None      # key-switching-key noise, absolute units of 1/q
-    sigma_glwe: int | None = None     # bootstrapping-key and fresh-input noise
-    bsk_group: int = 1                # key bits per blind-rotation step: 1, or 2 (n/2 steps on bundles of 3 GGSW samples)
-
-    def __post_init__(self):
-        if self.sigma_lwe is None:
-            object.__setattr__(self, "sigma_lwe", sigma_min(self.n))
-        if self.sigma_glwe is None:
-            object.__setattr__(self, "sigma_glwe", sigma_min(self.k * (1 << self.log_n_poly)))
-
-    @classmethod
-    def for_poly_size(cls, poly_size: int, **kw):
-        """Parameter set for polynomial size N.  A non-power-of-two N (BASELINE config 5 names one) raises
-        FbsError(FBS_E_POLY_SIZE): see include/fbs_exec.h `fbs_poly_size_check` for why that ring is refused."""
-        rc = lib.fbs_poly_size_check(int(poly_size))
-        if rc != 0:
-            raise FbsError(rc, lib.fbs_last_error(None).decode())
-        return cls(log_n_poly=int(poly_size).bit_length() - 1, **kw)
-
-    def reduced_noise(self, sigma: int = 1 << 6):
-        """The same shape with both noises at `sigma` (default 2^6 = 2^-40 q): throughput benchmarks and parity tests
-        only -- far below what any security level needs at these dimensions."""
-        return self.replace(sigma_lwe=sigma, sigma_glwe=sigma)
-
-    @property
-    def N(self):
-        return 1 << self.log_n_poly
-
-    @property
-    def big_dim(self):
-        return self.k * self.N
-
-    @property
-    def ct_words(self):
-        return self.big_dim + 1
-
-    def replace(self, **kw):
-        d = asdict(self)
-        d.update(kw)
-        return Params(**d)
-
-    def to_c(self):
-        return _Params(reserved=0, **asdict(self))
-
-    def bytes_per_fbs(self):
-        """Algorithmic bytes one FBS must consume: every
-        bootstrapping-key row and key-switching-key row once, its input and
-        output ciphertext and its test vector."""
-        N, k, n = self.N, self.k, self.n
-        ggsw = (k + 1) * self.l_bsk * (k + 1) * N * 8
-        bsk = (n // 2 * 3 if self.bsk_group == 2 else n) * ggsw
-        ksk = k * N * self.t_ksk * (n + 1) * 8
-        return bsk + ksk + 2 * (k * N + 1) * 8 + N * 8
-
-
 def _load():
     if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  tfhe_fbs_map_amd has no CPU fallback.")
+        raise ImportError(gpu_library_missing(LIB_PATH))
     # PyTorch ships its own copy of the HIP runtime; if it is going to be used in this process (device
     # tensors, RCCL) it has to be the first one loaded, or torch later finds "No HIP GPUs".
     try:
@@ -287,14 +200,6 @@ EXPORTED_SYMBOLS = (
 )
 
 lib = _load()
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data
-
-
-def _c(a, dtype):
-    return np.ascontiguousarray(a, dtype=dtype)
 
 
 def kernel_catalog():

@@ -1,0 +1,84 @@
+// What the entries of include/fbs_exec.h that run on the host check before they do anything -- buffers, keys, the secret, the
+// stream ranges, word counts that must not overflow, the fresh-stream counter, the widths of compact and packed outputs, the
+// packing key's parameters -- in one place, because two libraries serve those entries: libfbsexec.so (fbs_capi.cpp) and the
+// client library libfbsclient.so (fbs_client_capi.cpp).  The same checks in the same order give the same codes and texts, and a
+// refused call moves no counter in either.  Host code, no device in it.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "fbs_compact.hpp"
+#include "fbs_internal.hpp"
+#include "fbs_pack.hpp"
+
+namespace fbs {
+
+// what every entry that needs the secret keys says on a context made by fbs_import_seeded_keys
+constexpr const char *EVAL_ONLY = "this context holds evaluation keys only";
+
+// Streams [first, first + count) of [2^55, 2^56) that nobody has used, for every entry that takes fresh streams.  The range is
+// reserved atomically: two threads encrypting on one context never share a stream (the bound is checked BEFORE the counter
+// moves, so a refused call leaves it where it was).
+inline int reserve_fresh(const fbs_ctx *ctx, size_t count, uint64_t *first_out) {
+    uint64_t first = ctx->next_nonce.load(std::memory_order_relaxed);
+    do {
+        if (count > (1ull << 56) || first + count > (1ull << 56)) return set_error(ctx, FBS_E_STATE, "encryption streams of this context are used up");
+    } while (!ctx->next_nonce.compare_exchange_weak(first, first + count, std::memory_order_relaxed));
+    *first_out = first;
+    return FBS_OK;
+}
+// streams [2^55, 2^56) belong to the fresh entries: an explicit nonce can never repeat one the context handed out itself
+inline int check_nonces(const fbs_ctx *ctx, uint64_t nonce0, size_t count) {
+    if (nonce0 >= (1ull << 55) || count > (1ull << 55) - nonce0) return set_error(ctx, FBS_E_INVALID, "nonce0 + count must stay below 2^55");
+    return FBS_OK;
+}
+// seeded streams may be any the full entries may take, fresh ones included
+inline int check_seeded_streams(const fbs_ctx *ctx, uint64_t nonce0, size_t count) {
+    if (nonce0 >= (1ull << 56) || count > (1ull << 56) - nonce0) return set_error(ctx, FBS_E_INVALID, "nonce0 + count must stay below 2^56");
+    return FBS_OK;
+}
+// count ciphertexts of D + 1 words: more than fit in a size_t is refused before anything is launched
+inline int check_ct_words(const fbs_ctx *ctx, size_t count) {
+    if (count > SIZE_MAX / 8 / (ctx->D + 1)) return set_error(ctx, FBS_E_INVALID, "count * (D + 1) words overflow");
+    return FBS_OK;
+}
+
+// What the encrypt / decrypt / expand entries check, in this order: the buffers (a null one with count > 0 is FBS_E_INVALID
+// without a message), the keys, the secret (IO_SECRET), the explicit streams [*first, *first + count) (IO_BELOW_2_55 or
+// IO_BELOW_2_56), count * (D + 1) words (IO_CT_WORDS), and last a fresh range (IO_FRESH: reserved into *first), so that a
+// refused call never moves next_nonce.
+enum : unsigned { IO_SECRET = 1, IO_BELOW_2_55 = 2, IO_BELOW_2_56 = 4, IO_FRESH = 8, IO_CT_WORDS = 16 };
+inline int io_prologue(const fbs_ctx *ctx, const void *src, const void *dst, size_t count, unsigned checks, uint64_t *first) {
+    if (!ctx || (count && (!src || !dst))) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if ((checks & IO_SECRET) && ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    int rc = FBS_OK;
+    if ((checks & IO_BELOW_2_55) && (rc = check_nonces(ctx, *first, count))) return rc;
+    if ((checks & IO_BELOW_2_56) && (rc = check_seeded_streams(ctx, *first, count))) return rc;
+    if ((checks & IO_CT_WORDS) && (rc = check_ct_words(ctx, count))) return rc;
+    if (checks & IO_FRESH) rc = reserve_fresh(ctx, count, first);
+    return rc;
+}
+
+// compact and packed outputs: the width, and word counts that must not overflow
+inline int check_bits(const fbs_ctx *ctx, uint32_t bits) {
+    if (bits < ctx->p.log_n_poly + 1 || bits > 31) return set_error(ctx, FBS_E_INVALID, "compact width must lie in [log2(2N), 31]");
+    return FBS_OK;
+}
+inline int check_compact_words(const fbs_ctx *ctx, size_t count, uint32_t bits) {
+    if (count > SIZE_MAX / 8 / compact_words(ctx->p.n, bits)) return set_error(ctx, FBS_E_INVALID, "count * W words overflow");
+    return FBS_OK;
+}
+inline int check_packing_params(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) {
+    if (const char *why = packing_params_refused(t_p, gamma_p)) return set_error(ctx, FBS_E_INVALID, why);
+    if (!pack_shape_built(ctx->p.log_n_poly, ctx->p.k)) return set_error(ctx, FBS_E_INVALID, "no packing kernel for this (k, N)");
+    return FBS_OK;
+}
+inline int check_packed_words(const fbs_ctx *ctx, size_t count, uint32_t bits) {
+    if (count / ctx->N + 1 > SIZE_MAX / 8 / packed_sample_words(ctx->p.k, ctx->N, ctx->N, bits))
+        return set_error(ctx, FBS_E_INVALID, "packed words overflow");
+    return FBS_OK;
+}
+
+}  // namespace fbs

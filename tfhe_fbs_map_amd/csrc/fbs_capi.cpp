@@ -8,15 +8,13 @@
 #include <functional>
 #include <memory>
 
+#include "fbs_api_checks.hpp"
 #include "fbs_compact.hpp"
 #include "fbs_internal.hpp"
 #include "fbs_pack.hpp"
 #include "fbs_plan.hpp"
 
 using namespace fbs;
-
-// what every entry that needs the secret keys says on a context made by fbs_import_seeded_keys
-static const char *const EVAL_ONLY = "this context holds evaluation keys only";
 
 // ---------------------------------------------------------------------------------------------
 // program representation
@@ -368,50 +366,6 @@ int fbs_import_keys(fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glw
     ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
     return FBS_OK;
 } FBS_API_CATCH(ctx)
-
-// Streams [first, first + count) of [2^55, 2^56) that nobody has used, for every entry that takes fresh streams.  The range is
-// reserved atomically: two threads encrypting on one context never share a stream (the bound is checked BEFORE the counter
-// moves, so a refused call leaves it where it was).
-static int reserve_fresh(const fbs_ctx *ctx, size_t count, uint64_t *first_out) {
-    uint64_t first = ctx->next_nonce.load(std::memory_order_relaxed);
-    do {
-        if (count > (1ull << 56) || first + count > (1ull << 56)) return set_error(ctx, FBS_E_STATE, "encryption streams of this context are used up");
-    } while (!ctx->next_nonce.compare_exchange_weak(first, first + count, std::memory_order_relaxed));
-    *first_out = first;
-    return FBS_OK;
-}
-// streams [2^55, 2^56) belong to the fresh entries: an explicit nonce can never repeat one the context handed out itself
-static int check_nonces(const fbs_ctx *ctx, uint64_t nonce0, size_t count) {
-    if (nonce0 >= (1ull << 55) || count > (1ull << 55) - nonce0) return set_error(ctx, FBS_E_INVALID, "nonce0 + count must stay below 2^55");
-    return FBS_OK;
-}
-// seeded streams may be any the full entries may take, fresh ones included
-static int check_seeded_streams(const fbs_ctx *ctx, uint64_t nonce0, size_t count) {
-    if (nonce0 >= (1ull << 56) || count > (1ull << 56) - nonce0) return set_error(ctx, FBS_E_INVALID, "nonce0 + count must stay below 2^56");
-    return FBS_OK;
-}
-// count ciphertexts of D + 1 words: more than fit in a size_t is refused before anything is launched
-static int check_ct_words(const fbs_ctx *ctx, size_t count) {
-    if (count > SIZE_MAX / 8 / (ctx->D + 1)) return set_error(ctx, FBS_E_INVALID, "count * (D + 1) words overflow");
-    return FBS_OK;
-}
-
-// What the encrypt / decrypt / expand entries check, in this order: the buffers (a null one with count > 0 is FBS_E_INVALID
-// without a message), the keys, the secret (IO_SECRET), the explicit streams [*first, *first + count) (IO_BELOW_2_55 or
-// IO_BELOW_2_56), count * (D + 1) words (IO_CT_WORDS), and last a fresh range (IO_FRESH: reserved into *first), so that a
-// refused call never moves next_nonce.
-enum : unsigned { IO_SECRET = 1, IO_BELOW_2_55 = 2, IO_BELOW_2_56 = 4, IO_FRESH = 8, IO_CT_WORDS = 16 };
-static int io_prologue(const fbs_ctx *ctx, const void *src, const void *dst, size_t count, unsigned checks, uint64_t *first) {
-    if (!ctx || (count && (!src || !dst))) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if ((checks & IO_SECRET) && ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    int rc = FBS_OK;
-    if ((checks & IO_BELOW_2_55) && (rc = check_nonces(ctx, *first, count))) return rc;
-    if ((checks & IO_BELOW_2_56) && (rc = check_seeded_streams(ctx, *first, count))) return rc;
-    if ((checks & IO_CT_WORDS) && (rc = check_ct_words(ctx, count))) return rc;
-    if (checks & IO_FRESH) rc = reserve_fresh(ctx, count, first);
-    return rc;
-}
 
 int fbs_encrypt_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *cts, uint64_t *nonce0) try {
     uint64_t first = 0;
@@ -1247,14 +1201,6 @@ int fbs_eval_seeded(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t
 } FBS_API_CATCH(ctx)
 
 // ---- compact outputs: key switch to the small key, rounding to Z_(2^bits), bit packing (fbs_compact.hpp) --------------------
-static int check_bits(const fbs_ctx *ctx, uint32_t bits) {
-    if (bits < ctx->p.log_n_poly + 1 || bits > 31) return set_error(ctx, FBS_E_INVALID, "compact width must lie in [log2(2N), 31]");
-    return FBS_OK;
-}
-static int check_compact_words(const fbs_ctx *ctx, size_t count, uint32_t bits) {
-    if (count > SIZE_MAX / 8 / compact_words(ctx->p.n, bits)) return set_error(ctx, FBS_E_INVALID, "count * W words overflow");
-    return FBS_OK;
-}
 // fbs_compact_dev runs in passes of the modulus-switch scratch the context has, or of this many ciphertexts when it has less
 constexpr size_t COMPACT_PASS = 8192;
 
@@ -1763,16 +1709,6 @@ int fbs_state_put(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const u
 } FBS_API_CATCH(ctx)
 
 // ---- packed outputs: up to N outputs in one GLWE sample under the big key (fbs_pack.hpp, fbs_pack.hip) -----------------------
-static int check_packing_params(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) {
-    if (const char *why = packing_params_refused(t_p, gamma_p)) return set_error(ctx, FBS_E_INVALID, why);
-    if (!pack_shape_built(ctx->p.log_n_poly, ctx->p.k)) return set_error(ctx, FBS_E_INVALID, "no packing kernel for this (k, N)");
-    return FBS_OK;
-}
-static int check_packed_words(const fbs_ctx *ctx, size_t count, uint32_t bits) {
-    if (count / ctx->N + 1 > SIZE_MAX / 8 / packed_sample_words(ctx->p.k, ctx->N, ctx->N, bits))
-        return set_error(ctx, FBS_E_INVALID, "packed words overflow");
-    return FBS_OK;
-}
 // installs (t_p, gamma_p, bodies) as the context's packing key: expands the masks, transforms on the device; the previous key
 // stays until this has succeeded
 static int install_packing_key(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies) {

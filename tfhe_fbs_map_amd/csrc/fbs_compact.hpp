@@ -5,7 +5,9 @@
 // first and body last, packed into W = ceil((n + 1) w / 64) words; field j occupies bits [j w, j w + w) of the ciphertext's bit
 // stream, stream bit b being bit b mod 64 of word b / 64.
 #pragma once
+#ifndef FBS_HOST_ONLY   // (the client library, libfbsclient.so, is built without HIP)
 #include <hip/hip_runtime.h>
+#endif
 
 #include <cstdint>
 

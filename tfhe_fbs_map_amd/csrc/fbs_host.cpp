@@ -4,6 +4,7 @@
 // values back, as the reference's harness (fbs_mapper/map_circuit.py:137-180) expects.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <functional>
 #include <cstring>
 #include <thread>
@@ -71,8 +72,19 @@ int64_t noise_sample(const RandKey &seed, uint64_t stream, uint64_t idx, uint64_
     return irwin_hall_sample(w, sigma);
 }
 
+// Worker threads of parallel_for: OMP_NUM_THREADS when it is set to a positive number (the usual way a machine tells a process how
+// many CPUs are its own: a pool sized by a shared machine's CPU count only slows itself down), else the hardware's count.
+static unsigned worker_count() {
+    if (const char *env = std::getenv("OMP_NUM_THREADS")) {
+        char *end = nullptr;
+        const long v = std::strtol(env, &end, 10);
+        if (end != env && v >= 1) return (unsigned)std::min<long>(v, 1024);
+    }
+    return std::max(1u, std::thread::hardware_concurrency());
+}
+
 static void parallel_for(size_t n, const std::function<void(size_t, size_t)> &body) {
-    unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    unsigned hw = worker_count();
     size_t workers = std::min<size_t>(hw, std::max<size_t>(1, n));
     if (workers <= 1) {
         body(0, n);

@@ -1,7 +1,11 @@
 // Internal definitions shared by the host side (fbs_host.cpp, fbs_capi.cpp) and the HIP side
-// (fbs_kernels.hip) of libfbsexec.so.
+// (fbs_kernels.hip) of libfbsexec.so -- and, with FBS_HOST_ONLY defined, by the client library libfbsclient.so
+// (fbs_error.cpp, fbs_host.cpp, fbs_client_capi.cpp), which is built without HIP: it then sees the host state of a context
+// (fbs::HostState) and the host functions, and nothing that names a device type.
 #pragma once
+#ifndef FBS_HOST_ONLY
 #include <hip/hip_runtime.h>
+#endif
 
 #include <atomic>
 #include <cstdint>
@@ -132,6 +136,7 @@ struct PlainFill {
     uint64_t delta;           // 2 round(q / 4p): a message m in [0, 2p) is the body m delta mod q
 };
 
+#ifndef FBS_HOST_ONLY
 struct Profile {
     struct Pending {
         hipEvent_t begin, end;
@@ -150,17 +155,16 @@ struct Profile {
     // the same totals per kernel instantiation: a launch that is cut into a whole-round part and a remainder shows as two entries
     std::map<std::string, PerKernel> by_kernel[3];
 };
+#endif
 
-}  // namespace fbs
-
-struct fbs_ctx {
+// The host state of a context: everything fbs_host.cpp reads or writes -- parameters and what is derived from them, the random
+// keys, the nonce counter, the secrets and the host copies of the keys, the packing key's parameters and bodies, the error
+// text.  No device type in it: the client library's context is this and nothing more, the GPU library's adds the device side.
+struct HostState {
     fbs_params p{};
     uint64_t seed = 0;
-    fbs::RandKey rkey{};               // what all randomness of the context is expanded from
+    RandKey rkey{};                    // what all randomness of the context is expanded from
     mutable std::atomic<uint64_t> next_nonce{1ull << 55};  // fbs_encrypt_fresh: first unused encryption stream of [2^55, 2^56); reserved by compare-exchange
-    fbs::Tune tune;
-    int64_t scratch_growths = 0;       // how often a call had to (re)allocate scratch, i.e. blocked (fbs_ctx_stat)
-    int device = 0;
     uint32_t N = 0, D = 0, rows = 0;   // D = k*N, rows = (k+1)*l
     uint32_t group = 1;                // key bits per blind-rotation step (1 or 2)
     size_t n_ggsw = 0;                 // GGSW samples in the bootstrapping key: n, or 3n/2 for group 2
@@ -169,17 +173,33 @@ struct fbs_ctx {
     uint64_t g[16]{};                  // round(q / B^(lv+1))
     uint64_t h[64]{};                  // round(q / 2^(gamma (v+1)))
     mutable std::string err;
-    std::string devinfo;
-    int cu_count = 0;
-    hipStream_t stream = nullptr;
 
     bool have_keys = false;
     std::vector<uint64_t> sk_lwe, sk_glwe, bsk, ksk;   // host copies, standard layout
     // Seeded path: masks are drawn under `mask_key` (mask_key_of(rkey), or the one fbs_import_seeded_keys received).
     // seeded_keys: the evaluation keys came from fbs_keygen_seeded or fbs_import_seeded_keys; eval_only: they came from
     // fbs_import_seeded_keys, and the context holds no secret (sk_lwe, sk_glwe empty, d_sk_bits freed).
-    fbs::RandKey mask_key{};
+    RandKey mask_key{};
     bool seeded_keys = false, eval_only = false;
+
+    // Packed outputs: the packing key's parameters and bodies [n][t_p][N] (the masks come from mask_key)
+    bool have_pack = false;
+    uint32_t pack_t = 0, pack_gamma = 0;
+    std::vector<uint64_t> pack_bodies;
+};
+
+}  // namespace fbs
+
+#ifdef FBS_HOST_ONLY
+struct fbs_ctx : fbs::HostState {};
+#else
+struct fbs_ctx : fbs::HostState {
+    fbs::Tune tune;
+    int64_t scratch_growths = 0;       // how often a call had to (re)allocate scratch, i.e. blocked (fbs_ctx_stat)
+    int device = 0;
+    std::string devinfo;
+    int cu_count = 0;
+    hipStream_t stream = nullptr;
 
     uint64_t *d_bsk_hat = nullptr;   // [n][rows][k+1][N]  NTT domain, lane-interleaved, x N^-1
     uint64_t *d_bsk_hat_small = nullptr;   // the same in the evaluation order of the small-launch shape (fbs_ntt.hpp), where small_key_needed
@@ -208,12 +228,9 @@ struct fbs_ctx {
     uint32_t *d_sk_lwe_bits = nullptr;   // [ceil(n / 32)] the small LWE key as packed bits (decryption of compact outputs)
     uint64_t *d_compact = nullptr;   // scratch: packed compact ciphertexts of fbs_eval_seeded_compact's output groups
     size_t compact_capacity = 0;     // in words (also the staging of compact inputs, fbs_eval_sources)
-    // Packed outputs (fbs_pack.hip): the packing key's parameters and bodies [n][t_p][N] (the masks come from mask_key), the key
-    // in the transform domain [n][t_p][k+1][N] (centred doubles, x N^-1, key_word order), and the packing scratch: the rounded
+    // Packed outputs (fbs_pack.hip): the packing key (parameters and bodies: HostState) in the transform domain
+    // [n][t_p][k+1][N] (centred doubles, x N^-1, key_word order), and the packing scratch: the rounded
     // mask fields and the raw body fields of a pass transposed to [n+1][samples N], partial accumulators [samples][slices][k+1][N]
-    bool have_pack = false;
-    uint32_t pack_t = 0, pack_gamma = 0;
-    std::vector<uint64_t> pack_bodies;
     double *d_pack_key = nullptr;
     size_t pack_key_capacity = 0;    // in words
     uint32_t *d_pack_fields = nullptr;
@@ -266,6 +283,7 @@ struct fbs_tvset {
     std::vector<uint64_t> g_norm2;    //   (fbs_table_fusion_norms)
     std::vector<uint8_t> fusable;     // 0: the coefficients of D_F are too large for the 64-bit sums of k_multi_extract
 };
+#endif   // !FBS_HOST_ONLY
 
 namespace fbs {
 
@@ -352,6 +370,7 @@ void host_twiddles(uint32_t log_n, std::vector<uint64_t> &fwd, std::vector<uint6
 const char *imported_keys_mismatch(const fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glwe, const uint64_t *bsk,
                                    const uint64_t *ksk);
 
+#ifndef FBS_HOST_ONLY
 // device side (fbs_kernels.hip); all asynchronous on `stream`
 int dev_upload_keys(fbs_ctx *ctx);       // BSK -> NTT domain, KSK padded
 int dev_keyswitch_gemm_setup(fbs_ctx *ctx);   // limb fragments of the key-switching key for the int8 MFMA key switch
@@ -418,5 +437,6 @@ int dev_fill_plain(const fbs_ctx *ctx, const PlainFill &a, hipStream_t stream);
 // profiling helpers
 void prof_begin(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t *e0, hipEvent_t *e1);
 void prof_end(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t e0, hipEvent_t e1);
+#endif   // !FBS_HOST_ONLY
 
 }  // namespace fbs

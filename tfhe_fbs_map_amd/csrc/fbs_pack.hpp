@@ -4,7 +4,9 @@
 // one GLWE sample under the big key by a packing key switch; the sample is rounded to w bits a coefficient and bit-packed like a
 // compact ciphertext: k N mask fields (component-major), then the body fields of the coefficients in use.
 #pragma once
+#ifndef FBS_HOST_ONLY   // (the client library, libfbsclient.so, is built without HIP)
 #include <hip/hip_runtime.h>
+#endif
 
 #include <cstddef>
 #include <cstdint>

@@ -254,13 +254,7 @@ bool small_key_needed(const fbs_ctx *ctx) {
 }
 
 int check_kernel_built(const fbs_ctx *ctx) {
-    const fbs_params &p = ctx->p;
-    if (p.k >= 2 && !glwe_shape_built(p.log_n_poly, p.k))
-        return set_error(ctx, FBS_E_INVALID, "GLWE dimensions k >= 2 are built for k = 2, 3, 4 at N = 256 and 512 and k = 2, 3 at N = 1024");
-    if (p.log_n_poly < 8 || p.log_n_poly > 12)
-        return set_error(ctx, FBS_E_INVALID, "supported polynomial sizes are N = 256, 512, 1024, 2048, 4096");
-    if (p.bsk_group == 2 && p.k == 1 && (p.log_n_poly < 10 || p.l_bsk > 5))
-        return set_error(ctx, FBS_E_INVALID, "two key bits per step (bsk_group = 2) at k = 1 is built for N = 1024, 2048 and 4096, l <= 5");
+    if (const char *why = kernel_not_built(ctx->p)) return set_error(ctx, FBS_E_INVALID, why);
     return FBS_OK;
 }
 

@@ -4,7 +4,9 @@
 // fbs_kernels.hip) map a descriptor to its hipLaunchKernelGGL and decide nothing.  The instantiation lists below are what those
 // files instantiate and what fbs_kernel_catalog lists.
 #pragma once
+#ifndef FBS_HOST_ONLY   // (the client library, libfbsclient.so, is built without HIP)
 #include <hip/hip_runtime.h>   // (the attributes of fbs_field.hpp; nothing here calls HIP)
+#endif
 
 #include <cmath>
 #include <cstddef>
@@ -134,7 +136,17 @@ inline const char *params_out_of_range(const fbs_params &p, uint64_t D) {
     if (bits > 63.9 || bits - 32.0 > 31.9) return "key-switch accumulator would overflow";   // whole sum in 64 bits; high-word partial sums in 32
     return nullptr;
 }
-// ... and whether a kernel is built for the set: FBS_OK or FBS_E_INVALID (text in ctx->err).  fbs_ctx_create asks after host_ctx_init.
+// ... and whether a kernel is built for the set: null, or why not (the client library asks this directly: a set the GPU library
+// refuses is refused there too) ...
+inline const char *kernel_not_built(const fbs_params &p) {
+    if (p.k >= 2 && !glwe_shape_built(p.log_n_poly, p.k))
+        return "GLWE dimensions k >= 2 are built for k = 2, 3, 4 at N = 256 and 512 and k = 2, 3 at N = 1024";
+    if (p.log_n_poly < 8 || p.log_n_poly > 12) return "supported polynomial sizes are N = 256, 512, 1024, 2048, 4096";
+    if (p.bsk_group == 2 && p.k == 1 && (p.log_n_poly < 10 || p.l_bsk > 5))
+        return "two key bits per step (bsk_group = 2) at k = 1 is built for N = 1024, 2048 and 4096, l <= 5";
+    return nullptr;
+}
+// ... as FBS_OK or FBS_E_INVALID (text in ctx->err).  fbs_ctx_create asks after host_ctx_init.
 int check_kernel_built(const fbs_ctx *ctx);
 // the fbs_ctx_tune knob `name`, or null
 int64_t *tune_knob(Tune &t, const std::string &name);

@@ -32,7 +32,7 @@ from __future__ import annotations
 
 import math
 
-from ._native import Params
+from ._client_native import Params
 from .security import MODULUS, MODULUS_BITS
 
 # ---- security floor (constants and sigma_min live in security.py, which has no dependencies) --------------------

@@ -206,7 +206,7 @@ class ServerKey:
 
     @classmethod
     def load(cls, path):
-        from ._native import Params
+        from ._client_native import Params
         d = _load_npz(path, "server_key")
         vals = np.asarray(d["params"], np.int64)
         if vals.shape != (len(_PARAM_FIELDS),):
@@ -492,6 +492,16 @@ def client_choice(env, config: ExecConfig, programs=()):
     return config.params_choice(p, norm2), fuse
 
 
+def _host_client(host):
+    """`Client(host=...)` -> bool: None takes the GPU context where its library is there, the host context where only the client
+    library is"""
+    if host is not None:
+        return bool(host)
+    import os
+    from . import _client_native
+    return not os.path.exists(_client_native.gpu_library_path()) and _client_native.client_library_present()
+
+
 class Client:
     """Holds the secret.  Chooses (parameter set, fuse) for `env` with the rules of `ExecConfig.choose`, keys a context with
     `keygen_seeded`, encrypts inputs to bodies and decrypts outputs.
@@ -500,16 +510,25 @@ class Client:
     p any of them needs and the set `config.params_choice(p, max norm2)` over all of them; tables share rotations only when
     `config.fuse_tables is True`.  With programs=() the choice is `env`'s alone, as before."""
 
-    def __init__(self, env, config: ExecConfig | None = None, programs=(), packing=False):
+    def __init__(self, env, config: ExecConfig | None = None, programs=(), packing=False, host=None):
         """packing=True: the server key also carries a packing key (`Server.run_packed`, `PackedOutputs`), at the parameters
         `params.packing_choice` gives for the noisiest output of env and of every program; False (default): keys and files are
-        what they were without it."""
-        from ._native import Context
+        what they were without it.
+        host: where the client's own work runs.  True: on the host alone, through the client library (`HostContext`: no GPU, no
+        ROCm); False: on a GPU context (`Context`), as before there was a choice; None (default): the GPU context where
+        libfbsexec.so has been built, the host context where only the client library has.  Keys, inputs and decoded results
+        are the same either way, and so are the files."""
         self.env = env
         self.config = cfg = config or ExecConfig()
         self._low = env.lower()
         self.params, self.fuse_tables = client_choice(env, cfg, programs)
-        self.ctx = Context(self.params, seed=cfg.key_seed(), device=cfg.device, keygen=False)
+        self.host = _host_client(host)
+        if self.host:
+            from ._client_native import HostContext
+            self.ctx = HostContext(self.params, seed=cfg.key_seed(), keygen=False)
+        else:
+            from ._native import Context
+            self.ctx = Context(self.params, seed=cfg.key_seed(), device=cfg.device, keygen=False)
         self.ctx.keygen_seeded()
         self.packing = None
         if packing:
