@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 
 #include "fbs_blind_rotate.hpp"
 
@@ -60,6 +61,32 @@ __global__ __launch_bounds__(1 << LL) void k_polymul(const uint64_t *a, const ui
 }
 
 // ---------------------------------------------------------------------------------------------
+// The rotated read of a step where a wave holds a whole polynomial (PIECES in k_blind_rotate): register m takes word
+// ((m + C) mod E) * LANES behind one per-lane LDS byte address, C the same for the whole wave.  One copy of the E reads per C,
+// the register offsets as immediates of the reads -- written as instructions: left to the compiler, the copies are merged again
+// into one set of reads behind E addresses computed per copy (16 v_add_u32 per step).  The compiler does not count reads it did
+// not issue: rotated_reads_landed() waits for them and must follow before w is used.  All E reads are in flight together, where
+// the compiler's own schedule waited for each in turn.
+template <int BYTES>
+__device__ __forceinline__ void rotated_read(double &w, uint32_t from) {
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(w) : "v"(from), "n"(BYTES) : "memory");
+}
+template <int C, int E, int LANES, int... M>
+__device__ __forceinline__ void rotated_reads(double (&w)[E], uint32_t from, std::integer_sequence<int, M...>) {
+    (rotated_read<((M + C) & (E - 1)) * LANES * 8>(w[M], from), ...);
+}
+template <int E, int LANES, int... C>
+__device__ __forceinline__ void rotated_reads_for(uint32_t c, double (&w)[E], uint32_t from, std::integer_sequence<int, C...>) {
+    ((c == (uint32_t)C ? rotated_reads<C, E, LANES>(w, from, std::make_integer_sequence<int, E>{}) : (void)0), ...);
+}
+template <int E>
+__device__ __forceinline__ void rotated_reads_landed(double (&w)[E]) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int m = 0; m < E; m++) asm volatile("" : "+v"(w[m]));   // (nothing reads w[m] before the wait)
+}
+
+// ---------------------------------------------------------------------------------------------
 // DIG: what the launcher knows about the gadget --
 //   0  nothing;
 //   1  l <= 5: the 2l lazy products (each below 0.8 q; below 1.2 q after the fused opening of 3) that enter the inverse
@@ -91,13 +118,18 @@ __global__ __launch_bounds__((2 << LL) * FPW) __attribute__((amdgpu_waves_per_eu
     // first level peeled off the loop (it assigns the sums instead of adding to zeros): pays where registers allow
     constexpr bool PEEL = ONE_LEVEL || TWO_LEVELS || LL <= FBS_PEEL_MAX_LL;
     constexpr int N = W::N, E = W::E, LANES = W::LANES;
-    __shared__ double lds_all[FPW * 2 * 2 * N];   // [bootstrap][component][ping-pong][N]
+    // PIECES: a wave holds a whole polynomial, so the rotation X^r of a step splits into a lane part (r mod 64) and a
+    // register part (r / 64) that is the same for the whole wave (the step loop below).  Every component's region then
+    // starts with a guard slot of LANES words for the lanes whose lane part borrows from the register part.
+    constexpr bool PIECES = LL == 6;
+    constexpr int GUARD = PIECES ? LANES : 0, REGION = GUARD + 2 * N;
+    __shared__ double lds_all[FPW * 2 * REGION];   // [bootstrap][component][guard | ping-pong][N]
     const uint32_t sub = threadIdx.x >> (LL + 1);          // which bootstrap of the workgroup
     const uint32_t comp = __builtin_amdgcn_readfirstlane((threadIdx.x >> LL) & 1u);        // GLWE component owned by this thread: 0 = mask, 1 = body
     const uint32_t t = threadIdx.x & (LANES - 1);
-    double *lds = lds_all + sub * (2 * 2 * N);
-    double *mine = lds + comp * 2 * N;
-    double *theirs = lds + (comp ^ 1u) * 2 * N;
+    double *lds = lds_all + sub * (2 * REGION) + GUARD;
+    double *mine = lds + comp * REGION;
+    double *theirs = lds + (comp ^ 1u) * REGION;
     typename W::Xchg xc{mine, 0};
     Twiddles twf(a.tw_fwd + W::LANE_TABLE_OFFSET, a.tw_fwd), twi(a.tw_inv + W::LANE_TABLE_OFFSET, a.tw_inv);
     if constexpr (LL <= FBS_ONE_BUFFER_MAX_LL) {
@@ -111,7 +143,7 @@ __global__ __launch_bounds__((2 << LL) * FPW) __attribute__((amdgpu_waves_per_eu
         for (int m = 0; m < E; m++) table[t + (uint32_t)LANES * m] = src[t + (uint32_t)LANES * m];
         __syncthreads();
         twf.lane = lds + N;
-        twi.lane = lds + 3 * N;
+        twi.lane = lds + REGION + N;
     }
 
     // a workgroup past the end of an odd batch repeats the last bootstrap (its waves must keep meeting the others at
@@ -180,18 +212,44 @@ __global__ __launch_bounds__((2 << LL) * FPW) __attribute__((amdgpu_waves_per_eu
             // both the store and the rotated read walk consecutive words across the lanes: no swizzle needed here
 #pragma unroll
             for (int m = 0; m < E; m++) buf[t + (uint32_t)LANES * m] = acc[m];
-            W::sync();
-            const uint32_t from = (t - r) & (2u * N - 1u);   // coefficient t of X^r * ACC is +-ACC[(t - r) mod 2N]
+            // Signed representatives, not canonical ones: the rounding below treats q as 2^46, an error proportional
+            // to the value -- of one sign on [0, q) (it then adds up coherently through the key bits), symmetric
+            // here.  v and acc are centred, so the difference d = v - acc in (-q, q) needs no reduction of its own.
+            if constexpr (PIECES) {
+                // Coefficient t + 64 m of X^r * ACC is +-ACC[(t + 64 m - r) mod 2N].  With r = 64 rh + rl that is lane
+                // t - rl of register m - rh, read mod 2E: bits below E = the register, bit E = the sign -- both the same for
+                // every lane of the wave, so they are scalar arithmetic, and a lane supplies ONE address: word t - rl of the
+                // buffer.  Lanes t < rl land one register lower (64 words back) by themselves; where that leaves the buffer
+                // (register 0 -> register 2E - 1 = minus register E - 1, against the sign of the other lanes) they find the
+                // guard slot in front of it, which holds -ACC's last register.  The sign is a factor +-1.0 of the
+                // subtraction, one exact FMA in the place of the add: no vector instruction per coefficient for the rotation.
+                // (Measured and not kept: +-scale * w + (offset - scale * acc), the second FMA issued under the reads -- the
+                // same count, 8.764 against 8.750 ms per launch; profiles/headline_rotation_diet.)
+                constexpr int LOGE = LOGN - LL;
+                buf[(int)t - LANES] = -acc[E - 1];
+                W::sync();
+                const uint32_t first = (0u - (r >> LL)) & (uint32_t)(2 * E - 1);   // the register (mod 2E) that register 0 reads
+                const uint32_t from = (uint32_t)(uintptr_t)buf + 8u * (t - (r & (uint32_t)(LANES - 1)));   // LDS byte address (in the guard slot where t < rl)
+                double w[E];
+                rotated_reads_for<E, LANES>(first & (uint32_t)(E - 1), w, from, std::make_integer_sequence<int, E>{});
+                rotated_reads_landed(w);
 #pragma unroll
-            for (int m = 0; m < E; m++) {
-                const uint32_t idx = from + (uint32_t)LANES * m;   // < 3N: bit LOGN = sign, bits below = position
-                const double w = buf[idx & (N - 1)];
-                const double v = __hiloint2double(__double2hiint(w) ^ (int)((idx << (31 - LOGN)) & 0x80000000u), __double2loint(w));
-                // Signed representatives, not canonical ones: the rounding below treats q as 2^46, an error proportional
-                // to the value -- of one sign on [0, q) (it then adds up coherently through the key bits), symmetric
-                // here.  v and acc are centred, so the difference needs no reduction of its own.
-                const double d = v - acc[m];                     // in (-q, q)
-                digits[m] = (uint32_t)__builtin_fma(d, round_scale, round_offset) ^ sign_bits;   // truncation = floor, < 3 * 2^(l*beta)
+                for (int m = 0; m < E; m++) {
+                    const double sign = __hiloint2double((int)(0x3FF00000u | (((first + (uint32_t)m) << (31 - LOGE)) & 0x80000000u)), 0);
+                    const double d = __builtin_fma(w[m], sign, -acc[m]);
+                    digits[m] = (uint32_t)__builtin_fma(d, round_scale, round_offset) ^ sign_bits;   // truncation = floor, < 3 * 2^(l*beta)
+                }
+            } else {
+                W::sync();
+                const uint32_t from = (t - r) & (2u * N - 1u);   // coefficient t of X^r * ACC is +-ACC[(t - r) mod 2N]
+#pragma unroll
+                for (int m = 0; m < E; m++) {
+                    const uint32_t idx = from + (uint32_t)LANES * m;   // < 3N: bit LOGN = sign, bits below = position
+                    const double w = buf[idx & (N - 1)];
+                    const double v = __hiloint2double(__double2hiint(w) ^ (int)((idx << (31 - LOGN)) & 0x80000000u), __double2loint(w));
+                    const double d = v - acc[m];
+                    digits[m] = (uint32_t)__builtin_fma(d, round_scale, round_offset) ^ sign_bits;   // truncation = floor, < 3 * 2^(l*beta)
+                }
             }
         }
 
