@@ -66,7 +66,11 @@ typedef struct fbs_params {
     uint32_t bsk_group;  /* key bits consumed per blind-rotation step: 0 or 1 = one   */
                          /* (n CMUX steps); 2 = two ("multi-bit": n/2 steps on a     */
                          /* bundle of three GGSW samples per pair of key bits; n even)*/
-    uint32_t reserved;   /* 0                                                       */
+    union {              /* noise sampler of every key and fresh encryption (RANDOMNESS GRADE below):   */
+        uint32_t sampler;    /* 0 = Irwin-Hall(12), reproducible / test-grade, the default; 1 = rounded     */
+                             /* Gaussian; anything else is refused (FBS_E_INVALID)                          */
+        uint32_t reserved;   /* the field's name before it had a meaning: sources that set it to 0 compile  */
+    };
 } fbs_params;
 
 /* Polynomial sizes.  fbs_params carries log2 N: the ring is Z_q[X]/(X^N + 1) with N a power of two (this build:
@@ -94,9 +98,26 @@ typedef struct fbs_prog fbs_prog;
  * production keys, whatever noise the parameter set carries.  fbs_ctx_create_seeded
  * keys the generator with 32 caller-supplied bytes (e.g. from the OS) and mixes the
  * parameter set into the derivation, so that two parameter sets under one seed
- * share no key material.  In BOTH forms the noise sampler is an integer
- * Irwin-Hall(12) stand-in for a discrete Gaussian (bounded at 6 sigma): test-grade.
- * A deployment that needs more brings its own keys with fbs_import_keys. */
+ * share no key material.
+ *
+ * The noise of every key row and every fresh encryption comes from the sampler
+ * fbs_params.sampler names, in BOTH forms, on the host and on the device alike:
+ *   0  an integer Irwin-Hall(12) stand-in for a discrete Gaussian: a sum of twelve
+ *      uniform 32-bit terms, bounded at 6 sigma, excess kurtosis -0.1.  Reproducible,
+ *      test-grade, and the DEFAULT: the oracle and the committed known-answer tests
+ *      pin its streams word for word.  Making 1 the default is a later decision.
+ *   1  a rounded Gaussian: Box-Muller in double precision (the library's own ln, sin
+ *      and cos, bit-identical on host and device, z to better than 2^-46 relative)
+ *      on 128 + 53 bits of the ChaCha20 stream keyed from the caller's seed -- with
+ *      fbs_ctx_create_seeded, the caller's 32 bytes -- scaled by sigma and rounded to
+ *      the nearest integer, ties to even.  Its tail reaches sqrt(2 128 ln 2) = 13.3
+ *      sigma.  It is NOT constant-time (it branches on its random words), NOT a
+ *      certified discrete Gaussian (a continuous Gaussian evaluated in doubles and
+ *      rounded; no bound on its statistical or Renyi distance from one is claimed),
+ *      and it has NOT been audited.  sigma is accepted up to q.
+ * A sampler-1 context under fbs_ctx_create_seeded shares no key material with its
+ * sampler-0 twin (the sampler is mixed into the derivation when it is not 0).  A
+ * deployment that needs more than either brings its own keys with fbs_import_keys. */
 #define FBS_DEVICE_NONE (-1)   /* `device` of a context of the client library (below); libfbsexec.so refuses it like any ordinal it has no GPU for */
 int fbs_ctx_create(const fbs_params *params, uint64_t seed, int device, fbs_ctx **out);
 int fbs_ctx_create_seeded(const fbs_params *params, const uint8_t seed[32], int device, fbs_ctx **out);
@@ -602,6 +623,13 @@ int fbs_debug_polymul(fbs_ctx *ctx, const uint64_t *a, const uint64_t *b, uint64
  * NULL); out[i] is the RAW result as an integer -- the exact representative, not its residue.  op: 0 fp_mulmod(x, w),
  * 1 fp_mulmod_exact(x, w), 2 fp_center(x), 3 fp_canon(x), 4 fp_canon_near(x), 5 fp_to_u64(fp_from_u64(x)) (0 <= x < 2^52). */
 int fbs_debug_field(fbs_ctx *ctx, int op, const int64_t *x, const int64_t *w, size_t count, int64_t *out);
+/* The rounded Gaussian (sampler 1) alone, on raw windows a test supplies -- edge inputs no ChaCha20 stream would hit: out[i] = the
+ * sample of the six words words[6 i .. 6 i + 5] at standard deviation `sigma` (<= q, else FBS_E_INVALID; at most 2^26 windows).
+ * Both work whatever the context's own sampler.  fbs_debug_gauss runs on the host and reads no context (ctx may be NULL; it only
+ * takes the error text); fbs_debug_gauss_dev runs one kernel over `count` on device arrays, asynchronous on `stream`, and returns
+ * the same words.  libfbsexec.so only. */
+int fbs_debug_gauss(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint64_t sigma, int64_t *out);
+int fbs_debug_gauss_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint64_t sigma, int64_t *d_out, void *stream);
 /* Static text, no GPU needed: one line per transform variant some blind-rotation kernel instantiates, made from the lists the
  * kernels are instantiated from:
  *   "class=<PolyNtt|SplitNtt|WavesNtt|LaneNtt256|LaneNtt512> logn=<log2 N> lanes=<threads per polynomial> dir=forward first=<FIRST>[ np=<NP>]"

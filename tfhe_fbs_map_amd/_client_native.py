@@ -27,6 +27,21 @@ DEVICE_NONE = -1   # FBS_DEVICE_NONE
 
 RANDOMNESS_GRADE = ("test-grade: ChaCha20 streams keyed by the context seed; noise = integer Irwin-Hall(12) stand-in for a discrete "
                     "Gaussian, bounded at 6 sigma.  Bring keys made with a production sampler through Context.import_keys")
+# what Params.sampler = 1 / ExecConfig(sampler="gaussian") draws instead (include/fbs_exec.h, RANDOMNESS GRADE); sampler 0, the text
+# above, stays the default: the oracle and the known-answer tests pin its streams
+GAUSSIAN_SAMPLER_GRADE = ("opt-in: a double-precision rounded Gaussian (Box-Muller on the ChaCha20 stream keyed from the caller's 32 "
+                          "bytes, rounded to the nearest integer, tail to 13.3 sigma), bit-identical on host and GPU; not constant-time, "
+                          "not a certified discrete Gaussian, not audited")
+SAMPLERS = {"irwin_hall": 0, "gaussian": 1}
+
+
+def sampler_id(sampler):
+    """0 / 1 or their names "irwin_hall" / "gaussian" -> fbs_params.sampler"""
+    if isinstance(sampler, str):
+        if sampler not in SAMPLERS:
+            raise ValueError(f"sampler is one of {sorted(SAMPLERS)}, not {sampler!r}")
+        return SAMPLERS[sampler]
+    return int(sampler)
 
 
 class FbsError(RuntimeError):
@@ -38,7 +53,7 @@ class FbsError(RuntimeError):
 class _Params(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in
                 ("n", "log_n_poly", "k", "l_bsk", "beta_bsk", "t_ksk", "gamma_ksk", "p_msg")] + \
-               [("sigma_lwe", C.c_uint64), ("sigma_glwe", C.c_uint64), ("bsk_group", C.c_uint32), ("reserved", C.c_uint32)]
+               [("sigma_lwe", C.c_uint64), ("sigma_glwe", C.c_uint64), ("bsk_group", C.c_uint32), ("sampler", C.c_uint32)]
 
 
 def _ptr(a):
@@ -67,6 +82,7 @@ class Params:
     sigma_lwe: int | None = None      # key-switching-key noise, absolute units of 1/q
     sigma_glwe: int | None = None     # bootstrapping-key and fresh-input noise
     bsk_group: int = 1                # key bits per blind-rotation step: 1, or 2 (n/2 steps on bundles of 3 GGSW samples)
+    sampler: int = 0                  # noise sampler: 0 Irwin-Hall (reproducible / test-grade, the default), 1 rounded Gaussian
 
     def __post_init__(self):
         if self.sigma_lwe is None:
@@ -107,7 +123,7 @@ class Params:
         return Params(**d)
 
     def to_c(self):
-        return _Params(reserved=0, **asdict(self))
+        return _Params(**asdict(self))
 
     def bytes_per_fbs(self):
         """Algorithmic bytes one FBS must consume: every
@@ -204,7 +220,7 @@ def client_library_present():
 class _GpuLibraryMissing(types.ModuleType):
     """Stands in for `_native` where the package was imported with the client library alone: what a client needs resolves to
     this module's definitions, anything else raises the ImportError that importing `_native` itself raises there."""
-    _SHARED = ("RANDOMNESS_GRADE", "FbsError", "Params", "_Params", "_c", "_ptr", "MODULUS", "MODULUS_BITS", "sigma_min")
+    _SHARED = ("RANDOMNESS_GRADE", "GAUSSIAN_SAMPLER_GRADE", "SAMPLERS", "sampler_id", "FbsError", "Params", "_Params", "_c", "_ptr", "MODULUS", "MODULUS_BITS", "sigma_min")
 
     def __getattr__(self, name):
         if name in self._SHARED:

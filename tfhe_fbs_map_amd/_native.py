@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("FBS_LIB") or os.path.join(_HERE, "libfbsexec.so")   #
 
 from .security import MODULUS, MODULUS_BITS, sigma_min      # noqa: E402,F401
 # what a client shares with this module lives in `_client_native`, which needs neither this library nor a GPU
-from ._client_native import RANDOMNESS_GRADE, FbsError, Params, _Params, _c, _ptr, gpu_library_missing      # noqa: E402,F401
+from ._client_native import GAUSSIAN_SAMPLER_GRADE, RANDOMNESS_GRADE, SAMPLERS, FbsError, Params, _Params, _c, _ptr, gpu_library_missing      # noqa: E402,F401
 
 
 class _Layout(C.Structure):
@@ -162,6 +162,8 @@ def _load():
         "fbs_debug_polymul": (i32, [vp, vp, vp, vp]),
         "fbs_debug_raise": (i32, [vp, i32]),
         "fbs_debug_field": (i32, [vp, i32, vp, vp, sz, vp]),
+        "fbs_debug_gauss": (i32, [vp, vp, sz, u64, vp]),
+        "fbs_debug_gauss_dev": (i32, [vp, vp, sz, u64, vp, vp]),
         "fbs_debug_transform_list": (C.c_char_p, []),
         "fbs_debug_transform": (i32, [vp, C.c_char_p, vp, vp, sz]),
         "fbs_searcher_create": (i32, [i32, C.POINTER(vp)]),
@@ -188,7 +190,7 @@ EXPORTED_SYMBOLS = (
     "fbs_searcher_create", "fbs_searcher_destroy", "fbs_searcher_last_error", "fbs_searcher_last_kernel_ms",
     "fbs_search_lincomb_coefs", "fbs_eval", "fbs_eval_dev", "fbs_eval_messages", "fbs_program_layout", "fbs_program_level", "fbs_program_io_slots",
     "fbs_level_lincomb_dev", "fbs_level_bootstrap_dev", "fbs_level_scatter_dev", "fbs_profile_enable", "fbs_profile_kernel", "fbs_kernel_catalog", "fbs_profile_kernels", "fbs_profile_read", "fbs_sync", "fbs_debug_polymul", "fbs_debug_raise",
-    "fbs_debug_field", "fbs_debug_transform_list", "fbs_debug_transform",
+    "fbs_debug_field", "fbs_debug_transform_list", "fbs_debug_transform", "fbs_debug_gauss", "fbs_debug_gauss_dev",
     "fbs_keygen_seeded", "fbs_seeded_key_sizes", "fbs_export_seeded_keys", "fbs_import_seeded_keys", "fbs_encrypt_seeded",
     "fbs_encrypt_seeded_fresh", "fbs_encrypt_seeded_dev", "fbs_encrypt_seeded_fresh_dev", "fbs_expand_seeded",
     "fbs_expand_seeded_dev", "fbs_eval_seeded",
@@ -444,6 +446,17 @@ class DeviceState:
         self.close()
 
 
+def debug_gauss(words, sigma):
+    """The host's rounded Gaussian (sampler 1) of windows of six uint64 words [count][6] at standard deviation sigma -> int64 [count]
+    (fbs_debug_gauss: no context, no GPU)."""
+    words = _c(words, np.uint64).reshape(-1, 6)
+    out = np.empty(words.shape[0], np.int64)
+    rc = lib.fbs_debug_gauss(None, _ptr(words), words.shape[0], int(sigma), _ptr(out))
+    if rc != 0:
+        raise FbsError(rc, lib.fbs_last_error(None).decode())
+    return out
+
+
 class Context:
     """One GPU, one parameter set, one key set."""
 
@@ -453,7 +466,8 @@ class Context:
           oracle can be keyed identically.  Not a way to make production keys.
         * None or 32 bytes: fbs_ctx_create_seeded -- 256 bits (None: from os.urandom) with the parameter set mixed into the
           derivation.
-        Either way the noise sampler is a test-grade stand-in for a discrete Gaussian (`RANDOMNESS_GRADE`); a deployment
+        Either way the noise sampler is the one `params.sampler` names: 0, the default, a test-grade stand-in for a discrete
+        Gaussian (`RANDOMNESS_GRADE`); 1 a rounded Gaussian (`GAUSSIAN_SAMPLER_GRADE`: not certified, not audited).  A deployment
         that needs more brings its own keys with `import_keys`.  keygen=False leaves the context without keys (for
         `import_keys`)."""
         self.params = params
@@ -827,6 +841,18 @@ class Context:
         out = np.empty_like(x)
         self._check(lib.fbs_debug_field(self._h, self.DEBUG_FIELD_OPS.index(op), _ptr(x), _ptr(w), x.size, _ptr(out)))
         return out
+
+    def debug_gauss_dev(self, words, sigma):
+        """The device's rounded Gaussian (sampler 1) of windows of six uint64 words [count][6] at standard deviation sigma -> int64
+        [count], whatever the context's own sampler (fbs_debug_gauss_dev; `debug_gauss` is the host's)."""
+        import torch
+        words = _c(words, np.uint64).reshape(-1, 6)
+        dev = torch.device("cuda", self.device)
+        d_words = torch.from_numpy(words.view(np.int64)).to(dev)
+        d_out = torch.empty(words.shape[0], dtype=torch.int64, device=dev)
+        self._check(lib.fbs_debug_gauss_dev(self._h, d_words.data_ptr(), words.shape[0], int(sigma), d_out.data_ptr(), None))
+        self.sync()
+        return d_out.cpu().numpy()
 
     def debug_transform(self, variant, values):
         """One transform variant (a line of debug_transform_list) on [polys][N] int64 values, unreduced in and out."""

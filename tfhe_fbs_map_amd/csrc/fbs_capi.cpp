@@ -1985,6 +1985,22 @@ int fbs_debug_transform(fbs_ctx *ctx, const char *variant, const int64_t *in, in
     return dev_debug_transform(ctx, variant, in, out, polys);
 } FBS_API_CATCH(ctx)
 
+// test hooks of the rounded Gaussian (fbs_sampler.hpp) on raw windows of words, whatever the context's own sampler: on the host
+// (no context needed: the sampler has no state, ctx only takes the error text) and on the device with one thread per window
+int fbs_debug_gauss(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint64_t sigma, int64_t *out) try {
+    if (const char *why = debug_gauss_refused(words, count, sigma, out)) return set_error(ctx, FBS_E_INVALID, why);
+    host_debug_gauss(words, count, sigma, out);
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_debug_gauss_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint64_t sigma, int64_t *d_out, void *stream) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (const char *why = debug_gauss_refused(d_words, count, sigma, d_out)) return set_error(ctx, FBS_E_INVALID, why);
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_debug_gauss(ctx, d_words, count, sigma, d_out, pick(ctx, stream));
+} FBS_API_CATCH(ctx)
+
 // test hook: raise inside an entry point what a host allocation or a library call could raise, to show the barrier holds
 // (kind 0: std::bad_alloc, 1: std::length_error, 2: std::runtime_error, 3: a non-standard exception; anything else: no throw)
 int fbs_debug_raise(fbs_ctx *ctx, int kind) try {

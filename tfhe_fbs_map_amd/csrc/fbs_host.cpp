@@ -11,6 +11,7 @@
 
 #include "fbs_internal.hpp"
 #include "fbs_chacha.hpp"
+#include "fbs_sampler.hpp"
 #include "fbs_compact.hpp"
 #include "fbs_pack.hpp"
 
@@ -39,11 +40,14 @@ RandKey rand_key_derive(const uint8_t seed[32], const fbs_params &p) {
     uint64_t h = 0xcbf29ce484222325ull;   // FNV-1a over the fields that define the key material
     const uint64_t fields[] = {p.n, p.log_n_poly, p.k, p.l_bsk, p.beta_bsk, p.t_ksk, p.gamma_ksk, p.p_msg, p.sigma_lwe, p.sigma_glwe,
                                p.bsk_group == 2 ? 2u : 1u};
-    for (uint64_t f : fields)
+    auto mix = [&h](uint64_t f) {
         for (int b = 0; b < 8; b++) {
             h ^= (f >> (8 * b)) & 0xff;
             h *= 0x100000001b3ull;
         }
+    };
+    for (uint64_t f : fields) mix(f);
+    if (p.sampler) mix(p.sampler);   // (only then: the derivations of sampler 0 stay what they were)
     uint64_t blk[8];
     chacha_block(master.w, (0xFFull << 56) | (h & 0x00FFFFFFFFFFFFFFull), 0, blk);
     RandKey k;
@@ -64,12 +68,24 @@ void rand_words(const RandKey &seed, uint64_t stream, uint64_t idx0, uint64_t *d
     }
 }
 
-// sample idx of a stream: irwin_hall_sample (fbs_chacha.hpp) of its words 6 idx .. 6 idx + 5; no draw when sigma is 0
-int64_t noise_sample(const RandKey &seed, uint64_t stream, uint64_t idx, uint64_t sigma) {
+// sample idx of a stream: the sampler (fbs_sampler.hpp: 0 irwin_hall_sample, 1 gauss_sample) applied to its words 6 idx .. 6 idx + 5;
+// no draw when sigma is 0
+int64_t noise_sample(const RandKey &seed, uint64_t stream, uint64_t idx, uint64_t sigma, uint32_t sampler) {
     if (!sigma) return 0;
     uint64_t w[6];
     rand_words(seed, stream, idx * 6, w, 6);
-    return irwin_hall_sample(w, sigma);
+    return sample_window(sampler, w, sigma);
+}
+
+const char *debug_gauss_refused(const void *words, size_t count, uint64_t sigma, const void *out) {
+    if (count && (!words || !out)) return "debug_gauss: null array";
+    if (count > ((size_t)1 << 26)) return "debug_gauss: too many windows";
+    if (sigma > FQ) return "debug_gauss: sigma above q";
+    return nullptr;
+}
+
+void host_debug_gauss(const uint64_t *words, size_t count, uint64_t sigma, int64_t *out) {
+    for (size_t i = 0; i < count; i++) out[i] = gauss_sample(words + 6 * i, sigma);
 }
 
 // Worker threads of parallel_for: OMP_NUM_THREADS when it is set to a positive number (the usual way a machine tells a process how
@@ -116,6 +132,9 @@ int host_ctx_init(fbs_ctx *ctx, const fbs_params *params, uint64_t seed, const u
         return set_error(ctx, FBS_E_INVALID, "parameter out of range");
     if (p.bsk_group > 2 || (p.bsk_group == 2 && (p.n & 1)))
         return set_error(ctx, FBS_E_INVALID, "bsk_group is 0, 1 or 2, and 2 needs an even n");
+    if (p.sampler > SAMPLER_GAUSS) return set_error(ctx, FBS_E_INVALID, "sampler is 0 (Irwin-Hall) or 1 (rounded Gaussian)");
+    if (p.sampler == SAMPLER_GAUSS && (p.sigma_lwe > FQ || p.sigma_glwe > FQ))
+        return set_error(ctx, FBS_E_INVALID, "the rounded Gaussian takes standard deviations up to q");
     ctx->N = 1u << p.log_n_poly;
     ctx->D = p.k * ctx->N;
     ctx->rows = (p.k + 1) * p.l_bsk;
@@ -184,7 +203,7 @@ void host_keygen(fbs_ctx *ctx) {
             uint64_t *row = ctx->bsk.data() + r * row_words;
             uint64_t *body = row + (size_t)k * N;
             for (uint32_t j = 0; j < N; j++)
-                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_BSK_NOISE, r), j, p.sigma_glwe));
+                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_BSK_NOISE, r), j, p.sigma_glwe, p.sampler));
             for (uint32_t c = 0; c < k; c++) {
                 uint64_t *a = row + (size_t)c * N;
                 rand_words(ctx->rkey, stream_id(DOM_BSK_MASK, r), (uint64_t)c * N, a, N);
@@ -207,7 +226,7 @@ void host_keygen(fbs_ctx *ctx) {
             uint32_t j = (uint32_t)(r / t), v = (uint32_t)(r % t);
             uint64_t *row = ctx->ksk.data() + r * (n + 1);
             rand_words(ctx->rkey, stream_id(DOM_KSK_MASK, r), 0, row, n);
-            uint64_t b = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_KSK_NOISE, r), 0, p.sigma_lwe));
+            uint64_t b = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_KSK_NOISE, r), 0, p.sigma_lwe, p.sampler));
             for (uint32_t i = 0; i < n; i++) {
                 row[i] = fq_fold(row[i]);
                 if (ctx->sk_lwe[i]) b = fq_add(b, row[i]);
@@ -252,7 +271,7 @@ void host_keygen_seeded(fbs_ctx *ctx) {
             const uint32_t rr = (uint32_t)(r % rows), comp = rr / l, lv = rr % l;
             uint64_t *body = bsk_bodies.data() + r * N;
             for (uint32_t j = 0; j < N; j++)
-                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SBSK_NOISE, r), j, p.sigma_glwe));
+                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SBSK_NOISE, r), j, p.sigma_glwe, p.sampler));
             for (uint32_t c = 0; c < k; c++) {
                 rand_words(ctx->mask_key, stream_id(DOM_SBSK_MASK, r), (uint64_t)c * N, a.data(), N);
                 for (uint32_t j = 0; j < N; j++) a[j] = fq_fold(a[j]);
@@ -271,7 +290,7 @@ void host_keygen_seeded(fbs_ctx *ctx) {
         for (size_t r = r0; r < r1; r++) {
             const uint32_t j = (uint32_t)(r / t), v = (uint32_t)(r % t);
             rand_words(ctx->mask_key, stream_id(DOM_SKSK_MASK, r), 0, a.data(), n);
-            uint64_t b = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SKSK_NOISE, r), 0, p.sigma_lwe));
+            uint64_t b = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SKSK_NOISE, r), 0, p.sigma_lwe, p.sampler));
             for (uint32_t i = 0; i < n; i++)
                 if (ctx->sk_lwe[i]) b = fq_add(b, fq_fold(a[i]));
             if (ctx->sk_glwe[j]) b = fq_add(b, ctx->h[v]);
@@ -312,7 +331,7 @@ void host_encrypt_seeded(const fbs_ctx *ctx, const int64_t *msgs, size_t count, 
         std::vector<uint64_t> mask(D);
         for (size_t i = a; i < b; i++) {
             rand_words(ctx->mask_key, stream_id(DOM_SENC_MASK, nonce0 + i), 0, mask.data(), D);
-            uint64_t body = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SENC_NOISE, nonce0 + i), 0, ctx->p.sigma_glwe));
+            uint64_t body = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SENC_NOISE, nonce0 + i), 0, ctx->p.sigma_glwe, ctx->p.sampler));
             for (uint32_t j = 0; j < D; j++)
                 if (ctx->sk_glwe[j]) body = fq_add(body, fq_fold(mask[j]));
             bodies[i] = fq_add(body, fq_mul(fq_from_i64(msgs[i]), delta));
@@ -395,7 +414,7 @@ void host_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_
         for (size_t i = a; i < b; i++) {
             uint64_t *ct = cts + i * (D + 1);
             rand_words(ctx->rkey, stream_id(DOM_ENC_MASK, nonce0 + i), 0, ct, D);
-            uint64_t body = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_ENC_NOISE, nonce0 + i), 0, ctx->p.sigma_glwe));
+            uint64_t body = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_ENC_NOISE, nonce0 + i), 0, ctx->p.sigma_glwe, ctx->p.sampler));
             for (uint32_t j = 0; j < D; j++) {
                 ct[j] = fq_fold(ct[j]);
                 if (ctx->sk_glwe[j]) body = fq_add(body, ct[j]);
@@ -455,7 +474,7 @@ void host_packing_keygen(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std
             const uint32_t i = (uint32_t)(r / t_p), v = (uint32_t)(r % t_p);
             uint64_t *body = bodies.data() + r * N;
             for (uint32_t j = 0; j < N; j++)
-                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_PACK_NOISE, r), j, ctx->p.sigma_glwe));
+                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_PACK_NOISE, r), j, ctx->p.sigma_glwe, ctx->p.sampler));
             for (uint32_t c = 0; c < k; c++) {
                 rand_words(ctx->mask_key, stream_id(DOM_PACK_MASK, r), (uint64_t)c * N, a.data(), N);
                 for (uint32_t j = 0; j < N; j++) a[j] = fq_fold(a[j]);

@@ -45,7 +45,11 @@ struct RandKey {
 RandKey rand_key_from_seed64(uint64_t seed);
 RandKey rand_key_derive(const uint8_t seed[32], const fbs_params &p);
 void rand_words(const RandKey &key, uint64_t stream, uint64_t idx0, uint64_t *dst, size_t count);
-int64_t noise_sample(const RandKey &key, uint64_t stream, uint64_t idx, uint64_t sigma);
+// `sampler`: fbs_params.sampler of the context the draw belongs to (fbs_sampler.hpp)
+int64_t noise_sample(const RandKey &key, uint64_t stream, uint64_t idx, uint64_t sigma, uint32_t sampler = 0);
+// test hooks of the rounded Gaussian (fbs_debug_gauss, fbs_debug_gauss_dev): what both refuse (null: nothing), and the host loop
+const char *debug_gauss_refused(const void *words, size_t count, uint64_t sigma, const void *out);
+void host_debug_gauss(const uint64_t *words, size_t count, uint64_t sigma, int64_t *out);
 // the public mask key of the seeded path: the first four 64-bit words of chacha_block(key, stream_id(DOM_MASK_KEY, 0), 0),
 // little-endian (ChaCha20 is a PRF keyed by `key`: publishing this block reveals nothing about it)
 RandKey mask_key_of(const RandKey &key);
@@ -401,6 +405,8 @@ int dev_polymul(fbs_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, uint64_t
 int dev_debug_field(fbs_ctx *ctx, int op, const int64_t *x, const int64_t *w, size_t count, int64_t *out);
 const char *debug_transform_list();
 int dev_debug_transform(fbs_ctx *ctx, const char *variant, const int64_t *in, int64_t *out, size_t polys);
+// gauss_sample (fbs_sampler.hpp) of the windows d_words [count][6] -> d_out [count], one thread each (fbs_io.hip); asynchronous on `stream`
+int dev_debug_gauss(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint64_t sigma, int64_t *d_out, hipStream_t stream);
 
 // device encryption / decryption under the big key (fbs_io.hip), word for word host_encrypt / host_decrypt; asynchronous on `stream`
 int dev_upload_secret(fbs_ctx *ctx);     // sk_glwe -> d_sk_bits (after keygen or import)

@@ -5,6 +5,7 @@
 //   k_decrypt   round(phase * 2p / q) mod 2p, what host_decrypt returns
 //   k_encrypt_seeded   the body of host_encrypt_seeded: k_encrypt's sum over the mask of the seeded stream under the public mask
 //               key, noise and message; only the body is stored
+//   k_debug_gauss      the rounded Gaussian alone on windows of words a test supplies (fbs_debug_gauss_dev)
 //   k_expand_seeded    host_expand_seeded: the mask of the seeded stream under the mask key, then the given body.  No key-selected
 //               sum: the kernel needs no secret, and is what an evaluation-only context runs on its inputs
 //
@@ -17,6 +18,7 @@
 #include <algorithm>
 
 #include "fbs_chacha.hpp"
+#include "fbs_sampler.hpp"
 #include "fbs_internal.hpp"
 
 namespace fbs {
@@ -34,6 +36,7 @@ struct EncArgs {
     const uint32_t *sk;              // GLWE secret key, packed bits
     uint32_t D;
     uint64_t delta, sigma;
+    uint32_t sampler;                // fbs_params.sampler: which noise sample (fbs_sampler.hpp); the same for every wave
 };
 
 struct DecArgs {
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(64 * IO_WAVES) void k_encrypt(EncArgs a) {
             if (a.sigma) {
                 uint64_t w[8];
                 chacha_block(a.key.w, stream_id(DOM_ENC_NOISE, nonce), 0, w);   // noise_sample(.., idx 0, ..): words 0 .. 5
-                body = fq_add(body, fq_from_i64(irwin_hall_sample(w, a.sigma)));
+                body = fq_add(body, fq_from_i64(sample_window(a.sampler, w, a.sigma)));
             }
             const int64_t m = a.v.msgs[r * a.v.msg_stride + s];
             ct[D] = fq_add(body, fq_mul(fq_from_i64(m), a.delta));
@@ -125,6 +128,7 @@ struct SeededEncArgs {
     const uint32_t *sk;
     uint32_t D;
     uint64_t delta, sigma;
+    uint32_t sampler;                // fbs_params.sampler: which noise sample (fbs_sampler.hpp); the same for every wave
 };
 
 struct ExpandArgs {
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(64 * IO_WAVES) void k_encrypt_seeded(SeededEncArgs 
             if (a.sigma) {
                 uint64_t w[8];
                 chacha_block(a.key.w, stream_id(DOM_SENC_NOISE, nonce), 0, w);
-                body = fq_add(body, fq_from_i64(irwin_hall_sample(w, a.sigma)));
+                body = fq_add(body, fq_from_i64(sample_window(a.sampler, w, a.sigma)));
             }
             a.bodies[c] = fq_add(body, fq_mul(fq_from_i64(a.msgs[c]), a.delta));
         }
@@ -221,6 +225,7 @@ int dev_encrypt(const fbs_ctx *ctx, const IoView &v, uint64_t nonce0, uint64_t n
     a.D = ctx->D;
     a.delta = 2 * ctx->delta_half;
     a.sigma = ctx->p.sigma_glwe;
+    a.sampler = ctx->p.sampler;
     hipLaunchKernelGGL(k_encrypt, io_grid(total), dim3(64 * IO_WAVES), 0, stream, a);
     FBS_HIP(ctx, hipGetLastError());
     return FBS_OK;
@@ -252,7 +257,24 @@ int dev_encrypt_seeded(const fbs_ctx *ctx, const int64_t *d_msgs, size_t count, 
     a.D = ctx->D;
     a.delta = 2 * ctx->delta_half;
     a.sigma = ctx->p.sigma_glwe;
+    a.sampler = ctx->p.sampler;
     hipLaunchKernelGGL(k_encrypt_seeded, io_grid(count), dim3(64 * IO_WAVES), 0, stream, a);
+    FBS_HIP(ctx, hipGetLastError());
+    return FBS_OK;
+}
+
+// test hook: the rounded Gaussian of `count` windows of six words, one thread each
+__global__ __launch_bounds__(256) void k_debug_gauss(const uint64_t *words, size_t count, uint64_t sigma, int64_t *out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    uint64_t w[6];
+    for (int j = 0; j < 6; j++) w[j] = words[6 * i + j];
+    out[i] = gauss_sample(w, sigma);
+}
+
+int dev_debug_gauss(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint64_t sigma, int64_t *d_out, hipStream_t stream) {
+    if (count == 0) return FBS_OK;
+    hipLaunchKernelGGL(k_debug_gauss, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, d_words, count, sigma, d_out);
     FBS_HIP(ctx, hipGetLastError());
     return FBS_OK;
 }

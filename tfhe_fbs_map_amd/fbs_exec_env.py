@@ -95,7 +95,10 @@ class ExecConfig:
     What "128-bit" covers: the NOISE LEVELS of the chosen set (params.sigma_min).  The randomness behind them is test-grade
     (`_native.RANDOMNESS_GRADE`: ChaCha20 streams, an Irwin-Hall stand-in for the discrete Gaussian); with `seed=None` the
     generator is keyed with 256 bits from the OS and the parameter set is mixed into the derivation, with an int seed it is
-    the reproducible 64-bit form tests use.  A deployment brings its own keys: `Context.import_keys`."""
+    the reproducible 64-bit form tests use.  `sampler="gaussian"` draws every key row and fresh encryption from the rounded
+    Gaussian instead (`_native.GAUSSIAN_SAMPLER_GRADE`: double precision, a 13.3 sigma tail, not constant-time, not a certified
+    discrete Gaussian, not audited); "irwin_hall" stays the default because the oracle and the known-answer tests pin its
+    streams.  A deployment that needs more brings its own keys: `Context.import_keys`."""
     fbs_size: int | None = None
     params: object | None = None          # tfhe_fbs_map_amd.Params (p_msg is overridden by fbs_size)
     seed: int | bytes | None = None       # key seed: int = reproducible (tests); None = 32 bytes from os.urandom, once per ExecConfig
@@ -127,6 +130,9 @@ class ExecConfig:
     # True: `eval` encrypts the inputs and decrypts the outputs on the GPU (Program.eval_messages), only messages cross the bus;
     # False: on the host (ctx.encrypt, Program.eval, ctx.decrypt).  The same results and the same streams either way.
     device_io: bool = True
+    # The noise sampler of the chosen parameter set (`Params.sampler`): "irwin_hall" (0, reproducible / test-grade) or "gaussian" (1).
+    # With explicit `params`, "irwin_hall" leaves their own sampler as it is.
+    sampler: str | int = "irwin_hall"
     _contexts: dict = field(default_factory=dict, repr=False)
     _programs: "OrderedDict" = field(default_factory=OrderedDict, repr=False)
     last_choice: dict | None = field(default=None, repr=False)   # what `choose` decided for the most recent program
@@ -139,20 +145,22 @@ class ExecConfig:
     def params_choice(self, p, norm2=1, glwe_dims=None):
         """The parameter set a program with plaintext modulus p and noise statistic norm2 is evaluated with (`glwe_dims`: the GLWE
         dimensions admitted for it; default: this configuration's)."""
+        from ._client_native import sampler_id
         from .params import REFERENCE_MARGIN, choose_params, params_for
+        sampler = sampler_id(self.sampler)
         if self.params is None and self.reduced_noise:
-            return params_for(p)
+            return params_for(p).replace(sampler=sampler) if sampler else params_for(p)
         if self.params is None:
             floor = None if self.allow_margin_floor is None else min(self.min_margin, self.allow_margin_floor)
             try:
                 return choose_params(p, norm2, min_margin=self.min_margin, security=self.security, floor_margin=floor,
-                                     glwe_dims=tuple(self.glwe_dims if glwe_dims is None else glwe_dims))
+                                     glwe_dims=tuple(self.glwe_dims if glwe_dims is None else glwe_dims), sampler=sampler)
             except ValueError as e:
                 if floor is not None:
                     raise
                 raise ValueError("%s; ExecConfig(allow_margin_floor=%.1f) accepts the reference optimizer's own %.1f sigma "
                                  "(p_error 6.3e-5 per bootstrap)" % (e, REFERENCE_MARGIN, REFERENCE_MARGIN)) from None
-        return self.params.replace(p_msg=p)
+        return self.params.replace(p_msg=p, sampler=sampler) if sampler else self.params.replace(p_msg=p)
 
     def context_of(self, prm):
         from . import _native as nat

@@ -302,7 +302,7 @@ def _switch_fits(t, g, N):
 
 def choose_params(p: int, norm2: float = 1.0, min_margin: float = 6.0, security: int | None = 128,
                   sigma: int | None = None, poly_sizes=(9, 10, 11, 12), n_range=(450, 1200, 4),
-                  floor_margin: float | None = None, groups=(1, 2), glwe_dims=(1,)) -> Params:
+                  floor_margin: float | None = None, groups=(1, 2), glwe_dims=(1,), sampler: int = 0) -> Params:
     """Cheapest parameter set (n, N, l, beta, t, gamma and both noises) for plaintext modulus p and squared 2-norm
     `norm2` whose modelled margin is at least `min_margin` standard deviations -- what the reference obtains from its
     patched optimizer for (precision, sq_norm2) (experiments/add_exec_estimates.py:9-16, concrete.patch:21-27,163).
@@ -318,6 +318,8 @@ def choose_params(p: int, norm2: float = 1.0, min_margin: float = 6.0, security:
     k_blind_rotate_glwe (k + 1 waves per bootstrap) and is priced by that kernel's measured cost: k = 3 at N = 512 -- k N = 1536, a
     noise floor between the two k = 1 offers, on 512-point transforms -- is what p <= 7 takes (183-208 k FBS/s in full rounds against
     151-164 k at k = 2, 1.6-1.9 ms per launch of up to one bootstrap per CU against 2.0-2.4).
+    `sampler`: the noise sampler the set names (`Params.sampler`); it is carried through and moves nothing in the search -- both
+    samplers have the standard deviation they are asked for.
     Cost = `bootstrap_cost`.  Raises ValueError when nothing reaches `min_margin`
     (p too large for N <= 4096 at this security level); with `floor_margin` the requirement is first relaxed in steps of
     half a sigma down to that floor."""
@@ -326,7 +328,7 @@ def choose_params(p: int, norm2: float = 1.0, min_margin: float = 6.0, security:
         m = min_margin
         while True:
             try:
-                return choose_params(p, norm2, m, security, sigma, poly_sizes, n_range, None, groups, glwe_dims)
+                return choose_params(p, norm2, m, security, sigma, poly_sizes, n_range, None, groups, glwe_dims, sampler)
             except ValueError:
                 if m <= floor_margin:
                     raise
@@ -369,7 +371,7 @@ def choose_params(p: int, norm2: float = 1.0, min_margin: float = 6.0, security:
                     continue
                 n = int(ns[ok[0]])                          # cost grows with n: the smallest feasible n is the cheapest
                 cand = Params(n=n, log_n_poly=log_n, k=k, l_bsk=l, beta_bsk=beta, t_ksk=t, gamma_ksk=g, p_msg=p,
-                              sigma_lwe=int(round(s_lwe[ok[0]] * q)), sigma_glwe=int(round(s_glwe * q)), bsk_group=group)
+                              sigma_lwe=int(round(s_lwe[ok[0]] * q)), sigma_glwe=int(round(s_glwe * q)), bsk_group=group, sampler=int(sampler))
                 key = (bootstrap_cost(cand), n, l, t)
                 if best is None or key < best[0]:
                     best = (key, cand)

@@ -195,7 +195,13 @@ class ServerKey:
         np.savez(path, kind=np.array("server_key"), format_version=np.array(FORMAT_VERSION),
                  params=np.array([int(prm[f]) for f in _PARAM_FIELDS], np.int64), fuse_tables=np.array(bool(self.fuse_tables)),
                  mask_key=np.frombuffer(self.mask_key, np.uint8), fingerprint=np.frombuffer(self.fingerprint, np.uint8),
-                 bsk_bodies=self.bsk_bodies, ksk_bodies=self.ksk_bodies, **self._packing_fields())
+                 bsk_bodies=self.bsk_bodies, ksk_bodies=self.ksk_bodies, **self._packing_fields(), **self._sampler_field())
+
+    def _sampler_field(self):
+        """the noise sampler of the parameter set, beside the other parameters (a key of sampler 0 is written exactly as before:
+        a file without the field is a sampler-0 key)"""
+        sampler = int(getattr(self.params, "sampler", 0))
+        return dict(sampler=np.array(sampler, np.int64)) if sampler else {}
 
     def _packing_fields(self):
         """the optional packing key of a saved server key (a key without one is written exactly as before)"""
@@ -211,7 +217,7 @@ class ServerKey:
         vals = np.asarray(d["params"], np.int64)
         if vals.shape != (len(_PARAM_FIELDS),):
             raise ValueError("parameter record has the wrong length")
-        prm = Params(**{f: int(v) for f, v in zip(_PARAM_FIELDS, vals)})
+        prm = Params(sampler=int(d["sampler"]) if "sampler" in d else 0, **{f: int(v) for f, v in zip(_PARAM_FIELDS, vals)})
         if d["bsk_bodies"].dtype != np.uint64 or d["ksk_bodies"].dtype != np.uint64:
             raise ValueError("key bodies are uint64 words")
         packing = {}

@@ -5,6 +5,7 @@ N = 1024) folded into one body word.
 
     python tools/host_client_bench.py --client host      # libfbsclient.so alone; runs on a machine without a GPU
     python tools/host_client_bench.py --client gpu       # a GPU context (libfbsexec.so): keygen on its host, encryption on the device
+    python tools/host_client_bench.py --client host --sampler gaussian     # the same with the rounded-Gaussian noise sampler
 
 Each run appends one JSON line to profiles/host_client/<client>.jsonl (--out): seconds per stage (best and median of --repeats
 for the encryption), the parameter set, the thread count the host code sized its pool by, and a checksum of the bodies, which is
@@ -31,6 +32,7 @@ def main():
     ap.add_argument("--samples", type=int, default=1000)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--sampler", choices=("irwin_hall", "gaussian"), default="irwin_hall", help="the noise sampler of the keys and inputs (ExecConfig.sampler)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -43,7 +45,7 @@ def main():
     ins, _ = subsample(rec, args.samples)
 
     t0 = time.perf_counter()
-    client = Client(env, ExecConfig(seed=args.seed), host=args.client == "host")
+    client = Client(env, ExecConfig(seed=args.seed, sampler=args.sampler), host=args.client == "host")
     t1 = time.perf_counter()
     key = client.server_key()
     t2 = time.perf_counter()
@@ -55,7 +57,7 @@ def main():
         enc_s.append(time.perf_counter() - a)
         digest = hashlib.sha256(np.ascontiguousarray(enc.bodies).tobytes()).hexdigest()[:16]
     prm = client.params
-    line = dict(tool="host_client_bench", client=args.client, device_info=client.ctx.device_info, fixture=args.fixture,
+    line = dict(tool="host_client_bench", client=args.client, sampler=args.sampler, device_info=client.ctx.device_info, fixture=args.fixture,
                 samples=args.samples, n_inputs=len(enc.input_names), ciphertexts=int(enc.bodies.size),
                 mask_bytes=int(enc.bodies.size) * prm.big_dim * 8, params=asdict(prm),
                 keygen_s=round(t1 - t0, 4), server_key_export_s=round(t2 - t1, 4),
