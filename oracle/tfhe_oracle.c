@@ -51,7 +51,11 @@ static inline uint64_t gl_reduce(u128 x) {
     return r;
 }
 static inline uint64_t gl_mul(uint64_t a, uint64_t b) { return gl_reduce((u128)a * b); }
-static inline uint64_t gl_from_i64(int64_t v) { return v >= 0 ? (uint64_t)v % Q : Q - ((uint64_t)(-v) % Q); }
+/* canonical for every int64: |v| is taken in unsigned arithmetic (INT64_MIN has no negative), and a negative multiple of q is 0, not q */
+static inline uint64_t gl_from_i64(int64_t v) {
+    if (v >= 0) return (uint64_t)v % Q;
+    return gl_neg(((uint64_t)0 - (uint64_t)v) % Q);
+}
 
 uint64_t orc_gl_mul(uint64_t a, uint64_t b) { return gl_mul(a % Q, b % Q); }
 /* same product by 128-bit division: the unit tests hold the two against each other */

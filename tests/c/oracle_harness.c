@@ -62,6 +62,30 @@ static int run(orc_params p) {
         }
         free(tv0), free(diff);
     }
+    {   /* a linear combination whose coefficients and constant are the ends of int64 and multiples of q: every word canonical,
+         * equal to the sum in 128-bit arithmetic (ciphertext i is all i + 1) */
+        const int64_t coefs[6] = {INT64_MIN, INT64_MAX, -(int64_t)ORC_Q, -2 * (int64_t)ORC_Q, (int64_t)ORC_Q, -1};
+        const int64_t consts[4] = {INT64_MIN, INT64_MAX, -(int64_t)ORC_Q, -1};
+        const uint64_t *srcs[6];
+        __int128 sum = 0;
+        for (int i = 0; i < 6; i++) {
+            for (uint32_t j = 0; j < ctw; j++) out2[(size_t)i * ctw + j] = (uint64_t)i + 1;
+            srcs[i] = out2 + (size_t)i * ctw;
+            sum += (__int128)coefs[i] * (i + 1);
+        }
+        const __int128 q = (__int128)ORC_Q;
+        for (int t = 0; t < 4; t++) {
+            orc_lincomb(c, srcs, coefs, 6, consts[t], one);
+            const __int128 body = sum + (__int128)consts[t] * (__int128)(2 * orc_delta_half(c));
+            if (one[0] != (uint64_t)((sum % q + q) % q) || one[D] != (uint64_t)((body % q + q) % q)) return 11;
+            for (uint32_t j = 0; j < ctw; j++)
+                if (one[j] >= ORC_Q) return 12;
+        }
+        for (int i = 0; i < 6; i++) {                                      /* one term alone: a multiple of q gives the zero word */
+            orc_lincomb(c, srcs + i, coefs + i, 1, 0, one);
+            if (one[0] != (uint64_t)((((__int128)coefs[i] * (i + 1)) % q + q) % q)) return 13;
+        }
+    }
     if (tuned_supported()) {
         tuned_ctx *t = tuned_create(&p, orc_bsk(c), orc_ksk(c));
         if (t) {                                                           /* (NULL: a shape the tuned baseline does not cover) */

@@ -759,3 +759,175 @@ def ks_reached(prm, ksk, rows):
             share = max(max(hi[w * slice_len:(w + 1) * slice_len].sum(axis=(0, 1))) for w in range(waves))
             reached["lanes_hi_wave"] = max(reached["lanes_hi_wave"], share * waves)                        # as a fraction of the whole bound
     return reached
+
+
+# ==== linear combinations and shared-rotation extraction at their bounds (tests/test_level_arithmetic_reference.py, ===============
+# ==== tests/test_gpu_level_arithmetic.py) ==========================================================================================
+# k_lincomb keeps a lazy FP64 sum of products below 0.75 q each, centred after every 16th term; k_multi_extract sums value x word in
+# an int64 on the loader's promise sum |d| < 2^16.  The inputs below drive both to those bounds; everything is Python integers.
+INT64_MAX, INT64_MIN = (1 << 63) - 1, -(1 << 63)
+LC_SHAPES = [(1, 8), (2, 8), (4, 8), (3, 9), (2, 10), (1, 12)]          # (k, log N): ct_words 257, 513, 1025, 1537, 2049, 4097
+LC_TARGET = 49 * Q // 100                                               # |product| of a planted term: floor(0.49 q) - term index
+LC_NONZERO = [1, -1, 3, -3, HALF, -HALF, (Q + 1) // 2, Q - 1, 1 << 40, -(1 << 45), INT64_MAX, INT64_MIN]   # (none is 0 mod q)
+LC_ZERO = [Q, -Q, -2 * Q]                                               # 0 mod q: the product is 0 whatever the word
+LC_CONSTS = [0, 1, -1, 2 * 7 - 1, Q, -Q, INT64_MAX, INT64_MIN]          # (2p - 1 at p = 7)
+LC_SLOTS = 48                                                           # source slots of a launch; an output of more terms repeats them
+# (first slot, terms, constant) per output of a launch: term t reads slot (first + t) % LC_SLOTS.  Slots 0 .. 31 have coefficients
+# that are not 0 mod q, so every output of 16 terms or more opens with 16 planted products of one sign; the outputs of 15 terms and
+# of 48 and 100 run over slots 32 .. 47, where q, -q and -2q sit.  The constants of the outputs of 16 terms or more leave the body
+# column its peak (see lc_replay) at either sign.
+LC_OUTPUTS = [(0, 0, 2 * 7 - 1), (11, 1, -1), (33, 15, INT64_MAX), (0, 16, 1), (0, 17, Q), (0, 31, -Q), (0, 32, 0), (0, 33, -1),
+              (0, 48, INT64_MAX), (0, 100, INT64_MIN), (0, 400, 1)]
+# (400 terms: what shows a centring that is never done -- 196 q of one sign, past the 2^53 = 128 q to which a double holds every
+# integer.  Between 16 and 100 terms the sum stays exact with or without centring, and so does a cadence of 32.)
+
+
+def lc_delta(p=7):
+    """Delta = 2 round(q / 4p): what one unit of a LinearProd's constant adds to the body"""
+    return 2 * ((Q + 2 * p) // (4 * p))
+
+
+def lc_columns(ct_words):
+    """the planted columns: first word, either side of the 256-thread pass, the last mask word, the body"""
+    return [0, 255, 256, ct_words - 2, ct_words - 1]
+
+
+def lc_coefs(n_terms):
+    """coefficient of term (slot) i: twelve fixed ones that are not 0 mod q and four random int64 in every sixteen, the order turned
+    by five from one sixteen to the next; from term 32 on every fifth is q, -q or -2q in turn"""
+    rng = random.Random("lincomb coefficients")
+    out = []
+    for i in range(n_terms):
+        r = rng.randrange(INT64_MIN, INT64_MAX + 1)
+        while r % Q == 0:
+            r = rng.randrange(INT64_MIN, INT64_MAX + 1)
+        pool = LC_NONZERO + [r] * 4
+        c = pool[(i + 5 * (i // 16)) % 16]
+        if i >= 32 and i % 5 == 3:
+            c = LC_ZERO[(i // 5) % 3]
+        out.append(c)
+    return out
+
+
+def planted_lincomb(ct_words, n_terms, sign, seed):
+    """-> (words uint64 [n_terms][ct_words], coefs [n_terms] Python integers).  In the planted columns word j of term i is such that
+    coef_i * word = sign * (LC_TARGET - i) mod q (a coefficient that is 0 mod q keeps its random word); every other word is random
+    canonical, one in eight of them 0, q - 1, (q - 1) / 2 or (q + 1) / 2."""
+    coefs = lc_coefs(n_terms)
+    rng = np.random.default_rng([ct_words, n_terms, sign + 1, seed])
+    words = rng.integers(0, Q, (n_terms, ct_words), dtype=np.uint64)
+    edge = np.array([0, Q - 1, HALF, HALF + 1], np.uint64)[rng.integers(0, 4, words.shape)]
+    words = np.where(rng.integers(0, 8, words.shape) == 0, edge, words)
+    for i, c in enumerate(coefs):
+        if c % Q:
+            words[i, lc_columns(ct_words)] = sign * (LC_TARGET - i) * pow(c % Q, Q - 2, Q) % Q
+    return words, coefs
+
+
+def lc_terms(first, n_terms):
+    """the source slots of an output of LC_OUTPUTS, term by term"""
+    return [(first + t) % LC_SLOTS for t in range(n_terms)]
+
+
+def lc_definition(words, coefs, terms, const, p=7):
+    """THE DEFINITION on Python integers: sum of coef x word over the terms, const x Delta more on the body -> [ct_words] (object)"""
+    w = np.array(words, dtype=object)
+    out = np.zeros(w.shape[1], dtype=object)
+    if terms:
+        out = np.array([coefs[t] for t in terms], dtype=object).dot(w[terms])
+    out[-1] += const * lc_delta(p)
+    return out % Q
+
+
+def lc_replay(words, coefs, terms, const, column, p=7, every=16):
+    """k_lincomb's accumulation of one output word on the exact-integer model of the FP64 unit (fp_mulmod, fp_center above) ->
+    (canonical result, peak |accumulator|).  Asserts what the kernel relies on: every product below 0.75 q, every intermediate an
+    integer below 2^52 (exactly representable, and what fp_to_u64 takes).  every: the centring cadence (the kernel's 16; 0: never)."""
+    acc = exact(const % Q * lc_delta(p) % Q) if column == len(words[0]) - 1 else 0.0      # (the last column is the body)
+    peak = abs(acc)
+    for n, t in enumerate(terms):
+        c = centred(coefs[t])
+        assert abs(c) <= HALF
+        prod = fp_mulmod(exact(int(words[t][column])), exact(c))
+        assert abs(prod) < 0.75 * Q
+        acc = exact(int(acc) + int(prod))
+        peak = max(peak, abs(acc))
+        assert peak < 1 << 52
+        if every and n % every == every - 1:
+            acc = fp_center(acc)
+    return int(fp_canon(acc)), peak
+
+
+# ---- tables cut out of a shared rotation ------------------------------------------------------------------------------------------
+EX_P = 7
+# sum |d| of the difference polynomial: 65534 is the most an evaluable table can have below the loader's limit of 2^16 (the total
+# variation from f(0) round to -f(0) is even), 65536 the least above it
+EX_TABLES = {
+    "at_limit_a": [0, 32767, 0],
+    "at_limit_b": [1, 32767, 1, 1, 1, 1, 1],
+    "over_limit_a": [0, 32767, 0, 1, 0],
+    "over_limit_b": [0, 32768, 0],
+    "negative": [-3, -20000, 5, -1, 0, -7, 2],
+    "c1_long": [0, 9000, -7000, 3, 0, 1, 0, 1, -8999, 7001, -2, 1, 0, 1],       # f(x + p) = 1 - f(x)
+    "small": [0, 1, 2, 3, 2, 1, 0],
+}
+EX_ABS_SUM = {"at_limit_a": 65534, "at_limit_b": 65534, "over_limit_a": 65536, "over_limit_b": 65536, "negative": 40026,
+              "c1_long": 32009, "small": 6}
+
+
+def table_diff(table, N, p=EX_P):
+    """-> (D_F as N Python integers, c): G_j = +-(2 f(round(j p / N)) - c), the sign turning where the index reaches p, and
+    D_F = G (1 - X) / 2 mod X^N + 1"""
+    c = table[0] + table[p] if len(table) > p else 0
+    assert 0 < len(table) <= 2 * p and all(table[i] + table[i + p] == c for i in range(len(table) - p))
+    G = []
+    for j in range(N):
+        x = (2 * j * p + N) // (2 * N)
+        f = (table[x] if x < len(table) else 0) if x < p else table[0]
+        G.append(2 * f - c if x < p else -(2 * f - c))
+    d = [G[j] - G[j - 1] if j else G[0] + G[N - 1] for j in range(N)]
+    assert all(v % 2 == 0 for v in d)
+    return [v // 2 for v in d], c
+
+
+def planted_accumulators(k, N, seed=1):
+    """{name: (k + 1) N canonical words}: all q - 1, all 0, 0 and q - 1 in turn, q - 1 on one polynomial only (the body's when
+    seed is even, the first mask polynomial's when odd), random"""
+    rng = np.random.default_rng([k, N, seed])
+    one = np.zeros((k + 1, N), np.uint64)
+    one[k if seed % 2 == 0 else 0] = Q - 1
+    return {"all q-1": np.full((k + 1) * N, Q - 1, np.uint64), "all 0": np.zeros((k + 1) * N, np.uint64),
+            "alternating": np.array([0, Q - 1] * ((k + 1) * N // 2), np.uint64), "one polynomial": one.reshape(-1),
+            "random": rng.integers(0, Q, (k + 1) * N, dtype=np.uint64)}
+
+
+def extract_definition(acc, diff, post, k, N):
+    """THE DEFINITION on Python integers: every polynomial of the accumulator times D_F mod X^N + 1, then the sample extraction
+    (mask polynomial c gives words P_0, -P_(N-1), .., -P_1; the body is B_0 + post) -> [k N + 1]"""
+    out = []
+    for c in range(k + 1):
+        a = [int(x) for x in acc[c * N:(c + 1) * N]]
+        prod = [0] * N
+        for i, d in enumerate(diff):
+            if d:
+                for m in range(N):
+                    prod[m] += d * a[m - i] if m >= i else -d * a[m + N - i]
+        out += [prod[0]] + [-prod[N - j] for j in range(1, N)] if c < k else [prod[0] + post]
+    return [v % Q for v in out]
+
+
+def extract_kernel_sums(acc, pos, val, k, N):
+    """k_multi_extract's signed 64-bit sum of every output word before its one reduction, statement by statement, from the
+    (position, value) pairs the loader uploads -> [k N + 1] Python integers; asserts that each running sum fits an int64"""
+    D, out = k * N, []
+    for j in range(D + 1):
+        c = j // N
+        jj = j - c * N
+        m = 0 if jj == 0 else N - jj
+        total = 0
+        for at, v in zip(pos, val):
+            term = v * int(acc[c * N + m - at] if m >= at else acc[c * N + m + N - at])
+            total += term if m >= at else -term
+            assert -(1 << 63) <= total < 1 << 63
+        out.append(-total if jj else total)
+    return out

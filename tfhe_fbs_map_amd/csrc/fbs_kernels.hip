@@ -555,6 +555,8 @@ __global__ __launch_bounds__(256) void k_ks_gemm_finish(KsArgs a, KsGemm g, size
 
 // ---------------------------------------------------------------------------------------------
 // linear combination over wire slots: out = sum coef_i * wire_i + const (exact FP64 products, lazy sum)
+// The bounds below are held by tests/test_level_arithmetic_reference.py (a replay on planted worst cases: 16 products of one sign
+// near q/2 between two centrings) and tests/test_gpu_level_arithmetic.py (the same inputs through this kernel, up to 400 terms).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_lincomb(uint64_t *wires, size_t T, size_t s_begin, size_t s_count, uint32_t ct_words,
                                                  const uint32_t *dst, const uint32_t *term_off, const uint32_t *srcs,
@@ -592,6 +594,8 @@ __global__ __launch_bounds__(256) void k_scatter_rows(uint64_t *wires, size_t T,
 // host_build_tv_diff, given as (position, value) pairs.  Coefficient m of X^i * P is P[m - i], negated when it wrapped;
 // the extracted ciphertext holds A'_0, -A'_(N-1), .., -A'_1 and B'_0.  d * word < 2^16 * 2^46 summed in 64 bits (the loader
 // fuses only tables with sum |d| < 2^16), one reduction per output word.  HBM-bound copy work, a few hundred KB per row.
+// tests/test_level_arithmetic_reference.py and tests/test_gpu_level_arithmetic.py hold that bound: tables with sum |d| = 65534 on
+// accumulators of q - 1 throughout, and tables with 65536, which the loader keeps on a rotation of their own.
 __global__ __launch_bounds__(256) void k_multi_extract(const uint64_t *acc_rows, uint64_t *wires, size_t T, size_t s_begin,
                                                        size_t s_count, uint32_t N, uint32_t k, const uint32_t *x_row, const uint32_t *x_table,
                                                        const uint32_t *x_dst, const uint32_t *diff_pos, const int32_t *diff_val,
