@@ -541,6 +541,72 @@ int fbs_state_fetch_packed(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_
 /* the decode on the host, words [fbs_packed_words(count)] -> msgs[count].  FBS_E_STATE on an evaluation-only context. */
 int fbs_decrypt_packed(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs);
 
+/* ---- public-key inputs: encrypt without the secret, expand on the GPU ------------------------------------------------------------
+ * A data owner who is neither the key holder nor the server -- a sensor, a second company, a user of a service somebody else
+ * keyed -- encrypts under a PUBLIC KEY and sends GLWE samples; the server turns them into big-key ciphertexts by sample
+ * extraction, which needs no key at all.  Notation as above: GLWE key S_0 .. S_(k-1) (binary), D = k N, Delta = 2*round(q/4p),
+ * negacyclic ring mod q.
+ *
+ * PUBLIC KEY.  Masks A[r][c], r, c < k: uniform residues under the public mask key (the one the server key carries), on a ChaCha20
+ * domain no other key or ciphertext uses: A[r][c]_j = word c N + j of stream (18, r), folded as every other mask is.  Bodies
+ * P_r = sum_c A[r][c] S_c + E_r, E_r of standard deviation sigma_glwe from the parameter set's sampler (fbs_params.sampler, both
+ * samplers), coefficient j = sample j of stream (19, r) under a 32-byte noise seed the caller passes (the ChaCha20 key itself,
+ * little-endian words).  Only the bodies travel, [k][N] words.  The key is k GLWE encryptions of zero under masks the key holder
+ * does not choose: as hard as the bootstrapping-key rows, dimension k N at sigma_glwe.  NEVER make two public keys for one secret
+ * under one noise seed and different mask keys: their bodies would differ by (A - A') S.
+ *
+ * ENCRYPTION needs no secret.  GLWE sample g of a call takes stream nu = nonce0 + g under the encryptor's own ChaCha20 key, derived
+ * from 32 caller bytes and the parameter set the way fbs_ctx_create_seeded derives a context's:
+ *     u_r (r < k) binary: bit j of u_r = bit (r N + j) mod 64 of word (r N + j) / 64 of stream (20, nu);
+ *     e_c (c <= k) of standard deviation sigma_glwe: coefficient j = sample c N + j of stream (21, nu);
+ *     A'_c = sum_r u_r A[r][c] + e_c  (c < k);     B' = sum_r u_r P_r + e_k + Delta M(X)  mod q.
+ * u is a rank-k binary module secret with noise sigma_glwe, exactly as hard to recover as S itself for every (k, N) this library
+ * builds -- which is why the key is a k x k matrix and not one ring element (one u in R at k = 3, N = 512 would sit at dimension
+ * 512).  The phase is sum_r u_r E_r + e_k - sum_c e_c S_c + Delta M: variance (1 + k N) sigma_glwe^2 (params.public_input_variance),
+ * many orders below one blind rotation's output, so a public-key input enters a program unrefreshed.
+ * IND-CPA only, and malleable like every ciphertext here: nothing proves that a sample is well formed.  The samplers' caveats
+ * (RANDOMNESS GRADE above) apply to E, e and u alike.  Reusing (seed, nonce) reuses u and e: two such samples differ by exactly
+ * Delta (M - M') and leak the difference of their messages.
+ *
+ * WIRE FORMAT.  A sample is [k+1][N] canonical residues in 64-bit words: A'_0 .. A'_(k-1), then B'.  Message j of a call lies at
+ * coefficient j mod N of sample j / N (the packed outputs' rule); `count` messages are G = ceil(count / N) samples back to back;
+ * coefficients past the fill of the last sample carry message 0 and are never extracted.  Messages lie in [0, 2p).
+ *
+ * EXPANSION of message j at coefficient t = j mod N into the big-key ciphertext [D+1]:
+ *     word c N + i = A'_c[t - i] for i <= t,  (q - A'_c[N + t - i]) mod q for i > t (a zero word stays zero);   word D = B'[t].
+ * fbs_decrypt of the result returns the message: the sign convention is the blind rotation's own extraction.
+ *
+ * RULES.  Parameter sets pass the admission of fbs_ctx_create, with its codes and texts.  Body and sample words must be canonical
+ * residues and messages lie in [0, 2p): otherwise FBS_E_INVALID, and nothing is written.  Explicit nonces stay below 2^55 (nonce0 +
+ * G <= 2^55); fresh ones come from an atomic counter of the handle over [2^55, 2^56) (FBS_E_STATE when used up).  count = 0 does
+ * nothing.  The entries up to fbs_pub_expand use no context and no GPU; libfbspublic.so (make -C tfhe_fbs_map_amd/csrc public: a
+ * C++17 compiler, no ROCm) exports exactly those nine, and libfbsexec.so all of them. */
+typedef struct fbs_pub fbs_pub;
+int fbs_pub_key_words(const fbs_params *p, size_t *words);   /* k N */
+/* sk_glwe [k][N] bits, as fbs_export_keys returns them (anything but 0 and 1: FBS_E_INVALID) -> bodies [k][N] */
+int fbs_pub_keygen(const fbs_params *p, const uint8_t mask_key[32], const uint64_t *sk_glwe, const uint8_t noise_seed[32], uint64_t *bodies);
+/* the encryptor's handle: the public key and the key its own randomness is expanded from.  One thread at a time, except that
+ * fbs_pub_encrypt_fresh calls on several threads never share a stream. */
+int fbs_pub_create(const fbs_params *p, const uint8_t mask_key[32], const uint64_t *bodies, const uint8_t seed[32], fbs_pub **out);
+void fbs_pub_destroy(fbs_pub *pub);
+/* text of the last failure on `pub`; NULL: of the thread's last failed entry that takes no handle (creation, keygen, word counts, expansion) */
+const char *fbs_pub_last_error(const fbs_pub *pub);
+int fbs_pub_words(const fbs_params *p, size_t count, size_t *words);   /* ceil(count / N) (k + 1) N */
+int fbs_pub_encrypt(const fbs_pub *pub, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *glwe);
+int fbs_pub_encrypt_fresh(fbs_pub *pub, const int64_t *msgs, size_t count, uint64_t *glwe, uint64_t *nonce0);   /* *nonce0 (may be NULL): the first stream taken */
+/* glwe [fbs_pub_words(count)] -> cts [count][D+1] on the host: the reference the device entries are held to */
+int fbs_pub_expand(const fbs_params *p, const uint64_t *glwe, size_t count, uint64_t *cts);
+/* libfbsexec.so only.  The same on device buffers, asynchronous on `stream` (NULL = the context's own), one kernel (k_expand_public)
+ * that stages each sample's masks in LDS and writes whole ciphertexts, 16 bytes a lane; being device memory, the words cannot be
+ * checked by the host.  Needs no key and no scratch. */
+int fbs_pub_expand_dev(fbs_ctx *ctx, const uint64_t *d_glwe, size_t count, uint64_t *d_cts, void *stream);
+/* Rows [row0, row0 + rows) of a state, flattened [row][sample] (j = r T + s, the order of fbs_state_fetch_packed), from the
+ * G = ceil(rows T / N) samples at `glwe` in HOST memory.  Every word is checked on the host before anything is queued (FBS_E_INVALID,
+ * state untouched); (k + 1) N G words cross the bus into staging that belongs to the context's scratch (repeated calls of one
+ * shape do not grow it) and are expanded on the device into the rows.  Works on evaluation-only contexts and on contexts without
+ * any key.  Blocks until done, as fbs_state_put. */
+int fbs_state_put_public(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *glwe);
+
 /* ---- a loaded program, one level at a time (multi-GPU hosts) -----------------
  * The two independent axes of the reference's eval loop (fbs_exec_env.py:211-223) are the gates
  * of a bootstrap level and the samples.  A host that shards the GATES of a level over several

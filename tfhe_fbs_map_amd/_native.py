@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("FBS_LIB") or os.path.join(_HERE, "libfbsexec.so")   #
 
 from .security import MODULUS, MODULUS_BITS, sigma_min      # noqa: E402,F401
 # what a client shares with this module lives in `_client_native`, which needs neither this library nor a GPU
+from . import _public_native      # noqa: E402
 from ._client_native import GAUSSIAN_SAMPLER_GRADE, RANDOMNESS_GRADE, SAMPLERS, FbsError, Params, _Params, _c, _ptr, gpu_library_missing      # noqa: E402,F401
 
 
@@ -80,7 +81,8 @@ def _load():
         pass
     lib = C.CDLL(LIB_PATH)
     vp, u64, u32, sz, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_size_t, C.c_int
-    sig = {
+    sig = dict(_public_native.SIGNATURES)   # the host entries of "public-key inputs": the same code as libfbspublic.so's
+    sig.update({
         "fbs_poly_size_check": (i32, [u32]),
         "fbs_ctx_create": (i32, [C.POINTER(_Params), u64, i32, C.POINTER(vp)]),
         "fbs_ctx_create_seeded": (i32, [C.POINTER(_Params), vp, i32, C.POINTER(vp)]),
@@ -133,6 +135,8 @@ def _load():
         "fbs_eval_resident": (i32, [vp, vp, vp, vp, sz, u32, vp, vp]),
         "fbs_state_fetch": (i32, [vp, vp, sz, sz, u32, vp]),
         "fbs_state_put": (i32, [vp, vp, sz, sz, vp]),
+        "fbs_pub_expand_dev": (i32, [vp, vp, sz, vp, vp]),
+        "fbs_state_put_public": (i32, [vp, vp, sz, sz, vp]),
         "fbs_tvset_create": (i32, [vp, vp, vp, u32, C.POINTER(vp)]),
         "fbs_tvset_destroy": (None, [vp]),
         "fbs_bootstrap_batch": (i32, [vp, vp, vp, vp, sz, vp]),
@@ -171,7 +175,7 @@ def _load():
         "fbs_searcher_last_error": (C.c_char_p, [vp]),
         "fbs_searcher_last_kernel_ms": (C.c_double, [vp]),
         "fbs_search_lincomb_coefs": (i32, [vp, vp, vp, vp, u32, u32, u32, vp, vp, C.POINTER(i32)]),
-    }
+    })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = the library does not match the header
         fn.restype = res
@@ -199,7 +203,8 @@ EXPORTED_SYMBOLS = (
     "fbs_state_create", "fbs_state_destroy", "fbs_state_info", "fbs_eval_resident", "fbs_state_fetch", "fbs_state_put",
     "fbs_packing_keygen", "fbs_packing_key_sizes", "fbs_export_packing_key", "fbs_import_packing_key", "fbs_packed_words",
     "fbs_pack_dev", "fbs_state_fetch_packed", "fbs_decrypt_packed",
-)
+    "fbs_pub_expand_dev", "fbs_state_put_public",
+) + _public_native.EXPORTED_SYMBOLS
 
 lib = _load()
 
@@ -431,6 +436,18 @@ class DeviceState:
         self.ctx._check(lib.fbs_state_put(self.ctx._h, self._live(), int(row0), cts.shape[0], _ptr(cts)))
         return self
 
+    def put_public(self, glwe, row0=0, rows=None):
+        """public-key samples [ceil(rows * T / N)][k+1][N] (host; `_public_native.Encryptor.encrypt` of the rows' messages flattened
+        [row][sample]) -> rows [row0, row0 + rows), expanded on the GPU (fbs_state_put_public).  Needs no key."""
+        rows = self.rows - int(row0) if rows is None else int(rows)
+        prm = self.ctx.params
+        glwe = _c(glwe, np.uint64).reshape(-1)
+        want = -(-max(0, rows) * self.T // prm.N) * (prm.k + 1) * prm.N
+        if glwe.size != want:
+            raise ValueError(f"{glwe.size} sample words for {rows} rows of {self.T} samples (the parameter set needs {want})")
+        self.ctx._check(lib.fbs_state_put_public(self.ctx._h, self._live(), int(row0), rows, _ptr(glwe)))
+        return self
+
     def close(self):
         if not self.closed and lib is not None:
             lib.fbs_state_destroy(self._h)
@@ -604,6 +621,21 @@ class Context:
 
     def expand_seeded_dev(self, d_bodies, count, nonce0, d_cts, stream=0):
         self._check(lib.fbs_expand_seeded_dev(self._h, d_bodies or None, count, int(nonce0), d_cts or None, stream or None))
+
+    def pub_expand_dev(self, d_glwe, count, d_cts, stream=0):
+        """fbs_pub_expand_dev: public-key samples [ceil(count / N)][k+1][N] at d_glwe -> [count][D+1] ciphertexts at d_cts"""
+        self._check(lib.fbs_pub_expand_dev(self._h, d_glwe or None, count, d_cts or None, stream or None))
+
+    def pub_expand(self, glwe, count):
+        """`pub_expand_dev` on host arrays: samples -> np.ndarray [count][D+1] (the host form is `_public_native.expand`)"""
+        import torch
+        glwe = _c(glwe, np.uint64).reshape(-1)
+        dev = torch.device("cuda", self.device)
+        d_g = torch.from_numpy(glwe.view(np.int64)).to(dev)
+        d_c = torch.empty((max(1, int(count)), self.params.ct_words), dtype=torch.int64, device=dev)
+        self.pub_expand_dev(d_g.data_ptr() if glwe.size else None, int(count), d_c.data_ptr(), None)
+        self.sync()
+        return d_c[:int(count)].cpu().numpy().view(np.uint64)
 
     def reserve(self, max_keyswitches=0, max_shared_rows=0, wire_words=0):
         """Size the scratch up front so that no later `*_dev` call has to grow it (growing blocks): include/fbs_exec.h."""

@@ -2,10 +2,12 @@
 // stream ranges, word counts that must not overflow, the fresh-stream counter, the widths of compact and packed outputs, the
 // packing key's parameters -- in one place, because two libraries serve those entries: libfbsexec.so (fbs_capi.cpp) and the
 // client library libfbsclient.so (fbs_client_capi.cpp).  The same checks in the same order give the same codes and texts, and a
-// refused call moves no counter in either.  Host code, no device in it.
+// refused call moves no counter in either.  The public-key entries (fbs_public.cpp: libfbsexec.so and libfbspublic.so) take their
+// parameter admission from here.  Host code, no device in it.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 
 #include "fbs_compact.hpp"
@@ -16,6 +18,20 @@ namespace fbs {
 
 // what every entry that needs the secret keys says on a context made by fbs_import_seeded_keys
 constexpr const char *EVAL_ONLY = "this context holds evaluation keys only";
+
+// Parameter admission for the entries that take a parameter set and no context (fbs_pub_*): what fbs_ctx_create applies -- the range
+// rules of host_ctx_init, then whether a kernel is built for the set -- with its codes and texts, left as the thread's creation
+// error.  *probe: the host state of a context for the set (N, D, Delta), the caller's to delete.
+inline int params_admitted(const fbs_params *params, fbs_ctx **probe) {
+    if (!params) return set_error(nullptr, FBS_E_INVALID, "null argument");
+    std::unique_ptr<fbs_ctx> ctx(new fbs_ctx);
+    int rc = host_ctx_init(ctx.get(), params, 0, nullptr);
+    if (rc == FBS_OK)
+        if (const char *why = kernel_not_built(ctx->p)) rc = set_error(ctx.get(), FBS_E_INVALID, why);
+    if (rc != FBS_OK) return set_error(nullptr, rc, ctx->err);
+    *probe = ctx.release();
+    return FBS_OK;
+}
 
 // Streams [first, first + count) of [2^55, 2^56) that nobody has used, for every entry that takes fresh streams.  The range is
 // reserved atomically: two threads encrypting on one context never share a stream (the bound is checked BEFORE the counter

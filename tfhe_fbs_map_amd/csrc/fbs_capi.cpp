@@ -275,7 +275,7 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     for (void *p : {(void *)ctx->d_bsk_hat, (void *)ctx->d_bsk_hat_small, (void *)ctx->d_ksk, (void *)ctx->d_ksk_f, (void *)ctx->d_ks_corr, (void *)ctx->d_ks_a, (void *)ctx->d_ks_b, (void *)ctx->d_ks_c, (void *)ctx->d_tw_fwd, (void *)ctx->d_tw_inv, (void *)ctx->d_psi_pow, (void *)ctx->d_ms, (void *)ctx->d_ms_eps, (void *)ctx->d_ms_body, (void *)ctx->d_acc, (void *)ctx->d_stage_in, (void *)ctx->d_stage_out, (void *)ctx->d_stage_ids,
                     (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_sk_lwe_bits, (void *)ctx->d_io_msgs,
                     (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_key, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc,
-                    (void *)ctx->d_packed})
+                    (void *)ctx->d_packed, (void *)ctx->d_pub})
         if (p) (void)hipFree(p);
     for (fbs_state *st : ctx->states) {   // the states still alive
         (void)hipFree(st->d);
@@ -1706,6 +1706,37 @@ int fbs_state_put(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const u
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     FBS_HIP(ctx, hipMemcpyAsync(st->d + row0 * st->T * ctw, cts, words * 8, hipMemcpyHostToDevice, ctx->stream));
     return sync_stream(ctx, ctx->stream);
+} FBS_API_CATCH(ctx)
+
+// ---- public-key inputs: the device side of the expansion (fbs_public.hip); the host entries are fbs_public.cpp's ---------------
+int fbs_pub_expand_dev(fbs_ctx *ctx, const uint64_t *d_glwe, size_t count, uint64_t *d_cts, void *stream) try {
+    if (!ctx || (count && (!d_glwe || !d_cts))) return FBS_E_INVALID;
+    if (int rc = check_ct_words(ctx, count)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_expand_public(ctx, d_glwe, count, d_cts, pick(ctx, stream));
+} FBS_API_CATCH(ctx)
+
+// rows [row0, row0 + rows) flattened [row][sample] are one run of rows * T ciphertexts in the state: the kernel writes it as it
+// writes a plain batch
+int fbs_state_put_public(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *glwe) try {
+    if (!ctx) return FBS_E_INVALID;
+    int rc = check_state_rows(ctx, st, row0, rows, glwe);
+    if (rc != FBS_OK) return rc;
+    if (rows == 0) return FBS_OK;
+    const size_t ctw = ctx->D + 1, count = rows * st->T;   // (a state's rows * T * (D + 1) words fit a size_t, and so do the samples')
+    const size_t words = (count + ctx->N - 1) / ctx->N * ((size_t)ctx->D + ctx->N);
+    const size_t bad = first_noncanonical(glwe, words);
+    if (bad < words) return set_error(ctx, FBS_E_INVALID, "sample word " + std::to_string(bad) + " is not a canonical residue");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    if ((rc = grow(ctx, ctx->d_pub, ctx->pub_capacity, words, 8, true)) != FBS_OK) return rc;
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    if (hipMemcpyAsync(ctx->d_pub, glwe, words * 8, hipMemcpyHostToDevice, s) != hipSuccess)
+        return scratch_fail(ctx, s, set_error(ctx, FBS_E_DEVICE, "copying samples to the device failed"));
+    if ((rc = dev_expand_public(ctx, ctx->d_pub, count, st->d + row0 * st->T * ctw, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+    if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
+    return sync_stream(ctx, s);
 } FBS_API_CATCH(ctx)
 
 // ---- packed outputs: up to N outputs in one GLWE sample under the big key (fbs_pack.hpp, fbs_pack.hip) -----------------------

@@ -34,7 +34,10 @@ enum Domain : uint64_t {
     DOM_SBSK_MASK = 10, DOM_SBSK_NOISE = 11,            // seeded bootstrapping key: mask (mask key), noise (context key)
     DOM_SKSK_MASK = 12, DOM_SKSK_NOISE = 13,            // seeded key-switching key
     DOM_SENC_MASK = 14, DOM_SENC_NOISE = 15,            // seeded encryption
-    DOM_PACK_MASK = 16, DOM_PACK_NOISE = 17             // packing key (packed outputs): mask (mask key), noise (context key)
+    DOM_PACK_MASK = 16, DOM_PACK_NOISE = 17,            // packing key (packed outputs): mask (mask key), noise (context key)
+    // public-key inputs (fbs_public.cpp; include/fbs_exec.h, "public-key inputs"): the public key's masks (mask key) and noise
+    // (the key holder's noise seed); the encryptor's binary u and its noise, both under the encryptor's own key
+    DOM_PUB_MASK = 18, DOM_PUB_NOISE = 19, DOM_PUB_ENC_U = 20, DOM_PUB_ENC_NOISE = 21
 };
 FBS_HD uint64_t stream_id(Domain d, uint64_t sub) { return ((uint64_t)d << 56) | (sub & 0x00FFFFFFFFFFFFFFull); }
 // the 256-bit ChaCha key of a context: a 64-bit seed followed by a fixed tail (fbs_ctx_create: reproducible, test-grade), or
@@ -243,6 +246,8 @@ struct fbs_ctx : fbs::HostState {
     size_t pack_acc_capacity = 0;    // in words
     uint64_t *d_packed = nullptr;    // staging of fbs_state_fetch_packed's words
     size_t packed_capacity = 0;      // in words
+    uint64_t *d_pub = nullptr;       // staging of fbs_state_put_public's GLWE samples
+    size_t pub_capacity = 0;         // in words
     fbs_tvset *tv_identity = nullptr;   // the identity table [0, 1, .., p - 1], made on first use: what refreshes a compact input
     int64_t *d_io_msgs = nullptr;    // scratch: messages of fbs_eval_messages, [n_inputs + n_outputs][chunk]
     size_t io_msgs_capacity = 0;     // in words
@@ -369,6 +374,10 @@ int host_build_tv(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint64
 int host_build_tv_diff(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint32_t *pos, int32_t *val, uint32_t *count,
                        uint64_t *norm2, uint64_t *g_norm2, uint64_t *abs_sum);
 void host_twiddles(uint32_t log_n, std::vector<uint64_t> &fwd, std::vector<uint64_t> &inv);
+// public-key inputs (fbs_public.cpp): index of the first word of glwe[words] that is no canonical residue, or `words`; and the
+// sample extraction glwe [ceil(count / N)][k + 1][N] -> cts [count][k N + 1] (include/fbs_exec.h, "public-key inputs", Expansion)
+size_t first_noncanonical(const uint64_t *w, size_t words);
+void host_pub_expand(uint32_t k, uint32_t N, const uint64_t *glwe, size_t count, uint64_t *cts);
 // fbs_import_keys: null if sampled rows of bsk and ksk decrypt under sk_lwe [n] and sk_glwe [D] as the fbs_key_sizes layout says,
 // else why not
 const char *imported_keys_mismatch(const fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glwe, const uint64_t *bsk,
@@ -439,6 +448,9 @@ int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream)
 int dev_state_scatter(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);
 // plaintext inputs: the trivial ciphertexts of the links of `a` into their wire slots, one launch
 int dev_fill_plain(const fbs_ctx *ctx, const PlainFill &a, hipStream_t stream);
+// public-key inputs (fbs_public.hip): sample extraction of the GLWE samples d_glwe [ceil(count / N)][k + 1][N] into the big-key
+// ciphertexts d_cts [count][D + 1], message j from coefficient j mod N of sample j / N; word for word host_pub_expand
+int dev_expand_public(const fbs_ctx *ctx, const uint64_t *d_glwe, size_t count, uint64_t *d_cts, hipStream_t stream);
 
 // profiling helpers
 void prof_begin(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t *e0, hipEvent_t *e1);

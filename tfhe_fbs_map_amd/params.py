@@ -220,6 +220,19 @@ def refresh_margin_needed(prm: Params, norm2: float = 1.0) -> float:
     return margin_sigmas(prm, norm2) * (1.0 - 4.0 * prm.p_msg * compact_output_skew(prm))
 
 
+# ---- public-key inputs (include/fbs_exec.h, "public-key inputs") ---------------------------------------------------------------
+def public_input_variance(prm: Params) -> float:
+    """Phase variance, in torus units, of a public-key encryption under the GLWE key: the phase is sum_r u_r E_r + e_k - sum_c e_c S_c
+    + Delta M with u and S binary -- k N / 2 terms of variance sigma_glwe^2 from each sum on average, and e_k: (1 + k N) sigma_glwe^2."""
+    return (1.0 + prm.k * prm.N) * (prm.sigma_glwe / float(MODULUS)) ** 2
+
+
+def public_input_factor(prm: Params) -> float:
+    """`public_input_variance` in units of one blind rotation's output variance: the unit `split.output_noise_factors` and
+    `split.plan_chain` count in.  At most 1 means that a public-key input enters a program as a bootstrap output does."""
+    return public_input_variance(prm) / variances(prm)[0]
+
+
 def p_error(margin: float) -> float:
     """Probability that a Gaussian leaves +-margin standard deviations (one bootstrap)."""
     return math.erfc(margin / math.sqrt(2.0))

@@ -50,6 +50,18 @@ m * Delta: include/fbs_exec.h, "chained evaluation"), carry no noise and belong 
 
     round_key = PlainInputs(b_names, None, {f"b{i}": (k >> i) & 1 for i in range(8)})    # one value for all samples
     server.run(adder8, client.encrypt(query, names=a_names), plain=round_key)
+
+Public-key inputs: three parties.  A data owner who is neither the key holder nor the server -- a sensor, a second company, a user
+of a service somebody else keyed -- encrypts under the client's `PublicKey` (`public.PublicEncryptor`, on libfbspublic.so alone: no
+secret, no GPU) and sends GLWE samples, k + 1 words a bit (include/fbs_exec.h, "public-key inputs").  The server expands them on
+the GPU into resident state and evaluates as ever; their noise, (1 + kN) sigma_glwe^2, is far below a bootstrap output's, so
+they enter unrefreshed (`params.public_input_factor`).  IND-CPA only and malleable, like every ciphertext here.
+
+    client.public_key().save("public_key.npz")                                   # key holder -> the data owner, once
+    sensor = PublicEncryptor(PublicKey.load("public_key.npz"))                   # the data owner: os.urandom seeds it
+    sensor.encrypt(reading, names=a_names).save("reading.npz")                   # -> the server, per evaluation
+    out = server.run(adder8, client.encrypt(offset, names=b_names), public=PublicInputs.load("reading.npz"))
+    client.decrypt(out)                                                          # the key holder reads the result
 """
 from __future__ import annotations
 
@@ -546,6 +558,7 @@ class Client:
             self.packing = packing_choice(self.params, norm2, max(worst, 1.0))
             self.ctx.packing_keygen(*self.packing[:2])
         self._server_key = None
+        self._public_key = None
 
     def server_key(self) -> ServerKey:
         if self._server_key is None:
@@ -558,6 +571,21 @@ class Client:
     @property
     def fingerprint(self) -> bytes:
         return self.server_key().fingerprint
+
+    def public_key(self):
+        """-> `public.PublicKey`: what a third party needs to encrypt inputs for this client's server key (`public.PublicEncryptor`)
+        -- the parameter set, the public mask key and k N words of bodies; no secret.  Made on the host (fbs_pub_keygen, from
+        whichever library is there) from the exported GLWE key; its noise is drawn under a seed derived from the client's key seed
+        under a label of its own, so the same client makes the same key."""
+        from . import _public_native
+        from .public import PublicKey, public_key_noise_seed
+        if self._public_key is None:
+            mask_key = self.server_key().mask_key
+            sk = self.ctx.export_keys()["sk_glwe"]
+            bodies = _public_native.keygen(self.params, mask_key, sk, public_key_noise_seed(self.config.key_seed()))
+            sk[:] = 0
+            self._public_key = PublicKey(self.params, mask_key, bodies)
+        return self._public_key
 
     def encrypt(self, input_values, nonce0=None, names=None) -> EncryptedInputs:
         """{input name: array-like of bits} (the contract of `LutExecEnv.eval`) -> seeded ciphertexts.  nonce0: the first
@@ -631,11 +659,15 @@ class Server:
         self._programs[id(low)] = (prog, low)
         return prog, low
 
-    def run(self, env, inputs: EncryptedInputs, resident=False, plain=None):
+    def run(self, env, inputs: EncryptedInputs, resident=False, plain=None, public=None):
         """-> `EncryptedOutputs`; resident=True: the outputs stay on the GPU (fbs_eval_resident) -> `ResidentOutputs`.
-        plain: a `PlainInputs` with the inputs the server supplies in the clear; then `run_chain(env, [inputs, plain])`."""
-        if plain is not None:
-            return self.run_chain(env, [inputs, plain], resident=resident)
+        plain: a `PlainInputs` with the inputs the server supplies in the clear; then `run_chain(env, [inputs, plain])`.
+        public: a `public.PublicInputs` (or several) with the inputs a third party encrypted under the client's public key; likewise."""
+        if plain is not None or public is not None:
+            extra = [] if plain is None else [plain]
+            if public is not None:
+                extra += list(public) if isinstance(public, (list, tuple)) else [public]
+            return self.run_chain(env, [inputs] + extra, resident=resident)
         if inputs.fingerprint != self.key.fingerprint:
             raise ValueError("inputs were encrypted for another server key")
         prog, low = self.program_for(env)
@@ -731,25 +763,48 @@ class Server:
             raise
         return ResidentOutputs(list(outputs.output_names), outputs.T, self.key.fingerprint, outputs.out_norm2, state, self, compact_bits)
 
-    def run_chain(self, env, sources, rename=None, compact=False, bits=None, resident=False):
+    def run_chain(self, env, sources, rename=None, compact=False, bits=None, resident=False, refresh_public=False):
         """Evaluate `env` with each input taken by name from one of `sources`: the client's `EncryptedInputs` (seeded), the
         `EncryptedOutputs` / `CompactOutputs` of earlier evaluations under this server key, and the server's own `PlainInputs`
-        (cleartext bits, written on the GPU as trivial ciphertexts: noise-free, no key) (fbs_eval_sources).  rename: {input name:
+        (cleartext bits, written on the GPU as trivial ciphertexts: noise-free, no key) (fbs_eval_sources).  A `public.PublicInputs`
+        (a third party's public-key encryptions) is expanded on the GPU into a state of its own (fbs_state_put_public), read like
+        any resident row and freed after the evaluation, also when the evaluation raises.  rename: {input name:
         source name} for an input whose source carries another name.  Compact links, and full links whose producer was noisier
         than a bootstrap output, are refreshed on the GPU: one bootstrap each per sample.  compact=True: compact outputs at `bits`
         (None: the width `compact_bits` would pick for the noise these outputs carry).  `plan_chain` says what is refused.
         A source may also be a `ResidentOutputs` of this server (a closed one, or another server's, is refused): its rows are read
-        on the GPU.  resident=True: the outputs stay there too -> `ResidentOutputs` (not with compact=True)."""
-        from .params import compact_output_bits
+        on the GPU.  resident=True: the outputs stay there too -> `ResidentOutputs` (not with compact=True).
+        refresh_public=True: public-key inputs are bootstrapped through the identity table before use even though their noise
+        does not ask for it (one bootstrap per input and sample; they then go in with factor 1, as any refreshed link)."""
+        from .params import public_input_factor, refresh_margin
         if resident and compact:
             raise ValueError("resident outputs are full ciphertexts: fetch(compact=True) compacts them when they leave the GPU")
         prm, fuse = self.key.params, self.key.fuse_tables
-        sources = [sources] if isinstance(sources, _SOURCE_TYPES) else list(sources)
+        sources = [sources] if isinstance(sources, _source_types()) else list(sources)
         for k, src in enumerate(sources):
             if isinstance(src, ResidentOutputs) and not src.closed and (src.server is not self or src.state.ctx is not self.ctx):
                 raise ValueError("source %d is resident on another server" % k)
         links, T = plan_chain(prm, fuse, self.key.fingerprint, env, sources, rename)
+        if refresh_public:
+            for ln in links:
+                if ln.kind == "public" and not ln.refresh:
+                    ln.refresh, ln.noise, ln.margin = True, 1.0, refresh_margin(prm, None, public_input_factor(prm))
         prog, low = self.program_for(env)
+        expanded = {}   # source index -> the temporary state its public-key samples were expanded into
+        try:
+            for ln in links:
+                if ln.kind == "public" and ln.source not in expanded:
+                    src = sources[ln.source]
+                    expanded[ln.source] = state = self.ctx.state(len(src.input_names), T)
+                    state.put_public(src.samples)
+            return self._run_links(env, prog, low, sources, links, T, expanded, compact, bits, resident)
+        finally:
+            for state in expanded.values():   # (closing waits for the evaluations queued on the context)
+                state.close()
+
+    def _run_links(self, env, prog, low, sources, links, T, expanded, compact, bits, resident):
+        from .params import compact_output_bits
+        prm, fuse = self.key.params, self.key.fuse_tables
         feed = []
         for ln in links:
             src = sources[ln.source]
@@ -759,13 +814,15 @@ class Server:
                 feed.append(("full", src.cts[ln.index], ln.refresh))
             elif ln.kind == "state":
                 feed.append(("state", src.state, ln.index, ln.refresh))
+            elif ln.kind == "public":
+                feed.append(("state", expanded[ln.source], ln.index, ln.refresh))
             elif ln.kind == "plain":
                 feed.append(("plain", src.row(ln.index)))
             else:
                 feed.append(("compact", src.words[ln.index], int(src.bits)))
         out_norm2 = self._out_norm2(low, [ln.noise for ln in links])
         names = list(low["out_names"])
-        run = prog.eval_resident if any(ln.kind == "state" for ln in links) else prog.eval_sources
+        run = prog.eval_resident if any(ln.kind in ("state", "public") for ln in links) else prog.eval_sources
         if resident:
             return self._resident(env, prog, low, feed, T, out_norm2)
         if not compact:
@@ -783,17 +840,23 @@ class ChainLink:
     name: str                     # the program's input
     source: int                   # which of the sources
     index: int                    # its row there (input or output position)
-    kind: str                     # "seeded", "full", "compact", "state" (a row of a ResidentOutputs: full ciphertexts on the GPU) or "plain"
+    kind: str                     # "seeded", "full", "compact", "state" (a row of a ResidentOutputs: full ciphertexts on the GPU), "plain" or "public"
     refresh: bool                 # bootstrapped through the identity table before use
-    noise: float                  # its noise factor going in: 0 fresh or plain, 1 refreshed, the producer's out_norm2 for a plain full link
+    noise: float                  # its noise factor going in: 0 fresh or plain, 1 refreshed, the producer's out_norm2 for a plain full link,
+                                  # params.public_input_factor for a public-key input
     margin: float | None = None   # params.refresh_margin of a refreshed link
 
 
 _SOURCE_TYPES = (EncryptedInputs, EncryptedOutputs, CompactOutputs, ResidentOutputs, PlainInputs)
 
 
+def _source_types():
+    from .public import PublicInputs      # (`public` imports this module)
+    return _SOURCE_TYPES + (PublicInputs,)
+
+
 def _names_of(src):
-    return list(src.input_names if isinstance(src, (EncryptedInputs, PlainInputs)) else src.output_names)
+    return list(src.input_names if hasattr(src, "input_names") else src.output_names)
 
 
 def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_margin=None):
@@ -807,8 +870,13 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
     inputs no noisier than that.  Every other full link and every compact link is refreshed.  A `ResidentOutputs` is a full link
     whose ciphertexts are on the GPU (kind "state"), under the same rule; a closed one is refused.
     A `PlainInputs` is public and belongs to no key: no fingerprint is asked of it, its link is noise-free (kind "plain", noise 0)
-    and never refreshed; one without T takes the chain's, and a program fed by such sources alone has no T and is refused."""
-    from .params import margin_sigmas, refresh_margin, refresh_margin_needed
+    and never refreshed; one without T takes the chain's, and a program fed by such sources alone has no T and is refused.
+    A `public.PublicInputs` (public-key encryptions by a third party) is held to the fingerprint and to T like an `EncryptedInputs`;
+    its samples must have the shape the parameter set and T give (`public.public_sample_shape`).  Its noise factor is
+    `params.public_input_factor`: at most 1, it goes in as it is (kind "public") with that factor as its noise; above, it is
+    refreshed under exactly the full-link rule."""
+    from .params import margin_sigmas, public_input_factor, refresh_margin, refresh_margin_needed
+    from .public import PublicInputs, public_sample_shape
     low = env.lower()
     p = params.p_msg
     for t in low["tables"]:
@@ -828,8 +896,8 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
         if isinstance(src, PackedOutputs):
             raise ValueError("source %d is a PackedOutputs: a packed result is under the client's big key in GLWE form, for the client "
                              "only; link the EncryptedOutputs, CompactOutputs or ResidentOutputs of that evaluation instead" % k)
-        if not isinstance(src, _SOURCE_TYPES):
-            raise TypeError("source %d is a %s, not EncryptedInputs, EncryptedOutputs, CompactOutputs or ResidentOutputs, or PlainInputs" % (k, type(src).__name__))
+        if not isinstance(src, _source_types()):
+            raise TypeError("source %d is a %s, not EncryptedInputs, EncryptedOutputs, CompactOutputs or ResidentOutputs, or PublicInputs or PlainInputs" % (k, type(src).__name__))
         if isinstance(src, ResidentOutputs) and src.closed:
             raise ValueError("source %d is resident state that has been closed" % k)
         if not isinstance(src, PlainInputs) and src.fingerprint != fingerprint:
@@ -862,6 +930,21 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
             continue
         if isinstance(src, PlainInputs):
             links.append(ChainLink(name, k, j, "plain", False, 0.0))
+            continue
+        if isinstance(src, PublicInputs):
+            shape, want_shape = tuple(np.shape(src.samples)), public_sample_shape(params, len(src.input_names), src.T)
+            if shape != want_shape:
+                raise ValueError("input %s: public-key samples of shape %s, the server key's parameter set and T = %d need %s"
+                                 % (via, shape, src.T, want_shape))
+            factor = public_input_factor(params)
+            if factor <= 1.0:
+                links.append(ChainLink(name, k, j, "public", False, factor))
+                continue
+            link = ChainLink(name, k, j, "public", True, 1.0, refresh_margin(params, None, factor))
+            if link.margin < need * (1.0 - 1e-12):
+                raise ValueError("input %s: its refresh would keep %.3f sigma (public-key noise factor %g), below the %.3f the program's "
+                                 "bootstraps keep" % (via, link.margin, factor, need))
+            links.append(link)
             continue
         if src.out_norm2 is None:
             raise ValueError("input %s: source %d was saved without out_norm2 (before chains existed), so the noise it carries is "
