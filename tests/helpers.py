@@ -931,3 +931,214 @@ def extract_kernel_sums(acc, pos, val, k, N):
             assert -(1 << 63) <= total < 1 << 63
         out.append(-total if jj else total)
     return out
+
+
+# ==== compact ciphertexts at real key sizes, on planted rounding boundaries (tests/test_compact_reference.py, =======================
+# ==== tests/test_gpu_compact_wide.py) ==============================================================================================
+# The format kernels (k_compact_pack, k_compact_unpack, k_decrypt_compact) loop over rounds of 256 words and over passes of 64 lanes,
+# and their sums are exact through wrap-around and flooring shifts: none of it shows at n = 12 on random words.  The sets below reach
+# n = 4096 on the cheapest polynomial size; the key-switching key is planted so that the switched ciphertexts are CHOSEN words.
+# t = 1, so one digit is one key row; b = log2(2N) = 9 is the narrowest width the format has.
+COMPACT_WIDE_SETS = {"n%d" % n: dict(n=n, log_n_poly=8, k=1, l_bsk=2, beta_bsk=10, t_ksk=1, gamma_ksk=8, p_msg=7, sigma_lwe=1 << 8,
+                                     sigma_glwe=4, bsk_group=1) for n in (64, 65, 734, 4096)}
+COMPACT_PACK_WIDTHS = (9, 12, 23, 31)
+PLANT_WORD = 1 << 38                                          # the word whose only digit (t = 1, gamma = 8) is 1
+
+
+def planted_switch(keys, prm, targets, bodies=None, oracle=None):
+    """keys: dict(sk_lwe, sk_glwe, bsk, ksk) (export_keys / Oracle.keys); targets: at most N rows of n canonical words;
+    bodies[j]: the switched bodies wanted with row j (default: [0]).  -> (the same dict with key row (j, 0) planted, input ciphertexts
+    [sum of len(bodies[j])][D + 1], row after row).  Key row (j, 0) gets the mask -targets[j] mod q and the body
+    <mask, sk_lwe> + sk_glwe[j] h_0 without noise (a valid row for import_keys); a ciphertext of row j is zero but for mask word j,
+    whose one digit is 1, and its body, so that its key switch is 0 - 1 x (key row j) + (0, .., 0, body): exactly (targets[j], the body
+    wanted).  Asserted here through the oracle's key switch (`oracle`: one of this parameter set to use, its keys are replaced)."""
+    from oracle import tfhe_oracle as orc
+    n, D, t, gamma = ks_shape(prm)
+    assert t == 1 and len(targets) <= D and ks_digits(PLANT_WORD, t, gamma) == [1]
+    bodies = [[0]] * len(targets) if bodies is None else bodies
+    sk_lwe, sk_glwe = [int(x) for x in keys["sk_lwe"]], [int(x) for x in keys["sk_glwe"]]
+    h0 = ks_gadget(prm)[0]
+    ksk = np.array(keys["ksk"], dtype=np.uint64).reshape(D, n + 1)
+    cts, want = [], []
+    for j, (row, wanted) in enumerate(zip(targets, bodies)):
+        assert len(row) == n and all(0 <= int(x) < Q for x in row)
+        mask = [(Q - int(x)) % Q for x in row]
+        key_body = (sum(m for m, s in zip(mask, sk_lwe) if s) + (h0 if sk_glwe[j] else 0)) % Q
+        ksk[j, :n], ksk[j, n] = mask, key_body
+        for body in wanted:
+            ct = np.zeros(D + 1, np.uint64)
+            ct[j], ct[D] = PLANT_WORD, (int(body) + key_body) % Q
+            cts.append(ct)
+            want.append([int(x) for x in row] + [int(body)])
+    out = dict(keys)
+    out["ksk"] = ksk.reshape(-1)
+    o = oracle if oracle is not None else orc.Oracle(prm, seed=1, keygen=False)
+    o.set_keys(**out)
+    for ct, w in zip(cts, want):
+        assert [int(x) for x in o.keyswitch(ct)] == w
+    return out, np.stack(cts) if cts else np.zeros((0, D + 1), np.uint64)
+
+
+# ---- THE DEFINITIONS on Python integers (include/fbs_exec.h, "compact outputs" and "chained evaluation") ---------------------------
+def _half_up(x, sh):
+    """round-half-up(x / 2^sh), x >= 0"""
+    return (x + (1 << sh >> 1)) >> sh
+
+
+def _rounded_down(x, top, bits, modulus):
+    """n mask words and a body below `modulus` (2^top or the q just below it) -> n + 1 fields below 2^bits: every mask word
+    rounded half-up to a multiple of 2^(top - bits), the body taken down by floor(eps / 2) mod `modulus` first, eps the sum of the
+    mask words' signed rounding errors"""
+    sh = top - bits
+    x = [int(v) for v in x]
+    m = [_half_up(v, sh) for v in x[:-1]]
+    eps = sum(v - (r << sh) for v, r in zip(x, m))
+    body = (x[-1] - eps // 2) % modulus                                 # (// floors)
+    return [r % (1 << bits) for r in m + [_half_up(body, sh)]]
+
+
+def compact_definition(x, bits):
+    """a small-key ciphertext (n mask words, body; canonical mod q) -> its n + 1 fields at width `bits`"""
+    return _rounded_down(x, QBITS, bits, Q)
+
+
+def reround_definition(fields, bits, b):
+    """n + 1 fields at width `bits` -> the fields at width b <= bits the blind rotation reads"""
+    return [int(f) for f in fields] if bits == b else _rounded_down(fields, bits, b, 1 << bits)
+
+
+def decode_phase(body, mask_sum, bits, two_p):
+    """round-half-up(phase 2p / 2^bits) mod 2p, phase = (body - mask_sum) mod 2^bits"""
+    return _half_up((body - mask_sum) % (1 << bits) * two_p, bits) % two_p
+
+
+def decode_definition(fields, sk, bits, two_p):
+    """n + 1 fields and the small key's n bits -> the message"""
+    return decode_phase(int(fields[-1]), sum(int(f) for f, s in zip(fields, sk) if s), bits, two_p)
+
+
+def pack_definition(fields, bits):
+    """fields of `bits` bits -> the words of the bit stream they make, field j at stream bits [j bits, j bits + bits): the stream
+    written out as a string of binary digits, last field first, and cut into words of 64 from its low end"""
+    digits = "".join(format(int(f), "0%db" % bits) for f in reversed(fields))
+    W = -(-len(digits) // 64)
+    digits = digits.zfill(64 * W)
+    return [int(digits[64 * (W - 1 - w):64 * (W - w)], 2) for w in range(W)]
+
+
+def unpack_definition(words, n1, bits):
+    """the way back: n1 fields"""
+    digits = "".join(format(int(w), "064b") for w in reversed(words))
+    return [int(digits[len(digits) - (j + 1) * bits:len(digits) - j * bits], 2) for j in range(n1)]
+
+
+# ---- planted rows: every mask word on a chosen side of its rounding boundary -------------------------------------------------------
+def rounding_eps(x, top, bits):
+    """eps of a row of mask words: the sum of their signed rounding errors from 2^top down to 2^bits"""
+    sh = top - bits
+    return sum(int(v) - (_half_up(int(v), sh) << sh) for v in x)
+
+
+def boundary_rows(n, top, bits, modulus, seed):
+    """{name: n mask words below `modulus`} for the rounding from 2^top down to 2^bits (sh = top - bits; m_i random below 2^bits,
+    lowered where the word would reach `modulus`):
+    half   (m_i << sh) + 2^(sh-1): every word rounds up, eps = -n 2^(sh-1), the negative extreme
+    below  one less: every word rounds down, eps = +n (2^(sh-1) - 1), the positive extreme
+    top    every word modulus - 1: rounds up to 2^bits (the field wraps to 0) where modulus - 1 is in the upper half of its step
+    odd    every word one below a multiple of 2^sh, but the first on a multiple when n is even: eps is negative and odd
+    alt    half and below in turn
+    rand   uniform random words
+    With sh = 0 nothing is rounded: top, rand and zero rows only."""
+    rng = random.Random("boundary rows %d %d %d %d" % (n, top, bits, seed))
+    sh = top - bits
+    rand = [rng.randrange(modulus) for _ in range(n)]
+    if sh == 0:
+        return {"top": [modulus - 1] * n, "rand": rand, "zero": [0] * n}
+    hb = 1 << (sh - 1)
+    m = [min(rng.randrange(1 << bits), (modulus - 1 - hb) >> sh) for _ in range(n)]
+    half = [(v << sh) + hb for v in m]
+    below = [v - 1 for v in half]
+    odd = [(max(v, 1) << sh) - 1 for v in m]
+    if n % 2 == 0:
+        odd[0] += 1
+    alt = [h if i % 2 == 0 else b for i, (h, b) in enumerate(zip(half, below))]
+    return {"half": half, "below": below, "top": [modulus - 1] * n, "odd": odd, "alt": alt, "rand": rand}
+
+
+def boundary_bodies(row, top, bits, modulus, seed=0):
+    """the bodies x_n paired with a row of mask words: those for which y = (x_n - floor(eps / 2)) mod `modulus` is the last value that
+    rounds down, the first that rounds up and the one after it -- at a random step and at the highest step below `modulus` --, y = 0
+    and y = modulus - 1, then x_n = 0 and x_n = modulus - 1 themselves.  Whatever eps is, the subtraction wraps through `modulus` in
+    some of them: y = 0 and y = modulus - 1 lie either side of the wrap.  Computed from the definition of eps alone."""
+    sh = top - bits
+    rng = random.Random("boundary bodies %d %d %d %d" % (len(row), top, bits, seed))
+    if sh == 0:
+        return [0, modulus - 1, rng.randrange(modulus), rng.randrange(modulus)]
+    half_eps = rounding_eps(row, top, bits) // 2
+    hb = 1 << (sh - 1)
+    ys = []
+    for step in (rng.randrange(1 << bits), (modulus - 2 - hb) >> sh):
+        ys += [(step << sh) + hb - 1, (step << sh) + hb, (step << sh) + hb + 1]
+    ys += [0, modulus - 1]
+    assert all(0 <= y < modulus for y in ys)
+    return [(y + half_eps) % modulus for y in ys] + [0, modulus - 1]
+
+
+def compact_target_rows(n, bits, seed=0):
+    """{name: (n canonical words, [switched bodies])} for the pack at width `bits` (the row of q - 1 is called qm1 here)"""
+    rows = boundary_rows(n, QBITS, bits, Q, seed)
+    return {{"top": "qm1"}.get(name, name): (row, boundary_bodies(row, QBITS, bits, Q, seed)) for name, row in rows.items()}
+
+
+def reround_field_rows(n, bits, b, seed=0):
+    """{name: [rows of n + 1 fields below 2^bits]} for the unpack from width `bits` down to b"""
+    rows = boundary_rows(n, bits, b, 1 << bits, seed)
+    return {name: [row + [body] for body in boundary_bodies(row, bits, b, 1 << bits, seed)] for name, row in rows.items()}
+
+
+# ---- decode cases: phases on every boundary between two messages --------------------------------------------------------------------
+def decode_boundary_phases(bits, two_p):
+    """the phases either side of every decode boundary (2j + 1) 2^bits / (2 two_p), j < two_p, and the boundary itself where it is an
+    integer; in order, without repeats"""
+    out = []
+    for j in range(two_p):
+        num, den = (2 * j + 1) << bits, 2 * two_p
+        cands = (num // den - 1, num // den, num // den + 1) if num % den == 0 else (num // den, num // den + 1)
+        out += [c % (1 << bits) for c in cands]
+    return list(dict.fromkeys(out))
+
+
+def decode_cases(n, sk, bits, two_p, seed=0, random_count=64):
+    """-> {"ones": (mask fields [n], [body fields]), "zeros": (mask, bodies), "random": [rows of n + 1 fields]}: (a) every mask
+    field 2^bits - 1, so that the sum over the key's set bits wraps 2^32 as often as it can, (b) zero masks -- both with the bodies
+    that put the phase on every decode boundary and one either side -- and (c) `random_count` rows of random fields"""
+    top = (1 << bits) - 1
+    phases = decode_boundary_phases(bits, two_p)
+    ones = sum(int(s) for s in sk) * top
+    rng = random.Random("decode cases %d %d %d %d" % (n, bits, two_p, seed))
+    return {"ones": ([top] * n, [(ph + ones) % (1 << bits) for ph in phases]), "zeros": ([0] * n, phases),
+            "random": [[rng.randrange(1 << bits) for _ in range(n + 1)] for _ in range(random_count)]}
+
+
+def decode_case_batches(cases, sk, bits, two_p, pack, chunk=8192):
+    """the cases of decode_cases -> (name, packed words uint64 [<= chunk][W], the messages by the definition) per batch.  The mask
+    fields that a set shares are packed once with `pack` (the restatement of tests/test_gpu_compact.py) and summed under the key
+    once; the body field, the last of the stream, is set per row."""
+    n = len(sk)
+    at, o = n * bits // 64, n * bits % 64
+    for name in ("ones", "zeros"):
+        mask, bodies = cases[name]
+        template = pack(np.array([mask + [0]], dtype=np.uint64), bits)
+        mask_sum = sum(f for f, s in zip(mask, sk) if s)
+        assert decode_phase(bodies[0], mask_sum, bits, two_p) == decode_definition(mask + bodies[:1], sk, bits, two_p)
+        for c0 in range(0, len(bodies), chunk):
+            part = bodies[c0:c0 + chunk]
+            body = np.array(part, dtype=np.uint64)
+            words = np.repeat(template, len(part), axis=0)
+            words[:, at] |= body << np.uint64(o)
+            if o + bits > 64:
+                words[:, at + 1] |= body >> np.uint64(64 - o)
+            assert unpack_definition(words[-1], n + 1, bits) == mask + part[-1:]
+            yield name, words, [decode_phase(b, mask_sum, bits, two_p) for b in part]
+    rows = cases["random"]
+    yield "random", pack(np.array(rows, dtype=np.uint64), bits), [decode_definition(r, sk, bits, two_p) for r in rows]

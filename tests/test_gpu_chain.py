@@ -3,7 +3,11 @@ unpack and re-rounding at every width; fbs_refresh_compact_dev of fbs_compact_de
 the identity table, word for word; fbs_eval_sources with seeded sources is fbs_eval_seeded and fbs_eval_seeded_compact, chunked
 too, refuses with codes and does not grow scratch when called again; a 32-hop adder8 accumulator over compact, full and mixed
 links decrypts to the cleartext running sum after every hop; two processes hand a chain over through .npz files; and the noise
-of refreshed inputs is what params says."""
+of refreshed inputs is what params says.
+
+The restatement and the refresh are compared here at n = 12, on random words.  k_compact_unpack at real key sizes (several and
+partial passes of 64 lanes, its grid-stride loop), a re-rounding error sum at its extremes and of either parity, and the refresh
+at n = 734 are in tests/test_gpu_compact_wide.py; tests/test_compact_reference.py anchors `reround` in its definition."""
 import ctypes as C
 import os
 import subprocess

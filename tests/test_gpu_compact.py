@@ -2,7 +2,11 @@
 followed by the rounding and packing of the format, word for word, on every key-switch family; the host and device decodes agree
 with each other and with the decryption of the full ciphertexts; fbs_eval_seeded_compact is fbs_compact_dev of fbs_eval_seeded's
 outputs (constants included, in chunks too); a Client / Server pair in two processes exchanges compact files; and the phase
-noise of compact bootstrap outputs is what params.compact_output_variance says."""
+noise of compact bootstrap outputs is what params.compact_output_variance says.
+
+The word-for-word comparisons here run on the toy sets of tests/test_gpu_device_io.py (n = 12: one round of k_compact_pack, one
+pass of 64 lanes in k_decrypt_compact, a 32-bit sum that never wraps).  Real key sizes (n up to 4096), planted rounding
+boundaries and the definitions on Python integers are in tests/test_gpu_compact_wide.py and tests/test_compact_reference.py."""
 import os
 import subprocess
 import sys
