@@ -647,6 +647,45 @@ int fbs_level_scatter_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, ui
                           size_t s_begin, size_t s_count, const uint64_t *d_rows, size_t f_begin, size_t f_end,
                           void *stream);
 
+/* ---- audited evaluation: the noise of a stepped program, measured where its margin is defined -------------------------------
+ * Between the level calls above, fbs_audit_level_dev turns the ciphertexts of one point of one level, plus the cleartext value
+ * each should hold, into exact error statistics on the device (fbs_audit.hip), under the secret keys the context keeps there.
+ * Two units:
+ *   wire units   (INPUTS, LINCOMB, BOOTSTRAP): big-key ciphertexts in their wire slots.  phase = b - <a, S> mod q;
+ *                e = centred((phase - Delta m) mod q) with m = expected mod 2p and Delta = 2 round(q / 4p): an integer in
+ *                [-(q-1)/2, (q-1)/2], the torus error is e / q, and a sample is `over` when 4p |e| >= q.
+ *   field units  (ROTATION_INPUT): the (n + 1) fields of log2(2N) bits that the key switch and the modulus switch leave for the
+ *                blind rotation.  ph = body - <mask, s> mod 2N; e = centred((2p ph - 2N m) mod 4pN) in [-2pN, 2pN): the torus
+ *                error is e / (4pN), the half box is N, and a sample is `over` when |e| >= N.  (2p Delta stands for q here: a
+ *                relative difference of at most 4p / q.)
+ * `over` is a half-box criterion, not a comparison of decoded messages: an error of half a box or more is what makes a blind
+ * rotation land in a neighbouring box, whatever the table then returns there.
+ * FBS_AUDIT_ROTATION_INPUT runs the same key switch, at the same width log2(2N), that fbs_level_bootstrap_dev(level) runs over
+ * the level's full range, into the same scratch, and decodes that scratch; the key switch is deterministic, so these are the very
+ * words the rotation reads.  It must be called after fbs_level_lincomb_dev(level) and before fbs_level_bootstrap_dev(level): a
+ * source's slot may be reused by the level's own outputs.  Likewise INPUTS before level 0 runs, LINCOMB(level) right after
+ * fbs_level_lincomb_dev(level) and BOOTSTRAP(level) right after fbs_level_bootstrap_dev(level) (into the wire slots).  LINCOMB
+ * reports the LinearProds of the level whose slot still holds them when the level's LinearProds have all run (a wire nobody
+ * outside an earlier sub-stage reads may have lent its slot to a later one).  BOOTSTRAP of a fused program reports the outputs
+ * of the level's own rotations, then those cut out of shared rotations.
+ * Errors: FBS_E_STATE on a context without a secret (evaluation-only); FBS_E_INVALID for a level the point does not have
+ * (LINCOMB: [0, n_levels]; ROTATION_INPUT, BOOTSTRAP: [0, n_levels)), an unknown point, a bad sample range, more than 2^18
+ * samples in one call (the bound under which the 64-bit sum and the 128-bit sum of squares cannot overflow: |e| < 2^45), or null
+ * pointers with n_rows * s_count > 0.  s_count = 0 does nothing.  The statistics are exact integers, computed without floating
+ * point or atomics: the same inputs give the same words. */
+#define FBS_AUDIT_INPUTS          0u  /* the input slots (level ignored)                               : wire units   */
+#define FBS_AUDIT_LINCOMB         1u  /* wires the LinearProds of level L write                        : wire units   */
+#define FBS_AUDIT_ROTATION_INPUT  2u  /* the level's distinct key-switch sources, after KS + MS        : field units  */
+#define FBS_AUDIT_BOOTSTRAP       3u  /* wires the Bootstraps of level L write                         : wire units   */
+typedef struct fbs_audit_row { uint64_t count, over, max_abs; int64_t sum; uint64_t sumsq_lo, sumsq_hi; } fbs_audit_row;
+
+/* rows of (level, point) and the PROGRAM WIRE ID (fbs_program_desc numbering) of each, in the order the audit reports them */
+int fbs_audit_rows(const fbs_prog *prog, uint32_t level, uint32_t point, uint32_t *n_rows, uint32_t *wire_ids /* may be NULL */);
+/* d_expected: device [n_rows][s_count] int64, the cleartext value of each row's wire per sample (any integer; taken mod 2p).
+ * stats: host [n_rows]; errors: host [n_rows][s_count] or NULL.  Blocks until they are back. */
+int fbs_audit_level_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, uint32_t point, const uint64_t *d_wires, size_t T,
+                        size_t s_begin, size_t s_count, const int64_t *d_expected, fbs_audit_row *stats, int64_t *errors, void *stream);
+
 /* ---- measurement hooks ------------------------------------------------------
  * When enabled, every kernel launch is bracketed by HIP events on its own
  * stream; fbs_profile_read synchronises and returns per-kernel totals since the

@@ -11,6 +11,9 @@ evaluation -- the reference's self-check (:174-180) with ciphertexts in the midd
 or 1 is that value for every sample, BITS = samples the harness's own draws for NAME.  The run then goes through the client / server
 split -- the client encrypts the other inputs, the server evaluates without the secret, the client decrypts -- and the self-check
 covers the mixed run.
+
+`--audit` then runs the program once more as `LutExecEnv.audit` does and prints, after the JSON line, how close every gate came
+to a wrong rotation: the summary line and the ten rows with the least measured margin.
 """
 import argparse
 import json
@@ -76,8 +79,13 @@ def main(argv=None):
                     help="give every table a blind rotation of its own, even where several read one linear combination")
     ap.add_argument("--plain", action="append", default=[], metavar="NAME=BITS",
                     help="give input NAME to the server in the clear: BITS = 0 or 1 for every sample, or 'samples' for the harness's draws")
+    ap.add_argument("--audit", action="store_true",
+                    help="after the check, run once more with the noise measured at every blind rotation's input (LutExecEnv.audit) "
+                         "and print the summary and the ten gates with the least margin")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
+    if args.audit and args.plain:
+        ap.error("--audit measures under the secret key: it does not go with --plain (the server of a split run holds none)")
 
     from . import ExecConfig
     names = args.inputs.split(",") if args.inputs else None
@@ -130,6 +138,8 @@ def main(argv=None):
             np.array_equal(np.broadcast_to(np.asarray(out[k]), (args.samples,)),
                            np.broadcast_to(np.asarray(clear[k]), (args.samples,))) for k in clear)
     print(json.dumps(result))
+    if args.audit:
+        print(env.audit(values, config=cfg).summary(10))
     return 0 if result.get("matches_cleartext_netlist", True) else 1
 
 

@@ -44,6 +44,14 @@ class _ResidentSrc(C.Structure):   # fbs_resident_src (include/fbs_exec.h, "resi
     _fields_ = [("state", C.c_void_p), ("row", C.c_uint32), ("refresh", C.c_uint32)]
 
 
+class _AuditRow(C.Structure):   # fbs_audit_row (include/fbs_exec.h, "audited evaluation")
+    _fields_ = [("count", C.c_uint64), ("over", C.c_uint64), ("max_abs", C.c_uint64), ("sum", C.c_int64),
+                ("sumsq_lo", C.c_uint64), ("sumsq_hi", C.c_uint64)]
+
+
+AUDIT_INPUTS, AUDIT_LINCOMB, AUDIT_ROTATION_INPUT, AUDIT_BOOTSTRAP = 0, 1, 2, 3   # FBS_AUDIT_*
+AUDIT_MAX_SAMPLES = 1 << 18   # samples a row one fbs_audit_level_dev call takes
+
 SRC_SEEDED, SRC_FULL, SRC_COMPACT, SRC_PLAIN = 0, 1, 2, 3   # FBS_SRC_*
 
 
@@ -157,6 +165,8 @@ def _load():
         "fbs_level_lincomb_dev": (i32, [vp, vp, u32, vp, sz, sz, sz, vp]),
         "fbs_level_bootstrap_dev": (i32, [vp, vp, u32, vp, sz, sz, sz, sz, sz, vp, vp]),
         "fbs_level_scatter_dev": (i32, [vp, vp, u32, vp, sz, sz, sz, vp, sz, sz, vp]),
+        "fbs_audit_rows": (i32, [vp, u32, u32, C.POINTER(u32), vp]),
+        "fbs_audit_level_dev": (i32, [vp, vp, u32, u32, vp, sz, sz, sz, vp, vp, vp, vp]),
         "fbs_profile_enable": (i32, [vp, i32]),
         "fbs_profile_read": (i32, [vp, C.POINTER(C.c_double * 3), C.POINTER(u64 * 3), i32]),
         "fbs_profile_kernel": (C.c_char_p, [vp, i32]),
@@ -204,6 +214,7 @@ EXPORTED_SYMBOLS = (
     "fbs_packing_keygen", "fbs_packing_key_sizes", "fbs_export_packing_key", "fbs_import_packing_key", "fbs_packed_words",
     "fbs_pack_dev", "fbs_state_fetch_packed", "fbs_decrypt_packed",
     "fbs_pub_expand_dev", "fbs_state_put_public",
+    "fbs_audit_rows", "fbs_audit_level_dev",
 ) + _public_native.EXPORTED_SYMBOLS
 
 lib = _load()
@@ -380,6 +391,31 @@ class Program:
     def level_scatter_dev(self, level, d_wires, T, s_begin, s_count, d_rows, f_begin, f_end, stream=0):
         self.ctx._check(lib.fbs_level_scatter_dev(self.ctx._h, self._h, level, d_wires, T, s_begin, s_count, d_rows, f_begin,
                                                   f_end, stream or None))
+
+    def audit_rows(self, level, point):
+        """The program wire ids (fbs_program_desc numbering: inputs, then instructions) of the rows that point `point`
+        (AUDIT_*) of level `level` reports, in reporting order (fbs_audit_rows) -> np.ndarray uint32"""
+        n = C.c_uint32()
+        self.ctx._check(lib.fbs_audit_rows(self._h, int(level), int(point), C.byref(n), None))
+        ids = np.empty(n.value, np.uint32)
+        self.ctx._check(lib.fbs_audit_rows(self._h, int(level), int(point), C.byref(n), _ptr(ids)))
+        return ids
+
+    def audit_level_dev(self, level, point, d_wires, T, s_begin, s_count, d_expected, errors=False, stream=0):
+        """fbs_audit_level_dev: the exact error statistics of one point of one level of a stepped program.  d_expected: device
+        pointer to int64 [n_rows][s_count], the cleartext value of each row per sample (taken mod 2p).  Blocks.  Returns
+        (stats, errors): stats a list of dicts of Python ints (count, over, max_abs, sum, sumsq -- the 128-bit sum of squares),
+        one per row of `audit_rows(level, point)`; errors int64 [n_rows][s_count] when asked for, else None."""
+        n = C.c_uint32()
+        self.ctx._check(lib.fbs_audit_rows(self._h, int(level), int(point), C.byref(n), None))
+        rows = (_AuditRow * max(1, n.value))()
+        err = np.empty((n.value, int(s_count)), np.int64) if errors else None
+        self.ctx._check(lib.fbs_audit_level_dev(self.ctx._h, self._h, int(level), int(point), d_wires or None, int(T), int(s_begin),
+                                                int(s_count), d_expected or None, C.byref(rows), _ptr(err), stream or None))
+        live = n.value if int(s_count) else 0
+        stats = [dict(count=int(r.count), over=int(r.over), max_abs=int(r.max_abs), sum=int(r.sum),
+                      sumsq=(int(r.sumsq_hi) << 64) | int(r.sumsq_lo)) for r in rows[:live]]
+        return stats, err
 
     def close(self):
         if getattr(self, "_h", None) and self.ctx._h and lib is not None:

@@ -41,6 +41,11 @@ struct BootStage {
     uint32_t *d_x_gate = nullptr;      // [n_extract] position of the shared rotation in the gate list (a level cut across GPUs
                                        // finds the accumulator in that gate's gathered row)
 };
+// rows of one (level, point) of the audit (fbs_audit_rows): program wire id and wire slot of each, in reporting order
+struct AuditRows {
+    std::vector<uint32_t> wire;
+    uint32_t *d_slot = nullptr;   // [wire.size()]
+};
 struct fbs_prog {
     fbs_ctx *ctx = nullptr;
     const fbs_tvset *tv = nullptr;
@@ -57,6 +62,9 @@ struct fbs_prog {
     // schedule: for level L = 0..depth: lincomb stages (dependency order), then the bootstraps of level L+1
     std::vector<std::vector<LincombStage>> lin;   // [depth+1][sub]
     std::vector<BootStage> boot;                  // [depth]  (boot[L] = bootstraps of level L+1)
+    // audited evaluation: what each point of each level reports (inputs: wire i in slot in_slot[i])
+    std::vector<AuditRows> audit_lin, audit_boot;   // [depth+1], [depth]
+    std::vector<std::vector<uint32_t>> audit_src;   // [depth] wire id of each distinct key-switch source
     std::vector<void *> allocations;
 };
 
@@ -121,6 +129,10 @@ static int ensure_acc(fbs_ctx *ctx, size_t rows) {   // a row = a whole GLWE acc
     return grow(ctx, ctx->d_acc, ctx->acc_capacity, rows, (size_t)(ctx->p.k + 1) * ctx->N * 8, true);
 }
 static int ensure_wires(fbs_ctx *ctx, size_t words) { return grow(ctx, ctx->d_wires, ctx->wires_capacity, words, 8, true); }
+static int ensure_audit(fbs_ctx *ctx, size_t rows, size_t words) {   // (not counted: an audit is not a hot path and always blocks)
+    if (int rc = grow(ctx, ctx->d_audit_err, ctx->audit_err_capacity, words, 8, false)) return rc;
+    return grow(ctx, ctx->d_audit_stats, ctx->audit_stats_capacity, rows, sizeof(fbs_audit_row), false);
+}
 static int ensure_io_msgs(fbs_ctx *ctx, size_t words) { return grow(ctx, ctx->d_io_msgs, ctx->io_msgs_capacity, words, 8, true); }
 
 // Cross-stream ordering of the per-context scratch (d_ms, d_idx, d_wires): a call on stream `s` first waits for the last
@@ -275,7 +287,7 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     for (void *p : {(void *)ctx->d_bsk_hat, (void *)ctx->d_bsk_hat_small, (void *)ctx->d_ksk, (void *)ctx->d_ksk_f, (void *)ctx->d_ks_corr, (void *)ctx->d_ks_a, (void *)ctx->d_ks_b, (void *)ctx->d_ks_c, (void *)ctx->d_tw_fwd, (void *)ctx->d_tw_inv, (void *)ctx->d_psi_pow, (void *)ctx->d_ms, (void *)ctx->d_ms_eps, (void *)ctx->d_ms_body, (void *)ctx->d_acc, (void *)ctx->d_stage_in, (void *)ctx->d_stage_out, (void *)ctx->d_stage_ids,
                     (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_sk_lwe_bits, (void *)ctx->d_io_msgs,
                     (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_key, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc,
-                    (void *)ctx->d_packed, (void *)ctx->d_pub})
+                    (void *)ctx->d_packed, (void *)ctx->d_pub, (void *)ctx->d_audit_err, (void *)ctx->d_audit_stats})
         if (p) (void)hipFree(p);
     for (fbs_state *st : ctx->states) {   // the states still alive
         (void)hipFree(st->d);
@@ -853,6 +865,39 @@ int fbs_program_load_ex(fbs_ctx *ctx, const fbs_program_desc *d, const fbs_tvset
             return rc;
         prog->boot[L] = std::move(st);
     }
+    // ---- what the audit reports (fbs_audit_rows): wire id and slot of every row of every (level, point) ---------------------
+    prog->audit_lin.resize(plan.depth + 1);
+    prog->audit_boot.resize(plan.depth);
+    prog->audit_src.resize(plan.depth);
+    for (uint32_t L = 0; L <= plan.depth; L++) {
+        // a LinearProd that only an earlier sub-stage of its level reads may have lent its slot to a later one: the rows are the
+        // wires their slot still holds once every sub-stage has run
+        std::vector<uint32_t> holder(plan.n_slots, 0xFFFFFFFFu), slots;
+        for (const LinPlan &h : plan.lin[L])
+            for (size_t o = 0; o < h.dst.size(); o++) holder[h.dst[o]] = h.dst_wire[o];
+        for (const LinPlan &h : plan.lin[L])
+            for (size_t o = 0; o < h.dst.size(); o++)
+                if (holder[h.dst[o]] == h.dst_wire[o]) {
+                    prog->audit_lin[L].wire.push_back(h.dst_wire[o]);
+                    slots.push_back(h.dst[o]);
+                }
+        if ((rc = to_device(ctx, prog.get(), slots, &prog->audit_lin[L].d_slot))) return rc;
+    }
+    for (uint32_t L = 0; L < plan.depth; L++) {
+        const BootPlan &h = plan.boot[L];
+        std::vector<uint32_t> slots;
+        for (size_t g = 0; g < h.dst.size(); g++)
+            if (h.dst_wire[g] != 0xFFFFFFFFu) {   // (a shared rotation writes no wire)
+                prog->audit_boot[L].wire.push_back(h.dst_wire[g]);
+                slots.push_back(h.dst[g]);
+            }
+        for (size_t e = 0; e < h.x_dst.size(); e++) {
+            prog->audit_boot[L].wire.push_back(h.x_wire[e]);
+            slots.push_back(h.x_dst[e]);
+        }
+        if ((rc = to_device(ctx, prog.get(), slots, &prog->audit_boot[L].d_slot))) return rc;
+        prog->audit_src[L] = h.src_wire;
+    }
     *out = prog.release();
     return FBS_OK;
 } FBS_API_CATCH(ctx)
@@ -929,20 +974,9 @@ int fbs_level_lincomb_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, ui
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
-int fbs_level_bootstrap_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, uint64_t *d_wires, size_t T, size_t s_begin,
-                            size_t s_count, size_t f_begin, size_t f_end, uint64_t *d_rows, void *stream) try {
-    int rc = check_level_call(ctx, prog, d_wires, T, s_begin, s_count);
-    if (rc != FBS_OK) return rc;
-    if (level >= prog->depth) return set_error(ctx, FBS_E_INVALID, "level out of range");
-    const BootStage &b = prog->boot[level];
-    if (f_begin > f_end || f_end > (size_t)b.n_gates * s_count) return set_error(ctx, FBS_E_INVALID, "bad bootstrap range");
-    if (f_begin == f_end) return FBS_OK;   // (covers s_count == 0)
-    // A level with shared rotations: into the wire slots it runs whole (the tables of one source are cut from one accumulator
-    // right after the rotations).  Into rows it can be SLICED: rows are then (k + 1) N words (fbs_layout.row_words), an ordinary gate
-    // leaves its ciphertext in its row and a shared rotation its whole accumulator -- the unit dealt out across GPUs is the
-    // rotation -- and fbs_level_scatter_dev cuts the tables out once every row is there.
-    if (b.n_shared && !d_rows && (f_begin != 0 || f_end != (size_t)b.n_gates * s_count))
-        return set_error(ctx, FBS_E_INVALID, "a level of a fused program runs whole when it writes to the wire slots (slice it into rows)");
+// bootstraps [f_begin, f_end) (f_begin < f_end) of level stage `b` over samples [s_begin, s_begin + s_count), as the launchers see them
+static GateView level_view(const fbs_ctx *ctx, const fbs_prog *prog, const BootStage &b, uint64_t *d_wires, uint64_t *d_rows, size_t T,
+                           size_t s_begin, size_t s_count, size_t f_begin, size_t f_end) {
     // the key switches this slice needs: the (source, sample) pairs of its gates, as ONE flattened range.  Gates are
     // sorted by source, so only the first and the last gate of the slice can be cut short in the sample direction, and
     // only while no other gate of the slice shares their source.
@@ -968,6 +1002,24 @@ int fbs_level_bootstrap_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, 
     gv.ks_begin = u0 * s_count + (first_shared ? 0 : s0);
     gv.ks_count = u1 * s_count + (last_shared ? s_count : s1) - gv.ks_begin;
     gv.n_gates = b.n_gates;
+    return gv;
+}
+
+int fbs_level_bootstrap_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, uint64_t *d_wires, size_t T, size_t s_begin,
+                            size_t s_count, size_t f_begin, size_t f_end, uint64_t *d_rows, void *stream) try {
+    int rc = check_level_call(ctx, prog, d_wires, T, s_begin, s_count);
+    if (rc != FBS_OK) return rc;
+    if (level >= prog->depth) return set_error(ctx, FBS_E_INVALID, "level out of range");
+    const BootStage &b = prog->boot[level];
+    if (f_begin > f_end || f_end > (size_t)b.n_gates * s_count) return set_error(ctx, FBS_E_INVALID, "bad bootstrap range");
+    if (f_begin == f_end) return FBS_OK;   // (covers s_count == 0)
+    // A level with shared rotations: into the wire slots it runs whole (the tables of one source are cut from one accumulator
+    // right after the rotations).  Into rows it can be SLICED: rows are then (k + 1) N words (fbs_layout.row_words), an ordinary gate
+    // leaves its ciphertext in its row and a shared rotation its whole accumulator -- the unit dealt out across GPUs is the
+    // rotation -- and fbs_level_scatter_dev cuts the tables out once every row is there.
+    if (b.n_shared && !d_rows && (f_begin != 0 || f_end != (size_t)b.n_gates * s_count))
+        return set_error(ctx, FBS_E_INVALID, "a level of a fused program runs whole when it writes to the wire slots (slice it into rows)");
+    GateView gv = level_view(ctx, prog, b, d_wires, d_rows, T, s_begin, s_count, f_begin, f_end);
     rc = ensure_ms(ctx, gv.ks_count);
     if (rc != FBS_OK) return rc;
     if (b.n_shared && !d_rows) {
@@ -999,6 +1051,88 @@ int fbs_level_scatter_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, ui
     if (rc != FBS_OK || !b.n_shared) return rc;
     return dev_multi_extract(ctx, prog->tv, d_rows, d_wires, T, s_begin, s_count, b.n_extract, b.d_x_gate, b.d_x_table, b.d_x_dst,
                              pick(ctx, stream));
+} FBS_API_CATCH(ctx)
+
+// ---- audited evaluation (include/fbs_exec.h): the rows of a point, and their exact error statistics -------------------------------
+// FBS_OK and the rows of (level, point): their count, wire ids (null for the inputs: wire i) and device slots; or FBS_E_INVALID
+static int audit_rows_of(const fbs_prog *prog, uint32_t level, uint32_t point, uint32_t *n_rows, const uint32_t **wire, const uint32_t **d_slot) {
+    *wire = nullptr;
+    *d_slot = nullptr;
+    switch (point) {
+    case FBS_AUDIT_INPUTS:
+        *n_rows = prog->n_inputs;
+        *d_slot = prog->d_in_slot;
+        return FBS_OK;
+    case FBS_AUDIT_LINCOMB:
+        if (level > prog->depth) return FBS_E_INVALID;
+        *n_rows = (uint32_t)prog->audit_lin[level].wire.size();
+        *wire = prog->audit_lin[level].wire.data();
+        *d_slot = prog->audit_lin[level].d_slot;
+        return FBS_OK;
+    case FBS_AUDIT_ROTATION_INPUT:
+        if (level >= prog->depth) return FBS_E_INVALID;
+        *n_rows = (uint32_t)prog->audit_src[level].size();
+        *wire = prog->audit_src[level].data();
+        *d_slot = prog->boot[level].d_src_slot;
+        return FBS_OK;
+    case FBS_AUDIT_BOOTSTRAP:
+        if (level >= prog->depth) return FBS_E_INVALID;
+        *n_rows = (uint32_t)prog->audit_boot[level].wire.size();
+        *wire = prog->audit_boot[level].wire.data();
+        *d_slot = prog->audit_boot[level].d_slot;
+        return FBS_OK;
+    default:
+        return FBS_E_INVALID;
+    }
+}
+
+int fbs_audit_rows(const fbs_prog *prog, uint32_t level, uint32_t point, uint32_t *n_rows, uint32_t *wire_ids) try {
+    if (!prog || !n_rows) return FBS_E_INVALID;
+    const uint32_t *wire, *d_slot;
+    if (audit_rows_of(prog, level, point, n_rows, &wire, &d_slot) != FBS_OK)
+        return set_error(prog->ctx, FBS_E_INVALID, "no such level or point to audit");
+    if (wire_ids)
+        for (uint32_t r = 0; r < *n_rows; r++) wire_ids[r] = wire ? wire[r] : r;
+    return FBS_OK;
+} FBS_API_CATCH(prog ? prog->ctx : nullptr)
+
+int fbs_audit_level_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, uint32_t point, const uint64_t *d_wires, size_t T,
+                        size_t s_begin, size_t s_count, const int64_t *d_expected, fbs_audit_row *stats, int64_t *errors, void *stream) try {
+    int rc = check_prog(ctx, prog);
+    if (rc != FBS_OK) return rc;
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    uint32_t n_rows = 0;
+    const uint32_t *wire, *d_slot;
+    if (audit_rows_of(prog, level, point, &n_rows, &wire, &d_slot) != FBS_OK)
+        return set_error(ctx, FBS_E_INVALID, "no such level or point to audit");
+    if (s_begin > T || s_count > T - s_begin) return set_error(ctx, FBS_E_INVALID, "bad sample range");
+    if (n_rows == 0 || s_count == 0) return FBS_OK;
+    if (!d_wires || !d_expected || !stats) return set_error(ctx, FBS_E_INVALID, "null argument");
+    // the bound under which the reduction's 64-bit sum and 128-bit sum of squares cannot overflow (fbs_audit.hip)
+    if (s_count > AUDIT_MAX_SAMPLES) return set_error(ctx, FBS_E_INVALID, "more than 2^18 samples in one audit call");
+    const size_t total = (size_t)n_rows * s_count;
+    const bool fields = point == FBS_AUDIT_ROTATION_INPUT;
+    if ((rc = ensure_audit(ctx, n_rows, total)) != FBS_OK) return rc;
+    if (fields && (rc = ensure_ms(ctx, total)) != FBS_OK) return rc;
+    hipStream_t s = pick(ctx, stream);
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    if (fields) {
+        // the key switch of fbs_level_bootstrap_dev(level) over the level's full range: the same view, the same width, the same scratch
+        const BootStage &b = prog->boot[level];
+        const GateView gv = level_view(ctx, prog, b, const_cast<uint64_t *>(d_wires), nullptr, T, s_begin, s_count, 0, (size_t)b.n_gates * s_count);
+        if ((rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+        rc = dev_audit_fields(ctx, ctx->d_ms, n_rows, s_count, d_expected, ctx->d_audit_err, s);
+    } else {
+        rc = dev_audit_wire(ctx, d_wires, d_slot, n_rows, T, s_begin, s_count, d_expected, ctx->d_audit_err, s);
+    }
+    if (rc != FBS_OK || (rc = dev_audit_reduce(ctx, ctx->d_audit_err, n_rows, s_count, fields, ctx->d_audit_stats, s)) != FBS_OK)
+        return scratch_fail(ctx, s, rc);
+    if (hipMemcpyAsync(stats, ctx->d_audit_stats, (size_t)n_rows * sizeof(fbs_audit_row), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        (errors && hipMemcpyAsync(errors, ctx->d_audit_err, total * 8, hipMemcpyDeviceToHost, s) != hipSuccess))
+        return scratch_fail(ctx, s, set_error(ctx, FBS_E_DEVICE, "copying the audit's results back failed"));
+    if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
+    FBS_HIP(ctx, hipStreamSynchronize(s));
+    return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 static int run_levels(fbs_ctx *ctx, const fbs_prog *prog, uint64_t *d_wires, size_t T, size_t s_count, hipStream_t s) {

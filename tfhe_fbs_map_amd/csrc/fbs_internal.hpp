@@ -251,6 +251,10 @@ struct fbs_ctx : fbs::HostState {
     fbs_tvset *tv_identity = nullptr;   // the identity table [0, 1, .., p - 1], made on first use: what refreshes a compact input
     int64_t *d_io_msgs = nullptr;    // scratch: messages of fbs_eval_messages, [n_inputs + n_outputs][chunk]
     size_t io_msgs_capacity = 0;     // in words
+    int64_t *d_audit_err = nullptr;  // scratch of fbs_audit_level_dev: the errors [rows][s_count]
+    size_t audit_err_capacity = 0;   // in words
+    fbs_audit_row *d_audit_stats = nullptr;   // and the statistics [rows]
+    size_t audit_stats_capacity = 0; // in rows
     uint64_t *d_wires = nullptr;     // wire slots of fbs_eval, shared by every program of the context
     size_t wires_capacity = 0;       // in words
     // The scratch buffers above are shared by every call on the context.  Calls on ONE stream are ordered by the
@@ -442,6 +446,18 @@ int dev_compact_unpack(const fbs_ctx *ctx, const uint64_t *d_words, size_t count
 int dev_upload_packing_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_p);
 uint32_t pack_slices_for(const fbs_ctx *ctx, size_t samples);
 int dev_pack(fbs_ctx *ctx, const uint32_t *d_ms, size_t count, uint32_t bits, uint64_t *d_words, hipStream_t stream);
+
+// audited evaluation (fbs_audit.hip): errors of the big-key ciphertexts in slots d_row_slot[rows], samples [s_begin, s_begin + s_count),
+// against d_expected [rows][s_count] -> d_err [rows][s_count] (wire units); of the switched fields d_ms [rows * s_count][n + 1] at
+// log2(2N) bits (field units); and the exact statistics of each row of d_err -> d_stats [rows].  One call takes at most
+// AUDIT_MAX_SAMPLES samples a row: below that neither the 64-bit sum nor the 128-bit sum of squares can overflow
+constexpr size_t AUDIT_MAX_SAMPLES = (size_t)1 << 18;
+int dev_audit_wire(const fbs_ctx *ctx, const uint64_t *d_wires, const uint32_t *d_row_slot, size_t rows, size_t T, size_t s_begin,
+                   size_t s_count, const int64_t *d_expected, int64_t *d_err, hipStream_t stream);
+int dev_audit_fields(const fbs_ctx *ctx, const uint32_t *d_ms, size_t rows, size_t s_count, const int64_t *d_expected, int64_t *d_err,
+                     hipStream_t stream);
+int dev_audit_reduce(const fbs_ctx *ctx, const int64_t *d_err, size_t rows, size_t s_count, bool fields, fbs_audit_row *d_stats,
+                     hipStream_t stream);
 
 // resident state (fbs_state.hip): the links of `a` between state rows and wire slots, one launch each
 int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);

@@ -119,7 +119,7 @@ int plan_program(const fbs_program_desc *d, uint32_t n_tables, const uint8_t *fu
     plan.lin.assign(depth + 1, {});
     plan.boot.assign(depth, {});
     struct Gate {
-        uint32_t src, dst, tab;
+        uint32_t src, dst, tab, wire;
     };
     std::vector<std::vector<Gate>> bh(depth);
     for (uint32_t i = 0; i < d->n_instr; i++) {
@@ -129,6 +129,7 @@ int plan_program(const fbs_program_desc *d, uint32_t n_tables, const uint8_t *fu
             if (stages.size() <= sub[w]) stages.resize(sub[w] + 1);   // (kept even when empty: stage times above count every sub-stage)
             LinPlan &h = stages[sub[w]];
             h.dst.push_back(slot[w]);
+            h.dst_wire.push_back(w);
             for (uint32_t t = d->arg0[i]; t < d->arg0[i] + d->arg1[i]; t++) {
                 h.srcs.push_back(slot[d->term_src[t]]);
                 h.coefs.push_back(d->term_coef[t]);
@@ -136,7 +137,7 @@ int plan_program(const fbs_program_desc *d, uint32_t n_tables, const uint8_t *fu
             h.off.push_back((uint32_t)h.srcs.size());
             h.consts.push_back(d->const_coef[i]);
         } else {
-            bh[level[w] - 1].push_back({d->arg0[i], slot[w], d->arg1[i]});
+            bh[level[w] - 1].push_back({d->arg0[i], slot[w], d->arg1[i], w});
         }
     }
     for (uint32_t L = 0; L < depth; L++) {
@@ -147,6 +148,7 @@ int plan_program(const fbs_program_desc *d, uint32_t n_tables, const uint8_t *fu
             size_t e = g;
             while (e < gates.size() && gates[e].src == gates[g].src) e++;
             st.src_slot.push_back(slot[gates[g].src]);
+            st.src_wire.push_back(gates[g].src);
             const uint32_t u = (uint32_t)st.src_slot.size() - 1;
             // fused: the tables of this source that k_multi_extract can serve share one rotation of TV_0, if there are
             // at least two of them; the others keep a rotation of their own
@@ -158,6 +160,7 @@ int plan_program(const fbs_program_desc *d, uint32_t n_tables, const uint8_t *fu
             if (share) {
                 st.source_of.push_back(u);
                 st.dst.push_back(0x80000000u | st.n_shared);
+                st.dst_wire.push_back(0xFFFFFFFFu);
                 st.table.push_back(n_tables);
             }
             for (size_t i = g; i < e; i++) {
@@ -166,9 +169,11 @@ int plan_program(const fbs_program_desc *d, uint32_t n_tables, const uint8_t *fu
                     st.x_gate.push_back(shared_at);
                     st.x_table.push_back(gates[i].tab);
                     st.x_dst.push_back(gates[i].dst);
+                    st.x_wire.push_back(gates[i].wire);
                 } else {
                     st.source_of.push_back(u);
                     st.dst.push_back(gates[i].dst);
+                    st.dst_wire.push_back(gates[i].wire);
                     st.table.push_back(gates[i].tab);
                 }
             }

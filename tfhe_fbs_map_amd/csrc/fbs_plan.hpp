@@ -16,6 +16,7 @@ namespace fbs {
 struct LinPlan {
     std::vector<uint32_t> dst, off{0}, srcs;   // wire SLOTS; off[o] .. off[o + 1]: the terms of output o
     std::vector<int64_t> coefs, consts;        // as in the description (the caller maps them into the field)
+    std::vector<uint32_t> dst_wire;            // [n_out] program wire id of each output (fbs_audit_rows)
 };
 // Bootstraps of one level, sorted by source wire.  Gates that read the same wire (the reference's one-gate-one-bootstrap
 // lowering emits several tables per linear combination, fbs_mapper/map_to_fbs.py:41-45, and its CSE only merges identical
@@ -27,6 +28,9 @@ struct BootPlan {
     // (table id = n_tables, dst = 0x80000000 | shared index) -- and one entry each of the extraction list below
     uint32_t n_shared = 0;
     std::vector<uint32_t> x_row, x_table, x_dst, x_gate;   // [n_extract] shared index, table, wire slot, position of the rotation in the gate list
+    // program wire ids, for the audit (fbs_audit_rows): of each source, of each gate's output (0xFFFFFFFF: a shared rotation, which
+    // writes no wire) and of each extraction's output
+    std::vector<uint32_t> src_wire, dst_wire, x_wire;
 };
 struct ProgramPlan {
     uint32_t n_wires = 0, n_slots = 0, depth = 0, max_width = 0, max_sources = 0, max_shared = 0;

@@ -535,6 +535,17 @@ class LutExecEnv:
             result[name] = (-1 - w) if w < 0 else out[k].astype(int)
         return result
 
+    def audit(self, input_values, config: ExecConfig | None = None, points=("rotation_input",), chunk=None):
+        """`eval` with the noise measured on the way (no counterpart in the reference): the same parameter choice, program and
+        nonces, stepped level by level, and at every point of `points` -- "inputs", "lincomb", "rotation_input", "bootstrap" --
+        the exact error of every ciphertext against the program's cleartext value, reduced on the GPU.  Returns an
+        `audit.AuditReport`: per audited wire the measured mean, standard deviation and margin beside the model's, the samples at
+        half a box or beyond (`over`), and over all of them `min_margin`, `failures`, `first_failure`, `worst(n)`, `to_json()` and
+        `outputs`, what `eval` returns.  Needs the secret key, like `eval`.  chunk: samples per step (None: what fits half of the
+        free device memory)."""
+        from .audit import run_audit
+        return run_audit(self, input_values, config, points, chunk)
+
 
 FbsExecEnv = LutExecEnv
 
