@@ -63,7 +63,7 @@ def test_client_target_uses_no_gpu_toolchain():
     assert "__HIP_PLATFORM_AMD__" not in out
     for flag in ("-std=c++17", "-O3", "-fPIC", "-pthread", "-ffp-contract=off"):
         assert flag in out, flag
-    for src in ("fbs_plan.cpp", "fbs_select.cpp", "fbs_capi.cpp", ".hip"):
+    for src in ("fbs_plan.cpp", "fbs_select.cpp", "fbs_capi.cpp", "fbs_eval.cpp", ".hip"):
         assert src not in out, src
 
 

@@ -96,6 +96,29 @@ def _srcs(nat, kinds):
     return arr
 
 
+def eval_dev_of_expansion(ctx, prog, bodies, T, nonce0):
+    """fbs_eval_dev on what fbs_expand_seeded_dev makes of the bodies: the device entry keeps a load and a store of its own, and
+    the expansion is one flat run of streams, so nothing here goes through the code the host-buffer entries share"""
+    import torch
+    bodies = np.ascontiguousarray(bodies, np.uint64).reshape(-1)
+    ctw = ctx.params.ct_words
+    d_in = torch.full((bodies.size, ctw), 7, dtype=torch.int64, device="cuda")
+    ctx.expand_seeded_dev(dev(bodies).data_ptr(), bodies.size, nonce0, d_in.data_ptr())
+    d_out = torch.full((prog.n_outputs, T, ctw), 7, dtype=torch.int64, device="cuda")
+    prog.eval_dev(d_in.data_ptr(), T, d_out.data_ptr())
+    ctx.sync()
+    return host(d_out)
+
+
+def host_entries_are_eval_dev_of_the_expansion(client, ctx, prog, bodies, T, nonce0):
+    """fbs_eval_seeded and fbs_eval are eval_sources over sources they build themselves (input i at bodies + i T on stream
+    nonce0 + i T, or at cts + i T (D + 1)): word for word what the device entry returns.  Returns those words."""
+    want = eval_dev_of_expansion(ctx, prog, bodies, T, nonce0)
+    assert np.array_equal(prog.eval_seeded(bodies, T, nonce0), want)
+    assert np.array_equal(prog.eval(client.expand_seeded(bodies, nonce0), T), want)
+    return want
+
+
 def test_eval_sources_with_seeded_sources_is_eval_seeded(monkeypatch):
     from tfhe_fbs_map_amd import Context, FbsError, _native as nat
     client, server = _pair("k1_n1024")
@@ -107,6 +130,7 @@ def test_eval_sources_with_seeded_sources_is_eval_seeded(monkeypatch):
     b = server.params.log_n_poly + 1
     seeded = [("seeded", bodies[i], nonce0 + i * T) for i in range(n_in)]
     full = prog.eval_seeded(bodies, T, nonce0)
+    assert np.array_equal(host_entries_are_eval_dev_of_the_expansion(client, server, prog, bodies, T, nonce0), full)
     assert np.array_equal(prog.eval_sources(seeded, T), full)
     for bits in (b, b + 2):
         assert np.array_equal(prog.eval_sources(seeded, T, bits), prog.eval_seeded_compact(bodies, T, nonce0, bits))
@@ -134,9 +158,19 @@ def test_eval_sources_with_seeded_sources_is_eval_seeded(monkeypatch):
     fresh = Context.evaluation_only(client.params, **client.export_seeded_keys())
     _, _, cprog = _program(fresh, "adder8__search_p7")
     assert np.array_equal(cprog.eval_sources(seeded, T), full)
+    assert np.array_equal(host_entries_are_eval_dev_of_the_expansion(client, fresh, cprog, bodies, T, nonce0), full)   # ragged chunks
     assert np.array_equal(cprog.eval_sources(seeded, T, b + 2), prog.eval_seeded_compact(bodies, T, nonce0, b + 2))
     assert np.array_equal(cprog.eval_sources(mixed, T), first)
     monkeypatch.delenv("FBS_WIRE_BUDGET_MB")
+    # constant outputs and outputs that are inputs: the trivial-ciphertext store, two inputs' stream offsets
+    erec, elow, eprog = _program(server, "edge_outputs")
+    e_ins, e_expect = subsample(erec, 3)
+    e_bodies, e_nonce0 = client.encrypt_seeded(np.stack([np.asarray(e_ins[k], np.int64) for k in elow["input_names"]]), nonce0=900)
+    e_out = host_entries_are_eval_dev_of_the_expansion(client, server, eprog, e_bodies, 3, e_nonce0)
+    for k, name in enumerate(elow["out_names"]):
+        e = e_expect[name]
+        assert np.array_equal(client.decrypt(e_out[k]), np.full(3, e) if np.ndim(e) == 0 else np.asarray(e)), name
+    assert any(w < 0 for w in elow["out_wire"])
     # refusals: a code, and nothing written
     lib, h = nat.lib, server._h
     ctw = server.params.ct_words

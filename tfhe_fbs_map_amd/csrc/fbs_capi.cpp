@@ -1,5 +1,5 @@
-// extern "C" surface of libfbsexec.so (declared in include/fbs_exec.h) and the level-scheduled
-// program executor that stands behind `LutExecEnv.eval` (reference fbs_mapper/fbs_exec_env.py:208-229).
+// extern "C" surface of libfbsexec.so (declared in include/fbs_exec.h): contexts, keys, inputs and outputs, the loaded program and
+// its level calls.  The whole-program evaluations that stand behind `LutExecEnv.eval` are fbs_eval.cpp's.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -19,55 +19,6 @@ using namespace fbs;
 // ---------------------------------------------------------------------------------------------
 // program representation
 // ---------------------------------------------------------------------------------------------
-struct LincombStage {
-    uint32_t n_out = 0;
-    uint32_t *d_dst = nullptr, *d_term_off = nullptr, *d_srcs = nullptr;   // wire SLOTS
-    uint64_t *d_coefs = nullptr, *d_consts = nullptr;
-};
-// Bootstraps of one level, sorted by source wire.  Gates that read the same wire (the reference's one-gate-one-bootstrap
-// lowering emits several tables per linear combination, fbs_mapper/map_to_fbs.py:41-45, and its CSE only merges
-// identical tables, fbs_mapper/fbs_exec_env.py:93-100) share one key switch + modulus switch.
-struct BootStage {
-    uint32_t n_gates = 0, n_sources = 0;
-    uint32_t *d_src_slot = nullptr;    // [n_sources] wire slot of each distinct source
-    uint32_t *d_source_of = nullptr;   // [n_gates]   index into d_src_slot
-    uint32_t *d_dst = nullptr, *d_table = nullptr;   // [n_gates]
-    std::vector<uint32_t> source_of;   // host copy: which key switches a slice of the level needs
-    // Fused programs (FBS_LOAD_FUSE_TABLES): the tables of a source that several read are served by ONE gate of the list
-    // above -- the rotation of TV_0 (table id = the set's n_tables, dst = 0x80000000 | shared index) -- and one entry each
-    // of the extraction list below (k_multi_extract)
-    uint32_t n_shared = 0, n_extract = 0;
-    uint32_t *d_x_row = nullptr, *d_x_table = nullptr, *d_x_dst = nullptr;   // [n_extract] shared index, table, wire slot
-    uint32_t *d_x_gate = nullptr;      // [n_extract] position of the shared rotation in the gate list (a level cut across GPUs
-                                       // finds the accumulator in that gate's gathered row)
-};
-// rows of one (level, point) of the audit (fbs_audit_rows): program wire id and wire slot of each, in reporting order
-struct AuditRows {
-    std::vector<uint32_t> wire;
-    uint32_t *d_slot = nullptr;   // [wire.size()]
-};
-struct fbs_prog {
-    fbs_ctx *ctx = nullptr;
-    const fbs_tvset *tv = nullptr;
-    uint32_t n_inputs = 0, n_instr = 0, n_outputs = 0, n_wires = 0, n_slots = 0;
-    uint32_t depth = 0, max_width = 0, max_sources = 0, n_bootstrap = 0, n_keyswitch = 0;
-    uint32_t n_rotations = 0, max_shared = 0;   // blind rotations per sample (= n_bootstrap unless fused); shared rotations of the widest level
-    bool fused = false;
-    std::vector<uint32_t> in_slot;    // [n_inputs]
-    std::vector<int64_t> out_slot;    // [n_outputs]  slot, or -1-c for the constant c
-    uint32_t *d_in_slot = nullptr;    // [n_inputs]   the same on the device (fbs_eval_messages)
-    uint32_t *d_out_slot = nullptr;   // [n_outputs]  slot, or 0xFFFFFFFF for a constant
-    std::vector<uint32_t> live_out;   // the outputs that are wires, not constants, in output order
-    uint32_t *d_live_slot = nullptr;  // [live_out.size()] their slots (the key switches of fbs_eval_seeded_compact read them)
-    // schedule: for level L = 0..depth: lincomb stages (dependency order), then the bootstraps of level L+1
-    std::vector<std::vector<LincombStage>> lin;   // [depth+1][sub]
-    std::vector<BootStage> boot;                  // [depth]  (boot[L] = bootstraps of level L+1)
-    // audited evaluation: what each point of each level reports (inputs: wire i in slot in_slot[i])
-    std::vector<AuditRows> audit_lin, audit_boot;   // [depth+1], [depth]
-    std::vector<std::vector<uint32_t>> audit_src;   // [depth] wire id of each distinct key-switch source
-    std::vector<void *> allocations;
-};
-
 template <typename T>
 static int to_device(fbs_ctx *ctx, fbs_prog *prog, const std::vector<T> &v, T **out) {
     *out = nullptr;
@@ -88,11 +39,14 @@ static uint64_t coef_bits(int64_t c) {
     return u;
 }
 
-static hipStream_t pick(const fbs_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+// ---- helpers of the entries, shared with fbs_eval.cpp (declared in fbs_internal.hpp) ------------------------------------------
+namespace fbs {
+
+hipStream_t pick(const fbs_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 
 // Scratch is grown on demand, and growing it BLOCKS (the old buffers may still be read by queued kernels): a host that wants
 // its *_dev calls to be nothing but kernel launches sizes everything up front with fbs_ctx_reserve.
-static int ensure_ms(fbs_ctx *ctx, size_t count) {
+int ensure_ms(fbs_ctx *ctx, size_t count) {
     if (int rc = dev_keyswitch_reserve(ctx, count)) return rc;   // (the int8-GEMM key switch's digit and limb-sum scratch)
     if (count <= ctx->ms_capacity) return FBS_OK;
     ctx->scratch_growths++;
@@ -112,36 +66,23 @@ static int ensure_ms(fbs_ctx *ctx, size_t count) {
     return FBS_OK;
 }
 
-// one scratch buffer of `count` elements of `bytes` each; `counted`: a growth shows in scratch_growths
-template <typename T>
-static int grow(fbs_ctx *ctx, T *&buf, size_t &capacity, size_t count, size_t bytes, bool counted) {
-    if (count <= capacity) return FBS_OK;
-    if (counted) ctx->scratch_growths++;
-    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));   // kernels may still read the old buffer
-    if (buf) (void)hipFree(buf);
-    buf = nullptr;
-    capacity = 0;
-    FBS_HIP(ctx, hipMalloc(&buf, count * bytes));
-    capacity = count;
-    return FBS_OK;
-}
-static int ensure_acc(fbs_ctx *ctx, size_t rows) {   // a row = a whole GLWE accumulator
+int ensure_acc(fbs_ctx *ctx, size_t rows) {   // a row = a whole GLWE accumulator
     return grow(ctx, ctx->d_acc, ctx->acc_capacity, rows, (size_t)(ctx->p.k + 1) * ctx->N * 8, true);
 }
-static int ensure_wires(fbs_ctx *ctx, size_t words) { return grow(ctx, ctx->d_wires, ctx->wires_capacity, words, 8, true); }
+int ensure_wires(fbs_ctx *ctx, size_t words) { return grow(ctx, ctx->d_wires, ctx->wires_capacity, words, 8, true); }
 static int ensure_audit(fbs_ctx *ctx, size_t rows, size_t words) {   // (not counted: an audit is not a hot path and always blocks)
     if (int rc = grow(ctx, ctx->d_audit_err, ctx->audit_err_capacity, words, 8, false)) return rc;
     return grow(ctx, ctx->d_audit_stats, ctx->audit_stats_capacity, rows, sizeof(fbs_audit_row), false);
 }
-static int ensure_io_msgs(fbs_ctx *ctx, size_t words) { return grow(ctx, ctx->d_io_msgs, ctx->io_msgs_capacity, words, 8, true); }
+int ensure_io_msgs(fbs_ctx *ctx, size_t words) { return grow(ctx, ctx->d_io_msgs, ctx->io_msgs_capacity, words, 8, true); }
 
 // Cross-stream ordering of the per-context scratch (d_ms, d_idx, d_wires): a call on stream `s` first waits for the last
 // call that used the scratch on ANOTHER stream; calls on one stream are ordered by the stream itself.
-static int scratch_wait(fbs_ctx *ctx, hipStream_t s) {
+int scratch_wait(fbs_ctx *ctx, hipStream_t s) {
     if (ctx->scratch_used && ctx->scratch_stream != s) FBS_HIP(ctx, hipStreamWaitEvent(s, ctx->scratch_event, 0));
     return FBS_OK;
 }
-static int scratch_done(fbs_ctx *ctx, hipStream_t s) {
+int scratch_done(fbs_ctx *ctx, hipStream_t s) {
     FBS_HIP(ctx, hipEventRecord(ctx->scratch_event, s));
     ctx->scratch_stream = s;
     ctx->scratch_used = true;
@@ -150,7 +91,7 @@ static int scratch_done(fbs_ctx *ctx, hipStream_t s) {
 
 // A call that fails between scratch_wait and scratch_done may have left the "zero between launches" scratch (rounding-error
 // sums, limb sums of the GEMM key switch) half used: put it back, so that the next call on the context starts clean.
-static int scratch_fail(fbs_ctx *ctx, hipStream_t s, int rc) {
+int scratch_fail(fbs_ctx *ctx, hipStream_t s, int rc) {
     if (ctx->d_ms_eps && ctx->ms_capacity) (void)hipMemsetAsync(ctx->d_ms_eps, 0, ctx->ms_capacity * 8, s);
     (void)dev_keyswitch_rezero(ctx, s);
     (void)scratch_done(ctx, s);
@@ -158,7 +99,7 @@ static int scratch_fail(fbs_ctx *ctx, hipStream_t s, int rc) {
 }
 
 // the plain batch: gate g = ciphertext g, one sample each
-static GateView batch_view(const uint64_t *in, uint64_t *out, const uint32_t *table_ids, size_t count) {
+GateView batch_view(const uint64_t *in, uint64_t *out, const uint32_t *table_ids, size_t count) {
     GateView gv{};
     gv.in_base = in;
     gv.out_base = out;
@@ -173,6 +114,71 @@ static GateView batch_view(const uint64_t *in, uint64_t *out, const uint32_t *ta
     gv.n_gates = (uint32_t)count;
     return gv;
 }
+
+// `ng` wire slots (d_slot [ng], device) of a chunk of `tc` samples in a buffer of Tc a slot: gate g reads slot d_slot[g] of `in`
+// and, `out` given, writes the same slot of `out`
+GateView slots_view(const uint64_t *in, uint64_t *out, const uint32_t *d_slot, size_t ng, size_t Tc, size_t tc) {
+    GateView gv{};   // (the window and both ranges start at 0)
+    gv.in_base = in, gv.out_base = out, gv.src_slot = d_slot, gv.dst_slot = out ? d_slot : nullptr;
+    gv.T = Tc, gv.s_count = tc, gv.count = gv.ks_count = ng * tc, gv.n_gates = (uint32_t)ng;
+    return gv;
+}
+
+// `count` ciphertexts through the modulus-switch scratch in passes of what the context has of it, or of COMPACT_PASS when it has
+// less: `pass(f0, rows)` queues ciphertexts [f0, f0 + rows) on `s`
+size_t ms_pass_size(const fbs_ctx *ctx, size_t count) { return std::min(count, std::max(ctx->ms_capacity, COMPACT_PASS)); }
+int ms_passes(fbs_ctx *ctx, size_t count, hipStream_t s, const std::function<int(size_t f0, size_t rows)> &pass) {
+    const size_t per_pass = ms_pass_size(ctx, count);
+    int rc = ensure_ms(ctx, per_pass);
+    if (rc != FBS_OK) return rc;
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    for (size_t f0 = 0; f0 < count; f0 += per_pass)
+        if ((rc = pass(f0, std::min(per_pass, count - f0))) != FBS_OK) return scratch_fail(ctx, s, rc);
+    return scratch_done(ctx, s);
+}
+
+int sync_stream(fbs_ctx *ctx, hipStream_t s) {
+    FBS_HIP(ctx, hipStreamSynchronize(s));
+    return FBS_OK;
+}
+
+// what the entries that launch check first: the keys, the owner of a table set or a program, the device
+static int check_ready(fbs_ctx *ctx, const fbs_tvset *tv) {
+    if (!ctx) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (tv && tv->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "test-vector set belongs to another context");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return FBS_OK;
+}
+
+int check_prog(fbs_ctx *ctx, const fbs_prog *prog) {
+    int rc = check_ready(ctx, prog ? prog->tv : nullptr);
+    if (rc != FBS_OK) return rc;
+    if (!prog || prog->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "program belongs to another context");
+    return FBS_OK;
+}
+
+int ensure_idx(fbs_ctx *ctx, size_t words) {   // (not counted in scratch_growths)
+    return words <= ctx->idx_capacity ? FBS_OK : grow(ctx, ctx->d_idx, ctx->idx_capacity, std::max<size_t>(words, 1 << 16), 4, false);
+}
+
+// the context's identity table [0, 1, .., p - 1], made on first use: a blind rotation through it is a refresh
+int identity_tv(fbs_ctx *ctx, fbs_tvset **out) {
+    if (!ctx->tv_identity) {
+        std::vector<int32_t> vals(ctx->p.p_msg);
+        for (uint32_t v = 0; v < ctx->p.p_msg; v++) vals[v] = (int32_t)v;
+        const uint32_t off[2] = {0, ctx->p.p_msg};
+        if (int rc = fbs_tvset_create(ctx, vals.data(), off, 1, &ctx->tv_identity)) return rc;
+    }
+    *out = ctx->tv_identity;
+    return FBS_OK;
+}
+
+bool state_of(const fbs_ctx *ctx, const fbs_state *st) {   // (by address: a foreign or stale pointer is never dereferenced)
+    return st && std::find(ctx->states.begin(), ctx->states.end(), st) != ctx->states.end();
+}
+
+}   // namespace fbs
 
 extern "C" {
 
@@ -631,14 +637,6 @@ void fbs_tvset_destroy(fbs_tvset *tv) try {
 }
 
 // ---------------------------------------------------------------------------------------------
-static int check_ready(fbs_ctx *ctx, const fbs_tvset *tv) {
-    if (!ctx) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (tv && tv->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "test-vector set belongs to another context");
-    FBS_HIP(ctx, hipSetDevice(ctx->device));
-    return FBS_OK;
-}
-
 int fbs_bootstrap_batch_dev(fbs_ctx *ctx, const fbs_tvset *tv, const uint64_t *d_cts_in, const uint32_t *d_table_ids,
                             size_t count, uint64_t *d_cts_out, void *stream) try {
     int rc = check_ready(ctx, tv);
@@ -700,10 +698,6 @@ int fbs_bootstrap_batch(fbs_ctx *ctx, const fbs_tvset *tv, const uint64_t *cts_i
 // per-context buffer and waits for the copy; hosts that step a loaded program use the fbs_level_* calls below,
 // whose index arrays were uploaded once by fbs_program_load)
 // ---------------------------------------------------------------------------------------------
-static int ensure_idx(fbs_ctx *ctx, size_t words) {   // (not counted in scratch_growths)
-    return words <= ctx->idx_capacity ? FBS_OK : grow(ctx, ctx->d_idx, ctx->idx_capacity, std::max<size_t>(words, 1 << 16), 4, false);
-}
-
 int fbs_lincomb_dev(fbs_ctx *ctx, uint64_t *d_wires, size_t T, uint32_t n_out, const uint32_t *dst, const uint32_t *term_off,
                     const uint32_t *srcs, const int64_t *coefs, const int64_t *consts, void *stream) try {
     int rc = check_ready(ctx, nullptr);
@@ -948,12 +942,6 @@ int fbs_program_io_slots(const fbs_prog *prog, uint32_t *in_slot, int64_t *out_s
 } FBS_API_CATCH(prog ? prog->ctx : nullptr)
 
 // ---- one level at a time, device-resident wires, nothing but kernel launches on `stream` ------------------------
-static int check_prog(fbs_ctx *ctx, const fbs_prog *prog) {
-    int rc = check_ready(ctx, prog ? prog->tv : nullptr);
-    if (rc != FBS_OK) return rc;
-    if (!prog || prog->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "program belongs to another context");
-    return FBS_OK;
-}
 static int check_level_call(fbs_ctx *ctx, const fbs_prog *prog, const uint64_t *d_wires, size_t T, size_t s_begin, size_t s_count) {
     if (int rc = check_prog(ctx, prog)) return rc;
     if (!d_wires) return set_error(ctx, FBS_E_INVALID, "null argument");
@@ -1135,308 +1123,7 @@ int fbs_audit_level_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, uint
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
-static int run_levels(fbs_ctx *ctx, const fbs_prog *prog, uint64_t *d_wires, size_t T, size_t s_count, hipStream_t s) {
-    int rc;
-    for (uint32_t L = 0; L <= prog->depth; L++) {
-        if ((rc = fbs_level_lincomb_dev(ctx, prog, L, d_wires, T, 0, s_count, s)) != FBS_OK) return rc;
-        if (L == prog->depth) break;
-        const size_t total = (size_t)prog->boot[L].n_gates * s_count;
-        if ((rc = fbs_level_bootstrap_dev(ctx, prog, L, d_wires, T, 0, s_count, 0, total, nullptr, s)) != FBS_OK) return rc;
-    }
-    return FBS_OK;
-}
-
-// Samples are independent through the whole program: evaluate in chunks whose wire slots fit in HBM.  The wire buffer
-// belongs to the context and is shared by all of its programs (it only ever grows).
-// `extra_per_sample`: bytes per sample of a further buffer the caller sizes by the chunk (the packed staging of compact outputs)
-static int reserve_wires(fbs_ctx *ctx, const fbs_prog *prog, size_t T, size_t *chunk, size_t extra_per_sample = 0) {
-    const size_t ctw = ctx->D + 1;
-    const size_t per_sample = (size_t)prog->n_slots * ctw * 8 + (size_t)std::max(1u, prog->max_sources) * (ctx->p.n + 1) * 4 +
-                              (size_t)prog->max_shared * (ctx->p.k + 1) * ctx->N * 8 + extra_per_sample;
-    size_t free_b = 0, total_b = 0;
-    FBS_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-    size_t have = free_b + ctx->wires_capacity * 8 + ctx->ms_capacity * (ctx->p.n + 1) * 4 + ctx->acc_capacity * (size_t)(ctx->p.k + 1) * ctx->N * 8;
-    if (extra_per_sample) have += ctx->compact_capacity * 8;   // (the compact path reuses its packed staging; no other call does)
-    // test hook: FBS_WIRE_BUDGET_MB caps what the wire slots may take, so that the chunked path runs at small sizes
-    if (const char *cap = getenv("FBS_WIRE_BUDGET_MB")) have = std::min<size_t>(have, (size_t)std::max(1, atoi(cap)) << 20);
-    const size_t Tc = std::min<size_t>(T, std::max<size_t>(1, (size_t)(0.6 * (double)have) / per_sample));
-    const size_t words = Tc * (size_t)prog->n_slots * ctw;
-    int rc = ensure_wires(ctx, words);
-    if (rc != FBS_OK) return rc;
-    rc = ensure_ms(ctx, (size_t)std::max(1u, prog->max_sources) * Tc);
-    if (rc != FBS_OK) return rc;
-    if (prog->max_shared && (rc = ensure_acc(ctx, (size_t)prog->max_shared * Tc)) != FBS_OK) return rc;
-    *chunk = Tc;
-    return FBS_OK;
-}
-
-static uint64_t trivial_body(const fbs_ctx *ctx, int64_t out_slot) { return fq_mul(fq_from_i64(-1 - out_slot), 2 * ctx->delta_half); }
-
-// ---- the four program evaluations: one chunk loop, each entry its checks, its scratch and its two stages -------------------
-// what every evaluation checks first: the keys, the program's owner, the buffers of a call with samples
-static int check_eval(fbs_ctx *ctx, const fbs_prog *prog, const void *in, size_t T, const void *out) {
-    if (int rc = check_prog(ctx, prog)) return rc;
-    if (T && ((prog->n_inputs && !in) || (prog->n_outputs && !out))) return set_error(ctx, FBS_E_INVALID, "null argument");
-    return FBS_OK;
-}
-
-static int sync_stream(fbs_ctx *ctx, hipStream_t s) {
-    FBS_HIP(ctx, hipStreamSynchronize(s));
-    return FBS_OK;
-}
-
-// samples [s0, s0 + tc) of the chunk: put the inputs into their wire slots, or take the outputs out of theirs
-using ChunkStage = std::function<int(size_t s0, size_t tc)>;
-
-// Chunks of Tc samples (reserve_wires) on stream `s`: load, run_levels, store.  `sync`: the host-facing entries wait for each
-// chunk (pageable memory), then run `post` on it when given; fbs_eval_dev only launches.  A failure inside the loop puts the
-// scratch back (scratch_fail).
-static int eval_chunks(fbs_ctx *ctx, const fbs_prog *prog, size_t T, size_t Tc, hipStream_t s, bool sync, const ChunkStage &load,
-                       const ChunkStage &store, const ChunkStage &post = nullptr) {
-    int rc;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    for (size_t s0 = 0; s0 < T; s0 += Tc) {
-        const size_t tc = std::min(Tc, T - s0);
-        if ((rc = load(s0, tc)) || (rc = run_levels(ctx, prog, ctx->d_wires, Tc, tc, s)) || (rc = store(s0, tc))) return scratch_fail(ctx, s, rc);
-        if (sync && ((rc = sync_stream(ctx, s)) || (post && (rc = post(s0, tc))))) return scratch_fail(ctx, s, rc);
-    }
-    return scratch_done(ctx, s);
-}
-
-// ciphertexts [n_inputs][T][D + 1] -> the input slots (`kind`: from the host or the device)
-static int load_cts(fbs_ctx *ctx, const fbs_prog *prog, const uint64_t *in, size_t T, size_t Tc, size_t s0, size_t tc, hipMemcpyKind kind,
-                    hipStream_t s) {
-    const size_t ctw = ctx->D + 1;
-    for (uint32_t i = 0; i < prog->n_inputs; i++)
-        FBS_HIP(ctx, hipMemcpyAsync(ctx->d_wires + (size_t)prog->in_slot[i] * Tc * ctw, in + ((size_t)i * T + s0) * ctw, tc * ctw * 8, kind, s));
-    return FBS_OK;
-}
-
-// the output slots -> host ciphertexts [n_outputs][T][D + 1]; a constant output as its trivial ciphertext
-static int store_host_cts(fbs_ctx *ctx, const fbs_prog *prog, uint64_t *out, size_t T, size_t Tc, size_t s0, size_t tc, hipStream_t s) {
-    const size_t ctw = ctx->D + 1;
-    for (uint32_t o = 0; o < prog->n_outputs; o++) {
-        uint64_t *dst = out + ((size_t)o * T + s0) * ctw;
-        const int64_t w = prog->out_slot[o];
-        if (w >= 0) {
-            FBS_HIP(ctx, hipMemcpyAsync(dst, ctx->d_wires + (size_t)w * Tc * ctw, tc * ctw * 8, hipMemcpyDeviceToHost, s));
-        } else {
-            const uint64_t body = trivial_body(ctx, w);
-            for (size_t q = 0; q < tc; q++) {
-                std::memset(dst + q * ctw, 0, ctx->D * 8);
-                dst[q * ctw + ctx->D] = body;
-            }
-        }
-    }
-    return FBS_OK;
-}
-
-int fbs_eval_dev(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *d_in, size_t T, uint64_t *d_out, void *stream) try {
-    int rc = check_eval(ctx, prog, d_in, T, d_out);
-    if (rc != FBS_OK || T == 0) return rc;
-    hipStream_t s = pick(ctx, stream);
-    size_t Tc = 0;
-    if ((rc = reserve_wires(ctx, prog, T, &Tc)) != FBS_OK) return rc;
-    auto load = [&](size_t s0, size_t tc) { return load_cts(ctx, prog, d_in, T, Tc, s0, tc, hipMemcpyDeviceToDevice, s); };
-    auto store = [&](size_t s0, size_t tc) {
-        for (uint32_t o = 0; o < prog->n_outputs; o++) {
-            const int64_t w = prog->out_slot[o];
-            uint64_t *dst = d_out + ((size_t)o * T + s0) * (ctx->D + 1);
-            if (int rc = dev_copy_out(ctx, ctx->d_wires, Tc, 0, tc, w, w < 0 ? trivial_body(ctx, w) : 0, dst, s)) return rc;
-        }
-        return FBS_OK;
-    };
-    return eval_chunks(ctx, prog, T, Tc, s, false, load, store);
-} FBS_API_CATCH(ctx)
-
-int fbs_eval(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *in_cts, size_t T, uint64_t *out_cts) try {
-    int rc = check_eval(ctx, prog, in_cts, T, out_cts);
-    if (rc != FBS_OK || T == 0) return rc;
-    hipStream_t s = ctx->stream;
-    size_t Tc = 0;
-    if ((rc = reserve_wires(ctx, prog, T, &Tc)) != FBS_OK) return rc;
-    auto load = [&](size_t s0, size_t tc) { return load_cts(ctx, prog, in_cts, T, Tc, s0, tc, hipMemcpyHostToDevice, s); };
-    auto store = [&](size_t s0, size_t tc) { return store_host_cts(ctx, prog, out_cts, T, Tc, s0, tc, s); };
-    return eval_chunks(ctx, prog, T, Tc, s, true, load, store);
-} FBS_API_CATCH(ctx)
-
-// Messages in, messages out: fbs_eval with the inputs encrypted on the device straight into their wire slots and the output
-// slots decrypted there (the same chunks, scratch ordering and checks); only int64 messages cross the bus.
-int fbs_eval_messages(fbs_ctx *ctx, fbs_prog *prog, const int64_t *msgs, size_t T, int fresh, uint64_t *nonce0, int64_t *out_msgs) try {
-    int rc = check_eval(ctx, prog, msgs, T, out_msgs);
-    if (rc != FBS_OK) return rc;
-    if (!fresh && !nonce0) return set_error(ctx, FBS_E_INVALID, "null argument");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    if (T == 0) return FBS_OK;
-    const size_t n_in = prog->n_inputs, n_out = prog->n_outputs;
-    if (T > SIZE_MAX / 8 / std::max<size_t>(1, n_in + n_out) || (rc = check_ct_words(ctx, T * std::max<size_t>(1, n_in))))
-        return set_error(ctx, FBS_E_INVALID, "n_inputs * T ciphertexts overflow");
-    const size_t streams = n_in * T;
-    if (!fresh && (rc = check_nonces(ctx, *nonce0, streams))) return rc;
-    hipStream_t s = ctx->stream;
-    size_t Tc = 0;
-    if ((rc = reserve_wires(ctx, prog, T, &Tc)) != FBS_OK) return rc;
-    if ((rc = ensure_io_msgs(ctx, (n_in + n_out) * Tc)) != FBS_OK) return rc;
-    uint64_t first = fresh ? 0 : *nonce0;
-    if (fresh) {
-        if ((rc = reserve_fresh(ctx, streams, &first))) return rc;
-        if (nonce0) *nonce0 = first;
-    }
-    // what fbs_decrypt makes of the trivial ciphertext fbs_eval returns for a constant output
-    std::vector<int64_t> const_msg(n_out, 0);
-    {
-        std::vector<uint64_t> triv(ctx->D + 1, 0);
-        for (size_t o = 0; o < n_out; o++)
-            if (prog->out_slot[o] < 0) {
-                triv[ctx->D] = trivial_body(ctx, prog->out_slot[o]);
-                host_decrypt(ctx, triv.data(), 1, &const_msg[o]);
-            }
-    }
-    int64_t *d_in_msgs = ctx->d_io_msgs, *d_out_msgs = ctx->d_io_msgs + n_in * Tc;
-    auto load = [&](size_t s0, size_t tc) {
-        if (!n_in) return FBS_OK;
-        FBS_HIP(ctx, hipMemcpy2DAsync(d_in_msgs, Tc * 8, msgs + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
-        return dev_encrypt(ctx, IoView{d_in_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc}, first + s0, T, s);
-    };
-    auto store = [&](size_t s0, size_t tc) {
-        if (!n_out) return FBS_OK;
-        if (int rc = dev_decrypt(ctx, IoView{d_out_msgs, Tc, ctx->d_wires, prog->d_out_slot, Tc, n_out, tc}, s)) return rc;
-        FBS_HIP(ctx, hipMemcpy2DAsync(out_msgs + s0, T * 8, d_out_msgs, Tc * 8, tc * 8, n_out, hipMemcpyDeviceToHost, s));
-        return FBS_OK;
-    };
-    auto post = [&](size_t s0, size_t tc) {
-        for (size_t o = 0; o < n_out; o++)
-            if (prog->out_slot[o] < 0) std::fill(out_msgs + o * T + s0, out_msgs + o * T + s0 + tc, const_msg[o]);
-        return FBS_OK;
-    };
-    return eval_chunks(ctx, prog, T, Tc, s, true, load, store, post);
-} FBS_API_CATCH(ctx)
-
-// Seeded inputs: fbs_eval with the bodies copied to the device and expanded there straight into their wire slots (the chunks,
-// scratch ordering and outputs of fbs_eval); needs no secret.  The bodies use fbs_eval_messages's message scratch.
-int fbs_eval_seeded(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t T, uint64_t nonce0, uint64_t *out_cts) try {
-    int rc = check_eval(ctx, prog, bodies, T, out_cts);
-    if (rc != FBS_OK || T == 0) return rc;
-    const size_t n_in = prog->n_inputs, n_out = prog->n_outputs, ctw = ctx->D + 1;
-    if (T > SIZE_MAX / 8 / std::max<size_t>(1, std::max(n_in, n_out)) / ctw)
-        return set_error(ctx, FBS_E_INVALID, "n_inputs * T ciphertexts overflow");
-    if ((rc = check_seeded_streams(ctx, nonce0, n_in * T))) return rc;
-    hipStream_t s = ctx->stream;
-    size_t Tc = 0;
-    if ((rc = reserve_wires(ctx, prog, T, &Tc)) != FBS_OK) return rc;
-    if ((rc = ensure_io_msgs(ctx, std::max<size_t>(1, n_in) * Tc)) != FBS_OK) return rc;
-    auto load = [&](size_t s0, size_t tc) {
-        if (!n_in) return FBS_OK;
-        FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_io_msgs, Tc * 8, bodies + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
-        return dev_expand_seeded(ctx, IoView{ctx->d_io_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc}, nonce0 + s0, T, s);
-    };
-    auto store = [&](size_t s0, size_t tc) { return store_host_cts(ctx, prog, out_cts, T, Tc, s0, tc, s); };
-    return eval_chunks(ctx, prog, T, Tc, s, true, load, store);
-} FBS_API_CATCH(ctx)
-
-// ---- compact outputs: key switch to the small key, rounding to Z_(2^bits), bit packing (fbs_compact.hpp) --------------------
-// fbs_compact_dev runs in passes of the modulus-switch scratch the context has, or of this many ciphertexts when it has less
-constexpr size_t COMPACT_PASS = 8192;
-
-int fbs_compact_words(const fbs_ctx *ctx, uint32_t bits, size_t *words) try {
-    if (!ctx || !words) return FBS_E_INVALID;
-    if (int rc = check_bits(ctx, bits)) return rc;
-    *words = compact_words(ctx->p.n, bits);
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-// (no secret needed: runs on evaluation-only contexts)
-int fbs_compact_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_words, void *stream) try {
-    if (int rc = io_prologue(ctx, d_cts, d_words, count, IO_CT_WORDS, nullptr)) return rc;
-    if (int rc = check_bits(ctx, bits)) return rc;
-    if (int rc = check_compact_words(ctx, count, bits)) return rc;
-    if (count == 0) return FBS_OK;
-    FBS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t pass = std::min(count, std::max(ctx->ms_capacity, COMPACT_PASS)), ctw = ctx->D + 1, W = compact_words(ctx->p.n, bits);
-    int rc = ensure_ms(ctx, pass);
-    if (rc != FBS_OK) return rc;
-    hipStream_t s = pick(ctx, stream);
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    for (size_t f0 = 0; f0 < count; f0 += pass) {
-        const size_t rows = std::min(pass, count - f0);
-        const GateView gv = batch_view(d_cts + f0 * ctw, nullptr, nullptr, rows);
-        if ((rc = dev_keyswitch(ctx, gv, ctx->d_ms, bits, s)) || (rc = dev_compact_pack(ctx, ctx->d_ms, rows, bits, d_words + f0 * W, s)))
-            return scratch_fail(ctx, s, rc);
-    }
-    return scratch_done(ctx, s);
-} FBS_API_CATCH(ctx)
-
-// The compact store stage (fbs_eval_seeded_compact, fbs_eval_sources): the output slots of a chunk are key-switched and packed on
-// the device in groups of outputs whose rows fit the modulus-switch scratch reserve_wires sized (max_sources x Tc rows), and only
-// the packed words are copied back; a constant output is the compaction of the trivial ciphertext fbs_eval_seeded returns for it.
-// The caller counts the packed staging (cap_rows x W words) in the chunk's budget and grows d_compact to it.
-struct CompactStore {
-    uint32_t bits = 0;
-    size_t W = 0, cap_rows = 0;
-    std::vector<uint64_t> constant;   // [n_outputs][W]
-};
-static CompactStore compact_store_for(const fbs_ctx *ctx, const fbs_prog *prog, uint32_t bits, size_t Tc) {
-    CompactStore cs;
-    cs.bits = bits;
-    cs.W = compact_words(ctx->p.n, bits);
-    cs.cap_rows = (size_t)std::max(1u, prog->max_sources) * Tc;   // (ensure_ms has made d_ms at least this long)
-    cs.constant.assign((size_t)prog->n_outputs * cs.W, 0);
-    for (size_t o = 0; o < prog->n_outputs; o++)
-        if (prog->out_slot[o] < 0) host_compact_trivial(ctx, trivial_body(ctx, prog->out_slot[o]), bits, cs.constant.data() + o * cs.W);
-    return cs;
-}
-static int store_compact(fbs_ctx *ctx, const fbs_prog *prog, const CompactStore &cs, uint64_t *out_words, size_t T, size_t Tc,
-                         size_t s0, size_t tc, hipStream_t s) {
-    const size_t W = cs.W, n_live = prog->live_out.size(), group = std::max<size_t>(1, cs.cap_rows / tc);
-    for (size_t g0 = 0; g0 < n_live; g0 += group) {
-        const size_t ng = std::min(group, n_live - g0), rows = ng * tc;
-        GateView gv{};
-        gv.in_base = ctx->d_wires;
-        gv.src_slot = prog->d_live_slot + g0;
-        gv.T = Tc;
-        gv.s_begin = 0;
-        gv.s_count = tc;
-        gv.count = rows;
-        gv.ks_count = rows;
-        gv.n_gates = (uint32_t)ng;
-        if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, cs.bits, s)) return rc;
-        if (int rc = dev_compact_pack(ctx, ctx->d_ms, rows, cs.bits, ctx->d_compact, s)) return rc;
-        for (size_t i = 0; i < ng; i++)
-            FBS_HIP(ctx, hipMemcpyAsync(out_words + ((size_t)prog->live_out[g0 + i] * T + s0) * W, ctx->d_compact + i * tc * W, tc * W * 8,
-                                        hipMemcpyDeviceToHost, s));
-    }
-    for (size_t o = 0; o < prog->n_outputs; o++)
-        if (prog->out_slot[o] < 0)
-            for (size_t q = 0; q < tc; q++) std::memcpy(out_words + (o * T + s0 + q) * W, cs.constant.data() + o * W, W * 8);
-    return FBS_OK;
-}
-
-// fbs_eval_seeded with the compact store stage
-int fbs_eval_seeded_compact(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t T, uint64_t nonce0, uint32_t bits,
-                            uint64_t *out_words) try {
-    int rc = check_eval(ctx, prog, bodies, T, out_words);
-    if (rc != FBS_OK) return rc;
-    if ((rc = check_bits(ctx, bits)) != FBS_OK || T == 0) return rc;
-    const size_t n_in = prog->n_inputs, n_out = prog->n_outputs, ctw = ctx->D + 1, W = compact_words(ctx->p.n, bits);
-    if (T > SIZE_MAX / 8 / std::max<size_t>(1, std::max(n_in, n_out)) / std::max(ctw, W))
-        return set_error(ctx, FBS_E_INVALID, "n_inputs * T ciphertexts overflow");
-    if ((rc = check_seeded_streams(ctx, nonce0, n_in * T))) return rc;
-    hipStream_t s = ctx->stream;
-    const size_t rows_per_sample = std::max(1u, prog->max_sources);
-    size_t Tc = 0;
-    if ((rc = reserve_wires(ctx, prog, T, &Tc, rows_per_sample * W * 8)) != FBS_OK) return rc;
-    if ((rc = ensure_io_msgs(ctx, std::max<size_t>(1, n_in) * Tc)) != FBS_OK) return rc;
-    const CompactStore cs = compact_store_for(ctx, prog, bits, Tc);
-    if ((rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, cs.cap_rows * W, 8, true)) != FBS_OK) return rc;
-    auto load = [&](size_t s0, size_t tc) {
-        if (!n_in) return FBS_OK;
-        FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_io_msgs, Tc * 8, bodies + s0, T * 8, tc * 8, n_in, hipMemcpyHostToDevice, s));
-        return dev_expand_seeded(ctx, IoView{ctx->d_io_msgs, Tc, ctx->d_wires, prog->d_in_slot, Tc, n_in, tc}, nonce0 + s0, T, s);
-    };
-    auto store = [&](size_t s0, size_t tc) { return store_compact(ctx, prog, cs, out_words, T, Tc, s0, tc, s); };
-    return eval_chunks(ctx, prog, T, Tc, s, true, load, store);
-} FBS_API_CATCH(ctx)
-
+// ---- compact outputs: their decryption (fbs_compact_dev and the compact store stage: fbs_eval.cpp) ------------------------------
 int fbs_decrypt_compact(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs) try {
     if (int rc = io_prologue(ctx, words, msgs, count, IO_SECRET, nullptr)) return rc;
     if (int rc = check_bits(ctx, bits)) return rc;
@@ -1454,19 +1141,7 @@ int fbs_decrypt_compact_dev(const fbs_ctx *ctx, const uint64_t *d_words, size_t 
     return dev_decrypt_compact(ctx, d_words, count, bits, d_msgs, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
-// ---- chained evaluation: compact ciphertexts back into the blind rotation, and programs over mixed input sources ------------
-// the context's identity table [0, 1, .., p - 1], made on first use: a blind rotation through it is a refresh
-static int identity_tv(fbs_ctx *ctx, fbs_tvset **out) {
-    if (!ctx->tv_identity) {
-        std::vector<int32_t> vals(ctx->p.p_msg);
-        for (uint32_t v = 0; v < ctx->p.p_msg; v++) vals[v] = (int32_t)v;
-        const uint32_t off[2] = {0, ctx->p.p_msg};
-        if (int rc = fbs_tvset_create(ctx, vals.data(), off, 1, &ctx->tv_identity)) return rc;
-    }
-    *out = ctx->tv_identity;
-    return FBS_OK;
-}
-
+// ---- chained evaluation: compact ciphertexts back into the blind rotation (programs over mixed sources: fbs_eval.cpp) -----------
 // (no secret needed; no scratch: the fields go straight to the caller's buffer)
 int fbs_compact_fields_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint32_t *d_fields, void *stream) try {
     if (int rc = io_prologue(ctx, d_words, d_fields, count, 0, nullptr)) return rc;
@@ -1488,253 +1163,12 @@ int fbs_refresh_compact_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count,
     fbs_tvset *tv = nullptr;
     int rc = identity_tv(ctx, &tv);
     if (rc != FBS_OK) return rc;
-    const size_t pass = std::min(count, std::max(ctx->ms_capacity, COMPACT_PASS)), ctw = ctx->D + 1, W = compact_words(ctx->p.n, bits);
-    if ((rc = ensure_ms(ctx, pass)) != FBS_OK) return rc;
+    const size_t ctw = ctx->D + 1, W = compact_words(ctx->p.n, bits);
     hipStream_t s = pick(ctx, stream);
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    for (size_t f0 = 0; f0 < count; f0 += pass) {
-        const size_t rows = std::min(pass, count - f0);
-        if ((rc = dev_compact_unpack(ctx, d_words + f0 * W, rows, bits, ctx->d_ms, s)) ||
-            (rc = dev_blind_rotate(ctx, tv, batch_view(nullptr, d_cts + f0 * ctw, nullptr, rows), ctx->d_ms, s)))
-            return scratch_fail(ctx, s, rc);
-    }
-    return scratch_done(ctx, s);
-} FBS_API_CATCH(ctx)
-
-// the refresh of `ng` input slots (d_slot [ng], device) of a chunk whose rows d_ms [ng][tc][n + 1] hold already: a blind rotation
-// through the identity table written back into the same slots
-static int refresh_slots(fbs_ctx *ctx, const fbs_tvset *tv, const uint32_t *d_slot, size_t ng, size_t Tc, size_t tc, hipStream_t s) {
-    GateView gv{};
-    gv.in_base = ctx->d_wires;
-    gv.out_base = ctx->d_wires;
-    gv.src_slot = d_slot;
-    gv.dst_slot = d_slot;
-    gv.T = Tc;
-    gv.s_begin = 0;
-    gv.s_count = tc;
-    gv.f_begin = 0;
-    gv.count = ng * tc;
-    gv.ks_begin = 0;
-    gv.ks_count = ng * tc;
-    gv.n_gates = (uint32_t)ng;
-    return dev_blind_rotate(ctx, tv, gv, ctx->d_ms, s);
-}
-
-// One more pair of stages on eval_chunks.  Load: the full inputs are copied into their slots; runs of seeded inputs whose streams
-// step by T (and whose bodies lie T words apart) are expanded by one dev_expand_seeded each; plaintext inputs (FBS_SRC_PLAIN) send the
-// chunk's messages, 8 bytes a sample or nothing for a broadcast, and one launch writes all their trivial ciphertexts (dev_fill_plain); compact inputs are staged in the packed
-// buffer, unpacked into the modulus-switch scratch and refreshed, and full inputs marked `refresh` are key-switched, modulus-switched
-// and refreshed in place -- both in groups whose rows fit the scratch reserve_wires sized (max_sources x Tc rows).  Store: that of
-// fbs_eval_seeded (out_bits = 0) or fbs_eval_seeded_compact.
-//
-// fbs_eval_resident adds: inputs that are rows of states (res), gathered into their slots by one launch per chunk before the
-// refreshes (a resident input marked `refresh` joins the full ones), and out_state in place of the host buffer, filled by one scatter
-// launch per chunk.  With out_state and no full or compact host input (plaintext messages are none) nothing has to come back: the chunks are queued without
-// waiting, and the call returns once the arrays it was given have been read (`inputs_event`, after the last chunk's load).
-static bool state_of(const fbs_ctx *ctx, const fbs_state *st) {   // (by address: a foreign or stale pointer is never dereferenced)
-    return st && std::find(ctx->states.begin(), ctx->states.end(), st) != ctx->states.end();
-}
-
-static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res, size_t T, uint32_t out_bits,
-                        uint64_t *out, fbs_state *out_state) {
-    int rc = check_prog(ctx, prog);
-    if (rc != FBS_OK) return rc;
-    if (out_bits && (rc = check_bits(ctx, out_bits)) != FBS_OK) return rc;
-    if (out_state) {
-        if (!state_of(ctx, out_state)) return set_error(ctx, FBS_E_INVALID, "the output state is not a live state of this context");
-        if (out_bits) return set_error(ctx, FBS_E_INVALID, "outputs into a state are full ciphertexts: out_bits must be 0");
-        if (out_state->rows != prog->n_outputs)
-            return set_error(ctx, FBS_E_INVALID, "the output state has " + std::to_string(out_state->rows) + " rows for " +
-                                                     std::to_string(prog->n_outputs) + " outputs");
-        if (out_state->T != T) return set_error(ctx, FBS_E_INVALID, "the output state holds " + std::to_string(out_state->T) + " samples a row, the call has " + std::to_string(T));
-    }
-    for (size_t i = 0; res && i < prog->n_inputs; i++) {
-        const fbs_state *st = res[i].state;
-        if (!st) continue;
-        const std::string who = "input " + std::to_string(i) + ": ";
-        if (!state_of(ctx, st)) return set_error(ctx, FBS_E_INVALID, who + "not a live state of this context");
-        if (st == out_state) return set_error(ctx, FBS_E_INVALID, who + "the output state is also an input state (no in-place hops)");
-        if (res[i].row >= st->rows) return set_error(ctx, FBS_E_INVALID, who + "row " + std::to_string(res[i].row) + " of a state of " + std::to_string(st->rows) + " rows");
-        if (st->T != T) return set_error(ctx, FBS_E_INVALID, who + "its state holds " + std::to_string(st->T) + " samples a row, the call has " + std::to_string(T));
-    }
-    auto resident = [&](size_t i) { return res && res[i].state; };
-    if (T) {
-        bool from_src = false;
-        for (size_t i = 0; i < prog->n_inputs; i++) from_src |= !resident(i);
-        if ((from_src && !src) || (prog->n_outputs && !out && !out_state)) return set_error(ctx, FBS_E_INVALID, "null argument");
-    }
-    if (T == 0) return FBS_OK;
-    const size_t n_in = prog->n_inputs, n_out = prog->n_outputs, ctw = ctx->D + 1, W_out = out_bits ? compact_words(ctx->p.n, out_bits) : 0;
-    // every source is checked before anything is reserved, copied or launched
-    size_t W_in = 0;
-    std::vector<uint32_t> compact_in, full_refresh;   // input indices
-    std::vector<StateLink> links;                     // the gather list, then the scatter list
-    std::vector<uint32_t> plain_in;                   // input indices of the plaintext inputs
-    bool any_seeded = false, host_cts = false;        // host_cts: some input is ciphertexts in host memory
-    bool plain_msgs = false;                          // some plaintext input brings a message per sample
-    for (size_t i = 0; i < n_in; i++) {
-        if (resident(i)) {
-            links.push_back(StateLink{res[i].state->d + (size_t)res[i].row * T * ctw, prog->in_slot[i]});
-            if (res[i].refresh) full_refresh.push_back((uint32_t)i);
-            continue;
-        }
-        const fbs_input_src &x = src[i];
-        const std::string who = "input " + std::to_string(i) + ": ";
-        if (x.kind > FBS_SRC_PLAIN) return set_error(ctx, FBS_E_INVALID, who + "unknown source kind " + std::to_string(x.kind));
-        if (!x.data) return set_error(ctx, FBS_E_INVALID, who + "null data");
-        if (x.kind == FBS_SRC_PLAIN) {   // cleartext messages: [T], or one for every sample (bits = 1)
-            if (x.refresh) return set_error(ctx, FBS_E_INVALID, who + "a plaintext input is not refreshed");
-            if (x.bits > 1) return set_error(ctx, FBS_E_INVALID, who + "bits of a plaintext input is 0 ([T] messages) or 1 (one message for all)");
-            if (T > SIZE_MAX / 8) return set_error(ctx, FBS_E_INVALID, who + "T * words overflow");
-            const int64_t *m = reinterpret_cast<const int64_t *>(x.data);
-            for (size_t q = 0, count = x.bits ? 1 : T; q < count; q++)
-                if (m[q] < 0 || m[q] >= 2 * (int64_t)ctx->p.p_msg)
-                    return set_error(ctx, FBS_E_INVALID, who + "message " + std::to_string(m[q]) + " outside [0, 2p)");
-            plain_in.push_back((uint32_t)i);
-            plain_msgs |= !x.bits;
-            continue;
-        }
-        size_t words = x.kind == FBS_SRC_SEEDED ? 1 : ctw;
-        if (x.kind == FBS_SRC_COMPACT) {
-            if ((rc = check_bits(ctx, x.bits)) != FBS_OK) return rc;
-            words = compact_words(ctx->p.n, x.bits);
-            W_in = std::max(W_in, words);
-            compact_in.push_back((uint32_t)i);
-        }
-        if (x.kind == FBS_SRC_SEEDED) {
-            if ((rc = check_seeded_streams(ctx, x.nonce0, T)) != FBS_OK) return rc;
-            any_seeded = true;
-        }
-        if (x.kind == FBS_SRC_FULL && x.refresh) full_refresh.push_back((uint32_t)i);
-        host_cts |= x.kind != FBS_SRC_SEEDED;
-        if (T > SIZE_MAX / 8 / words) return set_error(ctx, FBS_E_INVALID, who + "T * words overflow");
-    }
-    if (T > SIZE_MAX / 8 / std::max<size_t>(1, n_out) / std::max(ctw, W_out)) return set_error(ctx, FBS_E_INVALID, "n_outputs * T words overflow");
-    hipStream_t s = ctx->stream;
-    const size_t W_stage = std::max(W_in, W_out), rows_per_sample = std::max(1u, prog->max_sources);
-    size_t Tc = 0;
-    if ((rc = reserve_wires(ctx, prog, T, &Tc, rows_per_sample * W_stage * 8)) != FBS_OK) return rc;
-    if ((any_seeded || plain_msgs) && (rc = ensure_io_msgs(ctx, n_in * Tc)) != FBS_OK) return rc;
-    const size_t cap_rows = rows_per_sample * Tc;   // (ensure_ms has made d_ms at least this long)
-    if (W_stage && (rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, cap_rows * W_stage, 8, true)) != FBS_OK) return rc;
-    // the slots to refresh, compact inputs first: uploaded with the first chunk (after eval_chunks's scratch_wait)
-    std::vector<uint32_t> refresh_slot;
-    for (uint32_t i : compact_in) refresh_slot.push_back(prog->in_slot[i]);
-    for (uint32_t i : full_refresh) refresh_slot.push_back(prog->in_slot[i]);
-    const fbs_tvset *tv = nullptr;
-    if (!refresh_slot.empty()) {
-        fbs_tvset *made = nullptr;
-        if ((rc = identity_tv(ctx, &made)) != FBS_OK || (rc = ensure_idx(ctx, refresh_slot.size())) != FBS_OK) return rc;
-        tv = made;
-    }
-    CompactStore cs;
-    if (out_bits) cs = compact_store_for(ctx, prog, out_bits, Tc);
-    const size_t n_gather = links.size();
-    for (size_t o = 0; out_state && o < n_out; o++) {
-        const int64_t w = prog->out_slot[o];
-        links.push_back(StateLink{out_state->d + o * T * ctw, w >= 0 ? (uint64_t)w : STATE_LINK_CONST | trivial_body(ctx, w)});
-    }
-    // the fill list of the plaintext inputs, behind the links in the same buffer: the messages of input i lie where its bodies would
-    std::vector<PlainLink> plain;
-    for (uint32_t i : plain_in) {
-        const int64_t *m = reinterpret_cast<const int64_t *>(src[i].data);
-        plain.push_back(src[i].bits ? PlainLink{nullptr, m[0], prog->in_slot[i]} : PlainLink{ctx->d_io_msgs + (size_t)i * Tc, 0, prog->in_slot[i]});
-    }
-    const size_t link_units = links.size() + (plain.size() * sizeof(PlainLink) + sizeof(StateLink) - 1) / sizeof(StateLink);
-    if (link_units && (rc = grow(ctx, ctx->d_links, ctx->links_capacity, std::max<size_t>(link_units, 1 << 12), sizeof(StateLink), false)) != FBS_OK)
-        return rc;
-    const PlainLink *d_plain = reinterpret_cast<const PlainLink *>(ctx->d_links + links.size());
-    const bool wait = !out_state || host_cts;   // results or pageable ciphertexts cross the bus: chunk by chunk, as fbs_eval_sources
-    if (!wait && !ctx->inputs_event) FBS_HIP(ctx, hipEventCreateWithFlags(&ctx->inputs_event, hipEventDisableTiming));
-    const size_t n1 = ctx->p.n + 1;
-    auto load = [&](size_t s0, size_t tc) {
-        if (s0 == 0 && !refresh_slot.empty())
-            FBS_HIP(ctx, hipMemcpyAsync(ctx->d_idx, refresh_slot.data(), refresh_slot.size() * 4, hipMemcpyHostToDevice, s));
-        if (s0 == 0 && !links.empty())
-            FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links, links.data(), links.size() * sizeof(StateLink), hipMemcpyHostToDevice, s));
-        if (s0 == 0 && !plain.empty())
-            FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links + links.size(), plain.data(), plain.size() * sizeof(PlainLink), hipMemcpyHostToDevice, s));
-        if (int rc = dev_state_gather(ctx, StateCopy{ctx->d_links, n_gather, ctx->d_wires, Tc, s0, tc, ctx->D}, s)) return rc;
-        auto per_sample = [&](size_t i) { return !resident(i) && src[i].kind == FBS_SRC_PLAIN && !src[i].bits; };
-        for (size_t j0 = 0; j0 < n_in;) {   // the messages of the chunk: one 2D copy per stretch of inputs whose rows lie T words apart
-            if (!per_sample(j0)) {
-                j0++;
-                continue;
-            }
-            size_t j1 = j0 + 1;
-            while (j1 < n_in && per_sample(j1) && src[j1].data == src[j1 - 1].data + T) j1++;
-            FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_io_msgs + j0 * Tc, Tc * 8, src[j0].data + s0, T * 8, tc * 8, j1 - j0, hipMemcpyHostToDevice, s));
-            j0 = j1;
-        }
-        if (int rc = dev_fill_plain(ctx, PlainFill{d_plain, plain.size(), ctx->d_wires, Tc, tc, ctx->D, 2 * ctx->delta_half}, s)) return rc;
-        for (size_t i = 0; i < n_in; i++)
-            if (!resident(i) && src[i].kind == FBS_SRC_FULL)
-                FBS_HIP(ctx, hipMemcpyAsync(ctx->d_wires + (size_t)prog->in_slot[i] * Tc * ctw, src[i].data + s0 * ctw, tc * ctw * 8,
-                                            hipMemcpyHostToDevice, s));
-        auto seeded = [&](size_t i) { return !resident(i) && src[i].kind == FBS_SRC_SEEDED; };
-        for (size_t i0 = 0; i0 < n_in;) {   // seeded runs: streams nonce0 + r T + s over the run's rows r
-            if (!seeded(i0)) {
-                i0++;
-                continue;
-            }
-            size_t i1 = i0 + 1;
-            while (i1 < n_in && seeded(i1) && src[i1].nonce0 == src[i1 - 1].nonce0 + T) i1++;
-            for (size_t j0 = i0; j0 < i1;) {   // the bodies: one 2D copy per stretch whose rows lie T words apart
-                size_t j1 = j0 + 1;
-                while (j1 < i1 && src[j1].data == src[j1 - 1].data + T) j1++;
-                FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_io_msgs + j0 * Tc, Tc * 8, src[j0].data + s0, T * 8, tc * 8, j1 - j0, hipMemcpyHostToDevice, s));
-                j0 = j1;
-            }
-            IoView v{ctx->d_io_msgs + i0 * Tc, Tc, ctx->d_wires, prog->d_in_slot + i0, Tc, i1 - i0, tc};
-            if (int rc = dev_expand_seeded(ctx, v, src[i0].nonce0 + s0, T, s)) return rc;
-            i0 = i1;
-        }
-        const size_t group = std::max<size_t>(1, cap_rows / tc);
-        for (size_t g0 = 0; g0 < compact_in.size(); g0 += group) {
-            const size_t ng = std::min(group, compact_in.size() - g0);
-            size_t staged = 0;
-            for (size_t j = 0; j < ng; j++) {
-                const fbs_input_src &x = src[compact_in[g0 + j]];
-                const size_t W = compact_words(ctx->p.n, x.bits);
-                FBS_HIP(ctx, hipMemcpyAsync(ctx->d_compact + staged, x.data + s0 * W, tc * W * 8, hipMemcpyHostToDevice, s));
-                if (int rc = dev_compact_unpack(ctx, ctx->d_compact + staged, tc, x.bits, ctx->d_ms + j * tc * n1, s)) return rc;
-                staged += tc * W;
-            }
-            if (int rc = refresh_slots(ctx, tv, ctx->d_idx + g0, ng, Tc, tc, s)) return rc;
-        }
-        for (size_t g0 = 0; g0 < full_refresh.size(); g0 += group) {
-            const size_t ng = std::min(group, full_refresh.size() - g0);
-            const uint32_t *d_slot = ctx->d_idx + compact_in.size() + g0;
-            GateView gv{};
-            gv.in_base = ctx->d_wires;
-            gv.src_slot = d_slot;
-            gv.T = Tc;
-            gv.s_begin = 0;
-            gv.s_count = tc;
-            gv.count = ng * tc;
-            gv.ks_count = ng * tc;
-            gv.n_gates = (uint32_t)ng;
-            if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) return rc;
-            if (int rc = refresh_slots(ctx, tv, d_slot, ng, Tc, tc, s)) return rc;
-        }
-        if (!wait && s0 + tc == T) FBS_HIP(ctx, hipEventRecord(ctx->inputs_event, s));   // every array of the caller has been queued
-        return FBS_OK;
-    };
-    auto store = [&](size_t s0, size_t tc) {
-        if (out_state) return dev_state_scatter(ctx, StateCopy{ctx->d_links + n_gather, n_out, ctx->d_wires, Tc, s0, tc, ctx->D}, s);
-        return out_bits ? store_compact(ctx, prog, cs, out, T, Tc, s0, tc, s) : store_host_cts(ctx, prog, out, T, Tc, s0, tc, s);
-    };
-    rc = eval_chunks(ctx, prog, T, Tc, s, wait, load, store);
-    // the link lists, refresh slots, seeded bodies and plaintext messages live in pageable memory of this call or its caller: read before it returns.
-    // A call that failed part way may have queued copies from them without reaching the event: it waits for the stream instead.
-    if (!wait && rc == FBS_OK) FBS_HIP(ctx, hipEventSynchronize(ctx->inputs_event));
-    if (!wait && rc != FBS_OK) (void)hipStreamSynchronize(s);
-    return rc;
-}
-
-int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, size_t T, uint32_t out_bits, uint64_t *out) try {
-    if (int rc = check_eval(ctx, prog, src, T, out)) return rc;
-    return eval_sources(ctx, prog, src, nullptr, T, out_bits, out, nullptr);
+    return ms_passes(ctx, count, s, [&](size_t f0, size_t rows) {
+        if (int rc = dev_compact_unpack(ctx, d_words + f0 * W, rows, bits, ctx->d_ms, s)) return rc;
+        return dev_blind_rotate(ctx, tv, batch_view(nullptr, d_cts + f0 * ctw, nullptr, rows), ctx->d_ms, s);
+    });
 } FBS_API_CATCH(ctx)
 
 // ---- resident state: device blocks of ciphertexts that stay on the card between evaluations (fbs_state.hip) -----------------
@@ -1782,14 +1216,6 @@ int fbs_state_info(const fbs_state *st, size_t *rows, size_t *T) try {
     return FBS_OK;
 } FBS_API_CATCH(st ? st->ctx : nullptr)
 
-int fbs_eval_resident(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res, size_t T, uint32_t out_bits,
-                      uint64_t *out_host, fbs_state *out_state) try {
-    if (!ctx) return FBS_E_INVALID;
-    if ((out_host != nullptr) == (out_state != nullptr))
-        return set_error(ctx, FBS_E_INVALID, "exactly one of out_host and out_state takes the outputs");
-    return eval_sources(ctx, prog, src, res, T, out_bits, out_host, out_state);
-} FBS_API_CATCH(ctx)
-
 // what fetch and put check: the state is this context's, the rows are its rows
 static int check_state_rows(const fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, const void *host) {
     if (!state_of(ctx, st)) return set_error(ctx, FBS_E_INVALID, "not a live state of this context");
@@ -1814,20 +1240,17 @@ int fbs_state_fetch(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows,
     }
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
     // fbs_compact_dev's passes, each packed into the staging of the compact outputs and copied back from there
-    const size_t pass = std::min(count, std::max(ctx->ms_capacity, COMPACT_PASS)), W = compact_words(ctx->p.n, bits);
-    if ((rc = ensure_ms(ctx, pass)) != FBS_OK) return rc;
-    if ((rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, pass * W, 8, true)) != FBS_OK) return rc;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    for (size_t f0 = 0; f0 < count; f0 += pass) {
-        const size_t n = std::min(pass, count - f0);
+    const size_t W = compact_words(ctx->p.n, bits);
+    if ((rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, ms_pass_size(ctx, count) * W, 8, true)) != FBS_OK) return rc;
+    rc = ms_passes(ctx, count, s, [&](size_t f0, size_t n) {
         const GateView gv = batch_view(d_cts + f0 * ctw, nullptr, nullptr, n);
-        if ((rc = dev_keyswitch(ctx, gv, ctx->d_ms, bits, s)) || (rc = dev_compact_pack(ctx, ctx->d_ms, n, bits, ctx->d_compact, s)))
-            return scratch_fail(ctx, s, rc);
+        if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, bits, s)) return rc;
+        if (int rc = dev_compact_pack(ctx, ctx->d_ms, n, bits, ctx->d_compact, s)) return rc;
         if (hipMemcpyAsync(out + f0 * W, ctx->d_compact, n * W * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
-            return scratch_fail(ctx, s, set_error(ctx, FBS_E_DEVICE, "copying compact words to the host failed"));
-    }
-    if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
-    return sync_stream(ctx, s);
+            return set_error(ctx, FBS_E_DEVICE, "copying compact words to the host failed");
+        return FBS_OK;
+    });
+    return rc != FBS_OK ? rc : sync_stream(ctx, s);
 } FBS_API_CATCH(ctx)
 
 int fbs_state_put(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *cts) try {

@@ -1,4 +1,4 @@
-// Internal definitions shared by the host side (fbs_host.cpp, fbs_capi.cpp) and the HIP side
+// Internal definitions shared by the host side (fbs_host.cpp, fbs_capi.cpp, fbs_eval.cpp) and the HIP side
 // (fbs_kernels.hip) of libfbsexec.so -- and, with FBS_HOST_ONLY defined, by the client library libfbsclient.so
 // (fbs_error.cpp, fbs_host.cpp, fbs_client_capi.cpp), which is built without HIP: it then sees the host state of a context
 // (fbs::HostState) and the host functions, and nothing that names a device type.
@@ -9,6 +9,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <new>
 #include <stdexcept>
@@ -296,6 +297,58 @@ struct fbs_tvset {
     std::vector<uint64_t> g_norm2;    //   (fbs_table_fusion_norms)
     std::vector<uint8_t> fusable;     // 0: the coefficients of D_F are too large for the 64-bit sums of k_multi_extract
 };
+
+// ---- a loaded program (fbs_program_load_ex in fbs_capi.cpp; evaluated by fbs_eval.cpp) ------------------------------------------
+namespace fbs {
+struct LincombStage {
+    uint32_t n_out = 0;
+    uint32_t *d_dst = nullptr, *d_term_off = nullptr, *d_srcs = nullptr;   // wire SLOTS
+    uint64_t *d_coefs = nullptr, *d_consts = nullptr;
+};
+// Bootstraps of one level, sorted by source wire.  Gates that read the same wire (the reference's one-gate-one-bootstrap
+// lowering emits several tables per linear combination, fbs_mapper/map_to_fbs.py:41-45, and its CSE only merges
+// identical tables, fbs_mapper/fbs_exec_env.py:93-100) share one key switch + modulus switch.
+struct BootStage {
+    uint32_t n_gates = 0, n_sources = 0;
+    uint32_t *d_src_slot = nullptr;    // [n_sources] wire slot of each distinct source
+    uint32_t *d_source_of = nullptr;   // [n_gates]   index into d_src_slot
+    uint32_t *d_dst = nullptr, *d_table = nullptr;   // [n_gates]
+    std::vector<uint32_t> source_of;   // host copy: which key switches a slice of the level needs
+    // Fused programs (FBS_LOAD_FUSE_TABLES): the tables of a source that several read are served by ONE gate of the list
+    // above -- the rotation of TV_0 (table id = the set's n_tables, dst = 0x80000000 | shared index) -- and one entry each
+    // of the extraction list below (k_multi_extract)
+    uint32_t n_shared = 0, n_extract = 0;
+    uint32_t *d_x_row = nullptr, *d_x_table = nullptr, *d_x_dst = nullptr;   // [n_extract] shared index, table, wire slot
+    uint32_t *d_x_gate = nullptr;      // [n_extract] position of the shared rotation in the gate list (a level cut across GPUs
+                                       // finds the accumulator in that gate's gathered row)
+};
+// rows of one (level, point) of the audit (fbs_audit_rows): program wire id and wire slot of each, in reporting order
+struct AuditRows {
+    std::vector<uint32_t> wire;
+    uint32_t *d_slot = nullptr;   // [wire.size()]
+};
+}  // namespace fbs
+struct fbs_prog {
+    fbs_ctx *ctx = nullptr;
+    const fbs_tvset *tv = nullptr;
+    uint32_t n_inputs = 0, n_instr = 0, n_outputs = 0, n_wires = 0, n_slots = 0;
+    uint32_t depth = 0, max_width = 0, max_sources = 0, n_bootstrap = 0, n_keyswitch = 0;
+    uint32_t n_rotations = 0, max_shared = 0;   // blind rotations per sample (= n_bootstrap unless fused); shared rotations of the widest level
+    bool fused = false;
+    std::vector<uint32_t> in_slot;    // [n_inputs]
+    std::vector<int64_t> out_slot;    // [n_outputs]  slot, or -1-c for the constant c
+    uint32_t *d_in_slot = nullptr;    // [n_inputs]   the same on the device (fbs_eval_messages)
+    uint32_t *d_out_slot = nullptr;   // [n_outputs]  slot, or 0xFFFFFFFF for a constant
+    std::vector<uint32_t> live_out;   // the outputs that are wires, not constants, in output order
+    uint32_t *d_live_slot = nullptr;  // [live_out.size()] their slots (the key switches of fbs_eval_seeded_compact read them)
+    // schedule: for level L = 0..depth: lincomb stages (dependency order), then the bootstraps of level L+1
+    std::vector<std::vector<fbs::LincombStage>> lin;   // [depth+1][sub]
+    std::vector<fbs::BootStage> boot;                  // [depth]  (boot[L] = bootstraps of level L+1)
+    // audited evaluation: what each point of each level reports (inputs: wire i in slot in_slot[i])
+    std::vector<fbs::AuditRows> audit_lin, audit_boot;   // [depth+1], [depth]
+    std::vector<std::vector<uint32_t>> audit_src;   // [depth] wire id of each distinct key-switch source
+    std::vector<void *> allocations;
+};
 #endif   // !FBS_HOST_ONLY
 
 namespace fbs {
@@ -467,6 +520,45 @@ int dev_fill_plain(const fbs_ctx *ctx, const PlainFill &a, hipStream_t stream);
 // public-key inputs (fbs_public.hip): sample extraction of the GLWE samples d_glwe [ceil(count / N)][k + 1][N] into the big-key
 // ciphertexts d_cts [count][D + 1], message j from coefficient j mod N of sample j / N; word for word host_pub_expand
 int dev_expand_public(const fbs_ctx *ctx, const uint64_t *d_glwe, size_t count, uint64_t *d_cts, hipStream_t stream);
+
+// ---- host side of the device library: what the entries of fbs_capi.cpp and fbs_eval.cpp share (defined in fbs_capi.cpp) --------
+hipStream_t pick(const fbs_ctx *ctx, void *stream);   // the caller's stream, or the context's
+// what an entry on a loaded program checks first: the keys, the device, the program's owner
+int check_prog(fbs_ctx *ctx, const fbs_prog *prog);
+int sync_stream(fbs_ctx *ctx, hipStream_t s);
+bool state_of(const fbs_ctx *ctx, const fbs_state *st);   // a live state of this context
+// Scratch is grown on demand, and growing it BLOCKS.  One scratch buffer of `count` elements of `bytes` each; `counted`: a growth
+// shows in scratch_growths
+template <typename T>
+int grow(fbs_ctx *ctx, T *&buf, size_t &capacity, size_t count, size_t bytes, bool counted) {
+    if (count <= capacity) return FBS_OK;
+    if (counted) ctx->scratch_growths++;
+    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));   // kernels may still read the old buffer
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    capacity = 0;
+    FBS_HIP(ctx, hipMalloc(&buf, count * bytes));
+    capacity = count;
+    return FBS_OK;
+}
+int ensure_ms(fbs_ctx *ctx, size_t count);       // modulus-switch scratch (and the GEMM key switch's) for `count` ciphertexts
+int ensure_acc(fbs_ctx *ctx, size_t rows);       // whole accumulators
+int ensure_wires(fbs_ctx *ctx, size_t words);
+int ensure_io_msgs(fbs_ctx *ctx, size_t words);
+int ensure_idx(fbs_ctx *ctx, size_t words);
+int identity_tv(fbs_ctx *ctx, fbs_tvset **out);  // the context's identity table, made on first use
+// cross-stream ordering of the scratch: wait before the first use, done after the last, fail (which returns rc) on an error between
+int scratch_wait(fbs_ctx *ctx, hipStream_t s);
+int scratch_done(fbs_ctx *ctx, hipStream_t s);
+int scratch_fail(fbs_ctx *ctx, hipStream_t s, int rc);
+// launch views: the plain batch (gate g = ciphertext g), and `ng` wire slots d_slot (device) of a chunk of tc samples, stride Tc
+GateView batch_view(const uint64_t *in, uint64_t *out, const uint32_t *table_ids, size_t count);
+GateView slots_view(const uint64_t *in, uint64_t *out, const uint32_t *d_slot, size_t ng, size_t Tc, size_t tc);
+// `count` ciphertexts through the modulus-switch scratch, in passes of what the context has of it or of this many when it has less,
+// under scratch_wait / scratch_fail / scratch_done: `pass(f0, rows)` queues ciphertexts [f0, f0 + rows) on `s`
+constexpr size_t COMPACT_PASS = 8192;
+size_t ms_pass_size(const fbs_ctx *ctx, size_t count);
+int ms_passes(fbs_ctx *ctx, size_t count, hipStream_t s, const std::function<int(size_t f0, size_t rows)> &pass);
 
 // profiling helpers
 void prof_begin(fbs_ctx *ctx, int which, hipStream_t s, hipEvent_t *e0, hipEvent_t *e1);

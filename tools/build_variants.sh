@@ -1,12 +1,12 @@
 #!/bin/bash
 # Variant builds of one kernel source into gpurun_exp/ (travels to the GPU box, not into the history):
 #   bash tools/build_variants.sh fbs_blind_rotate_k2.hip name1 "-DFLAG=1 ..." name2 "-D..."      -> gpurun_exp/libfbsexec_<name>.so
-# (the other objects are the in-tree build's: run make first)
+# (the other objects are the in-tree build's, the list the Makefile's NAMES: run make first)
 cd $(dirname $0)/../tfhe_fbs_map_amd/csrc || exit 1
 mkdir -p ../../gpurun_exp
 SRC=$1; shift
 OBJS=""
-for f in fbs_host.cpp fbs_plan.cpp fbs_capi.cpp fbs_kernels.hip fbs_blind_rotate.hip fbs_blind_rotate_cu.hip fbs_blind_rotate_k2.hip fbs_blind_rotate_glwe.hip fbs_mapper_search.hip; do
+for f in $(sed -n 's/^NAMES *:= *//p' Makefile); do
   [ $f = $SRC ] || OBJS="$OBJS build/$f.o"
 done
 while [ $# -ge 2 ]; do
