@@ -140,13 +140,17 @@ int fbs_ctx_reserve(fbs_ctx *ctx, size_t max_keyswitches, size_t max_shared_rows
  *   "br_k2_shape" (0)       GLWE dimension 2: 0 by launch size, 3 always three waves per bootstrap, 12 always twelve
  *   "br_glwe_fpw" (0)       other GLWE dimensions >= 2: bootstraps per workgroup, 0 by launch size; 1, 2; larger: the
  *                           throughput shape
- *   "pack_slices" (0)       packed outputs: slices the i-sum of one packed sample is cut into, 0 by launch size (at most 32) */
+ *   "pack_slices" (0)       packed outputs: slices the i-sum of one packed sample is cut into, 0 by launch size (at most 32)
+ *   "keys_on_device" (0)    1: fbs_keygen, fbs_keygen_seeded, fbs_import_seeded_keys and fbs_packing_keygen make (expand) the
+ *                           evaluation keys on the GPU instead of on host threads ("keys", below); every key word is the same */
 int fbs_ctx_tune(fbs_ctx *ctx, const char *knob, int64_t value);
 /* counters: "scratch_growths" (how often a call (re)allocated scratch, i.e. blocked), "ms_capacity", "acc_capacity",
  * "wires_capacity", "next_nonce", "cu_count"; "has_secret" (1: the context holds secret keys), "seeded_keys" (1: its keys
  * came from fbs_keygen_seeded or fbs_import_seeded_keys); "states_alive", "state_bytes" (resident state: fbs_state blocks not
  * yet destroyed, and the device bytes they hold); "packing_key" (1: the context holds a packing key), "packing_levels" and
- * "packing_base_bits" (its t_p and gamma_p, 0 without one) */
+ * "packing_base_bits" (its t_p and gamma_p, 0 without one); "keys_made_on_device" (1: the keys held now were made or expanded
+ * on the GPU, knob "keys_on_device"), "bsk_upload_bytes" (bytes of bootstrapping-key material the last key-making call copied
+ * host -> device: the whole key on the host path, 0 for keys made on the device, the bodies for a server key expanded there) */
 int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value);
 /* text of the last failure on `ctx` (or of the last failed fbs_ctx_create when ctx == NULL) */
 const char *fbs_last_error(const fbs_ctx *ctx);
@@ -158,7 +162,20 @@ const char *fbs_device_info(const fbs_ctx *ctx);
  * uploaded, transformed to the NTT domain on the GPU and kept resident, as is
  * the key-switching key.  The GLWE secret key (the big key ciphertexts are
  * encrypted under) also lives in device memory, as packed bits, for the life
- * of the context: the device encryption and decryption below read it. */
+ * of the context: the device encryption and decryption below read it.
+ *
+ * Knob "keys_on_device" = 1 (fbs_ctx_tune; default 0) moves the making of both
+ * evaluation keys to the GPU: the secrets are still drawn on the host and are
+ * uploaded first, the key rows are made from the same ChaCha20 streams, the same
+ * sampler and an exact negacyclic product by the secret, and the bootstrapping
+ * key is transformed from the device rows -- it is not uploaded at all.  The
+ * rows are copied back as the host copies that fbs_export_keys and
+ * fbs_export_seeded_keys read and that the key-switching tables are derived
+ * from (on the host, either way).  Every key word is what the host path makes:
+ * results never depend on the knob.  It covers fbs_keygen, fbs_keygen_seeded,
+ * fbs_import_seeded_keys (only the bodies are uploaded; the masks are expanded
+ * on the GPU) and the bodies of fbs_packing_keygen; fbs_import_keys takes full
+ * keys from the caller and is not affected. */
 int fbs_keygen(fbs_ctx *ctx);
 /* word counts of { sk_lwe, sk_glwe, bsk, ksk } in the standard (coefficient) layout:
  *   sk_lwe[n], sk_glwe[k][N] (bit c N + j = coefficient j of key polynomial S_c; read flat it is the key of the
@@ -220,7 +237,8 @@ int fbs_keygen_seeded(fbs_ctx *ctx);
 int fbs_seeded_key_sizes(const fbs_ctx *ctx, size_t sizes[2]);
 /* the server key: mask key and bodies.  FBS_E_STATE unless the keys came from fbs_keygen_seeded on this context. */
 int fbs_export_seeded_keys(const fbs_ctx *ctx, uint8_t mask_key[32], uint64_t *bsk_bodies, uint64_t *ksk_bodies);
-/* The mirror, on the server: expands (mask key, bodies) into full keys on the host and uploads them.  Every body word must
+/* The mirror, on the server: expands (mask key, bodies) into full keys on the host and uploads them (knob "keys_on_device":
+ * uploads the bodies and expands them on the GPU; the same checks, codes and texts, the same keys).  Every body word must
  * be a canonical residue (FBS_E_INVALID otherwise).  The phases cannot be checked, because there is no secret: keys
  * made for another parameter set or mask key are accepted and bootstrap to garbage.  A refused call leaves the previous
  * keys in place and usable.  Afterwards the context is EVALUATION-ONLY: its secret keys are gone from host and device,

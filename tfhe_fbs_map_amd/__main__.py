@@ -51,7 +51,7 @@ def split_run(env, cfg, values, plain, order):
     def evaluate():
         if not made:
             made["client"] = Client(env, cfg)
-            made["server"] = Server(made["client"].server_key(), device=cfg.device)
+            made["server"] = Server(made["client"].server_key(), device=cfg.device, device_keys=cfg.device_keys)
         client, server = made["client"], made["server"]
         T = len(next(iter(values.values())))
         rows = {n: int(plain[n]) if plain[n] != "samples" else np.asarray(values[n], np.int64) for n in order if n in plain}
@@ -64,7 +64,7 @@ def split_run(env, cfg, values, plain, order):
     return evaluate, lambda: [prog for prog, _ in made["server"]._programs.values()]
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m tfhe_fbs_map_amd", description=__doc__.split("\n\n")[0])
     ap.add_argument("filename")
     ap.add_argument("--type", choices=["auto", "fbs", "lbf", "blif", "bristol"], default="auto")
@@ -83,6 +83,13 @@ def main(argv=None):
                     help="after the check, run once more with the noise measured at every blind rotation's input (LutExecEnv.audit) "
                          "and print the summary and the ten gates with the least margin")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--device-keys", action="store_true",
+                    help="make the evaluation keys (and expand a server key) on the GPU instead of on the host (ExecConfig.device_keys)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
     if args.audit and args.plain:
         ap.error("--audit measures under the secret key: it does not go with --plain (the server of a split run holds none)")
@@ -96,7 +103,7 @@ def main(argv=None):
     values = {name: np.random.randint(0, 2, (args.samples)) for name in order}
 
     cfg = ExecConfig(fbs_size=args.fbs_size, seed=args.seed, device=args.device, reduced_noise=args.reduced_noise,
-                     fuse_tables=False if args.no_shared_rotations else None)
+                     fuse_tables=False if args.no_shared_rotations else None, device_keys=args.device_keys)
     plain = {}
     for item in args.plain:
         name, sep, what = item.partition("=")

@@ -513,7 +513,8 @@ def debug_gauss(words, sigma):
 class Context:
     """One GPU, one parameter set, one key set."""
 
-    def __init__(self, params: Params, seed: int | bytes | None = None, device: int = 0, keygen: bool = True):
+    def __init__(self, params: Params, seed: int | bytes | None = None, device: int = 0, keygen: bool = True,
+                 device_keys: bool = False):
         """seed: what all key material and encryption randomness derive from.
         * an int: the REPRODUCIBLE form (fbs_ctx_create, 64 bits) -- tests and benchmarks pass a constant so that the CPU
           oracle can be keyed identically.  Not a way to make production keys.
@@ -522,7 +523,9 @@ class Context:
         Either way the noise sampler is the one `params.sampler` names: 0, the default, a test-grade stand-in for a discrete
         Gaussian (`RANDOMNESS_GRADE`); 1 a rounded Gaussian (`GAUSSIAN_SAMPLER_GRADE`: not certified, not audited).  A deployment
         that needs more brings its own keys with `import_keys`.  keygen=False leaves the context without keys (for
-        `import_keys`)."""
+        `import_keys`).
+        device_keys=True: the evaluation keys are made -- and a server key is expanded -- on the GPU (knob "keys_on_device",
+        include/fbs_exec.h) instead of on the host and uploaded; the same words either way (`stat("keys_made_on_device")`)."""
         self.params = params
         self.seed = seed
         self.device = device
@@ -539,6 +542,8 @@ class Context:
         if rc != 0:
             self._h = None
             raise FbsError(rc, lib.fbs_last_error(None).decode())
+        if device_keys:
+            self.tune(keys_on_device=1)
         if keygen:
             self.keygen()
 
@@ -610,10 +615,11 @@ class Context:
         self._check(lib.fbs_import_seeded_keys(self._h, _ptr(mk), _ptr(bsk), _ptr(ksk)))
 
     @classmethod
-    def evaluation_only(cls, params: Params, mask_key, bsk_bodies, ksk_bodies, device: int = 0):
+    def evaluation_only(cls, params: Params, mask_key, bsk_bodies, ksk_bodies, device: int = 0, device_keys: bool = False):
         """A context that holds the evaluation keys of a server key and no secret: it evaluates (`Program.eval_seeded`,
-        `Program.eval`, the batch and level entries) and refuses to encrypt or decrypt."""
-        ctx = cls(params, seed=None, device=device, keygen=False)
+        `Program.eval`, the batch and level entries) and refuses to encrypt or decrypt.  device_keys=True: only the bodies are
+        uploaded and the masks are regenerated on the GPU."""
+        ctx = cls(params, seed=None, device=device, keygen=False, device_keys=device_keys)
         ctx.import_seeded_keys(mask_key, bsk_bodies, ksk_bodies)
         return ctx
 

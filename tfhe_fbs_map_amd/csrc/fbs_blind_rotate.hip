@@ -606,15 +606,21 @@ __global__ __launch_bounds__(2 << LL) __attribute__((amdgpu_waves_per_eu(2))) vo
 // ---------------------------------------------------------------------------------------------
 #define FBS_FOR_EACH_SHAPE(X) X(8) X(9) X(10) X(11) X(12)
 
+// d_given: the key in the coefficient domain, already on the device (keys made there, fbs_keygen.hip); null: ctx->bsk is uploaded
 template <int LOGN>
-static int upload_keys_t(fbs_ctx *ctx) {
+static int transform_bsk_t(fbs_ctx *ctx, const uint64_t *d_given) {
     constexpr int LL = lanes_log2_for(LOGN);
     const fbs_params &p = ctx->p;
     const uint32_t N = ctx->N;
     const size_t polys = ctx->n_ggsw * ctx->rows * (p.k + 1);
-    uint64_t *d_src = nullptr;
-    FBS_HIP(ctx, hipMalloc(&d_src, polys * N * 8));
-    hipError_t e = hipMemcpyAsync(d_src, ctx->bsk.data(), polys * N * 8, hipMemcpyHostToDevice, ctx->stream);
+    uint64_t *d_own = nullptr;
+    hipError_t e = hipSuccess;
+    if (!d_given) {
+        FBS_HIP(ctx, hipMalloc(&d_own, polys * N * 8));
+        e = hipMemcpyAsync(d_own, ctx->bsk.data(), polys * N * 8, hipMemcpyHostToDevice, ctx->stream);
+        ctx->bsk_upload_bytes = (int64_t)(polys * N * 8);
+    }
+    const uint64_t *d_src = d_given ? d_given : d_own;
     if (e == hipSuccess) {
         const double n_inv = fq_centered(fq_inv(N));
         unsigned grid = (unsigned)std::min<size_t>(polys, 4096);
@@ -634,12 +640,22 @@ static int upload_keys_t(fbs_ctx *ctx) {
         }
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_src);
+    if (d_own) (void)hipFree(d_own);
     if (e != hipSuccess) return set_error(ctx, FBS_E_DEVICE, std::string("bootstrapping-key transform: ") + hipGetErrorString(e));
     return FBS_OK;
 }
 
-int dev_upload_keys(fbs_ctx *ctx) {
+int dev_transform_bsk(fbs_ctx *ctx, const uint64_t *d_src) {
+    switch (ctx->p.log_n_poly) {
+#define X(L) case L: return transform_bsk_t<L>(ctx, d_src);
+        FBS_FOR_EACH_SHAPE(X)
+#undef X
+    }
+    return set_error(ctx, FBS_E_INVALID, "unsupported N");
+}
+
+// the twiddle tables (and psi^x for two key bits per step), and on first use the device buffers of both keys
+int dev_upload_tables(fbs_ctx *ctx) {
     const fbs_params &p = ctx->p;
     const uint32_t N = ctx->N;
     std::vector<uint64_t> fwd, inv;
@@ -660,20 +676,8 @@ int dev_upload_keys(fbs_ctx *ctx) {
         FBS_HIP(ctx, hipMalloc(&ctx->d_ksk_f, ksk_rows * ctx->ksk_stride * 8));
         FBS_HIP(ctx, hipMalloc(&ctx->d_ks_corr, (size_t)ctx->ksk_stride * 8));
     }
-    // (B/2) * sum of all key rows: what turns the unsigned bit fields of the key-switch kernels into balanced digits
-    std::vector<uint64_t> corr(ctx->ksk_stride, 0);
-    {
-        std::vector<unsigned __int128> sum(p.n + 1, 0);
-        for (size_t r = 0; r < ksk_rows; r++)
-            for (uint32_t i = 0; i <= p.n; i++) sum[i] += ctx->ksk[r * (p.n + 1) + i];
-        for (uint32_t i = 0; i <= p.n; i++) corr[i] = fq_mul((uint64_t)(sum[i] % FQ), 1ull << (p.gamma_ksk - 1));
-    }
-    FBS_HIP(ctx, hipMemcpyAsync(ctx->d_ks_corr, corr.data(), corr.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     FBS_HIP(ctx, hipMemcpyAsync(ctx->d_tw_fwd, fwd_c.data(), fwd_c.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     FBS_HIP(ctx, hipMemcpyAsync(ctx->d_tw_inv, inv_c.data(), inv_c.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    FBS_HIP(ctx, hipMemsetAsync(ctx->d_ksk, 0, ksk_rows * ctx->ksk_stride * 8, ctx->stream));
-    FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_ksk, (size_t)ctx->ksk_stride * 8, ctx->ksk.data(), (size_t)(p.n + 1) * 8,
-                                  (size_t)(p.n + 1) * 8, ksk_rows, hipMemcpyHostToDevice, ctx->stream));
     if (ctx->group == 2) {   // psi^x, x < N: what the pointwise factors zeta^e - 1 of the monomials X^e - 1 are made from
         std::vector<double> tbl(N);
         const uint64_t psi = fq_pow(FQ_GENERATOR, (FQ - 1) / (2ull * N));
@@ -685,20 +689,40 @@ int dev_upload_keys(fbs_ctx *ctx) {
         if (!ctx->d_psi_pow) FBS_HIP(ctx, hipMalloc(&ctx->d_psi_pow, tbl.size() * 8));
         FBS_HIP(ctx, hipMemcpy(ctx->d_psi_pow, tbl.data(), tbl.size() * 8, hipMemcpyHostToDevice));
     }
+    FBS_HIP(ctx, hipStreamSynchronize(ctx->stream));   // fwd_c / inv_c are about to go out of scope
+    return FBS_OK;
+}
+
+// the key-switching key from ctx->ksk: padded rows, centred doubles, the correction row, the GEMM's limb fragments
+int dev_upload_ksk(fbs_ctx *ctx) {
+    const fbs_params &p = ctx->p;
+    const size_t ksk_rows = (size_t)ctx->D * p.t_ksk;
+    // (B/2) * sum of all key rows: what turns the unsigned bit fields of the key-switch kernels into balanced digits
+    std::vector<uint64_t> corr(ctx->ksk_stride, 0);
+    {
+        std::vector<unsigned __int128> sum(p.n + 1, 0);
+        for (size_t r = 0; r < ksk_rows; r++)
+            for (uint32_t i = 0; i <= p.n; i++) sum[i] += ctx->ksk[r * (p.n + 1) + i];
+        for (uint32_t i = 0; i <= p.n; i++) corr[i] = fq_mul((uint64_t)(sum[i] % FQ), 1ull << (p.gamma_ksk - 1));
+    }
+    FBS_HIP(ctx, hipMemcpyAsync(ctx->d_ks_corr, corr.data(), corr.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    FBS_HIP(ctx, hipMemsetAsync(ctx->d_ksk, 0, ksk_rows * ctx->ksk_stride * 8, ctx->stream));
+    FBS_HIP(ctx, hipMemcpy2DAsync(ctx->d_ksk, (size_t)ctx->ksk_stride * 8, ctx->ksk.data(), (size_t)(p.n + 1) * 8,
+                                  (size_t)(p.n + 1) * 8, ksk_rows, hipMemcpyHostToDevice, ctx->stream));
     {   // centred doubles for the FP64 key-switch kernel, padded like the integer copy
         std::vector<double> kf(ksk_rows * (size_t)ctx->ksk_stride, 0.0);
         for (size_t r = 0; r < ksk_rows; r++)
             for (uint32_t i = 0; i <= p.n; i++) kf[r * ctx->ksk_stride + i] = fq_centered(ctx->ksk[r * (p.n + 1) + i]);
         FBS_HIP(ctx, hipMemcpy(ctx->d_ksk_f, kf.data(), kf.size() * 8, hipMemcpyHostToDevice));
     }
-    FBS_HIP(ctx, hipStreamSynchronize(ctx->stream));   // fwd_c / inv_c are about to go out of scope
-    if (int rc = dev_keyswitch_gemm_setup(ctx)) return rc;
-    switch (p.log_n_poly) {
-#define X(L) case L: return upload_keys_t<L>(ctx);
-        FBS_FOR_EACH_SHAPE(X)
-#undef X
-    }
-    return set_error(ctx, FBS_E_INVALID, "unsupported N");
+    FBS_HIP(ctx, hipStreamSynchronize(ctx->stream));   // corr is about to go out of scope
+    return dev_keyswitch_gemm_setup(ctx);
+}
+
+int dev_upload_keys(fbs_ctx *ctx) {
+    if (int rc = dev_upload_tables(ctx)) return rc;
+    if (int rc = dev_upload_ksk(ctx)) return rc;
+    return dev_transform_bsk(ctx, nullptr);
 }
 
 // the instantiation of a k_blind_rotate or k_blind_rotate_pairs descriptor (fbs_select.hpp); false for any other

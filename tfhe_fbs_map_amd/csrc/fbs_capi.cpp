@@ -271,6 +271,8 @@ int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value) try {
     else if (k == "packing_key") *value = ctx->have_pack;
     else if (k == "packing_levels") *value = ctx->have_pack ? ctx->pack_t : 0;
     else if (k == "packing_base_bits") *value = ctx->have_pack ? ctx->pack_gamma : 0;
+    else if (k == "keys_made_on_device") *value = ctx->have_keys && ctx->keys_made_on_device;
+    else if (k == "bsk_upload_bytes") *value = ctx->bsk_upload_bytes;
     else return set_error(ctx, FBS_E_INVALID, "unknown statistic '" + k + "'");
     return FBS_OK;
 } FBS_API_CATCH(ctx)
@@ -320,15 +322,33 @@ const char *fbs_last_error(const fbs_ctx *ctx) { return ctx ? ctx->err.c_str() :
 const char *fbs_device_info(const fbs_ctx *ctx) { return ctx ? ctx->devinfo.c_str() : ""; }
 
 // ---------------------------------------------------------------------------------------------
+// Keys on the device (knob "keys_on_device"): the secrets are drawn on the host and uploaded FIRST -- the kernels read them --, both
+// evaluation keys are made there (bsk_bodies null) or expanded there from the bodies of a server key, the bootstrapping key is
+// transformed straight from the device rows, and the rows come back as ctx->bsk / ctx->ksk: the exports and the key-switching
+// tables (derived on the host, as ever) read those.
+static int keys_on_device(fbs_ctx *ctx, bool seeded, const uint64_t *bsk_bodies, const uint64_t *ksk_bodies) {
+    ctx->have_keys = false;
+    int rc = bsk_bodies ? FBS_OK : dev_upload_secret(ctx);
+    if (rc == FBS_OK) rc = dev_upload_tables(ctx);
+    if (rc == FBS_OK) rc = dev_make_keys(ctx, seeded, ctx->mask_key, bsk_bodies, ksk_bodies);
+    if (rc == FBS_OK) rc = dev_upload_ksk(ctx);
+    if (rc != FBS_OK) return rc;
+    ctx->bsk_upload_bytes = bsk_bodies ? (int64_t)(ctx->n_ggsw * ctx->rows * ctx->N * 8) : 0;
+    return FBS_OK;
+}
+
 int fbs_keygen(fbs_ctx *ctx) try {
     if (!ctx) return FBS_E_INVALID;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
-    host_keygen(ctx);
+    const bool on_device = ctx->tune.keys_on_device != 0;
+    if (on_device) draw_secrets(ctx);
+    else host_keygen(ctx);
     ctx->mask_key = mask_key_of(ctx->rkey);
     ctx->seeded_keys = ctx->eval_only = false;
-    int rc = dev_upload_keys(ctx);
-    if (rc == FBS_OK) rc = dev_upload_secret(ctx);
+    int rc = on_device ? keys_on_device(ctx, false, nullptr, nullptr) : dev_upload_keys(ctx);
+    if (rc == FBS_OK && !on_device) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
+    ctx->keys_made_on_device = on_device;
     ctx->have_keys = true;
     ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
     return FBS_OK;
@@ -380,6 +400,7 @@ int fbs_import_keys(fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glw
     int rc = dev_upload_keys(ctx);
     if (rc == FBS_OK) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
+    ctx->keys_made_on_device = false;   // (the caller's keys: nothing to make)
     ctx->have_keys = true;
     ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
     return FBS_OK;
@@ -444,12 +465,19 @@ int fbs_decrypt_dev(const fbs_ctx *ctx, const uint64_t *d_cts, size_t count, int
 int fbs_keygen_seeded(fbs_ctx *ctx) try {
     if (!ctx) return FBS_E_INVALID;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
-    host_keygen_seeded(ctx);
+    const bool on_device = ctx->tune.keys_on_device != 0;
+    if (on_device) {
+        draw_secrets(ctx);
+        ctx->mask_key = mask_key_of(ctx->rkey);
+    } else {
+        host_keygen_seeded(ctx);
+    }
     ctx->seeded_keys = true;
     ctx->eval_only = false;
-    int rc = dev_upload_keys(ctx);
-    if (rc == FBS_OK) rc = dev_upload_secret(ctx);
+    int rc = on_device ? keys_on_device(ctx, true, nullptr, nullptr) : dev_upload_keys(ctx);
+    if (rc == FBS_OK && !on_device) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
+    ctx->keys_made_on_device = on_device;
     ctx->have_keys = true;
     ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
     return FBS_OK;
@@ -492,12 +520,15 @@ int fbs_import_seeded_keys(fbs_ctx *ctx, const uint8_t mask_key[32], const uint6
     for (int i = 0; i < 8; i++)
         mk.w[i] = (uint32_t)mask_key[4 * i] | ((uint32_t)mask_key[4 * i + 1] << 8) | ((uint32_t)mask_key[4 * i + 2] << 16) |
                   ((uint32_t)mask_key[4 * i + 3] << 24);
+    const bool on_device = ctx->tune.keys_on_device != 0;   // then only the bodies are uploaded, and expanded there
     std::vector<uint64_t> bsk, ksk;
-    host_expand_seeded_keys(ctx, mk, bsk_bodies, ksk_bodies, bsk, ksk);   // (the previous keys stay until this has succeeded)
+    if (!on_device) host_expand_seeded_keys(ctx, mk, bsk_bodies, ksk_bodies, bsk, ksk);   // (the previous keys stay until this has succeeded)
     if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));   // kernels may still read the old keys
     if (ctx->stream) FBS_HIP(ctx, hipStreamSynchronize(ctx->stream));               // ... or the old secret
-    ctx->bsk.swap(bsk);
-    ctx->ksk.swap(ksk);
+    if (!on_device) {
+        ctx->bsk.swap(bsk);
+        ctx->ksk.swap(ksk);
+    }
     std::fill(ctx->sk_lwe.begin(), ctx->sk_lwe.end(), 0);
     std::fill(ctx->sk_glwe.begin(), ctx->sk_glwe.end(), 0);
     std::vector<uint64_t>().swap(ctx->sk_lwe);
@@ -511,7 +542,8 @@ int fbs_import_seeded_keys(fbs_ctx *ctx, const uint8_t mask_key[32], const uint6
     ctx->have_keys = false;
     ctx->seeded_keys = true;
     ctx->eval_only = true;
-    if (int rc = dev_upload_keys(ctx)) return rc;
+    if (int rc = on_device ? keys_on_device(ctx, true, bsk_bodies, ksk_bodies) : dev_upload_keys(ctx)) return rc;
+    ctx->keys_made_on_device = on_device;
     ctx->have_keys = true;
     ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
     return FBS_OK;
@@ -1329,7 +1361,11 @@ int fbs_packing_keygen(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) try {
     if (int rc = check_packing_params(ctx, t_p, gamma_p)) return rc;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<uint64_t> bodies;
-    host_packing_keygen(ctx, t_p, gamma_p, bodies);
+    if (ctx->tune.keys_on_device) {
+        if (int rc = dev_packing_bodies(ctx, t_p, gamma_p, bodies)) return rc;
+    } else {
+        host_packing_keygen(ctx, t_p, gamma_p, bodies);
+    }
     return install_packing_key(ctx, t_p, gamma_p, bodies);
 } FBS_API_CATCH(ctx)
 

@@ -153,7 +153,7 @@ int host_ctx_init(fbs_ctx *ctx, const fbs_params *params, uint64_t seed, const u
 }
 
 // the secret keys of fbs_keygen and fbs_keygen_seeded alike (DOM_SK_LWE, DOM_SK_GLWE)
-static void draw_secrets(fbs_ctx *ctx) {
+void draw_secrets(fbs_ctx *ctx) {
     const uint32_t n = ctx->p.n, D = ctx->D;
     ctx->sk_lwe.assign(n, 0);
     ctx->sk_glwe.assign(D, 0);

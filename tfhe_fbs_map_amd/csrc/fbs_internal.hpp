@@ -68,6 +68,7 @@ struct Tune {
     int64_t br_k2_shape = 0;        // k = 2: 0 by launch size; 3 always three waves per bootstrap; 12 always the twelve-wave latency shape
     int64_t br_glwe_fpw = 0;        // k_blind_rotate_glwe: bootstraps per workgroup -- 0 by launch size; 1, 2; anything larger = the throughput shape
     int64_t pack_slices = 0;        // packed outputs: slices the i-sum of one packed sample is cut into -- 0 by launch size (fbs_pack.hip)
+    int64_t keys_on_device = 0;     // 1: the evaluation keys are made and expanded on the device (fbs_keygen.hip), not on the host
 };
 
 // ---- launch descriptors ------------------------------------------------------------------------
@@ -234,6 +235,8 @@ struct fbs_ctx : fbs::HostState {
     size_t idx_capacity = 0;
     uint32_t *d_sk_bits = nullptr;   // [ceil(D / 32)] the GLWE secret key as packed bits (device encryption / decryption, fbs_io.hip)
     uint32_t *d_sk_lwe_bits = nullptr;   // [ceil(n / 32)] the small LWE key as packed bits (decryption of compact outputs)
+    bool keys_made_on_device = false;    // the keys held now came from the device path (knob "keys_on_device"; fbs_ctx_stat)
+    int64_t bsk_upload_bytes = 0;        // bootstrapping-key bytes the last key-making call copied host -> device (fbs_ctx_stat)
     uint64_t *d_compact = nullptr;   // scratch: packed compact ciphertexts of fbs_eval_seeded_compact's output groups
     size_t compact_capacity = 0;     // in words (also the staging of compact inputs, fbs_eval_sources)
     // Packed outputs (fbs_pack.hip): the packing key (parameters and bodies: HostState) in the transform domain
@@ -401,6 +404,7 @@ int translate_exception(Report &&report) noexcept {
 
 // host side (fbs_host.cpp)
 int host_ctx_init(fbs_ctx *ctx, const fbs_params *params, uint64_t seed, const uint8_t *seed32);   // errors: text in ctx->err
+void draw_secrets(fbs_ctx *ctx);   // sk_lwe, sk_glwe: the first step of host_keygen and host_keygen_seeded
 void host_keygen(fbs_ctx *ctx);
 void host_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *cts);
 void host_decrypt(const fbs_ctx *ctx, const uint64_t *cts, size_t count, int64_t *msgs);
@@ -442,7 +446,19 @@ const char *imported_keys_mismatch(const fbs_ctx *ctx, const uint64_t *sk_lwe, c
 
 #ifndef FBS_HOST_ONLY
 // device side (fbs_kernels.hip); all asynchronous on `stream`
-int dev_upload_keys(fbs_ctx *ctx);       // BSK -> NTT domain, KSK padded
+int dev_upload_keys(fbs_ctx *ctx);       // BSK -> NTT domain, KSK padded: the three below, from the host copies
+int dev_upload_tables(fbs_ctx *ctx);     // twiddle tables; allocates the device buffers of the keys on first use
+int dev_upload_ksk(fbs_ctx *ctx);        // ctx->ksk -> d_ksk (padded), d_ksk_f, d_ks_corr, the GEMM's fragments
+// the bootstrapping key, coefficient domain -> d_bsk_hat (and d_bsk_hat_small): from d_src on the device, or (null) from ctx->bsk,
+// which is then uploaded and counted in bsk_upload_bytes; blocks until the transforms are done
+int dev_transform_bsk(fbs_ctx *ctx, const uint64_t *d_src);
+// Keys on the device (fbs_keygen.hip; knob "keys_on_device"), word for word the host functions.  dev_make_keys: after the secrets
+// and the tables are on the device, both evaluation keys made there (seeded: host_keygen_seeded under `mask_key`, else host_keygen)
+// or, bsk_bodies / ksk_bodies (host arrays) non-null, expanded there (host_expand_seeded_keys under `mask_key`; no secret); the
+// bootstrapping key transformed from the device rows, and ctx->bsk / ctx->ksk filled from them.  dev_packing_bodies:
+// host_packing_keygen's bodies [n][t_p][N]
+int dev_make_keys(fbs_ctx *ctx, bool seeded, const RandKey &mask_key, const uint64_t *bsk_bodies, const uint64_t *ksk_bodies);
+int dev_packing_bodies(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies);
 int dev_keyswitch_gemm_setup(fbs_ctx *ctx);   // limb fragments of the key-switching key for the int8 MFMA key switch
 // the key switch kN -> n and the rounding of every word to Z_(2^log2_mod) (log2(2N): what the blind rotation reads; up to 31: the
 // fields of compact outputs), into d_ms [gv.ks_count][n + 1]

@@ -260,7 +260,8 @@ int check_kernel_built(const fbs_ctx *ctx) {
 
 int64_t *tune_knob(Tune &t, const std::string &k) {
     return k == "ks_mfma" ? &t.ks_mfma : k == "ks_fp" ? &t.ks_fp : k == "br_cu_kernel" ? &t.br_cu_kernel : k == "br_cu_lean" ? &t.br_cu_lean :
-           k == "br_k2_shape" ? &t.br_k2_shape : k == "br_glwe_fpw" ? &t.br_glwe_fpw : k == "pack_slices" ? &t.pack_slices : nullptr;
+           k == "br_k2_shape" ? &t.br_k2_shape : k == "br_glwe_fpw" ? &t.br_glwe_fpw : k == "pack_slices" ? &t.pack_slices :
+           k == "keys_on_device" ? &t.keys_on_device : nullptr;
 }
 
 }  // namespace fbs

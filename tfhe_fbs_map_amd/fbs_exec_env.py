@@ -133,6 +133,9 @@ class ExecConfig:
     # The noise sampler of the chosen parameter set (`Params.sampler`): "irwin_hall" (0, reproducible / test-grade) or "gaussian" (1).
     # With explicit `params`, "irwin_hall" leaves their own sampler as it is.
     sampler: str | int = "irwin_hall"
+    # True: the evaluation keys are made on the GPU (`Context(device_keys=True)`; knob "keys_on_device") instead of on host threads
+    # and uploaded.  The same keys either way.  A host `Client` has no device and ignores it.
+    device_keys: bool = False
     _contexts: dict = field(default_factory=dict, repr=False)
     _programs: "OrderedDict" = field(default_factory=OrderedDict, repr=False)
     last_choice: dict | None = field(default=None, repr=False)   # what `choose` decided for the most recent program
@@ -167,7 +170,7 @@ class ExecConfig:
         key = (prm, self.key_seed(), self.device)
         ctx = self._contexts.get(key)
         if ctx is None:
-            ctx = self._contexts[key] = nat.Context(prm, seed=self.key_seed(), device=self.device)
+            ctx = self._contexts[key] = nat.Context(prm, seed=self.key_seed(), device=self.device, device_keys=self.device_keys)
         return ctx
 
     def context_for(self, p, norm2=1):

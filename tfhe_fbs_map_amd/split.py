@@ -535,7 +535,7 @@ class Client:
         host: where the client's own work runs.  True: on the host alone, through the client library (`HostContext`: no GPU, no
         ROCm); False: on a GPU context (`Context`), as before there was a choice; None (default): the GPU context where
         libfbsexec.so has been built, the host context where only the client library has.  Keys, inputs and decoded results
-        are the same either way, and so are the files."""
+        are the same either way, and so are the files.  A host client has no device: it ignores `config.device_keys`."""
         self.env = env
         self.config = cfg = config or ExecConfig()
         self._low = env.lower()
@@ -546,7 +546,7 @@ class Client:
             self.ctx = HostContext(self.params, seed=cfg.key_seed(), keygen=False)
         else:
             from ._native import Context
-            self.ctx = Context(self.params, seed=cfg.key_seed(), device=cfg.device, keygen=False)
+            self.ctx = Context(self.params, seed=cfg.key_seed(), device=cfg.device, keygen=False, device_keys=cfg.device_keys)
         self.ctx.keygen_seeded()
         self.packing = None
         if packing:
@@ -630,11 +630,13 @@ class Client:
 class Server:
     """Holds evaluation keys only (`Context.evaluation_only`).  Lowers each program itself and evaluates seeded inputs."""
 
-    def __init__(self, server_key: ServerKey, device: int = 0, max_programs: int = 8):
+    def __init__(self, server_key: ServerKey, device: int = 0, max_programs: int = 8, device_keys: bool = False):
+        """device_keys=True: the server key's bodies are uploaded and expanded into full keys on the GPU, instead of on the host
+        (`Context(device_keys=True)`); the evaluation keys, and every result, are the same."""
         from ._native import Context
         self.key = server_key
         self.ctx = Context.evaluation_only(server_key.params, server_key.mask_key, server_key.bsk_bodies, server_key.ksk_bodies,
-                                           device=device)
+                                           device=device, device_keys=device_keys)
         if server_key.packing_bodies is not None:
             self.ctx.import_packing_key(server_key.packing_levels, server_key.packing_base_bits, server_key.packing_bodies)
         self.max_programs = max_programs
