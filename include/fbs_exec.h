@@ -501,6 +501,41 @@ int fbs_state_fetch(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows,
  * canonical residue (FBS_E_INVALID otherwise, nothing written).  Blocks until the words are on the device. */
 int fbs_state_put(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *cts);
 
+/* ---- sample-axis operations: gather and group sum across the T samples of resident state ------------------------------------
+ * Everything above treats the T samples of a call as T independent lanes.  These two entries are the steps ACROSS lanes, on
+ * state that stays on the card: an evaluation whose resident inputs read their samples through an index (gather, shift,
+ * broadcast, stride, and the pairing of a tree reduction), and the sum of runs of samples (counts and totals).  Neither touches a
+ * bootstrap: a gathered ciphertext is the ciphertext it was, and a sum of g ciphertexts carries g times the noise variance, which
+ * the consumer removes by refresh = 1.  Neither needs a secret.  Neither is part of the client or public libraries. */
+#define FBS_SAMPLE_NONE 0xFFFFFFFFu
+typedef struct fbs_sample_map {
+    const uint32_t *index;   /* host, [T] entries; NULL: the identity (then the state's T must equal the call's, as today) */
+    int64_t fill;            /* message in [0, 2p): sample s with index[s] == FBS_SAMPLE_NONE is its trivial ciphertext */
+} fbs_sample_map;
+/* fbs_eval_resident with one addition: maps (may be NULL: then this IS fbs_eval_resident, which is a call of this entry) has one
+ * entry per input.  Where res[i].state is non-NULL and maps[i].index is non-NULL, sample s of input i is sample index[s] of that
+ * state row, whose state may hold any T_src >= 1 samples a row; where index[s] == FBS_SAMPLE_NONE the sample is the trivial
+ * ciphertext of `fill`, word for word what FBS_SRC_PLAIN writes for that message.  refresh = 1 works on a mapped input as on any
+ * other.  The index arrays are read before the call returns, like the caller's other arrays, and are uploaded once per call;
+ * chunk [s0, s0 + tc) reads index[s0 + q].  Unmapped state rows go through the gather launch of fbs_eval_resident; one more
+ * launch per chunk moves the mapped ones.  Refused with FBS_E_INVALID, nothing written, besides what fbs_eval_resident refuses:
+ * an index entry >= T_src that is not FBS_SAMPLE_NONE; a fill outside [0, 2p); a map (index != NULL) on an input that is not a
+ * state row; a NULL index with T_src != T (the rule of fbs_eval_resident).  Every entry is checked before anything is queued.
+ * The output state must still not be an input state. */
+int fbs_eval_resident_mapped(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res,
+                             const fbs_sample_map *maps /* one per input, may be NULL */, size_t T, uint32_t out_bits,
+                             uint64_t *out_host, fbs_state *out_state);
+/* Sample j of row dst_row0 + r of dst, r < rows, becomes the word-wise sum modulo q of samples [j group, min((j+1) group, T_src))
+ * of row row0 + r of src: the ciphertext of the sum of their messages (which the caller keeps inside [0, p)).  Every word of the
+ * result is a canonical residue.  dst must hold exactly ceil(T_src / group) samples a row, and src != dst.  1 <= group <=
+ * FBS_MAX_SUM_GROUP: 65536 residues below q < 2^46 sum to less than 2^62, so a 64-bit accumulator per word cannot wrap and one
+ * reduction at the end gives the residue.  group = 1 is a copy.  Queued on the context's stream like the other state entries (a
+ * later fetch or evaluation is ordered behind it).  Refused with FBS_E_INVALID, nothing written: rows past either state's rows; a
+ * dst of another T; a state of another context; src == dst; group out of range.  rows = 0 does nothing. */
+#define FBS_MAX_SUM_GROUP 65536u
+int fbs_state_sum_groups(fbs_ctx *ctx, const fbs_state *src, size_t row0, size_t rows, size_t group,
+                         fbs_state *dst, size_t dst_row0);
+
 /* ---- packed outputs: up to N output bits in one GLWE ciphertext under the key the client already holds ------------------------
  * A compact ciphertext costs (n + 1) w bits per output.  A PACKING KEY SWITCH writes up to N of them into the N coefficients of one
  * GLWE sample under the big key (S_0 .. S_(k-1)), (k + 1) N w bits for N outputs.

@@ -44,6 +44,14 @@ class _ResidentSrc(C.Structure):   # fbs_resident_src (include/fbs_exec.h, "resi
     _fields_ = [("state", C.c_void_p), ("row", C.c_uint32), ("refresh", C.c_uint32)]
 
 
+class _SampleMap(C.Structure):   # fbs_sample_map (include/fbs_exec.h, "sample-axis operations")
+    _fields_ = [("index", C.c_void_p), ("fill", C.c_int64)]
+
+
+SAMPLE_NONE = 0xFFFFFFFF   # FBS_SAMPLE_NONE
+MAX_SUM_GROUP = 65536      # FBS_MAX_SUM_GROUP
+
+
 class _AuditRow(C.Structure):   # fbs_audit_row (include/fbs_exec.h, "audited evaluation")
     _fields_ = [("count", C.c_uint64), ("over", C.c_uint64), ("max_abs", C.c_uint64), ("sum", C.c_int64),
                 ("sumsq_lo", C.c_uint64), ("sumsq_hi", C.c_uint64)]
@@ -141,6 +149,8 @@ def _load():
         "fbs_state_destroy": (None, [vp]),
         "fbs_state_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz)]),
         "fbs_eval_resident": (i32, [vp, vp, vp, vp, sz, u32, vp, vp]),
+        "fbs_eval_resident_mapped": (i32, [vp, vp, vp, vp, vp, sz, u32, vp, vp]),
+        "fbs_state_sum_groups": (i32, [vp, vp, sz, sz, sz, vp, sz]),
         "fbs_state_fetch": (i32, [vp, vp, sz, sz, u32, vp]),
         "fbs_state_put": (i32, [vp, vp, sz, sz, vp]),
         "fbs_pub_expand_dev": (i32, [vp, vp, sz, vp, vp]),
@@ -214,6 +224,7 @@ EXPORTED_SYMBOLS = (
     "fbs_packing_keygen", "fbs_packing_key_sizes", "fbs_export_packing_key", "fbs_import_packing_key", "fbs_packed_words",
     "fbs_pack_dev", "fbs_state_fetch_packed", "fbs_decrypt_packed",
     "fbs_pub_expand_dev", "fbs_state_put_public",
+    "fbs_eval_resident_mapped", "fbs_state_sum_groups",
     "fbs_audit_rows", "fbs_audit_level_dev",
 ) + _public_native.EXPORTED_SYMBOLS
 
@@ -349,32 +360,51 @@ class Program:
     def eval_resident(self, sources, T, out_bits=0, out_state=None):
         """`eval_sources` with resident state (fbs_eval_resident).  A source may also be
             ("state", state, row, refresh)     -- row `row` of a `DeviceState`; refresh=True: through the identity table first
+            ("state", state, row, refresh, index, fill)
+                                               -- the same through a sample map (fbs_eval_resident_mapped): sample s is sample
+                                                  index[s] of the row (uint32 [T]; the state may hold any number of samples), or,
+                                                  where index[s] == SAMPLE_NONE, the trivial ciphertext of the message `fill`
         out_state=None: returns the outputs as `eval_sources` does at `out_bits`.  out_state: a `DeviceState` of n_outputs rows and
         T samples a row that takes the full outputs, row o = output o; returns it.  With out_state and only state and seeded
         sources (and plain ones) the call does not wait for the evaluation: whatever reads the state next is queued behind it."""
         if len(sources) != self.n_inputs:
             raise ValueError(f"{len(sources)} sources for {self.n_inputs} inputs")
         arr, res, keep = (_InputSrc * max(1, self.n_inputs))(), (_ResidentSrc * max(1, self.n_inputs))(), []
+        maps, mapped = (_SampleMap * max(1, self.n_inputs))(), False
         ctw = self.ctx.params.ct_words
         for i, source in enumerate(sources):
             kind = source[0]
             if kind == "state":
-                _, state, row, refresh = source
+                _, state, row, refresh = source[:4]
                 if not isinstance(state, DeviceState) or state.closed:
                     raise ValueError(f"input {i}: a closed state")
                 res[i] = _ResidentSrc(state._h.value, int(row), int(bool(refresh)))
                 keep.append(state)
+                if len(source) > 4 and source[4] is not None:
+                    _, _, _, _, index, fill = source
+                    index = np.asarray(index)
+                    if index.shape != (T,) or (index.size and (index.min() < 0 or index.max() > SAMPLE_NONE)):
+                        raise ValueError(f"input {i}: a sample map is {T} indices that fit 32 bits")
+                    index = _c(index, np.uint32)
+                    maps[i], mapped = _SampleMap(index.ctypes.data, operator.index(fill)), True
+                    keep.append(index)
                 continue
             arr[i], a = _input_src(source, T, ctw)
             keep.append(a)
         bits = int(out_bits)
+
+        def run(ctx, prog, arr, res, *rest):   # (the feed of before goes through the entry of before)
+            if mapped:
+                return lib.fbs_eval_resident_mapped(ctx, prog, arr, res, C.byref(maps), *rest)
+            return lib.fbs_eval_resident(ctx, prog, arr, res, *rest)
+
         if out_state is not None:
             if not isinstance(out_state, DeviceState) or out_state.closed:
                 raise ValueError("out_state is a closed state")
-            self.ctx._check(lib.fbs_eval_resident(self.ctx._h, self._h, C.byref(arr), C.byref(res), T, bits, None, out_state._h))
+            self.ctx._check(run(self.ctx._h, self._h, C.byref(arr), C.byref(res), T, bits, None, out_state._h))
             return out_state
         out = np.empty((self.n_outputs, T, self.ctx.compact_words(bits) if bits else ctw), np.uint64)
-        self.ctx._check(lib.fbs_eval_resident(self.ctx._h, self._h, C.byref(arr), C.byref(res), T, bits, _ptr(out), None))
+        self.ctx._check(run(self.ctx._h, self._h, C.byref(arr), C.byref(res), T, bits, _ptr(out), None))
         return out
 
     # device-pointer entry points (ints from torch.Tensor.data_ptr()); asynchronous on `stream`, no host copies
@@ -471,6 +501,27 @@ class DeviceState:
         cts = _c(cts, np.uint64).reshape(-1, self.T, self.ctx.params.ct_words)
         self.ctx._check(lib.fbs_state_put(self.ctx._h, self._live(), int(row0), cts.shape[0], _ptr(cts)))
         return self
+
+    def sum_groups(self, group, row0=0, rows=None, out=None, out_row0=0):
+        """Sample j of row out_row0 + r of `out` <- the sum of samples [j group, (j + 1) group) of row row0 + r, word by word modulo q
+        (fbs_state_sum_groups): the ciphertext of the sum of their messages.  out=None: a new `DeviceState` of `rows` rows;
+        either way ceil(T / group) samples a row.  Queued on the context, no secret needed.  Returns `out`."""
+        rows = self.rows - int(row0) if rows is None else int(rows)
+        group = operator.index(group)
+        made = out is None
+        if made:
+            if not 1 <= group <= MAX_SUM_GROUP:
+                raise ValueError(f"group {group} outside [1, {MAX_SUM_GROUP}]")
+            out = DeviceState(self.ctx, rows, -(-self.T // group))
+        try:
+            if not isinstance(out, DeviceState) or out.closed:
+                raise ValueError("out is a closed state")
+            self.ctx._check(lib.fbs_state_sum_groups(self.ctx._h, self._live(), int(row0), rows, group, out._h, int(out_row0)))
+        except Exception:
+            if made:
+                out.close()
+            raise
+        return out
 
     def put_public(self, glwe, row0=0, rows=None):
         """public-key samples [ceil(rows * T / N)][k+1][N] (host; `_public_native.Encryptor.encrypt` of the rows' messages flattened

@@ -1297,6 +1297,25 @@ int fbs_state_put(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const u
     return sync_stream(ctx, ctx->stream);
 } FBS_API_CATCH(ctx)
 
+// ---- sample-axis operations: the group sum (fbs_state.hip); the mapped evaluation is fbs_eval.cpp's ---------------------------
+int fbs_state_sum_groups(fbs_ctx *ctx, const fbs_state *src, size_t row0, size_t rows, size_t group, fbs_state *dst, size_t dst_row0) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (!state_of(ctx, src) || !state_of(ctx, dst)) return set_error(ctx, FBS_E_INVALID, "not a live state of this context");
+    if (src == dst) return set_error(ctx, FBS_E_INVALID, "the sums of a state do not go into the same state");
+    if (group < 1 || group > FBS_MAX_SUM_GROUP) return set_error(ctx, FBS_E_INVALID, "group " + std::to_string(group) + " outside [1, 65536]");
+    if (row0 > src->rows || rows > src->rows - row0 || dst_row0 > dst->rows || rows > dst->rows - dst_row0)
+        return set_error(ctx, FBS_E_INVALID, "rows past the end of the state");
+    const size_t T_dst = (src->T - 1) / group + 1;
+    if (dst->T != T_dst)
+        return set_error(ctx, FBS_E_INVALID, "the destination holds " + std::to_string(dst->T) + " samples a row, groups of " + std::to_string(group) +
+                                                 " of " + std::to_string(src->T) + " samples make " + std::to_string(T_dst));
+    if (rows == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ctw = ctx->D + 1;
+    return dev_state_sum_groups(ctx, SumGroups{src->d + row0 * src->T * ctw, dst->d + dst_row0 * T_dst * ctw, rows, src->T, T_dst, group, ctx->D},
+                                ctx->stream);
+} FBS_API_CATCH(ctx)
+
 // ---- public-key inputs: the device side of the expansion (fbs_public.hip); the host entries are fbs_public.cpp's ---------------
 int fbs_pub_expand_dev(fbs_ctx *ctx, const uint64_t *d_glwe, size_t count, uint64_t *d_cts, void *stream) try {
     if (!ctx || (count && (!d_glwe || !d_cts))) return FBS_E_INVALID;

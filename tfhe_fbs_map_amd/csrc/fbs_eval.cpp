@@ -145,6 +145,7 @@ struct SourcePlan {
     const fbs_prog *prog = nullptr;   // the call's arguments
     const fbs_input_src *src = nullptr;
     const fbs_resident_src *res = nullptr;
+    const fbs_sample_map *maps = nullptr;
     size_t T = 0;
     uint32_t out_bits = 0;
     size_t W_in = 0, W_out = 0;                             // words of the widest compact input, of a compact output (0: none)
@@ -154,6 +155,8 @@ struct SourcePlan {
     std::vector<StateLink> links;                           // the gather list [n_gather], then the scatter list
     size_t n_gather = 0;
     std::vector<PlainLink> plain;                           // the fill list of the plaintext inputs, behind the links in the same buffer
+    std::vector<MappedLink> mapped;                         // the mapped gather list (resident inputs with a sample map), behind the fill list
+    std::vector<uint32_t> mapped_in;                        // and their input indices: map j of the call lies at d_idx + refresh slots + j T
     std::vector<uint32_t> refresh_slot;                     // the slots to refresh, compact inputs first
     bool wait = true;                                       // results or pageable ciphertexts cross the bus: chunk by chunk
     // reserve_sources: the chunk, the rows of the modulus-switch scratch a group of refreshes may fill, the identity table
@@ -162,6 +165,8 @@ struct SourcePlan {
     CompactStore cs;
 
     bool resident(size_t i) const { return res && res[i].state; }
+    bool has_map(size_t i) const { return maps && maps[i].index; }
+    size_t plain_bytes() const { return plain.size() * sizeof(PlainLink); }
     bool from(size_t i, uint32_t kind) const { return !resident(i) && src[i].kind == kind; }
     bool per_sample(size_t i) const { return from(i, FBS_SRC_PLAIN) && !src[i].bits; }
 };
@@ -171,9 +176,9 @@ struct Chunk {   // samples [s0, s0 + tc) in wire slots of Tc samples, queued on
 };
 
 // every argument is checked before anything is reserved, copied or launched
-static int plan_sources(const fbs_ctx *ctx, const fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res, size_t T,
-                        uint32_t out_bits, const uint64_t *out, const fbs_state *out_state, SourcePlan &p) {
-    p.prog = prog, p.src = src, p.res = res, p.T = T, p.out_bits = out_bits;
+static int plan_sources(const fbs_ctx *ctx, const fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res,
+                        const fbs_sample_map *maps, size_t T, uint32_t out_bits, const uint64_t *out, const fbs_state *out_state, SourcePlan &p) {
+    p.prog = prog, p.src = src, p.res = res, p.maps = maps, p.T = T, p.out_bits = out_bits;
     int rc;
     if (out_bits && (rc = check_bits(ctx, out_bits)) != FBS_OK) return rc;
     if (out_state) {
@@ -184,14 +189,25 @@ static int plan_sources(const fbs_ctx *ctx, const fbs_prog *prog, const fbs_inpu
                                                      std::to_string(prog->n_outputs) + " outputs");
         if (out_state->T != T) return set_error(ctx, FBS_E_INVALID, "the output state holds " + std::to_string(out_state->T) + " samples a row, the call has " + std::to_string(T));
     }
-    for (size_t i = 0; res && i < prog->n_inputs; i++) {
-        const fbs_state *st = res[i].state;
-        if (!st) continue;
+    for (size_t i = 0; (res || maps) && i < prog->n_inputs; i++) {
+        const fbs_state *st = res ? res[i].state : nullptr;
+        if (!st && !p.has_map(i)) continue;
         const std::string who = "input " + std::to_string(i) + ": ";
+        if (!st) return set_error(ctx, FBS_E_INVALID, who + "a sample map on an input that is not a state row");
         if (!state_of(ctx, st)) return set_error(ctx, FBS_E_INVALID, who + "not a live state of this context");
         if (st == out_state) return set_error(ctx, FBS_E_INVALID, who + "the output state is also an input state (no in-place hops)");
         if (res[i].row >= st->rows) return set_error(ctx, FBS_E_INVALID, who + "row " + std::to_string(res[i].row) + " of a state of " + std::to_string(st->rows) + " rows");
-        if (st->T != T) return set_error(ctx, FBS_E_INVALID, who + "its state holds " + std::to_string(st->T) + " samples a row, the call has " + std::to_string(T));
+        if (!p.has_map(i)) {
+            if (st->T != T) return set_error(ctx, FBS_E_INVALID, who + "its state holds " + std::to_string(st->T) + " samples a row, the call has " + std::to_string(T));
+            continue;
+        }
+        // a mapped input: sample s is sample index[s] of the row, or the trivial ciphertext of `fill`
+        if (maps[i].fill < 0 || maps[i].fill >= 2 * (int64_t)ctx->p.p_msg)
+            return set_error(ctx, FBS_E_INVALID, who + "fill " + std::to_string(maps[i].fill) + " outside [0, 2p)");
+        for (size_t s = 0; s < T; s++)
+            if (maps[i].index[s] != FBS_SAMPLE_NONE && maps[i].index[s] >= st->T)
+                return set_error(ctx, FBS_E_INVALID, who + "sample " + std::to_string(s) + " reads sample " + std::to_string(maps[i].index[s]) +
+                                                         " of a state of " + std::to_string(st->T) + " a row");
     }
     if (T == 0) return FBS_OK;
     const size_t n_in = prog->n_inputs, n_out = prog->n_outputs, ctw = ctx->D + 1;
@@ -201,7 +217,13 @@ static int plan_sources(const fbs_ctx *ctx, const fbs_prog *prog, const fbs_inpu
     p.W_out = out_bits ? compact_words(ctx->p.n, out_bits) : 0;
     for (size_t i = 0; i < n_in; i++) {
         if (p.resident(i)) {
-            p.links.push_back(StateLink{res[i].state->d + (size_t)res[i].row * T * ctw, prog->in_slot[i]});
+            // (a mapped link's index is filled in by reserve_sources; its fill body is what FBS_SRC_PLAIN writes for that message)
+            if (p.has_map(i)) {
+                p.mapped.push_back(MappedLink{res[i].state->d + (size_t)res[i].row * res[i].state->T * ctw, nullptr,
+                                              (uint64_t)maps[i].fill * (2 * ctx->delta_half) % FQ, prog->in_slot[i]});
+                p.mapped_in.push_back((uint32_t)i);
+            } else
+                p.links.push_back(StateLink{res[i].state->d + (size_t)res[i].row * T * ctw, prog->in_slot[i]});
             if (res[i].refresh) p.full_refresh.push_back((uint32_t)i);
             continue;
         }
@@ -262,17 +284,27 @@ static int reserve_sources(fbs_ctx *ctx, SourcePlan &p) {
     if (W_stage && (rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, p.cap_rows * W_stage, 8, true)) != FBS_OK) return rc;
     if (!p.refresh_slot.empty()) {
         fbs_tvset *made = nullptr;
-        if ((rc = identity_tv(ctx, &made)) != FBS_OK || (rc = ensure_idx(ctx, p.refresh_slot.size())) != FBS_OK) return rc;
+        if ((rc = identity_tv(ctx, &made)) != FBS_OK) return rc;
         p.tv = made;
     }
+    // the refresh slots, then the sample maps of the call [mapped inputs][T]
+    if (p.T > (SIZE_MAX / 4 - p.refresh_slot.size()) / std::max<size_t>(1, p.mapped.size())) return set_error(ctx, FBS_E_INVALID, "the sample maps overflow");
+    const size_t idx_words = p.refresh_slot.size() + p.mapped.size() * p.T;
+    if (idx_words && (rc = ensure_idx(ctx, idx_words)) != FBS_OK) return rc;
+    for (size_t j = 0; j < p.mapped.size(); j++) p.mapped[j].index = ctx->d_idx + p.refresh_slot.size() + j * p.T;
     if (p.out_bits) p.cs = compact_store_for(ctx, prog, p.out_bits, p.Tc);
     for (size_t j = 0; j < p.plain_in.size(); j++)
         if (p.per_sample(p.plain_in[j])) p.plain[j].msgs = ctx->d_io_msgs + (size_t)p.plain_in[j] * p.Tc;
-    const size_t link_units = p.links.size() + (p.plain.size() * sizeof(PlainLink) + sizeof(StateLink) - 1) / sizeof(StateLink);
+    const size_t link_units = p.links.size() + (p.plain_bytes() + p.mapped.size() * sizeof(MappedLink) + sizeof(StateLink) - 1) / sizeof(StateLink);
     if (link_units && (rc = grow(ctx, ctx->d_links, ctx->links_capacity, std::max<size_t>(link_units, 1 << 12), sizeof(StateLink), false)) != FBS_OK)
         return rc;
     if (!p.wait && !ctx->inputs_event) FBS_HIP(ctx, hipEventCreateWithFlags(&ctx->inputs_event, hipEventDisableTiming));
     return FBS_OK;
+}
+
+// the mapped gather list on the device: behind the link lists and the fill list (all three hold 8-byte members only)
+static MappedLink *d_mapped(const fbs_ctx *ctx, const SourcePlan &p) {
+    return reinterpret_cast<MappedLink *>(reinterpret_cast<char *>(ctx->d_links + p.links.size()) + p.plain_bytes());
 }
 
 // -- the load stage of a chunk, step by step --
@@ -284,13 +316,18 @@ static int upload_lists(fbs_ctx *ctx, const SourcePlan &p, const Chunk &c) {
     if (!p.links.empty())
         FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links, p.links.data(), p.links.size() * sizeof(StateLink), hipMemcpyHostToDevice, c.s));
     if (!p.plain.empty())
-        FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links + p.links.size(), p.plain.data(), p.plain.size() * sizeof(PlainLink), hipMemcpyHostToDevice, c.s));
+        FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links + p.links.size(), p.plain.data(), p.plain_bytes(), hipMemcpyHostToDevice, c.s));
+    if (!p.mapped.empty())
+        FBS_HIP(ctx, hipMemcpyAsync(d_mapped(ctx, p), p.mapped.data(), p.mapped.size() * sizeof(MappedLink), hipMemcpyHostToDevice, c.s));
+    for (size_t j = 0; j < p.mapped.size(); j++)   // the whole map of every mapped input, once a call: the chunks slice it
+        FBS_HIP(ctx, hipMemcpyAsync(const_cast<uint32_t *>(p.mapped[j].index), p.maps[p.mapped_in[j]].index, p.T * 4, hipMemcpyHostToDevice, c.s));
     return FBS_OK;
 }
 
-// inputs that are rows of states: one launch
+// inputs that are rows of states: one launch, and one more for those with a sample map
 static int gather_resident(fbs_ctx *ctx, const SourcePlan &p, const Chunk &c) {
-    return dev_state_gather(ctx, StateCopy{ctx->d_links, p.n_gather, ctx->d_wires, c.Tc, c.s0, c.tc, ctx->D}, c.s);
+    if (int rc = dev_state_gather(ctx, StateCopy{ctx->d_links, p.n_gather, ctx->d_wires, c.Tc, c.s0, c.tc, ctx->D}, c.s)) return rc;
+    return dev_state_gather_mapped(ctx, MappedCopy{d_mapped(ctx, p), p.mapped.size(), ctx->d_wires, c.Tc, c.s0, c.tc, ctx->D}, c.s);
 }
 
 // the end of the run of inputs that starts at i0: every later one, below n, `joins` it
@@ -386,12 +423,12 @@ static int refresh_full(fbs_ctx *ctx, const SourcePlan &p, const Chunk &c) {
     return FBS_OK;
 }
 
-static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res, size_t T, uint32_t out_bits,
-                        uint64_t *out, fbs_state *out_state) {
+static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res, const fbs_sample_map *maps,
+                        size_t T, uint32_t out_bits, uint64_t *out, fbs_state *out_state) {
     int rc = check_prog(ctx, prog);
     if (rc != FBS_OK) return rc;
     SourcePlan p;
-    if ((rc = plan_sources(ctx, prog, src, res, T, out_bits, out, out_state, p)) != FBS_OK || T == 0) return rc;
+    if ((rc = plan_sources(ctx, prog, src, res, maps, T, out_bits, out, out_state, p)) != FBS_OK || T == 0) return rc;
     if ((rc = reserve_sources(ctx, p)) != FBS_OK) return rc;
     hipStream_t s = ctx->stream;
     const size_t Tc = p.Tc;
@@ -422,7 +459,7 @@ static int eval_uniform(fbs_ctx *ctx, fbs_prog *prog, uint32_t kind, const uint6
                         uint32_t out_bits, uint64_t *out) {
     std::vector<fbs_input_src> src(prog->n_inputs);
     for (size_t i = 0; i < src.size(); i++) src[i] = fbs_input_src{kind, 0, 0, kind == FBS_SRC_SEEDED ? nonce0 + i * T : 0, data + i * stride};
-    return eval_sources(ctx, prog, src.data(), nullptr, T, out_bits, out, nullptr);
+    return eval_sources(ctx, prog, src.data(), nullptr, nullptr, T, out_bits, out, nullptr);
 }
 
 extern "C" {
@@ -561,15 +598,21 @@ int fbs_eval_seeded_compact(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies
 
 int fbs_eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, size_t T, uint32_t out_bits, uint64_t *out) try {
     if (int rc = check_eval(ctx, prog, src, T, out)) return rc;
-    return eval_sources(ctx, prog, src, nullptr, T, out_bits, out, nullptr);
+    return eval_sources(ctx, prog, src, nullptr, nullptr, T, out_bits, out, nullptr);
+} FBS_API_CATCH(ctx)
+
+// fbs_eval_resident with sample maps on its resident inputs (fbs_state.hip, "sample-axis operations")
+int fbs_eval_resident_mapped(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res, const fbs_sample_map *maps,
+                             size_t T, uint32_t out_bits, uint64_t *out_host, fbs_state *out_state) try {
+    if (!ctx) return FBS_E_INVALID;
+    if ((out_host != nullptr) == (out_state != nullptr))
+        return set_error(ctx, FBS_E_INVALID, "exactly one of out_host and out_state takes the outputs");
+    return eval_sources(ctx, prog, src, res, maps, T, out_bits, out_host, out_state);
 } FBS_API_CATCH(ctx)
 
 int fbs_eval_resident(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, const fbs_resident_src *res, size_t T, uint32_t out_bits,
                       uint64_t *out_host, fbs_state *out_state) try {
-    if (!ctx) return FBS_E_INVALID;
-    if ((out_host != nullptr) == (out_state != nullptr))
-        return set_error(ctx, FBS_E_INVALID, "exactly one of out_host and out_state takes the outputs");
-    return eval_sources(ctx, prog, src, res, T, out_bits, out_host, out_state);
+    return fbs_eval_resident_mapped(ctx, prog, src, res, nullptr, T, out_bits, out_host, out_state);
 } FBS_API_CATCH(ctx)
 
 }   // extern "C"

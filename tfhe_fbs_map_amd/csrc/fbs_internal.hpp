@@ -129,6 +129,33 @@ struct StateCopy {
     uint32_t D;
 };
 
+// Sample-axis operations (fbs_state.hip).  The mapped gather: link e of a launch fills wire slot `slot`, sample q < tc, with sample
+// index[s0 + q] of the state row at `row` ([T_src][D + 1] words; the host has checked every entry against T_src), or -- the entry
+// FBS_SAMPLE_NONE -- with the trivial ciphertext of body `fill` (fill Delta mod q, worked out on the host).  `index` is the
+// call's whole map on the device, [T] words.
+struct MappedLink {
+    const uint64_t *row;
+    const uint32_t *index;
+    uint64_t fill;
+    uint64_t slot;
+};
+struct MappedCopy {
+    const MappedLink *links;   // [n_links], device
+    size_t n_links;
+    uint64_t *wires;           // wire slots [n_slots][Tc][D + 1]
+    size_t Tc;
+    size_t s0, tc;
+    uint32_t D;
+};
+// The group sum: sample j < T_dst of row r < rows of dst ([T_dst][D + 1] words a row) becomes the word-wise sum modulo q of samples
+// [j group, min((j + 1) group, T_src)) of row r of src
+struct SumGroups {
+    const uint64_t *src;   // sample 0 of the first row read
+    uint64_t *dst;         // sample 0 of the first row written
+    size_t rows, T_src, T_dst, group;
+    uint32_t D;
+};
+
 // Plaintext inputs (FBS_SRC_PLAIN, fbs_state.hip): entry e of a launch fills wire slot `slot`, samples q < tc, with the trivial
 // ciphertexts of msgs[q] (the chunk's messages on the device) or, msgs null, of the one message `value` (a broadcast input)
 struct PlainLink {
@@ -531,6 +558,9 @@ int dev_audit_reduce(const fbs_ctx *ctx, const int64_t *d_err, size_t rows, size
 // resident state (fbs_state.hip): the links of `a` between state rows and wire slots, one launch each
 int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);
 int dev_state_scatter(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);
+// sample-axis operations: the mapped links of a chunk into their wire slots, one launch; the group sums of `a`, one launch
+int dev_state_gather_mapped(const fbs_ctx *ctx, const MappedCopy &a, hipStream_t stream);
+int dev_state_sum_groups(const fbs_ctx *ctx, const SumGroups &a, hipStream_t stream);
 // plaintext inputs: the trivial ciphertexts of the links of `a` into their wire slots, one launch
 int dev_fill_plain(const fbs_ctx *ctx, const PlainFill &a, hipStream_t stream);
 // public-key inputs (fbs_public.hip): sample extraction of the GLWE samples d_glwe [ceil(count / N)][k + 1][N] into the big-key

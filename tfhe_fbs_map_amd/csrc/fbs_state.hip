@@ -13,6 +13,15 @@
 // (as k_expand_seeded stores its blocks); where they differ, the stores stay 16 bytes wide and aligned and each takes two 8-byte
 // loads -- consecutive lanes on consecutive words either way.  Plain vector loads and stores only.  These kernels are copies: they
 // are not in fbs_kernel_catalog and the profile does not count them.
+//
+// Sample-axis operations (fbs_eval_resident_mapped, fbs_state_sum_groups) -- the steps ACROSS samples, next to the copies above:
+//
+//   k_state_gather_mapped   wire slot of link e, sample q  <-  row of link e, sample index[s0 + q], or the trivial ciphertext of
+//                           the link's fill where the entry is FBS_SAMPLE_NONE.  The same grid as k_state_gather; one index word
+//                           per ciphertext, wave-uniform.  Source and destination sample differ now, so the two alignment cases
+//                           of wave_copy_ct both occur within one row.
+//   k_state_sum_groups      row r, sample j of dst  <-  the word-wise sum mod q of samples [j group, (j + 1) group) of row r of src
+//                           (a streaming reduction: every source word is read once; no LDS, no atomics).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -82,6 +91,62 @@ __global__ __launch_bounds__(64 * ST_WAVES) void k_state_scatter(StateCopy a) {
     }
 }
 
+__global__ __launch_bounds__(64 * ST_WAVES) void k_state_gather_mapped(MappedCopy a) {
+    const uint32_t lane = threadIdx.x & 63u, words = a.D + 1;
+    const size_t total = a.n_links * a.tc;
+    for (size_t c = (size_t)blockIdx.x * ST_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * ST_WAVES) {   // wave-uniform
+        const size_t e = c / a.tc, q = c - e * a.tc;
+        const MappedLink ln = a.links[e];
+        const uint32_t from = ln.index[a.s0 + q];   // (one word for the wave; below the row's samples, or FBS_SAMPLE_NONE: the host checked)
+        uint64_t *dst = a.wires + ((size_t)ln.slot * a.Tc + q) * words;
+        if (from == FBS_SAMPLE_NONE) wave_fill_trivial(dst, ln.fill, words, lane);
+        else wave_copy_ct(dst, ln.row + (size_t)from * words, words, lane);
+    }
+}
+
+// One wave takes one (row, output sample, slab) item: a slab is SG_SLAB_PAIRS 16-byte pairs of the output ciphertext, one pair a
+// lane -- 1 KiB a wave instruction, the widest global access there is -- so a ciphertext of D + 1 words gives ceil(D / 256) items and
+// a launch with few output ciphertexts still spreads over the chip.  The pairs are aligned to the DESTINATION (head word first where
+// it starts 8 bytes off a line, as wave_copy_ct); a source sample whose start agrees with that is read 16 bytes a lane, one that
+// does not (every other sample: D + 1 is odd) 8 bytes a lane twice, consecutive lanes on consecutive words either way.  The word
+// the pairs leave (the first or the last) rides on lane 63 of slab 0.  Each lane walks its group's samples with 64-bit sums:
+// group <= 65536 residues below q < 2^46 stay below 2^62, so one remainder at the end gives the canonical sum.
+constexpr uint32_t SG_SLAB_PAIRS = 64;
+
+__global__ __launch_bounds__(64 * ST_WAVES) void k_state_sum_groups(SumGroups a) {
+    const uint32_t lane = threadIdx.x & 63u, words = a.D + 1;
+    const uint32_t pairs = (words - 1) / 2;   // (words odd: the same with and without a head word)
+    const uint32_t slabs = std::max(1u, (pairs + SG_SLAB_PAIRS - 1) / SG_SLAB_PAIRS);
+    const size_t total = a.rows * a.T_dst * slabs;
+    for (size_t c = (size_t)blockIdx.x * ST_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * ST_WAVES) {   // wave-uniform
+        const size_t rj = c / slabs, r = rj / a.T_dst, j = rj - r * a.T_dst;
+        const uint32_t slab = (uint32_t)(c - rj * slabs);
+        uint64_t *dst = a.dst + (r * a.T_dst + j) * words;
+        const uint32_t head = (uint32_t)(((uintptr_t)dst >> 3) & 1u);
+        const uint32_t pr = slab * SG_SLAB_PAIRS + lane, w = head + 2 * pr;   // this lane's pair: words w, w + 1
+        const bool paired = pr < pairs, single = slab == 0 && lane == 63;
+        const uint32_t ws = head ? 0 : words - 1;                             // the word the pairs leave
+        const size_t s_begin = j * a.group, s_end = std::min(s_begin + a.group, a.T_src);
+        const uint64_t *ct = a.src + (r * a.T_src + s_begin) * words;
+        uint64_t acc0 = 0, acc1 = 0, accs = 0;
+#pragma unroll 4
+        for (size_t s = s_begin; s < s_end; s++, ct += words) {
+            if (paired) {
+                const uint64_t *p = ct + w;
+                if (((uintptr_t)p & 15u) == 0) {   // wave-uniform
+                    const u64x2 v = *reinterpret_cast<const u64x2 *>(p);
+                    acc0 += v.x, acc1 += v.y;
+                } else {
+                    acc0 += p[0], acc1 += p[1];
+                }
+            }
+            if (single) accs += ct[ws];
+        }
+        if (paired) *reinterpret_cast<u64x2 *>(dst + w) = u64x2{acc0 % FQ, acc1 % FQ};
+        if (single) dst[ws] = accs % FQ;
+    }
+}
+
 // A pure streaming write: the wave stores 16 bytes a lane, aligned to the destination (wave_fill_trivial), and the body -- the only
 // non-zero word -- is computed once per ciphertext, wave-uniform.  m < 2p (checked by the host) and Delta <= q / 2p + 1, so
 // m Delta < q + 2p fits 64 bits and one 64-bit remainder is the residue fbs_eval's trivial_body computes.
@@ -108,6 +173,21 @@ int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream)
 int dev_state_scatter(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream) {
     if (a.n_links * a.tc == 0) return FBS_OK;
     hipLaunchKernelGGL(k_state_scatter, st_grid(a.n_links * a.tc), dim3(64 * ST_WAVES), 0, stream, a);
+    FBS_HIP(ctx, hipGetLastError());
+    return FBS_OK;
+}
+
+int dev_state_gather_mapped(const fbs_ctx *ctx, const MappedCopy &a, hipStream_t stream) {
+    if (a.n_links * a.tc == 0) return FBS_OK;
+    hipLaunchKernelGGL(k_state_gather_mapped, st_grid(a.n_links * a.tc), dim3(64 * ST_WAVES), 0, stream, a);
+    FBS_HIP(ctx, hipGetLastError());
+    return FBS_OK;
+}
+
+int dev_state_sum_groups(const fbs_ctx *ctx, const SumGroups &a, hipStream_t stream) {
+    const size_t pairs = a.D / 2, slabs = std::max<size_t>(1, (pairs + SG_SLAB_PAIRS - 1) / SG_SLAB_PAIRS);
+    if (a.rows * a.T_dst == 0) return FBS_OK;
+    hipLaunchKernelGGL(k_state_sum_groups, st_grid(a.rows * a.T_dst * slabs), dim3(64 * ST_WAVES), 0, stream, a);
     FBS_HIP(ctx, hipGetLastError());
     return FBS_OK;
 }

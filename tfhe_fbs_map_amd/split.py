@@ -481,6 +481,38 @@ class ResidentOutputs:
             raise ValueError("no default compact width is recorded for these outputs: pass bits")
         return CompactOutputs(list(self.output_names), self.T, int(bits), self.state.fetch(bits=int(bits)), self.fingerprint, self.out_norm2)
 
+    # -- sample-axis operations (include/fbs_exec.h): views that read the samples through an index, and sums of runs of samples --
+    def samples(self, index, fill=0, names=None) -> "SampleView":
+        """A `SampleView`: a source of `Server.run_chain` with T = len(index) whose sample s is sample index[s] of these rows, or,
+        where index[s] == SAMPLE_NONE, a ciphertext of `fill` made on the GPU (an int for every row, or {row name: int})."""
+        return SampleView(self, index, fill, names)
+
+    def shift(self, d, fill=0, names=None) -> "SampleView":
+        """sample s reads sample s - d (d of either sign); samples that fall off either end take `fill`"""
+        return self.samples(shift_index(self.T, d), fill, names)
+
+    def broadcast(self, s, T, names=None) -> "SampleView":
+        """T samples that all read sample s"""
+        if not 0 <= int(s) < self.T:
+            raise ValueError("sample %d of %d" % (int(s), self.T))
+        return self.samples(np.full(int(T), int(s), np.uint32), 0, names)
+
+    def stride(self, start, step, names=None) -> "SampleView":
+        """samples start, start + step, .. below T"""
+        if int(step) < 1 or not 0 <= int(start) < self.T:
+            raise ValueError("stride(%d, %d) over %d samples" % (int(start), int(step), self.T))
+        return self.samples(np.arange(int(start), self.T, int(step), dtype=np.uint32), 0, names)
+
+    def sum_groups(self, group, max_value=1) -> "ResidentOutputs":
+        """A new `ResidentOutputs` of T' = ceil(T / group) samples: sample j of every row is the sum of samples [j group, (j + 1) group)
+        of that row, added on the GPU (fbs_state_sum_groups) -- how many of a group's bits are set, or the total of values up to
+        `max_value`.  Refused (`plan_sum_groups`) when a sum could leave [0, p).  The sums carry `out_norm2 * group`; no default
+        fetch width is recorded for them.  A chain that reads them refreshes them first (`plan_chain`: out_norm2 > 1)."""
+        if self.closed:
+            raise ValueError("the resident outputs are closed")
+        T, out_norm2 = plan_sum_groups(self.server.key.params.p_msg, self.T, group, max_value, self.out_norm2)
+        return ResidentOutputs(list(self.output_names), T, self.fingerprint, out_norm2, self.state.sum_groups(int(group)), self.server)
+
     def close(self):
         if self.state is not None:
             self.state.close()
@@ -490,6 +522,66 @@ class ResidentOutputs:
 
     def __exit__(self, *exc):
         self.close()
+
+
+SAMPLE_NONE = 0xFFFFFFFF   # FBS_SAMPLE_NONE: a sample of a view that reads no sample of the state, but the view's fill
+
+
+def shift_index(T, d):
+    """the index of `ResidentOutputs.shift`: [T] uint32, s - d where that is a sample, else SAMPLE_NONE"""
+    s = np.arange(int(T), dtype=np.int64) - int(d)
+    return np.where((s >= 0) & (s < int(T)), s, SAMPLE_NONE).astype(np.uint32)
+
+
+def plan_sum_groups(p, T, group, max_value=1, out_norm2=None):
+    """The pure part of `ResidentOutputs.sum_groups`: -> (T', out_norm2') or ValueError.  T' = ceil(T / group).  The summed samples'
+    errors are independent, so their variances add: out_norm2' = out_norm2 * group, as `output_noise_factors` treats a LinearProd
+    of `group` unit coefficients.  A sum of `group` values in [0, max_value] must stay in [0, p) -- the range the identity refresh
+    and `Client.decrypt` cover -- so group * max_value > p - 1 is refused; so is a group outside [1, 65536] (FBS_MAX_SUM_GROUP)."""
+    group, max_value = int(group), int(max_value)
+    if not 1 <= group <= 65536:
+        raise ValueError("group %d outside [1, 65536]" % group)
+    if max_value < 0:
+        raise ValueError("max_value %d is negative" % max_value)
+    if group * max_value > int(p) - 1:
+        raise ValueError("a sum of %d values up to %d reaches %d, above p - 1 = %d: it would not decrypt"
+                         % (group, max_value, group * max_value, int(p) - 1))
+    return -(-int(T) // group), None if out_norm2 is None else np.asarray(out_norm2, np.float64).reshape(-1) * group
+
+
+class SampleView:
+    """The rows of a `ResidentOutputs` read through a sample map (`ResidentOutputs.samples`): T = len(index) samples, sample s the
+    state's sample index[s], or a trivial ciphertext of `fill` where index[s] == SAMPLE_NONE.  A source of `Server.run_chain`
+    like the `ResidentOutputs` under it (fbs_eval_resident_mapped gathers on the GPU); gathering changes no ciphertext, so the view
+    carries the fingerprint and the per-row `out_norm2` of its state.  names: {row name of the state: its name in the view}, so
+    that two views of one state can feed one evaluation.  It owns nothing: closing the state closes its views."""
+
+    def __init__(self, base, index, fill=0, names=None):
+        index = np.asarray(index)
+        if index.ndim != 1 or index.size < 1 or index.dtype.kind not in "iu":
+            raise ValueError("a sample map is a list of at least one sample number")
+        bad = (index != SAMPLE_NONE) & ((index < 0) | (index >= base.T))
+        if bad.any():
+            s = int(np.flatnonzero(bad)[0])
+            raise ValueError("sample %d reads sample %d of a state of %d" % (s, int(index[s]), base.T))
+        self.base, self.index = base, np.ascontiguousarray(index, np.uint32)
+        self.T = int(index.size)
+        rows = list(base.output_names)
+        names = {str(a): str(b) for a, b in (names or {}).items()}
+        fills = fill if isinstance(fill, dict) else {n: fill for n in rows}
+        unknown = sorted((set(names) | set(map(str, fills))) - set(rows))
+        if unknown:
+            raise ValueError("%s are not rows of the state" % unknown)
+        self.output_names = [names.get(n, n) for n in rows]
+        if len(set(self.output_names)) != len(rows):
+            raise ValueError("names gives two rows of the view one name")
+        self.fill = [int(fills.get(n, 0)) for n in rows]   # by row, the state's order
+
+    fingerprint = property(lambda self: self.base.fingerprint)
+    out_norm2 = property(lambda self: self.base.out_norm2)
+    state = property(lambda self: self.base.state)
+    server = property(lambda self: self.base.server)
+    closed = property(lambda self: self.base.closed)
 
 
 def client_choice(env, config: ExecConfig, programs=()):
@@ -775,7 +867,8 @@ class Server:
         than a bootstrap output, are refreshed on the GPU: one bootstrap each per sample.  compact=True: compact outputs at `bits`
         (None: the width `compact_bits` would pick for the noise these outputs carry).  `plan_chain` says what is refused.
         A source may also be a `ResidentOutputs` of this server (a closed one, or another server's, is refused): its rows are read
-        on the GPU.  resident=True: the outputs stay there too -> `ResidentOutputs` (not with compact=True).
+        on the GPU; so may a `SampleView` of one (`ResidentOutputs.samples`, `shift`, `broadcast`, `stride`), which reads the
+        rows' samples through an index.  resident=True: the outputs stay there too -> `ResidentOutputs` (not with compact=True).
         refresh_public=True: public-key inputs are bootstrapped through the identity table before use even though their noise
         does not ask for it (one bootstrap per input and sample; they then go in with factor 1, as any refreshed link)."""
         from .params import public_input_factor, refresh_margin
@@ -784,7 +877,7 @@ class Server:
         prm, fuse = self.key.params, self.key.fuse_tables
         sources = [sources] if isinstance(sources, _source_types()) else list(sources)
         for k, src in enumerate(sources):
-            if isinstance(src, ResidentOutputs) and not src.closed and (src.server is not self or src.state.ctx is not self.ctx):
+            if isinstance(src, (ResidentOutputs, SampleView)) and not src.closed and (src.server is not self or src.state.ctx is not self.ctx):
                 raise ValueError("source %d is resident on another server" % k)
         links, T = plan_chain(prm, fuse, self.key.fingerprint, env, sources, rename)
         if refresh_public:
@@ -804,6 +897,37 @@ class Server:
             for state in expanded.values():   # (closing waits for the evaluations queued on the context)
                 state.close()
 
+    def fold(self, env, state: "ResidentOutputs", left, right, back=None, fill=0) -> "ResidentOutputs":
+        """A tree reduction of the T samples of `state` to one, on the GPU: `env` combines two samples into one, and each round
+        runs it resident at ceil(T / 2) samples on two views of the current state -- input `i` of `left` reads row left[i] at
+        sample 2j, input `i` of `right` reads row right[i] at sample 2j + 1, or a ciphertext of `fill` (an int, or {row name:
+        int}) where there is no such sample.  back: {output name of env: row name} under which the next round finds the rows it
+        reads (None: the outputs carry the rows' names already).  -> a `ResidentOutputs` of one sample, its rows named through
+        `back`.  Every round's state but the last is closed; `state` itself is left open.  With T = 1 already: a copy.
+        ValueError, before anything runs, when left and right do not cover env's inputs exactly once or name a row that `state`
+        or a round's renamed outputs do not hold."""
+        left, right, back = fold_plan(env.lower(), list(state.output_names), left, right, back)
+        if state.closed:
+            raise ValueError("the resident outputs are closed")
+        if state.T == 1:   # (sum_groups(1): a copy made on the GPU, word for word)
+            return ResidentOutputs(list(state.output_names), 1, state.fingerprint, state.out_norm2, state.state.sum_groups(1), self, state.compact_bits)
+        cur = state
+        while cur.T > 1:
+            half = -(-cur.T // 2)
+            even, odd = 2 * np.arange(half, dtype=np.int64), 2 * np.arange(half, dtype=np.int64) + 1
+            odd[odd >= cur.T] = SAMPLE_NONE
+            rows = list(cur.output_names)
+            views = [cur.samples(even, 0, {n: n + "@left" for n in rows}), cur.samples(odd, fill, {n: n + "@right" for n in rows})]
+            rename = {**{i: r + "@left" for i, r in left.items()}, **{i: r + "@right" for i, r in right.items()}}
+            try:
+                nxt = self.run_chain(env, views, rename=rename, resident=True)
+            finally:
+                if cur is not state:
+                    cur.close()
+            nxt.output_names = [back.get(n, n) for n in nxt.output_names]
+            cur = nxt
+        return cur
+
     def _run_links(self, env, prog, low, sources, links, T, expanded, compact, bits, resident):
         from .params import compact_output_bits
         prm, fuse = self.key.params, self.key.fuse_tables
@@ -815,7 +939,7 @@ class Server:
             elif ln.kind == "full":
                 feed.append(("full", src.cts[ln.index], ln.refresh))
             elif ln.kind == "state":
-                feed.append(("state", src.state, ln.index, ln.refresh))
+                feed.append(("state", src.state, ln.index, ln.refresh) + (() if ln.sample_index is None else (ln.sample_index, ln.fill)))
             elif ln.kind == "public":
                 feed.append(("state", expanded[ln.source], ln.index, ln.refresh))
             elif ln.kind == "plain":
@@ -847,14 +971,41 @@ class ChainLink:
     noise: float                  # its noise factor going in: 0 fresh or plain, 1 refreshed, the producer's out_norm2 for a plain full link,
                                   # params.public_input_factor for a public-key input
     margin: float | None = None   # params.refresh_margin of a refreshed link
+    sample_index: np.ndarray | None = None   # a "state" link through a `SampleView`: its sample map (uint32 [T]) ..
+    fill: int = 0                            # .. and the message of the samples that read none (SAMPLE_NONE)
 
 
-_SOURCE_TYPES = (EncryptedInputs, EncryptedOutputs, CompactOutputs, ResidentOutputs, PlainInputs)
+_SOURCE_TYPES = (EncryptedInputs, EncryptedOutputs, CompactOutputs, ResidentOutputs, SampleView, PlainInputs)
 
 
 def _source_types():
     from .public import PublicInputs      # (`public` imports this module)
     return _SOURCE_TYPES + (PublicInputs,)
+
+
+def fold_plan(low, rows, left, right, back=None):
+    """The pure part of `Server.fold`: -> (left, right, back) as dicts of str, or ValueError when left and right together do not feed
+    every input of the program exactly once, name a row the state does not hold, or name one the outputs renamed through `back` do
+    not hold (so that the second round could not run)."""
+    left, right = ({str(a): str(b) for a, b in (m or {}).items()} for m in (left, right))
+    back = {str(a): str(b) for a, b in (back or {}).items()}
+    inputs, outs = list(low["input_names"]), list(low["out_names"])
+    both = sorted(set(left) & set(right))
+    if both or sorted(set(left) | set(right)) != sorted(inputs):
+        raise ValueError("left and right feed inputs %s, the program has %s%s"
+                         % (sorted(set(left) | set(right)), sorted(inputs), (" (%s in both)" % both) if both else ""))
+    unknown = sorted(set(back) - set(outs))
+    if unknown:
+        raise ValueError("back names %s, which are not outputs of the program" % unknown)
+    after = [back.get(n, n) for n in outs]
+    if len(set(after)) != len(after):
+        raise ValueError("back gives two outputs one name")
+    needed = set(left.values()) | set(right.values())
+    for where, have in (("the state", rows), ("the outputs renamed through back", after)):
+        missing = sorted(needed - set(have))
+        if missing:
+            raise ValueError("%s holds no rows %s, which left and right read" % (where, missing))
+    return left, right, back
 
 
 def _names_of(src):
@@ -870,7 +1021,9 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
     refresh margin (`params.refresh_margin`) is below `params.refresh_margin_needed` at the program's norm2.  A full link whose
     producer's factor is at most 1 (a bootstrap output or a constant) goes in as it is: the program's parameter set assumes
     inputs no noisier than that.  Every other full link and every compact link is refreshed.  A `ResidentOutputs` is a full link
-    whose ciphertexts are on the GPU (kind "state"), under the same rule; a closed one is refused.
+    whose ciphertexts are on the GPU (kind "state"), under the same rule; a closed one is refused.  A `SampleView` is its
+    `ResidentOutputs` read through a sample map: the same link with the map and the row's fill attached (`sample_index`, `fill`), the
+    same rule by the state's `out_norm2`; it counts with its own T = len(index), under the names it gives its rows.
     A `PlainInputs` is public and belongs to no key: no fingerprint is asked of it, its link is noise-free (kind "plain", noise 0)
     and never refreshed; one without T takes the chain's, and a program fed by such sources alone has no T and is refused.
     A `public.PublicInputs` (public-key encryptions by a third party) is held to the fingerprint and to T like an `EncryptedInputs`;
@@ -900,7 +1053,7 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
                              "only; link the EncryptedOutputs, CompactOutputs or ResidentOutputs of that evaluation instead" % k)
         if not isinstance(src, _source_types()):
             raise TypeError("source %d is a %s, not EncryptedInputs, EncryptedOutputs, CompactOutputs or ResidentOutputs, or PublicInputs or PlainInputs" % (k, type(src).__name__))
-        if isinstance(src, ResidentOutputs) and src.closed:
+        if isinstance(src, (ResidentOutputs, SampleView)) and src.closed:
             raise ValueError("source %d is resident state that has been closed" % k)
         if not isinstance(src, PlainInputs) and src.fingerprint != fingerprint:
             raise ValueError("source %d was computed under another server key" % k)
@@ -959,13 +1112,18 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
                                  % (via, src.words.shape[-1], bits))
             link = ChainLink(name, k, j, "compact", True, 1.0, refresh_margin(params, bits, o2))
         else:
-            kind = "state" if isinstance(src, ResidentOutputs) else "full"
+            kind = "state" if isinstance(src, (ResidentOutputs, SampleView)) else "full"
             if kind == "full" and src.cts.shape[-1] != params.ct_words:
                 raise ValueError("input %s: ciphertexts of %d words, the server key's set has %d" % (via, src.cts.shape[-1], params.ct_words))
+            mapped = {}
+            if isinstance(src, SampleView):
+                if not 0 <= src.fill[j] < 2 * p:
+                    raise ValueError("input %s: fill %d outside [0, 2p) at the server key's p = %d" % (via, src.fill[j], p))
+                mapped = dict(sample_index=src.index, fill=src.fill[j])
             if o2 <= 1.0:
-                links.append(ChainLink(name, k, j, kind, False, o2))
+                links.append(ChainLink(name, k, j, kind, False, o2, **mapped))
                 continue
-            link = ChainLink(name, k, j, kind, True, 1.0, refresh_margin(params, None, o2))
+            link = ChainLink(name, k, j, kind, True, 1.0, refresh_margin(params, None, o2), **mapped)
         if link.margin < need * (1.0 - 1e-12):
             raise ValueError("input %s: its refresh would keep %.3f sigma (out_norm2 %g), below the %.3f the program's bootstraps keep"
                              % (via, link.margin, o2, need))
