@@ -187,24 +187,51 @@ def test_mapped_rows_mix_with_the_other_source_kinds(adder8):
         assert np.array_equal(prog.eval_resident(both, T), prog.eval_sources(same, T))
 
 
-def test_chunks_slice_the_index(adder8, monkeypatch):
+def every_link_shape(a, state, short):
+    """-> (a feed with every shape of device-side link in one call, the same over host-gathered full links): by i mod 6 an
+    unmapped row of `short` (a state of the call's T), a message per sample, two mapped rows of `state` (inputs 2 and 3: their
+    maps have FBS_SAMPLE_NONE at sample 0 and at sample T - 1), a seeded input, one message for all.  A chunked call reads the maps
+    at s0 + q, the messages at q, in slots of stride Tc > tc in the last chunk."""
+    dev, host = [], []
+    for i in range(a.n_in):
+        kind, refresh = i % 6, i % 5 == 0
+        if kind == 0:
+            dev.append(("state", short, a.rows[i], refresh))
+            host.append(("full", a.first[a.rows[i], :T], refresh))
+        elif kind in (2, 3):
+            dev.append(a.state_link(i, refresh, state))
+            host.append(a.host_link(i, refresh))
+        else:
+            other = {1: ("plain", a.msgs[i].copy()), 4: ("seeded", a.bodies[i], a.nonce0 + i * T), 5: ("plain", 1)}[kind]
+            dev.append(other)
+            host.append(other)
+    for i in (2, 3):
+        assert len(dev[i]) == 6 and dev[i][4][0] == dev[i][4][T - 1] == NONE
+    assert {i % 6 for i in range(a.n_in)} == set(range(6))
+    return dev, host
+
+
+@pytest.mark.parametrize("feed", ["mapped", "every_link_shape"])
+def test_chunks_slice_the_index(adder8, monkeypatch, feed):
     from tfhe_fbs_map_amd import Context
     a = adder8
-    dev, host = a.feeds(lambda i: i % 5 == 0)
+    mapped = lambda state: a.feeds(lambda i: i % 5 == 0, state=state)
+    host = mapped(None)[1] if feed == "mapped" else every_link_shape(a, a.state, a.state)[1]
     want = a.prog.eval_sources(host, T)
     monkeypatch.setenv("FBS_WIRE_BUDGET_MB", "2")
     assert 2 * 2**20 * 0.6 / (a.prog.n_slots * a.prm.ct_words * 8) < T / 3          # three chunks or more
     fresh = Context.evaluation_only(a.client.params, **a.client.export_seeded_keys())
     _, _, prog = _program(fresh, "adder8__search_p7")
     state = fresh.state(9, T_SRC).put(a.first)
-    dev, _ = a.feeds(lambda i: i % 5 == 0, state=state)
+    short = fresh.state(9, T).put(a.first[:, :T])
+    dev = mapped(state)[0] if feed == "mapped" else every_link_shape(a, state, short)[0]
     assert np.array_equal(prog.eval_resident(dev, T), want)
     out = fresh.state(prog.n_outputs, T)
     prog.eval_resident(dev, T, out_state=out)
     assert np.array_equal(out.fetch(), want)
     monkeypatch.delenv("FBS_WIRE_BUDGET_MB")
     fresh.close()
-    assert out.closed and state.closed
+    assert out.closed and state.closed and short.closed
 
 
 def test_the_identity_map_is_the_unmapped_call_and_the_old_entry_is_unchanged(adder8):

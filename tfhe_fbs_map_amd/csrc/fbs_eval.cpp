@@ -50,6 +50,8 @@ static int reserve_wires(fbs_ctx *ctx, const fbs_prog *prog, size_t T, size_t *c
 }
 
 static uint64_t trivial_body(const fbs_ctx *ctx, int64_t out_slot) { return fq_mul(fq_from_i64(-1 - out_slot), 2 * ctx->delta_half); }
+// the body of the trivial ciphertext of a message m in [0, 2p): m Delta mod q, as k_wire_load works it out for a message per sample
+static uint64_t message_body(const fbs_ctx *ctx, int64_t m) { return (uint64_t)m * (2 * ctx->delta_half) % FQ; }
 
 // ---- the program evaluations: one chunk loop, each entry its checks, its scratch and its two stages -------------------------
 // what every evaluation checks first: the keys, the program's owner, the buffers of a call with samples
@@ -136,7 +138,7 @@ static int store_compact(fbs_ctx *ctx, const fbs_prog *prog, const CompactStore 
 // ---- eval_sources: programs over mixed input sources, the evaluation behind every host-buffer entry ---------------------------
 // One more pair of stages on eval_chunks.  Load: the steps below, in their order; compact inputs and inputs marked `refresh` are
 // refreshed in groups whose rows fit the scratch reserve_wires sized (max_sources x Tc rows).  Store: full ciphertexts
-// (store_host_cts), compact ones (store_compact), or -- fbs_eval_resident's out_state -- one scatter launch per chunk into a state.
+// (store_host_cts), compact ones (store_compact), or -- fbs_eval_resident's out_state -- one store launch per chunk (k_wire_store) into a state.
 // With out_state and no full or compact host input (plaintext messages are none) nothing has to come back: the chunks are queued
 // without waiting, and the call returns once the arrays it was given have been read (`inputs_event`, after the last chunk's load).
 //
@@ -149,14 +151,16 @@ struct SourcePlan {
     size_t T = 0;
     uint32_t out_bits = 0;
     size_t W_in = 0, W_out = 0;                             // words of the widest compact input, of a compact output (0: none)
-    std::vector<uint32_t> compact_in, full_refresh, plain_in;   // input indices by kind
-    bool any_seeded = false, host_cts = false, plain_msgs = false;   // host_cts: some input is ciphertexts in host memory;
-                                                                     // plain_msgs: some plaintext input brings a message per sample
-    std::vector<StateLink> links;                           // the gather list [n_gather], then the scatter list
-    size_t n_gather = 0;
-    std::vector<PlainLink> plain;                           // the fill list of the plaintext inputs, behind the links in the same buffer
-    std::vector<MappedLink> mapped;                         // the mapped gather list (resident inputs with a sample map), behind the fill list
-    std::vector<uint32_t> mapped_in;                        // and their input indices: map j of the call lies at d_idx + refresh slots + j T
+    std::vector<uint32_t> compact_in, full_refresh;         // input indices by kind
+    bool any_seeded = false, host_cts = false;              // host_cts: some input is ciphertexts in host memory
+    std::vector<WireLink> links;                            // the input links [n_in_links], in input order, then the output links
+    size_t n_in_links = 0;
+    struct At {
+        uint32_t input, link;
+    };
+    // the links reserve_sources patches a device address into, with their inputs: those with a sample map (map j of the call lies
+    // at d_idx + refresh slots + j T), those of plaintext inputs that bring a message per sample (at d_io_msgs + input Tc)
+    std::vector<At> mapped, msgs;
     std::vector<uint32_t> refresh_slot;                     // the slots to refresh, compact inputs first
     bool wait = true;                                       // results or pageable ciphertexts cross the bus: chunk by chunk
     // reserve_sources: the chunk, the rows of the modulus-switch scratch a group of refreshes may fill, the identity table
@@ -166,7 +170,6 @@ struct SourcePlan {
 
     bool resident(size_t i) const { return res && res[i].state; }
     bool has_map(size_t i) const { return maps && maps[i].index; }
-    size_t plain_bytes() const { return plain.size() * sizeof(PlainLink); }
     bool from(size_t i, uint32_t kind) const { return !resident(i) && src[i].kind == kind; }
     bool per_sample(size_t i) const { return from(i, FBS_SRC_PLAIN) && !src[i].bits; }
 };
@@ -218,12 +221,9 @@ static int plan_sources(const fbs_ctx *ctx, const fbs_prog *prog, const fbs_inpu
     for (size_t i = 0; i < n_in; i++) {
         if (p.resident(i)) {
             // (a mapped link's index is filled in by reserve_sources; its fill body is what FBS_SRC_PLAIN writes for that message)
-            if (p.has_map(i)) {
-                p.mapped.push_back(MappedLink{res[i].state->d + (size_t)res[i].row * res[i].state->T * ctw, nullptr,
-                                              (uint64_t)maps[i].fill * (2 * ctx->delta_half) % FQ, prog->in_slot[i]});
-                p.mapped_in.push_back((uint32_t)i);
-            } else
-                p.links.push_back(StateLink{res[i].state->d + (size_t)res[i].row * T * ctw, prog->in_slot[i]});
+            if (p.has_map(i)) p.mapped.push_back({(uint32_t)i, (uint32_t)p.links.size()});
+            p.links.push_back(WireLink{res[i].state->d + (size_t)res[i].row * res[i].state->T * ctw, nullptr, nullptr,
+                                       p.has_map(i) ? message_body(ctx, maps[i].fill) : 0, prog->in_slot[i]});
             if (res[i].refresh) p.full_refresh.push_back((uint32_t)i);
             continue;
         }
@@ -240,9 +240,8 @@ static int plan_sources(const fbs_ctx *ctx, const fbs_prog *prog, const fbs_inpu
                 if (m[q] < 0 || m[q] >= 2 * (int64_t)ctx->p.p_msg)
                     return set_error(ctx, FBS_E_INVALID, who + "message " + std::to_string(m[q]) + " outside [0, 2p)");
             // (a per-sample input's messages lie where its bodies would: reserve_sources fills in the device address)
-            p.plain.push_back(PlainLink{nullptr, x.bits ? m[0] : 0, prog->in_slot[i]});
-            p.plain_in.push_back((uint32_t)i);
-            p.plain_msgs |= !x.bits;
+            if (!x.bits) p.msgs.push_back({(uint32_t)i, (uint32_t)p.links.size()});
+            p.links.push_back(WireLink{nullptr, nullptr, nullptr, x.bits ? message_body(ctx, m[0]) : 0, prog->in_slot[i]});
             continue;
         }
         size_t words = x.kind == FBS_SRC_SEEDED ? 1 : ctw;
@@ -261,10 +260,10 @@ static int plan_sources(const fbs_ctx *ctx, const fbs_prog *prog, const fbs_inpu
         if (T > SIZE_MAX / 8 / words) return set_error(ctx, FBS_E_INVALID, who + "T * words overflow");
     }
     if (T > SIZE_MAX / 8 / std::max<size_t>(1, n_out) / std::max(ctw, p.W_out)) return set_error(ctx, FBS_E_INVALID, "n_outputs * T words overflow");
-    p.n_gather = p.links.size();
+    p.n_in_links = p.links.size();
     for (size_t o = 0; out_state && o < n_out; o++) {
         const int64_t w = prog->out_slot[o];
-        p.links.push_back(StateLink{out_state->d + o * T * ctw, w >= 0 ? (uint64_t)w : STATE_LINK_CONST | trivial_body(ctx, w)});
+        p.links.push_back(WireLink{out_state->d + o * T * ctw, nullptr, nullptr, w >= 0 ? 0 : trivial_body(ctx, w), w >= 0 ? (uint64_t)w : WIRE_NO_SLOT});
     }
     for (uint32_t i : p.compact_in) p.refresh_slot.push_back(prog->in_slot[i]);
     for (uint32_t i : p.full_refresh) p.refresh_slot.push_back(prog->in_slot[i]);
@@ -273,13 +272,13 @@ static int plan_sources(const fbs_ctx *ctx, const fbs_prog *prog, const fbs_inpu
 }
 
 // the scratch of a planned call: the chunk and its wire slots (the packed staging of compact inputs and outputs counted in its
-// budget), the message rows, the staging, the refresh slots and the identity table, the link lists, the event of the no-wait path
+// budget), the message rows, the staging, the refresh slots and the identity table, the links, the event of the no-wait path
 static int reserve_sources(fbs_ctx *ctx, SourcePlan &p) {
     const fbs_prog *prog = p.prog;
     const size_t W_stage = std::max(p.W_in, p.W_out), rows_per_sample = std::max(1u, prog->max_sources);
     int rc;
     if ((rc = reserve_wires(ctx, prog, p.T, &p.Tc, rows_per_sample * W_stage * 8)) != FBS_OK) return rc;
-    if ((p.any_seeded || p.plain_msgs) && (rc = ensure_io_msgs(ctx, prog->n_inputs * p.Tc)) != FBS_OK) return rc;
+    if ((p.any_seeded || !p.msgs.empty()) && (rc = ensure_io_msgs(ctx, prog->n_inputs * p.Tc)) != FBS_OK) return rc;
     p.cap_rows = rows_per_sample * p.Tc;   // (ensure_ms has made d_ms at least this long)
     if (W_stage && (rc = grow(ctx, ctx->d_compact, ctx->compact_capacity, p.cap_rows * W_stage, 8, true)) != FBS_OK) return rc;
     if (!p.refresh_slot.empty()) {
@@ -291,43 +290,26 @@ static int reserve_sources(fbs_ctx *ctx, SourcePlan &p) {
     if (p.T > (SIZE_MAX / 4 - p.refresh_slot.size()) / std::max<size_t>(1, p.mapped.size())) return set_error(ctx, FBS_E_INVALID, "the sample maps overflow");
     const size_t idx_words = p.refresh_slot.size() + p.mapped.size() * p.T;
     if (idx_words && (rc = ensure_idx(ctx, idx_words)) != FBS_OK) return rc;
-    for (size_t j = 0; j < p.mapped.size(); j++) p.mapped[j].index = ctx->d_idx + p.refresh_slot.size() + j * p.T;
+    for (size_t j = 0; j < p.mapped.size(); j++) p.links[p.mapped[j].link].index = ctx->d_idx + p.refresh_slot.size() + j * p.T;
     if (p.out_bits) p.cs = compact_store_for(ctx, prog, p.out_bits, p.Tc);
-    for (size_t j = 0; j < p.plain_in.size(); j++)
-        if (p.per_sample(p.plain_in[j])) p.plain[j].msgs = ctx->d_io_msgs + (size_t)p.plain_in[j] * p.Tc;
-    const size_t link_units = p.links.size() + (p.plain_bytes() + p.mapped.size() * sizeof(MappedLink) + sizeof(StateLink) - 1) / sizeof(StateLink);
-    if (link_units && (rc = grow(ctx, ctx->d_links, ctx->links_capacity, std::max<size_t>(link_units, 1 << 12), sizeof(StateLink), false)) != FBS_OK)
+    for (const SourcePlan::At &m : p.msgs) p.links[m.link].msgs = ctx->d_io_msgs + (size_t)m.input * p.Tc;
+    if (!p.links.empty() && (rc = grow(ctx, ctx->d_links, ctx->links_capacity, std::max<size_t>(p.links.size(), 1 << 12), sizeof(WireLink), false)) != FBS_OK)
         return rc;
     if (!p.wait && !ctx->inputs_event) FBS_HIP(ctx, hipEventCreateWithFlags(&ctx->inputs_event, hipEventDisableTiming));
     return FBS_OK;
 }
 
-// the mapped gather list on the device: behind the link lists and the fill list (all three hold 8-byte members only)
-static MappedLink *d_mapped(const fbs_ctx *ctx, const SourcePlan &p) {
-    return reinterpret_cast<MappedLink *>(reinterpret_cast<char *>(ctx->d_links + p.links.size()) + p.plain_bytes());
-}
-
 // -- the load stage of a chunk, step by step --
-// with the first chunk (after eval_chunks's scratch_wait): the refresh slots, the link lists and the fill list
+// with the first chunk (after eval_chunks's scratch_wait): the refresh slots, the links, the sample maps
 static int upload_lists(fbs_ctx *ctx, const SourcePlan &p, const Chunk &c) {
     if (c.s0 != 0) return FBS_OK;
     if (!p.refresh_slot.empty())
         FBS_HIP(ctx, hipMemcpyAsync(ctx->d_idx, p.refresh_slot.data(), p.refresh_slot.size() * 4, hipMemcpyHostToDevice, c.s));
     if (!p.links.empty())
-        FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links, p.links.data(), p.links.size() * sizeof(StateLink), hipMemcpyHostToDevice, c.s));
-    if (!p.plain.empty())
-        FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links + p.links.size(), p.plain.data(), p.plain_bytes(), hipMemcpyHostToDevice, c.s));
-    if (!p.mapped.empty())
-        FBS_HIP(ctx, hipMemcpyAsync(d_mapped(ctx, p), p.mapped.data(), p.mapped.size() * sizeof(MappedLink), hipMemcpyHostToDevice, c.s));
-    for (size_t j = 0; j < p.mapped.size(); j++)   // the whole map of every mapped input, once a call: the chunks slice it
-        FBS_HIP(ctx, hipMemcpyAsync(const_cast<uint32_t *>(p.mapped[j].index), p.maps[p.mapped_in[j]].index, p.T * 4, hipMemcpyHostToDevice, c.s));
+        FBS_HIP(ctx, hipMemcpyAsync(ctx->d_links, p.links.data(), p.links.size() * sizeof(WireLink), hipMemcpyHostToDevice, c.s));
+    for (const SourcePlan::At &m : p.mapped)   // the whole map of every mapped input, once a call: the chunks slice it
+        FBS_HIP(ctx, hipMemcpyAsync(const_cast<uint32_t *>(p.links[m.link].index), p.maps[m.input].index, p.T * 4, hipMemcpyHostToDevice, c.s));
     return FBS_OK;
-}
-
-// inputs that are rows of states: one launch, and one more for those with a sample map
-static int gather_resident(fbs_ctx *ctx, const SourcePlan &p, const Chunk &c) {
-    if (int rc = dev_state_gather(ctx, StateCopy{ctx->d_links, p.n_gather, ctx->d_wires, c.Tc, c.s0, c.tc, ctx->D}, c.s)) return rc;
-    return dev_state_gather_mapped(ctx, MappedCopy{d_mapped(ctx, p), p.mapped.size(), ctx->d_wires, c.Tc, c.s0, c.tc, ctx->D}, c.s);
 }
 
 // the end of the run of inputs that starts at i0: every later one, below n, `joins` it
@@ -349,17 +331,16 @@ static int upload_rows(fbs_ctx *ctx, const SourcePlan &p, const Chunk &c, size_t
     return FBS_OK;
 }
 
-// plaintext inputs: the messages of the chunk (8 bytes a sample, nothing for a broadcast), then one launch that writes every
-// trivial ciphertext
-static int fill_plain(fbs_ctx *ctx, const SourcePlan &p, const Chunk &c) {
+// inputs that are rows of states, read as they are or through a sample map, and plaintext inputs: the plaintext messages of the
+// chunk (8 bytes a sample, nothing for a broadcast), then one launch that moves every row and writes every trivial ciphertext
+static int load_links(fbs_ctx *ctx, const SourcePlan &p, const Chunk &c) {
     const size_t n_in = p.prog->n_inputs;
     for (size_t j0 = 0, j1; j0 < n_in; j0 = j1) {   // the messages of the chunk, by stretches of inputs that bring one a sample
         j1 = run_end(j0, n_in, [&](size_t i) { return p.per_sample(j0) && p.per_sample(i); });
         if (!p.per_sample(j0)) continue;
         if (int rc = upload_rows(ctx, p, c, j0, j1)) return rc;
     }
-    const PlainLink *d_plain = reinterpret_cast<const PlainLink *>(ctx->d_links + p.links.size());
-    return dev_fill_plain(ctx, PlainFill{d_plain, p.plain.size(), ctx->d_wires, c.Tc, c.tc, ctx->D, 2 * ctx->delta_half}, c.s);
+    return dev_wire_load(ctx, WireCopy{ctx->d_links, p.n_in_links, ctx->d_wires, c.Tc, c.s0, c.tc, ctx->D, 2 * ctx->delta_half}, c.s);
 }
 
 static int copy_full(fbs_ctx *ctx, const SourcePlan &p, const Chunk &c) {
@@ -435,18 +416,18 @@ static int eval_sources(fbs_ctx *ctx, fbs_prog *prog, const fbs_input_src *src, 
     auto load = [&](size_t s0, size_t tc) {
         const Chunk c{Tc, s0, tc, s};
         int rc;
-        if ((rc = upload_lists(ctx, p, c)) || (rc = gather_resident(ctx, p, c)) || (rc = fill_plain(ctx, p, c)) || (rc = copy_full(ctx, p, c)) ||
-            (rc = expand_seeded(ctx, p, c)) || (rc = refresh_compact(ctx, p, c)) || (rc = refresh_full(ctx, p, c)))
+        if ((rc = upload_lists(ctx, p, c)) || (rc = load_links(ctx, p, c)) || (rc = copy_full(ctx, p, c)) || (rc = expand_seeded(ctx, p, c)) ||
+            (rc = refresh_compact(ctx, p, c)) || (rc = refresh_full(ctx, p, c)))
             return rc;
         if (!p.wait && s0 + tc == T) FBS_HIP(ctx, hipEventRecord(ctx->inputs_event, s));   // every array of the caller has been queued
         return FBS_OK;
     };
     auto store = [&](size_t s0, size_t tc) {
-        if (out_state) return dev_state_scatter(ctx, StateCopy{ctx->d_links + p.n_gather, prog->n_outputs, ctx->d_wires, Tc, s0, tc, ctx->D}, s);
+        if (out_state) return dev_wire_store(ctx, WireCopy{ctx->d_links + p.n_in_links, prog->n_outputs, ctx->d_wires, Tc, s0, tc, ctx->D, 0}, s);
         return out_bits ? store_compact(ctx, prog, p.cs, out, T, Tc, s0, tc, s) : store_host_cts(ctx, prog, out, T, Tc, s0, tc, s);
     };
     rc = eval_chunks(ctx, prog, T, Tc, s, p.wait, load, store);
-    // the link lists, refresh slots, seeded bodies and plaintext messages live in pageable memory of this call or its caller: read before it returns.
+    // the links, sample maps, refresh slots, seeded bodies and plaintext messages live in pageable memory of this call or its caller: read before it returns.
     // A call that failed part way may have queued copies from them without reaching the event: it waits for the stream instead.
     if (!p.wait && rc == FBS_OK) FBS_HIP(ctx, hipEventSynchronize(ctx->inputs_event));
     if (!p.wait && rc != FBS_OK) (void)hipStreamSynchronize(s);

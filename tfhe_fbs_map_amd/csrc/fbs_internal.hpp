@@ -112,64 +112,38 @@ struct IoView {
     size_t rows, per_row;
 };
 
-// Resident state (fbs_state.hip): link e of a launch joins a state row and a wire slot.  `row` points at sample 0 of the row
-// ([T][D + 1] words of a state block); `slot` is the wire slot, or -- for the scatter -- STATE_LINK_CONST | body: the row takes
-// the trivial ciphertext of that body (a constant output; bodies are residues below 2^46).
-constexpr uint64_t STATE_LINK_CONST = 1ull << 63;
-struct StateLink {
+// The device-side inputs and outputs of a chunk (fbs_state.hip): link e of a launch joins wire slot `slot`, samples q < tc, and the
+// ciphertexts of samples s0 + q of a call; the side a link does not have is the trivial ciphertext (0, .., 0, body).  Loading,
+// sample q comes from `row` (sample 0 of a state row, [T_src][D + 1] words) at sample index[s0 + q] -- `index` is the call's whole
+// map on the device, [T] words, checked by the host against T_src; null is the identity -- and, where there is no row or the entry
+// is FBS_SAMPLE_NONE, is the trivial ciphertext of msgs[q] (the chunk's plaintext messages on the device; null: of `body`, a
+// residue worked out on the host).  Storing, sample s0 + q of `row` takes the slot's sample q, or -- slot WIRE_NO_SLOT, a constant
+// output -- the trivial ciphertext of `body`; `index` and `msgs` are not read.  Every member is 8 bytes.
+constexpr uint64_t WIRE_NO_SLOT = ~0ull;
+struct WireLink {
     uint64_t *row;
+    const uint32_t *index;
+    const int64_t *msgs;
+    uint64_t body;
     uint64_t slot;
 };
-struct StateCopy {
-    const StateLink *links;   // [n_links], device
+struct WireCopy {
+    const WireLink *links;   // [n_links], device
     size_t n_links;
-    uint64_t *wires;          // wire slots [n_slots][Tc][D + 1]
-    size_t Tc;                // samples per slot in the wire buffer (stride)
-    size_t s0, tc;            // sample q < tc of a slot is sample s0 + q of a row
+    uint64_t *wires;         // wire slots [n_slots][Tc][D + 1]
+    size_t Tc;               // samples per slot in the wire buffer (stride)
+    size_t s0, tc;           // sample q < tc of a slot is sample s0 + q of the call
     uint32_t D;
+    uint64_t delta;          // 2 round(q / 4p): a message m in [0, 2p) is the body m delta mod q (read by the load)
 };
 
-// Sample-axis operations (fbs_state.hip).  The mapped gather: link e of a launch fills wire slot `slot`, sample q < tc, with sample
-// index[s0 + q] of the state row at `row` ([T_src][D + 1] words; the host has checked every entry against T_src), or -- the entry
-// FBS_SAMPLE_NONE -- with the trivial ciphertext of body `fill` (fill Delta mod q, worked out on the host).  `index` is the
-// call's whole map on the device, [T] words.
-struct MappedLink {
-    const uint64_t *row;
-    const uint32_t *index;
-    uint64_t fill;
-    uint64_t slot;
-};
-struct MappedCopy {
-    const MappedLink *links;   // [n_links], device
-    size_t n_links;
-    uint64_t *wires;           // wire slots [n_slots][Tc][D + 1]
-    size_t Tc;
-    size_t s0, tc;
-    uint32_t D;
-};
-// The group sum: sample j < T_dst of row r < rows of dst ([T_dst][D + 1] words a row) becomes the word-wise sum modulo q of samples
+// The group sum (fbs_state.hip): sample j < T_dst of row r < rows of dst ([T_dst][D + 1] words a row) becomes the word-wise sum modulo q of samples
 // [j group, min((j + 1) group, T_src)) of row r of src
 struct SumGroups {
     const uint64_t *src;   // sample 0 of the first row read
     uint64_t *dst;         // sample 0 of the first row written
     size_t rows, T_src, T_dst, group;
     uint32_t D;
-};
-
-// Plaintext inputs (FBS_SRC_PLAIN, fbs_state.hip): entry e of a launch fills wire slot `slot`, samples q < tc, with the trivial
-// ciphertexts of msgs[q] (the chunk's messages on the device) or, msgs null, of the one message `value` (a broadcast input)
-struct PlainLink {
-    const int64_t *msgs;
-    int64_t value;
-    uint64_t slot;
-};
-struct PlainFill {
-    const PlainLink *links;   // [n_links], device
-    size_t n_links;
-    uint64_t *wires;          // wire slots [n_slots][Tc][D + 1]
-    size_t Tc, tc;
-    uint32_t D;
-    uint64_t delta;           // 2 round(q / 4p): a message m in [0, 2p) is the body m delta mod q
 };
 
 #ifndef FBS_HOST_ONLY
@@ -295,10 +269,10 @@ struct fbs_ctx : fbs::HostState {
     bool scratch_used = false;
 
     // Resident state: the blocks fbs_state_create made and nobody destroyed yet (fbs_ctx_destroy frees them), and the link lists
-    // of the current fbs_eval_resident (gather list, then scatter list), uploaded with its first chunk
+    // of the current eval_sources (input links, then output links), uploaded with its first chunk
     std::vector<fbs_state *> states;
     size_t state_bytes = 0;
-    fbs::StateLink *d_links = nullptr;
+    fbs::WireLink *d_links = nullptr;
     size_t links_capacity = 0;
     hipEvent_t inputs_event = nullptr;   // an fbs_eval_resident that does not wait for its results: its host arrays have been read
 
@@ -555,14 +529,11 @@ int dev_audit_fields(const fbs_ctx *ctx, const uint32_t *d_ms, size_t rows, size
 int dev_audit_reduce(const fbs_ctx *ctx, const int64_t *d_err, size_t rows, size_t s_count, bool fields, fbs_audit_row *d_stats,
                      hipStream_t stream);
 
-// resident state (fbs_state.hip): the links of `a` between state rows and wire slots, one launch each
-int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);
-int dev_state_scatter(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream);
-// sample-axis operations: the mapped links of a chunk into their wire slots, one launch; the group sums of `a`, one launch
-int dev_state_gather_mapped(const fbs_ctx *ctx, const MappedCopy &a, hipStream_t stream);
+// the device-side inputs and outputs of a chunk (fbs_state.hip): the links of `a` into their wire slots, or out of them into state
+// rows, one launch each; the group sums of `a`, one launch
+int dev_wire_load(const fbs_ctx *ctx, const WireCopy &a, hipStream_t stream);
+int dev_wire_store(const fbs_ctx *ctx, const WireCopy &a, hipStream_t stream);
 int dev_state_sum_groups(const fbs_ctx *ctx, const SumGroups &a, hipStream_t stream);
-// plaintext inputs: the trivial ciphertexts of the links of `a` into their wire slots, one launch
-int dev_fill_plain(const fbs_ctx *ctx, const PlainFill &a, hipStream_t stream);
 // public-key inputs (fbs_public.hip): sample extraction of the GLWE samples d_glwe [ceil(count / N)][k + 1][N] into the big-key
 // ciphertexts d_cts [count][D + 1], message j from coefficient j mod N of sample j / N; word for word host_pub_expand
 int dev_expand_public(const fbs_ctx *ctx, const uint64_t *d_glwe, size_t count, uint64_t *d_cts, hipStream_t stream);

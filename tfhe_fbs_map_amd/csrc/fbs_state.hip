@@ -1,27 +1,24 @@
-// Resident state (fbs_state, fbs_eval_resident), gfx950: ciphertexts between the rows of state blocks [rows][T][D + 1] and the wire
-// slots [n_slots][Tc][D + 1] of a chunk; and the plaintext inputs of a chunk (FBS_SRC_PLAIN), written into the same slots.
+// The device-side inputs and outputs of a chunk, gfx950: ciphertexts between the wire slots [n_slots][Tc][D + 1] of a chunk and the
+// rows of state blocks [rows][T][D + 1] (fbs_state, fbs_eval_resident, fbs_eval_resident_mapped), and the plaintext inputs of a chunk
+// (FBS_SRC_PLAIN) written into the same slots.  One list of links (WireLink, fbs_internal.hpp) says what goes where:
 //
-//   k_state_gather    wire slot of link e, sample q  <-  row of link e, sample s0 + q     (the resident inputs of a chunk)
-//   k_state_scatter   row of link e, sample s0 + q   <-  wire slot of link e, sample q    (its outputs; a constant output is
-//                     written as the trivial ciphertext fbs_eval returns for it)
-//   k_fill_plain      wire slot of link e, sample q  <-  the trivial ciphertext of the link's message for sample q (the plaintext
-//                     inputs of a chunk, FBS_SRC_PLAIN: D zero words, then m Delta mod q)
+//   k_wire_load    wire slot of link e, sample q  <-  row of link e, sample index[s0 + q] (no index: sample s0 + q); or, where the
+//                  link has no row or the entry is FBS_SAMPLE_NONE, the trivial ciphertext (D zero words, then the body) of the
+//                  link's message for sample q, m Delta mod q, or of its one body.  Every input of a chunk that is made on the
+//                  device: state rows read as they are or ACROSS samples, plaintext messages.
+//   k_wire_store   row of link e, sample s0 + q   <-  wire slot of link e, sample q    (the outputs into a state; a constant output
+//                  is written as the trivial ciphertext fbs_eval returns for it)
 //
-// One launch moves every link of the chunk: the (link, sample) grid is dealt to waves, one ciphertext per wave at a time.  A
-// ciphertext is D + 1 words, an odd number, so one at an odd index starts 8 bytes off a 16-byte line.  Where source and
-// destination agree in that, the wave moves 16 bytes a lane each way, with the one word before or after the pairs on its own
-// (as k_expand_seeded stores its blocks); where they differ, the stores stay 16 bytes wide and aligned and each takes two 8-byte
-// loads -- consecutive lanes on consecutive words either way.  Plain vector loads and stores only.  These kernels are copies: they
-// are not in fbs_kernel_catalog and the profile does not count them.
+// One launch moves every link of the chunk: the (link, sample) grid is dealt to waves, one ciphertext per wave at a time, and what
+// a wave does with it is one wave-uniform decision (one index word per ciphertext).  A ciphertext is D + 1 words, an odd number, so
+// one at an odd index starts 8 bytes off a 16-byte line.  Where source and destination agree in that, the wave moves 16 bytes a
+// lane each way, with the one word before or after the pairs on its own (as k_expand_seeded stores its blocks); where they differ
+// -- through an index both cases occur within one row -- the stores stay 16 bytes wide and aligned and each takes two 8-byte loads,
+// consecutive lanes on consecutive words either way.  Plain vector loads and stores only.  These kernels are copies: they are not
+// in fbs_kernel_catalog and the profile does not count them.
 //
-// Sample-axis operations (fbs_eval_resident_mapped, fbs_state_sum_groups) -- the steps ACROSS samples, next to the copies above:
-//
-//   k_state_gather_mapped   wire slot of link e, sample q  <-  row of link e, sample index[s0 + q], or the trivial ciphertext of
-//                           the link's fill where the entry is FBS_SAMPLE_NONE.  The same grid as k_state_gather; one index word
-//                           per ciphertext, wave-uniform.  Source and destination sample differ now, so the two alignment cases
-//                           of wave_copy_ct both occur within one row.
-//   k_state_sum_groups      row r, sample j of dst  <-  the word-wise sum mod q of samples [j group, (j + 1) group) of row r of src
-//                           (a streaming reduction: every source word is read once; no LDS, no atomics).
+//   k_state_sum_groups   row r, sample j of dst  <-  the word-wise sum mod q of samples [j group, (j + 1) group) of row r of src
+//                        (fbs_state_sum_groups; a streaming reduction: every source word is read once; no LDS, no atomics).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -69,38 +66,36 @@ __device__ __forceinline__ void wave_fill_trivial(uint64_t *dst, uint64_t body, 
     }
 }
 
-__global__ __launch_bounds__(64 * ST_WAVES) void k_state_gather(StateCopy a) {
+// A trivial ciphertext is a pure streaming write, its body -- the only non-zero word -- one value per ciphertext.  m < 2p (checked
+// by the host) and Delta <= q / 2p + 1, so m Delta < q + 2p fits 64 bits and one 64-bit remainder is the residue fbs_eval's
+// trivial_body computes.
+__global__ __launch_bounds__(64 * ST_WAVES) void k_wire_load(WireCopy a) {
     const uint32_t lane = threadIdx.x & 63u, words = a.D + 1;
     const size_t total = a.n_links * a.tc;
     for (size_t c = (size_t)blockIdx.x * ST_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * ST_WAVES) {   // wave-uniform
         const size_t e = c / a.tc, q = c - e * a.tc;
-        const StateLink ln = a.links[e];
-        wave_copy_ct(a.wires + ((size_t)ln.slot * a.Tc + q) * words, ln.row + (a.s0 + q) * words, words, lane);
-    }
-}
-
-__global__ __launch_bounds__(64 * ST_WAVES) void k_state_scatter(StateCopy a) {
-    const uint32_t lane = threadIdx.x & 63u, words = a.D + 1;
-    const size_t total = a.n_links * a.tc;
-    for (size_t c = (size_t)blockIdx.x * ST_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * ST_WAVES) {   // wave-uniform
-        const size_t e = c / a.tc, q = c - e * a.tc;
-        const StateLink ln = a.links[e];
-        uint64_t *dst = ln.row + (a.s0 + q) * words;
-        if (ln.slot & STATE_LINK_CONST) wave_fill_trivial(dst, ln.slot & ~STATE_LINK_CONST, words, lane);
-        else wave_copy_ct(dst, a.wires + ((size_t)ln.slot * a.Tc + q) * words, words, lane);
-    }
-}
-
-__global__ __launch_bounds__(64 * ST_WAVES) void k_state_gather_mapped(MappedCopy a) {
-    const uint32_t lane = threadIdx.x & 63u, words = a.D + 1;
-    const size_t total = a.n_links * a.tc;
-    for (size_t c = (size_t)blockIdx.x * ST_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * ST_WAVES) {   // wave-uniform
-        const size_t e = c / a.tc, q = c - e * a.tc;
-        const MappedLink ln = a.links[e];
-        const uint32_t from = ln.index[a.s0 + q];   // (one word for the wave; below the row's samples, or FBS_SAMPLE_NONE: the host checked)
+        const WireLink ln = a.links[e];
+        size_t from = a.s0 + q;
+        bool none = !ln.row;
+        if (ln.row && ln.index) {   // (one word for the wave; below the row's samples, or FBS_SAMPLE_NONE: the host checked)
+            const uint32_t j = ln.index[from];
+            from = j, none = j == FBS_SAMPLE_NONE;
+        }
         uint64_t *dst = a.wires + ((size_t)ln.slot * a.Tc + q) * words;
-        if (from == FBS_SAMPLE_NONE) wave_fill_trivial(dst, ln.fill, words, lane);
-        else wave_copy_ct(dst, ln.row + (size_t)from * words, words, lane);
+        if (none) wave_fill_trivial(dst, ln.msgs ? (uint64_t)ln.msgs[q] * a.delta % FQ : ln.body, words, lane);
+        else wave_copy_ct(dst, ln.row + from * words, words, lane);
+    }
+}
+
+__global__ __launch_bounds__(64 * ST_WAVES) void k_wire_store(WireCopy a) {
+    const uint32_t lane = threadIdx.x & 63u, words = a.D + 1;
+    const size_t total = a.n_links * a.tc;
+    for (size_t c = (size_t)blockIdx.x * ST_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * ST_WAVES) {   // wave-uniform
+        const size_t e = c / a.tc, q = c - e * a.tc;
+        const WireLink ln = a.links[e];
+        uint64_t *dst = ln.row + (a.s0 + q) * words;
+        if (ln.slot == WIRE_NO_SLOT) wave_fill_trivial(dst, ln.body, words, lane);
+        else wave_copy_ct(dst, a.wires + ((size_t)ln.slot * a.Tc + q) * words, words, lane);
     }
 }
 
@@ -147,54 +142,23 @@ __global__ __launch_bounds__(64 * ST_WAVES) void k_state_sum_groups(SumGroups a)
     }
 }
 
-// A pure streaming write: the wave stores 16 bytes a lane, aligned to the destination (wave_fill_trivial), and the body -- the only
-// non-zero word -- is computed once per ciphertext, wave-uniform.  m < 2p (checked by the host) and Delta <= q / 2p + 1, so
-// m Delta < q + 2p fits 64 bits and one 64-bit remainder is the residue fbs_eval's trivial_body computes.
-__global__ __launch_bounds__(64 * ST_WAVES) void k_fill_plain(PlainFill a) {
-    const uint32_t lane = threadIdx.x & 63u, words = a.D + 1;
-    const size_t total = a.n_links * a.tc;
-    for (size_t c = (size_t)blockIdx.x * ST_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * ST_WAVES) {   // wave-uniform
-        const size_t e = c / a.tc, q = c - e * a.tc;
-        const PlainLink ln = a.links[e];
-        const uint64_t m = (uint64_t)(ln.msgs ? ln.msgs[q] : ln.value);
-        wave_fill_trivial(a.wires + ((size_t)ln.slot * a.Tc + q) * words, m * a.delta % FQ, words, lane);
-    }
-}
-
 static dim3 st_grid(size_t total) { return dim3((unsigned)std::min<size_t>((total + ST_WAVES - 1) / ST_WAVES, ST_MAX_BLOCKS)); }
 
-int dev_state_gather(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream) {
+static int launch_links(const fbs_ctx *ctx, void (*kernel)(WireCopy), const WireCopy &a, hipStream_t stream) {
     if (a.n_links * a.tc == 0) return FBS_OK;
-    hipLaunchKernelGGL(k_state_gather, st_grid(a.n_links * a.tc), dim3(64 * ST_WAVES), 0, stream, a);
+    hipLaunchKernelGGL(kernel, st_grid(a.n_links * a.tc), dim3(64 * ST_WAVES), 0, stream, a);
     FBS_HIP(ctx, hipGetLastError());
     return FBS_OK;
 }
 
-int dev_state_scatter(const fbs_ctx *ctx, const StateCopy &a, hipStream_t stream) {
-    if (a.n_links * a.tc == 0) return FBS_OK;
-    hipLaunchKernelGGL(k_state_scatter, st_grid(a.n_links * a.tc), dim3(64 * ST_WAVES), 0, stream, a);
-    FBS_HIP(ctx, hipGetLastError());
-    return FBS_OK;
-}
+int dev_wire_load(const fbs_ctx *ctx, const WireCopy &a, hipStream_t stream) { return launch_links(ctx, k_wire_load, a, stream); }
 
-int dev_state_gather_mapped(const fbs_ctx *ctx, const MappedCopy &a, hipStream_t stream) {
-    if (a.n_links * a.tc == 0) return FBS_OK;
-    hipLaunchKernelGGL(k_state_gather_mapped, st_grid(a.n_links * a.tc), dim3(64 * ST_WAVES), 0, stream, a);
-    FBS_HIP(ctx, hipGetLastError());
-    return FBS_OK;
-}
+int dev_wire_store(const fbs_ctx *ctx, const WireCopy &a, hipStream_t stream) { return launch_links(ctx, k_wire_store, a, stream); }
 
 int dev_state_sum_groups(const fbs_ctx *ctx, const SumGroups &a, hipStream_t stream) {
     const size_t pairs = a.D / 2, slabs = std::max<size_t>(1, (pairs + SG_SLAB_PAIRS - 1) / SG_SLAB_PAIRS);
     if (a.rows * a.T_dst == 0) return FBS_OK;
     hipLaunchKernelGGL(k_state_sum_groups, st_grid(a.rows * a.T_dst * slabs), dim3(64 * ST_WAVES), 0, stream, a);
-    FBS_HIP(ctx, hipGetLastError());
-    return FBS_OK;
-}
-
-int dev_fill_plain(const fbs_ctx *ctx, const PlainFill &a, hipStream_t stream) {
-    if (a.n_links * a.tc == 0) return FBS_OK;
-    hipLaunchKernelGGL(k_fill_plain, st_grid(a.n_links * a.tc), dim3(64 * ST_WAVES), 0, stream, a);
     FBS_HIP(ctx, hipGetLastError());
     return FBS_OK;
 }

@@ -8,11 +8,11 @@ Wall-clock part (default), one JSON line each into <out-dir>/wall.jsonl:
     fetch of the single result: wall seconds and the bytes that go back to the client.  Against the route there was before: `run_compact` of all
     1000 results (server seconds, bytes), which the client decrypts and adds itself.
 (c) gather overhead: one resident adder8 hop at T = 1000 (a <- the state's s rows, b fresh), the state read through the identity
-    index (`state.samples(arange(T))`: k_state_gather_mapped) against the state read as it is (k_state_gather).
+    index (`state.samples(arange(T))`) against the state read as it is: k_wire_load either way, with and without an index word.
 
 Kernel part (`--kernels`, meant to run under `rocprofv3 --kernel-trace --stats -f csv`, a run of its own): the launches of (a), one
 unmapped and one identity-mapped adder8 hop over the same T = 4096 state, and into <out-dir>/kernels_run.jsonl the bytes each of
-the three state kernels read in that run.  `--stats <kernel_stats.csv>` then divides: <out-dir>/kernel_bandwidth.jsonl.
+the two state kernels read in that run (both kinds of hop load through k_wire_load: they are accounted for together).  `--stats <kernel_stats.csv>` then divides: <out-dir>/kernel_bandwidth.jsonl.
 
 `--table` prints the README's table from the three files.
 
@@ -148,8 +148,8 @@ def kernels_run(client, server, env, T=4096, group=8, launches=10):
         _hops(client, server, env, T, 1, state)      # two hops of each kind (one of them the warm-up)
     row = T * ctw * 8
     return [dict(bench="kernels_run", T=T, group=group, **_shape(client.params),
-                 bytes_read={"k_state_sum_groups": 2 * launches * 9 * row, "k_state_gather": 2 * 8 * row, "k_state_gather_mapped": 2 * 8 * row},
-                 bytes_written={"k_state_sum_groups": 2 * launches * 9 * row // group, "k_state_gather": 2 * 8 * row, "k_state_gather_mapped": 2 * 8 * row})]
+                 bytes_read={"k_state_sum_groups": 2 * launches * 9 * row, "k_wire_load": 4 * 8 * row},
+                 bytes_written={"k_state_sum_groups": 2 * launches * 9 * row // group, "k_wire_load": 4 * 8 * row})]
 
 
 def kernel_bandwidth(stats_csv, run_line):
