@@ -1,5 +1,5 @@
 /* The client library under AddressSanitizer and UBSan: a stand-alone C program that drives the SOURCES of libfbsclient.so
- * (csrc/fbs_error.cpp, fbs_host.cpp, fbs_client_capi.cpp, compiled with the sanitizers: make -C tests/c -f client.mk client_asan) through the C
+ * (csrc/fbs_error.cpp, fbs_host.cpp, fbs_client_entries.cpp, fbs_client_capi.cpp, compiled with the sanitizers: make -C tests/c -f client.mk client_asan) through the C
  * ABI of include/fbs_exec.h and nothing else.  Per parameter set -- one k = 1 set and one k = 2 set with two key bits per step --
  * it creates contexts in both seed forms, runs both key generations, exports everything into malloc buffers of EXACTLY the sizes the
  * size entries report (one word more read or written is a sanitizer report), encrypts and decrypts in every form, builds compact and

@@ -119,7 +119,7 @@ def test_no_exception_crosses_the_boundary():
         if text:
             assert text in lib.fbs_last_error(None).decode(), kind
     # and every entry point of the sources has the barrier: an `extern "C"` definition without `try` would be a hole
-    for src in ("fbs_capi.cpp", "fbs_eval.cpp", "fbs_mapper_search.hip"):
+    for src in ("fbs_capi.cpp", "fbs_eval.cpp", "fbs_client_entries.cpp", "fbs_mapper_search.hip"):
         text = open(os.path.join(ROOT, "tfhe_fbs_map_amd", "csrc", src)).read()
         body = text[text.index('extern "C" {'):]
         for m in re.finditer(r"^(?:int|void|double|const char \*) ?(fbs_\w+)\(([^{};]*?)\) (try )?\{", body, flags=re.M):

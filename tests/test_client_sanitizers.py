@@ -1,5 +1,5 @@
 """The client library's sources under AddressSanitizer and UBSan: tests/c/client_harness.c, a stand-alone C program, drives
-csrc/fbs_error.cpp, fbs_host.cpp and fbs_client_capi.cpp through the C ABI -- contexts in both seed forms, both key generations,
+csrc/fbs_error.cpp, fbs_host.cpp, fbs_client_entries.cpp and fbs_client_capi.cpp through the C ABI -- contexts in both seed forms, both key generations,
 every export into exactly-sized malloc buffers, every kind of encryption and decryption, the refusals.  Nothing is loaded into the
 interpreter under a sanitizer: the program is built and run as a process of its own."""
 import os
@@ -22,6 +22,6 @@ def test_harness_build_uses_the_sanitizers_and_no_gpu_toolchain():
     out = subprocess.run(["make", "-n", "-B", "-C", os.path.join(ROOT, "tests", "c"), "-f", "client.mk", "client_asan"], capture_output=True, text=True, check=True).stdout
     assert "-fsanitize=address,undefined" in out and "-fno-sanitize-recover=undefined" in out
     assert "hipcc" not in out and "rocm" not in out.lower() and "__HIP_PLATFORM_AMD__" not in out, out
-    for src in ("fbs_error.cpp", "fbs_host.cpp", "fbs_client_capi.cpp", "client_harness.c"):
+    for src in ("fbs_error.cpp", "fbs_host.cpp", "fbs_client_entries.cpp", "fbs_client_capi.cpp", "client_harness.c"):
         assert src in out, src
     assert "fbs_plan.cpp" not in out and "fbs_select.cpp" not in out

@@ -51,7 +51,7 @@ def test_public_target_uses_no_gpu_toolchain():
     out = subprocess.run(["make", "-n", "-B", "-C", CSRC, "public"], capture_output=True, text=True, check=True).stdout
     assert "fbs_public.cpp" in out and "libfbspublic.so" in out and "-DFBS_HOST_ONLY" in out and "-Wl,-Bsymbolic" in out
     assert "hipcc" not in out and "rocm" not in out.lower() and "__HIP_PLATFORM_AMD__" not in out, out
-    for src in ("fbs_plan.cpp", "fbs_select.cpp", "fbs_capi.cpp", "fbs_eval.cpp", "fbs_client_capi.cpp", ".hip"):
+    for src in ("fbs_plan.cpp", "fbs_select.cpp", "fbs_capi.cpp", "fbs_eval.cpp", "fbs_client_entries.cpp", "fbs_client_capi.cpp", ".hip"):
         assert src not in out, src
     everything = subprocess.run(["make", "-n", "-B", "-C", CSRC], capture_output=True, text=True, check=True).stdout
     assert "libfbspublic.so" in everything and "fbs_public.hip" in everything          # part of `all`, and the kernel is in NAMES

@@ -1,0 +1,87 @@
+"""Each entry of include/fbs_exec.h is written once.  libfbsexec.so and libfbsclient.so serve the client's entries from one text
+(csrc/fbs_client_entries.cpp), and `_native.Context` and `HostContext` wrap them with one set of methods (`ClientContext`), so that
+the two libraries say the same words, codes and texts by construction.  Only what differs on a machine with no device is written
+per library."""
+import glob
+import os
+import re
+
+import pytest
+
+from tests.test_capi_symbols import declared_symbols
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "tfhe_fbs_map_amd", "csrc")
+
+# what a library without a device does differently: one definition in fbs_capi.cpp, one in fbs_client_capi.cpp
+PER_LIBRARY = ["fbs_ctx_create", "fbs_ctx_stat", "fbs_ctx_destroy", "fbs_device_info", "fbs_keygen", "fbs_keygen_seeded",
+               "fbs_packing_keygen"]
+# the wrappers both bindings have: defined on the base, and nowhere else but for the GPU forms below
+SHARED_METHODS = ["__init__", "_check", "stat", "keygen", "export_keys", "keygen_seeded", "seeded_key_sizes", "export_seeded_keys",
+                  "encrypt", "decrypt", "encrypt_seeded", "expand_seeded", "default_compact_bits", "compact_words", "decrypt_compact",
+                  "packing_keygen", "packing_key_sizes", "export_packing_key", "packed_words", "decrypt_packed"]
+GPU_FORMS = {"__init__", "encrypt_seeded", "decrypt_compact"}   # the device part, the device=True branches
+
+
+def test_each_entry_is_written_once():
+    where = {}
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.cpp")) + glob.glob(os.path.join(CSRC, "*.hip"))):
+        for m in re.finditer(r"^(?:int|void|double|const char \*) ?(fbs_\w+)\(([^{};]*?)\) (try )?\{", open(path).read(), flags=re.M):
+            where.setdefault(m.group(1), []).append(os.path.basename(path))
+    declared = declared_symbols()
+    assert set(PER_LIBRARY) <= set(declared)
+    assert set(PER_LIBRARY) <= {"fbs_ctx_create", "fbs_ctx_create_seeded", "fbs_ctx_stat", "fbs_ctx_destroy", "fbs_device_info", "fbs_keygen",
+                                "fbs_keygen_seeded", "fbs_packing_keygen"}
+    for name in declared:
+        if name in PER_LIBRARY:
+            assert sorted(where.get(name, [])) == ["fbs_capi.cpp", "fbs_client_capi.cpp"], (name, where.get(name))
+        else:
+            assert len(where.get(name, [])) == 1, (name, where.get(name))
+    # and the shared text is in both libraries, and only there
+    makefile = open(os.path.join(CSRC, "Makefile")).read()
+    lists = {var: re.findall(r"^%s\s*:=(.*)$" % var, makefile, flags=re.M) for var in ("NAMES", "CLIENT_NAMES", "PUBLIC_NAMES")}
+    assert all(len(found) == 1 for found in lists.values()), lists
+    lists = {var: found[0].split() for var, found in lists.items()}
+    assert "fbs_client_entries.cpp" in lists["NAMES"] and "fbs_client_entries.cpp" in lists["CLIENT_NAMES"]
+    assert "fbs_client_entries.cpp" not in lists["PUBLIC_NAMES"]
+    assert "fbs_client_capi.cpp" not in lists["NAMES"] and "fbs_capi.cpp" not in lists["CLIENT_NAMES"]
+
+
+def test_no_library_exports_what_allocates_a_context():
+    """sizeof(fbs_ctx) is each library's own, and libfbsexec.so is not linked -Bsymbolic: were admit_params, params_admitted or
+    ctx_create in a dynamic symbol table, a process with two of the libraries could allocate a context with one and fill it with
+    the other"""
+    import subprocess
+    pkg = os.path.join(ROOT, "tfhe_fbs_map_amd")
+    subprocess.check_call(["make", "-s", "-C", CSRC, "client", "public"], timeout=600)
+    for lib in ("libfbsexec.so", "libfbsclient.so", "libfbspublic.so"):
+        names = subprocess.run(["nm", "-D", os.path.join(pkg, lib)], capture_output=True, text=True, check=True).stdout
+        assert names and not re.search(r"admit_params|params_admitted|3fbs10ctx_create", names), lib
+
+
+def test_both_bindings_wrap_the_client_entries_once():
+    from tfhe_fbs_map_amd import HostContext, _client_native, _native
+    from tfhe_fbs_map_amd._native import Context
+    base = _client_native.ClientContext
+    assert issubclass(Context, base) and issubclass(HostContext, base) and HostContext is _client_native.HostContext
+    assert Context.__mro__[1] is base and HostContext.__mro__[1] is base
+    for name in SHARED_METHODS:
+        assert name in base.__dict__, name
+        assert name not in HostContext.__dict__, name
+        assert (name in Context.__dict__) == (name in GPU_FORMS), name
+    # the one hook, and each closes its own handle (the GPU's with its states)
+    assert "_lib" in Context.__dict__ and "_lib" in HostContext.__dict__
+    assert "close" in Context.__dict__ and "close" in HostContext.__dict__
+    from tfhe_fbs_map_amd import Params
+    with pytest.raises(NotImplementedError):                            # the base alone names no library
+        base(Params(n=12, log_n_poly=8, p_msg=7, sigma_lwe=256, sigma_glwe=256), seed=1)
+    # one signature table: what the client library binds is what the GPU library binds under the same name
+    assert tuple(_client_native.SIGNATURES) == _client_native.EXPORTED_SYMBOLS and len(_client_native.SIGNATURES) == 27
+    for name, (res, args) in _client_native.SIGNATURES.items():
+        fn = getattr(_native.lib, name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name
+    src = open(os.path.join(ROOT, "tfhe_fbs_map_amd", "_native.py")).read()
+    load = src[src.index("def _load():"):src.index("EXPORTED_SYMBOLS = (")]
+    for name in _client_native.SIGNATURES:
+        assert '"%s"' % name not in load, name                          # not typed out a second time
+    assert "_client_native.SIGNATURES" in load

@@ -148,6 +148,40 @@ def gpu_library_missing(path):
             "(hipcc --offload-arch=gfx950).  tfhe_fbs_map_amd has no CPU fallback.")
 
 
+_vp, _u64, _u32, _sz, _i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_size_t, C.c_int
+# the client's entries: what libfbsclient.so exports, and libfbsexec.so beside its own
+SIGNATURES = {
+    "fbs_poly_size_check": (_i32, [_u32]),
+    "fbs_ctx_create": (_i32, [C.POINTER(_Params), _u64, _i32, C.POINTER(_vp)]),
+    "fbs_ctx_create_seeded": (_i32, [C.POINTER(_Params), _vp, _i32, C.POINTER(_vp)]),
+    "fbs_ctx_destroy": (None, [_vp]),
+    "fbs_ctx_stat": (_i32, [_vp, C.c_char_p, C.POINTER(C.c_int64)]),
+    "fbs_last_error": (C.c_char_p, [_vp]),
+    "fbs_device_info": (C.c_char_p, [_vp]),
+    "fbs_keygen": (_i32, [_vp]),
+    "fbs_key_sizes": (_i32, [_vp, C.POINTER(_sz * 4)]),
+    "fbs_export_keys": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "fbs_keygen_seeded": (_i32, [_vp]),
+    "fbs_seeded_key_sizes": (_i32, [_vp, C.POINTER(_sz * 2)]),
+    "fbs_export_seeded_keys": (_i32, [_vp, _vp, _vp, _vp]),
+    "fbs_encrypt": (_i32, [_vp, _vp, _sz, _u64, _vp]),
+    "fbs_encrypt_fresh": (_i32, [_vp, _vp, _sz, _vp, C.POINTER(_u64)]),
+    "fbs_decrypt": (_i32, [_vp, _vp, _sz, _vp]),
+    "fbs_encrypt_seeded": (_i32, [_vp, _vp, _sz, _u64, _vp]),
+    "fbs_encrypt_seeded_fresh": (_i32, [_vp, _vp, _sz, _vp, C.POINTER(_u64)]),
+    "fbs_expand_seeded": (_i32, [_vp, _vp, _sz, _u64, _vp]),
+    "fbs_compact_words": (_i32, [_vp, _u32, C.POINTER(_sz)]),
+    "fbs_decrypt_compact": (_i32, [_vp, _vp, _sz, _u32, _vp]),
+    "fbs_packing_keygen": (_i32, [_vp, _u32, _u32]),
+    "fbs_packing_key_sizes": (_i32, [_vp, _u32, C.POINTER(_sz * 2)]),
+    "fbs_export_packing_key": (_i32, [_vp, _vp, _vp]),
+    "fbs_packed_words": (_i32, [_vp, _sz, _u32, C.POINTER(_sz)]),
+    "fbs_decrypt_packed": (_i32, [_vp, _vp, _sz, _u32, _vp]),
+    "fbs_debug_raise": (_i32, [_vp, _i32]),
+}
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
+
+
 _lib_handle = None
 
 
@@ -159,50 +193,12 @@ def _lib():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} is missing: build it with `make -C tfhe_fbs_map_amd/csrc client` (a C++17 compiler is all it needs)")
     lib = C.CDLL(LIB_PATH)
-    vp, u64, u32, sz, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_size_t, C.c_int
-    for name, (res, args) in {
-        "fbs_poly_size_check": (i32, [u32]),
-        "fbs_ctx_create": (i32, [C.POINTER(_Params), u64, i32, C.POINTER(vp)]),
-        "fbs_ctx_create_seeded": (i32, [C.POINTER(_Params), vp, i32, C.POINTER(vp)]),
-        "fbs_ctx_destroy": (None, [vp]),
-        "fbs_ctx_stat": (i32, [vp, C.c_char_p, C.POINTER(C.c_int64)]),
-        "fbs_last_error": (C.c_char_p, [vp]),
-        "fbs_device_info": (C.c_char_p, [vp]),
-        "fbs_keygen": (i32, [vp]),
-        "fbs_key_sizes": (i32, [vp, C.POINTER(sz * 4)]),
-        "fbs_export_keys": (i32, [vp, vp, vp, vp, vp]),
-        "fbs_keygen_seeded": (i32, [vp]),
-        "fbs_seeded_key_sizes": (i32, [vp, C.POINTER(sz * 2)]),
-        "fbs_export_seeded_keys": (i32, [vp, vp, vp, vp]),
-        "fbs_encrypt": (i32, [vp, vp, sz, u64, vp]),
-        "fbs_encrypt_fresh": (i32, [vp, vp, sz, vp, C.POINTER(u64)]),
-        "fbs_decrypt": (i32, [vp, vp, sz, vp]),
-        "fbs_encrypt_seeded": (i32, [vp, vp, sz, u64, vp]),
-        "fbs_encrypt_seeded_fresh": (i32, [vp, vp, sz, vp, C.POINTER(u64)]),
-        "fbs_expand_seeded": (i32, [vp, vp, sz, u64, vp]),
-        "fbs_compact_words": (i32, [vp, u32, C.POINTER(sz)]),
-        "fbs_decrypt_compact": (i32, [vp, vp, sz, u32, vp]),
-        "fbs_packing_keygen": (i32, [vp, u32, u32]),
-        "fbs_packing_key_sizes": (i32, [vp, u32, C.POINTER(sz * 2)]),
-        "fbs_export_packing_key": (i32, [vp, vp, vp]),
-        "fbs_packed_words": (i32, [vp, sz, u32, C.POINTER(sz)]),
-        "fbs_decrypt_packed": (i32, [vp, vp, sz, u32, vp]),
-        "fbs_debug_raise": (i32, [vp, i32]),
-    }.items():
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError here = the library does not match the header
         fn.restype = res
         fn.argtypes = args
     _lib_handle = lib
     return lib
-
-
-EXPORTED_SYMBOLS = (
-    "fbs_poly_size_check", "fbs_ctx_create", "fbs_ctx_create_seeded", "fbs_ctx_destroy", "fbs_ctx_stat", "fbs_last_error",
-    "fbs_device_info", "fbs_keygen", "fbs_key_sizes", "fbs_export_keys", "fbs_keygen_seeded", "fbs_seeded_key_sizes",
-    "fbs_export_seeded_keys", "fbs_encrypt", "fbs_encrypt_fresh", "fbs_decrypt", "fbs_encrypt_seeded", "fbs_encrypt_seeded_fresh",
-    "fbs_expand_seeded", "fbs_compact_words", "fbs_decrypt_compact", "fbs_packing_keygen", "fbs_packing_key_sizes",
-    "fbs_export_packing_key", "fbs_packed_words", "fbs_decrypt_packed", "fbs_debug_raise",
-)
 
 
 def _any_lib():
@@ -236,69 +232,80 @@ def gpu_library_stand_in(name):
     return mod
 
 
-class HostContext:
-    """One parameter set, one key set, on the host: the client's subset of `_native.Context` (libfbsclient.so)."""
+class ClientContext:
+    """One parameter set, one key set, and what the holder of the secret does with them on host arrays: the entries of
+    `SIGNATURES`, written once for `HostContext` (libfbsclient.so) and `_native.Context` (libfbsexec.so, which adds the GPU's).
+    A subclass names its library (`_lib`) and closes its handle (`close`)."""
 
     def __init__(self, params: Params, seed: int | bytes | None = None, keygen: bool = False):
         """seed: as `Context` -- an int is the reproducible form (fbs_ctx_create), None or 32 bytes fbs_ctx_create_seeded (None:
         from os.urandom).  keygen=True: `keygen()` at once."""
-        lib = _lib()
+        self._create(params, seed, DEVICE_NONE)
+        if keygen:
+            self.keygen()
+
+    def _create(self, params, seed, device):
+        """the context handle, in the seed's form, on `device`"""
+        lib = self._lib
         self.params = params
         self.seed = seed
         self._h = C.c_void_p()
         cp = params.to_c()
         if isinstance(seed, int):
-            rc = lib.fbs_ctx_create(C.byref(cp), seed, DEVICE_NONE, C.byref(self._h))
+            rc = lib.fbs_ctx_create(C.byref(cp), seed, device, C.byref(self._h))
         else:
             raw = os.urandom(32) if seed is None else bytes(seed)
             if len(raw) != 32:
                 raise ValueError("a byte seed has 32 bytes")
-            rc = lib.fbs_ctx_create_seeded(C.byref(cp), raw, DEVICE_NONE, C.byref(self._h))
+            rc = lib.fbs_ctx_create_seeded(C.byref(cp), raw, device, C.byref(self._h))
         if rc != 0:
             self._h = None
             raise FbsError(rc, lib.fbs_last_error(None).decode())
-        if keygen:
-            self.keygen()
+
+    @property
+    def _lib(self):
+        """the loaded library that serves `SIGNATURES`"""
+        raise NotImplementedError("ClientContext is the shared part of HostContext and Context: make one of those")
+
+    def close(self):
+        """fbs_ctx_destroy through the subclass's library, once"""
+        raise NotImplementedError
 
     def _check(self, rc):
         if rc != 0:
-            raise FbsError(rc, _lib().fbs_last_error(self._h).decode())
-
-    def close(self):
-        if getattr(self, "_h", None) and _lib_handle is not None:      # (None while the interpreter shuts down)
-            _lib_handle.fbs_ctx_destroy(self._h)
-            self._h = None
+            raise FbsError(rc, self._lib.fbs_last_error(self._h).decode())
 
     def __del__(self):
-        self.close()
+        if getattr(self, "_h", None):
+            self.close()
 
     @property
     def device_info(self):
-        return _lib().fbs_device_info(self._h).decode()
+        return self._lib.fbs_device_info(self._h).decode()
 
     def stat(self, name):
         v = C.c_int64()
-        self._check(_lib().fbs_ctx_stat(self._h, name.encode(), C.byref(v)))
+        self._check(self._lib.fbs_ctx_stat(self._h, name.encode(), C.byref(v)))
         return v.value
 
     def keygen(self):
-        self._check(_lib().fbs_keygen(self._h))
+        self._check(self._lib.fbs_keygen(self._h))
 
     def export_keys(self):
         sizes = (C.c_size_t * 4)()
-        self._check(_lib().fbs_key_sizes(self._h, C.byref(sizes)))
+        self._check(self._lib.fbs_key_sizes(self._h, C.byref(sizes)))
         arrs = [np.empty(sizes[i], np.uint64) for i in range(4)]
-        self._check(_lib().fbs_export_keys(self._h, *[_ptr(a) for a in arrs]))
+        self._check(self._lib.fbs_export_keys(self._h, *[_ptr(a) for a in arrs]))
         return dict(sk_lwe=arrs[0], sk_glwe=arrs[1], bsk=arrs[2], ksk=arrs[3])
 
     # ---- seeded path: masks under a public key, only bodies travel (include/fbs_exec.h) ----
     def keygen_seeded(self):
         """fbs_keygen_seeded: keys whose masks a server regenerates from the public mask key (`export_seeded_keys`)."""
-        self._check(_lib().fbs_keygen_seeded(self._h))
+        self._check(self._lib.fbs_keygen_seeded(self._h))
 
     def seeded_key_sizes(self):
         sizes = (C.c_size_t * 2)()
-        self._check(_lib().fbs_seeded_key_sizes(self._h, C.byref(sizes)))
+        self._check(self._lib.fbs_seeded_key_sizes(self._h, C.byref(sizes)))
         return int(sizes[0]), int(sizes[1])
 
     def export_seeded_keys(self):
@@ -306,23 +313,24 @@ class HostContext:
         nb, nk = self.seeded_key_sizes()
         mk = np.zeros(32, np.uint8)
         bsk, ksk = np.empty(nb, np.uint64), np.empty(nk, np.uint64)
-        self._check(_lib().fbs_export_seeded_keys(self._h, _ptr(mk), _ptr(bsk), _ptr(ksk)))
+        self._check(self._lib.fbs_export_seeded_keys(self._h, _ptr(mk), _ptr(bsk), _ptr(ksk)))
         return dict(mask_key=mk.tobytes(), bsk_bodies=bsk, ksk_bodies=ksk)
 
     def encrypt(self, msgs, nonce0=None):
-        """nonce0=None: streams nobody has used (the context counts them); an int: ciphertext i takes stream nonce0 + i."""
+        """nonce0=None: streams nobody has used (the context counts them: no two calls share mask or noise); an int: ciphertext
+        i takes stream nonce0 + i -- reproducible, for tests and checkers."""
         msgs = _c(msgs, np.int64)
         cts = np.empty(msgs.shape + (self.params.ct_words,), np.uint64)
         if nonce0 is None:
-            self._check(_lib().fbs_encrypt_fresh(self._h, _ptr(msgs), msgs.size, _ptr(cts), None))
+            self._check(self._lib.fbs_encrypt_fresh(self._h, _ptr(msgs), msgs.size, _ptr(cts), None))
         else:
-            self._check(_lib().fbs_encrypt(self._h, _ptr(msgs), msgs.size, nonce0, _ptr(cts)))
+            self._check(self._lib.fbs_encrypt(self._h, _ptr(msgs), msgs.size, nonce0, _ptr(cts)))
         return cts
 
     def decrypt(self, cts):
         cts = _c(cts, np.uint64)
         out = np.empty(cts.shape[:-1], np.int64)
-        self._check(_lib().fbs_decrypt(self._h, _ptr(cts), out.size, _ptr(out)))
+        self._check(self._lib.fbs_decrypt(self._h, _ptr(cts), out.size, _ptr(out)))
         return out
 
     def encrypt_seeded(self, msgs, nonce0=None):
@@ -332,49 +340,56 @@ class HostContext:
         bodies = np.empty(msgs.shape, np.uint64)
         if nonce0 is None:
             first = C.c_uint64()
-            self._check(_lib().fbs_encrypt_seeded_fresh(self._h, _ptr(msgs), msgs.size, _ptr(bodies), C.byref(first)))
+            self._check(self._lib.fbs_encrypt_seeded_fresh(self._h, _ptr(msgs), msgs.size, _ptr(bodies), C.byref(first)))
             return bodies, first.value
-        self._check(_lib().fbs_encrypt_seeded(self._h, _ptr(msgs), msgs.size, int(nonce0), _ptr(bodies)))
+        self._check(self._lib.fbs_encrypt_seeded(self._h, _ptr(msgs), msgs.size, int(nonce0), _ptr(bodies)))
         return bodies, int(nonce0)
 
     def expand_seeded(self, bodies, nonce0):
-        """fbs_expand_seeded: bodies of streams nonce0, nonce0 + 1, .. -> full ciphertexts [..][D+1]"""
+        """fbs_expand_seeded (host): bodies of streams nonce0, nonce0 + 1, .. -> full ciphertexts [..][D+1]"""
         bodies = _c(bodies, np.uint64)
         cts = np.empty(bodies.shape + (self.params.ct_words,), np.uint64)
-        self._check(_lib().fbs_expand_seeded(self._h, _ptr(bodies), bodies.size, int(nonce0), _ptr(cts)))
+        self._check(self._lib.fbs_expand_seeded(self._h, _ptr(bodies), bodies.size, int(nonce0), _ptr(cts)))
         return cts
 
     # ---- compact outputs (include/fbs_exec.h) ----
     @property
     def default_compact_bits(self):
-        """log2(2N): the narrowest compact width"""
+        """log2(2N): the width the blind rotation reads, and the narrowest compact width"""
         return self.params.log_n_poly + 1
 
     def compact_words(self, bits=None):
+        """W, the uint64 words of one compact ciphertext at width `bits` (None: log2(2N)); FbsError(FBS_E_INVALID) outside
+        [log2(2N), 31]"""
         w = C.c_size_t()
-        self._check(_lib().fbs_compact_words(self._h, self.default_compact_bits if bits is None else int(bits), C.byref(w)))
+        self._check(self._lib.fbs_compact_words(self._h, self.default_compact_bits if bits is None else int(bits), C.byref(w)))
         return int(w.value)
 
-    def decrypt_compact(self, words, bits=None):
-        """Compact ciphertexts [..][W] -> messages [..] (fbs_decrypt_compact)"""
+    def _compact_io(self, words, bits):
+        """(the width, the words as uint64 [..][W], empty messages [..]) of a compact decryption; ValueError on another W"""
         bits = self.default_compact_bits if bits is None else int(bits)
         words = _c(words, np.uint64)
         W = words.shape[-1] if words.ndim else 0
         out = np.empty(words.shape[:-1], np.int64)
         if out.size and W != self.compact_words(bits):
             raise ValueError(f"compact ciphertexts of {W} words at {bits} bits (the parameter set needs {self.compact_words(bits)})")
-        self._check(_lib().fbs_decrypt_compact(self._h, _ptr(words), out.size, bits, _ptr(out)))
+        return bits, words, out
+
+    def decrypt_compact(self, words, bits=None):
+        """Compact ciphertexts [..][W] -> messages [..] (fbs_decrypt_compact, on the host)"""
+        bits, words, out = self._compact_io(words, bits)
+        self._check(self._lib.fbs_decrypt_compact(self._h, _ptr(words), out.size, bits, _ptr(out)))
         return out
 
     # ---- packed outputs (include/fbs_exec.h, "packed outputs") ----
     def packing_keygen(self, t_p, gamma_p):
         """fbs_packing_keygen: the packing key (t_p levels of gamma_p bits) beside the keys of `keygen_seeded`"""
-        self._check(_lib().fbs_packing_keygen(self._h, int(t_p), int(gamma_p)))
+        self._check(self._lib.fbs_packing_keygen(self._h, int(t_p), int(gamma_p)))
 
     def packing_key_sizes(self, t_p=0):
         """(bodies, whole key) in words for t_p levels (0: the context's own key)"""
         sizes = (C.c_size_t * 2)()
-        self._check(_lib().fbs_packing_key_sizes(self._h, int(t_p), C.byref(sizes)))
+        self._check(self._lib.fbs_packing_key_sizes(self._h, int(t_p), C.byref(sizes)))
         return int(sizes[0]), int(sizes[1])
 
     def export_packing_key(self, full=False):
@@ -383,7 +398,7 @@ class HostContext:
         nb, nf = self.packing_key_sizes()
         bodies = np.empty(nb, np.uint64)
         whole = np.empty(nf, np.uint64) if full else None
-        self._check(_lib().fbs_export_packing_key(self._h, _ptr(bodies), _ptr(whole)))
+        self._check(self._lib.fbs_export_packing_key(self._h, _ptr(bodies), _ptr(whole)))
         out = dict(packing_levels=self.stat("packing_levels"), packing_base_bits=self.stat("packing_base_bits"), packing_bodies=bodies)
         if full:
             prm = self.params
@@ -393,14 +408,27 @@ class HostContext:
     def packed_words(self, count, bits):
         """uint64 words of `count` outputs packed at width `bits` (fbs_packed_words)"""
         w = C.c_size_t()
-        self._check(_lib().fbs_packed_words(self._h, int(count), int(bits), C.byref(w)))
+        self._check(self._lib.fbs_packed_words(self._h, int(count), int(bits), C.byref(w)))
         return int(w.value)
 
     def decrypt_packed(self, words, count, bits):
-        """Packed words of `count` outputs -> messages [count] (fbs_decrypt_packed)"""
+        """Packed words of `count` outputs -> messages [count] (fbs_decrypt_packed, on the host)"""
         words = _c(words, np.uint64).ravel()
         if words.size != self.packed_words(count, bits):
             raise ValueError(f"{words.size} packed words for {count} outputs at {bits} bits (the parameter set needs {self.packed_words(count, bits)})")
         out = np.empty(int(count), np.int64)
-        self._check(_lib().fbs_decrypt_packed(self._h, _ptr(words), int(count), int(bits), _ptr(out)))
+        self._check(self._lib.fbs_decrypt_packed(self._h, _ptr(words), int(count), int(bits), _ptr(out)))
         return out
+
+
+class HostContext(ClientContext):
+    """One parameter set, one key set, on the host: the client's subset of `_native.Context` (libfbsclient.so)."""
+
+    @property
+    def _lib(self):
+        return _lib()
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib_handle is not None:      # (None while the interpreter shuts down)
+            _lib_handle.fbs_ctx_destroy(self._h)
+            self._h = None

@@ -18,8 +18,8 @@ LIB_PATH = os.environ.get("FBS_LIB") or os.path.join(_HERE, "libfbsexec.so")   #
 
 from .security import MODULUS, MODULUS_BITS, sigma_min      # noqa: E402,F401
 # what a client shares with this module lives in `_client_native`, which needs neither this library nor a GPU
-from . import _public_native      # noqa: E402
-from ._client_native import GAUSSIAN_SAMPLER_GRADE, RANDOMNESS_GRADE, SAMPLERS, FbsError, Params, _Params, _c, _ptr, gpu_library_missing      # noqa: E402,F401
+from . import _client_native, _public_native      # noqa: E402
+from ._client_native import GAUSSIAN_SAMPLER_GRADE, RANDOMNESS_GRADE, SAMPLERS, ClientContext, FbsError, Params, _Params, _c, _ptr, gpu_library_missing      # noqa: E402,F401
 
 
 class _Layout(C.Structure):
@@ -98,53 +98,28 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     vp, u64, u32, sz, i32 = C.c_void_p, C.c_uint64, C.c_uint32, C.c_size_t, C.c_int
     sig = dict(_public_native.SIGNATURES)   # the host entries of "public-key inputs": the same code as libfbspublic.so's
+    sig.update(_client_native.SIGNATURES)   # the client's entries: the same code as libfbsclient.so's, or this library's form of it
     sig.update({
-        "fbs_poly_size_check": (i32, [u32]),
-        "fbs_ctx_create": (i32, [C.POINTER(_Params), u64, i32, C.POINTER(vp)]),
-        "fbs_ctx_create_seeded": (i32, [C.POINTER(_Params), vp, i32, C.POINTER(vp)]),
-        "fbs_ctx_destroy": (None, [vp]),
         "fbs_ctx_reserve": (i32, [vp, sz, sz, sz]),
         "fbs_ctx_tune": (i32, [vp, C.c_char_p, C.c_int64]),
-        "fbs_ctx_stat": (i32, [vp, C.c_char_p, C.POINTER(C.c_int64)]),
-        "fbs_last_error": (C.c_char_p, [vp]),
-        "fbs_device_info": (C.c_char_p, [vp]),
-        "fbs_keygen": (i32, [vp]),
-        "fbs_key_sizes": (i32, [vp, C.POINTER(sz * 4)]),
-        "fbs_export_keys": (i32, [vp, vp, vp, vp, vp]),
         "fbs_import_keys": (i32, [vp, vp, vp, vp, vp]),
-        "fbs_encrypt": (i32, [vp, vp, sz, u64, vp]),
-        "fbs_encrypt_fresh": (i32, [vp, vp, sz, vp, C.POINTER(u64)]),
-        "fbs_decrypt": (i32, [vp, vp, sz, vp]),
         "fbs_encrypt_dev": (i32, [vp, vp, sz, u64, vp, vp]),
         "fbs_encrypt_fresh_dev": (i32, [vp, vp, sz, vp, C.POINTER(u64), vp]),
         "fbs_decrypt_dev": (i32, [vp, vp, sz, vp, vp]),
-        "fbs_keygen_seeded": (i32, [vp]),
-        "fbs_seeded_key_sizes": (i32, [vp, C.POINTER(sz * 2)]),
-        "fbs_export_seeded_keys": (i32, [vp, vp, vp, vp]),
         "fbs_import_seeded_keys": (i32, [vp, vp, vp, vp]),
-        "fbs_encrypt_seeded": (i32, [vp, vp, sz, u64, vp]),
-        "fbs_encrypt_seeded_fresh": (i32, [vp, vp, sz, vp, C.POINTER(u64)]),
         "fbs_encrypt_seeded_dev": (i32, [vp, vp, sz, u64, vp, vp]),
         "fbs_encrypt_seeded_fresh_dev": (i32, [vp, vp, sz, vp, C.POINTER(u64), vp]),
-        "fbs_expand_seeded": (i32, [vp, vp, sz, u64, vp]),
         "fbs_expand_seeded_dev": (i32, [vp, vp, sz, u64, vp, vp]),
         "fbs_eval_seeded": (i32, [vp, vp, vp, sz, u64, vp]),
-        "fbs_compact_words": (i32, [vp, u32, C.POINTER(sz)]),
         "fbs_compact_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_eval_seeded_compact": (i32, [vp, vp, vp, sz, u64, u32, vp]),
-        "fbs_decrypt_compact": (i32, [vp, vp, sz, u32, vp]),
         "fbs_decrypt_compact_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_compact_fields_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_refresh_compact_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_eval_sources": (i32, [vp, vp, vp, sz, u32, vp]),
-        "fbs_packing_keygen": (i32, [vp, u32, u32]),
-        "fbs_packing_key_sizes": (i32, [vp, u32, C.POINTER(sz * 2)]),
-        "fbs_export_packing_key": (i32, [vp, vp, vp]),
         "fbs_import_packing_key": (i32, [vp, u32, u32, vp]),
-        "fbs_packed_words": (i32, [vp, sz, u32, C.POINTER(sz)]),
         "fbs_pack_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_state_fetch_packed": (i32, [vp, vp, sz, sz, u32, vp]),
-        "fbs_decrypt_packed": (i32, [vp, vp, sz, u32, vp]),
         "fbs_state_create": (i32, [vp, sz, sz, C.POINTER(vp)]),
         "fbs_state_destroy": (None, [vp]),
         "fbs_state_info": (i32, [vp, C.POINTER(sz), C.POINTER(sz)]),
@@ -184,7 +159,6 @@ def _load():
         "fbs_profile_kernels": (i32, [vp, vp, sz, C.POINTER(sz)]),
         "fbs_sync": (i32, [vp, vp]),
         "fbs_debug_polymul": (i32, [vp, vp, vp, vp]),
-        "fbs_debug_raise": (i32, [vp, i32]),
         "fbs_debug_field": (i32, [vp, i32, vp, vp, sz, vp]),
         "fbs_debug_gauss": (i32, [vp, vp, sz, u64, vp]),
         "fbs_debug_gauss_dev": (i32, [vp, vp, sz, u64, vp, vp]),
@@ -561,8 +535,10 @@ def debug_gauss(words, sigma):
     return out
 
 
-class Context:
-    """One GPU, one parameter set, one key set."""
+class Context(ClientContext):
+    """One GPU, one parameter set, one key set.  What the holder of the secret does on host arrays is `ClientContext`'s, the same
+    wrappers `HostContext` has; here is what needs the GPU."""
+    _lib = property(lambda self: lib)
 
     def __init__(self, params: Params, seed: int | bytes | None = None, device: int = 0, keygen: bool = True,
                  device_keys: bool = False):
@@ -577,30 +553,13 @@ class Context:
         `import_keys`).
         device_keys=True: the evaluation keys are made -- and a server key is expanded -- on the GPU (knob "keys_on_device",
         include/fbs_exec.h) instead of on the host and uploaded; the same words either way (`stat("keys_made_on_device")`)."""
-        self.params = params
-        self.seed = seed
         self.device = device
         self._states = weakref.WeakSet()   # its DeviceStates: closed with it
-        self._h = C.c_void_p()
-        cp = params.to_c()
-        if isinstance(seed, int):
-            rc = lib.fbs_ctx_create(C.byref(cp), seed, device, C.byref(self._h))
-        else:
-            raw = os.urandom(32) if seed is None else bytes(seed)
-            if len(raw) != 32:
-                raise ValueError("a byte seed has 32 bytes")
-            rc = lib.fbs_ctx_create_seeded(C.byref(cp), raw, device, C.byref(self._h))
-        if rc != 0:
-            self._h = None
-            raise FbsError(rc, lib.fbs_last_error(None).decode())
+        self._create(params, seed, device)
         if device_keys:
             self.tune(keys_on_device=1)
         if keygen:
             self.keygen()
-
-    def _check(self, rc):
-        if rc != 0:
-            raise FbsError(rc, lib.fbs_last_error(self._h).decode())
 
     def close(self):
         if getattr(self, "_h", None) and lib is not None:      # `lib` is None while the interpreter shuts down
@@ -608,23 +567,6 @@ class Context:
                 st._h = None
             lib.fbs_ctx_destroy(self._h)
             self._h = None
-
-    def __del__(self):
-        self.close()
-
-    @property
-    def device_info(self):
-        return lib.fbs_device_info(self._h).decode()
-
-    def keygen(self):
-        self._check(lib.fbs_keygen(self._h))
-
-    def export_keys(self):
-        sizes = (C.c_size_t * 4)()
-        self._check(lib.fbs_key_sizes(self._h, C.byref(sizes)))
-        arrs = [np.empty(sizes[i], np.uint64) for i in range(4)]
-        self._check(lib.fbs_export_keys(self._h, *[_ptr(a) for a in arrs]))
-        return dict(sk_lwe=arrs[0], sk_glwe=arrs[1], bsk=arrs[2], ksk=arrs[3])
 
     def import_keys(self, sk_lwe, sk_glwe, bsk, ksk):
         """Keys made elsewhere (layout of `export_keys`) instead of `keygen`: a caller's own CSPRNG and sampler, or a checker's."""
@@ -637,23 +579,6 @@ class Context:
         self._check(lib.fbs_import_keys(self._h, *[_ptr(a) for a in arrs]))
 
     # ---- seeded path: masks under a public key, only bodies travel (include/fbs_exec.h) ----
-    def keygen_seeded(self):
-        """fbs_keygen_seeded: keys whose masks a server regenerates from the public mask key (`export_seeded_keys`)."""
-        self._check(lib.fbs_keygen_seeded(self._h))
-
-    def seeded_key_sizes(self):
-        sizes = (C.c_size_t * 2)()
-        self._check(lib.fbs_seeded_key_sizes(self._h, C.byref(sizes)))
-        return int(sizes[0]), int(sizes[1])
-
-    def export_seeded_keys(self):
-        """The server key: dict(mask_key=32 bytes, bsk_bodies, ksk_bodies).  Holds no secret."""
-        nb, nk = self.seeded_key_sizes()
-        mk = np.zeros(32, np.uint8)
-        bsk, ksk = np.empty(nb, np.uint64), np.empty(nk, np.uint64)
-        self._check(lib.fbs_export_seeded_keys(self._h, _ptr(mk), _ptr(bsk), _ptr(ksk)))
-        return dict(mask_key=mk.tobytes(), bsk_bodies=bsk, ksk_bodies=ksk)
-
     def import_seeded_keys(self, mask_key, bsk_bodies, ksk_bodies):
         """fbs_import_seeded_keys: expands the server key and leaves the context evaluation-only."""
         mk = np.frombuffer(bytes(mask_key), np.uint8).copy()
@@ -678,15 +603,9 @@ class Context:
         """Seeded encryption: (bodies with the shape of msgs, first stream).  Ciphertext i takes stream nonce0 + i; None = streams
         nobody has used (the counter of `encrypt`).  device=True (default): on the GPU (fbs_encrypt_seeded_dev), False: on the
         host -- the same words."""
-        msgs = _c(msgs, np.int64)
         if not device:
-            bodies = np.empty(msgs.shape, np.uint64)
-            if nonce0 is None:
-                first = C.c_uint64()
-                self._check(lib.fbs_encrypt_seeded_fresh(self._h, _ptr(msgs), msgs.size, _ptr(bodies), C.byref(first)))
-                return bodies, first.value
-            self._check(lib.fbs_encrypt_seeded(self._h, _ptr(msgs), msgs.size, int(nonce0), _ptr(bodies)))
-            return bodies, int(nonce0)
+            return super().encrypt_seeded(msgs, nonce0)
+        msgs = _c(msgs, np.int64)
         import torch
         d_m = torch.from_numpy(msgs.reshape(-1)).to("cuda:%d" % self.device)
         d_b = torch.empty(max(1, msgs.size), dtype=torch.int64, device=d_m.device)
@@ -704,13 +623,6 @@ class Context:
             return first.value
         self._check(lib.fbs_encrypt_seeded_dev(self._h, d_msgs or None, count, int(nonce0), d_bodies or None, stream or None))
         return int(nonce0)
-
-    def expand_seeded(self, bodies, nonce0):
-        """fbs_expand_seeded (host): bodies of streams nonce0, nonce0 + 1, .. -> full ciphertexts [..][D+1]"""
-        bodies = _c(bodies, np.uint64)
-        cts = np.empty(bodies.shape + (self.params.ct_words,), np.uint64)
-        self._check(lib.fbs_expand_seeded(self._h, _ptr(bodies), bodies.size, int(nonce0), _ptr(cts)))
-        return cts
 
     def expand_seeded_dev(self, d_bodies, count, nonce0, d_cts, stream=0):
         self._check(lib.fbs_expand_seeded_dev(self._h, d_bodies or None, count, int(nonce0), d_cts or None, stream or None))
@@ -739,28 +651,6 @@ class Context:
         for k, v in knobs.items():
             self._check(lib.fbs_ctx_tune(self._h, k.encode(), int(v)))
 
-    def stat(self, name):
-        v = C.c_int64()
-        self._check(lib.fbs_ctx_stat(self._h, name.encode(), C.byref(v)))
-        return v.value
-
-    def encrypt(self, msgs, nonce0=None):
-        """nonce0=None: streams nobody has used (the context counts them: no two calls share mask or noise); an int: ciphertext
-        i takes stream nonce0 + i -- reproducible, for tests and checkers."""
-        msgs = _c(msgs, np.int64)
-        cts = np.empty(msgs.shape + (self.params.ct_words,), np.uint64)
-        if nonce0 is None:
-            self._check(lib.fbs_encrypt_fresh(self._h, _ptr(msgs), msgs.size, _ptr(cts), None))
-        else:
-            self._check(lib.fbs_encrypt(self._h, _ptr(msgs), msgs.size, nonce0, _ptr(cts)))
-        return cts
-
-    def decrypt(self, cts):
-        cts = _c(cts, np.uint64)
-        out = np.empty(cts.shape[:-1], np.int64)
-        self._check(lib.fbs_decrypt(self._h, _ptr(cts), out.size, _ptr(out)))
-        return out
-
     def tvset(self, tables):
         return TvSet(self, tables)
 
@@ -769,18 +659,6 @@ class Context:
         return DeviceState(self, rows, T)
 
     # ---- compact outputs: key-switched to the small key, rounded to `bits` bits a field, bit-packed (include/fbs_exec.h) ----
-    @property
-    def default_compact_bits(self):
-        """log2(2N): the width the blind rotation reads, and the narrowest compact width"""
-        return self.params.log_n_poly + 1
-
-    def compact_words(self, bits=None):
-        """W, the uint64 words of one compact ciphertext at width `bits` (None: log2(2N)); FbsError(FBS_E_INVALID) outside
-        [log2(2N), 31]"""
-        w = C.c_size_t()
-        self._check(lib.fbs_compact_words(self._h, self.default_compact_bits if bits is None else int(bits), C.byref(w)))
-        return int(w.value)
-
     def compact_dev(self, d_cts, count, d_words, bits=None, stream=0):
         """fbs_compact_dev: `count` big-key ciphertexts at d_cts -> [count][W] words at d_words, asynchronous on `stream`; needs
         no secret"""
@@ -790,15 +668,9 @@ class Context:
     def decrypt_compact(self, words, bits=None, device=True):
         """Compact ciphertexts [..][W] -> messages [..].  device=True: on the GPU (fbs_decrypt_compact_dev), False: on the host
         (fbs_decrypt_compact) -- the same messages."""
-        bits = self.default_compact_bits if bits is None else int(bits)
-        words = _c(words, np.uint64)
-        W = words.shape[-1] if words.ndim else 0
-        out = np.empty(words.shape[:-1], np.int64)
-        if out.size and W != self.compact_words(bits):
-            raise ValueError(f"compact ciphertexts of {W} words at {bits} bits (the parameter set needs {self.compact_words(bits)})")
         if not device:
-            self._check(lib.fbs_decrypt_compact(self._h, _ptr(words), out.size, bits, _ptr(out)))
-            return out
+            return super().decrypt_compact(words, bits)
+        bits, words, out = self._compact_io(words, bits)
         import torch
         d_w = torch.from_numpy(words.reshape(-1).view(np.int64)).to("cuda:%d" % self.device) if words.size else None
         d_m = torch.empty(max(1, out.size), dtype=torch.int64, device="cuda:%d" % self.device)
@@ -825,41 +697,12 @@ class Context:
                                                 d_msgs or None, stream or None))
 
     # ---- packed outputs: up to N outputs in one GLWE sample under the big key (include/fbs_exec.h, "packed outputs") ----
-    def packing_keygen(self, t_p, gamma_p):
-        """fbs_packing_keygen: the packing key (t_p levels of gamma_p bits) beside the keys of `keygen_seeded`"""
-        self._check(lib.fbs_packing_keygen(self._h, int(t_p), int(gamma_p)))
-
-    def packing_key_sizes(self, t_p=0):
-        """(bodies, whole key) in words for t_p levels (0: the context's own key)"""
-        sizes = (C.c_size_t * 2)()
-        self._check(lib.fbs_packing_key_sizes(self._h, int(t_p), C.byref(sizes)))
-        return int(sizes[0]), int(sizes[1])
-
-    def export_packing_key(self, full=False):
-        """dict(packing_levels, packing_base_bits, packing_bodies [n][t_p][N]); full=True adds `full`, the whole key
-        [n][t_p][k+1][N] in the coefficient domain (a test hook)"""
-        nb, nf = self.packing_key_sizes()
-        bodies = np.empty(nb, np.uint64)
-        whole = np.empty(nf, np.uint64) if full else None
-        self._check(lib.fbs_export_packing_key(self._h, _ptr(bodies), _ptr(whole)))
-        out = dict(packing_levels=self.stat("packing_levels"), packing_base_bits=self.stat("packing_base_bits"), packing_bodies=bodies)
-        if full:
-            prm = self.params
-            out["full"] = whole.reshape(prm.n, out["packing_levels"], prm.k + 1, prm.N)
-        return out
-
     def import_packing_key(self, t_p, gamma_p, bodies):
         """fbs_import_packing_key: the masks come from the context's mask key; works on evaluation-only contexts"""
         bodies = _c(bodies, np.uint64).ravel()
         if 1 <= int(t_p) <= 31 and bodies.size != self.packing_key_sizes(t_p)[0]:
             raise ValueError(f"packing_bodies has {bodies.size} words, the parameter set needs {self.packing_key_sizes(t_p)[0]}")
         self._check(lib.fbs_import_packing_key(self._h, int(t_p), int(gamma_p), _ptr(bodies)))
-
-    def packed_words(self, count, bits):
-        """uint64 words of `count` outputs packed at width `bits` (fbs_packed_words)"""
-        w = C.c_size_t()
-        self._check(lib.fbs_packed_words(self._h, int(count), int(bits), C.byref(w)))
-        return int(w.value)
 
     def pack_dev(self, d_cts, count, d_words, bits, stream=0):
         """fbs_pack_dev: `count` big-key ciphertexts at d_cts -> packed words at d_words, asynchronous on `stream`; no secret"""
@@ -876,15 +719,6 @@ class Context:
         self.pack_dev(d_c.data_ptr(), count, d_w.data_ptr(), bits)
         self.sync()
         return d_w[:self.packed_words(count, bits)].cpu().numpy().view(np.uint64)
-
-    def decrypt_packed(self, words, count, bits):
-        """Packed words of `count` outputs -> messages [count] (fbs_decrypt_packed, on the host)"""
-        words = _c(words, np.uint64).ravel()
-        if words.size != self.packed_words(count, bits):
-            raise ValueError(f"{words.size} packed words for {count} outputs at {bits} bits (the parameter set needs {self.packed_words(count, bits)})")
-        out = np.empty(int(count), np.int64)
-        self._check(lib.fbs_decrypt_packed(self._h, _ptr(words), int(count), int(bits), _ptr(out)))
-        return out
 
     def bootstrap_batch(self, tvset, cts, table_ids=None):
         cts = _c(cts, np.uint64)

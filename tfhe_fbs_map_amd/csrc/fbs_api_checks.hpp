@@ -1,9 +1,11 @@
 // What the entries of include/fbs_exec.h that run on the host check before they do anything -- buffers, keys, the secret, the
 // stream ranges, word counts that must not overflow, the fresh-stream counter, the widths of compact and packed outputs, the
-// packing key's parameters -- in one place, because two libraries serve those entries: libfbsexec.so (fbs_capi.cpp) and the
-// client library libfbsclient.so (fbs_client_capi.cpp).  The same checks in the same order give the same codes and texts, and a
-// refused call moves no counter in either.  The public-key entries (fbs_public.cpp: libfbsexec.so and libfbspublic.so) take their
-// parameter admission from here.  Host code, no device in it.
+// packing key's parameters -- in one place, because two libraries serve those entries: libfbsexec.so and the client library
+// libfbsclient.so.  The entries that never turn to a device are one text compiled into both (fbs_client_entries.cpp); those that
+// differ -- contexts, key generation -- are fbs_capi.cpp's and fbs_client_capi.cpp's, and what the two share of them (parameter
+// admission, the common statistics, the state changes of a key generation) is here as well.  The same checks in the same order
+// give the same codes and texts, and a refused call moves no counter in either.  The public-key entries (fbs_public.cpp:
+// libfbsexec.so and libfbspublic.so) take their parameter admission from here.  Host code, no device in it.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -19,18 +21,53 @@ namespace fbs {
 // what every entry that needs the secret keys says on a context made by fbs_import_seeded_keys
 constexpr const char *EVAL_ONLY = "this context holds evaluation keys only";
 
-// Parameter admission for the entries that take a parameter set and no context (fbs_pub_*): what fbs_ctx_create applies -- the range
-// rules of host_ctx_init, then whether a kernel is built for the set -- with its codes and texts, left as the thread's creation
-// error.  *probe: the host state of a context for the set (N, D, Delta), the caller's to delete.
-inline int params_admitted(const fbs_params *params, fbs_ctx **probe) {
+// Parameter admission, what fbs_ctx_create applies in either library: the range rules of host_ctx_init (everything that is
+// arithmetic on the set: derived sizes, Delta, gadget factors, the random key from `seed` or `seed32`), then whether a kernel is
+// built for the set -- keys for a set no server can evaluate are of no use -- with the codes and texts left as the thread's
+// creation error.  *out: a context for the set with its host state filled in, the caller's to delete.
+// static: it allocates an fbs_ctx, whose size is the library's own (the host state alone under FBS_HOST_ONLY, the device side too
+// in libfbsexec.so).  An exported inline copy could be taken from another library loaded into the same process -- libfbsexec.so
+// is not linked -Bsymbolic -- and hand the GPU library a context too small for what it writes.  No library exports these two.
+static inline int admit_params(const fbs_params *params, uint64_t seed, const uint8_t *seed32, fbs_ctx **out) {
     if (!params) return set_error(nullptr, FBS_E_INVALID, "null argument");
     std::unique_ptr<fbs_ctx> ctx(new fbs_ctx);
-    int rc = host_ctx_init(ctx.get(), params, 0, nullptr);
+    int rc = host_ctx_init(ctx.get(), params, seed, seed32);
     if (rc == FBS_OK)
         if (const char *why = kernel_not_built(ctx->p)) rc = set_error(ctx.get(), FBS_E_INVALID, why);
     if (rc != FBS_OK) return set_error(nullptr, rc, ctx->err);
-    *probe = ctx.release();
+    *out = ctx.release();
     return FBS_OK;
+}
+// ... for the entries that take a parameter set and no context (fbs_pub_*): *probe tells them N, D and Delta
+static inline int params_admitted(const fbs_params *params, fbs_ctx **probe) { return admit_params(params, 0, nullptr, probe); }
+
+// fbs_ctx_create and fbs_ctx_create_seeded (fbs_client_entries.cpp) of a library end here: admit_params, then that library's rule
+// for `device`.  Each library has its own (fbs_capi.cpp, fbs_client_capi.cpp; libfbspublic.so has none and calls none); hidden,
+// so that a process that has loaded both never takes one library's for the other's.  Declared here, once, so that the two
+// definitions and the caller are checked against one signature.
+__attribute__((visibility("hidden"))) int ctx_create(const fbs_params *params, uint64_t seed, const uint8_t *seed32, int device, fbs_ctx **out);
+
+// The statistics of fbs_ctx_stat that both libraries answer; false: not one of them (the GPU library goes on to its own)
+inline bool host_stat(const fbs_ctx *ctx, const std::string &k, int64_t *value) {
+    if (k == "next_nonce") *value = (int64_t)ctx->next_nonce.load();
+    else if (k == "has_secret") *value = ctx->have_keys && !ctx->eval_only;
+    else if (k == "seeded_keys") *value = ctx->have_keys && ctx->seeded_keys;
+    else if (k == "packing_key") *value = ctx->have_pack;
+    else if (k == "packing_levels") *value = ctx->have_pack ? ctx->pack_t : 0;
+    else if (k == "packing_base_bits") *value = ctx->have_pack ? ctx->pack_gamma : 0;
+    else return false;
+    return true;
+}
+
+// What a call that replaces the keys of a context does to its state: which kind the new keys are, as soon as the host has them;
+// and, once they are in place (in the GPU library: on the device), that there are keys -- and no packing key any more
+inline void keys_replaced(fbs_ctx *ctx, bool seeded, bool eval_only) {
+    ctx->seeded_keys = seeded;
+    ctx->eval_only = eval_only;
+}
+inline void keys_in_place(fbs_ctx *ctx) {
+    ctx->have_keys = true;
+    ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
 }
 
 // Streams [first, first + count) of [2^55, 2^56) that nobody has used, for every entry that takes fresh streams.  The range is
@@ -90,6 +127,14 @@ inline int check_packing_params(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma
     if (const char *why = packing_params_refused(t_p, gamma_p)) return set_error(ctx, FBS_E_INVALID, why);
     if (!pack_shape_built(ctx->p.log_n_poly, ctx->p.k)) return set_error(ctx, FBS_E_INVALID, "no packing kernel for this (k, N)");
     return FBS_OK;
+}
+// what fbs_packing_keygen checks before it draws anything: the states in this order, then the parameters
+inline int check_packing_keygen(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) {
+    if (!ctx) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "a packing key goes with seeded keys (fbs_keygen_seeded)");
+    return check_packing_params(ctx, t_p, gamma_p);
 }
 inline int check_packed_words(const fbs_ctx *ctx, size_t count, uint32_t bits) {
     if (count / ctx->N + 1 > SIZE_MAX / 8 / packed_sample_words(ctx->p.k, ctx->N, ctx->N, bits))

@@ -178,35 +178,14 @@ bool state_of(const fbs_ctx *ctx, const fbs_state *st) {   // (by address: a for
     return st && std::find(ctx->states.begin(), ctx->states.end(), st) != ctx->states.end();
 }
 
-}   // namespace fbs
-
-extern "C" {
-
-// ---------------------------------------------------------------------------------------------
-int fbs_poly_size_check(uint32_t poly_size) try {
-    if (poly_size == 0) return set_error(nullptr, FBS_E_INVALID, "polynomial size 0");
-    if (poly_size & (poly_size - 1)) {
-        uint32_t pow2 = poly_size & (~poly_size + 1);   // largest power of two dividing N
-        return set_error(nullptr, FBS_E_POLY_SIZE,
-                         "N = " + std::to_string(poly_size) + " is not a power of two: X^N + 1 then has the factor X^" +
-                             std::to_string(pow2) + " + 1, so a GLWE sample over it is no harder than one of degree " +
-                             std::to_string(pow2) + "; use a power-of-two N (256 .. 4096) and any plaintext modulus p");
-    }
-    if (poly_size < 256 || poly_size > 4096)
-        return set_error(nullptr, FBS_E_INVALID, "supported polynomial sizes are N = 256, 512, 1024, 2048, 4096");
-    return FBS_OK;
-} FBS_API_CATCH(nullptr)
-
-static int ctx_create(const fbs_params *params, uint64_t seed, const uint8_t *seed32, int device, fbs_ctx **out) {
+// Parameter admission is host code with no device in it (admit_params: host_ctx_init of fbs_host.cpp, kernel_not_built of
+// fbs_select.hpp; the sanitizer harnesses of tests/c/ run those two).  Then the device.
+int ctx_create(const fbs_params *params, uint64_t seed, const uint8_t *seed32, int device, fbs_ctx **out) {
     if (!params || !out) return set_error(nullptr, FBS_E_INVALID, "null argument");
     *out = nullptr;
-    std::unique_ptr<fbs_ctx> ctx(new fbs_ctx);
-    // everything that is arithmetic on the parameter set (ranges, derived sizes, Delta, gadget factors, the random key): host code
-    // with no device in it (fbs_host.cpp), then whether a kernel is built for the set (fbs_select.cpp): the sanitizer harness of
-    // tests/c/ runs the same functions
-    int rc = host_ctx_init(ctx.get(), params, seed, seed32);
-    if (rc == FBS_OK) rc = check_kernel_built(ctx.get());
-    if (rc != FBS_OK) return set_error(nullptr, rc, ctx->err);
+    fbs_ctx *admitted = nullptr;
+    if (int rc = admit_params(params, seed, seed32, &admitted)) return rc;
+    std::unique_ptr<fbs_ctx> ctx(admitted);
     ctx->device = device;
 
     int n_dev = 0;
@@ -236,13 +215,15 @@ static int ctx_create(const fbs_params *params, uint64_t seed, const uint8_t *se
     return FBS_OK;
 }
 
+}   // namespace fbs
+
+// The entries that never turn to the device (sizes, exports, host encryption and decryption, the decoders, fbs_last_error) are
+// fbs_client_entries.cpp, one text for this library and the client library.
+extern "C" {
+
+// ---------------------------------------------------------------------------------------------
 int fbs_ctx_create(const fbs_params *params, uint64_t seed, int device, fbs_ctx **out) try {
     return ctx_create(params, seed, nullptr, device, out);
-} FBS_API_CATCH(nullptr)
-
-int fbs_ctx_create_seeded(const fbs_params *params, const uint8_t seed[32], int device, fbs_ctx **out) try {
-    if (!seed) return set_error(nullptr, FBS_E_INVALID, "null seed");
-    return ctx_create(params, 0, seed, device, out);
 } FBS_API_CATCH(nullptr)
 
 int fbs_ctx_tune(fbs_ctx *ctx, const char *knob, int64_t value) try {
@@ -258,19 +239,14 @@ int fbs_ctx_tune(fbs_ctx *ctx, const char *knob, int64_t value) try {
 int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value) try {
     if (!ctx || !name || !value) return FBS_E_INVALID;
     const std::string k(name);
+    if (host_stat(ctx, k, value)) return FBS_OK;   // (what the client library answers too)
     if (k == "scratch_growths") *value = ctx->scratch_growths;
     else if (k == "ms_capacity") *value = (int64_t)ctx->ms_capacity;
     else if (k == "acc_capacity") *value = (int64_t)ctx->acc_capacity;
     else if (k == "wires_capacity") *value = (int64_t)ctx->wires_capacity;
-    else if (k == "next_nonce") *value = (int64_t)ctx->next_nonce.load();
     else if (k == "cu_count") *value = ctx->cu_count;
-    else if (k == "has_secret") *value = ctx->have_keys && !ctx->eval_only;
-    else if (k == "seeded_keys") *value = ctx->have_keys && ctx->seeded_keys;
     else if (k == "states_alive") *value = (int64_t)ctx->states.size();
     else if (k == "state_bytes") *value = (int64_t)ctx->state_bytes;
-    else if (k == "packing_key") *value = ctx->have_pack;
-    else if (k == "packing_levels") *value = ctx->have_pack ? ctx->pack_t : 0;
-    else if (k == "packing_base_bits") *value = ctx->have_pack ? ctx->pack_gamma : 0;
     else if (k == "keys_made_on_device") *value = ctx->have_keys && ctx->keys_made_on_device;
     else if (k == "bsk_upload_bytes") *value = ctx->bsk_upload_bytes;
     else return set_error(ctx, FBS_E_INVALID, "unknown statistic '" + k + "'");
@@ -318,7 +294,6 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
 } catch (...) {   // (nothing here allocates; the promise of the ABI is kept anyway)
 }
 
-const char *fbs_last_error(const fbs_ctx *ctx) { return ctx ? ctx->err.c_str() : create_error(); }
 const char *fbs_device_info(const fbs_ctx *ctx) { return ctx ? ctx->devinfo.c_str() : ""; }
 
 // ---------------------------------------------------------------------------------------------
@@ -344,33 +319,12 @@ int fbs_keygen(fbs_ctx *ctx) try {
     if (on_device) draw_secrets(ctx);
     else host_keygen(ctx);
     ctx->mask_key = mask_key_of(ctx->rkey);
-    ctx->seeded_keys = ctx->eval_only = false;
+    keys_replaced(ctx, false, false);
     int rc = on_device ? keys_on_device(ctx, false, nullptr, nullptr) : dev_upload_keys(ctx);
     if (rc == FBS_OK && !on_device) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
     ctx->keys_made_on_device = on_device;
-    ctx->have_keys = true;
-    ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_key_sizes(const fbs_ctx *ctx, size_t sizes[4]) try {
-    if (!ctx || !sizes) return FBS_E_INVALID;
-    sizes[0] = ctx->p.n;
-    sizes[1] = ctx->D;
-    sizes[2] = ctx->n_ggsw * ctx->rows * (ctx->p.k + 1) * ctx->N;
-    sizes[3] = (size_t)ctx->D * ctx->p.t_ksk * (ctx->p.n + 1);
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_export_keys(const fbs_ctx *ctx, uint64_t *sk_lwe, uint64_t *sk_glwe, uint64_t *bsk, uint64_t *ksk) try {
-    if (!ctx) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if ((sk_lwe || sk_glwe) && ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    if (sk_lwe) std::memcpy(sk_lwe, ctx->sk_lwe.data(), ctx->sk_lwe.size() * 8);
-    if (sk_glwe) std::memcpy(sk_glwe, ctx->sk_glwe.data(), ctx->sk_glwe.size() * 8);
-    if (bsk) std::memcpy(bsk, ctx->bsk.data(), ctx->bsk.size() * 8);
-    if (ksk) std::memcpy(ksk, ctx->ksk.data(), ctx->ksk.size() * 8);
+    keys_in_place(ctx);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
@@ -396,33 +350,12 @@ int fbs_import_keys(fbs_ctx *ctx, const uint64_t *sk_lwe, const uint64_t *sk_glw
     ctx->ksk.assign(ksk, ksk + sizes[3]);
     ctx->have_keys = false;
     ctx->mask_key = mask_key_of(ctx->rkey);
-    ctx->seeded_keys = ctx->eval_only = false;
+    keys_replaced(ctx, false, false);
     int rc = dev_upload_keys(ctx);
     if (rc == FBS_OK) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
     ctx->keys_made_on_device = false;   // (the caller's keys: nothing to make)
-    ctx->have_keys = true;
-    ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_encrypt_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *cts, uint64_t *nonce0) try {
-    uint64_t first = 0;
-    if (int rc = io_prologue(ctx, msgs, cts, count, IO_SECRET | IO_FRESH, &first)) return rc;
-    if (nonce0) *nonce0 = first;
-    host_encrypt(ctx, msgs, count, first, cts);
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *cts) try {
-    if (int rc = io_prologue(ctx, msgs, cts, count, IO_SECRET | IO_BELOW_2_55, &nonce0)) return rc;
-    host_encrypt(ctx, msgs, count, nonce0, cts);
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_decrypt(const fbs_ctx *ctx, const uint64_t *cts, size_t count, int64_t *msgs) try {
-    if (int rc = io_prologue(ctx, cts, msgs, count, IO_SECRET, nullptr)) return rc;
-    host_decrypt(ctx, cts, count, msgs);
+    keys_in_place(ctx);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
@@ -472,37 +405,12 @@ int fbs_keygen_seeded(fbs_ctx *ctx) try {
     } else {
         host_keygen_seeded(ctx);
     }
-    ctx->seeded_keys = true;
-    ctx->eval_only = false;
+    keys_replaced(ctx, true, false);
     int rc = on_device ? keys_on_device(ctx, true, nullptr, nullptr) : dev_upload_keys(ctx);
     if (rc == FBS_OK && !on_device) rc = dev_upload_secret(ctx);
     if (rc != FBS_OK) return rc;
     ctx->keys_made_on_device = on_device;
-    ctx->have_keys = true;
-    ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_seeded_key_sizes(const fbs_ctx *ctx, size_t sizes[2]) try {
-    if (!ctx || !sizes) return FBS_E_INVALID;
-    sizes[0] = ctx->n_ggsw * ctx->rows * ctx->N;
-    sizes[1] = (size_t)ctx->D * ctx->p.t_ksk;
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_export_seeded_keys(const fbs_ctx *ctx, uint8_t mask_key[32], uint64_t *bsk_bodies, uint64_t *ksk_bodies) try {
-    if (!ctx) return FBS_E_INVALID;
-    if (!mask_key || !bsk_bodies || !ksk_bodies) return set_error(ctx, FBS_E_INVALID, "null argument");
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "the keys of this context did not come from fbs_keygen_seeded");
-    const uint32_t N = ctx->N, n = ctx->p.n, k = ctx->p.k;
-    const size_t bsk_rows = ctx->n_ggsw * ctx->rows, ksk_rows = (size_t)ctx->D * ctx->p.t_ksk;
-    for (int i = 0; i < 8; i++)
-        for (int b = 0; b < 4; b++) mask_key[4 * i + b] = (uint8_t)(ctx->mask_key.w[i] >> (8 * b));
-    for (size_t r = 0; r < bsk_rows; r++)
-        std::memcpy(bsk_bodies + r * N, ctx->bsk.data() + (r * (k + 1) + k) * (size_t)N, (size_t)N * 8);
-    for (size_t r = 0; r < ksk_rows; r++) ksk_bodies[r] = ctx->ksk[r * (n + 1) + n];
+    keys_in_place(ctx);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
@@ -540,26 +448,10 @@ int fbs_import_seeded_keys(fbs_ctx *ctx, const uint8_t mask_key[32], const uint6
         }
     ctx->mask_key = mk;
     ctx->have_keys = false;
-    ctx->seeded_keys = true;
-    ctx->eval_only = true;
+    keys_replaced(ctx, true, true);
     if (int rc = on_device ? keys_on_device(ctx, true, bsk_bodies, ksk_bodies) : dev_upload_keys(ctx)) return rc;
     ctx->keys_made_on_device = on_device;
-    ctx->have_keys = true;
-    ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_encrypt_seeded(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *bodies) try {
-    if (int rc = io_prologue(ctx, msgs, bodies, count, IO_SECRET | IO_BELOW_2_55, &nonce0)) return rc;
-    host_encrypt_seeded(ctx, msgs, count, nonce0, bodies);
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_encrypt_seeded_fresh(fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t *bodies, uint64_t *nonce0) try {
-    uint64_t first = 0;
-    if (int rc = io_prologue(ctx, msgs, bodies, count, IO_SECRET | IO_FRESH, &first)) return rc;
-    if (nonce0) *nonce0 = first;
-    host_encrypt_seeded(ctx, msgs, count, first, bodies);
+    keys_in_place(ctx);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 
@@ -577,13 +469,6 @@ int fbs_encrypt_seeded_fresh_dev(fbs_ctx *ctx, const int64_t *d_msgs, size_t cou
     if (count == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     return dev_encrypt_seeded(ctx, d_msgs, count, first, d_bodies, pick(ctx, stream));
-} FBS_API_CATCH(ctx)
-
-// (no secret needed: these run on evaluation-only contexts)
-int fbs_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count, uint64_t nonce0, uint64_t *cts) try {
-    if (int rc = io_prologue(ctx, bodies, cts, count, IO_BELOW_2_56 | IO_CT_WORDS, &nonce0)) return rc;
-    host_expand_seeded(ctx, bodies, count, nonce0, cts);
-    return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 int fbs_expand_seeded_dev(const fbs_ctx *ctx, const uint64_t *d_bodies, size_t count, uint64_t nonce0, uint64_t *d_cts, void *stream) try {
@@ -1156,14 +1041,6 @@ int fbs_audit_level_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, uint
 } FBS_API_CATCH(ctx)
 
 // ---- compact outputs: their decryption (fbs_compact_dev and the compact store stage: fbs_eval.cpp) ------------------------------
-int fbs_decrypt_compact(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs) try {
-    if (int rc = io_prologue(ctx, words, msgs, count, IO_SECRET, nullptr)) return rc;
-    if (int rc = check_bits(ctx, bits)) return rc;
-    if (int rc = check_compact_words(ctx, count, bits)) return rc;
-    host_decrypt_compact(ctx, words, count, bits, msgs);
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
 int fbs_decrypt_compact_dev(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, int64_t *d_msgs, void *stream) try {
     if (int rc = io_prologue(ctx, d_words, d_msgs, count, IO_SECRET, nullptr)) return rc;
     if (int rc = check_bits(ctx, bits)) return rc;
@@ -1373,11 +1250,7 @@ static int install_packing_key(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std
 }
 
 int fbs_packing_keygen(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) try {
-    if (!ctx) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "a packing key goes with seeded keys (fbs_keygen_seeded)");
-    if (int rc = check_packing_params(ctx, t_p, gamma_p)) return rc;
+    if (int rc = check_packing_keygen(ctx, t_p, gamma_p)) return rc;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<uint64_t> bodies;
     if (ctx->tune.keys_on_device) {
@@ -1386,30 +1259,6 @@ int fbs_packing_keygen(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) try {
         host_packing_keygen(ctx, t_p, gamma_p, bodies);
     }
     return install_packing_key(ctx, t_p, gamma_p, bodies);
-} FBS_API_CATCH(ctx)
-
-int fbs_packing_key_sizes(const fbs_ctx *ctx, uint32_t t_p, size_t sizes[2]) try {
-    if (!ctx || !sizes) return FBS_E_INVALID;
-    if (t_p == 0) {
-        if (!ctx->have_pack) return set_error(ctx, FBS_E_STATE, "the context has no packing key");
-        t_p = ctx->pack_t;
-    }
-    if (t_p > 31) return set_error(ctx, FBS_E_INVALID, "packing key needs 1 <= t_p <= 31");
-    sizes[0] = (size_t)ctx->p.n * t_p * ctx->N;
-    sizes[1] = sizes[0] * (ctx->p.k + 1);
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_export_packing_key(const fbs_ctx *ctx, uint64_t *bodies, uint64_t *full) try {
-    if (!ctx) return FBS_E_INVALID;
-    if (!ctx->have_pack) return set_error(ctx, FBS_E_STATE, "the context has no packing key");
-    if (bodies) std::memcpy(bodies, ctx->pack_bodies.data(), ctx->pack_bodies.size() * 8);
-    if (full) {
-        std::vector<uint64_t> key;
-        host_expand_packing_key(ctx, ctx->mask_key, ctx->pack_t, ctx->pack_bodies.data(), key);
-        std::memcpy(full, key.data(), key.size() * 8);
-    }
-    return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 int fbs_import_packing_key(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, const uint64_t *bodies) try {
@@ -1424,14 +1273,6 @@ int fbs_import_packing_key(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, const u
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<uint64_t> copy(bodies, bodies + words);
     return install_packing_key(ctx, t_p, gamma_p, copy);
-} FBS_API_CATCH(ctx)
-
-int fbs_packed_words(const fbs_ctx *ctx, size_t count, uint32_t bits, size_t *words) try {
-    if (!ctx || !words) return FBS_E_INVALID;
-    if (int rc = check_bits(ctx, bits)) return rc;
-    if (int rc = check_packed_words(ctx, count, bits)) return rc;
-    *words = packed_words(ctx->p.k, ctx->N, count, bits);
-    return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 // Ciphertexts per pass: what the modulus-switch scratch holds (at least COMPACT_PASS), cut down to whole samples -- and the
@@ -1503,14 +1344,6 @@ int fbs_state_fetch_packed(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_
         return scratch_fail(ctx, s, rc);
     if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
     return sync_stream(ctx, s);
-} FBS_API_CATCH(ctx)
-
-int fbs_decrypt_packed(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs) try {
-    if (int rc = io_prologue(ctx, words, msgs, count, IO_SECRET, nullptr)) return rc;
-    if (int rc = check_bits(ctx, bits)) return rc;
-    if (int rc = check_packed_words(ctx, count, bits)) return rc;
-    host_decrypt_packed(ctx, words, count, bits, msgs);
-    return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 // ---------------------------------------------------------------------------------------------
@@ -1642,16 +1475,6 @@ int fbs_debug_gauss_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uin
     if (count == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     return dev_debug_gauss(ctx, d_words, count, sigma, d_out, pick(ctx, stream));
-} FBS_API_CATCH(ctx)
-
-// test hook: raise inside an entry point what a host allocation or a library call could raise, to show the barrier holds
-// (kind 0: std::bad_alloc, 1: std::length_error, 2: std::runtime_error, 3: a non-standard exception; anything else: no throw)
-int fbs_debug_raise(fbs_ctx *ctx, int kind) try {
-    if (kind == 0) throw std::bad_alloc();
-    if (kind == 1) throw std::length_error("vector::_M_default_append");
-    if (kind == 2) throw std::runtime_error("raised on request");
-    if (kind == 3) throw 42;
-    return FBS_OK;
 } FBS_API_CATCH(ctx)
 
 }  // extern "C"

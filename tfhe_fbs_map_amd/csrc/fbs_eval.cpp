@@ -541,13 +541,6 @@ int fbs_eval_seeded(fbs_ctx *ctx, fbs_prog *prog, const uint64_t *bodies, size_t
 } FBS_API_CATCH(ctx)
 
 // ---- compact outputs: key switch to the small key, rounding to Z_(2^bits), bit packing (fbs_compact.hpp) --------------------
-int fbs_compact_words(const fbs_ctx *ctx, uint32_t bits, size_t *words) try {
-    if (!ctx || !words) return FBS_E_INVALID;
-    if (int rc = check_bits(ctx, bits)) return rc;
-    *words = compact_words(ctx->p.n, bits);
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
 // (no secret needed: runs on evaluation-only contexts)
 int fbs_compact_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_words, void *stream) try {
     if (int rc = io_prologue(ctx, d_cts, d_words, count, IO_CT_WORDS, nullptr)) return rc;

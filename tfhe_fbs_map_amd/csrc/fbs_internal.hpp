@@ -1,7 +1,7 @@
-// Internal definitions shared by the host side (fbs_host.cpp, fbs_capi.cpp, fbs_eval.cpp) and the HIP side
-// (fbs_kernels.hip) of libfbsexec.so -- and, with FBS_HOST_ONLY defined, by the client library libfbsclient.so
-// (fbs_error.cpp, fbs_host.cpp, fbs_client_capi.cpp), which is built without HIP: it then sees the host state of a context
-// (fbs::HostState) and the host functions, and nothing that names a device type.
+// Internal definitions shared by the host side (fbs_host.cpp, fbs_capi.cpp, fbs_eval.cpp, fbs_client_entries.cpp) and the HIP
+// side (fbs_kernels.hip) of libfbsexec.so -- and, with FBS_HOST_ONLY defined, by the client library libfbsclient.so
+// (fbs_error.cpp, fbs_host.cpp, fbs_client_entries.cpp, fbs_client_capi.cpp), which is built without HIP: it then sees the host
+// state of a context (fbs::HostState) and the host functions, and nothing that names a device type.
 #pragma once
 #ifndef FBS_HOST_ONLY
 #include <hip/hip_runtime.h>

@@ -136,8 +136,8 @@ inline const char *params_out_of_range(const fbs_params &p, uint64_t D) {
     if (bits > 63.9 || bits - 32.0 > 31.9) return "key-switch accumulator would overflow";   // whole sum in 64 bits; high-word partial sums in 32
     return nullptr;
 }
-// ... and whether a kernel is built for the set: null, or why not (the client library asks this directly: a set the GPU library
-// refuses is refused there too) ...
+// ... and whether a kernel is built for the set: null, or why not (fbs_ctx_create of either library asks this after host_ctx_init,
+// in admit_params of fbs_api_checks.hpp: a set the GPU library refuses is refused by the client library too) ...
 inline const char *kernel_not_built(const fbs_params &p) {
     if (p.k >= 2 && !glwe_shape_built(p.log_n_poly, p.k))
         return "GLWE dimensions k >= 2 are built for k = 2, 3, 4 at N = 256 and 512 and k = 2, 3 at N = 1024";
@@ -146,7 +146,8 @@ inline const char *kernel_not_built(const fbs_params &p) {
         return "two key bits per step (bsk_group = 2) at k = 1 is built for N = 1024, 2048 and 4096, l <= 5";
     return nullptr;
 }
-// ... as FBS_OK or FBS_E_INVALID (text in ctx->err).  fbs_ctx_create asks after host_ctx_init.
+// ... as FBS_OK or FBS_E_INVALID (text in ctx->err).  Kept for the host harness of tests/c/ (select mode), which builds no entry
+// file: the libraries ask kernel_not_built themselves, in admit_params.
 int check_kernel_built(const fbs_ctx *ctx);
 // the fbs_ctx_tune knob `name`, or null
 int64_t *tune_knob(Tune &t, const std::string &name);
