@@ -146,48 +146,12 @@ __global__ __launch_bounds__((2 << LL) * FPW) __attribute__((amdgpu_waves_per_eu
         twi.lane = lds + REGION + N;
     }
 
-    // a workgroup past the end of an odd batch repeats the last bootstrap (its waves must keep meeting the others at
-    // the barriers) and writes nothing
-    const size_t f_want = (size_t)blockIdx.x * FPW + sub;
-    const bool live = f_want < a.count;
-    const size_t f = live ? f_want : a.count - 1;
-    size_t gate, ms_row;
-    gate_of(a.gv, f, &gate, &ms_row);
-    // ids that arrive in device memory cannot be validated by the host: an id past the set reads table 0, never past
-    // the end of the buffer
-    uint32_t table = a.gv.table_ids ? a.gv.table_ids[gate] : 0;
-    if (table >= a.n_tables) table = 0;
-    const uint32_t *ms = a.ms + ms_row * (a.n + 1);
-    const uint64_t *tv = a.tvs + (size_t)table * N;
+    const BrJob job = br_job<N>(a, (size_t)blockIdx.x * FPW + sub);
+    const uint32_t *ms = job.ms;
     const uint32_t rows = 2 * a.l;
-
-    // ACC = (0, X^{-b~} * TV), kept CENTRED (|.| <= (q-1)/2) for the whole rotation; register m of lane t is
-    // coefficient t + LANES*m
     double acc[E];
-    {
-        const uint32_t r = (2u * N - ms[a.n]) & (2u * N - 1u);
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t idx = (t + (uint32_t)LANES * m - r) & (2u * N - 1u);
-            const uint64_t v = tv[idx & (N - 1)];
-            acc[m] = comp ? fp_center(fp_from_u64((idx & N) ? fq_neg(v) : v)) : 0.0;
-        }
-    }
-
-    // Rounding runs on doubles too (floor(x * 2^-s + c) is exact on integers): abar = (d + 2^(s-1)) >> s with
-    // s = 46 - l*beta, d = the difference of two centred residues (an integer in (-q, q), not reduced again), abar
-    // kept mod B^l -- B^l is added so that the value converted to an unsigned word is positive (l*beta <= 30).  Adding B/2 at every digit position turns the
-    // balanced digits (each in [-B/2, B/2), carries included) into plain bit fields:
-    //     digit_j = ((abar + (B/2)(1 + B + .. + B^(l-1))) >> j*beta) mod B - B/2.
-    const double round_scale = fp_exp2i(-(int)(FQ_BITS - a.l * a.beta));
-    // Flipping the top bit of every field then leaves digit_j in two's complement, ready for a signed bit-field extract.
-    const uint32_t bhalf = 1u << (a.beta - 1);
-    double round_offset = 0.5 + fp_exp2i((int)(a.l * a.beta));
-    uint32_t sign_bits = 0;
-    for (uint32_t j = 0; j < a.l; j++) {
-        round_offset += (double)(bhalf << (j * a.beta));
-        sign_bits |= bhalf << (j * a.beta);
-    }
+    br_acc_init<N, LANES>(acc, a, job, t, comp != 0u);
+    const auto [round_scale, round_offset, sign_bits] = br_rounding(a.l, a.beta);
 
     const uint32_t t16 = t * 16u;   // this thread's 16 bytes of a register pair's 16 LANES
     uint32_t r_next = ms[0];   // the rotation amount of a step is fetched one step ahead: its latency is never exposed
@@ -331,24 +295,32 @@ __global__ __launch_bounds__((2 << LL) * FPW) __attribute__((amdgpu_waves_per_eu
         for (int m = 0; m < E; m++) acc[m] = fp_center(acc[m] + own[m]);   // |.| <= 17 q -> centred
     }
 
-    // ---- sample extraction of coefficient 0, plus the table's constant -----------------------------
-    if (!live) return;
-    if (uint64_t *raw = gate_acc(a.gv, f, 2 * N)) {   // a rotation of TV_0 that several tables share: the whole accumulator
+    if constexpr (FPW == 4) {
+        // The benchmark shape keeps br_extract's text written out here.  With the call its step loop has the same 3 284
+        // instructions, four FP64 ones in other places (registers 256 -> 252, scratch 20 -> 0 B), and that schedule measured
+        // 0.2-0.3 % slower in three jobs (112 252 against 112 597 FBS/s, a second copy of the parent's library 112 551;
+        // profiles/rotation_frame).  Written out, the loop's vector instructions are the ones they were.  Every other
+        // instantiation takes the call: no slower anywhere it was timed, and 12 to 60 bytes less scratch in most.
+        if (!job.live) return;
+        if (uint64_t *raw = gate_acc(a.gv, job.f, 2 * N)) {
 #pragma unroll
-        for (int m = 0; m < E; m++) raw[comp * N + t + (uint32_t)LANES * m] = fp_to_u64(fp_canon(acc[m]));
-        return;
-    }
-    uint64_t *out = gate_out(a.gv, f, a.ct_words);
-    if (comp == 0) {
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t j = t + (uint32_t)LANES * m;
-            const uint64_t v = fp_to_u64(fp_canon(acc[m]));
-            if (j == 0) out[0] = v;
-            else out[N - j] = fq_neg(v);
+            for (int m = 0; m < E; m++) raw[comp * N + t + (uint32_t)LANES * m] = fp_to_u64(fp_canon(acc[m]));
+            return;
         }
-    } else if (t == 0) {
-        out[N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[table]);
+        uint64_t *out = gate_out(a.gv, job.f, a.ct_words);
+        if (comp == 0) {
+#pragma unroll
+            for (int m = 0; m < E; m++) {
+                const uint32_t j = t + (uint32_t)LANES * m;
+                const uint64_t v = fp_to_u64(fp_canon(acc[m]));
+                if (j == 0) out[0] = v;
+                else out[N - j] = fq_neg(v);
+            }
+        } else if (t == 0) {
+            out[N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[job.table]);
+        }
+    } else {
+        br_extract<N, LANES, 2>(a, job, acc, comp, t);
     }
 }
 
@@ -401,35 +373,12 @@ __global__ __launch_bounds__(2 << LL) __attribute__((amdgpu_waves_per_eu(2))) vo
         twi.lane = lds + 3 * N;
     }
 
-    const bool live = (size_t)blockIdx.x < a.count;
-    const size_t f = live ? (size_t)blockIdx.x : a.count - 1;
-    size_t gate, ms_row;
-    gate_of(a.gv, f, &gate, &ms_row);
-    uint32_t table = a.gv.table_ids ? a.gv.table_ids[gate] : 0;
-    if (table >= a.n_tables) table = 0;
-    const uint32_t *ms = a.ms + ms_row * (a.n + 1);
-    const uint64_t *tv = a.tvs + (size_t)table * N;
+    const BrJob job = br_job<N>(a, blockIdx.x);
+    const uint32_t *ms = job.ms;
     const uint32_t rows = 2 * a.l;
-
-    double acc[E];   // ACC = (0, X^{-b~} * TV), centred; register m of lane t = coefficient t + LANES*m
-    {
-        const uint32_t r = (2u * N - ms[a.n]) & (2u * N - 1u);
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t idx = (t + (uint32_t)LANES * m - r) & (2u * N - 1u);
-            const uint64_t v = tv[idx & (N - 1)];
-            acc[m] = comp ? fp_center(fp_from_u64((idx & N) ? fq_neg(v) : v)) : 0.0;
-        }
-    }
-    // rounding / digit constants: as in k_blind_rotate
-    const double round_scale = fp_exp2i(-(int)(FQ_BITS - a.l * a.beta));
-    const uint32_t bhalf = 1u << (a.beta - 1);
-    double round_offset = 0.5 + fp_exp2i((int)(a.l * a.beta));
-    uint32_t sign_bits = 0;
-    for (uint32_t j = 0; j < a.l; j++) {
-        round_offset += (double)(bhalf << (j * a.beta));
-        sign_bits |= bhalf << (j * a.beta);
-    }
+    double acc[E];
+    br_acc_init<N, LANES>(acc, a, job, t, comp != 0u);
+    const auto [round_scale, round_offset, sign_bits] = br_rounding(a.l, a.beta);
     // zeta^e for the evaluation point zeta = psi^o a register holds: exponent x = e * o mod 2N, o = o_lane + c_m with
     // o_lane = 2 bitrev(lane part of the array position) + 1 = G k_lane + r_lane (r_lane wave-uniform) and c_m = 2 bitrev(
     // register part), a compile-time constant.  x = G a + b with b wave-uniform; table word b N/G + (a mod N/G), sign = bit
@@ -581,24 +530,7 @@ __global__ __launch_bounds__(2 << LL) __attribute__((amdgpu_waves_per_eu(2))) vo
         for (int m = 0; m < E; m++) acc[m] = fp_center(acc[m] + own[m]);
     }
 
-    if (!live) return;
-    if (uint64_t *raw = gate_acc(a.gv, f, 2 * N)) {   // a rotation of TV_0 that several tables share: the whole accumulator
-#pragma unroll
-        for (int m = 0; m < E; m++) raw[comp * N + t + (uint32_t)LANES * m] = fp_to_u64(fp_canon(acc[m]));
-        return;
-    }
-    uint64_t *out = gate_out(a.gv, f, a.ct_words);
-    if (comp == 0) {
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t j = t + (uint32_t)LANES * m;
-            const uint64_t v = fp_to_u64(fp_canon(acc[m]));
-            if (j == 0) out[0] = v;
-            else out[N - j] = fq_neg(v);
-        }
-    } else if (t == 0) {
-        out[N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[table]);
-    }
+    br_extract<N, LANES, 2>(a, job, acc, comp, t);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,5 +1,7 @@
-// What the blind-rotation kernels of fbs_blind_rotate.hip and fbs_blind_rotate_cu.hip share: launch arguments, the issue-priority
-// hand-over of the two waves of a SIMD, and the launcher of the one-bootstrap-per-CU shape.
+// What the blind-rotation kernels of fbs_blind_rotate.hip, fbs_blind_rotate_cu.hip, fbs_blind_rotate_k2.hip and
+// fbs_blind_rotate_glwe.hip share: launch arguments, the issue-priority hand-over of the two waves of a SIMD, key words through
+// buffer loads, the frame of a kernel (which bootstrap a thread works on, the initial accumulator, the rounding constants, sample
+// extraction) and the launchers of the other three files.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -76,6 +78,104 @@ struct KeyRows {
         return r;
     }
 };
+
+// ---------------------------------------------------------------------------------------------
+// The frame of a blind-rotation kernel: everything around its step loop.  Every kernel opens with br_job, br_acc_init and
+// br_rounding and closes with br_extract; what lies between (LDS, twiddles, key addressing, the steps) is the kernel's own.
+
+// Which bootstrap a thread works on.  f_want: the bootstrap of the launch its workgroup (and, with several bootstraps per
+// workgroup, its part of the workgroup) stands for.  One past the end of a ragged batch repeats the last bootstrap -- its waves
+// must keep meeting the others at the barriers -- and is not `live`: br_extract writes nothing for it.
+struct BrJob {
+    bool live;
+    size_t f;             // bootstrap of the launch, < a.count
+    uint32_t table;       // its table, < a.n_tables
+    const uint32_t *ms;   // its n + 1 rotation amounts, the body's last
+    const uint64_t *tv;   // its table's test polynomial
+};
+template <int N>
+__device__ __forceinline__ BrJob br_job(const BrArgs &a, size_t f_want) {
+    BrJob job;
+    job.live = f_want < a.count;
+    job.f = job.live ? f_want : a.count - 1;
+    size_t gate, ms_row;
+    gate_of(a.gv, job.f, &gate, &ms_row);
+    // ids that arrive in device memory cannot be validated by the host: an id past the set reads table 0, never past
+    // the end of the buffer
+    job.table = a.gv.table_ids ? a.gv.table_ids[gate] : 0;
+    if (job.table >= a.n_tables) job.table = 0;
+    job.ms = a.ms + ms_row * (a.n + 1);
+    job.tv = a.tvs + (size_t)job.table * N;
+    return job;
+}
+
+// ACC = (0, .., 0, X^{-b~} * TV), kept CENTRED (|.| <= (q-1)/2) for the whole rotation; register m of thread t of a component
+// is coefficient t + LANES * m.  `body` (wave-uniform): this thread's component is the last one.
+template <int N, int LANES, int E>
+__device__ __forceinline__ void br_acc_init(double (&acc)[E], const BrArgs &a, const BrJob &job, uint32_t t, bool body) {
+    const uint32_t r = (2u * N - job.ms[a.n]) & (2u * N - 1u);
+#pragma unroll
+    for (int m = 0; m < E; m++) {
+        const uint32_t idx = (t + (uint32_t)LANES * m - r) & (2u * N - 1u);
+        const uint64_t v = job.tv[idx & (N - 1)];
+        acc[m] = body ? fp_center(fp_from_u64((idx & N) ? fq_neg(v) : v)) : 0.0;
+    }
+}
+
+// Rounding runs on doubles too (floor(x * 2^-s + c) is exact on integers): abar = (d + 2^(s-1)) >> s with
+// s = 46 - l*beta, d = what a step decomposes (a centred residue, or the difference of two: an integer in (-q, q), not reduced
+// again), abar kept mod B^l -- B^l is added so that the value converted to an unsigned word is positive (l*beta <= 30).  Adding
+// B/2 at every digit position turns the balanced digits (each in [-B/2, B/2), carries included) into plain bit fields:
+//     digit_j = ((abar + (B/2)(1 + B + .. + B^(l-1))) >> j*beta) mod B - B/2.
+// Flipping the top bit of every field then leaves digit_j in two's complement, ready for a signed bit-field extract:
+//     fields = (uint32_t)fma(d, scale, offset) ^ sign_bits      (truncation = floor, < 3 * 2^(l*beta)).
+// Every term of `offset` is an integer or a half that a double holds exactly, so the order of the additions changes no bit.
+// NL: the number of levels where the kernel knows it at compile time (the loop is unrolled); 0: `levels` at run time.
+struct BrRounding {
+    double scale, offset;
+    uint32_t sign_bits;
+};
+template <int NL = 0>
+__device__ __forceinline__ BrRounding br_rounding(uint32_t levels, uint32_t beta) {
+    if constexpr (NL != 0) levels = NL;
+    const uint32_t bhalf = 1u << (beta - 1);
+    BrRounding r{fp_exp2i(-(int)(FQ_BITS - levels * beta)), 0.5 + fp_exp2i((int)(levels * beta)), 0u};
+    auto level = [&](uint32_t j) {
+        r.offset += (double)(bhalf << (j * beta));
+        r.sign_bits |= bhalf << (j * beta);
+    };
+    if constexpr (NL != 0) {
+#pragma unroll
+        for (uint32_t j = 0; j < NL; j++) level(j);
+    } else {
+        for (uint32_t j = 0; j < levels; j++) level(j);
+    }
+    return r;
+}
+
+// Sample extraction of coefficient 0 of a K1-component accumulator (K1 - 1 mask polynomials, then the body), plus the table's
+// constant; the whole epilogue of a kernel.  `comp` (wave-uniform): the component this thread holds.
+template <int N, int LANES, int K1, int E>
+__device__ __forceinline__ void br_extract(const BrArgs &a, const BrJob &job, const double (&acc)[E], uint32_t comp, uint32_t t) {
+    if (!job.live) return;
+    if (uint64_t *raw = gate_acc(a.gv, job.f, K1 * N)) {   // a rotation of TV_0 that several tables share: the whole accumulator
+#pragma unroll
+        for (int m = 0; m < E; m++) raw[comp * N + t + (uint32_t)LANES * m] = fp_to_u64(fp_canon(acc[m]));
+        return;
+    }
+    uint64_t *out = gate_out(a.gv, job.f, a.ct_words);
+    if (comp < (uint32_t)(K1 - 1)) {
+#pragma unroll
+        for (int m = 0; m < E; m++) {
+            const uint32_t j = t + (uint32_t)LANES * m;
+            const uint64_t v = fp_to_u64(fp_canon(acc[m]));
+            if (j == 0) out[comp * N] = v;
+            else out[comp * N + N - j] = fq_neg(v);
+        }
+    } else if (t == 0) {
+        out[(K1 - 1) * N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[job.table]);
+    }
+}
 
 // the launch of one descriptor (fbs_select.hpp) in each launch file: false when the descriptor is not of its families
 // fbs_blind_rotate_cu.hip: one bootstrap on the eight waves of a CU (k = 1)

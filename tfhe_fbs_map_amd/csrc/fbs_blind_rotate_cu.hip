@@ -85,37 +85,12 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
     CuTwiddles<Part, LEAN> tw;
     tw.init(big_f, big_i, a.tw_fwd + W::LANE_TABLE_OFFSET, a.tw_inv + W::LANE_TABLE_OFFSET, w, ln, lds_all + 2 * N + 2 * NL * N);
 
-    const bool live = (size_t)blockIdx.x < a.count;
-    const size_t f = live ? (size_t)blockIdx.x : a.count - 1;
-    size_t gate, ms_row;
-    gate_of(a.gv, f, &gate, &ms_row);
-    uint32_t table = a.gv.table_ids ? a.gv.table_ids[gate] : 0;
-    if (table >= a.n_tables) table = 0;
-    const uint32_t *ms = a.ms + ms_row * (a.n + 1);
-    const uint64_t *tv = a.tvs + (size_t)table * N;
+    const BrJob job = br_job<N>(a, blockIdx.x);
+    const uint32_t *ms = job.ms;
     const uint32_t rows = 2 * NL;
-
-    // ACC = (0, X^{-b~} * TV), centred; register m of thread t = coefficient t + 256 m
     double acc[E];
-    {
-        const uint32_t r = (2u * N - ms[a.n]) & (2u * N - 1u);
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t idx = (t + (uint32_t)LANES * m - r) & (2u * N - 1u);
-            const uint64_t v = tv[idx & (N - 1)];
-            acc[m] = comp ? fp_center(fp_from_u64((idx & N) ? fq_neg(v) : v)) : 0.0;
-        }
-    }
-    // rounding / digit constants: as in k_blind_rotate
-    const double round_scale = fp_exp2i(-(int)(FQ_BITS - NL * a.beta));
-    const uint32_t bhalf = 1u << (a.beta - 1);
-    double round_offset = 0.5 + fp_exp2i((int)(NL * a.beta));
-    uint32_t sign_bits = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < NL; j++) {
-        round_offset += (double)(bhalf << (j * a.beta));
-        sign_bits |= bhalf << (j * a.beta);
-    }
+    br_acc_init<N, LANES>(acc, a, job, t, comp != 0u);
+    const auto [round_scale, round_offset, sign_bits] = br_rounding<NL>(NL, a.beta);
     // cross-stage twiddles: nodes 1, 2, 3 of the big tree (wave-uniform, scalar registers for the whole rotation)
     const double cw[3] = {big_f[1], big_f[2], big_f[3]}, iw[3] = {big_i[1], big_i[2], big_i[3]};
 
@@ -277,25 +252,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
         __syncthreads();
     }
 
-    // ---- sample extraction of coefficient 0, plus the table's constant -----------------------------
-    if (!live) return;
-    if (uint64_t *raw = gate_acc(a.gv, f, 2 * N)) {   // a rotation of TV_0 that several tables share: the whole accumulator
-#pragma unroll
-        for (int m = 0; m < E; m++) raw[comp * N + t + (uint32_t)LANES * m] = fp_to_u64(fp_canon(acc[m]));
-        return;
-    }
-    uint64_t *out = gate_out(a.gv, f, a.ct_words);
-    if (comp == 0) {
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t j = t + (uint32_t)LANES * m;
-            const uint64_t v = fp_to_u64(fp_canon(acc[m]));
-            if (j == 0) out[0] = v;
-            else out[N - j] = fq_neg(v);
-        }
-    } else if (t == 0) {
-        out[N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[table]);
-    }
+    br_extract<N, LANES, 2>(a, job, acc, comp, t);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -349,37 +306,12 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
     CuTwiddles<Part, false> tw;
     tw.init(big_f, big_i, a.tw_fwd + W::LANE_TABLE_OFFSET, a.tw_inv + W::LANE_TABLE_OFFSET, w, ln, lds_all + 2 * N + 2 * NL * N);
 
-    const bool live = (size_t)blockIdx.x < a.count;
-    const size_t f = live ? (size_t)blockIdx.x : a.count - 1;
-    size_t gate, ms_row;
-    gate_of(a.gv, f, &gate, &ms_row);
-    uint32_t table = a.gv.table_ids ? a.gv.table_ids[gate] : 0;
-    if (table >= a.n_tables) table = 0;
-    const uint32_t *ms = a.ms + ms_row * (a.n + 1);
-    const uint64_t *tv = a.tvs + (size_t)table * N;
+    const BrJob job = br_job<N>(a, blockIdx.x);
+    const uint32_t *ms = job.ms;
     constexpr uint32_t rows = 2 * NL;
-
-    double acc[E];   // ACC = (0, X^{-b~} * TV), centred; register m of thread t = coefficient t + 256 m
-    {
-        const uint32_t r = (2u * N - ms[a.n]) & (2u * N - 1u);
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t idx = (t + (uint32_t)LANES * m - r) & (2u * N - 1u);
-            const uint64_t v = tv[idx & (N - 1)];
-            acc[m] = comp ? fp_center(fp_from_u64((idx & N) ? fq_neg(v) : v)) : 0.0;
-        }
-    }
-    // rounding / digit constants: as in k_blind_rotate (abar = round(acc / 2^(46 - NL beta)) mod B^NL, balanced digits packed in
-    // two's complement fields)
-    const double round_scale = fp_exp2i(-(int)(FQ_BITS - NL * a.beta));
-    const uint32_t bhalf = 1u << (a.beta - 1);
-    double round_offset = 0.5 + fp_exp2i((int)(NL * a.beta));
-    uint32_t sign_bits = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < NL; j++) {
-        round_offset += (double)(bhalf << (j * a.beta));
-        sign_bits |= bhalf << (j * a.beta);
-    }
+    double acc[E];
+    br_acc_init<N, LANES>(acc, a, job, t, comp != 0u);
+    const auto [round_scale, round_offset, sign_bits] = br_rounding<NL>(NL, a.beta);
     const double cw[3] = {big_f[1], big_f[2], big_f[3]}, iw[3] = {big_i[1], big_i[2], big_i[3]};
     // o_lane = 2 bitrev11(512 w + (ln & 31) << 4 | (ln >> 5) << 3) + 1; omega^s = psi^(512 s), s = 1, 2, 3 (wave-uniform)
     const uint32_t o_lane = 2u * (__builtin_bitreverse32(512u * w + ((ln & 31u) << 4) + ((ln >> 5) << 3)) >> (32 - LOGN)) + 1u;
@@ -647,24 +579,7 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
     asm volatile("" ::"v"(ahead_word));   // (never looked at; this keeps the loads)
 #endif
 
-    if (!live) return;
-    if (uint64_t *raw = gate_acc(a.gv, f, 2 * N)) {
-#pragma unroll
-        for (int m = 0; m < E; m++) raw[comp * N + t + (uint32_t)LANES * m] = fp_to_u64(fp_canon(acc[m]));
-        return;
-    }
-    uint64_t *out = gate_out(a.gv, f, a.ct_words);
-    if (comp == 0) {
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t j = t + (uint32_t)LANES * m;
-            const uint64_t v = fp_to_u64(fp_canon(acc[m]));
-            if (j == 0) out[0] = v;
-            else out[N - j] = fq_neg(v);
-        }
-    } else if (t == 0) {
-        out[N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[table]);
-    }
+    br_extract<N, LANES, 2>(a, job, acc, comp, t);
 }
 
 // the instantiation of a k_blind_rotate_cu or k_blind_rotate_cu_pairs descriptor (fbs_select.hpp); false for any other

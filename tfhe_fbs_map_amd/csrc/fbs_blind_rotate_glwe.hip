@@ -94,38 +94,11 @@ __global__ __launch_bounds__(64 * K1 * FPW) void k_blind_rotate_glwe(BrArgs a) {
     for (uint32_t x = threadIdx.x; x < (uint32_t)(SETS * WAVES * N); x += 64u * WAVES) landing[x] = 0.0;
     __syncthreads();
 
-    // a workgroup past the end of a batch that is not a multiple of FPW repeats the last bootstrap (its waves must keep meeting
-    // the others at the barriers) and writes nothing
-    const size_t f_want = (size_t)blockIdx.x * FPW + sub;
-    const bool live = f_want < a.count;
-    const size_t f = live ? f_want : a.count - 1;
-    size_t gate, ms_row;
-    gate_of(a.gv, f, &gate, &ms_row);
-    uint32_t table = a.gv.table_ids ? a.gv.table_ids[gate] : 0;
-    if (table >= a.n_tables) table = 0;
-    const uint32_t *ms = a.ms + ms_row * (a.n + 1);
-    const uint64_t *tv = a.tvs + (size_t)table * N;
-
-    double acc[E];   // ACC = (0, .., 0, X^{-b~} * TV), centred; register m of lane t = coefficient t + 64 m
-    {
-        const uint32_t r = (2u * N - ms[a.n]) & (2u * N - 1u);
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t idx = (t + (uint32_t)LANES * m - r) & (2u * N - 1u);
-            const uint64_t v = tv[idx & (N - 1)];
-            acc[m] = comp == (uint32_t)(K1 - 1) ? fp_center(fp_from_u64((idx & N) ? fq_neg(v) : v)) : 0.0;
-        }
-    }
-    // rounding / digit constants: as in k_blind_rotate (abar = round(d / 2^(46 - l beta)) mod B^l, balanced digits as two's
-    // complement bit fields)
-    const double round_scale = fp_exp2i(-(int)(FQ_BITS - a.l * a.beta));
-    const uint32_t bhalf = 1u << (a.beta - 1);
-    double round_offset = 0.5 + fp_exp2i((int)(a.l * a.beta));
-    uint32_t sign_bits = 0;
-    for (uint32_t j = 0; j < a.l; j++) {
-        round_offset += (double)(bhalf << (j * a.beta));
-        sign_bits |= bhalf << (j * a.beta);
-    }
+    const BrJob job = br_job<N>(a, (size_t)blockIdx.x * FPW + sub);
+    const uint32_t *ms = job.ms;
+    double acc[E];
+    br_acc_init<N, LANES>(acc, a, job, t, comp == (uint32_t)(K1 - 1));
+    const auto [round_scale, round_offset, sign_bits] = br_rounding(a.l, a.beta);
     // the components in rotated order: d stands for component comp + d (mod K1); d = 0 is this wave's own
     uint32_t col_bytes[K1], land_word[K1];
 #pragma unroll
@@ -321,25 +294,7 @@ __global__ __launch_bounds__(64 * K1 * FPW) void k_blind_rotate_glwe(BrArgs a) {
 
     if constexpr (FBS_GLWE_L2_AHEAD != 0) asm volatile("" ::"v"(ahead_word));   // (never looked at; this keeps the loads)
 
-    // ---- sample extraction of coefficient 0 (k mask polynomials, the body), plus the table's constant -----------------
-    if (!live) return;
-    if (uint64_t *raw = gate_acc(a.gv, f, K1 * N)) {   // a rotation of TV_0 that several tables share: the whole accumulator
-#pragma unroll
-        for (int m = 0; m < E; m++) raw[comp * N + t + (uint32_t)LANES * m] = fp_to_u64(fp_canon(acc[m]));
-        return;
-    }
-    uint64_t *out = gate_out(a.gv, f, a.ct_words);
-    if (comp < (uint32_t)(K1 - 1)) {
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t j = t + (uint32_t)LANES * m;
-            const uint64_t v = fp_to_u64(fp_canon(acc[m]));
-            if (j == 0) out[comp * N] = v;
-            else out[comp * N + N - j] = fq_neg(v);
-        }
-    } else if (t == 0) {
-        out[(K1 - 1) * N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[table]);
-    }
+    br_extract<N, LANES, K1>(a, job, acc, comp, t);
 }
 
 // the instantiation of a k_blind_rotate_glwe descriptor (fbs_select.hpp); false for any other.  Bootstraps per workgroup: 1, 2

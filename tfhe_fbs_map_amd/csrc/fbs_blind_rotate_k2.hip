@@ -71,32 +71,11 @@ __global__ __launch_bounds__(192 * FPW) void k_blind_rotate_pairs_k2(BrArgs a) {
     }
     __syncthreads();
 
-    // a workgroup past the end of a batch that is not a multiple of FPW repeats the last bootstrap (its waves must keep meeting
-    // the others at the barriers) and writes nothing
-    const size_t f_want = (size_t)blockIdx.x * FPW + sub;
-    const bool live = f_want < a.count;
-    const size_t f = live ? f_want : a.count - 1;
-    size_t gate, ms_row;
-    gate_of(a.gv, f, &gate, &ms_row);
-    uint32_t table = a.gv.table_ids ? a.gv.table_ids[gate] : 0;
-    if (table >= a.n_tables) table = 0;
-    const uint32_t *ms = a.ms + ms_row * (a.n + 1);
-    const uint64_t *tv = a.tvs + (size_t)table * N;
-
-    double acc[E];   // ACC = (0, 0, X^{-b~} * TV), centred; register m of lane t = coefficient t + 64 m
-    {
-        const uint32_t r = (2u * N - ms[a.n]) & (2u * N - 1u);
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t idx = (t + (uint32_t)LANES * m - r) & (2u * N - 1u);
-            const uint64_t v = tv[idx & (N - 1)];
-            acc[m] = comp == 2u ? fp_center(fp_from_u64((idx & N) ? fq_neg(v) : v)) : 0.0;
-        }
-    }
-    // rounding / digit constants: as in k_blind_rotate (one level: abar = round(acc / 2^(46 - beta)) mod B, balanced)
-    const double round_scale = fp_exp2i(-(int)(FQ_BITS - a.beta));
-    const uint32_t bhalf = 1u << (a.beta - 1);
-    const double round_offset = 0.5 + fp_exp2i((int)a.beta) + (double)bhalf;
+    const BrJob job = br_job<N>(a, (size_t)blockIdx.x * FPW + sub);
+    const uint32_t *ms = job.ms;
+    double acc[E];
+    br_acc_init<N, LANES>(acc, a, job, t, comp == (uint32_t)(K1 - 1));
+    const auto [round_scale, round_offset, bhalf] = br_rounding<1>(1, a.beta);   // (one level: the sign bits are B/2)
     // zeta^e for the evaluation point a register holds: as in k_blind_rotate_pairs
     const uint32_t o_lane = 2u * (__builtin_bitreverse32(W::eval_position_lane(t)) >> (32 - LOGN)) + 1u;
     const uint32_t k_lane8 = (o_lane >> GLOG) << 3;
@@ -197,25 +176,7 @@ __global__ __launch_bounds__(192 * FPW) void k_blind_rotate_pairs_k2(BrArgs a) {
         for (int m = 0; m < E; m++) acc[m] = fp_center(acc[m] + own[m]);
     }
 
-    // ---- sample extraction of coefficient 0 (two mask polynomials, the body), plus the table's constant -----------------
-    if (!live) return;
-    if (uint64_t *raw = gate_acc(a.gv, f, K1 * N)) {   // a rotation of TV_0 that several tables share: the whole accumulator
-#pragma unroll
-        for (int m = 0; m < E; m++) raw[comp * N + t + (uint32_t)LANES * m] = fp_to_u64(fp_canon(acc[m]));
-        return;
-    }
-    uint64_t *out = gate_out(a.gv, f, a.ct_words);
-    if (comp < 2u) {
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t j = t + (uint32_t)LANES * m;
-            const uint64_t v = fp_to_u64(fp_canon(acc[m]));
-            if (j == 0) out[comp * N] = v;
-            else out[comp * N + N - j] = fq_neg(v);
-        }
-    } else if (t == 0) {
-        out[2 * N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[table]);
-    }
+    br_extract<N, LANES, K1>(a, job, acc, comp, t);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -288,29 +249,11 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
     Tw tw;
     tw.init(big_f, big_i, a.tw_fwd + W::LANE_TABLE_OFFSET, a.tw_inv + W::LANE_TABLE_OFFSET, w, ln, nullptr);
 
-    const bool live = (size_t)blockIdx.x < a.count;
-    const size_t f = live ? (size_t)blockIdx.x : a.count - 1;
-    size_t gate, ms_row;
-    gate_of(a.gv, f, &gate, &ms_row);
-    uint32_t table = a.gv.table_ids ? a.gv.table_ids[gate] : 0;
-    if (table >= a.n_tables) table = 0;
-    const uint32_t *ms = a.ms + ms_row * (a.n + 1);
-    const uint64_t *tv = a.tvs + (size_t)table * N;
-
-    double acc[E];   // ACC = (0, 0, X^{-b~} * TV), centred; register m of thread t = coefficient t + 256 m
-    {
-        const uint32_t r = (2u * N - ms[a.n]) & (2u * N - 1u);
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t idx = (t + (uint32_t)LANES * m - r) & (2u * N - 1u);
-            const uint64_t v = tv[idx & (N - 1)];
-            acc[m] = comp == 2u ? fp_center(fp_from_u64((idx & N) ? fq_neg(v) : v)) : 0.0;
-        }
-    }
-    // rounding / digit constants: as in k_blind_rotate_pairs_k2 (one level)
-    const double round_scale = fp_exp2i(-(int)(FQ_BITS - a.beta));
-    const uint32_t bhalf = 1u << (a.beta - 1);
-    const double round_offset = 0.5 + fp_exp2i((int)a.beta) + (double)bhalf;
+    const BrJob job = br_job<N>(a, blockIdx.x);
+    const uint32_t *ms = job.ms;
+    double acc[E];
+    br_acc_init<N, LANES>(acc, a, job, t, comp == (uint32_t)(K1 - 1));
+    const auto [round_scale, round_offset, bhalf] = br_rounding<1>(1, a.beta);   // (one level: the sign bits are B/2)
     // cross-stage twiddles: nodes 1, 2, 3 of the big tree (wave-uniform, scalar registers for the whole rotation)
     const double cw[3] = {big_f[1], big_f[2], big_f[3]}, iw[3] = {big_i[1], big_i[2], big_i[3]};
     const uint32_t o_lane = 2u * (__builtin_bitreverse32((uint32_t)M * w + (((ln & 15u) << 4) | ((ln >> 4) << 2))) >> (32 - LOGN)) + 1u;
@@ -471,25 +414,7 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
         for (int m = 0; m < E; m++) acc[m] = fp_center(acc[m] + own[m]);
     }
 
-    // ---- sample extraction of coefficient 0 (two mask polynomials, the body), plus the table's constant -----------------
-    if (!live) return;
-    if (uint64_t *raw = gate_acc(a.gv, f, K1 * N)) {   // a rotation of TV_0 that several tables share: the whole accumulator
-#pragma unroll
-        for (int m = 0; m < E; m++) raw[comp * N + t + (uint32_t)LANES * m] = fp_to_u64(fp_canon(acc[m]));
-        return;
-    }
-    uint64_t *out = gate_out(a.gv, f, a.ct_words);
-    if (comp < 2u) {
-#pragma unroll
-        for (int m = 0; m < E; m++) {
-            const uint32_t j = t + (uint32_t)LANES * m;
-            const uint64_t v = fp_to_u64(fp_canon(acc[m]));
-            if (j == 0) out[comp * N] = v;
-            else out[comp * N + N - j] = fq_neg(v);
-        }
-    } else if (t == 0) {
-        out[2 * N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[table]);
-    }
+    br_extract<N, LANES, K1>(a, job, acc, comp, t);
 }
 
 // the instantiation of a k_blind_rotate_pairs_k2 or k_blind_rotate_cu_k2 descriptor (fbs_select.hpp); false for any other
