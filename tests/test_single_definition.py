@@ -47,6 +47,70 @@ def test_each_entry_is_written_once():
     assert "fbs_client_capi.cpp" not in lists["NAMES"] and "fbs_capi.cpp" not in lists["CLIENT_NAMES"]
 
 
+def _csrc(name):
+    return open(os.path.join(CSRC, name)).read()
+
+
+def _function_bodies(text):
+    """{name: body} of the functions defined at the left margin or one namespace level in: a line that ends in ") {" or ") try {"
+    up to the next line that is "}" alone"""
+    return {m.group(1): m.group(2) for m in re.finditer(r"^[\w:<>*&, ]*?\b(\w+)\((?:[^;{}]|\n)*?\)(?: const)? (?:try )?\{\n(.*?)^\}", text, flags=re.M | re.S)}
+
+
+def test_the_frame_of_a_sample_is_written_once():
+    """Every LWE row and every GLWE zero sample comes from one generator on each side: csrc/fbs_rows.hpp on the
+    device, mask_words / lwe_body / glwe_zero_sample in csrc/fbs_host.cpp on the host."""
+    rows, io, keygen = _csrc("fbs_rows.hpp"), _csrc("fbs_io.hip"), _csrc("fbs_keygen.hip")
+    # the three-way block store and the vector type it stores, once across the sample kernels' files
+    ladder = r"& 15u\) == 0\) \{\n[^\n]*u64x2[^\n]*w\[i\], w\[i \+ 1\]"
+    typedef = r"typedef uint64_t u64x2\b"
+    assert len(re.findall(ladder, rows)) == 1 and len(re.findall(typedef, rows)) == 1
+    for text in (io, keygen):
+        assert not re.search(r"& 15u\) == 0", text) and not re.search(typedef, text)
+        assert '#include "fbs_rows.hpp"' in text
+    for name in ("fbs_public.hip", "fbs_state.hip"):   # (their own alignment code stores something else; the type is the shared one)
+        assert not re.search(typedef, _csrc(name)) and '#include "fbs_rows.hpp"' in _csrc(name), name
+    # the block loop over a ChaCha stream is in the frame and in k_glwe_key_rows (mask columns, noise), nowhere else in the two files
+    assert "chacha_block" not in io
+    assert len(re.findall(r"chacha_block\(", keygen)) == 2 and len(re.findall(r"chacha_block\(", rows)) == 2
+    # one wave sum, and no butterfly spelled out where it is a drop-in (k_audit_reduce propagates carries: its own)
+    sums = {name: len(re.findall(r"\+= __shfl_xor\(", _csrc(name))) for name in os.listdir(CSRC) if name.endswith((".hip", ".hpp"))}
+    assert {name: n for name, n in sums.items() if n} == {"fbs_rows.hpp": 1, "fbs_audit.hip": 2}, sums
+    assert "k_audit_reduce" in _csrc("fbs_audit.hip") and not re.search(r"\w*wave_sum\(\w+ \w+\) \{", io + keygen)
+
+
+def test_one_key_transform_kernel():
+    kernels = {}
+    for path in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")):
+        text = open(path).read()
+        for old in ("k_bsk_transform", "k_pack_key_transform", "k_secret_transform"):
+            assert old not in text, (old, os.path.basename(path))
+        for m in re.finditer(r"__global__[^;{]*?\bvoid (k_\w*transform\w*)\(", text):
+            kernels.setdefault(m.group(1), []).append(os.path.basename(path))
+    kernels.pop("k_debug_transform", None)   # (a test hook that runs one named transform variant: not a key's)
+    assert kernels == {"k_key_transform": ["fbs_blind_rotate.hpp"]}, kernels
+    launches = {name: len(re.findall(r"\(k_key_transform<", _csrc(name))) for name in ("fbs_blind_rotate.hip", "fbs_pack.hip", "fbs_keygen.hip")}
+    assert launches == {"fbs_blind_rotate.hip": 2, "fbs_pack.hip": 1, "fbs_keygen.hip": 1}, launches
+
+
+def test_the_host_draws_masks_and_products_in_one_place():
+    host, public = _csrc("fbs_host.cpp"), _csrc("fbs_public.cpp")
+    # no negacyclic add of its own in the public-key library: the shift-and-subtract idiom and the old name are gone
+    assert "add_times_bits" not in public and not re.search(r"\[j \+ sh - N\]", public)
+    assert "add_times_key(" in public and len(re.findall(r"^void add_times_key\(", host, flags=re.M)) == 1
+    assert "rand_words" not in public.replace("rand_words(pub->key, stream_id(DOM_PUB_ENC_U", "")   # (u: bits, not a mask)
+    # rand_words: its definition, the secrets, noise_sample and mask_words; every other caller goes through the helpers
+    bodies = _function_bodies(host)
+    assert {"rand_words", "noise_sample", "mask_words", "lwe_body", "glwe_zero_sample", "draw_secrets", "host_keygen", "host_encrypt"} <= set(bodies)
+    callers = sorted(name for name, body in bodies.items() if "rand_words(" in body)
+    assert callers == ["draw_secrets", "mask_words", "noise_sample"], callers
+    # and the fold of a mask word and the product by the secret are the helpers' alone
+    assert sorted(name for name, body in bodies.items() if "fq_fold(" in body) == ["mask_words"]
+    users = sorted(name for name, body in bodies.items() if "add_times_key(" in body)
+    assert users == ["glwe_zero_sample"], users
+    assert "std::fill(s.begin(), s.end(), 0u)" in public   # fbs_pub_keygen still wipes the secret's positions
+
+
 def test_no_library_exports_what_allocates_a_context():
     """sizeof(fbs_ctx) is each library's own, and libfbsexec.so is not linked -Bsymbolic: were admit_params, params_admitted or
     ctx_create in a dynamic symbol table, a process with two of the libraries could allocate a context with one and fill it with

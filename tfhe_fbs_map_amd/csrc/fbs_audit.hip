@@ -30,7 +30,7 @@
 
 #include <algorithm>
 
-#include "fbs_internal.hpp"
+#include "fbs_rows.hpp"
 
 namespace fbs {
 
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(64 * AUDIT_WAVES) void k_audit_wire(AuditWireArgs a
             const uint64_t w = ct[j];
             sum += ((a.sk[j >> 5] >> (j & 31u)) & 1u) ? w : 0;
         }
-        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+        sum = wave_sum(sum);
         if (lane == 0) {
             const uint64_t phase = fq_sub(ct[D], sum % FQ);
             const uint64_t want = (audit_message(a.expected[c], a.two_p) * a.delta) % FQ;   // < 2^13 2^46: no overflow
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(64 * AUDIT_WAVES) void k_audit_fields(AuditFieldArg
             const uint32_t f = row[i];
             sum += ((a.sk[i >> 5] >> (i & 31u)) & 1u) ? f : 0;
         }
-        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+        sum = wave_sum(sum);
         if (lane == 0) {
             const uint64_t ph = (row[a.n] - sum) & mask;                       // [0, 2N)
             const uint64_t two_n = (uint64_t)mask + 1, box = a.two_p * two_n;  // 4pN <= 2^13 2^13

@@ -22,23 +22,6 @@ namespace fbs {
 
 // ---------------------------------------------------------------------------------------------
 template <int LOGN, int LL>
-__global__ __launch_bounds__(1 << LL) void k_bsk_transform(const uint64_t *__restrict__ src, double *__restrict__ dst,
-                                                           const double *__restrict__ tw_fwd, double n_inv, size_t polys) {
-    using W = typename NttFor<LOGN, LL>::type;
-    __shared__ double lds[2 * W::N];
-    const uint32_t t = threadIdx.x;
-    typename W::Xchg xc{lds, 0};
-    for (size_t p = blockIdx.x; p < polys; p += gridDim.x) {   // uniform trip count per workgroup
-        double x[W::E];
-#pragma unroll
-        for (int m = 0; m < W::E; m++) x[m] = fp_from_u64(src[p * W::N + W::template index_of<0>(t, m)]);
-        W::forward(x, xc, t, Twiddles(tw_fwd + W::LANE_TABLE_OFFSET, tw_fwd));
-#pragma unroll
-        for (int m = 0; m < W::E; m++) dst[p * W::N + W::key_word(t, m)] = fp_center(fp_mulmod(x[m], n_inv));
-    }
-}
-
-template <int LOGN, int LL>
 __global__ __launch_bounds__(1 << LL) void k_polymul(const uint64_t *a, const uint64_t *b, uint64_t *c, const double *tw_fwd,
                                                      const double *tw_inv, double n_inv) {
     using W = typename NttFor<LOGN, LL>::type;
@@ -556,7 +539,7 @@ static int transform_bsk_t(fbs_ctx *ctx, const uint64_t *d_given) {
     if (e == hipSuccess) {
         const double n_inv = fq_centered(fq_inv(N));
         unsigned grid = (unsigned)std::min<size_t>(polys, 4096);
-        hipLaunchKernelGGL((k_bsk_transform<LOGN, LL>), dim3(grid), dim3(1 << LL), 0, ctx->stream, d_src,
+        hipLaunchKernelGGL((k_key_transform<LOGN, LL, KeyWords>), dim3(grid), dim3(1 << LL), 0, ctx->stream, KeyWords{d_src},
                            reinterpret_cast<double *>(ctx->d_bsk_hat), reinterpret_cast<const double *>(ctx->d_tw_fwd), n_inv,
                            polys);
         e = hipGetLastError();
@@ -564,7 +547,7 @@ static int transform_bsk_t(fbs_ctx *ctx, const uint64_t *d_given) {
         if (small_key_needed(ctx)) {
             if (e == hipSuccess && !ctx->d_bsk_hat_small) e = hipMalloc(&ctx->d_bsk_hat_small, polys * N * 8);
             if (e == hipSuccess) {
-                hipLaunchKernelGGL((k_bsk_transform<LOGN, LLS>), dim3(grid), dim3(1 << LLS), 0, ctx->stream, d_src,
+                hipLaunchKernelGGL((k_key_transform<LOGN, LLS, KeyWords>), dim3(grid), dim3(1 << LLS), 0, ctx->stream, KeyWords{d_src},
                                    reinterpret_cast<double *>(ctx->d_bsk_hat_small), reinterpret_cast<const double *>(ctx->d_tw_fwd),
                                    n_inv, polys);
                 e = hipGetLastError();

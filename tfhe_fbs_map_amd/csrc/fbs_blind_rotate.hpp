@@ -1,7 +1,8 @@
 // What the blind-rotation kernels of fbs_blind_rotate.hip, fbs_blind_rotate_cu.hip, fbs_blind_rotate_k2.hip and
 // fbs_blind_rotate_glwe.hip share: launch arguments, the issue-priority hand-over of the two waves of a SIMD, key words through
 // buffer loads, the frame of a kernel (which bootstrap a thread works on, the initial accumulator, the rounding constants, sample
-// extraction) and the launchers of the other three files.
+// extraction) and the launchers of the other three files; and the one-time transform of a key (k_key_transform), which
+// fbs_pack.hip and fbs_keygen.hip launch too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -174,6 +175,39 @@ __device__ __forceinline__ void br_extract(const BrArgs &a, const BrJob &job, co
         }
     } else if (t == 0) {
         out[(K1 - 1) * N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[job.table]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The one-time transform of a key: `polys` polynomials, coefficient domain -> transform domain, centred, x N^-1, in the register
+// order of the transform (key_word) -- the form every kernel multiplies by.  Src yields coefficient j of polynomial p:
+// KeyWords for a key of residues (the bootstrapping key, the packing key), KeyBits for a binary secret held as packed bits
+// (fbs_keygen.hip).  Workgroups stride over the polynomials.
+struct KeyWords {
+    const uint64_t *__restrict__ src;   // [polys][N]
+    __device__ __forceinline__ double coeff(size_t p, uint32_t n, uint32_t j) const { return fp_from_u64(src[p * n + j]); }
+};
+struct KeyBits {
+    const uint32_t *__restrict__ bits;  // bit p N + j; a secret has at most 4 polynomials: 32-bit indices
+    __device__ __forceinline__ double coeff(size_t p, uint32_t n, uint32_t j) const {
+        const uint32_t i = (uint32_t)p * n + j;
+        return ((bits[i >> 5] >> (i & 31u)) & 1u) ? 1.0 : 0.0;
+    }
+};
+template <int LOGN, int LL, class Src>
+__global__ __launch_bounds__(1 << LL) void k_key_transform(Src src, double *__restrict__ dst, const double *__restrict__ tw_fwd,
+                                                           double n_inv, size_t polys) {
+    using W = typename NttFor<LOGN, LL>::type;
+    __shared__ double lds[2 * W::N];
+    const uint32_t t = threadIdx.x;
+    typename W::Xchg xc{lds, 0};
+    for (size_t p = blockIdx.x; p < polys; p += gridDim.x) {   // uniform trip count per workgroup
+        double x[W::E];
+#pragma unroll
+        for (int m = 0; m < W::E; m++) x[m] = src.coeff(p, W::N, W::template index_of<0>(t, m));
+        W::forward(x, xc, t, Twiddles(tw_fwd + W::LANE_TABLE_OFFSET, tw_fwd));
+#pragma unroll
+        for (int m = 0; m < W::E; m++) dst[p * W::N + W::key_word(t, m)] = fp_center(fp_mulmod(x[m], n_inv));
     }
 }
 

@@ -22,7 +22,7 @@
 #include <algorithm>
 
 #include "fbs_compact.hpp"
-#include "fbs_internal.hpp"
+#include "fbs_rows.hpp"
 
 namespace fbs {
 
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void k_decrypt_compact(DecCompactAr
         uint32_t sum = 0;   // mod 2^32, hence mod 2^bits
         for (uint32_t i = lane; i < a.n; i += 64)
             if ((a.sk[i >> 5] >> (i & 31u)) & 1u) sum += compact_field(ct, i, a.bits);
-        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+        sum = wave_sum(sum);
         if (lane == 0) a.msgs[c] = compact_decode(compact_field(ct, a.n, a.bits), sum, a.bits, a.two_p);
     }
 }
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(64 * UNPACK_WAVES) void k_compact_unpack(UnpackArgs
             eps += (int64_t)x - ((int64_t)m << sh);
             row[i] = m & mask_b;
         }
-        for (int d = 32; d >= 1; d >>= 1) eps += __shfl_xor(eps, d);
+        eps = wave_sum(eps);
         if (lane == 0) row[a.n] = compact_reround_body(compact_field(ct, a.n, a.bits), eps, a.bits, sh) & mask_b;
     }
 }

@@ -77,6 +77,39 @@ int64_t noise_sample(const RandKey &seed, uint64_t stream, uint64_t idx, uint64_
     return sample_window(sampler, w, sigma);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The two samples everything here encrypts with (the device's frame of the first is fbs_rows.hpp, of the second k_glwe_key_rows).
+// An LWE row: mask_words, then lwe_body + the caller's message.  A GLWE zero sample: glwe_zero_sample, then the caller's message.
+// ---------------------------------------------------------------------------------------------
+void mask_words(const RandKey &key, uint64_t stream, uint64_t idx0, uint64_t *dst, size_t len) {
+    rand_words(key, stream, idx0, dst, len);
+    for (size_t i = 0; i < len; i++) dst[i] = fq_fold(dst[i]);
+}
+
+uint64_t lwe_body(const RandKey &noise_key, uint64_t noise_stream, uint64_t sigma, uint32_t sampler, const uint64_t *mask,
+                  const uint64_t *sk, size_t len) {
+    uint64_t b = fq_from_i64(noise_sample(noise_key, noise_stream, 0, sigma, sampler));
+    for (size_t i = 0; i < len; i++)
+        if (sk[i]) b = fq_add(b, mask[i]);
+    return b;
+}
+
+void add_times_key(uint64_t *acc, const uint64_t *a, const std::vector<uint32_t> &support, uint32_t N) {
+    for (uint32_t sh : support) {
+        for (uint32_t j = 0; j < N - sh; j++) acc[j + sh] = fq_add(acc[j + sh], a[j]);
+        for (uint32_t j = N - sh; j < N; j++) acc[j + sh - N] = fq_sub(acc[j + sh - N], a[j]);
+    }
+}
+
+void glwe_zero_sample(const RandKey &mask_key, uint64_t mask_stream, const RandKey &noise_key, uint64_t noise_stream, uint64_t sigma,
+                      uint32_t sampler, const std::vector<std::vector<uint32_t>> &support, uint32_t N, uint64_t *masks, uint64_t *body) {
+    for (uint32_t j = 0; j < N; j++) body[j] = fq_from_i64(noise_sample(noise_key, noise_stream, j, sigma, sampler));
+    for (size_t c = 0; c < support.size(); c++) {
+        mask_words(mask_key, mask_stream, c * N, masks + c * N, N);
+        add_times_key(body, masks + c * N, support[c], N);
+    }
+}
+
 const char *debug_gauss_refused(const void *words, size_t count, uint64_t sigma, const void *out) {
     if (count && (!words || !out)) return "debug_gauss: null array";
     if (count > ((size_t)1 << 26)) return "debug_gauss: too many windows";
@@ -180,14 +213,6 @@ static uint64_t ggsw_bit(const fbs_ctx *ctx, size_t g) {
     return g % 3 == 0 ? (s0 & (1 - s1)) : g % 3 == 1 ? ((1 - s0) & s1) : (s0 & s1);
 }
 
-// acc += a * S (negacyclic, binary S given by its support)
-static void add_times_key(uint64_t *acc, const uint64_t *a, const std::vector<uint32_t> &support, uint32_t N) {
-    for (uint32_t sh : support) {
-        for (uint32_t j = 0; j < N - sh; j++) acc[j + sh] = fq_add(acc[j + sh], a[j]);
-        for (uint32_t j = N - sh; j < N; j++) acc[j + sh - N] = fq_sub(acc[j + sh - N], a[j]);
-    }
-}
-
 void host_keygen(fbs_ctx *ctx) {
     const fbs_params &p = ctx->p;
     const uint32_t N = ctx->N, D = ctx->D, n = p.n, k = p.k, l = p.l_bsk, t = p.t_ksk, rows = ctx->rows;
@@ -196,43 +221,22 @@ void host_keygen(fbs_ctx *ctx) {
     const size_t row_words = (size_t)(k + 1) * N;
     ctx->bsk.assign(ctx->n_ggsw * rows * row_words, 0);
     parallel_for(ctx->n_ggsw * rows, [&](size_t r0, size_t r1) {
-        std::vector<uint64_t> prod(N);
         for (size_t r = r0; r < r1; r++) {
-            size_t i = r / rows;
-            uint32_t rr = (uint32_t)(r % rows), comp = rr / l, lv = rr % l;
+            const uint32_t rr = (uint32_t)(r % rows), comp = rr / l, lv = rr % l;
             uint64_t *row = ctx->bsk.data() + r * row_words;
-            uint64_t *body = row + (size_t)k * N;
-            for (uint32_t j = 0; j < N; j++)
-                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_BSK_NOISE, r), j, p.sigma_glwe, p.sampler));
-            for (uint32_t c = 0; c < k; c++) {
-                uint64_t *a = row + (size_t)c * N;
-                rand_words(ctx->rkey, stream_id(DOM_BSK_MASK, r), (uint64_t)c * N, a, N);
-                for (uint32_t j = 0; j < N; j++) a[j] = fq_fold(a[j]);
-                std::fill(prod.begin(), prod.end(), 0);
-                for (uint32_t sh : support[c]) {
-                    // prod += X^sh * a
-                    for (uint32_t j = 0; j < N - sh; j++) prod[j + sh] = fq_add(prod[j + sh], a[j]);
-                    for (uint32_t j = N - sh; j < N; j++) prod[j + sh - N] = fq_sub(prod[j + sh - N], a[j]);
-                }
-                for (uint32_t j = 0; j < N; j++) body[j] = fq_add(body[j], prod[j]);
-            }
-            if (ggsw_bit(ctx, i)) row[(size_t)comp * N] = fq_add(row[(size_t)comp * N], ctx->g[lv]);
+            glwe_zero_sample(ctx->rkey, stream_id(DOM_BSK_MASK, r), ctx->rkey, stream_id(DOM_BSK_NOISE, r), p.sigma_glwe, p.sampler,
+                             support, N, row, row + (size_t)k * N);
+            if (ggsw_bit(ctx, r / rows)) row[(size_t)comp * N] = fq_add(row[(size_t)comp * N], ctx->g[lv]);
         }
     });
 
     ctx->ksk.assign((size_t)D * t * (n + 1), 0);
     parallel_for((size_t)D * t, [&](size_t r0, size_t r1) {
         for (size_t r = r0; r < r1; r++) {
-            uint32_t j = (uint32_t)(r / t), v = (uint32_t)(r % t);
             uint64_t *row = ctx->ksk.data() + r * (n + 1);
-            rand_words(ctx->rkey, stream_id(DOM_KSK_MASK, r), 0, row, n);
-            uint64_t b = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_KSK_NOISE, r), 0, p.sigma_lwe, p.sampler));
-            for (uint32_t i = 0; i < n; i++) {
-                row[i] = fq_fold(row[i]);
-                if (ctx->sk_lwe[i]) b = fq_add(b, row[i]);
-            }
-            if (ctx->sk_glwe[j]) b = fq_add(b, ctx->h[v]);
-            row[n] = b;
+            mask_words(ctx->rkey, stream_id(DOM_KSK_MASK, r), 0, row, n);
+            row[n] = lwe_body(ctx->rkey, stream_id(DOM_KSK_NOISE, r), p.sigma_lwe, p.sampler, row, ctx->sk_lwe.data(), n);
+            if (ctx->sk_glwe[r / t]) row[n] = fq_add(row[n], ctx->h[r % t]);
         }
     });
 }
@@ -265,18 +269,13 @@ void host_keygen_seeded(fbs_ctx *ctx) {
     const std::vector<std::vector<uint32_t>> support = glwe_support(ctx);
     std::vector<uint64_t> bsk_bodies(ctx->n_ggsw * rows * N), ksk_bodies((size_t)D * t);
     parallel_for(ctx->n_ggsw * rows, [&](size_t r0, size_t r1) {
-        std::vector<uint64_t> a(N);
+        std::vector<uint64_t> a((size_t)k * N);
         for (size_t r = r0; r < r1; r++) {
             const size_t g = r / rows;
             const uint32_t rr = (uint32_t)(r % rows), comp = rr / l, lv = rr % l;
             uint64_t *body = bsk_bodies.data() + r * N;
-            for (uint32_t j = 0; j < N; j++)
-                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SBSK_NOISE, r), j, p.sigma_glwe, p.sampler));
-            for (uint32_t c = 0; c < k; c++) {
-                rand_words(ctx->mask_key, stream_id(DOM_SBSK_MASK, r), (uint64_t)c * N, a.data(), N);
-                for (uint32_t j = 0; j < N; j++) a[j] = fq_fold(a[j]);
-                add_times_key(body, a.data(), support[c], N);
-            }
+            glwe_zero_sample(ctx->mask_key, stream_id(DOM_SBSK_MASK, r), ctx->rkey, stream_id(DOM_SBSK_NOISE, r), p.sigma_glwe, p.sampler,
+                             support, N, a.data(), body);
             if (!ggsw_bit(ctx, g)) continue;
             if (comp == k) {
                 body[0] = fq_add(body[0], ctx->g[lv]);
@@ -288,13 +287,9 @@ void host_keygen_seeded(fbs_ctx *ctx) {
     parallel_for((size_t)D * t, [&](size_t r0, size_t r1) {
         std::vector<uint64_t> a(n);
         for (size_t r = r0; r < r1; r++) {
-            const uint32_t j = (uint32_t)(r / t), v = (uint32_t)(r % t);
-            rand_words(ctx->mask_key, stream_id(DOM_SKSK_MASK, r), 0, a.data(), n);
-            uint64_t b = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SKSK_NOISE, r), 0, p.sigma_lwe, p.sampler));
-            for (uint32_t i = 0; i < n; i++)
-                if (ctx->sk_lwe[i]) b = fq_add(b, fq_fold(a[i]));
-            if (ctx->sk_glwe[j]) b = fq_add(b, ctx->h[v]);
-            ksk_bodies[r] = b;
+            mask_words(ctx->mask_key, stream_id(DOM_SKSK_MASK, r), 0, a.data(), n);
+            ksk_bodies[r] = lwe_body(ctx->rkey, stream_id(DOM_SKSK_NOISE, r), p.sigma_lwe, p.sampler, a.data(), ctx->sk_lwe.data(), n);
+            if (ctx->sk_glwe[r / t]) ksk_bodies[r] = fq_add(ksk_bodies[r], ctx->h[r % t]);
         }
     });
     host_expand_seeded_keys(ctx, ctx->mask_key, bsk_bodies.data(), ksk_bodies.data(), ctx->bsk, ctx->ksk);
@@ -308,8 +303,7 @@ void host_expand_seeded_keys(const fbs_ctx *ctx, const RandKey &mask_key, const 
     parallel_for(ctx->n_ggsw * rows, [&](size_t r0, size_t r1) {
         for (size_t r = r0; r < r1; r++) {
             uint64_t *row = bsk.data() + r * row_words;
-            rand_words(mask_key, stream_id(DOM_SBSK_MASK, r), 0, row, (size_t)k * N);
-            for (size_t j = 0; j < (size_t)k * N; j++) row[j] = fq_fold(row[j]);
+            mask_words(mask_key, stream_id(DOM_SBSK_MASK, r), 0, row, (size_t)k * N);   // the k columns are one run of the stream
             std::memcpy(row + (size_t)k * N, bsk_bodies + r * N, (size_t)N * 8);
         }
     });
@@ -317,8 +311,7 @@ void host_expand_seeded_keys(const fbs_ctx *ctx, const RandKey &mask_key, const 
     parallel_for((size_t)D * t, [&](size_t r0, size_t r1) {
         for (size_t r = r0; r < r1; r++) {
             uint64_t *row = ksk.data() + r * (n + 1);
-            rand_words(mask_key, stream_id(DOM_SKSK_MASK, r), 0, row, n);
-            for (uint32_t i = 0; i < n; i++) row[i] = fq_fold(row[i]);
+            mask_words(mask_key, stream_id(DOM_SKSK_MASK, r), 0, row, n);
             row[n] = ksk_bodies[r];
         }
     });
@@ -330,10 +323,9 @@ void host_encrypt_seeded(const fbs_ctx *ctx, const int64_t *msgs, size_t count, 
     parallel_for(count, [&](size_t a, size_t b) {
         std::vector<uint64_t> mask(D);
         for (size_t i = a; i < b; i++) {
-            rand_words(ctx->mask_key, stream_id(DOM_SENC_MASK, nonce0 + i), 0, mask.data(), D);
-            uint64_t body = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_SENC_NOISE, nonce0 + i), 0, ctx->p.sigma_glwe, ctx->p.sampler));
-            for (uint32_t j = 0; j < D; j++)
-                if (ctx->sk_glwe[j]) body = fq_add(body, fq_fold(mask[j]));
+            mask_words(ctx->mask_key, stream_id(DOM_SENC_MASK, nonce0 + i), 0, mask.data(), D);
+            const uint64_t body = lwe_body(ctx->rkey, stream_id(DOM_SENC_NOISE, nonce0 + i), ctx->p.sigma_glwe, ctx->p.sampler, mask.data(),
+                                           ctx->sk_glwe.data(), D);
             bodies[i] = fq_add(body, fq_mul(fq_from_i64(msgs[i]), delta));
         }
     });
@@ -344,8 +336,7 @@ void host_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count
     parallel_for(count, [&](size_t a, size_t b) {
         for (size_t i = a; i < b; i++) {
             uint64_t *ct = cts + i * (D + 1);
-            rand_words(ctx->mask_key, stream_id(DOM_SENC_MASK, nonce0 + i), 0, ct, D);
-            for (uint32_t j = 0; j < D; j++) ct[j] = fq_fold(ct[j]);
+            mask_words(ctx->mask_key, stream_id(DOM_SENC_MASK, nonce0 + i), 0, ct, D);
             ct[D] = bodies[i];
         }
     });
@@ -413,12 +404,9 @@ void host_encrypt(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_
     parallel_for(count, [&](size_t a, size_t b) {
         for (size_t i = a; i < b; i++) {
             uint64_t *ct = cts + i * (D + 1);
-            rand_words(ctx->rkey, stream_id(DOM_ENC_MASK, nonce0 + i), 0, ct, D);
-            uint64_t body = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_ENC_NOISE, nonce0 + i), 0, ctx->p.sigma_glwe, ctx->p.sampler));
-            for (uint32_t j = 0; j < D; j++) {
-                ct[j] = fq_fold(ct[j]);
-                if (ctx->sk_glwe[j]) body = fq_add(body, ct[j]);
-            }
+            mask_words(ctx->rkey, stream_id(DOM_ENC_MASK, nonce0 + i), 0, ct, D);
+            const uint64_t body = lwe_body(ctx->rkey, stream_id(DOM_ENC_NOISE, nonce0 + i), ctx->p.sigma_glwe, ctx->p.sampler, ct,
+                                           ctx->sk_glwe.data(), D);
             ct[D] = fq_add(body, fq_mul(fq_from_i64(msgs[i]), delta));
         }
     });
@@ -469,17 +457,12 @@ void host_packing_keygen(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std
     const std::vector<std::vector<uint32_t>> support = glwe_support(ctx);
     bodies.assign((size_t)n * t_p * N, 0);
     parallel_for((size_t)n * t_p, [&](size_t r0, size_t r1) {
-        std::vector<uint64_t> a(N);
+        std::vector<uint64_t> a((size_t)k * N);
         for (size_t r = r0; r < r1; r++) {
             const uint32_t i = (uint32_t)(r / t_p), v = (uint32_t)(r % t_p);
             uint64_t *body = bodies.data() + r * N;
-            for (uint32_t j = 0; j < N; j++)
-                body[j] = fq_from_i64(noise_sample(ctx->rkey, stream_id(DOM_PACK_NOISE, r), j, ctx->p.sigma_glwe, ctx->p.sampler));
-            for (uint32_t c = 0; c < k; c++) {
-                rand_words(ctx->mask_key, stream_id(DOM_PACK_MASK, r), (uint64_t)c * N, a.data(), N);
-                for (uint32_t j = 0; j < N; j++) a[j] = fq_fold(a[j]);
-                add_times_key(body, a.data(), support[c], N);
-            }
+            glwe_zero_sample(ctx->mask_key, stream_id(DOM_PACK_MASK, r), ctx->rkey, stream_id(DOM_PACK_NOISE, r), ctx->p.sigma_glwe,
+                             ctx->p.sampler, support, N, a.data(), body);
             if (ctx->sk_lwe[i]) body[0] = fq_add(body[0], pack_gadget(gamma_p, v));
         }
     });
@@ -492,8 +475,7 @@ void host_expand_packing_key(const fbs_ctx *ctx, const RandKey &mask_key, uint32
     parallel_for((size_t)n * t_p, [&](size_t r0, size_t r1) {
         for (size_t r = r0; r < r1; r++) {
             uint64_t *row = full.data() + r * row_words;
-            rand_words(mask_key, stream_id(DOM_PACK_MASK, r), 0, row, (size_t)k * N);
-            for (size_t j = 0; j < (size_t)k * N; j++) row[j] = fq_fold(row[j]);
+            mask_words(mask_key, stream_id(DOM_PACK_MASK, r), 0, row, (size_t)k * N);
             std::memcpy(row + (size_t)k * N, bodies + r * N, (size_t)N * 8);
         }
     });

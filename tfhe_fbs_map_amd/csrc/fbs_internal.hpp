@@ -51,6 +51,17 @@ RandKey rand_key_derive(const uint8_t seed[32], const fbs_params &p);
 void rand_words(const RandKey &key, uint64_t stream, uint64_t idx0, uint64_t *dst, size_t count);
 // `sampler`: fbs_params.sampler of the context the draw belongs to (fbs_sampler.hpp)
 int64_t noise_sample(const RandKey &key, uint64_t stream, uint64_t idx, uint64_t sigma, uint32_t sampler = 0);
+// The two samples every key and ciphertext is made of (fbs_host.cpp); a caller adds its message.
+// mask_words: dst[i] = fold(word idx0 + i of (key, stream)), i < len.  lwe_body: noise sample 0 + sum_{sk_i = 1} mask_i.
+void mask_words(const RandKey &key, uint64_t stream, uint64_t idx0, uint64_t *dst, size_t len);
+uint64_t lwe_body(const RandKey &noise_key, uint64_t noise_stream, uint64_t sigma, uint32_t sampler, const uint64_t *mask,
+                  const uint64_t *sk, size_t len);
+// acc += a * S (negacyclic, S binary, given by its support)
+void add_times_key(uint64_t *acc, const uint64_t *a, const std::vector<uint32_t> &support, uint32_t N);
+// GLWE zero sample under the key of k = support.size() polynomials: masks [k][N], column c = mask_words at c N (the caller's row,
+// or scratch when only the body is kept); body [N] = noise samples 0 .. N - 1 + sum_c A_c S_c
+void glwe_zero_sample(const RandKey &mask_key, uint64_t mask_stream, const RandKey &noise_key, uint64_t noise_stream, uint64_t sigma,
+                      uint32_t sampler, const std::vector<std::vector<uint32_t>> &support, uint32_t N, uint64_t *masks, uint64_t *body);
 // test hooks of the rounded Gaussian (fbs_debug_gauss, fbs_debug_gauss_dev): what both refuse (null: nothing), and the host loop
 const char *debug_gauss_refused(const void *words, size_t count, uint64_t sigma, const void *out);
 void host_debug_gauss(const uint64_t *words, size_t count, uint64_t sigma, int64_t *out);

@@ -3,31 +3,26 @@
 //   k_encrypt   word for word what host_encrypt (fbs_host.cpp) writes: the same ChaCha20 streams (fbs_chacha.hpp), the same
 //               folds, the same body
 //   k_decrypt   round(phase * 2p / q) mod 2p, what host_decrypt returns
-//   k_encrypt_seeded   the body of host_encrypt_seeded: k_encrypt's sum over the mask of the seeded stream under the public mask
-//               key, noise and message; only the body is stored
+//   k_encrypt_seeded   the body of host_encrypt_seeded: the mask of the seeded stream under the public mask key is summed, not
+//               stored; noise and message under the context's key
 //   k_debug_gauss      the rounded Gaussian alone on windows of words a test supplies (fbs_debug_gauss_dev)
 //   k_expand_seeded    host_expand_seeded: the mask of the seeded stream under the mask key, then the given body.  No key-selected
 //               sum: the kernel needs no secret, and is what an evaluation-only context runs on its inputs
 //
-// One wave per ciphertext.  A lane makes one 64-byte ChaCha block of the mask (8 words) per iteration and stores it with
-// 16-byte stores, consecutive lanes on consecutive blocks; its key-selected words go into a 64-bit sum (D folded words stay
-// below D 2^46 <= 2^58), which the wave adds up and reduces once.  These kernels are not blind-rotation or key-switch
-// launches: they are not in fbs_kernel_catalog and the profile does not count them.
+// One wave per ciphertext, on the frame of fbs_rows.hpp (lwe_mask_row, lwe_noise); a kernel adds its addressing and its message.
+// These kernels are not blind-rotation or key-switch launches: they are not in fbs_kernel_catalog and the profile does not count
+// them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "fbs_chacha.hpp"
-#include "fbs_sampler.hpp"
-#include "fbs_internal.hpp"
+#include "fbs_rows.hpp"
 
 namespace fbs {
 
 constexpr uint32_t IO_WAVES = 4;              // waves (ciphertexts in flight) per workgroup
 constexpr uint32_t IO_MAX_BLOCKS = 1u << 16;  // grid cap; the waves stride over the rest
 constexpr uint32_t IO_NO_SLOT = 0xFFFFFFFFu;
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
 struct EncArgs {
     IoView v;
@@ -46,51 +41,17 @@ struct DecArgs {
     uint64_t two_p;
 };
 
-__device__ __forceinline__ uint64_t wave_sum(uint64_t x) {
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-    return x;
-}
-
 __global__ __launch_bounds__(64 * IO_WAVES) void k_encrypt(EncArgs a) {
-    const uint32_t lane = threadIdx.x & 63u, D = a.D, blocks = (D + 7) / 8;
+    const uint32_t lane = threadIdx.x & 63u, D = a.D;
     const size_t total = a.v.rows * a.v.per_row;
     for (size_t c = (size_t)blockIdx.x * IO_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * IO_WAVES) {   // wave-uniform
         const size_t r = c / a.v.per_row, s = c - r * a.v.per_row;
         const size_t slot = a.v.row_slot ? a.v.row_slot[r] : r;
         uint64_t *ct = a.v.cts + (slot * a.v.ct_stride + s) * (D + 1);
         const uint64_t nonce = a.nonce0 + r * a.nonce_stride + s;
-        const uint64_t stream = stream_id(DOM_ENC_MASK, nonce);
-        uint64_t sum = 0;
-        for (uint32_t b = lane; b < blocks; b += 64) {
-            uint64_t w[8];
-            chacha_block(a.key.w, stream, b, w);                     // mask words 8b .. 8b + 7
-            const uint32_t bits = (a.sk[b >> 2] >> (8 * (b & 3))) & 0xFFu;
-            for (int i = 0; i < 8; i++) {
-                w[i] = fq_fold(w[i]);
-                sum += ((bits >> i) & 1u) ? w[i] : 0;
-            }
-            uint64_t *p = ct + 8 * (size_t)b;
-            if (8 * b + 8 <= D) {
-                // D + 1 is odd: every other ciphertext starts on an odd word, and so do all of its blocks (the branch is uniform)
-                if (((uintptr_t)p & 15u) == 0) {
-                    for (int i = 0; i < 8; i += 2) *reinterpret_cast<u64x2 *>(p + i) = u64x2{w[i], w[i + 1]};
-                } else {
-                    p[0] = w[0];
-                    for (int i = 1; i < 7; i += 2) *reinterpret_cast<u64x2 *>(p + i) = u64x2{w[i], w[i + 1]};
-                    p[7] = w[7];
-                }
-            } else {
-                for (uint32_t i = 0; 8 * b + i < D; i++) p[i] = w[i];   // D % 8 != 0: the last, partial block
-            }
-        }
-        sum = wave_sum(sum);
+        const uint64_t sum = wave_sum(lwe_mask_row<true>(a.key, stream_id(DOM_ENC_MASK, nonce), D, ct, a.sk, lane));
         if (lane == 63) {   // (the lane with the least mask work when the blocks do not fill the last round)
-            uint64_t body = sum % FQ;
-            if (a.sigma) {
-                uint64_t w[8];
-                chacha_block(a.key.w, stream_id(DOM_ENC_NOISE, nonce), 0, w);   // noise_sample(.., idx 0, ..): words 0 .. 5
-                body = fq_add(body, fq_from_i64(sample_window(a.sampler, w, a.sigma)));
-            }
+            const uint64_t body = fq_add(sum % FQ, lwe_noise(a.key, stream_id(DOM_ENC_NOISE, nonce), a.sampler, a.sigma));
             const int64_t m = a.v.msgs[r * a.v.msg_stride + s];
             ct[D] = fq_add(body, fq_mul(fq_from_i64(m), a.delta));
         }
@@ -139,57 +100,26 @@ struct ExpandArgs {
 };
 
 __global__ __launch_bounds__(64 * IO_WAVES) void k_encrypt_seeded(SeededEncArgs a) {
-    const uint32_t lane = threadIdx.x & 63u, D = a.D, blocks = (D + 7) / 8;
+    const uint32_t lane = threadIdx.x & 63u;
     for (size_t c = (size_t)blockIdx.x * IO_WAVES + threadIdx.x / 64; c < a.count; c += (size_t)gridDim.x * IO_WAVES) {   // wave-uniform
         const uint64_t nonce = a.nonce0 + c;
-        const uint64_t stream = stream_id(DOM_SENC_MASK, nonce);
-        uint64_t sum = 0;
-        for (uint32_t b = lane; b < blocks; b += 64) {
-            uint64_t w[8];
-            chacha_block(a.mask_key.w, stream, b, w);                // mask words 8b .. 8b + 7
-            const uint32_t bits = (a.sk[b >> 2] >> (8 * (b & 3))) & 0xFFu;   // (bits past D are zero in the packed key)
-            for (int i = 0; i < 8; i++) sum += ((bits >> i) & 1u) ? fq_fold(w[i]) : 0;
-        }
-        sum = wave_sum(sum);
+        const uint64_t sum = wave_sum(lwe_mask_row<false>(a.mask_key, stream_id(DOM_SENC_MASK, nonce), a.D, nullptr, a.sk, lane));
         if (lane == 63) {
-            uint64_t body = sum % FQ;
-            if (a.sigma) {
-                uint64_t w[8];
-                chacha_block(a.key.w, stream_id(DOM_SENC_NOISE, nonce), 0, w);
-                body = fq_add(body, fq_from_i64(sample_window(a.sampler, w, a.sigma)));
-            }
+            const uint64_t body = fq_add(sum % FQ, lwe_noise(a.key, stream_id(DOM_SENC_NOISE, nonce), a.sampler, a.sigma));
             a.bodies[c] = fq_add(body, fq_mul(fq_from_i64(a.msgs[c]), a.delta));
         }
     }
 }
 
 __global__ __launch_bounds__(64 * IO_WAVES) void k_expand_seeded(ExpandArgs a) {
-    const uint32_t lane = threadIdx.x & 63u, D = a.D, blocks = (D + 7) / 8;
+    const uint32_t lane = threadIdx.x & 63u, D = a.D;
     const size_t total = a.v.rows * a.v.per_row;
     const uint64_t *bodies = reinterpret_cast<const uint64_t *>(a.v.msgs);
     for (size_t c = (size_t)blockIdx.x * IO_WAVES + threadIdx.x / 64; c < total; c += (size_t)gridDim.x * IO_WAVES) {   // wave-uniform
         const size_t r = c / a.v.per_row, s = c - r * a.v.per_row;
         const size_t slot = a.v.row_slot ? a.v.row_slot[r] : r;
         uint64_t *ct = a.v.cts + (slot * a.v.ct_stride + s) * (D + 1);
-        const uint64_t stream = stream_id(DOM_SENC_MASK, a.nonce0 + r * a.nonce_stride + s);
-        for (uint32_t b = lane; b < blocks; b += 64) {
-            uint64_t w[8];
-            chacha_block(a.mask_key.w, stream, b, w);
-            for (int i = 0; i < 8; i++) w[i] = fq_fold(w[i]);
-            uint64_t *p = ct + 8 * (size_t)b;
-            if (8 * b + 8 <= D) {
-                // D + 1 is odd: every other ciphertext starts on an odd word, and so do all of its blocks (the branch is uniform)
-                if (((uintptr_t)p & 15u) == 0) {
-                    for (int i = 0; i < 8; i += 2) *reinterpret_cast<u64x2 *>(p + i) = u64x2{w[i], w[i + 1]};
-                } else {
-                    p[0] = w[0];
-                    for (int i = 1; i < 7; i += 2) *reinterpret_cast<u64x2 *>(p + i) = u64x2{w[i], w[i + 1]};
-                    p[7] = w[7];
-                }
-            } else {
-                for (uint32_t i = 0; 8 * b + i < D; i++) p[i] = w[i];   // D % 8 != 0: the last, partial block
-            }
-        }
+        lwe_mask_row<true>(a.mask_key, stream_id(DOM_SENC_MASK, a.nonce0 + r * a.nonce_stride + s), D, ct, nullptr, lane);
         if (lane == 63) ct[D] = bodies[r * a.v.msg_stride + s];
     }
 }

@@ -15,7 +15,7 @@
 #include <cstdlib>
 
 #include "fbs_gate.hpp"
-#include "fbs_internal.hpp"
+#include "fbs_rows.hpp"
 
 namespace fbs {
 
@@ -547,8 +547,7 @@ __global__ __launch_bounds__(256) void k_ks_gemm_finish(KsArgs a, KsGemm g, size
             const uint64_t body = col == g.n ? ks_in(a.gv, f, a.ct_words)[g.D] : 0;
             ms_store(a, f, col, fq_sub(body, sum), &eps);
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) eps += __shfl_xor(eps, d);
+        eps = wave_sum(eps);
         if (lane == 0) ms_flush(a, f, eps);
     }
 }

@@ -3,13 +3,13 @@
 // streams (fbs_chacha.hpp), the same folds, the same sampler (fbs_sampler.hpp), and the negacyclic product by the secret as an
 // exact product of transforms (k_polymul's arithmetic: every value a residue, so the words do not depend on how it is computed).
 //
-//   k_secret_transform   the k polynomials of the GLWE secret, from its packed bits, in the form k_bsk_transform writes (centred,
-//                        x N^-1, key_word order): once per call, into a buffer the caller zeroes and frees before it returns
+//   k_key_transform<.., KeyBits>   (fbs_blind_rotate.hpp) the k polynomials of the GLWE secret, from its packed bits, in the form
+//                        the bootstrapping key's transform has: once per call, into a buffer the caller zeroes and frees before it returns
 //   k_glwe_key_rows      one GLWE key row per workgroup on the lanes of one polynomial (NttFor<LOGN, lanes_log2_for(LOGN)>): the
 //                        mask columns from their stream (a lane makes whole 64-byte blocks), the body = sum_c A_c S_c + e + message.
 //                        The transform's exchange buffer stages the mask words on their way into the lanes' registers and, after
 //                        the inverse transform, the noise samples (four samples are exactly three blocks)
-//   k_lwe_key_rows       one wave per key-switching row, the structure of k_encrypt (fbs_io.hip)
+//   k_lwe_key_rows       one wave per key-switching row, on the frame of fbs_rows.hpp
 //
 // Rows leave in the standard coefficient layout of fbs_key_sizes.  None of these is a key-switch or blind-rotation launch: they
 // are not in fbs_kernel_catalog and the profile does not count them.
@@ -18,13 +18,10 @@
 #include <algorithm>
 
 #include "fbs_blind_rotate.hpp"
-#include "fbs_chacha.hpp"
 #include "fbs_pack.hpp"
-#include "fbs_sampler.hpp"
+#include "fbs_rows.hpp"
 
 namespace fbs {
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
 // what a row of k_glwe_key_rows carries
 enum KeyRowsMode : uint32_t {
@@ -40,7 +37,7 @@ constexpr uint32_t LWE_ROWS_WAVES = 4;           // key-switching rows in flight
 struct GlweRowsArgs {
     uint64_t *dst;             // rows [n_rows][k + 1][N]; ROWS_PACK: bodies [n_rows][N]
     const uint64_t *bodies;    // ROWS_EXPAND: [n_rows][N]
-    const double *s_hat;       // [k][N] the secret's transforms (k_secret_transform)
+    const double *s_hat;       // [k][N] the secret's transforms (launch_secret_transform)
     const double *tw_fwd, *tw_inv;
     const uint32_t *sk_glwe_bits, *sk_lwe_bits;
     RandKey mask_key, noise_key;
@@ -70,22 +67,6 @@ __device__ __forceinline__ bool ggsw_bit_dev(const uint32_t *sk_lwe_bits, uint32
     if (group != 2) return packed_bit(sk_lwe_bits, g);
     const bool s0 = packed_bit(sk_lwe_bits, 2 * (g / 3)), s1 = packed_bit(sk_lwe_bits, 2 * (g / 3) + 1);
     return g % 3 == 0 ? (s0 && !s1) : g % 3 == 1 ? (!s0 && s1) : (s0 && s1);
-}
-
-template <int LOGN, int LL>
-__global__ __launch_bounds__(1 << LL) void k_secret_transform(const uint32_t *__restrict__ sk_bits, double *__restrict__ dst,
-                                                              const double *__restrict__ tw_fwd, double n_inv) {
-    using W = typename NttFor<LOGN, LL>::type;
-    __shared__ double lds[2 * W::N];
-    const uint32_t t = threadIdx.x;
-    const size_t p = blockIdx.x;   // one workgroup per key polynomial
-    typename W::Xchg xc{lds, 0};
-    double x[W::E];
-#pragma unroll
-    for (int m = 0; m < W::E; m++) x[m] = packed_bit(sk_bits, p * W::N + W::template index_of<0>(t, m)) ? 1.0 : 0.0;
-    W::forward(x, xc, t, Twiddles(tw_fwd + W::LANE_TABLE_OFFSET, tw_fwd));
-#pragma unroll
-    for (int m = 0; m < W::E; m++) dst[p * W::N + W::key_word(t, m)] = fp_center(fp_mulmod(x[m], n_inv));
 }
 
 template <int LOGN, int LL>
@@ -184,54 +165,21 @@ __global__ __launch_bounds__(1 << LL) void k_glwe_key_rows(GlweRowsArgs a) {
     }
 }
 
-__device__ __forceinline__ uint64_t key_rows_wave_sum(uint64_t x) {
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-    return x;
-}
-
 __global__ __launch_bounds__(64 * LWE_ROWS_WAVES) void k_lwe_key_rows(LweRowsArgs a) {
-    const uint32_t lane = threadIdx.x & 63u, n = a.n, blocks = (n + 7) / 8;
+    const uint32_t lane = threadIdx.x & 63u, n = a.n;
     for (size_t r = (size_t)blockIdx.x * LWE_ROWS_WAVES + threadIdx.x / 64; r < a.n_rows; r += (size_t)gridDim.x * LWE_ROWS_WAVES) {   // wave-uniform
         uint64_t *row = a.dst + r * (size_t)(n + 1);
-        const uint64_t stream = stream_id(a.mask_dom, r);
-        uint64_t sum = 0;   // n folded words stay below n 2^46
-        for (uint32_t b = lane; b < blocks; b += 64) {
-            uint64_t w[8];
-            chacha_block(a.mask_key.w, stream, b, w);   // mask words 8b .. 8b + 7
-            uint32_t bits = 0;                          // (bits past n are zero in the packed key)
-            if (!a.bodies) bits = (a.sk_lwe_bits[b >> 2] >> (8 * (b & 3))) & 0xFFu;
-            for (int i = 0; i < 8; i++) {
-                w[i] = fq_fold(w[i]);
-                sum += ((bits >> i) & 1u) ? w[i] : 0;
-            }
-            uint64_t *p = row + 8 * (size_t)b;
-            if (8 * b + 8 <= n) {
-                // rows of n + 1 words: with n even every other row starts on an odd word, and so do all of its blocks (the branch is uniform)
-                if (((uintptr_t)p & 15u) == 0) {
-                    for (int i = 0; i < 8; i += 2) *reinterpret_cast<u64x2 *>(p + i) = u64x2{w[i], w[i + 1]};
-                } else {
-                    p[0] = w[0];
-                    for (int i = 1; i < 7; i += 2) *reinterpret_cast<u64x2 *>(p + i) = u64x2{w[i], w[i + 1]};
-                    p[7] = w[7];
-                }
-            } else {
-                for (uint32_t i = 0; 8 * b + i < n; i++) p[i] = w[i];   // n % 8 != 0: the last, partial block
-            }
-        }
+        // n is any number: the one caller of the frame whose rows end in a partial block
+        uint64_t sum = lwe_mask_row<true>(a.mask_key, stream_id(a.mask_dom, r), n, row, a.bodies ? nullptr : a.sk_lwe_bits, lane);
         if (a.bodies) {
             if (lane == 63) row[n] = a.bodies[r];
             continue;
         }
-        sum = key_rows_wave_sum(sum);
+        sum = wave_sum(sum);
         if (lane == 63) {   // (the lane with the least mask work when the blocks do not fill the last round)
             const size_t j = r / a.t;
             const uint32_t v = (uint32_t)(r % a.t);
-            uint64_t body = sum % FQ;
-            if (a.sigma) {
-                uint64_t w[8];
-                chacha_block(a.noise_key.w, stream_id(a.noise_dom, r), 0, w);   // noise_sample(.., idx 0, ..): words 0 .. 5
-                body = fq_add(body, fq_from_i64(sample_window(a.sampler, w, a.sigma)));
-            }
+            uint64_t body = fq_add(sum % FQ, lwe_noise(a.noise_key, stream_id(a.noise_dom, r), a.sampler, a.sigma));
             if (packed_bit(a.sk_glwe_bits, j)) body = fq_add(body, a.h[v]);
             row[n] = body;
         }
@@ -263,8 +211,8 @@ static int launch_secret_transform(fbs_ctx *ctx, DevBuf &s_hat) {
     switch (ctx->p.log_n_poly) {
 #define X(L)                                                                                                                    \
     case L:                                                                                                                     \
-        hipLaunchKernelGGL((k_secret_transform<L, lanes_log2_for(L)>), dim3(k), dim3(1 << lanes_log2_for(L)), 0, ctx->stream,   \
-                           ctx->d_sk_bits, s_hat.as<double>(), twf, n_inv);                                                     \
+        hipLaunchKernelGGL((k_key_transform<L, lanes_log2_for(L), KeyBits>), dim3(k), dim3(1 << lanes_log2_for(L)), 0, ctx->stream, \
+                           KeyBits{ctx->d_sk_bits}, s_hat.as<double>(), twf, n_inv, (size_t)k);   /* one workgroup per polynomial */ \
         break;
         FBS_FOR_EACH_SHAPE(X)
 #undef X

@@ -2,8 +2,8 @@
 // coefficients of one GLWE sample under the big key -- a packing key switch on the transforms of fbs_ntt*.hpp and the FP64 field
 // of fbs_field.hpp (no new arithmetic: every product is fp_mulmod, every sum an exact integer-valued double).
 //
-//   k_pack_key_transform   the packing key [n][t_p][k+1][N], coefficient domain -> transform domain, centred, x N^-1, in the
-//                          register order of the transform (key_word): once per key, as the bootstrapping key is transformed.
+//   k_key_transform        (fbs_blind_rotate.hpp) the packing key [n][t_p][k+1][N], coefficient domain -> transform domain: once
+//                          per key, the kernel that transforms the bootstrapping key.
 //   k_pack_transpose       the switched fields of a pass, [ciphertext][n + 1] as the key switch leaves them, -> [n + 1][samples N]:
 //                          a digit polynomial D_(i,v) is a COLUMN of the first matrix and a contiguous row segment of the second.
 //                          64 x 64 tiles through LDS, coalesced 4-byte loads and stores both ways.  The mask fields are rounded to
@@ -33,23 +33,6 @@ namespace fbs {
 
 constexpr uint32_t PACK_MAX_SLICES = 32;   // partial sums of centred residues: 32 x q/2 stays far below 2^52
 constexpr uint32_t PACK_CENTRE_EVERY = 16; // lazy accumulators: 16 products below 0.8 q on top of q/2
-
-template <int LOGN, int LL>
-__global__ __launch_bounds__(1 << LL) void k_pack_key_transform(const uint64_t *__restrict__ src, double *__restrict__ dst,
-                                                                const double *__restrict__ tw_fwd, double n_inv, size_t polys) {
-    using W = typename NttFor<LOGN, LL>::type;
-    __shared__ double lds[2 * W::N];
-    const uint32_t t = threadIdx.x;
-    typename W::Xchg xc{lds, 0};
-    for (size_t p = blockIdx.x; p < polys; p += gridDim.x) {   // uniform trip count per workgroup
-        double x[W::E];
-#pragma unroll
-        for (int m = 0; m < W::E; m++) x[m] = fp_from_u64(src[p * W::N + W::template index_of<0>(t, m)]);
-        W::forward(x, xc, t, Twiddles(tw_fwd + W::LANE_TABLE_OFFSET, tw_fwd));
-#pragma unroll
-        for (int m = 0; m < W::E; m++) dst[p * W::N + W::key_word(t, m)] = fp_center(fp_mulmod(x[m], n_inv));
-    }
-}
 
 // ms [count][n1] -> out [n1][cols], cols = samples * N a multiple of 64; grid (ceil(n1 / 64), cols / 64), 256 threads
 __global__ __launch_bounds__(256) void k_pack_transpose(const uint32_t *__restrict__ ms, uint32_t n1, size_t count, uint32_t cols,
@@ -221,8 +204,9 @@ int dev_upload_packing_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint
         switch (ctx->p.log_n_poly) {
 #define X(L)                                                                                                                    \
     case L:                                                                                                                     \
-        hipLaunchKernelGGL((k_pack_key_transform<L, lanes_log2_for(L)>), dim3(grid), dim3(1 << lanes_log2_for(L)), 0, ctx->stream, \
-                           d_src, ctx->d_pack_key, reinterpret_cast<const double *>(ctx->d_tw_fwd), n_inv, polys);              \
+        hipLaunchKernelGGL((k_key_transform<L, lanes_log2_for(L), KeyWords>), dim3(grid), dim3(1 << lanes_log2_for(L)), 0,     \
+                           ctx->stream, KeyWords{d_src}, ctx->d_pack_key, reinterpret_cast<const double *>(ctx->d_tw_fwd), n_inv, \
+                           polys);                                                                                              \
         launched = true;                                                                                                        \
         break;
             X(8) X(9) X(10) X(11) X(12)

@@ -8,7 +8,7 @@
 //   encryption     sample nu: u_r from the bits of stream (DOM_PUB_ENC_U, nu), e_c = samples c N .. of stream (DOM_PUB_ENC_NOISE, nu),
 //                  both under the encryptor's key; A'_c = sum_r u_r A[r][c] + e_c, B' = sum_r u_r P_r + e_k + Delta M
 //   expansion      word c N + i of message t's ciphertext = A'_c[t - i] (i <= t), -A'_c[N + t - i] (i > t); word k N = B'[t]
-// Every product is by a binary polynomial: a signed sum of shifted copies (add_times_bits), as the key generation does it.
+// Every product is by a binary polynomial: a signed sum of shifted copies (add_times_key, fbs_host.cpp), as the key generation does it.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -89,19 +89,7 @@ RandKey key_of_bytes(const uint8_t b[32]) {
 // A[r][c] for r, c < k -> a [k][k][N]
 void draw_masks(const RandKey &mask_key, uint32_t k, uint32_t N, std::vector<uint64_t> &a) {
     a.resize((size_t)k * k * N);
-    for (uint32_t r = 0; r < k; r++) {
-        uint64_t *row = a.data() + (size_t)r * k * N;
-        rand_words(mask_key, stream_id(DOM_PUB_MASK, r), 0, row, (size_t)k * N);
-        for (size_t j = 0; j < (size_t)k * N; j++) row[j] = fq_fold(row[j]);
-    }
-}
-
-// acc += a * u (negacyclic), u binary, given by its support
-void add_times_bits(uint64_t *acc, const uint64_t *a, const std::vector<uint32_t> &support, uint32_t N) {
-    for (uint32_t sh : support) {
-        for (uint32_t j = 0; j < N - sh; j++) acc[j + sh] = fq_add(acc[j + sh], a[j]);
-        for (uint32_t j = N - sh; j < N; j++) acc[j + sh - N] = fq_sub(acc[j + sh - N], a[j]);
-    }
+    for (uint32_t r = 0; r < k; r++) mask_words(mask_key, stream_id(DOM_PUB_MASK, r), 0, a.data() + (size_t)r * k * N, (size_t)k * N);
 }
 
 size_t samples_of(size_t count, uint32_t N) { return count / N + (count % N ? 1 : 0); }
@@ -140,8 +128,8 @@ void pub_encrypt(const fbs_pub *pub, const int64_t *msgs, size_t count, uint64_t
         for (size_t i = 0; i < D + N; i++)
             out[i] = fq_from_i64(noise_sample(pub->key, stream_id(DOM_PUB_ENC_NOISE, nu), i, pub->p.sigma_glwe, pub->p.sampler));
         for (uint32_t r = 0; r < k; r++) {
-            for (uint32_t c = 0; c < k; c++) add_times_bits(out + (size_t)c * N, pub->a.data() + ((size_t)r * k + c) * N, support[r], N);
-            add_times_bits(out + D, pub->bodies.data() + (size_t)r * N, support[r], N);
+            for (uint32_t c = 0; c < k; c++) add_times_key(out + (size_t)c * N, pub->a.data() + ((size_t)r * k + c) * N, support[r], N);
+            add_times_key(out + D, pub->bodies.data() + (size_t)r * N, support[r], N);
         }
         const size_t fill = std::min<size_t>(N, count - g * N);
         for (size_t j = 0; j < fill; j++) out[D + j] = fq_add(out[D + j], fq_mul((uint64_t)msgs[g * N + j], pub->delta));
@@ -172,14 +160,11 @@ int fbs_pub_keygen(const fbs_params *p, const uint8_t mask_key[32], const uint64
             if (bit > 1) return pub_fail(nullptr, FBS_E_INVALID, "secret keys are binary");
             if (bit) support[c].push_back(j);
         }
-    std::vector<uint64_t> a, out((size_t)k * N);
-    draw_masks(key_of_bytes(mask_key), k, N, a);
-    const RandKey noise = key_of_bytes(noise_seed);
-    for (uint32_t r = 0; r < k; r++) {
-        uint64_t *body = out.data() + (size_t)r * N;
-        for (uint32_t j = 0; j < N; j++) body[j] = fq_from_i64(noise_sample(noise, stream_id(DOM_PUB_NOISE, r), j, p->sigma_glwe, p->sampler));
-        for (uint32_t c = 0; c < k; c++) add_times_bits(body, a.data() + ((size_t)r * k + c) * N, support[c], N);
-    }
+    std::vector<uint64_t> a((size_t)k * N), out((size_t)k * N);
+    const RandKey masks = key_of_bytes(mask_key), noise = key_of_bytes(noise_seed);
+    for (uint32_t r = 0; r < k; r++)   // row r: a GLWE zero sample; only its body travels
+        glwe_zero_sample(masks, stream_id(DOM_PUB_MASK, r), noise, stream_id(DOM_PUB_NOISE, r), p->sigma_glwe, p->sampler, support, N,
+                         a.data(), out.data() + (size_t)r * N);
     std::memcpy(bodies, out.data(), out.size() * 8);
     for (auto &s : support) std::fill(s.begin(), s.end(), 0u);   // (the secret's positions do not stay in freed memory)
     return FBS_OK;

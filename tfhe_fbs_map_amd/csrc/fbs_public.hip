@@ -15,15 +15,13 @@
 
 #include <algorithm>
 
-#include "fbs_internal.hpp"
+#include "fbs_rows.hpp"
 
 namespace fbs {
 
 constexpr uint32_t PX_WAVES = 4;              // waves per workgroup
 constexpr uint32_t PX_ROWS = 16;              // coefficients (ciphertexts) of one sample per workgroup; divides every N
 constexpr uint32_t PX_MAX_BLOCKS = 1u << 16;  // grid cap; the workgroups stride over the rest
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
 struct PubExpand {
     const uint64_t *glwe;   // [ceil(count / N)][k + 1][N]

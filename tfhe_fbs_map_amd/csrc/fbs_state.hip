@@ -23,14 +23,12 @@
 
 #include <algorithm>
 
-#include "fbs_internal.hpp"
+#include "fbs_rows.hpp"
 
 namespace fbs {
 
 constexpr uint32_t ST_WAVES = 4;              // waves (ciphertexts in flight) per workgroup
 constexpr uint32_t ST_MAX_BLOCKS = 1u << 16;  // grid cap; the waves stride over the rest
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
 // `words` words (odd: D + 1) from src to dst, both 8-byte aligned, by the 64 lanes of one wave
 __device__ __forceinline__ void wave_copy_ct(uint64_t *dst, const uint64_t *src, uint32_t words, uint32_t lane) {
