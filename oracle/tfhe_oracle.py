@@ -186,6 +186,13 @@ class Oracle:
         lib().orc_blind_rotate(self._h, ms.ctypes.data, tv.ctypes.data, acc.ctypes.data)
         return acc
 
+    def sample_extract(self, acc, post_add=0):
+        """coefficient 0 of the accumulator `blind_rotate` left, as a big-key ciphertext, post_add more on the body"""
+        acc = _c(acc, np.uint64)
+        out = np.empty(self.ctw, np.uint64)
+        lib().orc_sample_extract(self._h, acc.ctypes.data, post_add, out.ctypes.data)
+        return out
+
     # ---- several tables on one blind rotation (multi-value bootstrap, see tfhe_oracle.c) ----
     def tv0(self):
         tv = np.empty(self.N, np.uint64)

@@ -171,6 +171,8 @@ def recipe(name):
     if m:
         L, nl, first = int(m.group(1)), int(m.group(2)), int(m.group(3))
         beta = {2: 7, 1: 9, 0: 10}[first]
+        if nl == 1 and first == 0:                        # any beta > 9 reaches FIRST = 0: one level of 20 bits is a usable gadget,
+            beta = 20                                     # one of 10 is not (tests/test_gpu_rotation_amounts.py decrypts its outputs)
         if nl * beta > 30:
             beta = 30 // nl
         if m.group(4):                                    # two workgroups per CU: between one and two bootstraps per CU
@@ -1142,3 +1144,132 @@ def decode_case_batches(cases, sk, bits, two_p, pack, chunk=8192):
             yield name, words, [decode_phase(b, mask_sum, bits, two_p) for b in part]
     rows = cases["random"]
     yield "random", pack(np.array(rows, dtype=np.uint64), bits), [decode_definition(r, sk, bits, two_p) for r in rows]
+
+
+# ==== planted rotation amounts for every blind-rotation kernel (tests/test_rotation_amounts_reference.py, ==========================
+# ==== tests/test_gpu_rotation_amounts.py) ==========================================================================================
+# At bits = log2(2N) fbs_refresh_compact_dev unpacks its fields, unrounded, into the rows the blind rotation reads: the n + 1 fields of
+# a row ARE the rotation amounts of its n steps and of the accumulator's start.  The rows below choose them: every step-skipping
+# pattern (a step whose amounts are all zero is skipped) against every edge amount, on honest keys.
+PLANTED_STEPS = 16
+PLANTED_P = 7
+PLANTED_ROWS = 60                                                       # 5 mask lists x 12 bodies: row j = (list j % 5, body j // 5)
+PLANTED_DEFAULT_KNOBS = dict(br_cu_kernel=1, br_cu_lean=1, br_k2_shape=0, br_glwe_fpw=0)   # (Tune, csrc/fbs_internal.hpp)
+# the families of the CPU test: name -> parameter set (the gadgets of the toy sets above and of `recipe`)
+PLANTED_FAMILIES = {
+    "k1_n1024_g1": dict(log_n_poly=10, k=1, l_bsk=3, beta_bsk=7, bsk_group=1),
+    "k1_n2048_g2": dict(log_n_poly=11, k=1, l_bsk=1, beta_bsk=20, bsk_group=2),
+    "k2_n1024_g2": dict(log_n_poly=10, k=2, l_bsk=1, beta_bsk=20, bsk_group=2),
+    "k3_n512_g2": dict(log_n_poly=9, k=3, l_bsk=1, beta_bsk=18, bsk_group=2),
+    "k4_n256_g2": dict(log_n_poly=8, k=4, l_bsk=2, beta_bsk=8, bsk_group=2),
+}
+
+
+def planted_set(log_n_poly, k, l_bsk, beta_bsk, bsk_group, n=PLANTED_STEPS):
+    """the full parameter dict (what Oracle and Params take) of a planted-amounts case: the set tests/test_gpu_dispatch.py makes
+    of a recipe, at n steps"""
+    return dict(n=n, log_n_poly=log_n_poly, k=k, l_bsk=l_bsk, beta_bsk=beta_bsk, t_ksk=4, gamma_ksk=4 if log_n_poly < 12 else 3,
+                p_msg=PLANTED_P, sigma_lwe=1 << 6, sigma_glwe=1 << 4, bsk_group=bsk_group)
+
+
+def planted_edges(N, group):
+    """the edge set: amounts E of a step of one key bit; pairs P (e0, e1) of a step of two, x = 5 and y = N + 7"""
+    if group == 1:
+        return [1, 2, 63, 64, 65, N // 2, N - 1, N, N + 1, 3 * N // 2, 2 * N - 2, 2 * N - 1]
+    x, y, M = 5, N + 7, 2 * N
+    return [(0, x), (x, 0), (x, M - x), (N, N), (N, 0), (0, N), (1, M - 1), (M - 1, M - 1), (N - 1, 1), (N, 1), (1, 1), (M - 2, 3),
+            (y, M - y), (63, 65), (64, N - 64)]
+
+
+def step_properties(amounts, N):
+    """what the amounts of ONE step hit, as a set of names.  One key bit: 'odd', 'even', 'e == N'.  Two: the same of each of e0, e1
+    and e2 = (e0 + e1) mod 2N that is not zero, and 'e2 == 0, parts non-zero', 'e2 == N', 'wrapped sum' (e0 + e1 > 2N),
+    'one part zero'"""
+    es = [int(a) for a in amounts]
+    hits = set()
+    if len(es) == 2:
+        e0, e1 = es
+        es = [e0, e1, (e0 + e1) % (2 * N)]
+        if e0 and e1 and es[2] == 0:
+            hits.add("e2 == 0, parts non-zero")
+        if es[2] == N:
+            hits.add("e2 == N")
+        if e0 + e1 > 2 * N:
+            hits.add("wrapped sum")
+        if (e0 == 0) != (e1 == 0):
+            hits.add("one part zero")
+    for e in es:
+        if e:
+            hits.add("odd" if e & 1 else "even")
+            if e == N:
+                hits.add("e == N")
+    return hits
+
+
+def planted_mask_lists(N, n, group):
+    """the five lists of n amounts: L0 skips its even steps (the first among them), L1 its odd steps (the last among them), L2 all but
+    the middle one, L3 and L4 none.  A step is `group` amounts; the steps that run walk the edge set, each list from where the one
+    before stopped (L3, L4, L0, L1, L2 in that order), so that n / group >= 6 steps cover it."""
+    edges = planted_edges(N, group)
+    steps = n // group
+    assert n % group == 0 and steps % 2 == 0
+    zero = 0 if group == 1 else (0, 0)
+    at = [0]
+
+    def walk():
+        at[0] += 1
+        return edges[(at[0] - 1) % len(edges)]
+    L3 = [walk() for _ in range(steps)]
+    L4 = [walk() for _ in range(steps)]
+    L0 = [walk() if i % 2 else zero for i in range(steps)]
+    L1 = [zero if i % 2 else walk() for i in range(steps)]
+    L2 = [walk() if i == steps // 2 else zero for i in range(steps)]
+    lists = [L0, L1, L2, L3, L4]
+    return lists if group == 1 else [[e for pair in lst for e in pair] for lst in lists]
+
+
+def planted_amount_rows(N, n, group, sk_lwe, p, turn=0):
+    """-> (fields uint32 [60][n + 1], meta).  Row j: mask list j % 5 (planted_mask_lists), body j // 5.  Bodies 0 .. 6 are SEMANTIC:
+    m_n = (<mask, sk_lwe> + round(msg N / p) + off) mod 2N for msg = body, so that the rotation through the identity table decrypts
+    to msg; off is 0, +(N / 2p - 2), -(N / 2p - 2) in turn by row, from row `turn` on (either edge of the message's slot, two short of it:
+    turn = 0, 1, 2 give every row every off).  Bodies 7 .. 11 are RAW: m_n = 0, 1, N - 1, N, 2N - 1.
+    meta: dict(lists=[dict(amounts, skipped, hits)] per list -- skipped: its steps whose amounts are all zero; hits: the union of
+    step_properties over its steps --, msg=[the message of a semantic row, -1 for a raw one] per row)"""
+    lists = planted_mask_lists(N, n, group)
+    sk = [int(s) for s in sk_lwe]
+    assert len(sk) == n and len(lists) == 5
+    edge = N // (2 * p) - 2
+    raw = [0, 1, N - 1, N, 2 * N - 1]
+    assert PLANTED_ROWS == 5 * (p + len(raw)) and edge > 0
+    fields = np.zeros((PLANTED_ROWS, n + 1), np.uint32)
+    msg = []
+    for j in range(PLANTED_ROWS):
+        mask, body = lists[j % 5], j // 5
+        fields[j, :n] = mask
+        if body < p:
+            off = (0, edge, -edge)[(j + turn) % 3]
+            fields[j, n] = (sum(m for m, s in zip(mask, sk) if s) + (2 * body * N + p) // (2 * p) + off) % (2 * N)
+            msg.append(body)
+        else:
+            fields[j, n] = raw[body - p]
+            msg.append(-1)
+    meta_lists = []
+    for lst in lists:
+        steps = [lst[i:i + group] for i in range(0, n, group)]
+        meta_lists.append(dict(amounts=list(lst), skipped=[i for i, s in enumerate(steps) if not any(s)],
+                               hits=set().union(*(step_properties(s, N) for s in steps))))
+    return fields, dict(lists=meta_lists, msg=msg)
+
+
+def planted_output_margin(prm):
+    """standard deviations between a bootstrap output's phase and the edge of its box, q / 4p over the blind rotation's own noise
+    (params.variances: the planted fields carry no noise of their own, and neither key switch nor modulus switch runs).  Six
+    instantiations, k_blind_rotate_cu<L,1,1> and <L,1,2>, are by their template arguments ONE gadget level of at most 9 and 7 bits: no
+    gadget that reaches them is a usable parameter set (0.2 to 1 sigma at N >= 1024, the reference itself decrypts many rows wrongly
+    there); they are compared word for word only."""
+    from tfhe_fbs_map_amd import Params
+    from tfhe_fbs_map_amd.params import variances
+    return (1.0 / (4.0 * prm["p_msg"])) / math.sqrt(variances(Params(**prm))[0])
+
+
+PLANTED_MARGIN = 6.0                                                    # the margin the selector asks of a usable set (params.py)

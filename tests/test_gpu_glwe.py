@@ -36,7 +36,10 @@ SHAPES = [  # (log_n, k, l, beta, key bits per step)
 def test_ragged_batches_bit_exact(nat, log_n, k, l, beta, group):
     """Batches that are not multiples of a workgroup's bootstraps, all three table modes and a multi-valued table, a trivial ciphertext
     (every step skipped: the other bootstraps of its workgroup still meet their barriers) and maximal residues: every output word equal
-    to the oracle's, at one to four gadget levels, with one and with two key bits per step."""
+    to the oracle's, at one to four gadget levels, with one and with two key bits per step.  Two more ciphertexts have words of their
+    big-key mask zeroed; that skips NO step (the rotation amounts are made after the key switch and the modulus switch, which mix every
+    mask word into every amount): they are two more ordinary inputs.  Steps skipped one by one -- first, last, every other, all but
+    one -- are in tests/test_gpu_rotation_amounts.py, which plants the amounts themselves."""
     prm = toy(log_n_poly=log_n, k=k, l_bsk=l, beta_bsk=beta, bsk_group=group)
     ctx, o = nat.Context(prm, seed=4), orc.Oracle(prm, seed=4)
     tv = ctx.tvset(TABLES)
@@ -50,7 +53,9 @@ def test_ragged_batches_bit_exact(nat, log_n, k, l, beta, group):
         if B > 2:
             cts[B - 1, :-1] = 0
             cts[B // 2, :] = orc.Q - 1
-            # every other step skipped (both rotation amounts of the pair zero): the landing sets take turns by the steps EXECUTED
+            # words of the big-key mask zeroed, at the indices an interleaved skip pattern of the small key would have.  This zeroes no
+            # rotation amount (at k = 3, N = 512, two levels of 9 bits, two key bits per step and B = 5 the oracle's amounts at these
+            # positions are 8, 820, 254, 349, 966 and 27): kept as recorded inputs; interleaved skips run in tests/test_gpu_rotation_amounts.py
             n = prm.n
             skip = np.arange(n).reshape(-1, 2)[1::2].reshape(-1) if group == 2 else np.arange(1, n, 2)
             cts[0, skip] = 0
