@@ -788,6 +788,12 @@ int fbs_debug_field(fbs_ctx *ctx, int op, const int64_t *x, const int64_t *w, si
  * the same words.  libfbsexec.so only. */
 int fbs_debug_gauss(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint64_t sigma, int64_t *out);
 int fbs_debug_gauss_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint64_t sigma, int64_t *d_out, void *stream);
+/* The packing kernels alone (steps 2 - 5 and the transport of "packed outputs"), on fields a test supplies -- mask fields no key
+ * switch under seeded keys can be made to give: d_fields [count][n + 1] uint32 below 2^31 (device), laid out as step 1 leaves them,
+ * -> d_words [fbs_packed_words], asynchronous on `stream`.  No key switch, so a packing key is all it needs; rows past `count` are
+ * not read.  Refuses what fbs_pack_dev refuses and, with FBS_E_INVALID, more than one pass of it (max(8192, the modulus-switch
+ * scratch) ciphertexts, cut down to whole samples).  libfbsexec.so only (tests/test_gpu_pack_shapes.py). */
+int fbs_debug_pack_fields_dev(fbs_ctx *ctx, const uint32_t *d_fields, size_t count, uint32_t bits, uint64_t *d_words, void *stream);
 /* Static text, no GPU needed: one line per transform variant some blind-rotation kernel instantiates, made from the lists the
  * kernels are instantiated from:
  *   "class=<PolyNtt|SplitNtt|WavesNtt|LaneNtt256|LaneNtt512> logn=<log2 N> lanes=<threads per polynomial> dir=forward first=<FIRST>[ np=<NP>]"

@@ -1273,3 +1273,196 @@ def planted_output_margin(prm):
 
 
 PLANTED_MARGIN = 6.0                                                    # the margin the selector asks of a usable set (params.py)
+
+
+# ---- packed outputs: the definition restated, its fast form, the shapes and the planted fields -------------------------------------
+# (include/fbs_exec.h, "packed outputs", steps 2 - 5 and the transport; tests/test_packed_reference.py holds these helpers to their
+# claims without a GPU, tests/test_gpu_pack_shapes.py and tests/test_gpu_packed.py hold the kernels of csrc/fbs_pack.hip to them)
+PACK_SHAPES = [(8, 1), (9, 1), (10, 1), (11, 1), (12, 1),               # (log N, k): what FBS_PACK_SHAPES instantiates, restated
+               (8, 2), (8, 3), (8, 4), (9, 2), (9, 3), (9, 4), (10, 2), (10, 3)]
+PACK_BODY_FIELDS = (0, 1, 1 << 30, (1 << 31) - 1, 2114, 2115)           # 2114 < 2^30 / 507903 < 2115: pack_lift_body's floor term
+PACK_KEYS = ((3, 10), (1, 27))                                          # n t_p = 18 > 16 centres the lazy sums, 6 does not; the shipped digit
+PACK_EDGE_KEYS = ((1, 31), (31, 1), (2, 15))                            # r = 0 and the widest digit; r = 0 and the most levels; r = 1
+_PACK_ACC = {}
+
+
+def pack_toy(log_n, k, n, p=3):
+    """the smallest parameter set of a packing shape: the toy recipes of the packed and GLWE tests, and at k = 1, N = 2048 / 4096 the
+    gadgets of tests/test_gpu_device_keys.py"""
+    from tfhe_fbs_map_amd import Params
+    if k == 1:
+        l, beta = {11: (2, 14), 12: (1, 21)}.get(log_n, (2, 10))
+        return Params(n=n, log_n_poly=log_n, k=1, l_bsk=l, beta_bsk=beta, t_ksk=8, gamma_ksk=2, p_msg=p, sigma_lwe=1 << 8, sigma_glwe=4)
+    return Params(n=n, log_n_poly=log_n, k=k, l_bsk=1, beta_bsk=21 if k == 2 else 18, t_ksk=8, gamma_ksk=2, p_msg=p,
+                  sigma_lwe=1 << 8, sigma_glwe=4, bsk_group=2)
+
+
+def balanced_digits(a, t, gamma):
+    """a' [..] -> digits [t][..], v = 0 the most significant; carries upwards, the carry out of the top dropped"""
+    a = np.asarray(a, np.int64)
+    B = 1 << gamma
+    out = np.zeros((t,) + a.shape, np.int64)
+    carry = np.zeros(a.shape, np.int64)
+    for v in range(t - 1, -1, -1):
+        u = ((a >> (gamma * (t - 1 - v))) & (B - 1)) + carry
+        carry = (u >= B // 2).astype(np.int64)
+        out[v] = u - carry * B
+    return out
+
+
+def rounded_mask_fields(m, t, gamma):
+    """mask fields at 31 bits -> a' at t gamma bits (step 2)"""
+    m = np.asarray(m, np.int64)
+    r = 31 - t * gamma
+    return (((m >> (r - 1)) + 1) >> 1) % (1 << (t * gamma)) if r > 0 else m
+
+
+def negacyclic(d, a):
+    """d (small signed integers) times a (canonical residues): rotations when d is sparse, else the oracle's schoolbook product"""
+    from oracle import tfhe_oracle as orc
+    N = len(a)
+    nz = np.flatnonzero(d)
+    if nz.size <= 4:
+        acc = [0] * N
+        for j in nz:
+            for i in range(N):
+                s = int(d[j]) * int(a[i])
+                if i + j < N:
+                    acc[i + j] += s
+                else:
+                    acc[i + j - N] -= s
+        return np.array([x % Q for x in acc], np.uint64)
+    return orc.polymul_schoolbook(np.array([int(x) % Q for x in d], np.uint64), a)
+
+
+def sample_residues(fields, key, t, gamma, tag, fast=False):
+    """fields [fill][n+1] at 31 bits -> the k + 1 polynomials of the packed sample mod q (steps 2 - 5); `tag` names the key (the
+    memo is per key, digits and fields).  fast: every product D_(i,v) times a key polynomial by the oracle's NTT, the digits taken
+    mod q -- the same residues (tests/test_packed_reference.py), milliseconds where the schoolbook product takes seconds"""
+    memo = (tag, t, gamma, fast, fields.tobytes())
+    if memo in _PACK_ACC:
+        return _PACK_ACC[memo]
+    fill, n = fields.shape[0], fields.shape[1] - 1
+    k1, N = key.shape[2], key.shape[3]
+    digits = balanced_digits(rounded_mask_fields(fields[:, :n], t, gamma), t, gamma)                 # [t][fill][n]
+    acc = np.zeros((k1, N), np.uint64)
+    if fast:
+        from oracle import tfhe_oracle as orc
+        residues = np.mod(digits, Q).astype(np.uint64)
+    for i in range(n):
+        for v in range(t):
+            if fast:
+                d = np.zeros(N, np.uint64)
+                d[:fill] = residues[v, :, i]
+            else:
+                d = np.zeros(N, np.int64)
+                d[:fill] = digits[v, :, i]
+            for c in range(k1):
+                prod = orc.polymul_ntt(d, key[i, v, c]) if fast else negacyclic(d, key[i, v, c])
+                acc[c] = (acc[c] + prod) % np.uint64(Q)
+    res = (np.uint64(Q) - acc) % np.uint64(Q)
+    for j in range(fill):
+        res[k1 - 1, j] = (int(res[k1 - 1, j]) + ((int(fields[j, n]) * Q + (1 << 30)) >> 31)) % Q
+    _PACK_ACC[memo] = res
+    return res
+
+
+def packed_sample_count(k, N, fill, bits):
+    """words of a packed sample that holds `fill` outputs, restated"""
+    return k * N * bits // 64 + -(-fill * bits // 64)
+
+
+def packed_count(k, N, count, bits):
+    """words of a batch of `count` outputs: full samples, then the rest"""
+    return count // N * packed_sample_count(k, N, N, bits) + (packed_sample_count(k, N, count % N, bits) if count % N else 0)
+
+
+def reference_pack(fields, key, t, gamma, bits, tag, fast=False):
+    """fields [count][n+1] -> the packed words of the batch (transport rounding and format).  fast: `sample_residues`' fast form,
+    and the bit stream made from its bits with numpy instead of one long integer"""
+    k1, N = key.shape[2], key.shape[3]
+    words = []
+    for g0 in range(0, fields.shape[0], N):
+        part = fields[g0:g0 + N]
+        res = sample_residues(part, key, t, gamma, tag, fast)
+        rounded = (((res >> np.uint64(45 - bits)) + np.uint64(1)) >> np.uint64(1)) & np.uint64((1 << bits) - 1)
+        n_words = packed_sample_count(k1 - 1, N, part.shape[0], bits)
+        if fast:
+            flat = np.concatenate([rounded[:k1 - 1].reshape(-1), rounded[k1 - 1, :part.shape[0]]])
+            stream = ((flat[:, None] >> np.arange(bits, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(np.uint8).reshape(-1)
+            stream = np.concatenate([stream, np.zeros(64 * n_words - stream.size, np.uint8)])
+            words += [int(w) for w in np.packbits(stream, bitorder="little").view("<u8")]
+            continue
+        flat = [int(x) for c in range(k1 - 1) for x in rounded[c]] + [int(x) for x in rounded[k1 - 1, :part.shape[0]]]
+        stream = 0
+        for idx, f in enumerate(flat):
+            stream |= f << (idx * bits)
+        words += [(stream >> (64 * j)) & (2 ** 64 - 1) for j in range(n_words)]
+    return np.array(words, np.uint64)
+
+
+def decode_phases(words, prm, count, bits, sk_glwe):
+    """packed words -> phases [count] mod 2^bits (numpy restatement of the decode)"""
+    N, k = prm.N, prm.k
+    full = (k + 1) * N * bits // 64
+    S = np.asarray(sk_glwe, np.int64).reshape(k, N)
+    out = []
+    for g in range(-(-count // N)):
+        fill = min(N, count - g * N)
+        sample = words[g * full:]
+        stream = 0
+        n_words = k * N * bits // 64 + -(-fill * bits // 64)
+        for j in range(n_words):
+            stream |= int(sample[j]) << (64 * j)
+        f = np.array([(stream >> (i * bits)) & ((1 << bits) - 1) for i in range(k * N + fill)], np.int64)
+        phase = np.zeros(N, np.int64)
+        phase[:fill] = f[k * N:]
+        for c in range(k):
+            full_conv = np.convolve(f[c * N:(c + 1) * N], S[c])
+            prod = full_conv[:N].copy()
+            prod[:N - 1] -= full_conv[N:]
+            phase -= prod
+        out.append(phase[:fill] % (1 << bits))
+    return np.concatenate(out)
+
+
+def planted_mask_fields(t, gamma):
+    """{name: a mask field at 31 bits} for a packing key (t, gamma), r = 31 - t gamma: the edges of pack_round_mask and of the
+    balanced digits that random words do not reach.  A field a' << r rounds to a'.
+      zero, ones        0, and 2^31 - 1: rounds up to 2^(t gamma) and wraps to 0 when r > 0 (at r = 0 it is a' itself)
+      tie, below_tie    2^(r-1) -> 1 and 2^(r-1) - 1 -> 0, when r > 0
+      all_low           a' = -offs mod 2^(t gamma), offs = B/2 at every position: every digit -B/2.  As an unsigned number that is
+                        the lowest gamma bits B/2 and every higher group B/2 - 1: the carry that starts at the bottom, runs through
+                        every level and is dropped at the top -- one value under both descriptions
+      all_high          every digit B/2 - 1
+      top_half          a' = 2^(t gamma - 1): the top digit alone is -B/2 (and the carry dropped); all_low itself at t = 1"""
+    tg, r, B = t * gamma, 31 - t * gamma, 1 << gamma
+    offs = sum((B // 2) << (gamma * v) for v in range(t))
+    out = {"zero": 0, "ones": (1 << 31) - 1, "all_low": ((-offs) % (1 << tg)) << r, "all_high": ((1 << tg) - 1 - offs) << r,
+           "top_half": (1 << (tg - 1)) << r}
+    if r > 0:
+        out.update(tie=1 << (r - 1), below_tie=(1 << (r - 1)) - 1)
+    return out
+
+
+def planted_positions(count):
+    """the ciphertext positions the planted mask fields are spread over: the first two and the last two"""
+    return sorted({j for j in (0, 1, count - 2, count - 1) if 0 <= j < count})
+
+
+def planted_pack_fields(n, count, t_p, gamma_p, seed):
+    """[count][n + 1] uint32 below 2^31, as the key switch of fbs_pack_dev leaves them: random fields; in every mask column the
+    values of `planted_mask_fields` in turn over `planted_positions` (column i starts where column i - 1 stopped, so that n = 6
+    columns of four positions hold every value); in the body column PACK_BODY_FIELDS over the first and the last three positions"""
+    rng = np.random.default_rng(seed)
+    fields = rng.integers(0, 1 << 31, (count, n + 1), dtype=np.uint32)
+    values = list(planted_mask_fields(t_p, gamma_p).values())
+    turn = 0
+    for i in range(n):
+        for j in planted_positions(count):
+            fields[j, i] = values[turn % len(values)]
+            turn += 1
+    spots = sorted({j for j in (0, 1, 2, count - 3, count - 2, count - 1) if 0 <= j < count})
+    for s, j in enumerate(spots):
+        fields[j, n] = PACK_BODY_FIELDS[s % len(PACK_BODY_FIELDS)]
+    return fields

@@ -1,13 +1,13 @@
-"""Packed outputs on the GPU (include/fbs_exec.h, "packed outputs"): fbs_pack_dev is, word for word, the definition restated here in
-numpy on the oracle's schoolbook products, whatever the number of slices; the rows of the packing key decrypt to s_i h_v within the
-sampler's bound; an evaluation-only context with the imported bodies packs the same words; fbs_decrypt_packed recovers bootstrap
+"""Packed outputs on the GPU (include/fbs_exec.h, "packed outputs"): fbs_pack_dev is, word for word, the definition restated in
+numpy (tests/helpers.py) on the oracle's schoolbook products, whatever the number of slices; the rows of the packing key decrypt
+to s_i h_v within the sampler's bound; an evaluation-only context with the imported bodies packs the same words; fbs_decrypt_packed recovers bootstrap
 outputs at every width and fbs_state_fetch_packed is fbs_pack_dev of the full fetch; a Client / Server pair runs a golden program
 end to end; the phase noise is what params.packed_output_variance says; and what is refused is refused with nothing written."""
 import numpy as np
 import pytest
 
 from oracle import tfhe_oracle as orc
-from tests.helpers import assert_outputs_equal, load_fixture, subsample
+from tests.helpers import assert_outputs_equal, decode_phases, load_fixture, reference_pack, subsample
 from tests.test_gpu_compact import compact_on_device, unpack
 from tests.test_gpu_device_io import dev, host
 
@@ -18,7 +18,6 @@ E_INVALID, E_STATE = -1, -3
 PACK_SETS = {"k1_n256": (1, 8, 24), "k2_n256": (2, 8, 24), "k3_n512": (3, 9, 24), "k1_n1024": (1, 10, 16)}
 PACK_KEYS = ((1, 8), (2, 7), (3, 10))
 _CTX = {}
-_ACC = {}
 
 
 def toy(k, log_n, n, p=3):
@@ -48,104 +47,6 @@ def planted_cts(prm, count, seed):
     cts[min(1, count - 1), -1] = 0
     cts[count - 1, -2] = Q - 1
     return cts
-
-
-# ---- the definition, restated -------------------------------------------------------------------------------------------------
-def balanced_digits(a, t, gamma):
-    """a' [..] -> digits [t][..], v = 0 the most significant; carries upwards, the carry out of the top dropped"""
-    a = np.asarray(a, np.int64)
-    B = 1 << gamma
-    out = np.zeros((t,) + a.shape, np.int64)
-    carry = np.zeros(a.shape, np.int64)
-    for v in range(t - 1, -1, -1):
-        u = ((a >> (gamma * (t - 1 - v))) & (B - 1)) + carry
-        carry = (u >= B // 2).astype(np.int64)
-        out[v] = u - carry * B
-    return out
-
-
-def negacyclic(d, a):
-    """d (small signed integers) times a (canonical residues): rotations when d is sparse, else the oracle's schoolbook product"""
-    N = len(a)
-    nz = np.flatnonzero(d)
-    if nz.size <= 4:
-        acc = [0] * N
-        for j in nz:
-            for i in range(N):
-                s = int(d[j]) * int(a[i])
-                if i + j < N:
-                    acc[i + j] += s
-                else:
-                    acc[i + j - N] -= s
-        return np.array([x % Q for x in acc], np.uint64)
-    return orc.polymul_schoolbook(np.array([int(x) % Q for x in d], np.uint64), a)
-
-
-def sample_residues(fields, key, t, gamma, tag):
-    """fields [fill][n+1] at 31 bits -> the k + 1 polynomials of the packed sample mod q (steps 2 - 5)"""
-    memo = (tag, t, gamma, fields.tobytes())
-    if memo in _ACC:
-        return _ACC[memo]
-    fill, n = fields.shape[0], fields.shape[1] - 1
-    k1, N = key.shape[2], key.shape[3]
-    r = 31 - t * gamma
-    m = fields[:, :n].astype(np.int64)
-    a = (((m >> (r - 1)) + 1) >> 1) % (1 << (t * gamma)) if r > 0 else m
-    digits = balanced_digits(a, t, gamma)                       # [t][fill][n]
-    acc = np.zeros((k1, N), np.uint64)
-    for i in range(n):
-        for v in range(t):
-            d = np.zeros(N, np.int64)
-            d[:fill] = digits[v, :, i]
-            for c in range(k1):
-                acc[c] = (acc[c] + negacyclic(d, key[i, v, c])) % np.uint64(Q)
-    res = (np.uint64(Q) - acc) % np.uint64(Q)
-    for j in range(fill):
-        res[k1 - 1, j] = (int(res[k1 - 1, j]) + ((int(fields[j, n]) * Q + (1 << 30)) >> 31)) % Q
-    _ACC[memo] = res
-    return res
-
-
-def reference_pack(fields, key, t, gamma, bits, tag):
-    """fields [count][n+1] -> the packed words of the batch (transport rounding and format)"""
-    k1, N = key.shape[2], key.shape[3]
-    words = []
-    for g0 in range(0, fields.shape[0], N):
-        part = fields[g0:g0 + N]
-        res = sample_residues(part, key, t, gamma, tag)
-        rounded = (((res >> np.uint64(45 - bits)) + np.uint64(1)) >> np.uint64(1)) & np.uint64((1 << bits) - 1)
-        flat = [int(x) for c in range(k1 - 1) for x in rounded[c]] + [int(x) for x in rounded[k1 - 1, :part.shape[0]]]
-        stream = 0
-        for idx, f in enumerate(flat):
-            stream |= f << (idx * bits)
-        n_words = (k1 - 1) * N * bits // 64 + -(-part.shape[0] * bits // 64)
-        words += [(stream >> (64 * j)) & (2 ** 64 - 1) for j in range(n_words)]
-    return np.array(words, np.uint64)
-
-
-def decode_phases(words, prm, count, bits, sk_glwe):
-    """packed words -> phases [count] mod 2^bits (numpy restatement of the decode)"""
-    N, k = prm.N, prm.k
-    full = (k + 1) * N * bits // 64
-    S = np.asarray(sk_glwe, np.int64).reshape(k, N)
-    out = []
-    for g in range(-(-count // N)):
-        fill = min(N, count - g * N)
-        sample = words[g * full:]
-        stream = 0
-        n_words = k * N * bits // 64 + -(-fill * bits // 64)
-        for j in range(n_words):
-            stream |= int(sample[j]) << (64 * j)
-        f = np.array([(stream >> (i * bits)) & ((1 << bits) - 1) for i in range(k * N + fill)], np.int64)
-        phase = np.zeros(N, np.int64)
-        phase[:fill] = f[k * N:]
-        for c in range(k):
-            full_conv = np.convolve(f[c * N:(c + 1) * N], S[c])
-            prod = full_conv[:N].copy()
-            prod[:N - 1] -= full_conv[N:]
-            phase -= prod
-        out.append(phase[:fill] % (1 << bits))
-    return np.concatenate(out)
 
 
 # ---- 1. word for word ------------------------------------------------------------------------------------------------------------

@@ -162,6 +162,7 @@ def _load():
         "fbs_debug_field": (i32, [vp, i32, vp, vp, sz, vp]),
         "fbs_debug_gauss": (i32, [vp, vp, sz, u64, vp]),
         "fbs_debug_gauss_dev": (i32, [vp, vp, sz, u64, vp, vp]),
+        "fbs_debug_pack_fields_dev": (i32, [vp, vp, sz, u32, vp, vp]),
         "fbs_debug_transform_list": (C.c_char_p, []),
         "fbs_debug_transform": (i32, [vp, C.c_char_p, vp, vp, sz]),
         "fbs_searcher_create": (i32, [i32, C.POINTER(vp)]),
@@ -188,7 +189,7 @@ EXPORTED_SYMBOLS = (
     "fbs_searcher_create", "fbs_searcher_destroy", "fbs_searcher_last_error", "fbs_searcher_last_kernel_ms",
     "fbs_search_lincomb_coefs", "fbs_eval", "fbs_eval_dev", "fbs_eval_messages", "fbs_program_layout", "fbs_program_level", "fbs_program_io_slots",
     "fbs_level_lincomb_dev", "fbs_level_bootstrap_dev", "fbs_level_scatter_dev", "fbs_profile_enable", "fbs_profile_kernel", "fbs_kernel_catalog", "fbs_profile_kernels", "fbs_profile_read", "fbs_sync", "fbs_debug_polymul", "fbs_debug_raise",
-    "fbs_debug_field", "fbs_debug_transform_list", "fbs_debug_transform", "fbs_debug_gauss", "fbs_debug_gauss_dev",
+    "fbs_debug_field", "fbs_debug_transform_list", "fbs_debug_transform", "fbs_debug_gauss", "fbs_debug_gauss_dev", "fbs_debug_pack_fields_dev",
     "fbs_keygen_seeded", "fbs_seeded_key_sizes", "fbs_export_seeded_keys", "fbs_import_seeded_keys", "fbs_encrypt_seeded",
     "fbs_encrypt_seeded_fresh", "fbs_encrypt_seeded_dev", "fbs_encrypt_seeded_fresh_dev", "fbs_expand_seeded",
     "fbs_expand_seeded_dev", "fbs_eval_seeded",
@@ -707,6 +708,11 @@ class Context(ClientContext):
     def pack_dev(self, d_cts, count, d_words, bits, stream=0):
         """fbs_pack_dev: `count` big-key ciphertexts at d_cts -> packed words at d_words, asynchronous on `stream`; no secret"""
         self._check(lib.fbs_pack_dev(self._h, d_cts or None, int(count), int(bits), d_words or None, stream or None))
+
+    def debug_pack_fields_dev(self, d_fields, count, d_words, bits, stream=0):
+        """fbs_debug_pack_fields_dev (a test hook): uint32 fields [count][n + 1] at 31 bits at d_fields, as the key switch of
+        `pack_dev` leaves them, -> packed words at d_words; one pass at the most, no key switch"""
+        self._check(lib.fbs_debug_pack_fields_dev(self._h, d_fields or None, int(count), int(bits), d_words or None, stream or None))
 
     def pack(self, cts, bits):
         """Host ciphertexts [..][D+1] -> packed words (through `pack_dev`); for tests and one-off calls"""

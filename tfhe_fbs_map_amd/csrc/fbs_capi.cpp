@@ -1477,4 +1477,23 @@ int fbs_debug_gauss_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uin
     return dev_debug_gauss(ctx, d_words, count, sigma, d_out, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
+// test hook of the packing kernels: fbs_pack_dev without its key switch, on fields [count][n + 1] at 31 bits that a test supplies --
+// mask fields no key switch under seeded keys could be made to give.  One pass of fbs_pack_dev: its scratch growth, then dev_pack
+// on the caller's pointer in place of the modulus-switch scratch.
+int fbs_debug_pack_fields_dev(fbs_ctx *ctx, const uint32_t *d_fields, size_t count, uint32_t bits, uint64_t *d_words, void *stream) try {
+    if (int rc = io_prologue(ctx, d_fields, d_words, count, 0, nullptr)) return rc;
+    if (int rc = pack_prologue(ctx, count, bits)) return rc;
+    if (count == 0) return FBS_OK;
+    if (count > std::max(ctx->ms_capacity, COMPACT_PASS) / ctx->N * ctx->N)
+        return set_error(ctx, FBS_E_INVALID, "more fields than one pass of fbs_pack_dev holds");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    size_t pass = 0;
+    int rc = pack_reserve(ctx, count, &pass);
+    if (rc != FBS_OK) return rc;
+    hipStream_t s = pick(ctx, stream);
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    if ((rc = dev_pack(ctx, d_fields, count, bits, d_words, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+    return scratch_done(ctx, s);
+} FBS_API_CATCH(ctx)
+
 }  // extern "C"

@@ -21,6 +21,15 @@
 //                          (N w is a multiple of 64), so the workgroups of a sample write disjoint words.
 //
 // Every value is an exact residue: the words do not depend on the number of slices or on the order of the sums.
+// tests/test_gpu_pack_shapes.py holds that word for word against the definition restated in tests/helpers.py, on fields fed in
+// through fbs_debug_pack_fields_dev (dev_pack below, without the key switch in front of it): every (k, N) of FBS_PACK_SHAPES at
+// (t_p, gamma_p) = (3, 10) and the shipped (1, 27), fills 1, N - 1, N, N + 1, every slicing; (1, 31), (31, 1) and (2, 15) -- both
+// branches of pack_round_mask, the widest digit, the most levels -- on one shape per transform class; n + 1 = 64, 65 and 735 columns
+// through k_pack_transpose, stale rows behind `count`; two passes of fbs_pack_dev.  The fields are planted (planted_pack_fields): a
+// mask field that rounds up and wraps, the rounding tie, -B/2 and B/2 - 1 on every level, the carry dropped at the top, the body
+// fields either side of pack_lift_body's sign change.  tests/test_packed_reference.py holds the restatement to the host decode.
+// Not reachable from the coefficient side: the lazy accumulator at its worst, 16 same-signed products near 0.8 q in the transform
+// domain; that rests on the arithmetic stated at PACK_CENTRE_EVERY (16 x 0.8 q + q / 2 < 2^52).
 // None of these is a key-switch or blind-rotation launch: they are not in fbs_kernel_catalog and the profile does not count them.
 #include <hip/hip_runtime.h>
 
