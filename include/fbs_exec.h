@@ -804,7 +804,10 @@ const char *fbs_debug_transform_list(void);
  * must be of the variant's N (FBS_E_INVALID otherwise; the twiddle tables depend on N alone, so any k serves), polys a multiple of np.
  * int64 in and out, not reduced.  Coefficient side: natural order (a lane transform: its four parts back to back, each in natural
  * order).  Evaluation side: register order, word t*E + m = register m of thread t, E = N / lanes -- what forward leaves in a word
- * is what inverse takes from it; which evaluation point a word holds is found by transforming the monomial X. */
+ * is what inverse takes from it; which evaluation point a word holds is found by transforming the monomial X.
+ * One line is accepted without being listed: "class=SplitNtt logn=10 lanes=64 dir=inverse bounded=1 centre=exit", the inverse
+ * k_blind_rotate takes where a wave holds a whole N = 1024 polynomial (SplitNtt::inverse_exit_centred: the residues of the listed
+ * "bounded=1" line, other representatives). */
 int fbs_debug_transform(fbs_ctx *ctx, const char *variant, const int64_t *in, int64_t *out, size_t polys);
 /* ---- test hook: raises a C++ exception INSIDE the library (kind 0 std::bad_alloc, 1 std::length_error, 2 std::runtime_error,
  * 3 a non-standard one; else nothing) to show that none crosses this boundary: returns FBS_E_NOMEM, FBS_E_NOMEM,

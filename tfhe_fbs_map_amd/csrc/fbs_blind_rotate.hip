@@ -273,7 +273,12 @@ __global__ __launch_bounds__((2 << LL) * FPW) __attribute__((amdgpu_waves_per_eu
 
         if constexpr (PRIO == 7) lead_if<PRIO>(2u * i + 1u, slot);
         // ---- back to coefficients (the 1/N is folded into the key) and accumulate ---------------
-        W::template inverse<BOUNDED>(own, xc, t, twi, inv_uni);
+        // (a whole polynomial on one wave, inputs below 16 q: the inverse that centres one register per group at the group's exit,
+        // 18 centring instructions per step instead of 96 -- same residues, and the same 8 q at the exit)
+        if constexpr (has_fused_opening<W>::value && BOUNDED)
+            W::inverse_exit_centred(own, xc, t, twi, inv_uni);
+        else
+            W::template inverse<BOUNDED>(own, xc, t, twi, inv_uni);
 #pragma unroll
         for (int m = 0; m < E; m++) acc[m] = fp_center(acc[m] + own[m]);   // |.| <= 17 q -> centred
     }

@@ -111,6 +111,25 @@ __global__ __launch_bounds__(W::LANES) void k_debug_inverse(const long long *in,
     for (int m = 0; m < W::E; m++) dst[W::template index_of<0>(t, m)] = (long long)x[m];
 }
 
+// SplitNtt::inverse_exit_centred, called as k_blind_rotate calls it where a wave holds a whole polynomial and DIG >= 1
+template <class W>
+__global__ __launch_bounds__(W::LANES) void k_debug_inverse_exit_centred(const long long *in, long long *out, const double *, const double *tw_inv) {
+    __shared__ double lds[2 * W::N];
+    const uint32_t t = threadIdx.x;
+    const Twiddles twi = debug_twiddles<W>(lds, tw_inv, t);
+    typename W::Xchg xc{lds, 0};
+    xc.stride = 0;
+    const long long *src = in + (size_t)blockIdx.x * W::N;
+    long long *dst = out + (size_t)blockIdx.x * W::N;
+    double x[W::E];
+#pragma unroll
+    for (int m = 0; m < W::E; m++) x[m] = (double)src[t * W::E + m];
+    const typename W::InvUniform inv_uni = W::inverse_uniform(t, twi);
+    W::inverse_exit_centred(x, xc, t, twi, inv_uni);
+#pragma unroll
+    for (int m = 0; m < W::E; m++) dst[W::template index_of<0>(t, m)] = (long long)x[m];
+}
+
 // ---- the wave-private lane transforms: the four parts of a polynomial on four waves, NP polynomials side by side -------------------
 template <int LOGN, int NP>
 __global__ __launch_bounds__(256) void k_debug_lane_forward(const long long *in, long long *out, const double *tw_fwd, const double *tw_inv) {
@@ -195,6 +214,7 @@ struct Variant {
     std::string line;
     int logn, lanes, np;   // np: polynomials a workgroup takes
     DebugKernel kernel;
+    bool listed = true;    // named by fbs_debug_transform_list (false: fbs_debug_transform runs it all the same)
 };
 
 static void add(std::vector<Variant> &v, const char *cls, int logn, int lanes, const char *dir, const char *what, int value, int np,
@@ -252,6 +272,12 @@ static const std::vector<Variant> &variants() {
         FBS_CU_PAIRS_KERNELS(X)
 #undef X
         add_lane<10, 1>(v);   // k_blind_rotate_cu_k2 (Family::CU_K2: not a template)
+        // Accepted by fbs_debug_transform, NOT named by fbs_debug_transform_list: the list is one forward and one inverse line per
+        // kernel by (class, N, lanes, FIRST or BOUNDED) -- what tests/test_transform_reference.py derives from a kernel's name --
+        // and k_blind_rotate<10,6,DIG >= 1,.> keeps its "bounded=1" line there, which SplitNtt::inverse<true> still answers (the
+        // pairs kernels call it).  The inverse those kernels take instead is this line (tests/test_exit_centred_inverse.py).
+        v.push_back({"class=SplitNtt logn=10 lanes=64 dir=inverse bounded=1 centre=exit", 10, 64, 1, k_debug_inverse_exit_centred<SplitNtt<10, 6>>,
+                     false});
         return v;
     }();
     return all;
@@ -260,7 +286,8 @@ static const std::vector<Variant> &variants() {
 const char *debug_transform_list() {
     static const std::string text = [] {
         std::string t;
-        for (const Variant &v : variants()) t += v.line + "\n";
+        for (const Variant &v : variants())
+            if (v.listed) t += v.line + "\n";
         return t;
     }();
     return text.c_str();

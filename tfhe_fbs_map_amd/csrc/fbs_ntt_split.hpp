@@ -284,6 +284,59 @@ struct SplitNtt {
             x[r + EH] = fp_mulmod(u - v, w0);
         }
     }
+
+    // The same inverse with the centring moved from the entry of groups 1 and 0 (all eight registers of a half) to the EXIT of
+    // every group (one register of a half): 18 instructions per transform where inverse<true> spends 96.  Same arguments, twiddle
+    // requests, exchanges and layouts as inverse<true>; the results are the same residues, not the same representatives.
+    // Why one register is enough: the three Gentleman-Sande stages of a group run register bit 0, then bit 1, then bit 2, and a
+    // register is overwritten by a product at its last set bit and only doubles after that.  Registers 4..7 of a half leave the group
+    // as one product, 2 and 3 as a sum of two, 1 as a sum of four -- register 0 alone is a sum of all eight inputs.
+    // Entry promise: integers, every |x| at most 16 q - 1 (what DIG >= 1 gives the kernel).  Group by group:
+    //   group 2   in: 16 q - 1.  fp_mulmod sees differences of at most 8 (16 q - 1) < 2^53: exact, each product under 1.24 q
+    //             (fbs_field.hpp).  Register 0 reaches at most 8 (16 q - 1) < 128 q < 2^53, an exact integer that fp_center takes
+    //             (the quotient estimate is off by far less than 2^-40 there); the other seven hold at most 4 * 1.24 q < 5 q.
+    //   group 1   in: 5 q at most (register 0 comes in centred, q / 2).  Differences of at most 40 q < 2^52: each product under
+    //             0.8 q.  Register 0 reaches at most 40 q, the others 4 * 0.8 q = 3.2 q.
+    //   group 0   as group 1 (its inputs are the smaller 3.2 q).
+    //   joining   both operands at most 3.2 q: sums at most 6.4 q, products under 0.8 q -- inside the 8 q that inverse<> publishes,
+    //             so a caller's accumulate-and-centre is the one it was.
+    // tests/test_exit_centred_inverse.py replays this on exact integers at the promise, and holds the device to the replay.
+    template <int G, int H>
+    __device__ static __forceinline__ void inv_group_exit(double (&x)[E], const GroupTw &g) {
+        inv_group<G, H, false>(x, g);
+        x[H * EH] = fp_center(x[H * EH]);
+    }
+    __device__ static __forceinline__ void inverse_exit_centred(double (&x)[E], Xchg &xc, uint32_t t, const Twiddles &tw,
+                                                                const InvUniform &uni, uint32_t R = 1) {
+        double *half0 = xc.next(), *half1 = half0 + N / 2;
+        GroupTw ta, tb;
+        load_twiddles<2, 0>(t, tw, ta, R);
+        load_twiddles<2, 1>(t, tw, tb, R);
+        const GroupTw &t0a = uni.a, &t0b = uni.b;
+        const double w0 = uni.w0;
+        inv_group_exit<2, 0>(x, ta);
+        exchange<2, 1, 0>(x, half0, t);
+        load_twiddles<1, 0>(t, tw, ta, R);
+        pin();
+        inv_group_exit<2, 1>(x, tb);
+        exchange<2, 1, 1>(x, half1, t);
+        load_twiddles<1, 1>(t, tw, tb, R);
+        pin();
+        inv_group_exit<1, 0>(x, ta);
+        exchange<1, 0, 0>(x, half0, t);
+        pin();
+        inv_group_exit<1, 1>(x, tb);
+        exchange<1, 0, 1>(x, half1, t);
+        pin();
+        inv_group_exit<0, 0>(x, t0a);
+        inv_group_exit<0, 1>(x, t0b);
+#pragma unroll
+        for (int r = 0; r < EH; r++) {
+            const double u = x[r], v = x[r + EH];
+            x[r] = u + v;
+            x[r + EH] = fp_mulmod(u - v, w0);
+        }
+    }
 };
 
 // Negacyclic NTT of one polynomial of size N = W M held by W = 2^LOGW wavefronts (M = 1024: N = 2048 on two waves,

@@ -13,17 +13,21 @@ TAG=${1:-r04}; shift
 SETS=${@:-p1024 cu256 secure p31}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TOP=gpurun_out/prof_$TAG
+LIMIT=${PROFILE_PASS_LIMIT:-300}   # seconds per rocprofv3 pass
 mkdir -p $TOP
 PMCS=("FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SMEM GRBM_GUI_ACTIVE SQ_BUSY_CYCLES" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_WAVE_CYCLES" "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_LDS_IDX_ACTIVE")
 run_set() {   # $1 = subdir, rest = command
   local NAME=$1
   local OUT=$TOP/$1; shift
   rm -rf $OUT && mkdir -p $OUT
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- "$@" > $OUT/under_rocprof.out 2> $OUT/under_rocprof.err
+  # every pass under a time limit of its own; a pass that fails or runs into it ends the round (nothing more starts on that GPU)
+  timeout -k 10 $LIMIT rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- "$@" > $OUT/under_rocprof.out 2> $OUT/under_rocprof.err \
+    || { echo "set $NAME: the kernel-trace pass failed"; return 1; }
   local i=0
   for c in "${PMCS[@]}"; do
     i=$((i+1))
-    rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$i -- "$@" > /dev/null 2> $OUT/pmc_$i.err
+    timeout -k 10 $LIMIT rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$i -- "$@" > /dev/null 2> $OUT/pmc_$i.err \
+      || { echo "set $NAME: counter pass $i failed"; return 1; }
   done
   python3 tools/profile_summary.py $OUT > $OUT/summary.json
   cp $OUT/kt/*/*kernel_stats.csv $OUT/kernel_stats.csv 2>/dev/null
@@ -49,5 +53,5 @@ for S in $SETS; do
     k2cu512) run_set k2cu512 python3 tools/secure_bench.py 512 6 15 70 k2 ;;
     p31cu)   run_set p31cu python3 tools/secure_bench.py 256 6 31 325 ;;
     lean512) run_set lean512 python3 bench.py --batch 512 --steps 10 --cpu-sample 0 --no-secure ;;
-  esac
+  esac || exit 1
 done
