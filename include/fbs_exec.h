@@ -148,7 +148,8 @@ int fbs_ctx_tune(fbs_ctx *ctx, const char *knob, int64_t value);
  * "wires_capacity", "next_nonce", "cu_count"; "has_secret" (1: the context holds secret keys), "seeded_keys" (1: its keys
  * came from fbs_keygen_seeded or fbs_import_seeded_keys); "states_alive", "state_bytes" (resident state: fbs_state blocks not
  * yet destroyed, and the device bytes they hold); "packing_key" (1: the context holds a packing key), "packing_levels" and
- * "packing_base_bits" (its t_p and gamma_p, 0 without one); "keys_made_on_device" (1: the keys held now were made or expanded
+ * "packing_base_bits" (its t_p and gamma_p, 0 without one); "fold_key", "fold_levels" and "fold_base_bits" (the same for the fold
+ * key of "folded state": t_f and gamma_f); "keys_made_on_device" (1: the keys held now were made or expanded
  * on the GPU, knob "keys_on_device"), "bsk_upload_bytes" (bytes of bootstrapping-key material the last key-making call copied
  * host -> device: the whole key on the host path, 0 for keys made on the device, the bodies for a server key expanded there) */
 int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value);
@@ -660,6 +661,62 @@ int fbs_pub_expand_dev(fbs_ctx *ctx, const uint64_t *d_glwe, size_t count, uint6
  * any key.  Blocks until done, as fbs_state_put. */
 int fbs_state_put_public(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *glwe);
 
+/* ---- folded state: N resident bits in one full-precision GLWE sample, linked back in without a refresh ---------------------------
+ * A full ciphertext costs D + 1 words per bit; a compact one has been through the key switch and pays a bootstrap to come back; a
+ * packed output cannot come back at all.  A FOLD is a packing key switch taken straight from the big key: up to N big-key
+ * ciphertexts go into the N coefficients of one GLWE sample under the same key, (k + 1) N words for N bits, with no rounding of
+ * the result.  The sample is exactly what "public-key inputs" calls a sample, and fbs_pub_expand / fbs_pub_expand_dev turn it back
+ * into big-key ciphertexts with no key at all (UNFOLD).  Its noise (params.folded_state_variance) never touches sigma_lwe, so the
+ * unfolded ciphertexts enter the next program unrefreshed.  libfbsexec.so only.
+ *
+ * FOLD KEY, parameters (t_f, gamma_f), 1 <= t_f, 1 <= gamma_f, t_f gamma_f <= 31.  Rows (i, v), i < D = k N, v < t_f, layout
+ * [D][t_f][k+1][N]: row (i, v) is a GLWE encryption of the constant polynomial s_i h_v, where s_i is word i of the flattened big key
+ * -- the key bit under which word i of a big-key ciphertext's mask is read, the extraction convention of "public-key inputs" -- and
+ * h_v = round(q / 2^(gamma_f (v+1))): polynomials A_0 .. A_(k-1), then B = sum_c A_c S_c + e + s_i h_v (e: sigma_glwe).  Row
+ * r = i t_f + v takes its masks from stream (22, r) under the public mask key and its noise from stream (23, r) under the context's
+ * key: two domains nothing else draws from, so every other key, ciphertext and known answer is word for word what it was.  Only
+ * the bodies [D][t_f][N] travel.  The key belongs to the evaluation keys it was made beside: fbs_keygen, fbs_import_keys,
+ * fbs_keygen_seeded and fbs_import_seeded_keys drop it, as they drop the packing key.
+ *
+ * FOLD.  Input: `count` big-key ciphertexts (a_j, b_j), in order; ciphertext j goes to coefficient j mod N of sample g = j / N; the
+ * last sample may be partly filled.
+ *   1. every mask word a in [0, q) to t_f gamma_f bits, q treated as 2^46: r = 46 - t_f gamma_f,
+ *      a' = (((a >> (r-1)) + 1) >> 1) mod 2^(t_f gamma_f) -- the key switch's own rounding (the integer function its kernels
+ *      compute before they add the digit offsets; in the sources, compact_round);
+ *   2. a' into t_f BALANCED digits exactly as step 3 of PACKING;
+ *   3. the body word b_j is used as it is: there is no lift;
+ *   4. D_(i,v)(X) = sum_j d_v(a'_(j,i)) X^j;  ACC_c = - sum_(i,v) D_(i,v) A_c^(i,v)  (c < k),
+ *      ACC_k = sum_j b_j X^j - sum_(i,v) D_(i,v) B^(i,v);  negacyclic, mod q; coefficients at and above the fill take b_j = 0.
+ * There is NO transport rounding: a sample is its k + 1 polynomials as canonical residues, [k+1][N] words, the layout
+ * fbs_pub_expand reads; a batch is its samples back to back, fbs_pub_words(count) words.  Every value is an exact residue: the
+ * words do not depend on "pack_slices" (which cuts the i-sum here as it does for packing, at most min(32, D) ways) or launch shape.
+ * UNFOLD is fbs_pub_expand / fbs_pub_expand_dev as they stand: the phase of ciphertext j is that of its source plus the fold's noise.
+ *
+ * Every entry writes nothing when it fails.  fbs_ctx_stat: "fold_key", "fold_levels", "fold_base_bits". */
+/* Makes the fold key (on the device with "keys_on_device", else on the host) and uploads it in the transform domain.  FBS_E_STATE
+ * unless the context's keys came from fbs_keygen_seeded on this context; FBS_E_INVALID for parameters outside the range above. */
+int fbs_fold_keygen(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f);
+/* word counts for t_f levels (0: the context's own key; FBS_E_STATE without one): sizes[0] = D t_f N (bodies), sizes[1] = D t_f (k+1) N */
+int fbs_fold_key_sizes(const fbs_ctx *ctx, uint32_t t_f, size_t sizes[2]);
+/* bodies [D][t_f][N]; full (a test hook) the whole key [D][t_f][k+1][N] in the coefficient domain.  Either pointer may be NULL. */
+int fbs_export_fold_key(const fbs_ctx *ctx, uint64_t *bodies, uint64_t *full);
+/* The mirror: expands the masks from the context's mask key and uploads.  Works on evaluation-only contexts.  Every body word must
+ * be a canonical residue (FBS_E_INVALID); a refused call leaves the previous fold key in place. */
+int fbs_import_fold_key(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, const uint64_t *bodies);
+/* d_cts [count][D+1] (any big-key ciphertexts, device) -> d_glwe [fbs_pub_words(count)] (device, 16-byte aligned: FBS_E_INVALID
+ * otherwise), asynchronous on `stream`; needs no secret; FBS_E_STATE without a fold key.  Runs in passes of whole samples (8192
+ * ciphertexts, one sample where N is larger); its scratch (the rounded fields of a pass, partial accumulators) is the packing
+ * scratch and grows like any other: repeated calls of one shape do not grow it. */
+int fbs_fold_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, void *stream);
+/* Rows [row0, row0 + rows) of a resident state, flattened [row][sample] as fbs_state_fetch_packed flattens them, folded on the
+ * device (word for word fbs_fold_dev of the full fetch); out [fbs_pub_words(rows T)] on the host.  Blocks until they are back. */
+int fbs_state_fold(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint64_t *out);
+/* The same into a device buffer (16-byte aligned), queued on the context's stream like the other state entries. */
+int fbs_state_fold_dev(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint64_t *d_glwe);
+/* The device-source twin of fbs_state_put_public: the samples at d_glwe (device) expanded into rows [row0, row0 + rows), no host
+ * copy, no staging; being device memory, the words cannot be checked.  Queued on the context's stream; needs no key. */
+int fbs_state_unfold_dev(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *d_glwe);
+
 /* ---- a loaded program, one level at a time (multi-GPU hosts) -----------------
  * The two independent axes of the reference's eval loop (fbs_exec_env.py:211-223) are the gates
  * of a bootstrap level and the samples.  A host that shards the GATES of a level over several
@@ -794,6 +851,10 @@ int fbs_debug_gauss_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uin
  * not read.  Refuses what fbs_pack_dev refuses and, with FBS_E_INVALID, more than one pass of it (max(8192, the modulus-switch
  * scratch) ciphertexts, cut down to whole samples).  libfbsexec.so only (tests/test_gpu_pack_shapes.py). */
 int fbs_debug_pack_fields_dev(fbs_ctx *ctx, const uint32_t *d_fields, size_t count, uint32_t bits, uint64_t *d_words, void *stream);
+/* The front kernel of "folded state" alone (step 1 and the transposition): d_cts [count][D+1] -> d_fields, [D][cols] uint32 mask
+ * words rounded to tg bits, then cols 64-bit body words (8-byte aligned; (D + 2) cols uint32 in all); cols a multiple of N,
+ * count <= cols; columns past `count` are zero and the ciphertexts behind `count` are not read.  Needs no key.  libfbsexec.so only. */
+int fbs_debug_fold_front_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t cols, uint32_t tg, uint32_t *d_fields, void *stream);
 /* Static text, no GPU needed: one line per transform variant some blind-rotation kernel instantiates, made from the lists the
  * kernels are instantiated from:
  *   "class=<PolyNtt|SplitNtt|WavesNtt|LaneNtt256|LaneNtt512> logn=<log2 N> lanes=<threads per polynomial> dir=forward first=<FIRST>[ np=<NP>]"

@@ -1,0 +1,19 @@
+# Sanitizer build of the host side of folded state (a makefile of its own beside tests/c/Makefile, client.mk, sampler.mk and
+# public.mk, with the same build/ directory, which tests/c/Makefile's `clean` removes):        make -C tests/c -f fold.mk fold_asan
+#   build/fold_harness  fold_harness.cpp + the host sources it calls (fbs_error.cpp, fbs_host.cpp) with -DFBS_HOST_ONLY, g++ and
+#                       no HIP headers, under AddressSanitizer and UBSan
+# tests/test_fold_sanitizers.py builds it and runs it as a program of its own.
+HERE  := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))
+ROOT  := $(HERE)../..
+CSRC  := $(ROOT)/tfhe_fbs_map_amd/csrc
+OUT   := $(HERE)build
+SAN   := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1
+SRCS  := $(HERE)fold_harness.cpp $(CSRC)/fbs_error.cpp $(CSRC)/fbs_host.cpp
+
+fold_asan: $(OUT)/fold_harness
+
+$(OUT)/fold_harness: $(SRCS) $(wildcard $(CSRC)/*.hpp) $(ROOT)/include/fbs_exec.h
+	@mkdir -p $(OUT)
+	g++ -std=c++17 $(SAN) -Wall -Wextra -pthread -ffp-contract=off -DFBS_HOST_ONLY -o $@ $(SRCS)
+
+.PHONY: fold_asan

@@ -1,0 +1,111 @@
+// Sanitizer harness for the HOST side of folded state (include/fbs_exec.h, "folded state"): csrc/fbs_host.cpp's host_fold_keygen and
+// host_expand_fold_key on exactly-sized buffers, built by tests/c/fold.mk with g++ under AddressSanitizer and UBSan and run by
+// tests/test_fold_sanitizers.py as a program of its own.  No GPU, no HIP call.
+//
+// At two toy sets and several (t_f, gamma_f): the key a client generates and the key a server expands from (mask key, bodies) are
+// identical; every row's phase minus s_i h_v is within 6 sigma_glwe, s_i word i of the flattened big key; the fold key shares no
+// word with the packing key of the same parameters (its streams are its own); a fold of one trivially keyed ciphertext computed
+// from the rows here -- rounding (compact_round), digits (pack_digit), the sum against the rows -- carries the source's phase.
+#include <cstdio>
+#include <cstring>
+#include <random>
+#include <vector>
+
+#include "../../tfhe_fbs_map_amd/csrc/fbs_internal.hpp"
+#include "../../tfhe_fbs_map_amd/csrc/fbs_pack.hpp"
+
+using namespace fbs;
+
+static bool make_ctx(fbs_ctx &ctx, uint32_t n, uint32_t log_n, uint32_t k, uint64_t seed) {
+    fbs_params prm{};
+    prm.n = n, prm.log_n_poly = log_n, prm.k = k, prm.l_bsk = 1, prm.beta_bsk = 18, prm.t_ksk = 4, prm.gamma_ksk = 3, prm.p_msg = 7;
+    prm.sigma_lwe = 1 << 8, prm.sigma_glwe = 1 << 4, prm.bsk_group = 1;
+    if (host_ctx_init(&ctx, &prm, seed, nullptr) != FBS_OK) {
+        printf("FAIL host_ctx_init: %s\n", ctx.err.c_str());
+        return false;
+    }
+    host_keygen_seeded(&ctx);   // the secrets, the mask key (and the other seeded keys: toy sizes)
+    return true;
+}
+
+static int64_t centred(uint64_t x) { return x > FQ / 2 ? -(int64_t)(FQ - x) : (int64_t)x; }
+
+// phase of the GLWE row (A_0 .. A_(k-1), B) under the key of ctx: B - sum_c A_c S_c
+static std::vector<uint64_t> row_phase(const fbs_ctx &ctx, const uint64_t *row) {
+    const uint32_t N = ctx.N, k = ctx.p.k;
+    std::vector<uint64_t> phase(row + (size_t)k * N, row + (size_t)(k + 1) * N);
+    for (uint32_t c = 0; c < k; c++)
+        for (uint32_t s = 0; s < N; s++) {
+            if (!ctx.sk_glwe[(size_t)c * N + s]) continue;
+            const uint64_t *a = row + (size_t)c * N;
+            for (uint32_t j = 0; j < N - s; j++) phase[j + s] = fq_sub(phase[j + s], a[j]);
+            for (uint32_t j = N - s; j < N; j++) phase[j + s - N] = fq_add(phase[j + s - N], a[j]);
+        }
+    return phase;
+}
+
+int main() {
+    int failures = 0;
+    const uint32_t shapes[2][3] = {{4, 8, 1}, {4, 8, 2}};   // (n, log N, k)
+    const uint32_t keys[4][2] = {{1, 19}, {2, 13}, {3, 10}, {1, 31}};
+    for (auto &sh : shapes)
+        for (auto &tk : keys) {
+            const uint32_t n = sh[0], k = sh[2], t = tk[0], gamma = tk[1];
+            fbs_ctx ctx;
+            if (!make_ctx(ctx, n, sh[1], k, 5)) return 1;
+            const uint32_t N = ctx.N, D = ctx.D;
+            std::vector<uint64_t> bodies, client, server, pack_bodies;
+            host_fold_keygen(&ctx, t, gamma, bodies);
+            if (bodies.size() != (size_t)D * t * N) failures++, printf("FAIL bodies of %zu words\n", bodies.size());
+            std::vector<uint64_t> exact(bodies);   // an exactly-sized copy: a read past the bodies is a finding
+            host_expand_fold_key(&ctx, ctx.mask_key, t, exact.data(), client);
+            fbs_ctx srv;                           // the server: another context of the same set, no secret, the client's mask key
+            if (!make_ctx(srv, n, sh[1], k, 99)) return 1;
+            srv.sk_lwe.clear(), srv.sk_glwe.clear();
+            host_expand_fold_key(&srv, ctx.mask_key, t, exact.data(), server);
+            if (client != server || client.size() != (size_t)D * t * (k + 1) * N) {
+                printf("FAIL client and server keys differ k=%u t=%u\n", k, t);
+                failures++;
+            }
+            host_packing_keygen(&ctx, t, gamma, pack_bodies);   // rows 0 .. n t - 1 of both keys: other streams, other words
+            if (!memcmp(pack_bodies.data(), bodies.data(), pack_bodies.size() * 8)) failures++, printf("FAIL the fold key repeats the packing key\n");
+            int64_t worst = 0;
+            for (uint32_t i = 0; i < D; i++)
+                for (uint32_t v = 0; v < t; v++) {
+                    std::vector<uint64_t> phase = row_phase(ctx, client.data() + ((size_t)i * t + v) * (k + 1) * N);
+                    if (ctx.sk_glwe[i]) phase[0] = fq_sub(phase[0], pack_gadget(gamma, v));
+                    for (uint32_t j = 0; j < N; j++) worst = std::max<int64_t>(worst, std::llabs(centred(phase[j])));
+                }
+            if (worst == 0 || worst > 6 * (int64_t)ctx.p.sigma_glwe) {
+                printf("FAIL row phase %lld beyond 6 sigma k=%u t=%u gamma=%u\n", (long long)worst, k, t, gamma);
+                failures++;
+            }
+            // one ciphertext folded by hand into coefficient 0: sample = (0, .., b) - sum_(i,v) d_v(a'_i) row(i, v); its phase at X^0
+            // is b - sum_i s_i a_i up to the rounding to t gamma bits, the skew of q read as 2^46 and the rows' noise
+            std::mt19937_64 rng(t * 100 + gamma);
+            std::vector<uint64_t> ct(D + 1), sample((size_t)(k + 1) * N, 0);
+            for (auto &w : ct) w = rng() % FQ;
+            ct[0] = FQ - 1, ct[1] = 0, ct[2] = 1ull << (FQ_BITS - t * gamma - 1);   // the largest word, zero, the rounding tie
+            const uint32_t tg = t * gamma, offs = pack_digit_offsets(t, gamma);
+            for (uint32_t i = 0; i < D; i++) {
+                const uint32_t z = (uint32_t)(((uint64_t)compact_round(ct[i], tg) + offs) & ((1ull << tg) - 1));
+                for (uint32_t v = 0; v < t; v++) {
+                    const uint64_t d = fq_from_i64(pack_digit(z, v, t, gamma));
+                    const uint64_t *row = client.data() + ((size_t)i * t + v) * (k + 1) * N;
+                    for (size_t w = 0; w < sample.size(); w++) sample[w] = fq_sub(sample[w], fq_mul(d, row[w]));
+                }
+            }
+            sample[(size_t)k * N] = fq_add(sample[(size_t)k * N], ct[D]);
+            uint64_t want = ct[D];
+            for (uint32_t i = 0; i < D; i++)
+                if (ctx.sk_glwe[i]) want = fq_sub(want, ct[i]);
+            const int64_t err = centred(fq_sub(row_phase(ctx, sample.data())[0], want));
+            // rounding: D/2 words off by at most half an ulp of 2^(46 - tg); skew: D words by at most 507903; noise: D t digits of
+            // at most 2^(gamma - 1) against 6 sigma_glwe
+            const double bound = D / 2.0 * (double)(1ull << (FQ_BITS - tg)) / 2 + D * 507903.0 + (double)D * t * (double)(1ull << (gamma - 1)) * 6 * ctx.p.sigma_glwe;
+            if ((double)std::llabs(err) > bound) failures++, printf("FAIL folded phase off by %lld (bound %.0f) k=%u t=%u\n", (long long)err, bound, k, t);
+            printf("ok fold key k=%u t=%u gamma=%u worst=%lld phase error %lld\n", k, t, gamma, (long long)worst, (long long)err);
+        }
+    printf(failures ? "FAIL\n" : "fold ok\n");
+    return failures ? 1 : 0;
+}

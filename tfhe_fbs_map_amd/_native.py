@@ -130,6 +130,15 @@ def _load():
         "fbs_state_put": (i32, [vp, vp, sz, sz, vp]),
         "fbs_pub_expand_dev": (i32, [vp, vp, sz, vp, vp]),
         "fbs_state_put_public": (i32, [vp, vp, sz, sz, vp]),
+        "fbs_fold_keygen": (i32, [vp, u32, u32]),
+        "fbs_fold_key_sizes": (i32, [vp, u32, C.POINTER(sz * 2)]),
+        "fbs_export_fold_key": (i32, [vp, vp, vp]),
+        "fbs_import_fold_key": (i32, [vp, u32, u32, vp]),
+        "fbs_fold_dev": (i32, [vp, vp, sz, vp, vp]),
+        "fbs_state_fold": (i32, [vp, vp, sz, sz, vp]),
+        "fbs_state_fold_dev": (i32, [vp, vp, sz, sz, vp]),
+        "fbs_state_unfold_dev": (i32, [vp, vp, sz, sz, vp]),
+        "fbs_debug_fold_front_dev": (i32, [vp, vp, sz, u32, u32, vp, vp]),
         "fbs_tvset_create": (i32, [vp, vp, vp, u32, C.POINTER(vp)]),
         "fbs_tvset_destroy": (None, [vp]),
         "fbs_bootstrap_batch": (i32, [vp, vp, vp, vp, sz, vp]),
@@ -199,6 +208,8 @@ EXPORTED_SYMBOLS = (
     "fbs_packing_keygen", "fbs_packing_key_sizes", "fbs_export_packing_key", "fbs_import_packing_key", "fbs_packed_words",
     "fbs_pack_dev", "fbs_state_fetch_packed", "fbs_decrypt_packed",
     "fbs_pub_expand_dev", "fbs_state_put_public",
+    "fbs_fold_keygen", "fbs_fold_key_sizes", "fbs_export_fold_key", "fbs_import_fold_key", "fbs_fold_dev", "fbs_state_fold",
+    "fbs_state_fold_dev", "fbs_state_unfold_dev", "fbs_debug_fold_front_dev",
     "fbs_eval_resident_mapped", "fbs_state_sum_groups",
     "fbs_audit_rows", "fbs_audit_level_dev",
 ) + _public_native.EXPORTED_SYMBOLS
@@ -510,6 +521,44 @@ class DeviceState:
         self.ctx._check(lib.fbs_state_put_public(self.ctx._h, self._live(), int(row0), rows, _ptr(glwe)))
         return self
 
+    def _fold_words(self, rows):
+        prm = self.ctx.params
+        return -(-max(0, rows) * self.T // prm.N) * (prm.k + 1) * prm.N
+
+    def fold(self, row0=0, rows=None, device=False):
+        """rows [row0, row0 + rows), flattened [row][sample], folded on the GPU into full-precision GLWE samples
+        [ceil(rows * T / N)][k+1][N] (include/fbs_exec.h, "folded state"): a numpy array (fbs_state_fold), or with device=True an
+        int64 torch tensor that stays on the card (fbs_state_fold_dev; the call waits for the fold).  Needs a fold key, no secret."""
+        rows = self.rows - int(row0) if rows is None else int(rows)
+        words = self._fold_words(rows)
+        if not device:
+            out = np.empty(words, np.uint64)
+            self.ctx._check(lib.fbs_state_fold(self.ctx._h, self._live(), int(row0), rows, _ptr(out)))
+            return out
+        import torch
+        out = torch.empty(max(2, words), dtype=torch.int64, device=f"cuda:{self.ctx.device}")
+        torch.cuda.synchronize(out.device)
+        self.ctx._check(lib.fbs_state_fold_dev(self.ctx._h, self._live(), int(row0), rows, out.data_ptr()))
+        self.ctx.sync()
+        return out[:words]
+
+    def unfold(self, glwe, row0=0, rows=None):
+        """The way back: folded samples -> rows [row0, row0 + rows), by sample extraction on the GPU, no key.  A numpy array goes
+        through `put_public` (checked word by word on the host); a torch tensor on the context's device is expanded where it lies
+        (fbs_state_unfold_dev; the call waits for it)."""
+        if isinstance(glwe, np.ndarray):
+            return self.put_public(glwe, row0, rows)
+        rows = self.rows - int(row0) if rows is None else int(rows)
+        import torch
+        if glwe.dtype != torch.int64 or not glwe.is_cuda or glwe.device.index != self.ctx.device or not glwe.is_contiguous():
+            raise ValueError("folded samples on the device are a contiguous int64 tensor on the context's device")
+        if glwe.numel() != self._fold_words(rows):
+            raise ValueError(f"{glwe.numel()} sample words for {rows} rows of {self.T} samples (the parameter set needs {self._fold_words(rows)})")
+        torch.cuda.synchronize(glwe.device)
+        self.ctx._check(lib.fbs_state_unfold_dev(self.ctx._h, self._live(), int(row0), rows, glwe.data_ptr() if rows else None))
+        self.ctx.sync()
+        return self
+
     def close(self):
         if not self.closed and lib is not None:
             lib.fbs_state_destroy(self._h)
@@ -704,6 +753,59 @@ class Context(ClientContext):
         if 1 <= int(t_p) <= 31 and bodies.size != self.packing_key_sizes(t_p)[0]:
             raise ValueError(f"packing_bodies has {bodies.size} words, the parameter set needs {self.packing_key_sizes(t_p)[0]}")
         self._check(lib.fbs_import_packing_key(self._h, int(t_p), int(gamma_p), _ptr(bodies)))
+
+    # ---- folded state: N resident ciphertexts in one full-precision GLWE sample (include/fbs_exec.h, "folded state") ----
+    def fold_keygen(self, t_f, gamma_f):
+        """fbs_fold_keygen: the fold key (t_f levels of gamma_f bits) beside the keys of `keygen_seeded`"""
+        self._check(lib.fbs_fold_keygen(self._h, int(t_f), int(gamma_f)))
+
+    def fold_key_sizes(self, t_f=0):
+        """(bodies, whole key) in words for t_f levels (0: the context's own key)"""
+        sizes = (C.c_size_t * 2)()
+        self._check(lib.fbs_fold_key_sizes(self._h, int(t_f), C.byref(sizes)))
+        return int(sizes[0]), int(sizes[1])
+
+    def export_fold_key(self, full=False):
+        """dict(fold_levels, fold_base_bits, fold_bodies [D][t_f][N]); full=True adds `full`, the whole key [D][t_f][k+1][N] in the
+        coefficient domain (a test hook)"""
+        nb, nf = self.fold_key_sizes()
+        bodies = np.empty(nb, np.uint64)
+        whole = np.empty(nf, np.uint64) if full else None
+        self._check(lib.fbs_export_fold_key(self._h, _ptr(bodies), _ptr(whole)))
+        out = dict(fold_levels=self.stat("fold_levels"), fold_base_bits=self.stat("fold_base_bits"), fold_bodies=bodies)
+        if full:
+            prm = self.params
+            out["full"] = whole.reshape(prm.k * prm.N, out["fold_levels"], prm.k + 1, prm.N)
+        return out
+
+    def import_fold_key(self, t_f, gamma_f, bodies):
+        """fbs_import_fold_key: the masks come from the context's mask key; works on evaluation-only contexts"""
+        bodies = _c(bodies, np.uint64).reshape(-1)
+        if 1 <= int(t_f) <= 31 and bodies.size != self.fold_key_sizes(t_f)[0]:
+            raise ValueError(f"fold_bodies has {bodies.size} words, the parameter set needs {self.fold_key_sizes(t_f)[0]}")
+        self._check(lib.fbs_import_fold_key(self._h, int(t_f), int(gamma_f), _ptr(bodies)))
+
+    def fold_dev(self, d_cts, count, d_glwe, stream=0):
+        """fbs_fold_dev: `count` big-key ciphertexts at d_cts -> folded samples at d_glwe, asynchronous on `stream`; no secret"""
+        self._check(lib.fbs_fold_dev(self._h, d_cts or None, int(count), d_glwe or None, stream or None))
+
+    def debug_fold_front_dev(self, d_cts, count, cols, tg, d_fields, stream=0):
+        """fbs_debug_fold_front_dev (a test hook): the fold's front kernel alone"""
+        self._check(lib.fbs_debug_fold_front_dev(self._h, d_cts or None, int(count), int(cols), int(tg), d_fields or None, stream or None))
+
+    def fold(self, cts):
+        """Host ciphertexts [..][D+1] -> folded samples (through `fold_dev`); for tests and one-off calls"""
+        import torch
+        cts = _c(cts, np.uint64).reshape(-1, self.params.ct_words)
+        count, prm = cts.shape[0], self.params
+        words = -(-count // prm.N) * (prm.k + 1) * prm.N
+        dev = f"cuda:{self.device}"
+        d_c = torch.from_numpy(cts.view(np.int64)).to(dev) if count else torch.zeros(1, dtype=torch.int64, device=dev)
+        d_w = torch.zeros(max(2, words), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(d_w.device)
+        self.fold_dev(d_c.data_ptr(), count, d_w.data_ptr())
+        self.sync()
+        return d_w[:words].cpu().numpy().view(np.uint64)
 
     def pack_dev(self, d_cts, count, d_words, bits, stream=0):
         """fbs_pack_dev: `count` big-key ciphertexts at d_cts -> packed words at d_words, asynchronous on `stream`; no secret"""

@@ -68,6 +68,7 @@ inline void keys_replaced(fbs_ctx *ctx, bool seeded, bool eval_only) {
 inline void keys_in_place(fbs_ctx *ctx) {
     ctx->have_keys = true;
     ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
+    ctx->have_fold = false;   // (and so did a fold key)
 }
 
 // Streams [first, first + count) of [2^55, 2^56) that nobody has used, for every entry that takes fresh streams.  The range is

@@ -241,6 +241,9 @@ int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value) try {
     const std::string k(name);
     if (host_stat(ctx, k, value)) return FBS_OK;   // (what the client library answers too)
     if (k == "scratch_growths") *value = ctx->scratch_growths;
+    else if (k == "fold_key") *value = ctx->have_fold;   // (folded state: this library's alone)
+    else if (k == "fold_levels") *value = ctx->have_fold ? ctx->fold_t : 0;
+    else if (k == "fold_base_bits") *value = ctx->have_fold ? ctx->fold_gamma : 0;
     else if (k == "ms_capacity") *value = (int64_t)ctx->ms_capacity;
     else if (k == "acc_capacity") *value = (int64_t)ctx->acc_capacity;
     else if (k == "wires_capacity") *value = (int64_t)ctx->wires_capacity;
@@ -270,7 +273,7 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     if (ctx->scratch_used) (void)hipStreamSynchronize(ctx->scratch_stream);
     for (void *p : {(void *)ctx->d_bsk_hat, (void *)ctx->d_bsk_hat_small, (void *)ctx->d_ksk, (void *)ctx->d_ksk_f, (void *)ctx->d_ks_corr, (void *)ctx->d_ks_a, (void *)ctx->d_ks_b, (void *)ctx->d_ks_c, (void *)ctx->d_tw_fwd, (void *)ctx->d_tw_inv, (void *)ctx->d_psi_pow, (void *)ctx->d_ms, (void *)ctx->d_ms_eps, (void *)ctx->d_ms_body, (void *)ctx->d_acc, (void *)ctx->d_stage_in, (void *)ctx->d_stage_out, (void *)ctx->d_stage_ids,
                     (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_sk_lwe_bits, (void *)ctx->d_io_msgs,
-                    (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_key, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc,
+                    (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_key, (void *)ctx->d_fold_key, (void *)ctx->d_folded, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc,
                     (void *)ctx->d_packed, (void *)ctx->d_pub, (void *)ctx->d_audit_err, (void *)ctx->d_audit_stats})
         if (p) (void)hipFree(p);
     for (fbs_state *st : ctx->states) {   // the states still alive
@@ -1284,7 +1287,7 @@ static int pack_reserve(fbs_ctx *ctx, size_t count, size_t *pass_out) {
     if (int rc = grow(ctx, ctx->d_pack_fields, ctx->pack_fields_capacity, (size_t)(ctx->p.n + 1) * pass, 4, true)) return rc;
     // (slices x samples is largest for the whole pass or for a single sample, whichever the launch rule favours)
     size_t rows = 0;
-    for (size_t g = 1; g <= samples; g++) rows = std::max(rows, g * pack_slices_for(ctx, g));
+    for (size_t g = 1; g <= samples; g++) rows = std::max(rows, g * pack_slices_for(ctx, g, ctx->p.n));
     if (int rc = grow(ctx, ctx->d_pack_acc, ctx->pack_acc_capacity, rows * (ctx->p.k + 1) * N, 8, true)) return rc;
     *pass_out = pass;
     return FBS_OK;
@@ -1344,6 +1347,192 @@ int fbs_state_fetch_packed(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_
         return scratch_fail(ctx, s, rc);
     if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
     return sync_stream(ctx, s);
+} FBS_API_CATCH(ctx)
+
+// ---- folded state: N resident ciphertexts in one full-precision GLWE sample under the big key (fbs_fold.hip) --------------------
+// installs (t_f, gamma_f, bodies) as the context's fold key, as install_packing_key installs a packing key
+static int install_fold_key(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, std::vector<uint64_t> &bodies) {
+    std::vector<uint64_t> full;
+    host_expand_fold_key(ctx, ctx->mask_key, t_f, bodies.data(), full);
+    const bool had = ctx->have_fold;
+    ctx->have_fold = false;
+    if (int rc = dev_upload_fold_key(ctx, full, t_f)) {
+        if (had) {   // (the device copy may be half written: the previous key goes back, or the context is left without one)
+            host_expand_fold_key(ctx, ctx->mask_key, ctx->fold_t, ctx->fold_bodies.data(), full);
+            const std::string text = ctx->err;
+            ctx->have_fold = dev_upload_fold_key(ctx, full, ctx->fold_t) == FBS_OK;
+            ctx->err = text;
+        }
+        return rc;
+    }
+    ctx->fold_bodies.swap(bodies);
+    ctx->fold_t = t_f;
+    ctx->fold_gamma = gamma_f;
+    ctx->have_fold = true;
+    return FBS_OK;
+}
+// the parameter range and the shapes are the packing key's (the accumulate kernel is the same one)
+static int check_fold_params(const fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f) {
+    if (t_f < 1 || gamma_f < 1) return set_error(ctx, FBS_E_INVALID, "fold key needs t_f >= 1 and gamma_f >= 1");
+    if (t_f > 31 || gamma_f > 31 || t_f * gamma_f > 31) return set_error(ctx, FBS_E_INVALID, "fold key needs t_f * gamma_f <= 31");
+    if (!pack_shape_built(ctx->p.log_n_poly, ctx->p.k)) return set_error(ctx, FBS_E_INVALID, "no fold kernel for this (k, N)");
+    return FBS_OK;
+}
+
+int fbs_fold_keygen(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "a fold key goes with seeded keys (fbs_keygen_seeded)");
+    if (int rc = check_fold_params(ctx, t_f, gamma_f)) return rc;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> bodies;
+    if (ctx->tune.keys_on_device) {
+        if (int rc = dev_fold_bodies(ctx, t_f, gamma_f, bodies)) return rc;
+    } else {
+        host_fold_keygen(ctx, t_f, gamma_f, bodies);
+    }
+    return install_fold_key(ctx, t_f, gamma_f, bodies);
+} FBS_API_CATCH(ctx)
+
+int fbs_fold_key_sizes(const fbs_ctx *ctx, uint32_t t_f, size_t sizes[2]) try {
+    if (!ctx || !sizes) return FBS_E_INVALID;
+    if (t_f == 0) {
+        if (!ctx->have_fold) return set_error(ctx, FBS_E_STATE, "the context has no fold key");
+        t_f = ctx->fold_t;
+    }
+    if (t_f > 31) return set_error(ctx, FBS_E_INVALID, "fold key needs 1 <= t_f <= 31");
+    sizes[0] = (size_t)ctx->D * t_f * ctx->N;
+    sizes[1] = sizes[0] * (ctx->p.k + 1);
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_export_fold_key(const fbs_ctx *ctx, uint64_t *bodies, uint64_t *full) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (!ctx->have_fold) return set_error(ctx, FBS_E_STATE, "the context has no fold key");
+    if (bodies) std::memcpy(bodies, ctx->fold_bodies.data(), ctx->fold_bodies.size() * 8);
+    if (full) {
+        std::vector<uint64_t> key;
+        host_expand_fold_key(ctx, ctx->mask_key, ctx->fold_t, ctx->fold_bodies.data(), key);
+        std::memcpy(full, key.data(), key.size() * 8);
+    }
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+int fbs_import_fold_key(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, const uint64_t *bodies) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (!bodies) return set_error(ctx, FBS_E_INVALID, "null argument");
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "a fold key goes with seeded keys (fbs_import_seeded_keys)");
+    if (int rc = check_fold_params(ctx, t_f, gamma_f)) return rc;
+    const size_t words = (size_t)ctx->D * t_f * ctx->N;
+    for (size_t i = 0; i < words; i++)
+        if (bodies[i] >= FQ) return set_error(ctx, FBS_E_INVALID, "fold-key body word is not a canonical residue");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> copy(bodies, bodies + words);
+    return install_fold_key(ctx, t_f, gamma_f, copy);
+} FBS_API_CATCH(ctx)
+
+// Ciphertexts per pass: COMPACT_PASS cut down to whole samples (one sample at N = 4096 and above it), and the packing scratch for
+// a pass of that size: D rows of rounded fields and the 64-bit body words, the partial accumulators
+static int fold_reserve(fbs_ctx *ctx, size_t count, size_t *pass_out) {
+    const size_t N = ctx->N, whole = std::max(COMPACT_PASS, N) / N * N;
+    const size_t pass = std::min((count + N - 1) / N * N, whole), samples = pass / N;
+    if (int rc = grow(ctx, ctx->d_pack_fields, ctx->pack_fields_capacity, ((size_t)ctx->D + 2) * pass, 4, true)) return rc;
+    size_t rows = 0;
+    for (size_t g = 1; g <= samples; g++) rows = std::max(rows, g * pack_slices_for(ctx, g, ctx->D));
+    if (int rc = grow(ctx, ctx->d_pack_acc, ctx->pack_acc_capacity, rows * (ctx->p.k + 1) * N, 8, true)) return rc;
+    *pass_out = pass;
+    return FBS_OK;
+}
+static int fold_prologue(const fbs_ctx *ctx, size_t count) {
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    if (!ctx->have_fold) return set_error(ctx, FBS_E_STATE, "the context has no fold key (fbs_fold_keygen / fbs_import_fold_key)");
+    return check_ct_words(ctx, count);   // (the samples are fewer words than the ciphertexts)
+}
+// the passes of fbs_fold_dev; `out` non-null: each pass is folded into d_glwe (staging) and copied to the host array `out`
+static int fold_passes(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, uint64_t *out, size_t pass, hipStream_t s) {
+    const size_t ctw = ctx->D + 1, sw = (size_t)ctx->D + ctx->N;
+    for (size_t f0 = 0; f0 < count; f0 += pass) {
+        const size_t rows = std::min(pass, count - f0), w0 = f0 / ctx->N * sw, words = (rows + ctx->N - 1) / ctx->N * sw;
+        uint64_t *dst = out ? d_glwe : d_glwe + w0;
+        if (int rc = dev_fold(ctx, d_cts + f0 * ctw, rows, dst, s)) return rc;
+        if (out && hipMemcpyAsync(out + w0, dst, words * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+            return set_error(ctx, FBS_E_DEVICE, "copying folded samples to the host failed");
+    }
+    return FBS_OK;
+}
+
+// (no secret needed: runs on evaluation-only contexts)
+int fbs_fold_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, void *stream) try {
+    if (!ctx || (count && (!d_cts || !d_glwe))) return FBS_E_INVALID;
+    if (int rc = fold_prologue(ctx, count)) return rc;
+    if ((uintptr_t)d_glwe & 15u) return set_error(ctx, FBS_E_INVALID, "folded samples are written 16 bytes a lane: d_glwe must be 16-byte aligned");
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    size_t pass = 0;
+    int rc = fold_reserve(ctx, count, &pass);
+    if (rc != FBS_OK) return rc;
+    hipStream_t s = pick(ctx, stream);
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    if ((rc = fold_passes(ctx, d_cts, count, d_glwe, nullptr, pass, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+    return scratch_done(ctx, s);
+} FBS_API_CATCH(ctx)
+
+int fbs_state_fold(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint64_t *out) try {
+    if (!ctx) return FBS_E_INVALID;
+    int rc = check_state_rows(ctx, st, row0, rows, out);
+    if (rc != FBS_OK) return rc;
+    const size_t count = rows * st->T;   // (a state's rows * T * (D + 1) words fit a size_t)
+    if ((rc = fold_prologue(ctx, count)) != FBS_OK) return rc;
+    if (rows == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    size_t pass = 0;
+    if ((rc = fold_reserve(ctx, count, &pass)) != FBS_OK) return rc;
+    if ((rc = grow(ctx, ctx->d_folded, ctx->folded_capacity, pass / ctx->N * ((size_t)ctx->D + ctx->N), 8, true)) != FBS_OK) return rc;
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    if ((rc = fold_passes(ctx, st->d + row0 * st->T * (ctx->D + 1), count, ctx->d_folded, out, pass, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+    if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
+    return sync_stream(ctx, s);
+} FBS_API_CATCH(ctx)
+
+int fbs_state_fold_dev(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint64_t *d_glwe) try {
+    if (!ctx) return FBS_E_INVALID;
+    int rc = check_state_rows(ctx, st, row0, rows, d_glwe);
+    if (rc != FBS_OK) return rc;
+    const size_t count = rows * st->T;
+    if ((rc = fold_prologue(ctx, count)) != FBS_OK) return rc;
+    if ((uintptr_t)d_glwe & 15u) return set_error(ctx, FBS_E_INVALID, "folded samples are written 16 bytes a lane: d_glwe must be 16-byte aligned");
+    if (rows == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    size_t pass = 0;
+    if ((rc = fold_reserve(ctx, count, &pass)) != FBS_OK) return rc;
+    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
+    if ((rc = fold_passes(ctx, st->d + row0 * st->T * (ctx->D + 1), count, d_glwe, nullptr, pass, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
+    return scratch_done(ctx, s);
+} FBS_API_CATCH(ctx)
+
+// the device-source twin of fbs_state_put_public: no staging, no check of the words (device memory), queued on the context's stream
+int fbs_state_unfold_dev(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *d_glwe) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (int rc = check_state_rows(ctx, st, row0, rows, d_glwe)) return rc;
+    if (rows == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_expand_public(ctx, d_glwe, rows * st->T, st->d + row0 * st->T * (ctx->D + 1), ctx->stream);
+} FBS_API_CATCH(ctx)
+
+// test hook of the front kernel alone: d_cts [count][D + 1] -> d_fields [D][cols] uint32 rounded to tg bits, then cols 64-bit body
+// words; cols a multiple of N with count <= cols.  Needs no key.
+int fbs_debug_fold_front_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t cols, uint32_t tg, uint32_t *d_fields, void *stream) try {
+    if (!ctx || !d_fields || (count && !d_cts)) return FBS_E_INVALID;
+    if (tg < 1 || tg > 31) return set_error(ctx, FBS_E_INVALID, "the fields are rounded to 1 .. 31 bits");
+    if (cols == 0 || cols % ctx->N || count > cols || cols > (1u << 20))
+        return set_error(ctx, FBS_E_INVALID, "cols is a multiple of N, at most 2^20, that holds the ciphertexts");
+    if ((uintptr_t)d_fields & 7u) return set_error(ctx, FBS_E_INVALID, "d_fields must be 8-byte aligned");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    return dev_fold_front(ctx, d_cts, count, cols, tg, d_fields, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
 // ---------------------------------------------------------------------------------------------

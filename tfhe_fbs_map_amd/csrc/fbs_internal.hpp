@@ -38,7 +38,8 @@ enum Domain : uint64_t {
     DOM_PACK_MASK = 16, DOM_PACK_NOISE = 17,            // packing key (packed outputs): mask (mask key), noise (context key)
     // public-key inputs (fbs_public.cpp; include/fbs_exec.h, "public-key inputs"): the public key's masks (mask key) and noise
     // (the key holder's noise seed); the encryptor's binary u and its noise, both under the encryptor's own key
-    DOM_PUB_MASK = 18, DOM_PUB_NOISE = 19, DOM_PUB_ENC_U = 20, DOM_PUB_ENC_NOISE = 21
+    DOM_PUB_MASK = 18, DOM_PUB_NOISE = 19, DOM_PUB_ENC_U = 20, DOM_PUB_ENC_NOISE = 21,
+    DOM_FOLD_MASK = 22, DOM_FOLD_NOISE = 23             // fold key (folded state): mask (mask key), noise (context key)
 };
 FBS_HD uint64_t stream_id(Domain d, uint64_t sub) { return ((uint64_t)d << 56) | (sub & 0x00FFFFFFFFFFFFFFull); }
 // the 256-bit ChaCha key of a context: a 64-bit seed followed by a fixed tail (fbs_ctx_create: reproducible, test-grade), or
@@ -207,6 +208,10 @@ struct HostState {
     bool have_pack = false;
     uint32_t pack_t = 0, pack_gamma = 0;
     std::vector<uint64_t> pack_bodies;
+    // Folded state: the fold key's parameters and bodies [D][t_f][N] (the masks come from mask_key)
+    bool have_fold = false;
+    uint32_t fold_t = 0, fold_gamma = 0;
+    std::vector<uint64_t> fold_bodies;
 };
 
 }  // namespace fbs
@@ -262,6 +267,12 @@ struct fbs_ctx : fbs::HostState {
     size_t pack_acc_capacity = 0;    // in words
     uint64_t *d_packed = nullptr;    // staging of fbs_state_fetch_packed's words
     size_t packed_capacity = 0;      // in words
+    // Folded state (fbs_fold.hip): the fold key [D][t_f][k+1][N] in the form of the packing key; its scratch is the packing
+    // scratch (rounded mask fields [D][samples N], then the raw body words; the same partial accumulators)
+    double *d_fold_key = nullptr;
+    size_t fold_key_capacity = 0;    // in words
+    uint64_t *d_folded = nullptr;    // staging of fbs_state_fold's samples
+    size_t folded_capacity = 0;      // in words
     uint64_t *d_pub = nullptr;       // staging of fbs_state_put_public's GLWE samples
     size_t pub_capacity = 0;         // in words
     fbs_tvset *tv_identity = nullptr;   // the identity table [0, 1, .., p - 1], made on first use: what refreshes a compact input
@@ -439,6 +450,11 @@ void host_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count
 // host_packing_keygen -> bodies [n][t_p][N]; host_expand_packing_key: (mask key, bodies) -> the whole key [n][t_p][k+1][N]
 void host_packing_keygen(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies);
 void host_expand_packing_key(const fbs_ctx *ctx, const RandKey &mask_key, uint32_t t_p, const uint64_t *bodies, std::vector<uint64_t> &full);
+// Folded state (include/fbs_exec.h, "folded state").  Row r = i t_f + v of the fold key, i < D: the packing key's row with
+// sk_glwe[i] (word i of the flattened big key) for sk_lwe[i] and the streams (DOM_FOLD_MASK, r), (DOM_FOLD_NOISE, r).
+// host_fold_keygen -> bodies [D][t_f][N]; host_expand_fold_key: (mask key, bodies) -> the whole key [D][t_f][k+1][N]
+void host_fold_keygen(const fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, std::vector<uint64_t> &bodies);
+void host_expand_fold_key(const fbs_ctx *ctx, const RandKey &mask_key, uint32_t t_f, const uint64_t *bodies, std::vector<uint64_t> &full);
 // packed words of `count` outputs at width `bits` -> msgs[count] under sk_glwe
 void host_decrypt_packed(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs);
 int host_build_tv(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint64_t *tv, uint64_t *post_add);
@@ -468,9 +484,10 @@ int dev_transform_bsk(fbs_ctx *ctx, const uint64_t *d_src);
 // and the tables are on the device, both evaluation keys made there (seeded: host_keygen_seeded under `mask_key`, else host_keygen)
 // or, bsk_bodies / ksk_bodies (host arrays) non-null, expanded there (host_expand_seeded_keys under `mask_key`; no secret); the
 // bootstrapping key transformed from the device rows, and ctx->bsk / ctx->ksk filled from them.  dev_packing_bodies:
-// host_packing_keygen's bodies [n][t_p][N]
+// host_packing_keygen's bodies [n][t_p][N]; dev_fold_bodies: host_fold_keygen's bodies [D][t_f][N]
 int dev_make_keys(fbs_ctx *ctx, bool seeded, const RandKey &mask_key, const uint64_t *bsk_bodies, const uint64_t *ksk_bodies);
 int dev_packing_bodies(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies);
+int dev_fold_bodies(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, std::vector<uint64_t> &bodies);
 int dev_keyswitch_gemm_setup(fbs_ctx *ctx);   // limb fragments of the key-switching key for the int8 MFMA key switch
 // the key switch kN -> n and the rounding of every word to Z_(2^log2_mod) (log2(2N): what the blind rotation reads; up to 31: the
 // fields of compact outputs), into d_ms [gv.ks_count][n + 1]
@@ -521,12 +538,22 @@ int dev_decrypt_compact(const fbs_ctx *ctx, const uint64_t *d_words, size_t coun
 int dev_compact_unpack(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint32_t *d_ms, hipStream_t stream);
 
 // packed outputs (fbs_pack.hip).  dev_upload_packing_key: the whole key in the coefficient domain -> d_pack_key (transformed on
-// the device; blocks).  pack_slices_for: slices per sample of a launch of `samples` packed samples.  dev_pack: the switched
-// 31-bit fields d_ms [count][n + 1] of ciphertexts that start a packed sample -> packed words at width `bits`; uses d_pack_fields
-// ((n + 1) * samples * N words) and d_pack_acc (samples * slices * (k + 1) * N words), which the caller has sized
+// the device; blocks); dev_upload_fold_key: the same for the fold key [D][t_f][k+1][N] -> d_fold_key.  pack_slices_for: slices
+// per sample of a launch of `samples` samples whose sum runs over `rows` key rows (n for packing, D for folding).  dev_pack: the
+// switched 31-bit fields d_ms [count][n + 1] of ciphertexts that start a packed sample -> packed words at width `bits`; uses
+// d_pack_fields ((n + 1) * samples * N words) and d_pack_acc (samples * slices * (k + 1) * N words), which the caller has sized
 int dev_upload_packing_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_p);
-uint32_t pack_slices_for(const fbs_ctx *ctx, size_t samples);
+int dev_upload_fold_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_f);
+uint32_t pack_slices_for(const fbs_ctx *ctx, size_t samples, uint32_t rows);
 int dev_pack(fbs_ctx *ctx, const uint32_t *d_ms, size_t count, uint32_t bits, uint64_t *d_words, hipStream_t stream);
+// k_pack_accumulate alone, on the fields, key and row count of `a` (fbs_pack.hpp): samples * a.slices workgroups
+struct PackArgs;
+int dev_pack_accumulate(const fbs_ctx *ctx, const PackArgs &a, size_t samples, hipStream_t stream);
+// folded state (fbs_fold.hip).  dev_fold: the big-key ciphertexts d_cts [count][D + 1] that start a folded sample -> the samples
+// d_glwe [ceil(count / N)][k + 1][N]; uses d_pack_fields (D * samples * N + 2 * samples * N words) and d_pack_acc, which the caller
+// has sized.  dev_fold_front: its first kernel alone, d_cts -> d_fields [D][cols] rounded to tg bits, then cols body words
+int dev_fold(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, hipStream_t stream);
+int dev_fold_front(const fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t cols, uint32_t tg, uint32_t *d_fields, hipStream_t stream);
 
 // audited evaluation (fbs_audit.hip): errors of the big-key ciphertexts in slots d_row_slot[rows], samples [s_begin, s_begin + s_count),
 // against d_expected [rows][s_count] -> d_err [rows][s_count] (wire units); of the switched fields d_ms [rows * s_count][n + 1] at

@@ -319,9 +319,11 @@ int dev_make_keys(fbs_ctx *ctx, bool seeded, const RandKey &mask_key, const uint
     return FBS_OK;
 }
 
-int dev_packing_bodies(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies) {
+// bodies [src_rows][t][N] of gadget_key_bodies (fbs_host.cpp): ROWS_PACK rows whose bit is bit i of `d_src_bits`
+static int dev_gadget_bodies(fbs_ctx *ctx, size_t src_rows, const uint32_t *d_src_bits, Domain mask_dom, Domain noise_dom, uint32_t t,
+                             uint32_t gamma, std::vector<uint64_t> &bodies) {
     const uint32_t N = ctx->N, k = ctx->p.k;
-    const size_t n_rows = (size_t)ctx->p.n * t_p;
+    const size_t n_rows = src_rows * t;
     if (!ctx->d_tw_fwd || !ctx->d_sk_bits) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
     bodies.assign(n_rows * N, 0);
     if (!n_rows) return FBS_OK;
@@ -334,19 +336,19 @@ int dev_packing_bodies(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector
     ga.tw_fwd = reinterpret_cast<const double *>(ctx->d_tw_fwd);
     ga.tw_inv = reinterpret_cast<const double *>(ctx->d_tw_inv);
     ga.sk_glwe_bits = ctx->d_sk_bits;
-    ga.sk_lwe_bits = ctx->d_sk_lwe_bits;
+    ga.sk_lwe_bits = d_src_bits;   // (ROWS_PACK reads the bit of "sample" i here: the small key's, or for the fold key the big key's)
     ga.mask_key = ctx->mask_key;
     ga.noise_key = ctx->rkey;
-    ga.mask_dom = DOM_PACK_MASK;
-    ga.noise_dom = DOM_PACK_NOISE;
+    ga.mask_dom = mask_dom;
+    ga.noise_dom = noise_dom;
     ga.n_rows = n_rows;
     ga.mode = ROWS_PACK;
     ga.k = k;
-    ga.l = ga.rows_per_sample = t_p;   // row r = i t_p + v: "sample" i, level v
+    ga.l = ga.rows_per_sample = t;   // row r = i t + v: "sample" i, level v
     ga.group = 1;
     ga.sampler = ctx->p.sampler;
     ga.sigma = ctx->p.sigma_glwe;
-    for (uint32_t v = 0; v < t_p; v++) ga.gadget[v] = pack_gadget(gamma_p, v);
+    for (uint32_t v = 0; v < t; v++) ga.gadget[v] = pack_gadget(gamma, v);
     int rc = launch_glwe_rows(ctx, ga);
     if (rc == FBS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_error(ctx, FBS_E_DEVICE, "packing-key rows failed");
     const int wiped = wipe(ctx, s_hat, (size_t)k * N * 8);
@@ -354,6 +356,14 @@ int dev_packing_bodies(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector
     if (wiped != FBS_OK) return wiped;
     FBS_HIP(ctx, hipMemcpy(bodies.data(), d_bodies.p, bodies.size() * 8, hipMemcpyDeviceToHost));
     return FBS_OK;
+}
+
+int dev_packing_bodies(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies) {
+    return dev_gadget_bodies(ctx, ctx->p.n, ctx->d_sk_lwe_bits, DOM_PACK_MASK, DOM_PACK_NOISE, t_p, gamma_p, bodies);
+}
+
+int dev_fold_bodies(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, std::vector<uint64_t> &bodies) {
+    return dev_gadget_bodies(ctx, ctx->D, ctx->d_sk_bits, DOM_FOLD_MASK, DOM_FOLD_NOISE, t_f, gamma_f, bodies);
 }
 
 }  // namespace fbs

@@ -31,6 +31,8 @@
 // Not reachable from the coefficient side: the lazy accumulator at its worst, 16 same-signed products near 0.8 q in the transform
 // domain; that rests on the arithmetic stated at PACK_CENTRE_EVERY (16 x 0.8 q + q / 2 < 2^52).
 // None of these is a key-switch or blind-rotation launch: they are not in fbs_kernel_catalog and the profile does not count them.
+// k_pack_accumulate is generic in its row count and field source (PackArgs.n, fields, key: fbs_pack.hpp): folded state
+// (fbs_fold.hip) launches it through dev_pack_accumulate with n := D, the fold's fields and the fold key, as it stands.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -62,17 +64,6 @@ __global__ __launch_bounds__(256) void k_pack_transpose(const uint32_t *__restri
         out[(size_t)i * cols + j0 + tx] = i + 1 < n1 ? pack_round_mask(x, tg) : x;
     }
 }
-
-struct PackArgs {
-    const uint32_t *fields;   // [n + 1][cols]: rounded mask fields, then the raw body fields
-    const double *key;        // [n][t][k + 1][N]
-    double *acc;              // [samples][slices][k + 1][N]
-    const double *tw_fwd, *tw_inv;
-    uint64_t *words;          // packed output of the launch
-    size_t count;             // ciphertexts of the launch
-    size_t sample_words;      // words of a full sample
-    uint32_t n, t, gamma, cols, slices, bits;
-};
 
 template <int LOGN, int LL, int K1>
 __global__ __launch_bounds__(1 << LL) void k_pack_accumulate(PackArgs a) {
@@ -180,8 +171,8 @@ __global__ __launch_bounds__(1 << LL) void k_pack_finish(PackArgs a, uint32_t k1
 // the shapes a context can have (check_kernel_built): k = 1 at N = 256 .. 4096, and the GLWE shapes of fbs_select.hpp
 #define FBS_PACK_SHAPES(X) X(8, 2) X(9, 2) X(10, 2) X(11, 2) X(12, 2) FBS_GLWE_SHAPES(X)
 
-uint32_t pack_slices_for(const fbs_ctx *ctx, size_t samples) {
-    const uint32_t cap = std::min<uint32_t>(PACK_MAX_SLICES, ctx->p.n);
+uint32_t pack_slices_for(const fbs_ctx *ctx, size_t samples, uint32_t rows) {
+    const uint32_t cap = std::min<uint32_t>(PACK_MAX_SLICES, rows);
     if (ctx->tune.pack_slices > 0) return (uint32_t)std::min<int64_t>(ctx->tune.pack_slices, cap);
     // one wave per SIMD where a polynomial is one wave; a workgroup per CU where it is four
     const int ll = lanes_log2_for((int)ctx->p.log_n_poly);
@@ -189,19 +180,22 @@ uint32_t pack_slices_for(const fbs_ctx *ctx, size_t samples) {
     return (uint32_t)std::min<size_t>(cap, std::max<size_t>(1, room / std::max<size_t>(1, samples)));
 }
 
-int dev_upload_packing_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_p) {
+// a key of `src_rows` x `t` GLWE rows (the packing key: n rows of the small key; the fold key: D words of the big key), whole
+// and in the coefficient domain, -> `d_key` in the transform domain
+static int upload_gadget_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t src_rows, uint32_t t, double *&d_key,
+                             size_t &key_capacity) {
     const uint32_t N = ctx->N, k1 = ctx->p.k + 1;
-    const size_t polys = (size_t)ctx->p.n * t_p * k1, words = polys * N;
+    const size_t polys = (size_t)src_rows * t * k1, words = polys * N;
     if (full.size() != words) return set_error(ctx, FBS_E_INVALID, "packing key of the wrong size");
     if (!ctx->d_tw_fwd) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
     if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));   // kernels may still read the old key
     FBS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (words > ctx->pack_key_capacity) {
-        if (ctx->d_pack_key) (void)hipFree(ctx->d_pack_key);
-        ctx->d_pack_key = nullptr;
-        ctx->pack_key_capacity = 0;
-        FBS_HIP(ctx, hipMalloc(&ctx->d_pack_key, words * 8));
-        ctx->pack_key_capacity = words;
+    if (words > key_capacity) {
+        if (d_key) (void)hipFree(d_key);
+        d_key = nullptr;
+        key_capacity = 0;
+        FBS_HIP(ctx, hipMalloc(&d_key, words * 8));
+        key_capacity = words;
     }
     uint64_t *d_src = nullptr;
     FBS_HIP(ctx, hipMalloc(&d_src, words * 8));
@@ -214,8 +208,7 @@ int dev_upload_packing_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint
 #define X(L)                                                                                                                    \
     case L:                                                                                                                     \
         hipLaunchKernelGGL((k_key_transform<L, lanes_log2_for(L), KeyWords>), dim3(grid), dim3(1 << lanes_log2_for(L)), 0,     \
-                           ctx->stream, KeyWords{d_src}, ctx->d_pack_key, reinterpret_cast<const double *>(ctx->d_tw_fwd), n_inv, \
-                           polys);                                                                                              \
+                           ctx->stream, KeyWords{d_src}, d_key, reinterpret_cast<const double *>(ctx->d_tw_fwd), n_inv, polys);               \
         launched = true;                                                                                                        \
         break;
             X(8) X(9) X(10) X(11) X(12)
@@ -227,6 +220,30 @@ int dev_upload_packing_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint
     (void)hipFree(d_src);
     if (e != hipSuccess) return set_error(ctx, FBS_E_DEVICE, std::string("packing-key transform: ") + hipGetErrorString(e));
     if (!launched) return set_error(ctx, FBS_E_INVALID, "no packing kernel for this polynomial size");
+    return FBS_OK;
+}
+
+int dev_upload_packing_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_p) {
+    return upload_gadget_key(ctx, full, ctx->p.n, t_p, ctx->d_pack_key, ctx->pack_key_capacity);
+}
+int dev_upload_fold_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_f) {
+    return upload_gadget_key(ctx, full, ctx->D, t_f, ctx->d_fold_key, ctx->fold_key_capacity);
+}
+
+// k_pack_accumulate on the fields, key and row count of `a` (a.n = n: packing; a.n = D: folding): samples * a.slices workgroups
+int dev_pack_accumulate(const fbs_ctx *ctx, const PackArgs &a, size_t samples, hipStream_t stream) {
+    const uint32_t k1 = ctx->p.k + 1;
+    bool launched = false;
+#define X(L, K1)                                                                                                                \
+    if (ctx->p.log_n_poly == L && k1 == K1) {                                                                                   \
+        hipLaunchKernelGGL((k_pack_accumulate<L, lanes_log2_for(L), K1>), dim3((unsigned)(samples * a.slices)),                 \
+                           dim3(1 << lanes_log2_for(L)), 0, stream, a);                                                         \
+        launched = true;                                                                                                        \
+    }
+    FBS_PACK_SHAPES(X)
+#undef X
+    if (!launched) return set_error(ctx, FBS_E_INVALID, "no packing kernel for this (k, N)");
+    FBS_HIP(ctx, hipGetLastError());
     return FBS_OK;
 }
 
@@ -247,18 +264,17 @@ int dev_pack(fbs_ctx *ctx, const uint32_t *d_ms, size_t count, uint32_t bits, ui
     a.t = ctx->pack_t;
     a.gamma = ctx->pack_gamma;
     a.cols = (uint32_t)(samples * N);
-    a.slices = pack_slices_for(ctx, samples);
+    a.slices = pack_slices_for(ctx, samples, n);
     a.bits = bits;
     if ((size_t)(n + 1) * a.cols > ctx->pack_fields_capacity || samples * a.slices * k1 * N > ctx->pack_acc_capacity)
         return set_error(ctx, FBS_E_INVALID, "packing scratch too small for the launch");
     hipLaunchKernelGGL(k_pack_transpose, dim3((n + 1 + 63) / 64, a.cols / 64), dim3(256), 0, stream, d_ms, n + 1, count, a.cols,
                        a.t * a.gamma, ctx->d_pack_fields);
     FBS_HIP(ctx, hipGetLastError());
+    if (int rc = dev_pack_accumulate(ctx, a, samples, stream)) return rc;
     bool launched = false;
 #define X(L, K1)                                                                                                                \
     if (ctx->p.log_n_poly == L && k1 == K1) {                                                                                   \
-        hipLaunchKernelGGL((k_pack_accumulate<L, lanes_log2_for(L), K1>), dim3((unsigned)(samples * a.slices)),                 \
-                           dim3(1 << lanes_log2_for(L)), 0, stream, a);                                                         \
         hipLaunchKernelGGL((k_pack_finish<L, lanes_log2_for(L)>), dim3((unsigned)(samples * k1)), dim3(1 << lanes_log2_for(L)), 0, \
                            stream, a, k1);                                                                                      \
         launched = true;                                                                                                        \

@@ -67,4 +67,19 @@ FBS_HD uint64_t pack_lift_body(uint32_t m) {
     return ((uint64_t)m << 15) + (uint64_t)(((int64_t)(1ll << 30) - (int64_t)m * 507903) >> 31);
 }
 
+
+#ifndef FBS_HOST_ONLY
+// what the accumulate kernel reads (fbs_pack.hip), shared with the fold (fbs_fold.hip), whose rows are the D words of the big key
+struct PackArgs {
+    const uint32_t *fields;   // [n + 1][cols]: rounded mask fields, then the raw body fields (folding: [n][cols], then 64-bit bodies)
+    const double *key;        // [n][t][k + 1][N]
+    double *acc;              // [samples][slices][k + 1][N]
+    const double *tw_fwd, *tw_inv;
+    uint64_t *words;          // packed output of the launch (folding: the samples [k + 1][N])
+    size_t count;             // ciphertexts of the launch
+    size_t sample_words;      // words of a full sample
+    uint32_t n, t, gamma, cols, slices, bits;
+};
+#endif
+
 }  // namespace fbs

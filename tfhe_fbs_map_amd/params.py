@@ -233,6 +233,52 @@ def public_input_factor(prm: Params) -> float:
     return public_input_variance(prm) / variances(prm)[0]
 
 
+# ---- folded state (include/fbs_exec.h, "folded state") ---------------------------------------------------------------------------
+def folded_state_variance(prm: Params, t_f: int, gamma_f: int) -> float:
+    """Phase variance, in torus units, that a fold adds to each ciphertext it holds (and an unfold gives back unchanged: sample
+    extraction is exact).  Modelled as the packing key is in `packed_output_variance`, with the D = k N words of the big key in
+    place of the n of the small one: D t_f N balanced digits of variance (2^(2 gamma_f) + 2) / 12 against sigma_glwe, and the
+    rounding of the D mask words to t_f gamma_f bits seen through a binary key.  Neither sigma_lwe nor any transport rounding
+    enters: the key switch is taken straight from the big key and the sample keeps every bit."""
+    s_glwe = prm.sigma_glwe / float(MODULUS)
+    D = prm.k * prm.N
+    return D * t_f * prm.N * (2.0 ** (2 * gamma_f) + 2.0) / 12.0 * s_glwe ** 2 + (D / 2.0) * 2.0 ** (-2 * t_f * gamma_f) / 12.0
+
+
+def folded_state_skew(prm: Params) -> float:
+    """`packed_output_skew` for a fold: the D mask words are rounded with q treated as 2^46, each off by at most (2^46 - q) / 2^46
+    of the torus; the body is not rounded at all."""
+    return prm.k * prm.N * float((1 << MODULUS_BITS) - MODULUS) / float(1 << MODULUS_BITS)
+
+
+def folded_state_factor(prm: Params, t_f: int, gamma_f: int) -> float:
+    """`folded_state_variance` in units of one blind rotation's output variance, the unit `split.plan_chain` counts in"""
+    return folded_state_variance(prm, t_f, gamma_f) / variances(prm)[0]
+
+
+def folded_margin(prm: Params, norm2: float, t_f: int, gamma_f: int) -> float:
+    """`margin_sigmas(prm, norm2)` recomputed with v_br (1 + folded_state_factor) in place of v_br: every input of the linear
+    combination has been through one fold since its bootstrap"""
+    v_br, v_ks, v_ms = variances(prm)
+    v_br += folded_state_variance(prm, t_f, gamma_f)
+    return (1.0 / (4.0 * prm.p_msg)) / math.sqrt(norm2 * v_br + v_ks + v_ms)
+
+
+def fold_choice(prm: Params, norm2: float = 1.0, min_margin: float = 6.0):
+    """(t_f, gamma_f) of the fold key for programs of that norm2: the fewest levels t_f at which some digit width keeps
+    `folded_margin` at or above `min_margin`, and at that level count the gamma_f of least `folded_state_variance` (t_f gamma_f <=
+    31).  The last resort, when no choice reaches the margin: the (t_f, gamma_f) of least variance over all of them -- the fold then
+    costs as little margin as it can, and `split.plan_chain` refreshes the link if its own rule refuses it."""
+    best = None
+    for t_f in range(1, 32):
+        gamma_f = min(range(1, 31 // t_f + 1), key=lambda g: folded_state_variance(prm, t_f, g))
+        if folded_margin(prm, norm2, t_f, gamma_f) >= min_margin:
+            return t_f, gamma_f
+        if best is None or folded_state_variance(prm, t_f, gamma_f) < folded_state_variance(prm, *best):
+            best = (t_f, gamma_f)
+    return best
+
+
 def p_error(margin: float) -> float:
     """Probability that a Gaussian leaves +-margin standard deviations (one bootstrap)."""
     return math.erfc(margin / math.sqrt(2.0))

@@ -66,6 +66,7 @@ they enter unrefreshed (`params.public_input_factor`).  IND-CPA only and malleab
 from __future__ import annotations
 
 import hashlib
+import math
 from dataclasses import asdict, dataclass
 
 import numpy as np
@@ -176,6 +177,9 @@ class ServerKey:
     packing_bodies: np.ndarray | None = None   # [n][t_p][N] bodies of the packing key (packed outputs); None: the key has none
     packing_levels: int = 0                    # t_p
     packing_base_bits: int = 0                 # gamma_p
+    fold_bodies: np.ndarray | None = None      # [D][t_f][N] bodies of the fold key (folded state); None: the key has none
+    fold_levels: int = 0                       # t_f
+    fold_base_bits: int = 0                    # gamma_f
 
     def __post_init__(self):
         self.mask_key = bytes(self.mask_key)
@@ -197,6 +201,17 @@ class ServerKey:
                 raise ValueError(f"a packing key of {t} levels of {g} bits")
             if self.packing_bodies.size != self.params.n * t * self.params.N:
                 raise ValueError(f"packing_bodies has {self.packing_bodies.size} words, the parameter set needs {self.params.n * t * self.params.N}")
+        if self.fold_bodies is None:
+            self.fold_levels = self.fold_base_bits = 0
+        else:
+            t, g = int(self.fold_levels), int(self.fold_base_bits)
+            self.fold_levels, self.fold_base_bits = t, g
+            self.fold_bodies = np.ascontiguousarray(self.fold_bodies, np.uint64).reshape(-1)
+            want = self.params.k * self.params.N * t * self.params.N
+            if t < 1 or g < 1 or t * g > 31:
+                raise ValueError(f"a fold key of {t} levels of {g} bits")
+            if self.fold_bodies.size != want:
+                raise ValueError(f"fold_bodies has {self.fold_bodies.size} words, the parameter set needs {want}")
 
     @property
     def fingerprint(self) -> bytes:
@@ -207,7 +222,8 @@ class ServerKey:
         np.savez(path, kind=np.array("server_key"), format_version=np.array(FORMAT_VERSION),
                  params=np.array([int(prm[f]) for f in _PARAM_FIELDS], np.int64), fuse_tables=np.array(bool(self.fuse_tables)),
                  mask_key=np.frombuffer(self.mask_key, np.uint8), fingerprint=np.frombuffer(self.fingerprint, np.uint8),
-                 bsk_bodies=self.bsk_bodies, ksk_bodies=self.ksk_bodies, **self._packing_fields(), **self._sampler_field())
+                 bsk_bodies=self.bsk_bodies, ksk_bodies=self.ksk_bodies, **self._packing_fields(), **self._fold_fields(),
+                 **self._sampler_field())
 
     def _sampler_field(self):
         """the noise sampler of the parameter set, beside the other parameters (a key of sampler 0 is written exactly as before:
@@ -221,6 +237,19 @@ class ServerKey:
             return {}
         return dict(packing_bodies=self.packing_bodies, packing_levels=np.array(self.packing_levels, np.int64),
                     packing_base_bits=np.array(self.packing_base_bits, np.int64))
+
+    def _fold_fields(self):
+        """the optional fold key of a saved server key (a key without one is written exactly as before)"""
+        if self.fold_bodies is None:
+            return {}
+        return dict(fold_bodies=self.fold_bodies, fold_levels=np.array(self.fold_levels, np.int64),
+                    fold_base_bits=np.array(self.fold_base_bits, np.int64))
+
+    @property
+    def fold_factor(self):
+        """what one fold under this key adds to a ciphertext, in units of a blind rotation's output variance (None: no fold key)"""
+        from .params import folded_state_factor
+        return None if self.fold_bodies is None else folded_state_factor(self.params, self.fold_levels, self.fold_base_bits)
 
     @classmethod
     def load(cls, path):
@@ -238,6 +267,10 @@ class ServerKey:
                 raise ValueError("key bodies are uint64 words")
             packing = dict(packing_bodies=d["packing_bodies"], packing_levels=int(d["packing_levels"]),
                            packing_base_bits=int(d["packing_base_bits"]))
+        if "fold_bodies" in d:
+            if d["fold_bodies"].dtype != np.uint64:
+                raise ValueError("key bodies are uint64 words")
+            packing.update(fold_bodies=d["fold_bodies"], fold_levels=int(d["fold_levels"]), fold_base_bits=int(d["fold_base_bits"]))
         key = cls(prm, bool(d["fuse_tables"]), np.asarray(d["mask_key"], np.uint8).tobytes(), d["bsk_bodies"], d["ksk_bodies"], **packing)
         if _fingerprint_of(d) != key.fingerprint:
             raise ValueError("the saved fingerprint is not the mask key's")
@@ -442,6 +475,52 @@ class PackedOutputs:
         return cls(names, T, bits, words, _fingerprint_of(d), _norm2_of(d, len(names)))
 
 
+def folded_words(prm, count):
+    """Words of `count` ciphertexts folded (include/fbs_exec.h, "folded state"): ceil(count / N) samples of (k + 1) N words"""
+    return -(-int(count) // prm.N) * (prm.k + 1) * prm.N
+
+
+class FoldedOutputs:
+    """Folded state (`ResidentOutputs.fold`): the n_outputs * T output ciphertexts, flattened [output][sample], written N at a time
+    into full-precision GLWE samples under the client's big key -- (k + 1) N words for N bits, against (D + 1) N full.  `words` is
+    the flat array `folded_words(params, n_outputs * T)` long: a numpy array, or (device=True) an int64 torch tensor that stays on
+    the card.  A source of `Server.run_chain` that links in unrefreshed, like a public-key input (`plan_chain`: out_norm2 +
+    fold_factor); `Server.restore` turns it back into `ResidentOutputs`, `Client.decrypt` reads it."""
+
+    def __init__(self, output_names, T, words, fingerprint, out_norm2=None, fold_factor=0.0):
+        self.output_names, self.T, self.fingerprint = list(output_names), int(T), bytes(fingerprint)
+        self.words = words
+        self.out_norm2 = None if out_norm2 is None else np.asarray(out_norm2, np.float64).reshape(-1)
+        self.fold_factor = float(fold_factor)   # what the fold added, in units of a blind rotation's output variance
+
+    @property
+    def on_device(self):
+        return not isinstance(self.words, np.ndarray)
+
+    def host_words(self):
+        """the words as a numpy array (a device-held one is fetched)"""
+        if self.on_device:
+            return self.words.cpu().numpy().view(np.uint64)
+        return np.ascontiguousarray(self.words, np.uint64).reshape(-1)
+
+    def save(self, path):
+        np.savez(path, kind=np.array("folded_outputs"), format_version=np.array(FORMAT_VERSION),
+                 output_names=np.array(list(self.output_names), dtype=str), T=np.array(self.T, np.int64), words=self.host_words(),
+                 fingerprint=np.frombuffer(self.fingerprint, np.uint8), fold_factor=np.array(self.fold_factor, np.float64),
+                 **_norm2_fields(self))
+
+    @classmethod
+    def load(cls, path):
+        d = _load_npz(path, "folded_outputs")
+        names = [str(n) for n in np.asarray(d["output_names"]).reshape(-1)]
+        T, words, factor = int(d["T"]), np.asarray(d["words"]), float(d["fold_factor"])
+        if T < 0 or not np.isfinite(factor) or factor < 0:
+            raise ValueError(f"folded outputs of {T} samples, fold factor {factor}")
+        if words.dtype != np.uint64 or words.ndim != 1:
+            raise ValueError(f"folded words of shape {words.shape} and type {words.dtype}")
+        return cls(names, T, words, _fingerprint_of(d), _norm2_of(d, len(names)), factor)
+
+
 class ResidentOutputs:
     """Full output ciphertexts of one evaluation that stayed on the server's GPU (`Server.run` / `Server.run_chain` with
     `resident=True`): row o of `state` (a `DeviceState`, [n_outputs][T][D+1]) is output o.  A source of `Server.run_chain` on the
@@ -480,6 +559,18 @@ class ResidentOutputs:
         if bits is None:
             raise ValueError("no default compact width is recorded for these outputs: pass bits")
         return CompactOutputs(list(self.output_names), self.T, int(bits), self.state.fetch(bits=int(bits)), self.fingerprint, self.out_norm2)
+
+    def fold(self, device=False) -> "FoldedOutputs":
+        """-> `FoldedOutputs`: every row folded on the GPU with the server key's fold key (include/fbs_exec.h, "folded state"), 24
+        bytes a bit at k = 2 where the rows hold 16 392.  device=True: the words stay on the card (a torch tensor); else only they
+        cross the bus.  The rows themselves are untouched: close them to free their memory."""
+        if self.closed:
+            raise ValueError("the resident outputs are closed")
+        if self.server is None or self.server.key.fold_bodies is None:
+            raise ValueError("the server key holds no fold key (Client(..., folding=True))")
+        out_norm2 = np.ones(len(self.output_names)) if self.out_norm2 is None else self.out_norm2
+        return FoldedOutputs(list(self.output_names), self.T, self.state.fold(device=bool(device)), self.fingerprint, out_norm2,
+                             self.server.key.fold_factor)
 
     # -- sample-axis operations (include/fbs_exec.h): views that read the samples through an index, and sums of runs of samples --
     def samples(self, index, fill=0, names=None) -> "SampleView":
@@ -620,8 +711,11 @@ class Client:
     p any of them needs and the set `config.params_choice(p, max norm2)` over all of them; tables share rotations only when
     `config.fuse_tables is True`.  With programs=() the choice is `env`'s alone, as before."""
 
-    def __init__(self, env, config: ExecConfig | None = None, programs=(), packing=False, host=None):
-        """packing=True: the server key also carries a packing key (`Server.run_packed`, `PackedOutputs`), at the parameters
+    def __init__(self, env, config: ExecConfig | None = None, programs=(), packing=False, host=None, folding=False):
+        """folding=True: the server key also carries a fold key (`ResidentOutputs.fold`, `FoldedOutputs`), at the parameters
+        `params.fold_choice` gives for the largest norm2 of env and of every program and the margin the config chose the set for.
+        The fold keygen is the GPU library's: with host=True it raises NotImplementedError.
+        packing=True: the server key also carries a packing key (`Server.run_packed`, `PackedOutputs`), at the parameters
         `params.packing_choice` gives for the noisiest output of env and of every program; False (default): keys and files are
         what they were without it.
         host: where the client's own work runs.  True: on the host alone, through the client library (`HostContext`: no GPU, no
@@ -633,6 +727,8 @@ class Client:
         self._low = env.lower()
         self.params, self.fuse_tables = client_choice(env, cfg, programs)
         self.host = _host_client(host)
+        if folding and self.host:
+            raise NotImplementedError("the fold keygen is in the GPU library (libfbsexec.so) only: Client(..., host=False, folding=True)")
         if self.host:
             from ._client_native import HostContext
             self.ctx = HostContext(self.params, seed=cfg.key_seed(), keygen=False)
@@ -649,6 +745,13 @@ class Client:
             worst = max(output_noise_factor(e.lower(), p, self.fuse_tables) for e in everything)
             self.packing = packing_choice(self.params, norm2, max(worst, 1.0))
             self.ctx.packing_keygen(*self.packing[:2])
+        self.folding = None
+        if folding:
+            from .params import fold_choice
+            everything = [env] + [e for e in programs if e is not env]
+            norm2 = max((e.fusion_stats(self.params.p_msg) if self.fuse_tables else e.stats())["norm2_linprod"] for e in everything)
+            self.folding = fold_choice(self.params, norm2, float(getattr(cfg, "min_margin", 6.0)))
+            self.ctx.fold_keygen(*self.folding)
         self._server_key = None
         self._public_key = None
 
@@ -657,6 +760,8 @@ class Client:
             packing = {}
             if self.packing:
                 packing = {k: v for k, v in self.ctx.export_packing_key().items() if k.startswith("packing_")}
+            if self.folding:
+                packing.update(self.ctx.export_fold_key())
             self._server_key = ServerKey(self.params, self.fuse_tables, **self.ctx.export_seeded_keys(), **packing)
         return self._server_key
 
@@ -692,14 +797,21 @@ class Client:
         return EncryptedInputs(list(names), T, first, bodies.reshape(len(names), T), self.fingerprint)
 
     def decrypt(self, outputs, env=None):
-        """EncryptedOutputs, CompactOutputs or PackedOutputs -> exactly what `LutExecEnv.eval` returns: {output name: np.ndarray of ints},
+        """EncryptedOutputs, CompactOutputs, PackedOutputs or FoldedOutputs (expanded on the host first) -> exactly what `LutExecEnv.eval` returns: {output name: np.ndarray of ints},
         constant outputs as python ints.  env: the program that computed them (None: the client's own; any program of a chain)."""
         low = self._low if env is None else env.lower()
         if outputs.fingerprint != self.fingerprint:
             raise ValueError("outputs were computed under another server key")
         if list(outputs.output_names) != list(low["out_names"]):
             raise ValueError("outputs belong to another program")
-        if isinstance(outputs, PackedOutputs):
+        if isinstance(outputs, FoldedOutputs):
+            from . import _public_native
+            count, words = len(low["out_names"]) * int(outputs.T), outputs.host_words()
+            if words.size != folded_words(self.params, count):
+                raise ValueError(f"{words.size} folded words do not fit this parameter set and {count} outputs")
+            cts = _public_native.expand(self.params, words, count) if count else np.zeros((0, self.params.ct_words), np.uint64)
+            out = (self.ctx.decrypt(cts) if count else np.zeros(0, np.int64)).reshape(len(low["out_names"]), int(outputs.T))
+        elif isinstance(outputs, PackedOutputs):
             bits, count = int(outputs.bits), len(low["out_names"]) * int(outputs.T)
             words = np.ascontiguousarray(outputs.words, np.uint64).reshape(-1)
             if not self.params.log_n_poly + 1 <= bits <= 31 or words.size != packed_words(self.params, count, bits):
@@ -731,6 +843,8 @@ class Server:
                                            device=device, device_keys=device_keys)
         if server_key.packing_bodies is not None:
             self.ctx.import_packing_key(server_key.packing_levels, server_key.packing_base_bits, server_key.packing_bodies)
+        if server_key.fold_bodies is not None:
+            self.ctx.import_fold_key(server_key.fold_levels, server_key.fold_base_bits, server_key.fold_bodies)
         self.max_programs = max_programs
         self._programs = {}
 
@@ -843,9 +957,24 @@ class Server:
 
     def restore(self, outputs: EncryptedOutputs, compact_bits=None) -> "ResidentOutputs":
         """An `EncryptedOutputs` (a `ResidentOutputs.fetch()`, possibly saved and loaded) back into device memory
-        (fbs_state_put).  compact_bits: the default width of a later fetch(compact=True) (None: it has to be passed then)."""
+        (fbs_state_put).  compact_bits: the default width of a later fetch(compact=True) (None: it has to be passed then).
+        A `FoldedOutputs` is expanded on the GPU by sample extraction (no key; a device-held one without a host copy); the rows
+        then carry out_norm2 + fold_factor."""
         if outputs.fingerprint != self.key.fingerprint:
             raise ValueError("outputs were computed under another server key")
+        if isinstance(outputs, FoldedOutputs):
+            rows, T = len(outputs.output_names), int(outputs.T)
+            size = outputs.words.numel() if outputs.on_device else np.asarray(outputs.words).size
+            if not rows or T < 1 or size != folded_words(self.key.params, rows * T):
+                raise ValueError(f"{size} folded words do not fit the server key's parameter set and {rows} outputs of {T} samples")
+            state = self.ctx.state(rows, T)
+            try:
+                state.unfold(outputs.words if outputs.on_device else outputs.host_words())
+            except Exception:
+                state.close()
+                raise
+            out_norm2 = None if outputs.out_norm2 is None else outputs.out_norm2 + outputs.fold_factor
+            return ResidentOutputs(list(outputs.output_names), T, self.key.fingerprint, out_norm2, state, self, compact_bits)
         cts = np.ascontiguousarray(outputs.cts, np.uint64)
         if cts.ndim != 3 or cts.shape[:2] != (len(outputs.output_names), outputs.T) or cts.shape[2] != self.key.params.ct_words or not cts.size:
             raise ValueError(f"ciphertexts of shape {cts.shape} do not fit the server key's parameter set")
@@ -892,6 +1021,10 @@ class Server:
                     src = sources[ln.source]
                     expanded[ln.source] = state = self.ctx.state(len(src.input_names), T)
                     state.put_public(src.samples)
+                if ln.kind == "folded" and ln.source not in expanded:   # folded state: unfolded into a state of its own, likewise
+                    src = sources[ln.source]
+                    expanded[ln.source] = state = self.ctx.state(len(src.output_names), T)
+                    state.unfold(src.words if src.on_device else src.host_words())
             return self._run_links(env, prog, low, sources, links, T, expanded, compact, bits, resident)
         finally:
             for state in expanded.values():   # (closing waits for the evaluations queued on the context)
@@ -940,7 +1073,7 @@ class Server:
                 feed.append(("full", src.cts[ln.index], ln.refresh))
             elif ln.kind == "state":
                 feed.append(("state", src.state, ln.index, ln.refresh) + (() if ln.sample_index is None else (ln.sample_index, ln.fill)))
-            elif ln.kind == "public":
+            elif ln.kind in ("public", "folded"):
                 feed.append(("state", expanded[ln.source], ln.index, ln.refresh))
             elif ln.kind == "plain":
                 feed.append(("plain", src.row(ln.index)))
@@ -948,7 +1081,7 @@ class Server:
                 feed.append(("compact", src.words[ln.index], int(src.bits)))
         out_norm2 = self._out_norm2(low, [ln.noise for ln in links])
         names = list(low["out_names"])
-        run = prog.eval_resident if any(ln.kind in ("state", "public") for ln in links) else prog.eval_sources
+        run = prog.eval_resident if any(ln.kind in ("state", "public", "folded") for ln in links) else prog.eval_sources
         if resident:
             return self._resident(env, prog, low, feed, T, out_norm2)
         if not compact:
@@ -966,7 +1099,8 @@ class ChainLink:
     name: str                     # the program's input
     source: int                   # which of the sources
     index: int                    # its row there (input or output position)
-    kind: str                     # "seeded", "full", "compact", "state" (a row of a ResidentOutputs: full ciphertexts on the GPU), "plain" or "public"
+    kind: str                     # "seeded", "full", "compact", "state" (a row of a ResidentOutputs: full ciphertexts on the GPU), "plain", "public"
+                                  # or "folded" (a row of a FoldedOutputs: unfolded on the GPU into a temporary state)
     refresh: bool                 # bootstrapped through the identity table before use
     noise: float                  # its noise factor going in: 0 fresh or plain, 1 refreshed, the producer's out_norm2 for a plain full link,
                                   # params.public_input_factor for a public-key input
@@ -975,7 +1109,7 @@ class ChainLink:
     fill: int = 0                            # .. and the message of the samples that read none (SAMPLE_NONE)
 
 
-_SOURCE_TYPES = (EncryptedInputs, EncryptedOutputs, CompactOutputs, ResidentOutputs, SampleView, PlainInputs)
+_SOURCE_TYPES = (EncryptedInputs, EncryptedOutputs, CompactOutputs, ResidentOutputs, SampleView, PlainInputs, FoldedOutputs)
 
 
 def _source_types():
@@ -1029,8 +1163,13 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
     A `public.PublicInputs` (public-key encryptions by a third party) is held to the fingerprint and to T like an `EncryptedInputs`;
     its samples must have the shape the parameter set and T give (`public.public_sample_shape`).  Its noise factor is
     `params.public_input_factor`: at most 1, it goes in as it is (kind "public") with that factor as its noise; above, it is
-    refreshed under exactly the full-link rule."""
-    from .params import margin_sigmas, public_input_factor, refresh_margin, refresh_margin_needed
+    refreshed under exactly the full-link rule.
+    A `FoldedOutputs` is a full link that has been through one fold (kind "folded"): its words must be the
+    `folded_words(params, n_outputs T)` of the parameter set.  It goes in as it is, with noise out_norm2 + fold_factor, when its
+    producer's factor is at most 1 (the full-link rule) and the program keeps `min_margin` with every such input that much
+    noisier -- `margin_sigmas` recomputed with v_br (1 + fold_factor), what `params.fold_choice` chose the fold key for.
+    Otherwise it is refreshed like any full link, at out_norm2 + fold_factor."""
+    from .params import margin_sigmas, public_input_factor, refresh_margin, refresh_margin_needed, variances
     from .public import PublicInputs, public_sample_shape
     low = env.lower()
     p = params.p_msg
@@ -1105,6 +1244,22 @@ def plan_chain(params, fuse_tables, fingerprint, env, sources, rename=None, min_
             raise ValueError("input %s: source %d was saved without out_norm2 (before chains existed), so the noise it carries is "
                              "unknown and it cannot be linked; it still decrypts" % (via, k))
         o2 = float(np.asarray(src.out_norm2).reshape(-1)[j])
+        if isinstance(src, FoldedOutputs):
+            size = src.words.numel() if src.on_device else np.asarray(src.words).size
+            if size != folded_words(params, len(src.output_names) * src.T):
+                raise ValueError("input %s: %d folded words do not fit the server key's parameter set and %d outputs of %d samples"
+                                 % (via, size, len(src.output_names), src.T))
+            v_br, v_ks, v_ms = variances(params)
+            kept = (1.0 / (4.0 * p)) / math.sqrt(norm2 * v_br * (1.0 + src.fold_factor) + v_ks + v_ms)
+            if o2 <= 1.0 and kept >= floor - 1e-9:
+                links.append(ChainLink(name, k, j, "folded", False, o2 + src.fold_factor))
+                continue
+            link = ChainLink(name, k, j, "folded", True, 1.0, refresh_margin(params, None, o2 + src.fold_factor))
+            if link.margin < need * (1.0 - 1e-12):
+                raise ValueError("input %s: its refresh would keep %.3f sigma (out_norm2 %g, fold factor %g), below the %.3f the "
+                                 "program's bootstraps keep" % (via, link.margin, o2, src.fold_factor, need))
+            links.append(link)
+            continue
         if isinstance(src, CompactOutputs):
             bits = int(src.bits)
             if not params.log_n_poly + 1 <= bits <= 31 or src.words.shape[-1] != compact_words(params, bits):
