@@ -1,5 +1,5 @@
-// Sanitizer harness for the HOST side of folded state (include/fbs_exec.h, "folded state"): csrc/fbs_host.cpp's host_fold_keygen and
-// host_expand_fold_key on exactly-sized buffers, built by tests/c/fold.mk with g++ under AddressSanitizer and UBSan and run by
+// Sanitizer harness for the HOST side of folded state (include/fbs_exec.h, "folded state"): csrc/fbs_host.cpp's host_gadget_keygen and
+// host_expand_gadget_key (GK_FOLD) on exactly-sized buffers, built by tests/c/fold.mk with g++ under AddressSanitizer and UBSan and run by
 // tests/test_fold_sanitizers.py as a program of its own.  No GPU, no HIP call.
 //
 // At two toy sets and several (t_f, gamma_f): the key a client generates and the key a server expands from (mask key, bodies) are
@@ -55,19 +55,19 @@ int main() {
             if (!make_ctx(ctx, n, sh[1], k, 5)) return 1;
             const uint32_t N = ctx.N, D = ctx.D;
             std::vector<uint64_t> bodies, client, server, pack_bodies;
-            host_fold_keygen(&ctx, t, gamma, bodies);
+            host_gadget_keygen(&ctx, GK_FOLD, t, gamma, bodies);
             if (bodies.size() != (size_t)D * t * N) failures++, printf("FAIL bodies of %zu words\n", bodies.size());
             std::vector<uint64_t> exact(bodies);   // an exactly-sized copy: a read past the bodies is a finding
-            host_expand_fold_key(&ctx, ctx.mask_key, t, exact.data(), client);
+            host_expand_gadget_key(&ctx, GK_FOLD, ctx.mask_key, t, exact.data(), client);
             fbs_ctx srv;                           // the server: another context of the same set, no secret, the client's mask key
             if (!make_ctx(srv, n, sh[1], k, 99)) return 1;
             srv.sk_lwe.clear(), srv.sk_glwe.clear();
-            host_expand_fold_key(&srv, ctx.mask_key, t, exact.data(), server);
+            host_expand_gadget_key(&srv, GK_FOLD, ctx.mask_key, t, exact.data(), server);
             if (client != server || client.size() != (size_t)D * t * (k + 1) * N) {
                 printf("FAIL client and server keys differ k=%u t=%u\n", k, t);
                 failures++;
             }
-            host_packing_keygen(&ctx, t, gamma, pack_bodies);   // rows 0 .. n t - 1 of both keys: other streams, other words
+            host_gadget_keygen(&ctx, GK_PACK, t, gamma, pack_bodies);   // rows 0 .. n t - 1 of both keys: other streams, other words
             if (!memcmp(pack_bodies.data(), bodies.data(), pack_bodies.size() * 8)) failures++, printf("FAIL the fold key repeats the packing key\n");
             int64_t worst = 0;
             for (uint32_t i = 0; i < D; i++)

@@ -1,5 +1,5 @@
 // Sanitizer harness for the HOST side of packed outputs (include/fbs_exec.h, "packed outputs"): csrc/fbs_host.cpp's
-// host_packing_keygen, host_expand_packing_key and host_decrypt_packed with the arithmetic of csrc/fbs_pack.hpp, built by
+// host_gadget_keygen, host_expand_gadget_key (GK_PACK) and host_decrypt_packed with the arithmetic of csrc/fbs_pack.hpp, built by
 // tests/test_packed_abi.py with g++ and the -fsanitize=address,undefined flags of tests/c/Makefile.  No GPU, no HIP call.
 //
 //   packed_harness keys      at two toy sets and several (t_p, gamma_p): the key a client generates and the key a server expands from
@@ -39,18 +39,18 @@ static int mode_keys() {
             fbs_ctx ctx;
             if (!make_ctx(ctx, n, sh[1], k, 7, 5)) return 1;
             const uint32_t N = ctx.N;
-            if (packing_params_refused(t, gamma)) {
+            if (gadget_params_refused(t, gamma)) {
                 printf("FAIL (%u, %u) refused\n", t, gamma);
                 return 1;
             }
             std::vector<uint64_t> bodies, client, server;
-            host_packing_keygen(&ctx, t, gamma, bodies);
-            host_expand_packing_key(&ctx, ctx.mask_key, t, bodies.data(), client);
+            host_gadget_keygen(&ctx, GK_PACK, t, gamma, bodies);
+            host_expand_gadget_key(&ctx, GK_PACK, ctx.mask_key, t, bodies.data(), client);
             // the server: another context of the same set, no secret, the client's mask key
             fbs_ctx srv;
             if (!make_ctx(srv, n, sh[1], k, 7, 99)) return 1;
             srv.sk_lwe.clear(), srv.sk_glwe.clear();
-            host_expand_packing_key(&srv, ctx.mask_key, t, bodies.data(), server);
+            host_expand_gadget_key(&srv, GK_PACK, ctx.mask_key, t, bodies.data(), server);
             if (client != server || client.size() != (size_t)n * t * (k + 1) * N) {
                 printf("FAIL client and server keys differ n=%u k=%u t=%u\n", n, k, t);
                 failures++;
@@ -98,7 +98,7 @@ static int mode_keys() {
         }
     const uint32_t bad[][2] = {{0, 5}, {5, 0}, {4, 8}, {2, 16}, {1, 32}, {32, 1}, {0xFFFFFFFFu, 0xFFFFFFFFu}, {65536, 65536}, {0x80000000u, 2}};
     for (auto &b : bad)
-        if (!packing_params_refused(b[0], b[1])) {
+        if (!gadget_params_refused(b[0], b[1])) {
             printf("FAIL (%u, %u) accepted\n", b[0], b[1]);
             failures++;
         }

@@ -478,6 +478,39 @@ def test_calls_out_of_order_and_bad_arguments():
     ctx.close()
 
 
+def test_packing_key_refusals_word_for_word():
+    """(call, code, text) of every refusal of the packing-key entries, as the library said them before the packing and fold keys
+    were given one code path (tests/test_gpu_fold.py pins the fold key's and the imports' on the GPU library)"""
+    from tfhe_fbs_map_amd import FbsError, HostContext
+    prm = toy_sets()["k1_N256"]
+    ctx = HostContext(prm, seed=2)
+
+    def refused(call, code, text):
+        with pytest.raises(FbsError) as e:
+            call()
+        assert (e.value.code, str(e.value)) == (code, f"libfbsexec error {code}: {text}"), (code, text, str(e.value))
+
+    no_key = "the context has no packing key"
+    refused(lambda: ctx.packing_keygen(2, 7), E_STATE, "fbs_keygen has not run")                       # no keys
+    refused(lambda: ctx.packing_key_sizes(0), E_STATE, no_key)
+    refused(lambda: ctx.export_packing_key(), E_STATE, no_key)
+    refused(lambda: ctx.packing_key_sizes(32), E_INVALID, "packing key needs 1 <= t_p <= 31")
+    ctx.keygen()                                                                                       # plain keys, not seeded ones
+    refused(lambda: ctx.packing_keygen(2, 7), E_STATE, "a packing key goes with seeded keys (fbs_keygen_seeded)")
+    ctx.keygen_seeded()
+    refused(lambda: ctx.packing_keygen(0, 1), E_INVALID, "packing key needs t_p >= 1 and gamma_p >= 1")
+    refused(lambda: ctx.packing_keygen(1, 0), E_INVALID, "packing key needs t_p >= 1 and gamma_p >= 1")
+    refused(lambda: ctx.packing_keygen(32, 1), E_INVALID, "packing key needs t_p * gamma_p <= 31")
+    refused(lambda: ctx.packing_keygen(4, 8), E_INVALID, "packing key needs t_p * gamma_p <= 31")
+    refused(lambda: ctx.packing_key_sizes(0), E_STATE, no_key)                                         # keys, and still no packing key
+    refused(lambda: ctx.packing_key_sizes(32), E_INVALID, "packing key needs 1 <= t_p <= 31")
+    lib, buf = _raw(), np.zeros(1, np.uint64)
+    assert lib.fbs_export_packing_key(ctx._h, buf.ctypes.data, None) == E_STATE
+    assert lib.fbs_last_error(ctx._h).decode() == no_key
+    assert ctx.packing_key_sizes(31) == (prm.n * 31 * prm.N, prm.n * 31 * prm.N * (prm.k + 1)) and ctx.stat("packing_key") == 0
+    ctx.close()
+
+
 # ---- 6. no GPU library at all -----------------------------------------------------------------------------------------------------
 CHILD = r"""
 import json, os, sys

@@ -327,3 +327,117 @@ def test_refusals_write_nothing_and_leave_the_context_usable():
     assert np.array_equal(fold_dev(server, cts), good) and np.array_equal(fold_dev(client, cts), good)
     server.close()
     client.close()
+
+
+def test_gadget_key_refusals_word_for_word():
+    """(call, code, text) of every refusal of the fold key's entries and of the imports of both keys, as the library said them before
+    the packing and fold keys were given one code path (tests/test_client_lib.py pins the packing key's on the client library)"""
+    from tfhe_fbs_map_amd import Context, FbsError, _native as nat
+    lib = nat.lib
+    prm = F.fold_toy(8, 2)
+    N, D = prm.N, prm.k * prm.N
+
+    def refused(call, code, text):
+        with pytest.raises(FbsError) as e:
+            call()
+        assert (e.value.code, str(e.value)) == (code, f"libfbsexec error {code}: {text}"), (code, text, str(e.value))
+
+    def raw(ctx, entry, *args):
+        return lambda: ctx._check(entry(ctx._h, *args))
+
+    no_keys, eval_only = "fbs_keygen has not run", "this context holds evaluation keys only"
+    ctx = Context(prm, seed=5, keygen=False)                                       # no keys at all
+    good = np.zeros(D * 2 * N, np.uint64)
+    refused(lambda: ctx.fold_keygen(2, 7), E_STATE, no_keys)
+    refused(lambda: ctx.import_fold_key(2, 7, good), E_STATE, no_keys)
+    refused(lambda: ctx.import_packing_key(2, 7, good[:prm.n * 2 * N]), E_STATE, no_keys)
+    refused(lambda: ctx.fold_key_sizes(0), E_STATE, "the context has no fold key")
+    refused(raw(ctx, lib.fbs_export_fold_key, good.ctypes.data, None), E_STATE, "the context has no fold key")
+    refused(lambda: ctx.fold_key_sizes(32), E_INVALID, "fold key needs 1 <= t_f <= 31")
+    ctx.keygen()                                                                   # plain keys, not seeded ones
+    refused(lambda: ctx.fold_keygen(2, 7), E_STATE, "a fold key goes with seeded keys (fbs_keygen_seeded)")
+    refused(lambda: ctx.import_fold_key(2, 7, good), E_STATE, "a fold key goes with seeded keys (fbs_import_seeded_keys)")
+    refused(lambda: ctx.import_packing_key(2, 7, good[:prm.n * 2 * N]), E_STATE, "a packing key goes with seeded keys (fbs_import_seeded_keys)")
+    ctx.keygen_seeded()
+    for (t, g), text in (((0, 1), "fold key needs t_f >= 1 and gamma_f >= 1"), ((1, 0), "fold key needs t_f >= 1 and gamma_f >= 1"),
+                         ((32, 1), "fold key needs t_f * gamma_f <= 31"), ((4, 8), "fold key needs t_f * gamma_f <= 31")):
+        refused(lambda: ctx.fold_keygen(t, g), E_INVALID, text)
+    refused(lambda: ctx.fold_key_sizes(0), E_STATE, "the context has no fold key")
+    refused(lambda: ctx.fold_key_sizes(32), E_INVALID, "fold key needs 1 <= t_f <= 31")
+    refused(raw(ctx, lib.fbs_export_fold_key, good.ctypes.data, None), E_STATE, "the context has no fold key")
+    d_c = dev(np.zeros((2, D + 1), np.uint64))
+    refused(lambda: ctx.fold_dev(d_c.data_ptr(), 1, d_c.data_ptr()), E_STATE, "the context has no fold key (fbs_fold_keygen / fbs_import_fold_key)")
+    refused(lambda: ctx.pack_dev(d_c.data_ptr(), 1, d_c.data_ptr(), 31), E_STATE,
+            "the context has no packing key (fbs_packing_keygen / fbs_import_packing_key)")
+    server = Context.evaluation_only(prm, **ctx.export_seeded_keys())              # no secret: no keygen of either kind
+    refused(lambda: server.fold_keygen(2, 7), E_STATE, eval_only)
+    refused(lambda: server.packing_keygen(2, 7), E_STATE, eval_only)
+    bad = good.copy()
+    bad[-1] = Q
+    for noun, letter, entry, rows in (("fold", "f", lib.fbs_import_fold_key, D), ("packing", "p", lib.fbs_import_packing_key, prm.n)):
+        bodies = good[:rows * 2 * N]
+        refused(raw(server, entry, 2, 7, None), E_INVALID, "null argument")
+        refused(raw(server, entry, 2, 7, bad[-rows * 2 * N:].ctypes.data), E_INVALID, f"{noun}-key body word is not a canonical residue")
+        refused(raw(server, entry, 2, 16, bodies.ctypes.data), E_INVALID, f"{noun} key needs t_{letter} * gamma_{letter} <= 31")
+        refused(raw(server, entry, 0, 7, bodies.ctypes.data), E_INVALID, f"{noun} key needs t_{letter} >= 1 and gamma_{letter} >= 1")
+        assert server.stat(noun + "_key") == 0
+    server.close()
+    ctx.close()
+
+
+@pytest.mark.parametrize("log_n,k", [(8, 2), (9, 1)])
+def test_both_gadget_keys_on_one_context(log_n, k):
+    """A packing key and a fold key on one context: each output is word for word what a context holding that key alone returns, also
+    interleaved (the fields and accumulator scratch is shared); making or refusing one key leaves the other where it was; new seeded
+    keys drop both.  Two samples, the second a one-coefficient tail.  At (9, 1) -- the other transform class, k = 1 -- the interleaving
+    alone."""
+    from tfhe_fbs_map_amd import Context
+    prm = F.fold_toy(log_n, k)
+    assert prm.n == 12
+    N, D = prm.N, prm.k * prm.N
+    cts = F.planted_cts(D, N + 1, 2, 9, seed=31, N=N)
+
+    def keyed_with(packing, folding):
+        ctx = Context(prm, seed=17, keygen=False)
+        ctx.keygen_seeded()
+        if packing:
+            ctx.packing_keygen(2, 9)
+        if folding:
+            ctx.fold_keygen(2, 9)
+        return ctx
+
+    alone_p, alone_f = keyed_with(True, False), keyed_with(False, True)
+    packed, folded = alone_p.pack(cts, 31), alone_f.fold(cts)
+    assert packed.size == alone_p.packed_words(N + 1, 31) and folded.size == 2 * (k + 1) * N
+    alone_p.close()
+    alone_f.close()
+    both = keyed_with(True, True)
+    for _ in range(2):                                                             # pack, fold, pack, fold
+        assert np.array_equal(both.pack(cts, 31), packed)
+        assert np.array_equal(both.fold(cts), folded)
+    if (log_n, k) != (8, 2):
+        both.close()
+        return
+    pack_key, fold_key_ = both.export_packing_key(), both.export_fold_key()
+    assert (both.stat("packing_key"), both.stat("packing_levels"), both.stat("packing_base_bits")) == (1, 2, 9)
+    assert (both.stat("fold_key"), both.stat("fold_levels"), both.stat("fold_base_bits")) == (1, 2, 9)
+
+    def same(a, b):
+        return a.keys() == b.keys() and all(np.array_equal(a[name], b[name]) for name in a)
+
+    both.fold_keygen(3, 7)                                                         # a new fold key: the packing key stays
+    assert both.stat("fold_levels") == 3 and both.stat("packing_levels") == 2 and same(both.export_packing_key(), pack_key)
+    assert np.array_equal(both.pack(cts, 31), packed) and not np.array_equal(both.fold(cts), folded)
+    both.fold_keygen(2, 9)
+    assert same(both.export_fold_key(), fold_key_) and np.array_equal(both.fold(cts), folded)
+    both.packing_keygen(3, 7)                                                      # and the other way round
+    assert both.stat("packing_levels") == 3 and both.stat("fold_levels") == 2 and same(both.export_fold_key(), fold_key_)
+    assert np.array_equal(both.fold(cts), folded) and not np.array_equal(both.pack(cts, 31), packed)
+    both.packing_keygen(2, 9)
+    assert same(both.export_packing_key(), pack_key) and np.array_equal(both.pack(cts, 31), packed)
+    assert _code(lambda: both.import_fold_key(2, 16, fold_key_["fold_bodies"])) == E_INVALID           # t gamma > 31: nothing moves
+    assert same(both.export_packing_key(), pack_key) and same(both.export_fold_key(), fold_key_)
+    assert np.array_equal(both.pack(cts, 31), packed) and np.array_equal(both.fold(cts), folded)
+    both.keygen_seeded()                                                           # new keys drop both
+    assert both.stat("packing_key") == both.stat("fold_key") == 0
+    both.close()

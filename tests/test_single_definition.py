@@ -93,6 +93,28 @@ def test_one_key_transform_kernel():
     assert launches == {"fbs_blind_rotate.hip": 2, "fbs_pack.hip": 1, "fbs_keygen.hip": 1}, launches
 
 
+def test_one_gadget_key_path():
+    """The packing key and the fold key are one family (GadgetKind, csrc/fbs_internal.hpp): no per-key wrapper is left, their
+    ChaCha20 domains are named in the kind table alone, and the bracket of the shared scratch is written once."""
+    texts = {name: _csrc(name) for name in sorted(os.listdir(CSRC)) if name.endswith((".cpp", ".hip", ".hpp", ".h")) or name == "Makefile"}
+    for old in ("host_packing_keygen", "host_fold_keygen", "host_expand_packing_key", "host_expand_fold_key", "dev_packing_bodies",
+                "dev_fold_bodies", "dev_upload_packing_key", "dev_upload_fold_key", "install_fold_key", "fold_passes", "check_fold_params"):
+        assert [name for name, text in texts.items() if old in text] == [], old
+    internal = texts["fbs_internal.hpp"]
+    table = re.findall(r"^constexpr GadgetKindInfo GADGET_KINDS\[2\] = .*$", internal, flags=re.M)
+    assert len(table) == 1
+    for dom in ("DOM_FOLD_MASK", "DOM_PACK_MASK"):
+        assert [name for name, text in texts.items() if dom in text] == ["fbs_internal.hpp"], dom
+        assert len(re.findall(r"\b%s\b" % dom, internal)) == 2 and len(re.findall(r"\b%s\b" % dom, table[0])) == 1   # the enum, the table
+        assert re.search(r"\b%s = \d+" % dom, internal)
+    capi = texts["fbs_capi.cpp"]
+    bodies = _function_bodies(capi)
+    callers = sorted(name for name, body in bodies.items() if "scratch_wait(" in body)
+    assert callers == ["scratch_section"], callers
+    assert len(re.findall(r"scratch_wait\(", capi)) == 2                              # its definition, and that call
+    assert len(re.findall(r"^int scratch_wait\(", capi, flags=re.M)) == 1
+
+
 def test_the_host_draws_masks_and_products_in_one_place():
     host, public = _csrc("fbs_host.cpp"), _csrc("fbs_public.cpp")
     # no negacyclic add of its own in the public-key library: the shift-and-subtract idiom and the old name are gone

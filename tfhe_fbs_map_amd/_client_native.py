@@ -386,24 +386,31 @@ class ClientContext:
         """fbs_packing_keygen: the packing key (t_p levels of gamma_p bits) beside the keys of `keygen_seeded`"""
         self._check(self._lib.fbs_packing_keygen(self._h, int(t_p), int(gamma_p)))
 
+    def _gadget_key_sizes(self, noun, t):
+        """fbs_<noun>_key_sizes: the sizes of the packing key or (the GPU library's) of the fold key"""
+        sizes = (C.c_size_t * 2)()
+        self._check(getattr(self._lib, f"fbs_{noun}_key_sizes")(self._h, int(t), C.byref(sizes)))
+        return int(sizes[0]), int(sizes[1])
+
+    def _export_gadget_key(self, noun, rows, full):
+        """fbs_export_<noun>_key: dict(<noun>_levels, <noun>_base_bits, <noun>_bodies [rows][t][N]), and `full` [rows][t][k+1][N]"""
+        nb, nf = self._gadget_key_sizes(noun, 0)
+        bodies = np.empty(nb, np.uint64)
+        whole = np.empty(nf, np.uint64) if full else None
+        self._check(getattr(self._lib, f"fbs_export_{noun}_key")(self._h, _ptr(bodies), _ptr(whole)))
+        out = {f"{noun}_levels": self.stat(f"{noun}_levels"), f"{noun}_base_bits": self.stat(f"{noun}_base_bits"), f"{noun}_bodies": bodies}
+        if full:
+            out["full"] = whole.reshape(rows, out[f"{noun}_levels"], self.params.k + 1, self.params.N)
+        return out
+
     def packing_key_sizes(self, t_p=0):
         """(bodies, whole key) in words for t_p levels (0: the context's own key)"""
-        sizes = (C.c_size_t * 2)()
-        self._check(self._lib.fbs_packing_key_sizes(self._h, int(t_p), C.byref(sizes)))
-        return int(sizes[0]), int(sizes[1])
+        return self._gadget_key_sizes("packing", t_p)
 
     def export_packing_key(self, full=False):
         """dict(packing_levels, packing_base_bits, packing_bodies [n][t_p][N]); full=True adds `full`, the whole key
         [n][t_p][k+1][N] in the coefficient domain (a test hook)"""
-        nb, nf = self.packing_key_sizes()
-        bodies = np.empty(nb, np.uint64)
-        whole = np.empty(nf, np.uint64) if full else None
-        self._check(self._lib.fbs_export_packing_key(self._h, _ptr(bodies), _ptr(whole)))
-        out = dict(packing_levels=self.stat("packing_levels"), packing_base_bits=self.stat("packing_base_bits"), packing_bodies=bodies)
-        if full:
-            prm = self.params
-            out["full"] = whole.reshape(prm.n, out["packing_levels"], prm.k + 1, prm.N)
-        return out
+        return self._export_gadget_key("packing", self.params.n, full)
 
     def packed_words(self, count, bits):
         """uint64 words of `count` outputs packed at width `bits` (fbs_packed_words)"""

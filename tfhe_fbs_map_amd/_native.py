@@ -747,12 +747,16 @@ class Context(ClientContext):
                                                 d_msgs or None, stream or None))
 
     # ---- packed outputs: up to N outputs in one GLWE sample under the big key (include/fbs_exec.h, "packed outputs") ----
+    def _import_gadget_key(self, noun, t, gamma, bodies):
+        """fbs_import_<noun>_key, once the bodies are as many as `t` levels need"""
+        bodies = _c(bodies, np.uint64).reshape(-1)
+        if 1 <= int(t) <= 31 and bodies.size != self._gadget_key_sizes(noun, t)[0]:
+            raise ValueError(f"{noun}_bodies has {bodies.size} words, the parameter set needs {self._gadget_key_sizes(noun, t)[0]}")
+        self._check(getattr(lib, f"fbs_import_{noun}_key")(self._h, int(t), int(gamma), _ptr(bodies)))
+
     def import_packing_key(self, t_p, gamma_p, bodies):
         """fbs_import_packing_key: the masks come from the context's mask key; works on evaluation-only contexts"""
-        bodies = _c(bodies, np.uint64).ravel()
-        if 1 <= int(t_p) <= 31 and bodies.size != self.packing_key_sizes(t_p)[0]:
-            raise ValueError(f"packing_bodies has {bodies.size} words, the parameter set needs {self.packing_key_sizes(t_p)[0]}")
-        self._check(lib.fbs_import_packing_key(self._h, int(t_p), int(gamma_p), _ptr(bodies)))
+        self._import_gadget_key("packing", t_p, gamma_p, bodies)
 
     # ---- folded state: N resident ciphertexts in one full-precision GLWE sample (include/fbs_exec.h, "folded state") ----
     def fold_keygen(self, t_f, gamma_f):
@@ -761,29 +765,16 @@ class Context(ClientContext):
 
     def fold_key_sizes(self, t_f=0):
         """(bodies, whole key) in words for t_f levels (0: the context's own key)"""
-        sizes = (C.c_size_t * 2)()
-        self._check(lib.fbs_fold_key_sizes(self._h, int(t_f), C.byref(sizes)))
-        return int(sizes[0]), int(sizes[1])
+        return self._gadget_key_sizes("fold", t_f)
 
     def export_fold_key(self, full=False):
         """dict(fold_levels, fold_base_bits, fold_bodies [D][t_f][N]); full=True adds `full`, the whole key [D][t_f][k+1][N] in the
         coefficient domain (a test hook)"""
-        nb, nf = self.fold_key_sizes()
-        bodies = np.empty(nb, np.uint64)
-        whole = np.empty(nf, np.uint64) if full else None
-        self._check(lib.fbs_export_fold_key(self._h, _ptr(bodies), _ptr(whole)))
-        out = dict(fold_levels=self.stat("fold_levels"), fold_base_bits=self.stat("fold_base_bits"), fold_bodies=bodies)
-        if full:
-            prm = self.params
-            out["full"] = whole.reshape(prm.k * prm.N, out["fold_levels"], prm.k + 1, prm.N)
-        return out
+        return self._export_gadget_key("fold", self.params.k * self.params.N, full)
 
     def import_fold_key(self, t_f, gamma_f, bodies):
         """fbs_import_fold_key: the masks come from the context's mask key; works on evaluation-only contexts"""
-        bodies = _c(bodies, np.uint64).reshape(-1)
-        if 1 <= int(t_f) <= 31 and bodies.size != self.fold_key_sizes(t_f)[0]:
-            raise ValueError(f"fold_bodies has {bodies.size} words, the parameter set needs {self.fold_key_sizes(t_f)[0]}")
-        self._check(lib.fbs_import_fold_key(self._h, int(t_f), int(gamma_f), _ptr(bodies)))
+        self._import_gadget_key("fold", t_f, gamma_f, bodies)
 
     def fold_dev(self, d_cts, count, d_glwe, stream=0):
         """fbs_fold_dev: `count` big-key ciphertexts at d_cts -> folded samples at d_glwe, asynchronous on `stream`; no secret"""

@@ -9,6 +9,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <string>
 
@@ -47,15 +48,32 @@ static inline int params_admitted(const fbs_params *params, fbs_ctx **probe) { r
 // definitions and the caller are checked against one signature.
 __attribute__((visibility("hidden"))) int ctx_create(const fbs_params *params, uint64_t seed, const uint8_t *seed32, int device, fbs_ctx **out);
 
+// a message about a gadget key: '@' stands for the kind's noun ("packing", "fold"), '#' for the letter of its parameters (t_p, t_f)
+inline std::string gadget_text(GadgetKind kind, const std::string &pattern) {
+    std::string text;
+    for (char c : pattern) {
+        if (c == '@') text += GADGET_KINDS[kind].noun;
+        else if (c == '#') text += GADGET_KINDS[kind].letter;
+        else text += c;
+    }
+    return text;
+}
+// the three statistics of a gadget key: <noun>_key, <noun>_levels, <noun>_base_bits; false: `k` is none of them
+inline bool gadget_stat(const fbs_ctx *ctx, GadgetKind kind, const std::string &k, int64_t *value) {
+    const HostState::GadgetKeyState &key = ctx->gadget[kind];
+    if (k == gadget_text(kind, "@_key")) *value = key.have;
+    else if (k == gadget_text(kind, "@_levels")) *value = key.have ? key.t : 0;
+    else if (k == gadget_text(kind, "@_base_bits")) *value = key.have ? key.gamma : 0;
+    else return false;
+    return true;
+}
+
 // The statistics of fbs_ctx_stat that both libraries answer; false: not one of them (the GPU library goes on to its own)
 inline bool host_stat(const fbs_ctx *ctx, const std::string &k, int64_t *value) {
     if (k == "next_nonce") *value = (int64_t)ctx->next_nonce.load();
     else if (k == "has_secret") *value = ctx->have_keys && !ctx->eval_only;
     else if (k == "seeded_keys") *value = ctx->have_keys && ctx->seeded_keys;
-    else if (k == "packing_key") *value = ctx->have_pack;
-    else if (k == "packing_levels") *value = ctx->have_pack ? ctx->pack_t : 0;
-    else if (k == "packing_base_bits") *value = ctx->have_pack ? ctx->pack_gamma : 0;
-    else return false;
+    else return gadget_stat(ctx, GK_PACK, k, value);
     return true;
 }
 
@@ -67,8 +85,7 @@ inline void keys_replaced(fbs_ctx *ctx, bool seeded, bool eval_only) {
 }
 inline void keys_in_place(fbs_ctx *ctx) {
     ctx->have_keys = true;
-    ctx->have_pack = false;   // (a packing key belonged to the keys this call replaced)
-    ctx->have_fold = false;   // (and so did a fold key)
+    for (auto &key : ctx->gadget) key.have = false;   // (a packing key, a fold key belonged to the keys this call replaced)
 }
 
 // Streams [first, first + count) of [2^55, 2^56) that nobody has used, for every entry that takes fresh streams.  The range is
@@ -124,18 +141,55 @@ inline int check_compact_words(const fbs_ctx *ctx, size_t count, uint32_t bits) 
     if (count > SIZE_MAX / 8 / compact_words(ctx->p.n, bits)) return set_error(ctx, FBS_E_INVALID, "count * W words overflow");
     return FBS_OK;
 }
-inline int check_packing_params(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) {
-    if (const char *why = packing_params_refused(t_p, gamma_p)) return set_error(ctx, FBS_E_INVALID, why);
-    if (!pack_shape_built(ctx->p.log_n_poly, ctx->p.k)) return set_error(ctx, FBS_E_INVALID, "no packing kernel for this (k, N)");
+// The gadget keys (GadgetKind, fbs_internal.hpp): what their entries check and answer, once for the packing key (both libraries)
+// and the fold key (the GPU library).  The parameter range and the shapes are one (the accumulate kernel is the same one).
+inline int check_gadget_params(const fbs_ctx *ctx, GadgetKind kind, uint32_t t, uint32_t gamma) {
+    if (const char *why = gadget_params_refused(t, gamma)) return set_error(ctx, FBS_E_INVALID, gadget_text(kind, std::string("@ key needs ") + why));
+    if (!pack_shape_built(ctx->p.log_n_poly, ctx->p.k)) return set_error(ctx, FBS_E_INVALID, gadget_text(kind, "no @ kernel for this (k, N)"));
     return FBS_OK;
 }
-// what fbs_packing_keygen checks before it draws anything: the states in this order, then the parameters
-inline int check_packing_keygen(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) {
+// what a keygen checks before it draws anything, an import (`entry`: who makes the seeded keys it goes with) before it reads its
+// bodies: the states in this order, then the parameters
+inline int check_gadget_keygen(const fbs_ctx *ctx, GadgetKind kind, uint32_t t, uint32_t gamma, bool needs_secret = true,
+                               const char *entry = "fbs_keygen_seeded") {
     if (!ctx) return FBS_E_INVALID;
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "a packing key goes with seeded keys (fbs_keygen_seeded)");
-    return check_packing_params(ctx, t_p, gamma_p);
+    if (needs_secret && ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
+    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, gadget_text(kind, "a @ key goes with seeded keys (") + entry + ")");
+    return check_gadget_params(ctx, kind, t, gamma);
+}
+// the state change of a keygen or an import, once the key is where it is used (in the GPU library: on the device)
+inline void gadget_key_in_place(fbs_ctx *ctx, GadgetKind kind, uint32_t t, uint32_t gamma, std::vector<uint64_t> &bodies) {
+    HostState::GadgetKeyState &key = ctx->gadget[kind];
+    key.bodies.swap(bodies);
+    key.t = t;
+    key.gamma = gamma;
+    key.have = true;
+}
+// fbs_<noun>_key_sizes: words of the bodies and of the whole key at t levels (0: the context's own key)
+inline int gadget_key_sizes(const fbs_ctx *ctx, GadgetKind kind, uint32_t t, size_t sizes[2]) {
+    if (!ctx || !sizes) return FBS_E_INVALID;
+    if (t == 0) {
+        if (!ctx->gadget[kind].have) return set_error(ctx, FBS_E_STATE, gadget_text(kind, "the context has no @ key"));
+        t = ctx->gadget[kind].t;
+    }
+    if (t > 31) return set_error(ctx, FBS_E_INVALID, gadget_text(kind, "@ key needs 1 <= t_# <= 31"));
+    sizes[0] = (size_t)gadget_rows(*ctx, kind) * t * ctx->N;
+    sizes[1] = sizes[0] * (ctx->p.k + 1);
+    return FBS_OK;
+}
+// fbs_export_<noun>_key: the bodies, and (a test hook) the whole key in the coefficient domain
+inline int gadget_key_export(const fbs_ctx *ctx, GadgetKind kind, uint64_t *bodies, uint64_t *full) {
+    if (!ctx) return FBS_E_INVALID;
+    const HostState::GadgetKeyState &key = ctx->gadget[kind];
+    if (!key.have) return set_error(ctx, FBS_E_STATE, gadget_text(kind, "the context has no @ key"));
+    if (bodies) std::memcpy(bodies, key.bodies.data(), key.bodies.size() * 8);
+    if (full) {
+        std::vector<uint64_t> whole;
+        host_expand_gadget_key(ctx, kind, ctx->mask_key, key.t, key.bodies.data(), whole);
+        std::memcpy(full, whole.data(), whole.size() * 8);
+    }
+    return FBS_OK;
 }
 inline int check_packed_words(const fbs_ctx *ctx, size_t count, uint32_t bits) {
     if (count / ctx->N + 1 > SIZE_MAX / 8 / packed_sample_words(ctx->p.k, ctx->N, ctx->N, bits))

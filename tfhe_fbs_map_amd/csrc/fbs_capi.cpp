@@ -97,6 +97,13 @@ int scratch_fail(fbs_ctx *ctx, hipStream_t s, int rc) {
     (void)scratch_done(ctx, s);
     return rc;
 }
+// The bracket of every use of the scratch: wait, what `body` queues on `s`, then done -- or fail, with the code `body` gave
+template <typename Body>
+static int scratch_section(fbs_ctx *ctx, hipStream_t s, Body &&body) {
+    if (int rc = scratch_wait(ctx, s)) return rc;
+    if (int rc = body()) return scratch_fail(ctx, s, rc);
+    return scratch_done(ctx, s);
+}
 
 // the plain batch: gate g = ciphertext g, one sample each
 GateView batch_view(const uint64_t *in, uint64_t *out, const uint32_t *table_ids, size_t count) {
@@ -129,12 +136,12 @@ GateView slots_view(const uint64_t *in, uint64_t *out, const uint32_t *d_slot, s
 size_t ms_pass_size(const fbs_ctx *ctx, size_t count) { return std::min(count, std::max(ctx->ms_capacity, COMPACT_PASS)); }
 int ms_passes(fbs_ctx *ctx, size_t count, hipStream_t s, const std::function<int(size_t f0, size_t rows)> &pass) {
     const size_t per_pass = ms_pass_size(ctx, count);
-    int rc = ensure_ms(ctx, per_pass);
-    if (rc != FBS_OK) return rc;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    for (size_t f0 = 0; f0 < count; f0 += per_pass)
-        if ((rc = pass(f0, std::min(per_pass, count - f0))) != FBS_OK) return scratch_fail(ctx, s, rc);
-    return scratch_done(ctx, s);
+    if (int rc = ensure_ms(ctx, per_pass)) return rc;
+    return scratch_section(ctx, s, [&]() -> int {
+        for (size_t f0 = 0; f0 < count; f0 += per_pass)
+            if (int rc = pass(f0, std::min(per_pass, count - f0))) return rc;
+        return FBS_OK;
+    });
 }
 
 int sync_stream(fbs_ctx *ctx, hipStream_t s) {
@@ -240,10 +247,8 @@ int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value) try {
     if (!ctx || !name || !value) return FBS_E_INVALID;
     const std::string k(name);
     if (host_stat(ctx, k, value)) return FBS_OK;   // (what the client library answers too)
+    if (gadget_stat(ctx, GK_FOLD, k, value)) return FBS_OK;   // (folded state: this library's alone)
     if (k == "scratch_growths") *value = ctx->scratch_growths;
-    else if (k == "fold_key") *value = ctx->have_fold;   // (folded state: this library's alone)
-    else if (k == "fold_levels") *value = ctx->have_fold ? ctx->fold_t : 0;
-    else if (k == "fold_base_bits") *value = ctx->have_fold ? ctx->fold_gamma : 0;
     else if (k == "ms_capacity") *value = (int64_t)ctx->ms_capacity;
     else if (k == "acc_capacity") *value = (int64_t)ctx->acc_capacity;
     else if (k == "wires_capacity") *value = (int64_t)ctx->wires_capacity;
@@ -273,9 +278,11 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     if (ctx->scratch_used) (void)hipStreamSynchronize(ctx->scratch_stream);
     for (void *p : {(void *)ctx->d_bsk_hat, (void *)ctx->d_bsk_hat_small, (void *)ctx->d_ksk, (void *)ctx->d_ksk_f, (void *)ctx->d_ks_corr, (void *)ctx->d_ks_a, (void *)ctx->d_ks_b, (void *)ctx->d_ks_c, (void *)ctx->d_tw_fwd, (void *)ctx->d_tw_inv, (void *)ctx->d_psi_pow, (void *)ctx->d_ms, (void *)ctx->d_ms_eps, (void *)ctx->d_ms_body, (void *)ctx->d_acc, (void *)ctx->d_stage_in, (void *)ctx->d_stage_out, (void *)ctx->d_stage_ids,
                     (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_sk_lwe_bits, (void *)ctx->d_io_msgs,
-                    (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_key, (void *)ctx->d_fold_key, (void *)ctx->d_folded, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc,
-                    (void *)ctx->d_packed, (void *)ctx->d_pub, (void *)ctx->d_audit_err, (void *)ctx->d_audit_stats})
+                    (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc, (void *)ctx->d_pub, (void *)ctx->d_audit_err, (void *)ctx->d_audit_stats})
         if (p) (void)hipFree(p);
+    for (auto &key : ctx->gadget_dev)
+        for (void *p : {(void *)key.d_key, (void *)key.d_out})
+            if (p) (void)hipFree(p);
     for (fbs_state *st : ctx->states) {   // the states still alive
         (void)hipFree(st->d);
         delete st;
@@ -568,12 +575,10 @@ int fbs_bootstrap_batch_dev(fbs_ctx *ctx, const fbs_tvset *tv, const uint64_t *d
     if (rc != FBS_OK) return rc;
     const GateView gv = batch_view(d_cts_in, d_cts_out, d_table_ids, count);
     hipStream_t s = pick(ctx, stream);
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s);
-    if (rc != FBS_OK) return scratch_fail(ctx, s, rc);
-    rc = dev_blind_rotate(ctx, tv, gv, ctx->d_ms, s);
-    if (rc != FBS_OK) return scratch_fail(ctx, s, rc);
-    return scratch_done(ctx, s);
+    return scratch_section(ctx, s, [&]() -> int {
+        if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) return rc;
+        return dev_blind_rotate(ctx, tv, gv, ctx->d_ms, s);
+    });
 } FBS_API_CATCH(ctx)
 
 int fbs_bootstrap_batch(fbs_ctx *ctx, const fbs_tvset *tv, const uint64_t *cts_in, const uint32_t *table_ids, size_t count,
@@ -600,9 +605,12 @@ int fbs_bootstrap_batch(fbs_ctx *ctx, const fbs_tvset *tv, const uint64_t *cts_i
         ctx->stage_capacity = count;
     }
     hipStream_t s = ctx->stream;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;   // the staging buffers are per-context scratch too
-    FBS_HIP(ctx, hipMemcpyAsync(ctx->d_stage_in, cts_in, words * 8, hipMemcpyHostToDevice, s));
-    if (table_ids) FBS_HIP(ctx, hipMemcpyAsync(ctx->d_stage_ids, table_ids, count * 4, hipMemcpyHostToDevice, s));
+    rc = scratch_section(ctx, s, [&]() -> int {   // the staging buffers are per-context scratch too
+        FBS_HIP(ctx, hipMemcpyAsync(ctx->d_stage_in, cts_in, words * 8, hipMemcpyHostToDevice, s));
+        if (table_ids) FBS_HIP(ctx, hipMemcpyAsync(ctx->d_stage_ids, table_ids, count * 4, hipMemcpyHostToDevice, s));
+        return FBS_OK;
+    });
+    if (rc != FBS_OK) return rc;
     rc = fbs_bootstrap_batch_dev(ctx, tv, ctx->d_stage_in, table_ids ? ctx->d_stage_ids : nullptr, count, ctx->d_stage_out, nullptr);
     if (rc != FBS_OK) {
         (void)hipStreamSynchronize(s);
@@ -935,13 +943,12 @@ int fbs_level_bootstrap_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, 
         gv.acc_rows = ctx->d_acc;
     }
     hipStream_t s = pick(ctx, stream);
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    if ((rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-    if ((rc = dev_blind_rotate(ctx, prog->tv, gv, ctx->d_ms, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-    if (b.n_shared && !d_rows &&
-        (rc = dev_multi_extract(ctx, prog->tv, ctx->d_acc, d_wires, T, s_begin, s_count, b.n_extract, b.d_x_row, b.d_x_table, b.d_x_dst, s)) != FBS_OK)
-        return scratch_fail(ctx, s, rc);
-    return scratch_done(ctx, s);
+    return scratch_section(ctx, s, [&]() -> int {
+        if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) return rc;
+        if (int rc = dev_blind_rotate(ctx, prog->tv, gv, ctx->d_ms, s)) return rc;
+        if (!b.n_shared || d_rows) return FBS_OK;
+        return dev_multi_extract(ctx, prog->tv, ctx->d_acc, d_wires, T, s_begin, s_count, b.n_extract, b.d_x_row, b.d_x_table, b.d_x_dst, s);
+    });
 } FBS_API_CATCH(ctx)
 
 int fbs_level_scatter_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, uint64_t *d_wires, size_t T, size_t s_begin,
@@ -1023,22 +1030,24 @@ int fbs_audit_level_dev(fbs_ctx *ctx, const fbs_prog *prog, uint32_t level, uint
     if ((rc = ensure_audit(ctx, n_rows, total)) != FBS_OK) return rc;
     if (fields && (rc = ensure_ms(ctx, total)) != FBS_OK) return rc;
     hipStream_t s = pick(ctx, stream);
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    if (fields) {
-        // the key switch of fbs_level_bootstrap_dev(level) over the level's full range: the same view, the same width, the same scratch
-        const BootStage &b = prog->boot[level];
-        const GateView gv = level_view(ctx, prog, b, const_cast<uint64_t *>(d_wires), nullptr, T, s_begin, s_count, 0, (size_t)b.n_gates * s_count);
-        if ((rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-        rc = dev_audit_fields(ctx, ctx->d_ms, n_rows, s_count, d_expected, ctx->d_audit_err, s);
-    } else {
-        rc = dev_audit_wire(ctx, d_wires, d_slot, n_rows, T, s_begin, s_count, d_expected, ctx->d_audit_err, s);
-    }
-    if (rc != FBS_OK || (rc = dev_audit_reduce(ctx, ctx->d_audit_err, n_rows, s_count, fields, ctx->d_audit_stats, s)) != FBS_OK)
-        return scratch_fail(ctx, s, rc);
-    if (hipMemcpyAsync(stats, ctx->d_audit_stats, (size_t)n_rows * sizeof(fbs_audit_row), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        (errors && hipMemcpyAsync(errors, ctx->d_audit_err, total * 8, hipMemcpyDeviceToHost, s) != hipSuccess))
-        return scratch_fail(ctx, s, set_error(ctx, FBS_E_DEVICE, "copying the audit's results back failed"));
-    if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
+    rc = scratch_section(ctx, s, [&]() -> int {
+        int rc;
+        if (fields) {
+            // the key switch of fbs_level_bootstrap_dev(level) over the level's full range: the same view, the same width, the same scratch
+            const BootStage &b = prog->boot[level];
+            const GateView gv = level_view(ctx, prog, b, const_cast<uint64_t *>(d_wires), nullptr, T, s_begin, s_count, 0, (size_t)b.n_gates * s_count);
+            if ((rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) != FBS_OK) return rc;
+            rc = dev_audit_fields(ctx, ctx->d_ms, n_rows, s_count, d_expected, ctx->d_audit_err, s);
+        } else {
+            rc = dev_audit_wire(ctx, d_wires, d_slot, n_rows, T, s_begin, s_count, d_expected, ctx->d_audit_err, s);
+        }
+        if (rc != FBS_OK || (rc = dev_audit_reduce(ctx, ctx->d_audit_err, n_rows, s_count, fields, ctx->d_audit_stats, s)) != FBS_OK) return rc;
+        if (hipMemcpyAsync(stats, ctx->d_audit_stats, (size_t)n_rows * sizeof(fbs_audit_row), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            (errors && hipMemcpyAsync(errors, ctx->d_audit_err, total * 8, hipMemcpyDeviceToHost, s) != hipSuccess))
+            return set_error(ctx, FBS_E_DEVICE, "copying the audit's results back failed");
+        return FBS_OK;
+    });
+    if (rc != FBS_OK) return rc;
     FBS_HIP(ctx, hipStreamSynchronize(s));
     return FBS_OK;
 } FBS_API_CATCH(ctx)
@@ -1135,6 +1144,15 @@ static int check_state_rows(const fbs_ctx *ctx, const fbs_state *st, size_t row0
     if (rows && !host) return set_error(ctx, FBS_E_INVALID, "null argument");
     return FBS_OK;
 }
+// rows [row0, row0 + rows) of a checked state, flattened [row][sample]: one run of rows * T ciphertexts, which the kernels read and
+// write as they do a plain batch (a state's rows * T * (D + 1) words fit a size_t)
+struct StateSpan {
+    uint64_t *d;
+    size_t count;
+};
+static StateSpan state_span(const fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows) {
+    return {st->d + row0 * st->T * (ctx->D + 1), rows * st->T};
+}
 
 int fbs_state_fetch(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint32_t bits, uint64_t *out) try {
     if (!ctx) return FBS_E_INVALID;
@@ -1144,8 +1162,9 @@ int fbs_state_fetch(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows,
     if (rows == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const size_t ctw = ctx->D + 1, count = rows * st->T;
-    const uint64_t *d_cts = st->d + row0 * st->T * ctw;
+    const StateSpan span = state_span(ctx, st, row0, rows);
+    const size_t ctw = ctx->D + 1, count = span.count;
+    const uint64_t *d_cts = span.d;
     if (!bits) {
         FBS_HIP(ctx, hipMemcpyAsync(out, d_cts, count * ctw * 8, hipMemcpyDeviceToHost, s));
         return sync_stream(ctx, s);
@@ -1169,11 +1188,12 @@ int fbs_state_put(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const u
     if (!ctx) return FBS_E_INVALID;
     if (int rc = check_state_rows(ctx, st, row0, rows, cts)) return rc;
     if (rows == 0) return FBS_OK;
-    const size_t ctw = ctx->D + 1, words = rows * st->T * ctw;
+    const StateSpan span = state_span(ctx, st, row0, rows);
+    const size_t words = span.count * (ctx->D + 1);
     for (size_t i = 0; i < words; i++)
         if (cts[i] >= FQ) return set_error(ctx, FBS_E_INVALID, "word " + std::to_string(i) + " is not a canonical residue");
     FBS_HIP(ctx, hipSetDevice(ctx->device));
-    FBS_HIP(ctx, hipMemcpyAsync(st->d + row0 * st->T * ctw, cts, words * 8, hipMemcpyHostToDevice, ctx->stream));
+    FBS_HIP(ctx, hipMemcpyAsync(span.d, cts, words * 8, hipMemcpyHostToDevice, ctx->stream));
     return sync_stream(ctx, ctx->stream);
 } FBS_API_CATCH(ctx)
 
@@ -1191,8 +1211,7 @@ int fbs_state_sum_groups(fbs_ctx *ctx, const fbs_state *src, size_t row0, size_t
                                                  " of " + std::to_string(src->T) + " samples make " + std::to_string(T_dst));
     if (rows == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t ctw = ctx->D + 1;
-    return dev_state_sum_groups(ctx, SumGroups{src->d + row0 * src->T * ctw, dst->d + dst_row0 * T_dst * ctw, rows, src->T, T_dst, group, ctx->D},
+    return dev_state_sum_groups(ctx, SumGroups{state_span(ctx, src, row0, rows).d, state_span(ctx, dst, dst_row0, rows).d, rows, src->T, T_dst, group, ctx->D},
                                 ctx->stream);
 } FBS_API_CATCH(ctx)
 
@@ -1205,313 +1224,214 @@ int fbs_pub_expand_dev(fbs_ctx *ctx, const uint64_t *d_glwe, size_t count, uint6
     return dev_expand_public(ctx, d_glwe, count, d_cts, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
-// rows [row0, row0 + rows) flattened [row][sample] are one run of rows * T ciphertexts in the state: the kernel writes it as it
-// writes a plain batch
 int fbs_state_put_public(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *glwe) try {
     if (!ctx) return FBS_E_INVALID;
     int rc = check_state_rows(ctx, st, row0, rows, glwe);
     if (rc != FBS_OK) return rc;
     if (rows == 0) return FBS_OK;
-    const size_t ctw = ctx->D + 1, count = rows * st->T;   // (a state's rows * T * (D + 1) words fit a size_t, and so do the samples')
-    const size_t words = (count + ctx->N - 1) / ctx->N * ((size_t)ctx->D + ctx->N);
+    const StateSpan span = state_span(ctx, st, row0, rows);
+    const size_t count = span.count, words = (count + ctx->N - 1) / ctx->N * ((size_t)ctx->D + ctx->N);   // (the samples are fewer words)
     const size_t bad = first_noncanonical(glwe, words);
     if (bad < words) return set_error(ctx, FBS_E_INVALID, "sample word " + std::to_string(bad) + " is not a canonical residue");
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     if ((rc = grow(ctx, ctx->d_pub, ctx->pub_capacity, words, 8, true)) != FBS_OK) return rc;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    if (hipMemcpyAsync(ctx->d_pub, glwe, words * 8, hipMemcpyHostToDevice, s) != hipSuccess)
-        return scratch_fail(ctx, s, set_error(ctx, FBS_E_DEVICE, "copying samples to the device failed"));
-    if ((rc = dev_expand_public(ctx, ctx->d_pub, count, st->d + row0 * st->T * ctw, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-    if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
-    return sync_stream(ctx, s);
+    rc = scratch_section(ctx, s, [&]() -> int {
+        if (hipMemcpyAsync(ctx->d_pub, glwe, words * 8, hipMemcpyHostToDevice, s) != hipSuccess)
+            return set_error(ctx, FBS_E_DEVICE, "copying samples to the device failed");
+        return dev_expand_public(ctx, ctx->d_pub, count, span.d, s);
+    });
+    return rc != FBS_OK ? rc : sync_stream(ctx, s);
 } FBS_API_CATCH(ctx)
 
-// ---- packed outputs: up to N outputs in one GLWE sample under the big key (fbs_pack.hpp, fbs_pack.hip) -----------------------
-// installs (t_p, gamma_p, bodies) as the context's packing key: expands the masks, transforms on the device; the previous key
-// stays until this has succeeded
-static int install_packing_key(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies) {
+// ---- the gadget keys (GadgetKind, fbs_internal.hpp): the packing key of packed outputs, the fold key of folded state ------------
+// installs (t, gamma, bodies) as the context's key of `kind`: expands the masks, transforms on the device; the previous key stays
+// until this has succeeded
+static int install_gadget_key(fbs_ctx *ctx, GadgetKind kind, uint32_t t, uint32_t gamma, std::vector<uint64_t> &bodies) {
+    HostState::GadgetKeyState &key = ctx->gadget[kind];
     std::vector<uint64_t> full;
-    host_expand_packing_key(ctx, ctx->mask_key, t_p, bodies.data(), full);
-    const bool had = ctx->have_pack;
-    ctx->have_pack = false;
-    if (int rc = dev_upload_packing_key(ctx, full, t_p)) {
+    host_expand_gadget_key(ctx, kind, ctx->mask_key, t, bodies.data(), full);
+    const bool had = key.have;
+    key.have = false;
+    if (int rc = dev_upload_gadget_key(ctx, kind, full, t)) {
         // (the device copy may be half written: re-install the previous key, or leave the context without one)
         if (had) {
-            host_expand_packing_key(ctx, ctx->mask_key, ctx->pack_t, ctx->pack_bodies.data(), full);
+            host_expand_gadget_key(ctx, kind, ctx->mask_key, key.t, key.bodies.data(), full);
             const std::string text = ctx->err;
-            ctx->have_pack = dev_upload_packing_key(ctx, full, ctx->pack_t) == FBS_OK;
+            key.have = dev_upload_gadget_key(ctx, kind, full, key.t) == FBS_OK;
             ctx->err = text;
         }
         return rc;
     }
-    ctx->pack_bodies.swap(bodies);
-    ctx->pack_t = t_p;
-    ctx->pack_gamma = gamma_p;
-    ctx->have_pack = true;
+    gadget_key_in_place(ctx, kind, t, gamma, bodies);
     return FBS_OK;
 }
-
-int fbs_packing_keygen(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) try {
-    if (int rc = check_packing_keygen(ctx, t_p, gamma_p)) return rc;
+static int gadget_keygen(fbs_ctx *ctx, GadgetKind kind, uint32_t t, uint32_t gamma) {
+    if (int rc = check_gadget_keygen(ctx, kind, t, gamma)) return rc;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<uint64_t> bodies;
     if (ctx->tune.keys_on_device) {
-        if (int rc = dev_packing_bodies(ctx, t_p, gamma_p, bodies)) return rc;
+        if (int rc = dev_gadget_bodies(ctx, kind, t, gamma, bodies)) return rc;
     } else {
-        host_packing_keygen(ctx, t_p, gamma_p, bodies);
+        host_gadget_keygen(ctx, kind, t, gamma, bodies);
     }
-    return install_packing_key(ctx, t_p, gamma_p, bodies);
+    return install_gadget_key(ctx, kind, t, gamma, bodies);
+}
+// (no secret needed: the masks come from the mask key an evaluation-only context has received)
+static int import_gadget_key(fbs_ctx *ctx, GadgetKind kind, uint32_t t, uint32_t gamma, const uint64_t *bodies) {
+    if (!ctx) return FBS_E_INVALID;
+    if (!bodies) return set_error(ctx, FBS_E_INVALID, "null argument");
+    if (int rc = check_gadget_keygen(ctx, kind, t, gamma, false, "fbs_import_seeded_keys")) return rc;
+    const size_t words = (size_t)gadget_rows(*ctx, kind) * t * ctx->N;
+    for (size_t i = 0; i < words; i++)
+        if (bodies[i] >= FQ) return set_error(ctx, FBS_E_INVALID, gadget_text(kind, "@-key body word is not a canonical residue"));
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> copy(bodies, bodies + words);
+    return install_gadget_key(ctx, kind, t, gamma, copy);
+}
+
+int fbs_packing_keygen(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) try {
+    return gadget_keygen(ctx, GK_PACK, t_p, gamma_p);
 } FBS_API_CATCH(ctx)
 
 int fbs_import_packing_key(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, const uint64_t *bodies) try {
-    if (!ctx) return FBS_E_INVALID;
-    if (!bodies) return set_error(ctx, FBS_E_INVALID, "null argument");
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "a packing key goes with seeded keys (fbs_import_seeded_keys)");
-    if (int rc = check_packing_params(ctx, t_p, gamma_p)) return rc;
-    const size_t words = (size_t)ctx->p.n * t_p * ctx->N;
-    for (size_t i = 0; i < words; i++)
-        if (bodies[i] >= FQ) return set_error(ctx, FBS_E_INVALID, "packing-key body word is not a canonical residue");
-    FBS_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint64_t> copy(bodies, bodies + words);
-    return install_packing_key(ctx, t_p, gamma_p, copy);
+    return import_gadget_key(ctx, GK_PACK, t_p, gamma_p, bodies);
 } FBS_API_CATCH(ctx)
 
-// Ciphertexts per pass: what the modulus-switch scratch holds (at least COMPACT_PASS), cut down to whole samples -- and the
-// packing scratch for a pass of that size (transposed fields, partial accumulators), grown like any other scratch
-static int pack_reserve(fbs_ctx *ctx, size_t count, size_t *pass_out) {
-    const size_t N = ctx->N, whole = std::max(ctx->ms_capacity, COMPACT_PASS) / N * N;
-    const size_t pass = std::min((count + N - 1) / N * N, whole), samples = pass / N;
-    if (int rc = ensure_ms(ctx, std::min(count, pass))) return rc;
-    if (int rc = grow(ctx, ctx->d_pack_fields, ctx->pack_fields_capacity, (size_t)(ctx->p.n + 1) * pass, 4, true)) return rc;
-    // (slices x samples is largest for the whole pass or for a single sample, whichever the launch rule favours)
-    size_t rows = 0;
-    for (size_t g = 1; g <= samples; g++) rows = std::max(rows, g * pack_slices_for(ctx, g, ctx->p.n));
-    if (int rc = grow(ctx, ctx->d_pack_acc, ctx->pack_acc_capacity, rows * (ctx->p.k + 1) * N, 8, true)) return rc;
-    *pass_out = pass;
-    return FBS_OK;
-}
-static int pack_prologue(const fbs_ctx *ctx, size_t count, uint32_t bits) {
+int fbs_fold_keygen(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f) try {
+    return gadget_keygen(ctx, GK_FOLD, t_f, gamma_f);
+} FBS_API_CATCH(ctx)
+
+int fbs_fold_key_sizes(const fbs_ctx *ctx, uint32_t t_f, size_t sizes[2]) try {
+    return gadget_key_sizes(ctx, GK_FOLD, t_f, sizes);
+} FBS_API_CATCH(ctx)
+
+int fbs_export_fold_key(const fbs_ctx *ctx, uint64_t *bodies, uint64_t *full) try {
+    return gadget_key_export(ctx, GK_FOLD, bodies, full);
+} FBS_API_CATCH(ctx)
+
+int fbs_import_fold_key(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, const uint64_t *bodies) try {
+    return import_gadget_key(ctx, GK_FOLD, t_f, gamma_f, bodies);
+} FBS_API_CATCH(ctx)
+
+// ---- packed outputs: up to N outputs in one GLWE sample under the big key (fbs_pack.hpp, fbs_pack.hip); folded state: N resident
+// ---- ciphertexts in one full-precision GLWE sample under the big key (fbs_fold.hip) ------------------------------------------------
+// what both check first; the words of the result must not overflow (folding: the samples are fewer words than the ciphertexts)
+static int gadget_prologue(const fbs_ctx *ctx, GadgetKind kind, size_t count, uint32_t bits) {
     if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (!ctx->have_pack) return set_error(ctx, FBS_E_STATE, "the context has no packing key (fbs_packing_keygen / fbs_import_packing_key)");
+    if (!ctx->gadget[kind].have) return set_error(ctx, FBS_E_STATE, gadget_text(kind, "the context has no @ key (fbs_@_keygen / fbs_import_@_key)"));
+    if (kind == GK_FOLD) return check_ct_words(ctx, count);
     if (int rc = check_bits(ctx, bits)) return rc;
     return check_packed_words(ctx, count, bits);
 }
-// the passes of fbs_pack_dev; `staging` non-null: each pass is packed there and copied to the host array `out`
-static int pack_passes(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_words, uint64_t *out, size_t pass,
-                       hipStream_t s) {
-    const size_t ctw = ctx->D + 1, per_pass = packed_words(ctx->p.k, ctx->N, pass, bits);
-    for (size_t f0 = 0; f0 < count; f0 += pass) {
-        const size_t rows = std::min(pass, count - f0), w0 = f0 / pass * per_pass;
-        const GateView gv = batch_view(d_cts + f0 * ctw, nullptr, nullptr, rows);
-        uint64_t *dst = out ? d_words : d_words + w0;
-        int rc = dev_keyswitch(ctx, gv, ctx->d_ms, 31, s);
-        if (rc == FBS_OK) rc = dev_pack(ctx, ctx->d_ms, rows, bits, dst, s);
-        if (rc != FBS_OK) return rc;
-        if (out && hipMemcpyAsync(out + w0, dst, packed_words(ctx->p.k, ctx->N, rows, bits) * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
-            return set_error(ctx, FBS_E_DEVICE, "copying packed words to the host failed");
+// The scratch both share for a pass of `pass` ciphertexts, grown like any other: `col_words` field words a ciphertext, and the
+// partial accumulators of a sum over `rows` key rows
+static int pack_scratch_reserve(fbs_ctx *ctx, size_t pass, size_t col_words, uint32_t rows) {
+    if (int rc = grow(ctx, ctx->d_pack_fields, ctx->pack_fields_capacity, col_words * pass, 4, true)) return rc;
+    // (slices x samples is largest for the whole pass or for a single sample, whichever the launch rule favours)
+    size_t acc = 0;
+    for (size_t g = 1; g <= pass / ctx->N; g++) acc = std::max(acc, g * pack_slices_for(ctx, g, rows));
+    return grow(ctx, ctx->d_pack_acc, ctx->pack_acc_capacity, acc * (ctx->p.k + 1) * ctx->N, 8, true);
+}
+// Ciphertexts per pass: what the modulus-switch scratch holds (at least COMPACT_PASS), cut down to whole samples -- and the
+// scratch for a pass of that size: the modulus switch's, the transposed fields [n + 1]
+static int pack_reserve(fbs_ctx *ctx, size_t count, size_t *pass_out) {
+    const size_t N = ctx->N, whole = std::max(ctx->ms_capacity, COMPACT_PASS) / N * N;
+    *pass_out = std::min((count + N - 1) / N * N, whole);
+    if (int rc = ensure_ms(ctx, std::min(count, *pass_out))) return rc;
+    return pack_scratch_reserve(ctx, *pass_out, (size_t)ctx->p.n + 1, ctx->p.n);
+}
+// Ciphertexts per pass: COMPACT_PASS cut down to whole samples (one sample at N = 4096 and above it) -- and the scratch for a pass
+// of that size: D rows of rounded fields and the 64-bit body words
+static int fold_reserve(fbs_ctx *ctx, size_t count, size_t *pass_out) {
+    const size_t N = ctx->N, whole = std::max(COMPACT_PASS, N) / N * N;
+    *pass_out = std::min((count + N - 1) / N * N, whole);
+    return pack_scratch_reserve(ctx, *pass_out, (size_t)ctx->D + 2, ctx->D);
+}
+// What the five entries below do once their arguments are checked: the scratch, then inside one scratch section the passes of
+// `count` ciphertexts at d_cts, packed at `bits` (GK_PACK) or folded (GK_FOLD).  A pass of `rows` ciphertexts leaves words_of(rows)
+// words, in d_dst at words_of(pass) a pass -- or, `out` given, in the kind's staging and from there in that host array, which is
+// complete when the call returns
+static int gadget_passes(fbs_ctx *ctx, GadgetKind kind, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_dst, uint64_t *out,
+                         hipStream_t s) {
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t N = ctx->N, k = ctx->p.k;
+    const bool packing = kind == GK_PACK;
+    size_t pass = 0;
+    int rc = packing ? pack_reserve(ctx, count, &pass) : fold_reserve(ctx, count, &pass);
+    if (rc != FBS_OK) return rc;
+    auto words_of = [=](size_t rows) { return packing ? packed_words(k, N, rows, bits) : (rows + N - 1) / N * ((size_t)k * N + N); };
+    if (out) {
+        fbs_ctx::GadgetKeyDev &dev = ctx->gadget_dev[kind];
+        if ((rc = grow(ctx, dev.d_out, dev.out_capacity, words_of(pass), 8, true)) != FBS_OK) return rc;
+        d_dst = dev.d_out;
     }
-    return FBS_OK;
+    rc = scratch_section(ctx, s, [&]() -> int {
+        const size_t ctw = ctx->D + 1;
+        for (size_t f0 = 0; f0 < count; f0 += pass) {
+            const size_t rows = std::min(pass, count - f0), w0 = f0 / pass * words_of(pass);
+            const uint64_t *cts = d_cts + f0 * ctw;
+            uint64_t *dst = out ? d_dst : d_dst + w0;
+            int rc = packing ? dev_keyswitch(ctx, batch_view(cts, nullptr, nullptr, rows), ctx->d_ms, 31, s) : dev_fold(ctx, cts, rows, dst, s);
+            if (rc == FBS_OK && packing) rc = dev_pack(ctx, ctx->d_ms, rows, bits, dst, s);
+            if (rc != FBS_OK) return rc;
+            if (out && hipMemcpyAsync(out + w0, dst, words_of(rows) * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+                return set_error(ctx, FBS_E_DEVICE, packing ? "copying packed words to the host failed" : "copying folded samples to the host failed");
+        }
+        return FBS_OK;
+    });
+    return rc != FBS_OK || !out ? rc : sync_stream(ctx, s);
 }
 
 // (no secret needed: runs on evaluation-only contexts)
 int fbs_pack_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_words, void *stream) try {
     if (int rc = io_prologue(ctx, d_cts, d_words, count, IO_CT_WORDS, nullptr)) return rc;
-    if (int rc = pack_prologue(ctx, count, bits)) return rc;
+    if (int rc = gadget_prologue(ctx, GK_PACK, count, bits)) return rc;
     if (count == 0) return FBS_OK;
-    FBS_HIP(ctx, hipSetDevice(ctx->device));
-    size_t pass = 0;
-    int rc = pack_reserve(ctx, count, &pass);
-    if (rc != FBS_OK) return rc;
-    hipStream_t s = pick(ctx, stream);
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    if ((rc = pack_passes(ctx, d_cts, count, bits, d_words, nullptr, pass, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-    return scratch_done(ctx, s);
+    return gadget_passes(ctx, GK_PACK, d_cts, count, bits, d_words, nullptr, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
 int fbs_state_fetch_packed(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint32_t bits, uint64_t *out) try {
     if (!ctx) return FBS_E_INVALID;
-    int rc = check_state_rows(ctx, st, row0, rows, out);
-    if (rc != FBS_OK) return rc;
-    const size_t count = rows * st->T;   // (a state's rows * T * (D + 1) words fit a size_t)
-    if ((rc = pack_prologue(ctx, count, bits)) != FBS_OK) return rc;
+    if (int rc = check_state_rows(ctx, st, row0, rows, out)) return rc;
+    const StateSpan span = state_span(ctx, st, row0, rows);
+    if (int rc = gadget_prologue(ctx, GK_PACK, span.count, bits)) return rc;
     if (rows == 0) return FBS_OK;
-    FBS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    size_t pass = 0;
-    if ((rc = pack_reserve(ctx, count, &pass)) != FBS_OK) return rc;
-    if ((rc = grow(ctx, ctx->d_packed, ctx->packed_capacity, packed_words(ctx->p.k, ctx->N, pass, bits), 8, true)) != FBS_OK) return rc;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    if ((rc = pack_passes(ctx, st->d + row0 * st->T * (ctx->D + 1), count, bits, ctx->d_packed, out, pass, s)) != FBS_OK)
-        return scratch_fail(ctx, s, rc);
-    if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
-    return sync_stream(ctx, s);
+    return gadget_passes(ctx, GK_PACK, span.d, span.count, bits, nullptr, out, ctx->stream);
 } FBS_API_CATCH(ctx)
 
-// ---- folded state: N resident ciphertexts in one full-precision GLWE sample under the big key (fbs_fold.hip) --------------------
-// installs (t_f, gamma_f, bodies) as the context's fold key, as install_packing_key installs a packing key
-static int install_fold_key(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, std::vector<uint64_t> &bodies) {
-    std::vector<uint64_t> full;
-    host_expand_fold_key(ctx, ctx->mask_key, t_f, bodies.data(), full);
-    const bool had = ctx->have_fold;
-    ctx->have_fold = false;
-    if (int rc = dev_upload_fold_key(ctx, full, t_f)) {
-        if (had) {   // (the device copy may be half written: the previous key goes back, or the context is left without one)
-            host_expand_fold_key(ctx, ctx->mask_key, ctx->fold_t, ctx->fold_bodies.data(), full);
-            const std::string text = ctx->err;
-            ctx->have_fold = dev_upload_fold_key(ctx, full, ctx->fold_t) == FBS_OK;
-            ctx->err = text;
-        }
-        return rc;
-    }
-    ctx->fold_bodies.swap(bodies);
-    ctx->fold_t = t_f;
-    ctx->fold_gamma = gamma_f;
-    ctx->have_fold = true;
-    return FBS_OK;
-}
-// the parameter range and the shapes are the packing key's (the accumulate kernel is the same one)
-static int check_fold_params(const fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f) {
-    if (t_f < 1 || gamma_f < 1) return set_error(ctx, FBS_E_INVALID, "fold key needs t_f >= 1 and gamma_f >= 1");
-    if (t_f > 31 || gamma_f > 31 || t_f * gamma_f > 31) return set_error(ctx, FBS_E_INVALID, "fold key needs t_f * gamma_f <= 31");
-    if (!pack_shape_built(ctx->p.log_n_poly, ctx->p.k)) return set_error(ctx, FBS_E_INVALID, "no fold kernel for this (k, N)");
-    return FBS_OK;
-}
-
-int fbs_fold_keygen(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f) try {
-    if (!ctx) return FBS_E_INVALID;
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (ctx->eval_only) return set_error(ctx, FBS_E_STATE, EVAL_ONLY);
-    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "a fold key goes with seeded keys (fbs_keygen_seeded)");
-    if (int rc = check_fold_params(ctx, t_f, gamma_f)) return rc;
-    FBS_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint64_t> bodies;
-    if (ctx->tune.keys_on_device) {
-        if (int rc = dev_fold_bodies(ctx, t_f, gamma_f, bodies)) return rc;
-    } else {
-        host_fold_keygen(ctx, t_f, gamma_f, bodies);
-    }
-    return install_fold_key(ctx, t_f, gamma_f, bodies);
-} FBS_API_CATCH(ctx)
-
-int fbs_fold_key_sizes(const fbs_ctx *ctx, uint32_t t_f, size_t sizes[2]) try {
-    if (!ctx || !sizes) return FBS_E_INVALID;
-    if (t_f == 0) {
-        if (!ctx->have_fold) return set_error(ctx, FBS_E_STATE, "the context has no fold key");
-        t_f = ctx->fold_t;
-    }
-    if (t_f > 31) return set_error(ctx, FBS_E_INVALID, "fold key needs 1 <= t_f <= 31");
-    sizes[0] = (size_t)ctx->D * t_f * ctx->N;
-    sizes[1] = sizes[0] * (ctx->p.k + 1);
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_export_fold_key(const fbs_ctx *ctx, uint64_t *bodies, uint64_t *full) try {
-    if (!ctx) return FBS_E_INVALID;
-    if (!ctx->have_fold) return set_error(ctx, FBS_E_STATE, "the context has no fold key");
-    if (bodies) std::memcpy(bodies, ctx->fold_bodies.data(), ctx->fold_bodies.size() * 8);
-    if (full) {
-        std::vector<uint64_t> key;
-        host_expand_fold_key(ctx, ctx->mask_key, ctx->fold_t, ctx->fold_bodies.data(), key);
-        std::memcpy(full, key.data(), key.size() * 8);
-    }
-    return FBS_OK;
-} FBS_API_CATCH(ctx)
-
-int fbs_import_fold_key(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, const uint64_t *bodies) try {
-    if (!ctx) return FBS_E_INVALID;
-    if (!bodies) return set_error(ctx, FBS_E_INVALID, "null argument");
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (!ctx->seeded_keys) return set_error(ctx, FBS_E_STATE, "a fold key goes with seeded keys (fbs_import_seeded_keys)");
-    if (int rc = check_fold_params(ctx, t_f, gamma_f)) return rc;
-    const size_t words = (size_t)ctx->D * t_f * ctx->N;
-    for (size_t i = 0; i < words; i++)
-        if (bodies[i] >= FQ) return set_error(ctx, FBS_E_INVALID, "fold-key body word is not a canonical residue");
-    FBS_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint64_t> copy(bodies, bodies + words);
-    return install_fold_key(ctx, t_f, gamma_f, copy);
-} FBS_API_CATCH(ctx)
-
-// Ciphertexts per pass: COMPACT_PASS cut down to whole samples (one sample at N = 4096 and above it), and the packing scratch for
-// a pass of that size: D rows of rounded fields and the 64-bit body words, the partial accumulators
-static int fold_reserve(fbs_ctx *ctx, size_t count, size_t *pass_out) {
-    const size_t N = ctx->N, whole = std::max(COMPACT_PASS, N) / N * N;
-    const size_t pass = std::min((count + N - 1) / N * N, whole), samples = pass / N;
-    if (int rc = grow(ctx, ctx->d_pack_fields, ctx->pack_fields_capacity, ((size_t)ctx->D + 2) * pass, 4, true)) return rc;
-    size_t rows = 0;
-    for (size_t g = 1; g <= samples; g++) rows = std::max(rows, g * pack_slices_for(ctx, g, ctx->D));
-    if (int rc = grow(ctx, ctx->d_pack_acc, ctx->pack_acc_capacity, rows * (ctx->p.k + 1) * N, 8, true)) return rc;
-    *pass_out = pass;
-    return FBS_OK;
-}
-static int fold_prologue(const fbs_ctx *ctx, size_t count) {
-    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
-    if (!ctx->have_fold) return set_error(ctx, FBS_E_STATE, "the context has no fold key (fbs_fold_keygen / fbs_import_fold_key)");
-    return check_ct_words(ctx, count);   // (the samples are fewer words than the ciphertexts)
-}
-// the passes of fbs_fold_dev; `out` non-null: each pass is folded into d_glwe (staging) and copied to the host array `out`
-static int fold_passes(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, uint64_t *out, size_t pass, hipStream_t s) {
-    const size_t ctw = ctx->D + 1, sw = (size_t)ctx->D + ctx->N;
-    for (size_t f0 = 0; f0 < count; f0 += pass) {
-        const size_t rows = std::min(pass, count - f0), w0 = f0 / ctx->N * sw, words = (rows + ctx->N - 1) / ctx->N * sw;
-        uint64_t *dst = out ? d_glwe : d_glwe + w0;
-        if (int rc = dev_fold(ctx, d_cts + f0 * ctw, rows, dst, s)) return rc;
-        if (out && hipMemcpyAsync(out + w0, dst, words * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
-            return set_error(ctx, FBS_E_DEVICE, "copying folded samples to the host failed");
-    }
+// folded samples are written 16 bytes a lane
+static int check_fold_target(const fbs_ctx *ctx, const uint64_t *d_glwe) {
+    if ((uintptr_t)d_glwe & 15u) return set_error(ctx, FBS_E_INVALID, "folded samples are written 16 bytes a lane: d_glwe must be 16-byte aligned");
     return FBS_OK;
 }
 
 // (no secret needed: runs on evaluation-only contexts)
 int fbs_fold_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, void *stream) try {
     if (!ctx || (count && (!d_cts || !d_glwe))) return FBS_E_INVALID;
-    if (int rc = fold_prologue(ctx, count)) return rc;
-    if ((uintptr_t)d_glwe & 15u) return set_error(ctx, FBS_E_INVALID, "folded samples are written 16 bytes a lane: d_glwe must be 16-byte aligned");
+    if (int rc = gadget_prologue(ctx, GK_FOLD, count, 0)) return rc;
+    if (int rc = check_fold_target(ctx, d_glwe)) return rc;
     if (count == 0) return FBS_OK;
-    FBS_HIP(ctx, hipSetDevice(ctx->device));
-    size_t pass = 0;
-    int rc = fold_reserve(ctx, count, &pass);
-    if (rc != FBS_OK) return rc;
-    hipStream_t s = pick(ctx, stream);
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    if ((rc = fold_passes(ctx, d_cts, count, d_glwe, nullptr, pass, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-    return scratch_done(ctx, s);
+    return gadget_passes(ctx, GK_FOLD, d_cts, count, 0, d_glwe, nullptr, pick(ctx, stream));
 } FBS_API_CATCH(ctx)
 
 int fbs_state_fold(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint64_t *out) try {
     if (!ctx) return FBS_E_INVALID;
-    int rc = check_state_rows(ctx, st, row0, rows, out);
-    if (rc != FBS_OK) return rc;
-    const size_t count = rows * st->T;   // (a state's rows * T * (D + 1) words fit a size_t)
-    if ((rc = fold_prologue(ctx, count)) != FBS_OK) return rc;
+    if (int rc = check_state_rows(ctx, st, row0, rows, out)) return rc;
+    const StateSpan span = state_span(ctx, st, row0, rows);
+    if (int rc = gadget_prologue(ctx, GK_FOLD, span.count, 0)) return rc;
     if (rows == 0) return FBS_OK;
-    FBS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    size_t pass = 0;
-    if ((rc = fold_reserve(ctx, count, &pass)) != FBS_OK) return rc;
-    if ((rc = grow(ctx, ctx->d_folded, ctx->folded_capacity, pass / ctx->N * ((size_t)ctx->D + ctx->N), 8, true)) != FBS_OK) return rc;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    if ((rc = fold_passes(ctx, st->d + row0 * st->T * (ctx->D + 1), count, ctx->d_folded, out, pass, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-    if ((rc = scratch_done(ctx, s)) != FBS_OK) return rc;
-    return sync_stream(ctx, s);
+    return gadget_passes(ctx, GK_FOLD, span.d, span.count, 0, nullptr, out, ctx->stream);
 } FBS_API_CATCH(ctx)
 
 int fbs_state_fold_dev(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint64_t *d_glwe) try {
     if (!ctx) return FBS_E_INVALID;
-    int rc = check_state_rows(ctx, st, row0, rows, d_glwe);
-    if (rc != FBS_OK) return rc;
-    const size_t count = rows * st->T;
-    if ((rc = fold_prologue(ctx, count)) != FBS_OK) return rc;
-    if ((uintptr_t)d_glwe & 15u) return set_error(ctx, FBS_E_INVALID, "folded samples are written 16 bytes a lane: d_glwe must be 16-byte aligned");
+    if (int rc = check_state_rows(ctx, st, row0, rows, d_glwe)) return rc;
+    const StateSpan span = state_span(ctx, st, row0, rows);
+    if (int rc = gadget_prologue(ctx, GK_FOLD, span.count, 0)) return rc;
+    if (int rc = check_fold_target(ctx, d_glwe)) return rc;
     if (rows == 0) return FBS_OK;
-    FBS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    size_t pass = 0;
-    if ((rc = fold_reserve(ctx, count, &pass)) != FBS_OK) return rc;
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    if ((rc = fold_passes(ctx, st->d + row0 * st->T * (ctx->D + 1), count, d_glwe, nullptr, pass, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-    return scratch_done(ctx, s);
+    return gadget_passes(ctx, GK_FOLD, span.d, span.count, 0, d_glwe, nullptr, ctx->stream);
 } FBS_API_CATCH(ctx)
 
 // the device-source twin of fbs_state_put_public: no staging, no check of the words (device memory), queued on the context's stream
@@ -1520,7 +1440,8 @@ int fbs_state_unfold_dev(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, 
     if (int rc = check_state_rows(ctx, st, row0, rows, d_glwe)) return rc;
     if (rows == 0) return FBS_OK;
     FBS_HIP(ctx, hipSetDevice(ctx->device));
-    return dev_expand_public(ctx, d_glwe, rows * st->T, st->d + row0 * st->T * (ctx->D + 1), ctx->stream);
+    const StateSpan span = state_span(ctx, st, row0, rows);
+    return dev_expand_public(ctx, d_glwe, span.count, span.d, ctx->stream);
 } FBS_API_CATCH(ctx)
 
 // test hook of the front kernel alone: d_cts [count][D + 1] -> d_fields [D][cols] uint32 rounded to tg bits, then cols 64-bit body
@@ -1671,18 +1592,15 @@ int fbs_debug_gauss_dev(fbs_ctx *ctx, const uint64_t *d_words, size_t count, uin
 // on the caller's pointer in place of the modulus-switch scratch.
 int fbs_debug_pack_fields_dev(fbs_ctx *ctx, const uint32_t *d_fields, size_t count, uint32_t bits, uint64_t *d_words, void *stream) try {
     if (int rc = io_prologue(ctx, d_fields, d_words, count, 0, nullptr)) return rc;
-    if (int rc = pack_prologue(ctx, count, bits)) return rc;
+    if (int rc = gadget_prologue(ctx, GK_PACK, count, bits)) return rc;
     if (count == 0) return FBS_OK;
     if (count > std::max(ctx->ms_capacity, COMPACT_PASS) / ctx->N * ctx->N)
         return set_error(ctx, FBS_E_INVALID, "more fields than one pass of fbs_pack_dev holds");
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     size_t pass = 0;
-    int rc = pack_reserve(ctx, count, &pass);
-    if (rc != FBS_OK) return rc;
+    if (int rc = pack_reserve(ctx, count, &pass)) return rc;
     hipStream_t s = pick(ctx, stream);
-    if ((rc = scratch_wait(ctx, s)) != FBS_OK) return rc;
-    if ((rc = dev_pack(ctx, d_fields, count, bits, d_words, s)) != FBS_OK) return scratch_fail(ctx, s, rc);
-    return scratch_done(ctx, s);
+    return scratch_section(ctx, s, [&] { return dev_pack(ctx, d_fields, count, bits, d_words, s); });
 } FBS_API_CATCH(ctx)
 
 }  // extern "C"

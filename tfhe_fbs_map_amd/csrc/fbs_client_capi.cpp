@@ -74,13 +74,10 @@ int fbs_keygen_seeded(fbs_ctx *ctx) try {
 } FBS_API_CATCH(ctx)
 
 int fbs_packing_keygen(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p) try {
-    if (int rc = check_packing_keygen(ctx, t_p, gamma_p)) return rc;
+    if (int rc = check_gadget_keygen(ctx, GK_PACK, t_p, gamma_p)) return rc;
     std::vector<uint64_t> bodies;
-    host_packing_keygen(ctx, t_p, gamma_p, bodies);
-    ctx->pack_bodies.swap(bodies);
-    ctx->pack_t = t_p;
-    ctx->pack_gamma = gamma_p;
-    ctx->have_pack = true;
+    host_gadget_keygen(ctx, GK_PACK, t_p, gamma_p, bodies);
+    gadget_key_in_place(ctx, GK_PACK, t_p, gamma_p, bodies);
     return FBS_OK;
 } FBS_API_CATCH(ctx)
 

@@ -146,27 +146,11 @@ int fbs_decrypt_compact(const fbs_ctx *ctx, const uint64_t *words, size_t count,
 
 // ---- packed outputs: the packing key's sizes and export, the decoder (fbs_pack.hpp) ------------
 int fbs_packing_key_sizes(const fbs_ctx *ctx, uint32_t t_p, size_t sizes[2]) try {
-    if (!ctx || !sizes) return FBS_E_INVALID;
-    if (t_p == 0) {
-        if (!ctx->have_pack) return set_error(ctx, FBS_E_STATE, "the context has no packing key");
-        t_p = ctx->pack_t;
-    }
-    if (t_p > 31) return set_error(ctx, FBS_E_INVALID, "packing key needs 1 <= t_p <= 31");
-    sizes[0] = (size_t)ctx->p.n * t_p * ctx->N;
-    sizes[1] = sizes[0] * (ctx->p.k + 1);
-    return FBS_OK;
+    return gadget_key_sizes(ctx, GK_PACK, t_p, sizes);
 } FBS_API_CATCH(ctx)
 
 int fbs_export_packing_key(const fbs_ctx *ctx, uint64_t *bodies, uint64_t *full) try {
-    if (!ctx) return FBS_E_INVALID;
-    if (!ctx->have_pack) return set_error(ctx, FBS_E_STATE, "the context has no packing key");
-    if (bodies) std::memcpy(bodies, ctx->pack_bodies.data(), ctx->pack_bodies.size() * 8);
-    if (full) {
-        std::vector<uint64_t> key;
-        host_expand_packing_key(ctx, ctx->mask_key, ctx->pack_t, ctx->pack_bodies.data(), key);
-        std::memcpy(full, key.data(), key.size() * 8);
-    }
-    return FBS_OK;
+    return gadget_key_export(ctx, GK_PACK, bodies, full);
 } FBS_API_CATCH(ctx)
 
 int fbs_packed_words(const fbs_ctx *ctx, size_t count, uint32_t bits, size_t *words) try {

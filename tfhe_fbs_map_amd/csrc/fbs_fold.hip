@@ -123,7 +123,7 @@ int dev_fold(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe
     const size_t samples = (count + N - 1) / N;
     PackArgs a{};
     a.fields = ctx->d_pack_fields;
-    a.key = ctx->d_fold_key;
+    a.key = ctx->gadget_dev[GK_FOLD].d_key;
     a.acc = ctx->d_pack_acc;
     a.tw_fwd = reinterpret_cast<const double *>(ctx->d_tw_fwd);
     a.tw_inv = reinterpret_cast<const double *>(ctx->d_tw_inv);
@@ -131,8 +131,8 @@ int dev_fold(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe
     a.count = count;
     a.sample_words = (size_t)k1 * N;
     a.n = D;
-    a.t = ctx->fold_t;
-    a.gamma = ctx->fold_gamma;
+    a.t = ctx->gadget[GK_FOLD].t;
+    a.gamma = ctx->gadget[GK_FOLD].gamma;
     a.cols = (uint32_t)(samples * N);
     a.slices = pack_slices_for(ctx, samples, D);
     if (((size_t)D + 2) * a.cols > ctx->pack_fields_capacity || samples * a.slices * k1 * N > ctx->pack_acc_capacity)

@@ -448,15 +448,17 @@ void host_compact_trivial(const fbs_ctx *ctx, uint64_t body, uint32_t bits, uint
 }
 
 // ---------------------------------------------------------------------------------------------
-// Packed outputs (fbs_pack.hpp; include/fbs_exec.h, "packed outputs").  The packing key: n t_p GLWE encryptions under the big key of
-// the constants sk_lwe[i] h_v, masks under the public mask key on streams of their own (DOM_PACK_MASK), noise under the context's
-// key (DOM_PACK_NOISE) -- made only when asked for, so that nothing else a context derives changes.
+// Packed outputs (fbs_pack.hpp; include/fbs_exec.h, "packed outputs") and folded state.  The gadget keys (GadgetKind,
+// fbs_internal.hpp): GLWE encryptions under the big key of the constants src[i] h_v, masks under the public mask key and noise
+// under the context's key, each on streams of the kind's own -- made only when asked for, so that nothing else a context
+// derives changes.
 // ---------------------------------------------------------------------------------------------
-// bodies [src.size()][t][N] of the rows (i, v): a GLWE zero sample on the streams (mask_dom, r), (noise_dom, r), r = i t + v, plus
+// bodies [rows][t][N] of the rows (i, v): a GLWE zero sample on the kind's streams (mask_dom, r), (noise_dom, r), r = i t + v, plus
 // src[i] h_v at X^0 -- the packing key's rows (src = sk_lwe) and the fold key's (src = sk_glwe)
-static void gadget_key_bodies(const fbs_ctx *ctx, const std::vector<uint64_t> &src, Domain mask_dom, Domain noise_dom, uint32_t t,
-                              uint32_t gamma, std::vector<uint64_t> &bodies) {
+void host_gadget_keygen(const fbs_ctx *ctx, GadgetKind kind, uint32_t t, uint32_t gamma, std::vector<uint64_t> &bodies) {
     const uint32_t N = ctx->N, k = ctx->p.k;
+    const GadgetKindInfo &gk = GADGET_KINDS[kind];
+    const std::vector<uint64_t> &src = gadget_secret(*ctx, kind);
     const std::vector<std::vector<uint32_t>> support = glwe_support(ctx);
     bodies.assign(src.size() * t * N, 0);
     parallel_for(src.size() * t, [&](size_t r0, size_t r1) {
@@ -465,43 +467,25 @@ static void gadget_key_bodies(const fbs_ctx *ctx, const std::vector<uint64_t> &s
             const size_t i = r / t;
             const uint32_t v = (uint32_t)(r % t);
             uint64_t *body = bodies.data() + r * N;
-            glwe_zero_sample(ctx->mask_key, stream_id(mask_dom, r), ctx->rkey, stream_id(noise_dom, r), ctx->p.sigma_glwe, ctx->p.sampler,
-                             support, N, a.data(), body);
+            glwe_zero_sample(ctx->mask_key, stream_id(gk.mask_dom, r), ctx->rkey, stream_id(gk.noise_dom, r), ctx->p.sigma_glwe,
+                             ctx->p.sampler, support, N, a.data(), body);
             if (src[i]) body[0] = fq_add(body[0], pack_gadget(gamma, v));
         }
     });
 }
-// (mask key, bodies [rows][N]) -> the whole rows [rows][k+1][N]
-static void expand_gadget_key(const fbs_ctx *ctx, const RandKey &mask_key, Domain mask_dom, size_t rows, const uint64_t *bodies,
-                              std::vector<uint64_t> &full) {
+// (mask key, bodies [rows t][N]) -> the whole rows [rows t][k+1][N]
+void host_expand_gadget_key(const fbs_ctx *ctx, GadgetKind kind, const RandKey &mask_key, uint32_t t, const uint64_t *bodies,
+                            std::vector<uint64_t> &full) {
     const uint32_t N = ctx->N, k = ctx->p.k;
-    const size_t row_words = (size_t)(k + 1) * N;
+    const size_t rows = (size_t)gadget_rows(*ctx, kind) * t, row_words = (size_t)(k + 1) * N;
     full.assign(rows * row_words, 0);
     parallel_for(rows, [&](size_t r0, size_t r1) {
         for (size_t r = r0; r < r1; r++) {
             uint64_t *row = full.data() + r * row_words;
-            mask_words(mask_key, stream_id(mask_dom, r), 0, row, (size_t)k * N);
+            mask_words(mask_key, stream_id(GADGET_KINDS[kind].mask_dom, r), 0, row, (size_t)k * N);
             std::memcpy(row + (size_t)k * N, bodies + r * N, (size_t)N * 8);
         }
     });
-}
-
-void host_packing_keygen(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies) {
-    gadget_key_bodies(ctx, ctx->sk_lwe, DOM_PACK_MASK, DOM_PACK_NOISE, t_p, gamma_p, bodies);
-}
-
-void host_expand_packing_key(const fbs_ctx *ctx, const RandKey &mask_key, uint32_t t_p, const uint64_t *bodies, std::vector<uint64_t> &full) {
-    expand_gadget_key(ctx, mask_key, DOM_PACK_MASK, (size_t)ctx->p.n * t_p, bodies, full);
-}
-
-// Folded state (include/fbs_exec.h, "folded state"): the fold key is the packing key's construction on the D words of the big key
-// itself, on streams of its own (DOM_FOLD_MASK, DOM_FOLD_NOISE) -- made only when asked for
-void host_fold_keygen(const fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, std::vector<uint64_t> &bodies) {
-    gadget_key_bodies(ctx, ctx->sk_glwe, DOM_FOLD_MASK, DOM_FOLD_NOISE, t_f, gamma_f, bodies);
-}
-
-void host_expand_fold_key(const fbs_ctx *ctx, const RandKey &mask_key, uint32_t t_f, const uint64_t *bodies, std::vector<uint64_t> &full) {
-    expand_gadget_key(ctx, mask_key, DOM_FOLD_MASK, (size_t)ctx->D * t_f, bodies, full);
 }
 
 // The decode: phase_j = body_j - sum_c (A_c S_c)_j mod 2^w over the fields of each sample (32-bit wrapping sums are exact mod 2^w),

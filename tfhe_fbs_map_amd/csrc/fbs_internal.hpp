@@ -204,15 +204,27 @@ struct HostState {
     RandKey mask_key{};
     bool seeded_keys = false, eval_only = false;
 
-    // Packed outputs: the packing key's parameters and bodies [n][t_p][N] (the masks come from mask_key)
-    bool have_pack = false;
-    uint32_t pack_t = 0, pack_gamma = 0;
-    std::vector<uint64_t> pack_bodies;
-    // Folded state: the fold key's parameters and bodies [D][t_f][N] (the masks come from mask_key)
-    bool have_fold = false;
-    uint32_t fold_t = 0, fold_gamma = 0;
-    std::vector<uint64_t> fold_bodies;
+    // Packed outputs and folded state: the parameters and bodies [rows][t][N] of each gadget key (the masks come from mask_key)
+    struct GadgetKeyState {
+        bool have = false;
+        uint32_t t = 0, gamma = 0;
+        std::vector<uint64_t> bodies;
+    } gadget[2];   // [GadgetKind]
 };
+
+// The gadget keys: rows x t GLWE encryptions under the big key of the constants src[i] h_v, i < rows, v < t.  Row r = i t + v:
+// masks A_c = fold(words c N .. of stream (mask_dom, r)) under the mask key, body = e + sum_c A_c S_c + src[i] h_v at X^0, e on
+// stream (noise_dom, r) under the context's key.  The packing key (packed outputs, fbs_pack.hpp) is the case src = sk_lwe,
+// rows = n; the fold key (include/fbs_exec.h, "folded state") the case src = sk_glwe (the flattened big key itself), rows = D.
+// What differs between the two is this table, gadget_rows and gadget_secret, and the device secret in dev_gadget_bodies.
+enum GadgetKind { GK_PACK = 0, GK_FOLD = 1 };
+struct GadgetKindInfo {
+    const char *noun, *letter;   // what the entries and their messages call the key and its parameters (t_p, gamma_f)
+    Domain mask_dom, noise_dom;
+};
+constexpr GadgetKindInfo GADGET_KINDS[2] = {{"packing", "p", DOM_PACK_MASK, DOM_PACK_NOISE}, {"fold", "f", DOM_FOLD_MASK, DOM_FOLD_NOISE}};
+inline uint32_t gadget_rows(const HostState &c, GadgetKind kind) { return kind == GK_PACK ? c.p.n : c.D; }
+inline const std::vector<uint64_t> &gadget_secret(const HostState &c, GadgetKind kind) { return kind == GK_PACK ? c.sk_lwe : c.sk_glwe; }
 
 }  // namespace fbs
 
@@ -256,23 +268,21 @@ struct fbs_ctx : fbs::HostState {
     int64_t bsk_upload_bytes = 0;        // bootstrapping-key bytes the last key-making call copied host -> device (fbs_ctx_stat)
     uint64_t *d_compact = nullptr;   // scratch: packed compact ciphertexts of fbs_eval_seeded_compact's output groups
     size_t compact_capacity = 0;     // in words (also the staging of compact inputs, fbs_eval_sources)
-    // Packed outputs (fbs_pack.hip): the packing key (parameters and bodies: HostState) in the transform domain
-    // [n][t_p][k+1][N] (centred doubles, x N^-1, key_word order), and the packing scratch: the rounded
-    // mask fields and the raw body fields of a pass transposed to [n+1][samples N], partial accumulators [samples][slices][k+1][N]
-    double *d_pack_key = nullptr;
-    size_t pack_key_capacity = 0;    // in words
+    // Packed outputs (fbs_pack.hip) and folded state (fbs_fold.hip), per gadget key (parameters and bodies: HostState): the key in
+    // the transform domain [rows][t][k+1][N] (centred doubles, x N^-1, key_word order), and the staging of the entry that hands
+    // its result to the host (fbs_state_fetch_packed's words, fbs_state_fold's samples)
+    struct GadgetKeyDev {
+        double *d_key = nullptr;
+        size_t capacity = 0;           // in words
+        uint64_t *d_out = nullptr;
+        size_t out_capacity = 0;       // in words
+    } gadget_dev[2];   // [GadgetKind]
+    // The scratch both share: the rounded mask fields and the raw body fields of a pass transposed to [n+1][samples N] (folding:
+    // [D][samples N], then the 64-bit body words), partial accumulators [samples][slices][k+1][N]
     uint32_t *d_pack_fields = nullptr;
     size_t pack_fields_capacity = 0; // in words
     double *d_pack_acc = nullptr;
     size_t pack_acc_capacity = 0;    // in words
-    uint64_t *d_packed = nullptr;    // staging of fbs_state_fetch_packed's words
-    size_t packed_capacity = 0;      // in words
-    // Folded state (fbs_fold.hip): the fold key [D][t_f][k+1][N] in the form of the packing key; its scratch is the packing
-    // scratch (rounded mask fields [D][samples N], then the raw body words; the same partial accumulators)
-    double *d_fold_key = nullptr;
-    size_t fold_key_capacity = 0;    // in words
-    uint64_t *d_folded = nullptr;    // staging of fbs_state_fold's samples
-    size_t folded_capacity = 0;      // in words
     uint64_t *d_pub = nullptr;       // staging of fbs_state_put_public's GLWE samples
     size_t pub_capacity = 0;         // in words
     fbs_tvset *tv_identity = nullptr;   // the identity table [0, 1, .., p - 1], made on first use: what refreshes a compact input
@@ -445,16 +455,11 @@ void host_expand_seeded_keys(const fbs_ctx *ctx, const RandKey &mask_key, const 
 void host_encrypt_seeded(const fbs_ctx *ctx, const int64_t *msgs, size_t count, uint64_t nonce0, uint64_t *bodies);
 // bodies[count] -> cts [count][D+1]: the mask of stream nonce0 + i under ctx->mask_key, then the body
 void host_expand_seeded(const fbs_ctx *ctx, const uint64_t *bodies, size_t count, uint64_t nonce0, uint64_t *cts);
-// Packed outputs (fbs_pack.hpp).  Row r = i t_p + v of the packing key: masks A_c = fold(words c N .. of stream (DOM_PACK_MASK, r))
-// under the mask key, body = e + sum_c A_c S_c + sk_lwe[i] h_v at X^0, e on stream (DOM_PACK_NOISE, r) under the context's key.
-// host_packing_keygen -> bodies [n][t_p][N]; host_expand_packing_key: (mask key, bodies) -> the whole key [n][t_p][k+1][N]
-void host_packing_keygen(const fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies);
-void host_expand_packing_key(const fbs_ctx *ctx, const RandKey &mask_key, uint32_t t_p, const uint64_t *bodies, std::vector<uint64_t> &full);
-// Folded state (include/fbs_exec.h, "folded state").  Row r = i t_f + v of the fold key, i < D: the packing key's row with
-// sk_glwe[i] (word i of the flattened big key) for sk_lwe[i] and the streams (DOM_FOLD_MASK, r), (DOM_FOLD_NOISE, r).
-// host_fold_keygen -> bodies [D][t_f][N]; host_expand_fold_key: (mask key, bodies) -> the whole key [D][t_f][k+1][N]
-void host_fold_keygen(const fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, std::vector<uint64_t> &bodies);
-void host_expand_fold_key(const fbs_ctx *ctx, const RandKey &mask_key, uint32_t t_f, const uint64_t *bodies, std::vector<uint64_t> &full);
+// The gadget keys (GadgetKind, above).  host_gadget_keygen -> bodies [rows][t][N]; host_expand_gadget_key: (mask key, bodies) ->
+// the whole key [rows][t][k+1][N]
+void host_gadget_keygen(const fbs_ctx *ctx, GadgetKind kind, uint32_t t, uint32_t gamma, std::vector<uint64_t> &bodies);
+void host_expand_gadget_key(const fbs_ctx *ctx, GadgetKind kind, const RandKey &mask_key, uint32_t t, const uint64_t *bodies,
+                            std::vector<uint64_t> &full);
 // packed words of `count` outputs at width `bits` -> msgs[count] under sk_glwe
 void host_decrypt_packed(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs);
 int host_build_tv(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint64_t *tv, uint64_t *post_add);
@@ -483,11 +488,10 @@ int dev_transform_bsk(fbs_ctx *ctx, const uint64_t *d_src);
 // Keys on the device (fbs_keygen.hip; knob "keys_on_device"), word for word the host functions.  dev_make_keys: after the secrets
 // and the tables are on the device, both evaluation keys made there (seeded: host_keygen_seeded under `mask_key`, else host_keygen)
 // or, bsk_bodies / ksk_bodies (host arrays) non-null, expanded there (host_expand_seeded_keys under `mask_key`; no secret); the
-// bootstrapping key transformed from the device rows, and ctx->bsk / ctx->ksk filled from them.  dev_packing_bodies:
-// host_packing_keygen's bodies [n][t_p][N]; dev_fold_bodies: host_fold_keygen's bodies [D][t_f][N]
+// bootstrapping key transformed from the device rows, and ctx->bsk / ctx->ksk filled from them.  dev_gadget_bodies:
+// host_gadget_keygen's bodies [rows][t][N]
 int dev_make_keys(fbs_ctx *ctx, bool seeded, const RandKey &mask_key, const uint64_t *bsk_bodies, const uint64_t *ksk_bodies);
-int dev_packing_bodies(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies);
-int dev_fold_bodies(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, std::vector<uint64_t> &bodies);
+int dev_gadget_bodies(fbs_ctx *ctx, GadgetKind kind, uint32_t t, uint32_t gamma, std::vector<uint64_t> &bodies);
 int dev_keyswitch_gemm_setup(fbs_ctx *ctx);   // limb fragments of the key-switching key for the int8 MFMA key switch
 // the key switch kN -> n and the rounding of every word to Z_(2^log2_mod) (log2(2N): what the blind rotation reads; up to 31: the
 // fields of compact outputs), into d_ms [gv.ks_count][n + 1]
@@ -537,13 +541,12 @@ int dev_decrypt_compact(const fbs_ctx *ctx, const uint64_t *d_words, size_t coun
 // (re-rounded as the modulus switch rounds when bits > log2(2N))
 int dev_compact_unpack(const fbs_ctx *ctx, const uint64_t *d_words, size_t count, uint32_t bits, uint32_t *d_ms, hipStream_t stream);
 
-// packed outputs (fbs_pack.hip).  dev_upload_packing_key: the whole key in the coefficient domain -> d_pack_key (transformed on
-// the device; blocks); dev_upload_fold_key: the same for the fold key [D][t_f][k+1][N] -> d_fold_key.  pack_slices_for: slices
+// packed outputs (fbs_pack.hip).  dev_upload_gadget_key: the whole key of `kind` in the coefficient domain -> its d_key
+// (transformed on the device; blocks).  pack_slices_for: slices
 // per sample of a launch of `samples` samples whose sum runs over `rows` key rows (n for packing, D for folding).  dev_pack: the
 // switched 31-bit fields d_ms [count][n + 1] of ciphertexts that start a packed sample -> packed words at width `bits`; uses
 // d_pack_fields ((n + 1) * samples * N words) and d_pack_acc (samples * slices * (k + 1) * N words), which the caller has sized
-int dev_upload_packing_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_p);
-int dev_upload_fold_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_f);
+int dev_upload_gadget_key(fbs_ctx *ctx, GadgetKind kind, const std::vector<uint64_t> &full, uint32_t t);
 uint32_t pack_slices_for(const fbs_ctx *ctx, size_t samples, uint32_t rows);
 int dev_pack(fbs_ctx *ctx, const uint32_t *d_ms, size_t count, uint32_t bits, uint64_t *d_words, hipStream_t stream);
 // k_pack_accumulate alone, on the fields, key and row count of `a` (fbs_pack.hpp): samples * a.slices workgroups

@@ -1,5 +1,5 @@
 // The evaluation keys made and expanded on the device (knob "keys_on_device", include/fbs_exec.h), gfx950: word for word what
-// host_keygen, host_keygen_seeded, host_expand_seeded_keys and host_packing_keygen (fbs_host.cpp) write -- the same ChaCha20
+// host_keygen, host_keygen_seeded, host_expand_seeded_keys and host_gadget_keygen (fbs_host.cpp) write -- the same ChaCha20
 // streams (fbs_chacha.hpp), the same folds, the same sampler (fbs_sampler.hpp), and the negacyclic product by the secret as an
 // exact product of transforms (k_polymul's arithmetic: every value a residue, so the words do not depend on how it is computed).
 //
@@ -27,7 +27,7 @@ namespace fbs {
 enum KeyRowsMode : uint32_t {
     ROWS_FULL = 0,     // host_keygen: all k + 1 columns; bit g_lv on coefficient 0 of column comp
     ROWS_SEEDED = 1,   // host_keygen_seeded: all k + 1 columns; the message in the body whatever the component
-    ROWS_PACK = 2,     // host_packing_keygen: the body alone; sk_lwe[i] h_v on coefficient 0
+    ROWS_PACK = 2,     // host_gadget_keygen: the body alone; sk_lwe[i] h_v on coefficient 0
     ROWS_EXPAND = 3    // host_expand_seeded_keys: the mask columns, then the given body; no secret
 };
 
@@ -319,11 +319,10 @@ int dev_make_keys(fbs_ctx *ctx, bool seeded, const RandKey &mask_key, const uint
     return FBS_OK;
 }
 
-// bodies [src_rows][t][N] of gadget_key_bodies (fbs_host.cpp): ROWS_PACK rows whose bit is bit i of `d_src_bits`
-static int dev_gadget_bodies(fbs_ctx *ctx, size_t src_rows, const uint32_t *d_src_bits, Domain mask_dom, Domain noise_dom, uint32_t t,
-                             uint32_t gamma, std::vector<uint64_t> &bodies) {
+// bodies [rows][t][N] of host_gadget_keygen (fbs_host.cpp): ROWS_PACK rows whose bit is bit i of the kind's secret on the device
+int dev_gadget_bodies(fbs_ctx *ctx, GadgetKind kind, uint32_t t, uint32_t gamma, std::vector<uint64_t> &bodies) {
     const uint32_t N = ctx->N, k = ctx->p.k;
-    const size_t n_rows = src_rows * t;
+    const size_t n_rows = (size_t)gadget_rows(*ctx, kind) * t;
     if (!ctx->d_tw_fwd || !ctx->d_sk_bits) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
     bodies.assign(n_rows * N, 0);
     if (!n_rows) return FBS_OK;
@@ -336,11 +335,12 @@ static int dev_gadget_bodies(fbs_ctx *ctx, size_t src_rows, const uint32_t *d_sr
     ga.tw_fwd = reinterpret_cast<const double *>(ctx->d_tw_fwd);
     ga.tw_inv = reinterpret_cast<const double *>(ctx->d_tw_inv);
     ga.sk_glwe_bits = ctx->d_sk_bits;
-    ga.sk_lwe_bits = d_src_bits;   // (ROWS_PACK reads the bit of "sample" i here: the small key's, or for the fold key the big key's)
+    // (ROWS_PACK reads the bit of "sample" i here: the small key's, or for the fold key the big key's)
+    ga.sk_lwe_bits = kind == GK_PACK ? ctx->d_sk_lwe_bits : ctx->d_sk_bits;
     ga.mask_key = ctx->mask_key;
     ga.noise_key = ctx->rkey;
-    ga.mask_dom = mask_dom;
-    ga.noise_dom = noise_dom;
+    ga.mask_dom = GADGET_KINDS[kind].mask_dom;
+    ga.noise_dom = GADGET_KINDS[kind].noise_dom;
     ga.n_rows = n_rows;
     ga.mode = ROWS_PACK;
     ga.k = k;
@@ -356,14 +356,6 @@ static int dev_gadget_bodies(fbs_ctx *ctx, size_t src_rows, const uint32_t *d_sr
     if (wiped != FBS_OK) return wiped;
     FBS_HIP(ctx, hipMemcpy(bodies.data(), d_bodies.p, bodies.size() * 8, hipMemcpyDeviceToHost));
     return FBS_OK;
-}
-
-int dev_packing_bodies(fbs_ctx *ctx, uint32_t t_p, uint32_t gamma_p, std::vector<uint64_t> &bodies) {
-    return dev_gadget_bodies(ctx, ctx->p.n, ctx->d_sk_lwe_bits, DOM_PACK_MASK, DOM_PACK_NOISE, t_p, gamma_p, bodies);
-}
-
-int dev_fold_bodies(fbs_ctx *ctx, uint32_t t_f, uint32_t gamma_f, std::vector<uint64_t> &bodies) {
-    return dev_gadget_bodies(ctx, ctx->D, ctx->d_sk_bits, DOM_FOLD_MASK, DOM_FOLD_NOISE, t_f, gamma_f, bodies);
 }
 
 }  // namespace fbs

@@ -180,12 +180,13 @@ uint32_t pack_slices_for(const fbs_ctx *ctx, size_t samples, uint32_t rows) {
     return (uint32_t)std::min<size_t>(cap, std::max<size_t>(1, room / std::max<size_t>(1, samples)));
 }
 
-// a key of `src_rows` x `t` GLWE rows (the packing key: n rows of the small key; the fold key: D words of the big key), whole
-// and in the coefficient domain, -> `d_key` in the transform domain
-static int upload_gadget_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t src_rows, uint32_t t, double *&d_key,
-                             size_t &key_capacity) {
+// a key of rows x `t` GLWE rows (the packing key: n rows of the small key; the fold key: D words of the big key), whole
+// and in the coefficient domain, -> the kind's d_key in the transform domain
+int dev_upload_gadget_key(fbs_ctx *ctx, GadgetKind kind, const std::vector<uint64_t> &full, uint32_t t) {
     const uint32_t N = ctx->N, k1 = ctx->p.k + 1;
-    const size_t polys = (size_t)src_rows * t * k1, words = polys * N;
+    const size_t polys = (size_t)gadget_rows(*ctx, kind) * t * k1, words = polys * N;
+    double *&d_key = ctx->gadget_dev[kind].d_key;
+    size_t &key_capacity = ctx->gadget_dev[kind].capacity;
     if (full.size() != words) return set_error(ctx, FBS_E_INVALID, "packing key of the wrong size");
     if (!ctx->d_tw_fwd) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
     if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));   // kernels may still read the old key
@@ -223,13 +224,6 @@ static int upload_gadget_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, ui
     return FBS_OK;
 }
 
-int dev_upload_packing_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_p) {
-    return upload_gadget_key(ctx, full, ctx->p.n, t_p, ctx->d_pack_key, ctx->pack_key_capacity);
-}
-int dev_upload_fold_key(fbs_ctx *ctx, const std::vector<uint64_t> &full, uint32_t t_f) {
-    return upload_gadget_key(ctx, full, ctx->D, t_f, ctx->d_fold_key, ctx->fold_key_capacity);
-}
-
 // k_pack_accumulate on the fields, key and row count of `a` (a.n = n: packing; a.n = D: folding): samples * a.slices workgroups
 int dev_pack_accumulate(const fbs_ctx *ctx, const PackArgs &a, size_t samples, hipStream_t stream) {
     const uint32_t k1 = ctx->p.k + 1;
@@ -253,7 +247,7 @@ int dev_pack(fbs_ctx *ctx, const uint32_t *d_ms, size_t count, uint32_t bits, ui
     const size_t samples = (count + N - 1) / N;
     PackArgs a{};
     a.fields = ctx->d_pack_fields;
-    a.key = ctx->d_pack_key;
+    a.key = ctx->gadget_dev[GK_PACK].d_key;
     a.acc = ctx->d_pack_acc;
     a.tw_fwd = reinterpret_cast<const double *>(ctx->d_tw_fwd);
     a.tw_inv = reinterpret_cast<const double *>(ctx->d_tw_inv);
@@ -261,8 +255,8 @@ int dev_pack(fbs_ctx *ctx, const uint32_t *d_ms, size_t count, uint32_t bits, ui
     a.count = count;
     a.sample_words = packed_sample_words(ctx->p.k, N, N, bits);
     a.n = n;
-    a.t = ctx->pack_t;
-    a.gamma = ctx->pack_gamma;
+    a.t = ctx->gadget[GK_PACK].t;
+    a.gamma = ctx->gadget[GK_PACK].gamma;
     a.cols = (uint32_t)(samples * N);
     a.slices = pack_slices_for(ctx, samples, n);
     a.bits = bits;

@@ -19,10 +19,11 @@ namespace fbs {
 
 static_assert(FQ == (1ull << 46) - 507903, "pack_lift_body is written for this q");
 
-// null, or why (t_p, gamma_p) is no packing key: 1 <= gamma_p, 1 <= t_p, t_p gamma_p <= 31
-inline const char *packing_params_refused(uint32_t t_p, uint32_t gamma_p) {
-    if (t_p < 1 || gamma_p < 1) return "packing key needs t_p >= 1 and gamma_p >= 1";
-    if (t_p > 31 || gamma_p > 31 || t_p * gamma_p > 31) return "packing key needs t_p * gamma_p <= 31";
+// null, or what (t, gamma) lacks to be a gadget key's parameters (a packing key's, a fold key's): 1 <= gamma, 1 <= t, t gamma <= 31;
+// '#' stands for the letter of the key's parameters (check_gadget_params, fbs_api_checks.hpp)
+inline const char *gadget_params_refused(uint32_t t, uint32_t gamma) {
+    if (t < 1 || gamma < 1) return "t_# >= 1 and gamma_# >= 1";
+    if (t > 31 || gamma > 31 || t * gamma > 31) return "t_# * gamma_# <= 31";
     return nullptr;
 }
 

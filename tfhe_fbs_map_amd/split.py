@@ -191,27 +191,22 @@ class ServerKey:
         for a, w, name in zip((self.bsk_bodies, self.ksk_bodies), want, ("bsk_bodies", "ksk_bodies")):
             if a.size != w:
                 raise ValueError(f"{name} has {a.size} words, the parameter set needs {w}")
-        if self.packing_bodies is None:
-            self.packing_levels = self.packing_base_bits = 0
-        else:
-            t, g = int(self.packing_levels), int(self.packing_base_bits)
-            self.packing_levels, self.packing_base_bits = t, g
-            self.packing_bodies = np.ascontiguousarray(self.packing_bodies, np.uint64).reshape(-1)
+        self._gadget_key("packing", self.params.n)
+        self._gadget_key("fold", self.params.k * self.params.N)
+
+    def _gadget_key(self, noun, rows):
+        """normalises and checks the optional `noun` key: `noun`_bodies [rows][t][N], `noun`_levels t, `noun`_base_bits gamma"""
+        bodies, t, g = getattr(self, noun + "_bodies"), 0, 0
+        if bodies is not None:
+            t, g = int(getattr(self, noun + "_levels")), int(getattr(self, noun + "_base_bits"))
+            bodies, want = np.ascontiguousarray(bodies, np.uint64).reshape(-1), rows * t * self.params.N
             if t < 1 or g < 1 or t * g > 31:
-                raise ValueError(f"a packing key of {t} levels of {g} bits")
-            if self.packing_bodies.size != self.params.n * t * self.params.N:
-                raise ValueError(f"packing_bodies has {self.packing_bodies.size} words, the parameter set needs {self.params.n * t * self.params.N}")
-        if self.fold_bodies is None:
-            self.fold_levels = self.fold_base_bits = 0
-        else:
-            t, g = int(self.fold_levels), int(self.fold_base_bits)
-            self.fold_levels, self.fold_base_bits = t, g
-            self.fold_bodies = np.ascontiguousarray(self.fold_bodies, np.uint64).reshape(-1)
-            want = self.params.k * self.params.N * t * self.params.N
-            if t < 1 or g < 1 or t * g > 31:
-                raise ValueError(f"a fold key of {t} levels of {g} bits")
-            if self.fold_bodies.size != want:
-                raise ValueError(f"fold_bodies has {self.fold_bodies.size} words, the parameter set needs {want}")
+                raise ValueError(f"a {noun} key of {t} levels of {g} bits")
+            if bodies.size != want:
+                raise ValueError(f"{noun}_bodies has {bodies.size} words, the parameter set needs {want}")
+        setattr(self, noun + "_bodies", bodies)
+        setattr(self, noun + "_levels", t)
+        setattr(self, noun + "_base_bits", g)
 
     @property
     def fingerprint(self) -> bytes:
@@ -222,7 +217,7 @@ class ServerKey:
         np.savez(path, kind=np.array("server_key"), format_version=np.array(FORMAT_VERSION),
                  params=np.array([int(prm[f]) for f in _PARAM_FIELDS], np.int64), fuse_tables=np.array(bool(self.fuse_tables)),
                  mask_key=np.frombuffer(self.mask_key, np.uint8), fingerprint=np.frombuffer(self.fingerprint, np.uint8),
-                 bsk_bodies=self.bsk_bodies, ksk_bodies=self.ksk_bodies, **self._packing_fields(), **self._fold_fields(),
+                 bsk_bodies=self.bsk_bodies, ksk_bodies=self.ksk_bodies, **self._gadget_fields("packing"), **self._gadget_fields("fold"),
                  **self._sampler_field())
 
     def _sampler_field(self):
@@ -231,19 +226,13 @@ class ServerKey:
         sampler = int(getattr(self.params, "sampler", 0))
         return dict(sampler=np.array(sampler, np.int64)) if sampler else {}
 
-    def _packing_fields(self):
-        """the optional packing key of a saved server key (a key without one is written exactly as before)"""
-        if self.packing_bodies is None:
+    def _gadget_fields(self, prefix):
+        """the optional packing or fold key of a saved server key (a key without one is written exactly as before)"""
+        bodies = getattr(self, prefix + "_bodies")
+        if bodies is None:
             return {}
-        return dict(packing_bodies=self.packing_bodies, packing_levels=np.array(self.packing_levels, np.int64),
-                    packing_base_bits=np.array(self.packing_base_bits, np.int64))
-
-    def _fold_fields(self):
-        """the optional fold key of a saved server key (a key without one is written exactly as before)"""
-        if self.fold_bodies is None:
-            return {}
-        return dict(fold_bodies=self.fold_bodies, fold_levels=np.array(self.fold_levels, np.int64),
-                    fold_base_bits=np.array(self.fold_base_bits, np.int64))
+        return {prefix + "_bodies": bodies, prefix + "_levels": np.array(getattr(self, prefix + "_levels"), np.int64),
+                prefix + "_base_bits": np.array(getattr(self, prefix + "_base_bits"), np.int64)}
 
     @property
     def fold_factor(self):
@@ -261,20 +250,23 @@ class ServerKey:
         prm = Params(sampler=int(d["sampler"]) if "sampler" in d else 0, **{f: int(v) for f, v in zip(_PARAM_FIELDS, vals)})
         if d["bsk_bodies"].dtype != np.uint64 or d["ksk_bodies"].dtype != np.uint64:
             raise ValueError("key bodies are uint64 words")
-        packing = {}
-        if "packing_bodies" in d:
-            if d["packing_bodies"].dtype != np.uint64:
-                raise ValueError("key bodies are uint64 words")
-            packing = dict(packing_bodies=d["packing_bodies"], packing_levels=int(d["packing_levels"]),
-                           packing_base_bits=int(d["packing_base_bits"]))
-        if "fold_bodies" in d:
-            if d["fold_bodies"].dtype != np.uint64:
-                raise ValueError("key bodies are uint64 words")
-            packing.update(fold_bodies=d["fold_bodies"], fold_levels=int(d["fold_levels"]), fold_base_bits=int(d["fold_base_bits"]))
-        key = cls(prm, bool(d["fuse_tables"]), np.asarray(d["mask_key"], np.uint8).tobytes(), d["bsk_bodies"], d["ksk_bodies"], **packing)
+        gadget = {}
+        for prefix in ("packing", "fold"):
+            gadget.update(cls._gadget_loaded(d, prefix))
+        key = cls(prm, bool(d["fuse_tables"]), np.asarray(d["mask_key"], np.uint8).tobytes(), d["bsk_bodies"], d["ksk_bodies"], **gadget)
         if _fingerprint_of(d) != key.fingerprint:
             raise ValueError("the saved fingerprint is not the mask key's")
         return key
+
+    @staticmethod
+    def _gadget_loaded(d, prefix):
+        """the fields of `_gadget_fields(prefix)` as constructor arguments ({}: the file has no such key)"""
+        if prefix + "_bodies" not in d:
+            return {}
+        if d[prefix + "_bodies"].dtype != np.uint64:
+            raise ValueError("key bodies are uint64 words")
+        return {prefix + "_bodies": d[prefix + "_bodies"], prefix + "_levels": int(d[prefix + "_levels"]),
+                prefix + "_base_bits": int(d[prefix + "_base_bits"])}
 
 
 @dataclass
@@ -736,21 +728,18 @@ class Client:
             from ._native import Context
             self.ctx = Context(self.params, seed=cfg.key_seed(), device=cfg.device, keygen=False, device_keys=cfg.device_keys)
         self.ctx.keygen_seeded()
-        self.packing = None
-        if packing:
-            from .params import packing_choice
-            everything = [env] + [e for e in programs if e is not env]
+        self.packing = self.folding = None
+        if packing or folding:
+            from .params import fold_choice, packing_choice
             p = self.params.p_msg
-            norm2 = min((e.fusion_stats(p) if self.fuse_tables else e.stats())["norm2_linprod"] for e in everything)
-            worst = max(output_noise_factor(e.lower(), p, self.fuse_tables) for e in everything)
-            self.packing = packing_choice(self.params, norm2, max(worst, 1.0))
-            self.ctx.packing_keygen(*self.packing[:2])
-        self.folding = None
-        if folding:
-            from .params import fold_choice
             everything = [env] + [e for e in programs if e is not env]
-            norm2 = max((e.fusion_stats(self.params.p_msg) if self.fuse_tables else e.stats())["norm2_linprod"] for e in everything)
-            self.folding = fold_choice(self.params, norm2, float(getattr(cfg, "min_margin", 6.0)))
+            norm2 = [(e.fusion_stats(p) if self.fuse_tables else e.stats())["norm2_linprod"] for e in everything]
+        if packing:
+            worst = max(output_noise_factor(e.lower(), p, self.fuse_tables) for e in everything)
+            self.packing = packing_choice(self.params, min(norm2), max(worst, 1.0))
+            self.ctx.packing_keygen(*self.packing[:2])
+        if folding:
+            self.folding = fold_choice(self.params, max(norm2), float(getattr(cfg, "min_margin", 6.0)))
             self.ctx.fold_keygen(*self.folding)
         self._server_key = None
         self._public_key = None
