@@ -717,6 +717,70 @@ int fbs_state_fold_dev(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t ro
  * copy, no staging; being device memory, the words cannot be checked.  Queued on the context's stream; needs no key. */
 int fbs_state_unfold_dev(fbs_ctx *ctx, fbs_state *st, size_t row0, size_t rows, const uint64_t *d_glwe);
 
+/* ---- encrypted-index reads: rotate a folded table by an encrypted index -------------------------------------------------------------
+ * A folded sample is a full-precision GLWE sample under the big key, the key the blind rotation works under, and its words are
+ * canonical residues like a test polynomial's: it can BE the accumulator of a blind rotation.  Started from
+ * (X^-b~ A_0, .., X^-b~ B) instead of the trivial (0, .., 0, X^-b~ TV), the rotation turns an encrypted table by an encrypted
+ * amount, and sample extraction returns the entry.  libfbsexec.so only.
+ *
+ * BOX MAP, the box rule of the test polynomials: for coefficient j < N, slot(j) = floor((2 p j + N) / (2 N)).  slot(j) < p:
+ * coefficient j carries entry slot(j).  slot(j) == p, the top half box: coefficient j carries MINUS entry 0 -- the half box below
+ * X^N wraps negacyclically.
+ *
+ * TABLE: one GLWE sample, [k+1][N] canonical residues, the layout fbs_fold_dev writes; coefficient j of its phase is the phase of
+ * the ciphertext the box map puts there.
+ *
+ * MAPPED FOLD.  map[j], j < count, names the source of fold position j: the low 31 bits an index into d_cts; bit 31
+ * (FBS_MAP_NEG) set: the ciphertext is negated before anything else, every word, masks and body, x -> (q - x) mod q;
+ * FBS_MAP_NONE: no ciphertext, zero words, as for positions past the fill.  The result is WORD FOR WORD fbs_fold_dev of the
+ * materialised array: rounding, digits, slicing and passes are the fold's own.
+ *
+ * LOOKUP.  Input: an index ciphertext under the big key, and a table.
+ *   1. key switch and modulus switch exactly as fbs_bootstrap_batch_dev runs them: (a~_1 .. a~_n, b~) in [0, 2N);
+ *   2. the blind rotation, its initial accumulator component c = X^-b~ (polynomial c of the table), centred;
+ *   3. sample extraction of coefficient 0; no constant is added.
+ * With r = b~ - sum a~_i s_i mod 2N the output's phase is coefficient r of the table's for r < N and minus coefficient r - N for
+ * r >= N.  An index of message x < p therefore reads entry x; an index with its padding bit set reads the NEGATED entry
+ * (documented, not refused); the same holds for any table of at most p entries laid out by the box map.
+ *
+ * NOISE.  Rotating by a monomial adds nothing: the output's variance is v_br (table_out_norm2 + fold_factor + 1)
+ * (params.lookup_output_norm2); the index is read like any refreshed full link (params.lookup_index_margin).
+ *
+ * Every entry writes nothing when it fails. */
+#define FBS_MAP_NONE 0xFFFFFFFFu
+#define FBS_MAP_NEG 0x80000000u
+/* The box map of a table of `len` <= p entries, host side and pure: map_out[j], j < N, = base + slot(j) stride for slot(j) < len,
+ * FBS_MAP_NONE for len <= slot(j) < p, and base | FBS_MAP_NEG for slot(j) == p (minus entry 0).  FBS_E_INVALID for p < 2, N not a
+ * power of two in [2, 2^16], len == 0, len > p, or a source index that does not fit 31 bits. */
+int fbs_lookup_map(uint32_t p, uint32_t N, uint32_t len, uint32_t base, uint32_t stride, uint32_t *map_out);
+/* d_cts [n_src][D+1] and d_map [count] (device) -> d_glwe [fbs_pub_words(count)] (device, 16-byte aligned: FBS_E_INVALID
+ * otherwise), asynchronous on `stream`, in the passes and on the scratch of fbs_fold_dev.  The map is device memory the host cannot
+ * check: an index >= n_src that is not FBS_MAP_NONE reads source 0, never past the array.  n_src in [1, 2^31); needs no secret;
+ * FBS_E_STATE without a fold key. */
+int fbs_fold_mapped_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t n_src, const uint32_t *d_map, size_t count, uint64_t *d_glwe, void *stream);
+/* d_tables [n_tables][k+1][N] (device, 16-byte aligned), d_cts_index [count][D+1] -> d_cts_out [count][D+1], the LOOKUP above,
+ * asynchronous on `stream`.  d_table_of [count] (device) names each index's table, an id >= n_tables reading table 0; NULL: index i
+ * reads table i.  Needs neither a secret nor a fold key. */
+int fbs_lookup_dev(fbs_ctx *ctx, const uint64_t *d_tables, uint32_t n_tables, const uint32_t *d_table_of, const uint64_t *d_cts_index,
+                   size_t count, uint64_t *d_cts_out, void *stream);
+/* The same with the indices as compact ciphertexts d_words [count][W] at width `bits`: fbs_refresh_compact_dev with the table in
+ * place of the identity polynomial, in that entry's passes and with its unpack.  At bits = log2(2N) the fields ARE the rotation
+ * amounts. */
+int fbs_lookup_compact_dev(fbs_ctx *ctx, const uint64_t *d_tables, uint32_t n_tables, const uint32_t *d_table_of, const uint64_t *d_words,
+                           size_t count, uint32_t bits, uint64_t *d_cts_out, void *stream);
+/* Resident state read by an encrypted index.  For every sample s < T of the index state and every plane m < n_planes, row
+ * out_row0 + m of out_state at sample s is the entry, chosen by row `index_row` of index_state at sample s, of plane m's table.
+ * axis = 0 (rows): plane m's entries are rows rows[m len .. m len + len) of table_state at sample s -- or, where table_state has
+ * T = 1, at sample 0 for every s: one shared table per plane, folded once.  axis = 1 (samples): plane m's entries are samples
+ * 0 .. len - 1 of row rows[m], shared by every query; len is table_state's T.  1 <= len <= p.  The box maps are made on the host and
+ * uploaded once per call; the tables (T n_planes of them, n_planes where shared) are one mapped fold into a scratch of their own,
+ * (k+1) N words a table, which grows like the others; the rotation is one launch sequence in which the planes of an index share its
+ * key switch and modulus switch.  out_state has the index state's T and is neither of the other two.  Queued on the context's
+ * stream like the other state entries; FBS_E_STATE without a fold key; needs no secret.
+ * fbs_ctx_stat: "lookup_tables" (tables the last call folded), "lookup_scratch_words" (words of the table scratch). */
+int fbs_state_lookup(fbs_ctx *ctx, const fbs_state *table_state, const uint32_t *rows, uint32_t n_planes, uint32_t len, uint32_t axis,
+                     const fbs_state *index_state, size_t index_row, fbs_state *out_state, size_t out_row0);
+
 /* ---- a loaded program, one level at a time (multi-GPU hosts) -----------------
  * The two independent axes of the reference's eval loop (fbs_exec_env.py:211-223) are the gates
  * of a bootstrap level and the samples.  A host that shards the GATES of a level over several

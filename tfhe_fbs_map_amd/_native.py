@@ -139,6 +139,11 @@ def _load():
         "fbs_state_fold_dev": (i32, [vp, vp, sz, sz, vp]),
         "fbs_state_unfold_dev": (i32, [vp, vp, sz, sz, vp]),
         "fbs_debug_fold_front_dev": (i32, [vp, vp, sz, u32, u32, vp, vp]),
+        "fbs_lookup_map": (i32, [u32, u32, u32, u32, u32, vp]),
+        "fbs_fold_mapped_dev": (i32, [vp, vp, sz, vp, sz, vp, vp]),
+        "fbs_lookup_dev": (i32, [vp, vp, u32, vp, vp, sz, vp, vp]),
+        "fbs_lookup_compact_dev": (i32, [vp, vp, u32, vp, vp, sz, u32, vp, vp]),
+        "fbs_state_lookup": (i32, [vp, vp, vp, u32, u32, u32, vp, sz, vp, sz]),
         "fbs_tvset_create": (i32, [vp, vp, vp, u32, C.POINTER(vp)]),
         "fbs_tvset_destroy": (None, [vp]),
         "fbs_bootstrap_batch": (i32, [vp, vp, vp, vp, sz, vp]),
@@ -210,11 +215,23 @@ EXPORTED_SYMBOLS = (
     "fbs_pub_expand_dev", "fbs_state_put_public",
     "fbs_fold_keygen", "fbs_fold_key_sizes", "fbs_export_fold_key", "fbs_import_fold_key", "fbs_fold_dev", "fbs_state_fold",
     "fbs_state_fold_dev", "fbs_state_unfold_dev", "fbs_debug_fold_front_dev",
+    "fbs_lookup_map", "fbs_fold_mapped_dev", "fbs_lookup_dev", "fbs_lookup_compact_dev", "fbs_state_lookup",
     "fbs_eval_resident_mapped", "fbs_state_sum_groups",
     "fbs_audit_rows", "fbs_audit_level_dev",
 ) + _public_native.EXPORTED_SYMBOLS
 
 lib = _load()
+
+MAP_NONE, MAP_NEG = 0xFFFFFFFF, 0x80000000   # FBS_MAP_NONE, FBS_MAP_NEG of a mapped fold's map
+
+
+def lookup_map(p, N, length, base=0, stride=1):
+    """fbs_lookup_map: the box map of a table of `length` <= p entries, uint32 [N] (host side, pure)"""
+    out = np.zeros(max(1, int(N)), dtype=np.uint32)
+    rc = lib.fbs_lookup_map(int(p), int(N), int(length), int(base), int(stride), out.ctypes.data)
+    if rc != 0:
+        raise FbsError(rc, lib.fbs_last_error(None).decode())
+    return out
 
 
 def kernel_catalog():
@@ -487,6 +504,36 @@ class DeviceState:
         cts = _c(cts, np.uint64).reshape(-1, self.T, self.ctx.params.ct_words)
         self.ctx._check(lib.fbs_state_put(self.ctx._h, self._live(), int(row0), cts.shape[0], _ptr(cts)))
         return self
+
+    def lookup(self, rows, index, index_row, out=None, out_row0=0, axis=0):
+        """This state as encrypted tables read by an encrypted index (fbs_state_lookup).  axis=0: `rows` is [planes][len] row
+        numbers, plane m's entry e being row rows[m][e] at the query's own sample (or at sample 0 where this state has T = 1: a
+        shared table); axis=1: `rows` is [planes], plane m's entries being the samples of row rows[m].  Sample s of row
+        out_row0 + m of `out` <- the entry that row `index_row` of `index` names at sample s.  out=None: a new `DeviceState` of
+        `planes` rows and the index's T.  Queued on the context; needs a fold key, no secret.  Returns `out`."""
+        if axis == 0:
+            rows = _c(rows, np.uint32)
+            if rows.ndim != 2 or rows.size == 0:
+                raise ValueError("rows is [planes][len]")
+            planes, length = rows.shape
+        else:
+            rows = _c(rows, np.uint32).reshape(-1)
+            planes, length = rows.size, self.T
+        if not isinstance(index, DeviceState) or index.closed:
+            raise ValueError("index is a closed state")
+        made = out is None
+        if made:
+            out = DeviceState(self.ctx, max(1, planes), index.T)
+        try:
+            if not isinstance(out, DeviceState) or out.closed:
+                raise ValueError("out is a closed state")
+            self.ctx._check(lib.fbs_state_lookup(self.ctx._h, self._live(), _ptr(rows), int(planes), int(length), int(axis), index._h,
+                                                 int(index_row), out._h, int(out_row0)))
+        except Exception:
+            if made:
+                out.close()
+            raise
+        return out
 
     def sum_groups(self, group, row0=0, rows=None, out=None, out_row0=0):
         """Sample j of row out_row0 + r of `out` <- the sum of samples [j group, (j + 1) group) of row row0 + r, word by word modulo q
@@ -779,6 +826,23 @@ class Context(ClientContext):
     def fold_dev(self, d_cts, count, d_glwe, stream=0):
         """fbs_fold_dev: `count` big-key ciphertexts at d_cts -> folded samples at d_glwe, asynchronous on `stream`; no secret"""
         self._check(lib.fbs_fold_dev(self._h, d_cts or None, int(count), d_glwe or None, stream or None))
+
+    # ---- encrypted-index reads: a folded table rotated by an encrypted index (include/fbs_exec.h, "encrypted-index reads") ----
+    def fold_mapped_dev(self, d_cts, n_src, d_map, count, d_glwe, stream=0):
+        """fbs_fold_mapped_dev: fold position j takes ciphertext d_map[j] of the `n_src` at d_cts (MAP_NEG: negated, MAP_NONE: none)
+        -> folded samples at d_glwe, asynchronous on `stream`; no secret"""
+        self._check(lib.fbs_fold_mapped_dev(self._h, d_cts or None, int(n_src), d_map or None, int(count), d_glwe or None, stream or None))
+
+    def lookup_dev(self, d_tables, n_tables, d_table_of, d_cts_index, count, d_cts_out, stream=0):
+        """fbs_lookup_dev: big-key index ciphertexts [count][D+1] -> the entries they name of the folded tables at d_tables
+        ([n_tables][k+1][N]; d_table_of [count] or 0: index i reads table i), asynchronous on `stream`; no secret, no fold key"""
+        self._check(lib.fbs_lookup_dev(self._h, d_tables or None, int(n_tables), d_table_of or None, d_cts_index or None, int(count),
+                                       d_cts_out or None, stream or None))
+
+    def lookup_compact_dev(self, d_tables, n_tables, d_table_of, d_words, count, d_cts_out, bits=None, stream=0):
+        """fbs_lookup_compact_dev: the same lookup with the indices as compact ciphertexts [count][W] at width `bits`"""
+        self._check(lib.fbs_lookup_compact_dev(self._h, d_tables or None, int(n_tables), d_table_of or None, d_words or None, int(count),
+                                               self.default_compact_bits if bits is None else int(bits), d_cts_out or None, stream or None))
 
     def debug_fold_front_dev(self, d_cts, count, cols, tg, d_fields, stream=0):
         """fbs_debug_fold_front_dev (a test hook): the fold's front kernel alone"""

@@ -133,7 +133,7 @@ __global__ __launch_bounds__((2 << LL) * FPW) __attribute__((amdgpu_waves_per_eu
     const uint32_t *ms = job.ms;
     const uint32_t rows = 2 * a.l;
     double acc[E];
-    br_acc_init<N, LANES>(acc, a, job, t, comp != 0u);
+    br_acc_init<N, LANES, 2>(acc, a, job, t, comp != 0u ? 1u : 0u);
     const auto [round_scale, round_offset, sign_bits] = br_rounding(a.l, a.beta);
 
     const uint32_t t16 = t * 16u;   // this thread's 16 bytes of a register pair's 16 LANES
@@ -305,7 +305,8 @@ __global__ __launch_bounds__((2 << LL) * FPW) __attribute__((amdgpu_waves_per_eu
                 else out[N - j] = fq_neg(v);
             }
         } else if (t == 0) {
-            out[N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[job.table]);
+            const uint64_t b = fp_to_u64(fp_canon(acc[0]));
+            out[N] = a.post ? fq_add(b, a.post[job.table]) : b;
         }
     } else {
         br_extract<N, LANES, 2>(a, job, acc, comp, t);
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(2 << LL) __attribute__((amdgpu_waves_per_eu(2))) vo
     const uint32_t *ms = job.ms;
     const uint32_t rows = 2 * a.l;
     double acc[E];
-    br_acc_init<N, LANES>(acc, a, job, t, comp != 0u);
+    br_acc_init<N, LANES, 2>(acc, a, job, t, comp != 0u ? 1u : 0u);
     const auto [round_scale, round_offset, sign_bits] = br_rounding(a.l, a.beta);
     // zeta^e for the evaluation point zeta = psi^o a register holds: exponent x = e * o mod 2N, o = o_lane + c_m with
     // o_lane = 2 bitrev(lane part of the array position) + 1 = G k_lane + r_lane (r_lane wave-uniform) and c_m = 2 bitrev(
@@ -670,26 +671,39 @@ static bool launch_blind_rotate_main(const Kernel &k, const BrArgs &a, hipStream
     return false;
 }
 
-int dev_blind_rotate(fbs_ctx *ctx, const fbs_tvset *tv, const GateView &gv, const uint32_t *d_ms, hipStream_t stream) {
+int dev_blind_rotate(fbs_ctx *ctx, const fbs_tvset *tv, const GateView &gv, const uint32_t *d_ms, hipStream_t stream,
+                     const BrStart *start) {
     const fbs_params &p = ctx->p;
     BrArgs a{};
+    if (start) {
+        // a fused rotation leaves its whole accumulator for several tables to extract from: that has no meaning for a table that
+        // is itself the accumulator
+        if (gv.acc_rows || gv.row_words) return set_error(ctx, FBS_E_INVALID, "a rotation of an encrypted table cannot be a fused one");
+        if (!start->d_acc0 || start->n_acc == 0) return set_error(ctx, FBS_E_INVALID, "no encrypted table to rotate");
+        a.acc0 = start->d_acc0;
+        a.n_acc = start->n_acc;
+        a.acc_of = start->d_acc_of;
+    } else if (!tv) {
+        return set_error(ctx, FBS_E_INVALID, "null argument");
+    }
     a.ms = d_ms;
     a.tw_fwd = reinterpret_cast<const double *>(ctx->d_tw_fwd);
     a.tw_inv = reinterpret_cast<const double *>(ctx->d_tw_inv);
     a.psi_pow = reinterpret_cast<const double *>(ctx->d_psi_pow);
-    a.tvs = tv->d_tvs;
-    a.post = tv->d_post;
+    a.tvs = tv ? tv->d_tvs : nullptr;   // (never read where the rotation starts from an encrypted table)
+    a.post = tv && !start ? tv->d_post : nullptr;   // br_extract adds a constant where it has one: none with an encrypted table
     a.n = p.n;
     a.l = p.l_bsk;
     a.beta = p.beta_bsk;
     a.ct_words = ctx->D + 1;
     // (entry n_tables of the set is TV_0: selectable only by the rotations of a fused program, whose ids the host wrote)
-    a.n_tables = (gv.acc_rows || gv.row_words) ? tv->n_tables + 1 : std::max(1u, tv->n_tables);
+    a.n_tables = !tv ? 1u : (gv.acc_rows || gv.row_words) ? tv->n_tables + 1 : std::max(1u, tv->n_tables);
     if (gv.count > 0x7FFFFFFFull) return set_error(ctx, FBS_E_INVALID, "batch too large for one launch");
     for (const Launch &l : select_blind_rotate(ctx, gv.count)) {
         a.gv = gv;
         a.gv.f_begin += l.first;
         a.gv.count = a.count = l.count;
+        a.acc_first = (uint32_t)((start ? start->first : 0) + l.first);
         if (a.gv.out_rows) a.gv.out_rows += l.first * (size_t)(gv.row_words ? gv.row_words : ctx->D + 1);
         a.bsk_hat = reinterpret_cast<const double *>(reads_small_key(l.kernel) ? ctx->d_bsk_hat_small : ctx->d_bsk_hat);
         ctx->prof.kernel[1] = kernel_name(l.kernel);

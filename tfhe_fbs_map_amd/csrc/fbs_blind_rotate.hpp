@@ -21,10 +21,15 @@ struct BrArgs {
     const double *bsk_hat;   // [n][rows][2][N]  centred, NTT order, times 1/N
     const double *tw_fwd, *tw_inv;
     const uint64_t *tvs;     // [tables][N]
-    const uint64_t *post;    // [tables]
+    const uint64_t *post;    // [tables]; null exactly when acc0 is set: sample extraction then adds no constant
     uint32_t n, l, beta, ct_words, n_tables;
     size_t count;            // bootstraps in this launch
     const double *psi_pow;   // [N] psi^x, centred (two key bits per step only)
+    // encrypted-index reads (include/fbs_exec.h): the rotation starts from a whole GLWE sample instead of (0, .., 0, TV)
+    const uint64_t *acc0;    // [n_acc][(k + 1) N] canonical residues; null: the trivial sample, every kernel as it always was
+    const uint32_t *acc_of;  // [bootstraps of the CALL] which sample each starts from; null: bootstrap i of the call from sample i
+    uint32_t n_acc;
+    uint32_t acc_first;      // the launch's first bootstrap, counted within the call (a call may be cut into several launches)
 };
 
 // Issue priority of the two waves that share a SIMD.  They sit in wave slots 0 and 1 of it (HW_ID bits 3:0); left alone,
@@ -111,15 +116,30 @@ __device__ __forceinline__ BrJob br_job(const BrArgs &a, size_t f_want) {
 }
 
 // ACC = (0, .., 0, X^{-b~} * TV), kept CENTRED (|.| <= (q-1)/2) for the whole rotation; register m of thread t of a component
-// is coefficient t + LANES * m.  `body` (wave-uniform): this thread's component is the last one.
-template <int N, int LANES, int E>
-__device__ __forceinline__ void br_acc_init(double (&acc)[E], const BrArgs &a, const BrJob &job, uint32_t t, bool body) {
+// is coefficient t + LANES * m.  `comp` (wave-uniform): the component this thread holds, the body being component K1 - 1.
+// With a.acc0 set (encrypted-index reads) ACC = X^{-b~} * (the GLWE sample the bootstrap starts from): every component makes the
+// gather the body makes from the test polynomial, from its own polynomial of the sample.  One wave-uniform branch on a kernel
+// argument, taken once per bootstrap; a sample id that arrived in device memory and lies past the set reads sample 0.
+template <int N, int LANES, int K1, int E>
+__device__ __forceinline__ void br_acc_init(double (&acc)[E], const BrArgs &a, const BrJob &job, uint32_t t, uint32_t comp) {
     const uint32_t r = (2u * N - job.ms[a.n]) & (2u * N - 1u);
+    const bool body = comp == (uint32_t)(K1 - 1);
+    // one gather for both: what differs is where it reads and whether a mask component keeps what it read (written as two
+    // loops behind a branch, nine kernels took more registers; as one, none does: profiles/lookup/resources.txt)
+    const uint64_t *src = job.tv;
+    bool mine = body;
+    if (a.acc0) {
+        const size_t i = (size_t)a.acc_first + job.f;
+        uint32_t id = a.acc_of ? a.acc_of[i] : (uint32_t)i;
+        if (id >= a.n_acc) id = 0;
+        src = a.acc0 + ((size_t)id * K1 + comp) * N;
+        mine = true;
+    }
 #pragma unroll
     for (int m = 0; m < E; m++) {
         const uint32_t idx = (t + (uint32_t)LANES * m - r) & (2u * N - 1u);
-        const uint64_t v = job.tv[idx & (N - 1)];
-        acc[m] = body ? fp_center(fp_from_u64((idx & N) ? fq_neg(v) : v)) : 0.0;
+        const uint64_t v = src[idx & (N - 1)];
+        acc[m] = mine ? fp_center(fp_from_u64((idx & N) ? fq_neg(v) : v)) : 0.0;
     }
 }
 
@@ -155,7 +175,8 @@ __device__ __forceinline__ BrRounding br_rounding(uint32_t levels, uint32_t beta
 }
 
 // Sample extraction of coefficient 0 of a K1-component accumulator (K1 - 1 mask polynomials, then the body), plus the table's
-// constant; the whole epilogue of a kernel.  `comp` (wave-uniform): the component this thread holds.
+// constant (none where the rotation started from an encrypted sample, a.acc0); the whole epilogue of a kernel.  `comp`
+// (wave-uniform): the component this thread holds.
 template <int N, int LANES, int K1, int E>
 __device__ __forceinline__ void br_extract(const BrArgs &a, const BrJob &job, const double (&acc)[E], uint32_t comp, uint32_t t) {
     if (!job.live) return;
@@ -174,7 +195,8 @@ __device__ __forceinline__ void br_extract(const BrArgs &a, const BrJob &job, co
             else out[comp * N + N - j] = fq_neg(v);
         }
     } else if (t == 0) {
-        out[(K1 - 1) * N] = fq_add(fp_to_u64(fp_canon(acc[0])), a.post[job.table]);
+        const uint64_t b = fp_to_u64(fp_canon(acc[0]));
+        out[(K1 - 1) * N] = a.post ? fq_add(b, a.post[job.table]) : b;   // (no `post` with acc0: nothing new lives through the steps)
     }
 }
 

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : FBS_CU_WAVES_PER_EU) void k_blind_r
     const uint32_t *ms = job.ms;
     const uint32_t rows = 2 * NL;
     double acc[E];
-    br_acc_init<N, LANES>(acc, a, job, t, comp != 0u);
+    br_acc_init<N, LANES, 2>(acc, a, job, t, comp != 0u ? 1u : 0u);
     const auto [round_scale, round_offset, sign_bits] = br_rounding<NL>(NL, a.beta);
     // cross-stage twiddles: nodes 1, 2, 3 of the big tree (wave-uniform, scalar registers for the whole rotation)
     const double cw[3] = {big_f[1], big_f[2], big_f[3]}, iw[3] = {big_i[1], big_i[2], big_i[3]};
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(512, 2) void k_blind_rotate_cu_pairs(BrArgs a) {
     const uint32_t *ms = job.ms;
     constexpr uint32_t rows = 2 * NL;
     double acc[E];
-    br_acc_init<N, LANES>(acc, a, job, t, comp != 0u);
+    br_acc_init<N, LANES, 2>(acc, a, job, t, comp != 0u ? 1u : 0u);
     const auto [round_scale, round_offset, sign_bits] = br_rounding<NL>(NL, a.beta);
     const double cw[3] = {big_f[1], big_f[2], big_f[3]}, iw[3] = {big_i[1], big_i[2], big_i[3]};
     // o_lane = 2 bitrev11(512 w + (ln & 31) << 4 | (ln >> 5) << 3) + 1; omega^s = psi^(512 s), s = 1, 2, 3 (wave-uniform)

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(64 * K1 * FPW) void k_blind_rotate_glwe(BrArgs a) {
     const BrJob job = br_job<N>(a, (size_t)blockIdx.x * FPW + sub);
     const uint32_t *ms = job.ms;
     double acc[E];
-    br_acc_init<N, LANES>(acc, a, job, t, comp == (uint32_t)(K1 - 1));
+    br_acc_init<N, LANES, K1>(acc, a, job, t, comp);
     const auto [round_scale, round_offset, sign_bits] = br_rounding(a.l, a.beta);
     // the components in rotated order: d stands for component comp + d (mod K1); d = 0 is this wave's own
     uint32_t col_bytes[K1], land_word[K1];

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(192 * FPW) void k_blind_rotate_pairs_k2(BrArgs a) {
     const BrJob job = br_job<N>(a, (size_t)blockIdx.x * FPW + sub);
     const uint32_t *ms = job.ms;
     double acc[E];
-    br_acc_init<N, LANES>(acc, a, job, t, comp == (uint32_t)(K1 - 1));
+    br_acc_init<N, LANES, K1>(acc, a, job, t, comp);
     const auto [round_scale, round_offset, bhalf] = br_rounding<1>(1, a.beta);   // (one level: the sign bits are B/2)
     // zeta^e for the evaluation point a register holds: as in k_blind_rotate_pairs
     const uint32_t o_lane = 2u * (__builtin_bitreverse32(W::eval_position_lane(t)) >> (32 - LOGN)) + 1u;
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(768) void k_blind_rotate_cu_k2(BrArgs a) {
     const BrJob job = br_job<N>(a, blockIdx.x);
     const uint32_t *ms = job.ms;
     double acc[E];
-    br_acc_init<N, LANES>(acc, a, job, t, comp == (uint32_t)(K1 - 1));
+    br_acc_init<N, LANES, K1>(acc, a, job, t, comp);
     const auto [round_scale, round_offset, bhalf] = br_rounding<1>(1, a.beta);   // (one level: the sign bits are B/2)
     // cross-stage twiddles: nodes 1, 2, 3 of the big tree (wave-uniform, scalar registers for the whole rotation)
     const double cw[3] = {big_f[1], big_f[2], big_f[3]}, iw[3] = {big_i[1], big_i[2], big_i[3]};

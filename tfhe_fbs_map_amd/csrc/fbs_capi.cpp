@@ -257,6 +257,8 @@ int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value) try {
     else if (k == "state_bytes") *value = (int64_t)ctx->state_bytes;
     else if (k == "keys_made_on_device") *value = ctx->have_keys && ctx->keys_made_on_device;
     else if (k == "bsk_upload_bytes") *value = ctx->bsk_upload_bytes;
+    else if (k == "lookup_tables") *value = ctx->lookup_tables;
+    else if (k == "lookup_scratch_words") *value = (int64_t)ctx->lookup_tables_capacity;
     else return set_error(ctx, FBS_E_INVALID, "unknown statistic '" + k + "'");
     return FBS_OK;
 } FBS_API_CATCH(ctx)
@@ -278,7 +280,7 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     if (ctx->scratch_used) (void)hipStreamSynchronize(ctx->scratch_stream);
     for (void *p : {(void *)ctx->d_bsk_hat, (void *)ctx->d_bsk_hat_small, (void *)ctx->d_ksk, (void *)ctx->d_ksk_f, (void *)ctx->d_ks_corr, (void *)ctx->d_ks_a, (void *)ctx->d_ks_b, (void *)ctx->d_ks_c, (void *)ctx->d_tw_fwd, (void *)ctx->d_tw_inv, (void *)ctx->d_psi_pow, (void *)ctx->d_ms, (void *)ctx->d_ms_eps, (void *)ctx->d_ms_body, (void *)ctx->d_acc, (void *)ctx->d_stage_in, (void *)ctx->d_stage_out, (void *)ctx->d_stage_ids,
                     (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_sk_lwe_bits, (void *)ctx->d_io_msgs,
-                    (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc, (void *)ctx->d_pub, (void *)ctx->d_audit_err, (void *)ctx->d_audit_stats})
+                    (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc, (void *)ctx->d_pub, (void *)ctx->d_lookup_tables, (void *)ctx->d_lookup_idx, (void *)ctx->d_audit_err, (void *)ctx->d_audit_stats})
         if (p) (void)hipFree(p);
     for (auto &key : ctx->gadget_dev)
         for (void *p : {(void *)key.d_key, (void *)key.d_out})
@@ -1351,9 +1353,9 @@ static int fold_reserve(fbs_ctx *ctx, size_t count, size_t *pass_out) {
 // What the five entries below do once their arguments are checked: the scratch, then inside one scratch section the passes of
 // `count` ciphertexts at d_cts, packed at `bits` (GK_PACK) or folded (GK_FOLD).  A pass of `rows` ciphertexts leaves words_of(rows)
 // words, in d_dst at words_of(pass) a pass -- or, `out` given, in the kind's staging and from there in that host array, which is
-// complete when the call returns
+// complete when the call returns.  d_map (a mapped fold): position j takes ciphertext d_map[j] of the n_src at d_cts
 static int gadget_passes(fbs_ctx *ctx, GadgetKind kind, const uint64_t *d_cts, size_t count, uint32_t bits, uint64_t *d_dst, uint64_t *out,
-                         hipStream_t s) {
+                         hipStream_t s, const uint32_t *d_map = nullptr, size_t n_src = 0) {
     FBS_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t N = ctx->N, k = ctx->p.k;
     const bool packing = kind == GK_PACK;
@@ -1370,9 +1372,10 @@ static int gadget_passes(fbs_ctx *ctx, GadgetKind kind, const uint64_t *d_cts, s
         const size_t ctw = ctx->D + 1;
         for (size_t f0 = 0; f0 < count; f0 += pass) {
             const size_t rows = std::min(pass, count - f0), w0 = f0 / pass * words_of(pass);
-            const uint64_t *cts = d_cts + f0 * ctw;
+            const uint64_t *cts = d_map ? d_cts : d_cts + f0 * ctw;
             uint64_t *dst = out ? d_dst : d_dst + w0;
-            int rc = packing ? dev_keyswitch(ctx, batch_view(cts, nullptr, nullptr, rows), ctx->d_ms, 31, s) : dev_fold(ctx, cts, rows, dst, s);
+            int rc = packing ? dev_keyswitch(ctx, batch_view(cts, nullptr, nullptr, rows), ctx->d_ms, 31, s)
+                             : dev_fold(ctx, cts, rows, dst, s, d_map ? d_map + f0 : nullptr, n_src);
             if (rc == FBS_OK && packing) rc = dev_pack(ctx, ctx->d_ms, rows, bits, dst, s);
             if (rc != FBS_OK) return rc;
             if (out && hipMemcpyAsync(out + w0, dst, words_of(rows) * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
@@ -1413,6 +1416,130 @@ int fbs_fold_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_
     if (int rc = check_fold_target(ctx, d_glwe)) return rc;
     if (count == 0) return FBS_OK;
     return gadget_passes(ctx, GK_FOLD, d_cts, count, 0, d_glwe, nullptr, pick(ctx, stream));
+} FBS_API_CATCH(ctx)
+
+// ---- encrypted-index reads (include/fbs_exec.h): the mapped fold that lays a table out, the rotation that reads it ----------------
+int fbs_lookup_map(uint32_t p, uint32_t N, uint32_t len, uint32_t base, uint32_t stride, uint32_t *map_out) try {
+    return host_lookup_map(p, N, len, base, stride, map_out);
+} FBS_API_CATCH(nullptr)
+
+// (no secret needed: runs on evaluation-only contexts)
+int fbs_fold_mapped_dev(fbs_ctx *ctx, const uint64_t *d_cts, size_t n_src, const uint32_t *d_map, size_t count, uint64_t *d_glwe,
+                        void *stream) try {
+    if (!ctx || (count && (!d_cts || !d_map || !d_glwe))) return FBS_E_INVALID;
+    if (int rc = gadget_prologue(ctx, GK_FOLD, count, 0)) return rc;
+    if (int rc = check_ct_words(ctx, n_src)) return rc;
+    if (int rc = check_fold_target(ctx, d_glwe)) return rc;
+    if (count == 0) return FBS_OK;
+    if (n_src == 0 || n_src >= FOLD_MAP_NEG) return set_error(ctx, FBS_E_INVALID, "a mapped fold reads 1 .. 2^31 - 1 source ciphertexts");
+    return gadget_passes(ctx, GK_FOLD, d_cts, count, 0, d_glwe, nullptr, pick(ctx, stream), d_map, n_src);
+} FBS_API_CATCH(ctx)
+
+// what both lookups check once their buffers and keys are: the tables
+static int check_lookup_tables(const fbs_ctx *ctx, const uint64_t *d_tables, uint32_t n_tables, size_t count) {
+    if (count && (!d_tables || n_tables == 0)) return set_error(ctx, FBS_E_INVALID, "a lookup needs at least one table");
+    if ((uintptr_t)d_tables & 15u) return set_error(ctx, FBS_E_INVALID, "tables are folded samples: d_tables must be 16-byte aligned");
+    if (count > 0x7FFFFFFFull) return set_error(ctx, FBS_E_INVALID, "batch too large");
+    return FBS_OK;
+}
+
+// (needs neither a secret nor a fold key)
+int fbs_lookup_dev(fbs_ctx *ctx, const uint64_t *d_tables, uint32_t n_tables, const uint32_t *d_table_of, const uint64_t *d_cts_index,
+                   size_t count, uint64_t *d_cts_out, void *stream) try {
+    if (int rc = io_prologue(ctx, d_cts_index, d_cts_out, count, IO_CT_WORDS, nullptr)) return rc;
+    if (int rc = check_lookup_tables(ctx, d_tables, n_tables, count)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure_ms(ctx, count)) return rc;
+    const GateView gv = batch_view(d_cts_index, d_cts_out, nullptr, count);
+    const BrStart start{d_tables, n_tables, d_table_of, 0};
+    hipStream_t s = pick(ctx, stream);
+    return scratch_section(ctx, s, [&]() -> int {
+        if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) return rc;
+        return dev_blind_rotate(ctx, nullptr, gv, ctx->d_ms, s, &start);
+    });
+} FBS_API_CATCH(ctx)
+
+// fbs_refresh_compact_dev with the table in place of the identity polynomial: its passes, its unpack
+int fbs_lookup_compact_dev(fbs_ctx *ctx, const uint64_t *d_tables, uint32_t n_tables, const uint32_t *d_table_of, const uint64_t *d_words,
+                           size_t count, uint32_t bits, uint64_t *d_cts_out, void *stream) try {
+    if (int rc = io_prologue(ctx, d_words, d_cts_out, count, IO_CT_WORDS, nullptr)) return rc;
+    if (int rc = check_bits(ctx, bits)) return rc;
+    if (int rc = check_compact_words(ctx, count, bits)) return rc;
+    if (int rc = check_lookup_tables(ctx, d_tables, n_tables, count)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ctw = ctx->D + 1, W = compact_words(ctx->p.n, bits);
+    hipStream_t s = pick(ctx, stream);
+    return ms_passes(ctx, count, s, [&](size_t f0, size_t rows) {
+        if (int rc = dev_compact_unpack(ctx, d_words + f0 * W, rows, bits, ctx->d_ms, s)) return rc;
+        const BrStart start{d_tables, n_tables, d_table_of, f0};
+        return dev_blind_rotate(ctx, nullptr, batch_view(nullptr, d_cts_out + f0 * ctw, nullptr, rows), ctx->d_ms, s, &start);
+    });
+} FBS_API_CATCH(ctx)
+
+// Resident state read by an encrypted index: for every sample s of the index state and every plane m, row out_row0 + m of the output
+// at sample s is the entry of plane m's table that index row `index_row` names at sample s.  The maps (the box map per table), the
+// table each bootstrap reads and the planes' one shared key-switch source are made on the host and uploaded once; the tables are
+// one mapped fold into a scratch of their own; the rotation is one dev_blind_rotate whose planes share the index's key switch and
+// modulus switch through GateView::source_of.  Table (m, s) is number m T + s, or m where the planes' tables are shared.
+int fbs_state_lookup(fbs_ctx *ctx, const fbs_state *table_state, const uint32_t *rows, uint32_t n_planes, uint32_t len, uint32_t axis,
+                     const fbs_state *index_state, size_t index_row, fbs_state *out_state, size_t out_row0) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (!state_of(ctx, table_state) || !state_of(ctx, index_state) || !state_of(ctx, out_state))
+        return set_error(ctx, FBS_E_INVALID, "not a live state of this context");
+    if (!rows || n_planes == 0) return set_error(ctx, FBS_E_INVALID, "a lookup reads at least one plane");
+    if (axis > 1) return set_error(ctx, FBS_E_INVALID, "axis is 0 (rows) or 1 (samples)");
+    if (out_state == table_state || out_state == index_state) return set_error(ctx, FBS_E_INVALID, "the output state must be another state");
+    const size_t T = index_state->T, Tt = table_state->T;
+    const uint32_t N = ctx->N, p = ctx->p.p_msg, k1 = ctx->p.k + 1;
+    if (len == 0) return set_error(ctx, FBS_E_INVALID, "a table has at least one entry");
+    if (len > p) return set_error(ctx, FBS_E_INVALID, "a table has at most p entries");
+    if (axis == 0 && Tt != 1 && Tt != T) return set_error(ctx, FBS_E_INVALID, "the table state has neither one sample nor the index state's");
+    if (axis == 1 && Tt != len) return set_error(ctx, FBS_E_INVALID, "along the samples a table is the table state's samples: len must be its T");
+    if (index_row >= index_state->rows) return set_error(ctx, FBS_E_INVALID, "rows past the end of the state");
+    if (out_state->T != T || out_row0 > out_state->rows || n_planes > out_state->rows - out_row0)
+        return set_error(ctx, FBS_E_INVALID, "the output state holds n_planes rows of the index state's samples from out_row0 on");
+    const size_t n_rows = axis == 0 ? (size_t)n_planes * len : n_planes;
+    for (size_t i = 0; i < n_rows; i++)
+        if (rows[i] >= table_state->rows) return set_error(ctx, FBS_E_INVALID, "rows past the end of the state");
+    const bool shared = axis == 1 || Tt == 1;
+    const size_t n_tab = shared ? n_planes : (size_t)n_planes * T, n_src = table_state->rows * Tt, count = (size_t)n_planes * T;
+    if (n_src >= FOLD_MAP_NEG || n_tab > 0x7FFFFFFFull / N || count > 0x7FFFFFFFull) return set_error(ctx, FBS_E_INVALID, "batch too large");
+    if (int rc = gadget_prologue(ctx, GK_FOLD, n_tab * N, 0)) return rc;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    // the index arrays: [n_tab][N] maps, [count] table of bootstrap f = m T + s, [n_planes] zeros (every plane reads source 0)
+    std::vector<uint32_t> idx(n_tab * N + count + n_planes, 0u);
+    std::vector<uint32_t> box(N);
+    for (uint32_t j = 0; j < N; j++) box[j] = (uint32_t)(((uint64_t)j * 2 * p + N) / (2ull * N));
+    for (size_t t = 0; t < n_tab; t++) {
+        const size_t m = shared ? t : t / T, s = shared ? 0 : t % T;
+        auto src = [&](uint32_t x) -> uint32_t {
+            return axis == 0 ? (uint32_t)((size_t)rows[m * len + x] * Tt + (Tt == 1 ? 0 : s)) : (uint32_t)((size_t)rows[m] * Tt + x);
+        };
+        uint32_t *map = idx.data() + t * N;
+        for (uint32_t j = 0; j < N; j++) map[j] = box[j] < len ? src(box[j]) : box[j] < p ? FOLD_MAP_NONE : src(0) | FOLD_MAP_NEG;
+    }
+    for (size_t f = 0; f < count; f++) idx[n_tab * N + f] = (uint32_t)(shared ? f / T : f);
+    hipStream_t s = ctx->stream;
+    if (int rc = grow(ctx, ctx->d_lookup_idx, ctx->lookup_idx_capacity, idx.size(), 4, false)) return rc;
+    if (int rc = grow(ctx, ctx->d_lookup_tables, ctx->lookup_tables_capacity, n_tab * k1 * N, 8, true)) return rc;
+    if (int rc = ensure_ms(ctx, T)) return rc;
+    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));   // (an earlier call may still read the index arrays)
+    FBS_HIP(ctx, hipMemcpy(ctx->d_lookup_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+    if (int rc = gadget_passes(ctx, GK_FOLD, table_state->d, n_tab * N, 0, ctx->d_lookup_tables, nullptr, s, ctx->d_lookup_idx, n_src)) return rc;
+    ctx->lookup_tables = (int64_t)n_tab;
+    const size_t ctw = ctx->D + 1;
+    GateView gv{};
+    gv.in_base = index_state->d + index_row * T * ctw;
+    gv.out_base = out_state->d + out_row0 * T * ctw;
+    gv.source_of = ctx->d_lookup_idx + n_tab * N + count;
+    gv.T = T, gv.s_count = T, gv.count = count, gv.ks_count = T, gv.n_gates = n_planes;
+    const BrStart start{ctx->d_lookup_tables, (uint32_t)n_tab, ctx->d_lookup_idx + n_tab * N, 0};
+    return scratch_section(ctx, s, [&]() -> int {
+        if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) return rc;
+        return dev_blind_rotate(ctx, nullptr, gv, ctx->d_ms, s, &start);
+    });
 } FBS_API_CATCH(ctx)
 
 int fbs_state_fold(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint64_t *out) try {

@@ -9,6 +9,8 @@
 //                       to the SOURCE: D + 1 is odd, so every other row starts 8 bytes off a 16-byte line; the word the pairs
 //                       leave at either end is read on its own (the cases of wave_copy_ct).  No lane reads with the stride of a
 //                       ciphertext.  Stores are 256 coalesced bytes a wave.  Ciphertexts past `count` are not read: zero.
+//   k_fold_front_mapped the same front for a MAPPED fold ("encrypted-index reads"): position j takes ciphertext map[j], negated or
+//                       none at all as the map says; everything behind it is the fold's own.
 //   k_pack_accumulate   (fbs_pack.hip, as it stands) with n := D, the fields above and the fold key: its slicing for launches of
 //                       few samples, its common row order, PACK_CENTRE_EVERY.
 //   k_fold_finish       one workgroup per (sample, component): the slices summed, inverse transform, negated, the raw body words
@@ -72,6 +74,58 @@ __global__ __launch_bounds__(256) void k_fold_front(const uint64_t *__restrict__
     if (last && threadIdx.x < FF_ROWS) reinterpret_cast<uint64_t *>(fields + (size_t)D * cols)[j0 + threadIdx.x] = bodies[threadIdx.x];
 }
 
+// The mapped fold's front ("encrypted-index reads" in include/fbs_exec.h): position j of the pass takes ciphertext map[j] of the
+// n_src at cts instead of ciphertext j -- the same tile, the same source-aligned 16-byte row reads, the same stores.  Bit 31 of
+// map[j]: every word of the ciphertext, masks and body, is negated (fq_neg) before anything else, so the rounding sees what it
+// would see in the materialised array.  FOLD_MAP_NONE: no ciphertext, zero words, as past `count`.  The map is device memory the
+// host cannot check: an index at or past n_src reads ciphertext 0, never past the array.  A box map names the same source N / p
+// positions running, so most of a tile's rows re-read one row out of L2.
+__global__ __launch_bounds__(256) void k_fold_front_mapped(const uint64_t *__restrict__ cts, size_t n_src, const uint32_t *__restrict__ map,
+                                                           uint32_t D, size_t count, uint32_t cols, uint32_t tg, uint32_t *__restrict__ fields) {
+    __shared__ uint32_t tile[FF_ROWS][FF_COLS + 1];
+    __shared__ uint64_t bodies[FF_ROWS];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t w0 = blockIdx.x * FF_COLS, j0 = blockIdx.y * FF_ROWS;
+    const bool last = w0 + FF_COLS == D;
+    const uint32_t w1 = w0 + FF_COLS + (last ? 1u : 0u);
+#pragma unroll 4
+    for (uint32_t r = wave; r < FF_ROWS; r += 4) {          // wave-uniform
+        const size_t j = (size_t)j0 + r;
+        const uint32_t m = j < count ? map[j] : FOLD_MAP_NONE;
+        if (m == FOLD_MAP_NONE) {
+            tile[r][lane] = 0u;
+            tile[r][lane + 64] = 0u;
+            if (lane == 0) bodies[r] = 0;
+            continue;
+        }
+        const bool neg = (m & 0x80000000u) != 0;
+        size_t src = m & 0x7FFFFFFFu;
+        if (src >= n_src) src = 0;
+        auto put = [&](uint32_t w, uint64_t x) {            // w in [w0, w1)
+            if (neg) x = fq_neg(x);
+            if (w == D) bodies[r] = x;
+            else tile[r][w - w0] = compact_round(x, tg);
+        };
+        const uint64_t *row = cts + src * ((size_t)D + 1);
+        const uint32_t head = (uint32_t)(((uintptr_t)(row + w0) >> 3) & 1u);
+        const uint32_t w = w0 + head + 2 * lane;
+        if (w + 1 < w1) {
+            const u64x2 p = *reinterpret_cast<const u64x2 *>(row + w);
+            put(w, p[0]);
+            put(w + 1, p[1]);
+        } else if (w < w1) {
+            put(w, row[w]);
+        }
+        if (lane == 63) {
+            if (head) put(w0, row[w0]);
+            else if (last) put(D, row[D]);
+        }
+    }
+    __syncthreads();
+    for (uint32_t c = wave; c < FF_COLS; c += 4) fields[(size_t)(w0 + c) * cols + j0 + lane] = tile[lane][c];
+    if (last && threadIdx.x < FF_ROWS) reinterpret_cast<uint64_t *>(fields + (size_t)D * cols)[j0 + threadIdx.x] = bodies[threadIdx.x];
+}
+
 // grid: samples * (k + 1) workgroups, component fastest; a.words [samples][k + 1][N], 16-byte aligned
 template <int LOGN, int LL>
 __global__ __launch_bounds__(1 << LL) void k_fold_finish(PackArgs a, uint32_t k1) {
@@ -117,7 +171,7 @@ int dev_fold_front(const fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint
     return FBS_OK;
 }
 
-int dev_fold(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, hipStream_t stream) {
+int dev_fold(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, hipStream_t stream, const uint32_t *d_map, size_t n_src) {
     if (count == 0) return FBS_OK;
     const uint32_t N = ctx->N, D = ctx->D, k1 = ctx->p.k + 1;
     const size_t samples = (count + N - 1) / N;
@@ -137,7 +191,13 @@ int dev_fold(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe
     a.slices = pack_slices_for(ctx, samples, D);
     if (((size_t)D + 2) * a.cols > ctx->pack_fields_capacity || samples * a.slices * k1 * N > ctx->pack_acc_capacity)
         return set_error(ctx, FBS_E_INVALID, "fold scratch too small for the launch");
-    if (int rc = dev_fold_front(ctx, d_cts, count, a.cols, a.t * a.gamma, ctx->d_pack_fields, stream)) return rc;
+    if (d_map) {
+        hipLaunchKernelGGL(k_fold_front_mapped, dim3(D / FF_COLS, a.cols / FF_ROWS), dim3(256), 0, stream, d_cts, n_src, d_map, D, count,
+                           a.cols, a.t * a.gamma, ctx->d_pack_fields);
+        FBS_HIP(ctx, hipGetLastError());
+    } else if (int rc = dev_fold_front(ctx, d_cts, count, a.cols, a.t * a.gamma, ctx->d_pack_fields, stream)) {
+        return rc;
+    }
     if (int rc = dev_pack_accumulate(ctx, a, samples, stream)) return rc;
     bool launched = false;
 #define X(L, K1)                                                                                                                \

@@ -542,6 +542,23 @@ int host_build_tv(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint64
     return FBS_OK;
 }
 
+// The box rule above as the map of a mapped fold (fbs_lookup_map of include/fbs_exec.h, "encrypted-index reads"): coefficient j takes
+// source base + slot stride for slot < len, nothing for len <= slot < p, and source `base` negated in the half box below X^N.
+// Pure: no context.  A source index must fit the 31 bits a map entry has for it.
+int host_lookup_map(uint32_t p, uint32_t N, uint32_t len, uint32_t base, uint32_t stride, uint32_t *map_out) {
+    if (!map_out) return FBS_E_INVALID;
+    if (p < 2) return set_error(nullptr, FBS_E_INVALID, "a table needs p >= 2");
+    if (N < 2 || N > (1u << 16) || (N & (N - 1))) return set_error(nullptr, FBS_E_INVALID, "N must be a power of two in [2, 2^16]");
+    if (len == 0) return set_error(nullptr, FBS_E_INVALID, "a table has at least one entry");
+    if (len > p) return set_error(nullptr, FBS_E_INVALID, "a table has at most p entries");
+    if ((uint64_t)base + (uint64_t)(len - 1) * stride >= FOLD_MAP_NEG) return set_error(nullptr, FBS_E_INVALID, "a source index must stay below 2^31");
+    for (uint32_t j = 0; j < N; j++) {
+        const uint64_t x = ((uint64_t)j * 2 * p + N) / (2ull * N);
+        map_out[j] = x < len ? base + (uint32_t)x * stride : x < p ? FOLD_MAP_NONE : base | FOLD_MAP_NEG;
+    }
+    return FBS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Several tables on one blind rotation (multi-value bootstrap; Carpov, Izabachene, Mollimard, CT-RSA 2019).  The test
 // vector above is delta_half * G(X) with G_j = +-(2 f - c), and (1 + X + .. + X^(N-1)) (1 - X) = 2 in Z[X]/(X^N + 1), so

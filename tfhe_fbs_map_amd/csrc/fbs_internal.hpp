@@ -223,6 +223,8 @@ struct GadgetKindInfo {
     Domain mask_dom, noise_dom;
 };
 constexpr GadgetKindInfo GADGET_KINDS[2] = {{"packing", "p", DOM_PACK_MASK, DOM_PACK_NOISE}, {"fold", "f", DOM_FOLD_MASK, DOM_FOLD_NOISE}};
+// a mapped fold's map entries (include/fbs_exec.h, "encrypted-index reads"): no ciphertext; the ciphertext negated
+constexpr uint32_t FOLD_MAP_NONE = 0xFFFFFFFFu, FOLD_MAP_NEG = 0x80000000u;
 inline uint32_t gadget_rows(const HostState &c, GadgetKind kind) { return kind == GK_PACK ? c.p.n : c.D; }
 inline const std::vector<uint64_t> &gadget_secret(const HostState &c, GadgetKind kind) { return kind == GK_PACK ? c.sk_lwe : c.sk_glwe; }
 
@@ -283,6 +285,13 @@ struct fbs_ctx : fbs::HostState {
     size_t pack_fields_capacity = 0; // in words
     double *d_pack_acc = nullptr;
     size_t pack_acc_capacity = 0;    // in words
+    // encrypted-index reads of resident state (fbs_state_lookup): the tables of a call, [tables][k+1][N], the packing scratch's
+    // neighbour, grown like it; and the call's index arrays (the maps [tables][N], which table a bootstrap reads, the planes' shared source)
+    uint64_t *d_lookup_tables = nullptr;
+    size_t lookup_tables_capacity = 0;   // in words
+    uint32_t *d_lookup_idx = nullptr;
+    size_t lookup_idx_capacity = 0;      // in words
+    int64_t lookup_tables = 0;           // tables the last fbs_state_lookup folded (fbs_ctx_stat)
     uint64_t *d_pub = nullptr;       // staging of fbs_state_put_public's GLWE samples
     size_t pub_capacity = 0;         // in words
     fbs_tvset *tv_identity = nullptr;   // the identity table [0, 1, .., p - 1], made on first use: what refreshes a compact input
@@ -463,6 +472,8 @@ void host_expand_gadget_key(const fbs_ctx *ctx, GadgetKind kind, const RandKey &
 // packed words of `count` outputs at width `bits` -> msgs[count] under sk_glwe
 void host_decrypt_packed(const fbs_ctx *ctx, const uint64_t *words, size_t count, uint32_t bits, int64_t *msgs);
 int host_build_tv(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint64_t *tv, uint64_t *post_add);
+// the same box rule as the map of a mapped fold: what fbs_lookup_map answers (map_out [N])
+int host_lookup_map(uint32_t p, uint32_t N, uint32_t len, uint32_t base, uint32_t stride, uint32_t *map_out);
 // D_F with TV_F = TV_0 * D_F as (position, value) pairs of its non-zero coefficients, at most p + 1 of them (`pos`, `val`
 // sized for that); *norm2 = |D_F|^2, *g_norm2 = |G_F|^2 (TV_F = delta_half G_F), *abs_sum = sum |d|.  Errors as host_build_tv.
 int host_build_tv_diff(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint32_t *pos, int32_t *val, uint32_t *count,
@@ -498,7 +509,16 @@ int dev_keyswitch_gemm_setup(fbs_ctx *ctx);   // limb fragments of the key-switc
 int dev_keyswitch(fbs_ctx *ctx, const GateView &gv, uint32_t *d_ms, uint32_t log2_mod, hipStream_t stream);
 int dev_keyswitch_reserve(fbs_ctx *ctx, size_t count);          // scratch of the GEMM key switch for launches of `count` (blocks when it grows)
 int dev_keyswitch_rezero(fbs_ctx *ctx, hipStream_t stream);     // puts its "zero between launches" scratch back after a failed call
-int dev_blind_rotate(fbs_ctx *ctx, const fbs_tvset *tv, const GateView &gv, const uint32_t *d_ms, hipStream_t stream);
+// `start` (encrypted-index reads): the GLWE samples the rotations start from instead of the trivial sample of a table -- `tv` may
+// then be null, no constant is added at the extraction, and the fused path (accumulator rows) is refused
+struct BrStart {
+    const uint64_t *d_acc0;     // [n_acc][(k + 1) N] canonical residues, 16-byte aligned
+    uint32_t n_acc;
+    const uint32_t *d_acc_of;   // [first + gv.count] device memory, or null: bootstrap i starts from sample first + i
+    size_t first;               // the pass's first bootstrap, counted within the entry's call (an entry may run in passes)
+};
+int dev_blind_rotate(fbs_ctx *ctx, const fbs_tvset *tv, const GateView &gv, const uint32_t *d_ms, hipStream_t stream,
+                     const BrStart *start = nullptr);
 // `T` = sample stride of the wire buffer, samples [s_begin, s_begin + s_count) are computed
 int dev_lincomb(fbs_ctx *ctx, uint64_t *d_wires, size_t T, size_t s_begin, size_t s_count, uint32_t n_out,
                 const uint32_t *d_dst, const uint32_t *d_term_off, const uint32_t *d_srcs, const uint64_t *d_coefs,
@@ -554,8 +574,10 @@ struct PackArgs;
 int dev_pack_accumulate(const fbs_ctx *ctx, const PackArgs &a, size_t samples, hipStream_t stream);
 // folded state (fbs_fold.hip).  dev_fold: the big-key ciphertexts d_cts [count][D + 1] that start a folded sample -> the samples
 // d_glwe [ceil(count / N)][k + 1][N]; uses d_pack_fields (D * samples * N + 2 * samples * N words) and d_pack_acc, which the caller
-// has sized.  dev_fold_front: its first kernel alone, d_cts -> d_fields [D][cols] rounded to tg bits, then cols body words
-int dev_fold(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, hipStream_t stream);
+// has sized.  dev_fold_front: its first kernel alone, d_cts -> d_fields [D][cols] rounded to tg bits, then cols body words.
+// d_map (the mapped fold, "encrypted-index reads" in include/fbs_exec.h): position j takes ciphertext d_map[j] of the n_src at d_cts
+int dev_fold(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, hipStream_t stream, const uint32_t *d_map = nullptr,
+             size_t n_src = 0);
 int dev_fold_front(const fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t cols, uint32_t tg, uint32_t *d_fields, hipStream_t stream);
 
 // audited evaluation (fbs_audit.hip): errors of the big-key ciphertexts in slots d_row_slot[rows], samples [s_begin, s_begin + s_count),

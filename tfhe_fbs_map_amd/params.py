@@ -279,6 +279,25 @@ def fold_choice(prm: Params, norm2: float = 1.0, min_margin: float = 6.0):
     return best
 
 
+# ---- encrypted-index reads (include/fbs_exec.h, "encrypted-index reads") ------------------------------------------------------------
+def lookup_output_norm2(table_out_norm2: float, fold_factor: float, digits: int = 1) -> float:
+    """What a lookup's output carries, in units of one blind rotation's output variance: the table entry's own noise, and per digit
+    the fold that laid the round's table out (`folded_state_factor`) and the rotation that read it.  Rotating by a monomial adds
+    nothing, so the entry's noise goes through once however many digits there are."""
+    return table_out_norm2 + digits * (fold_factor + 1.0)
+
+
+# what `choose_params` and `fold_choice` ask of a set by default (their min_margin): the floor `split.plan_lookup` holds a lookup's
+# refreshed output to when its caller names none
+SET_MARGIN = 6.0
+
+
+def lookup_index_margin(prm: Params, index_out_norm2: float = 1.0) -> float:
+    """Standard deviations between the phase a lookup rotates by and the edge of its box: the index is read like any refreshed
+    full link (`refresh_margin` at bits=None)"""
+    return refresh_margin(prm, None, index_out_norm2)
+
+
 def p_error(margin: float) -> float:
     """Probability that a Gaussian leaves +-margin standard deviations (one bootstrap)."""
     return math.erfc(margin / math.sqrt(2.0))

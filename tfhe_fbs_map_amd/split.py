@@ -632,6 +632,49 @@ def plan_sum_groups(p, T, group, max_value=1, out_norm2=None):
     return -(-int(T) // group), None if out_norm2 is None else np.asarray(out_norm2, np.float64).reshape(-1) * group
 
 
+def plan_lookup(params, fold_factor, p, T_table, T_index, n_entries, digits, table_out_norm2, index_out_norm2, axis, min_margin=None):
+    """The pure part of an encrypted-index read of resident state (include/fbs_exec.h, "encrypted-index reads"): -> (rounds,
+    out_norm2) or ValueError.  `n_entries` entries per plane are read by an index of `digits` digits base p, least significant first,
+    as a cascade of one primitive: round r cuts what round r - 1 left (round 0: the entries) into blocks of p and reads every block by
+    digit r, so rounds[r] = ceil(n_entries / p^(r + 1)) lookups per plane and sample.  Every round folds its table
+    (`fold_factor`: the server key's `fold_factor`, None without a fold key) and rotates it once:
+    out_norm2 = `params.lookup_output_norm2(table_out_norm2, fold_factor, digits)`.  axis "rows": a plane's entries are rows of the
+    table state, at the index's own sample (T_table == T_index) or shared by every sample (T_table == 1); axis "samples": they are
+    the samples of one row, shared by every query, so n_entries == T_table <= p.  Refused: no fold key; no entry, or more than
+    p^digits; a table whose T fits neither; an index that the rotation would read with less than `params.refresh_margin_needed(
+    params, 1)`, the margin of a program's own bootstraps at norm2 = 1 (a bootstrap output meets it with equality); an output
+    that, refreshed by the chain that reads it (out_norm2 > 1: `plan_chain` refreshes it), would keep less than `params.SET_MARGIN`, the 6 standard
+    deviations `params.choose_params` and `params.fold_choice` ask of a set by default (a set chosen for another margin: pass it) -- at norm2 = 1 itself nothing that has been through a
+    fold and a rotation can stay: 6.60 against 6.61 at the default (15, 70) set.  `min_margin`, when given, stands in for both."""
+    from .params import SET_MARGIN, lookup_index_margin, lookup_output_norm2, refresh_margin, refresh_margin_needed
+    p, n_entries, digits, T_table, T_index = int(p), int(n_entries), int(digits), int(T_table), int(T_index)
+    if fold_factor is None:
+        raise ValueError("the server key has no fold key: an encrypted-index read folds its table first")
+    if axis not in ("rows", "samples"):
+        raise ValueError("axis %r is neither 'rows' nor 'samples'" % (axis,))
+    if digits < 1:
+        raise ValueError("an index has at least one digit")
+    if n_entries == 0:
+        raise ValueError("a table has at least one entry")
+    if n_entries > p ** digits:
+        raise ValueError("%d entries are more than %d digit(s) base %d name (%d)" % (n_entries, digits, p, p ** digits))
+    if axis == "rows" and T_table not in (1, T_index):
+        raise ValueError("a table of %d samples is neither shared (1) nor the index's own (%d)" % (T_table, T_index))
+    if axis == "samples" and (n_entries != T_table or n_entries > p):
+        raise ValueError("along the samples a table is its state's %d samples, at most p = %d: %d entries asked" % (T_table, p, n_entries))
+    need = refresh_margin_needed(params, 1.0) if min_margin is None else float(min_margin)
+    need_out = SET_MARGIN if min_margin is None else float(min_margin)
+    index_margin = lookup_index_margin(params, float(np.max(index_out_norm2)))
+    if index_margin < need:
+        raise ValueError("the index would be read at %.2f standard deviations, below the %.2f needed: refresh it first" % (index_margin, need))
+    out_norm2 = lookup_output_norm2(float(np.max(table_out_norm2)), float(fold_factor), digits)
+    out_margin = refresh_margin(params, None, out_norm2)
+    if out_margin < need_out:
+        raise ValueError("the entry read would refresh at %.2f standard deviations, below the %.2f needed: refresh the table first"
+                         % (out_margin, need_out))
+    return [-(-n_entries // p ** (r + 1)) for r in range(digits)], out_norm2
+
+
 class SampleView:
     """The rows of a `ResidentOutputs` read through a sample map (`ResidentOutputs.samples`): T = len(index) samples, sample s the
     state's sample index[s], or a trivial ciphertext of `fill` where index[s] == SAMPLE_NONE.  A source of `Server.run_chain`
@@ -1018,6 +1061,76 @@ class Server:
         finally:
             for state in expanded.values():   # (closing waits for the evaluations queued on the context)
                 state.close()
+
+    def lookup(self, table: "ResidentOutputs", entries, index: "ResidentOutputs", index_name, out_names=None, axis="rows") -> "ResidentOutputs":
+        """Encrypted-index reads of resident state (include/fbs_exec.h, "encrypted-index reads"; fbs_state_lookup): for every sample
+        of `index`, entry `i` of each plane of `table`, `i` being the encrypted value of row `index_name` at that sample -- or of
+        several rows, digits base p, least significant first.  entries: a list of planes; axis "rows": each plane a list of row
+        names of `table` (entry e = name e), read at the query's own sample, or at sample 0 where `table` has one sample (a shared
+        table, folded once); axis "samples": each plane one row name, its entries being that row's samples.  Several digits run as
+        a cascade of the one primitive: round 0 cuts each plane into blocks of p entries and reads every block by digit 0; the
+        results, a temporary resident state, are the entries of round 1, read by digit 1, and so on (`plan_lookup`: ceil(E/p) +
+        ceil(E/p^2) + .. lookups per plane and sample).  Temporaries are freed also when a round raises.  An index past the
+        entries reads 0.  -> a `ResidentOutputs` of one row per plane (`out_names`, or lookup0, lookup1, ..) carrying
+        `params.lookup_output_norm2`; a chain that reads it refreshes it (`plan_chain`: out_norm2 > 1).  `plan_lookup` says what
+        is refused; so is a closed state or one resident on another server."""
+        for what, res in (("table", table), ("index", index)):
+            if not isinstance(res, ResidentOutputs) or res.closed:
+                raise ValueError("the %s is not an open ResidentOutputs" % what)
+            if res.server is not self or res.state.ctx is not self.ctx or res.fingerprint != self.key.fingerprint:
+                raise ValueError("the %s is resident on another server" % what)
+        prm = self.key.params
+        p = prm.p_msg
+        digit_names = [index_name] if isinstance(index_name, str) else list(index_name)
+        planes = [list(pl) if axis == "rows" else [pl] for pl in entries]
+        if not planes or any(len(pl) != len(planes[0]) for pl in planes):
+            raise ValueError("every plane has the same number of entries, and there is at least one plane")
+
+        def rows_of(res, names):
+            missing = [n for n in names if n not in res.output_names]
+            if missing:
+                raise ValueError("no row named %s" % ", ".join(map(str, missing)))
+            return [res.output_names.index(n) for n in names]
+        digit_rows = rows_of(index, digit_names)
+        cur_rows = [rows_of(table, pl) for pl in planes]
+        used = sorted({r for pl in cur_rows for r in pl})
+        t2 = np.ones(len(table.output_names)) if table.out_norm2 is None else table.out_norm2
+        i2 = np.ones(len(index.output_names)) if index.out_norm2 is None else index.out_norm2
+        n_entries = table.T if axis == "samples" else len(planes[0])
+        fold_factor = None if self.key.fold_bodies is None else self.key.fold_factor
+        _, out_norm2 = plan_lookup(prm, fold_factor, p, table.T, index.T, n_entries, len(digit_names), t2[used], i2[digit_rows], axis)
+        names = ["lookup%d" % m for m in range(len(planes))] if out_names is None else list(out_names)
+        if len(names) != len(planes):
+            raise ValueError("%d output names for %d planes" % (len(names), len(planes)))
+        cur, temps = table.state, []
+        try:
+            for r, digit in enumerate(digit_rows):
+                if r == 0 and axis == "samples":
+                    new = cur.lookup([pl[0] for pl in cur_rows], index.state, digit, axis=1)
+                    temps.append(new)
+                    cur_rows = [[m] for m in range(len(planes))]
+                else:
+                    blocks = [(m, pl[b:b + p]) for m, pl in enumerate(cur_rows) for b in range(0, len(pl), p)]
+                    order = sorted(range(len(blocks)), key=lambda i: -len(blocks[i][1]))          # whole blocks first, then the tails
+                    new = self.ctx.state(len(blocks), index.T)
+                    temps.append(new)
+                    at = 0
+                    while at < len(order):                                                         # one call per block length: two at most
+                        group = [i for i in order[at:] if len(blocks[i][1]) == len(blocks[order[at]][1])]
+                        cur.lookup([blocks[i][1] for i in group], index.state, digit, out=new, out_row0=at, axis=0)
+                        at += len(group)
+                    row_of = {i: row for row, i in enumerate(order)}
+                    cur_rows = [[row_of[i] for i, (m2, _) in enumerate(blocks) if m2 == m] for m in range(len(planes))]
+                if len(temps) > 1:
+                    temps.pop(0).close()
+                cur = new
+            assert all(len(pl) == 1 for pl in cur_rows)
+            if [pl[0] for pl in cur_rows] != list(range(len(planes))):                             # (one block a plane: already in order)
+                raise AssertionError("the last round leaves one row a plane, in order")
+            return ResidentOutputs(names, index.T, self.key.fingerprint, np.full(len(planes), out_norm2), temps.pop(), self)
+        finally:
+            for st in temps:
+                st.close()
 
     def fold(self, env, state: "ResidentOutputs", left, right, back=None, fill=0) -> "ResidentOutputs":
         """A tree reduction of the T samples of `state` to one, on the GPU: `env` combines two samples into one, and each round
