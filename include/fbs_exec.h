@@ -781,6 +781,84 @@ int fbs_lookup_compact_dev(fbs_ctx *ctx, const uint64_t *d_tables, uint32_t n_ta
 int fbs_state_lookup(fbs_ctx *ctx, const fbs_state *table_state, const uint32_t *rows, uint32_t n_planes, uint32_t len, uint32_t axis,
                      const fbs_state *index_state, size_t index_row, fbs_state *out_state, size_t out_row0);
 
+/* ---- encrypted tables: the primitives of a write by an encrypted index -------------------------------------------------------------
+ * A read takes entry i of a folded table by rotating the table by the index's amount r and extracting coefficient 0.  A WRITE adds
+ * X^{+r} U to the table, U a folded sample that holds the value in the box of entry 0 and zero elsewhere: the same rotation kernels,
+ * started from U, turned by the NEGATED amounts, with the whole rotated sample kept instead of one coefficient of it.
+ * libfbsexec.so only.
+ *
+ * WIDE BOXES.  The amount a write turns by and the amount a later read of the same entry turns by differ by the index's noise, so
+ * under the box map above (width N/p) a read can fall outside what a write covered.  A writable table gives an entry `spread` = s
+ * ordinary boxes, and its index holds s i instead of i.  With W(c) = floor((2 p c + s N) / (2 s N)) for signed c in (-N, N) (floor
+ * towards minus infinity), coefficient j < N of a table of len <= floor(p / s) entries takes
+ *     entry W(j)                 where W(j) < len,
+ *     MINUS entry 0              where W(j - N) == 0 (the half box of entry 0 below X^N),
+ *     nothing                    elsewhere.
+ * At s = 1 this is the box map, word for word; at len = 1 it is the unit box U of a write.  For s >= 2, any entries i, i' <
+ * floor(p / s) and any amounts r_w, r_r that the box rule decodes to s i and s i': reading X^{r_w} U at r_r gives 1 if i = i' and 0
+ * otherwise (tests/test_table_reference.py, exhaustively at small N) -- the index margin that admits a read admits a write at
+ * spread 2.
+ *
+ * Every entry writes nothing when it fails. */
+/* The map of a writable table, host side and pure: map_out[j], j < N, = base + W(j) stride, base | FBS_MAP_NEG or FBS_MAP_NONE as
+ * above.  spread = 1 is fbs_lookup_map.  FBS_E_INVALID for p < 2, N not a power of two in [2, 2^16], spread < 1, len == 0,
+ * len > floor(p / spread), or a source index that does not fit 31 bits. */
+int fbs_table_map(uint32_t p, uint32_t N, uint32_t spread, uint32_t len, uint32_t base, uint32_t stride, uint32_t *map_out);
+/* fbs_lookup_dev without its sample extraction: d_glwe_out [count][k+1][N] (device, 16-byte aligned) takes the WHOLE rotated sample
+ * of every index, canonical residues, X^{-r} (its table) -- or, with FBS_ROTATE_NEGATE in `flags`, X^{+r} (its table): every one of
+ * the n + 1 amounts of every row a -> (2N - a) mod 2N after the modulus switch (zero stays zero: skipped steps stay skipped).  Other
+ * flag bits: FBS_E_INVALID.  Extracting coefficient 0 of an output without the flag gives fbs_lookup_dev's ciphertext, word for
+ * word.  Needs neither a secret nor a fold key. */
+#define FBS_ROTATE_NEGATE 1u
+int fbs_rotate_dev(fbs_ctx *ctx, const uint64_t *d_tables, uint32_t n_tables, const uint32_t *d_table_of, const uint64_t *d_cts_index,
+                   size_t count, uint32_t flags, uint64_t *d_glwe_out, void *stream);
+/* The same with the indices as compact ciphertexts, as fbs_lookup_compact_dev takes them. */
+int fbs_rotate_compact_dev(fbs_ctx *ctx, const uint64_t *d_tables, uint32_t n_tables, const uint32_t *d_table_of, const uint64_t *d_words,
+                           size_t count, uint32_t bits, uint32_t flags, uint64_t *d_glwe_out, void *stream);
+/* Sample dst_of[f] of d_dst [n_dst][k+1][N] += sample f of d_src [count][k+1][N], f < count, word by word modulo q (both device,
+ * 16-byte aligned, canonical residues, and DISJOINT: overlapping arrays are FBS_E_INVALID), asynchronous on `stream`.  dst_of is
+ * HOST memory [count] and is checked: a target >= n_dst
+ * or a target named twice (two sums into one sample in one launch would race) is FBS_E_INVALID.  The upload of dst_of blocks.
+ * Needs no key. */
+int fbs_glwe_add_dev(fbs_ctx *ctx, uint64_t *d_dst, size_t n_dst, const uint32_t *dst_of, const uint64_t *d_src, size_t count, void *stream);
+
+/* RESIDENT TABLES.  An fbs_table owns folded samples in device memory that persist until freed: fbs_state_lookup folds its tables
+ * again on every call, a resident table is folded once, read by rotation and updated by rotation.  Tables are made of rows of a
+ * resident state as at fbs_state_lookup, axis 0: plane m's entries are rows rows[m len .. m len + len) of `state`, at every sample s
+ * of it -- n_planes T tables, table (m, s) being number m T + s -- or, where the state has T = 1, one SHARED table per plane.
+ * Every entry below is queued on the context's stream like the state entries and needs no secret.
+ *
+ * WRITE, mode 0 (ADD): entry[index] += value, plain integer addition that must stay below p (the caller's bound).  The value of
+ * table (m, s) is row value_rows[m] of value_state at sample s.  One key switch and modulus switch of the index; every value folded
+ * into a unit box (fbs_table_map at len = 1); the boxes turned by the negated amounts, whole samples out; the sums into the
+ * tables.  Mode 1 (SET): entry[index] = value.  First the old entry is read by the same amounts and refreshed through an ordinary
+ * bootstrap by the identity table (without it a written box would carry twice the table's noise after every set), then value -
+ * old is added as above.  `identity`: a table set of this context whose table 0 is the identity, or NULL for the context's own.
+ * A shared table is written only by an index state of T = 1: several samples writing one table in one call have no order.
+ *
+ * NOISE (params.table_write_norm2): a written table carries table + value + fold_factor + 1 in units of the blind rotation's
+ * variance, one more after a set; a read's output the table's + 1.
+ * fbs_ctx_stat: "tables_alive", "table_scratch_words" (the write scratch: two samples and a ciphertext a table).  The unit-box
+ * maps of the writes are made once by fbs_table_create, N words a table on the device; a write uploads a few words a table. */
+typedef struct fbs_table fbs_table;
+/* FBS_E_INVALID for spread < 1, len == 0, len > floor(p / spread), a row past the state; FBS_E_STATE without a fold key. */
+int fbs_table_create(fbs_ctx *ctx, const fbs_state *state, const uint32_t *rows, uint32_t n_planes, uint32_t len, uint32_t spread,
+                     fbs_table **out);
+/* Waits for the work queued on the context, then frees.  NULL is allowed.  fbs_ctx_destroy frees the tables still alive. */
+void fbs_table_free(fbs_table *table);
+/* "tables", "planes", "samples" (T, or 1: shared), "len", "spread", "writes" (the writes that succeeded), "words" (tables (k+1) N). */
+int fbs_table_stat(const fbs_table *table, const char *name, int64_t *value);
+/* Every table, [tables][k+1][N] words, to the host (for tests, and for saving a table); blocks. */
+int fbs_table_words(fbs_ctx *ctx, const fbs_table *table, uint64_t *out);
+/* Row out_row0 + m of out_state at sample s <- the entry of table (m, s) -- of plane m's shared table -- that row index_row of
+ * index_state names at sample s: fbs_state_lookup's rotation without its fold; the planes share the index's one key switch.  The
+ * index state has the tables' T (any T where they are shared); out_state has the index state's T and is another state. */
+int fbs_table_read(fbs_ctx *ctx, const fbs_table *table, const fbs_state *index_state, size_t index_row, fbs_state *out_state,
+                   size_t out_row0);
+/* value_rows [n_planes].  The tables are untouched when the call fails. */
+int fbs_table_write(fbs_ctx *ctx, fbs_table *table, const fbs_state *index_state, size_t index_row, const fbs_state *value_state,
+                    const uint32_t *value_rows, uint32_t mode, const fbs_tvset *identity);
+
 /* ---- a loaded program, one level at a time (multi-GPU hosts) -----------------
  * The two independent axes of the reference's eval loop (fbs_exec_env.py:211-223) are the gates
  * of a bootstrap level and the samples.  A host that shards the GATES of a level over several

@@ -144,6 +144,16 @@ def _load():
         "fbs_lookup_dev": (i32, [vp, vp, u32, vp, vp, sz, vp, vp]),
         "fbs_lookup_compact_dev": (i32, [vp, vp, u32, vp, vp, sz, u32, vp, vp]),
         "fbs_state_lookup": (i32, [vp, vp, vp, u32, u32, u32, vp, sz, vp, sz]),
+        "fbs_table_map": (i32, [u32, u32, u32, u32, u32, u32, vp]),
+        "fbs_rotate_dev": (i32, [vp, vp, u32, vp, vp, sz, u32, vp, vp]),
+        "fbs_rotate_compact_dev": (i32, [vp, vp, u32, vp, vp, sz, u32, u32, vp, vp]),
+        "fbs_glwe_add_dev": (i32, [vp, vp, sz, vp, vp, sz, vp]),
+        "fbs_table_create": (i32, [vp, vp, vp, u32, u32, u32, C.POINTER(vp)]),
+        "fbs_table_free": (None, [vp]),
+        "fbs_table_stat": (i32, [vp, C.c_char_p, C.POINTER(C.c_int64)]),
+        "fbs_table_words": (i32, [vp, vp, vp]),
+        "fbs_table_read": (i32, [vp, vp, vp, sz, vp, sz]),
+        "fbs_table_write": (i32, [vp, vp, vp, sz, vp, vp, u32, vp]),
         "fbs_tvset_create": (i32, [vp, vp, vp, u32, C.POINTER(vp)]),
         "fbs_tvset_destroy": (None, [vp]),
         "fbs_bootstrap_batch": (i32, [vp, vp, vp, vp, sz, vp]),
@@ -216,6 +226,8 @@ EXPORTED_SYMBOLS = (
     "fbs_fold_keygen", "fbs_fold_key_sizes", "fbs_export_fold_key", "fbs_import_fold_key", "fbs_fold_dev", "fbs_state_fold",
     "fbs_state_fold_dev", "fbs_state_unfold_dev", "fbs_debug_fold_front_dev",
     "fbs_lookup_map", "fbs_fold_mapped_dev", "fbs_lookup_dev", "fbs_lookup_compact_dev", "fbs_state_lookup",
+    "fbs_table_map", "fbs_rotate_dev", "fbs_rotate_compact_dev", "fbs_glwe_add_dev",
+    "fbs_table_create", "fbs_table_free", "fbs_table_stat", "fbs_table_words", "fbs_table_read", "fbs_table_write",
     "fbs_eval_resident_mapped", "fbs_state_sum_groups",
     "fbs_audit_rows", "fbs_audit_level_dev",
 ) + _public_native.EXPORTED_SYMBOLS
@@ -229,6 +241,18 @@ def lookup_map(p, N, length, base=0, stride=1):
     """fbs_lookup_map: the box map of a table of `length` <= p entries, uint32 [N] (host side, pure)"""
     out = np.zeros(max(1, int(N)), dtype=np.uint32)
     rc = lib.fbs_lookup_map(int(p), int(N), int(length), int(base), int(stride), out.ctypes.data)
+    if rc != 0:
+        raise FbsError(rc, lib.fbs_last_error(None).decode())
+    return out
+
+ROTATE_NEGATE = 1   # FBS_ROTATE_NEGATE of fbs_rotate_dev's flags
+
+
+def table_map(p, N, spread, length, base=0, stride=1):
+    """fbs_table_map: the map of a writable table of `length` <= p // spread entries, `spread` boxes an entry, uint32 [N] (host side,
+    pure); spread = 1 is `lookup_map`, length = 1 the unit box of a write"""
+    out = np.zeros(max(1, int(N)), dtype=np.uint32)
+    rc = lib.fbs_table_map(int(p), int(N), int(spread), int(length), int(base), int(stride), out.ctypes.data)
     if rc != 0:
         raise FbsError(rc, lib.fbs_last_error(None).decode())
     return out
@@ -621,6 +645,94 @@ class DeviceState:
         self.close()
 
 
+class DeviceTable:
+    """Resident tables (fbs_table, include/fbs_exec.h, "encrypted tables"): folded samples that stay in the context's device memory,
+    made once of rows of a `DeviceState` (`rows` [planes][len]: plane m's entry e is row rows[m][e], at every sample of the state,
+    or one shared table per plane where the state has T = 1), `spread` boxes an entry; read and written by an encrypted index.
+    `close()` frees them (also as a context manager); closing the context closes its tables."""
+    ADD, SET = 0, 1
+
+    def __init__(self, state, rows, spread=2):
+        self._h, self.ctx = None, getattr(state, "ctx", None)   # (before anything can fail: __del__ closes)
+        rows = _c(rows, np.uint32)
+        if rows.ndim != 2 or rows.size == 0:
+            raise ValueError("rows is [planes][len]")
+        if not isinstance(state, DeviceState) or state.closed:
+            raise ValueError("state is a closed state")
+        self.planes, self.len, self.spread, self.T = rows.shape[0], rows.shape[1], int(spread), state.T
+        h = C.c_void_p()
+        self.ctx._check(lib.fbs_table_create(self.ctx._h, state._h, _ptr(rows), self.planes, self.len, self.spread, C.byref(h)))
+        self._h = h
+        self.ctx._states.add(self)
+
+    @property
+    def closed(self):
+        return self._h is None or self.ctx is None or not self.ctx._h
+
+    def _live(self):
+        if self.closed:
+            raise ValueError("the table is closed")
+        return self._h
+
+    def stat(self, name):
+        """fbs_table_stat: one of tables, planes, samples, len, spread, writes, words"""
+        v = C.c_int64()
+        self.ctx._check(lib.fbs_table_stat(self._live(), name.encode(), C.byref(v)))
+        return v.value
+
+    def words(self):
+        """every table, uint64 [tables][k+1][N] (fbs_table_words; waits for the writes queued before it)"""
+        prm = self.ctx.params
+        out = np.empty((self.stat("tables"), prm.k + 1, prm.N), np.uint64)
+        self.ctx._check(lib.fbs_table_words(self.ctx._h, self._live(), _ptr(out)))
+        return out
+
+    def read(self, index, index_row, out=None, out_row0=0):
+        """Sample s of row out_row0 + m of `out` <- the entry of plane m's table that row `index_row` of `index` names at sample s
+        (fbs_table_read).  out=None: a new `DeviceState` of `planes` rows and the index's T.  Returns `out`."""
+        if not isinstance(index, DeviceState) or index.closed:
+            raise ValueError("index is a closed state")
+        made = out is None
+        if made:
+            out = DeviceState(self.ctx, self.planes, index.T)
+        try:
+            if not isinstance(out, DeviceState) or out.closed:
+                raise ValueError("out is a closed state")
+            self.ctx._check(lib.fbs_table_read(self.ctx._h, self._live(), index._h, int(index_row), out._h, int(out_row0)))
+        except Exception:
+            if made:
+                out.close()
+            raise
+        return out
+
+    def write(self, index, index_row, values, value_rows, mode=ADD, identity=None):
+        """entry[index] += value (mode ADD) or = value (SET) in every table: the value of plane m's table at sample s is row
+        value_rows[m] of `values` at sample s (fbs_table_write).  identity: a `TvSet` whose table 0 is the identity, for a SET's
+        refresh (None: the context's own)."""
+        if not isinstance(index, DeviceState) or index.closed or not isinstance(values, DeviceState) or values.closed:
+            raise ValueError("index and values are live states")
+        value_rows = _c(value_rows, np.uint32).reshape(-1)
+        if value_rows.size != self.planes:
+            raise ValueError("one value row a plane")
+        self.ctx._check(lib.fbs_table_write(self.ctx._h, self._live(), index._h, int(index_row), values._h, _ptr(value_rows), int(mode),
+                                            identity._h if identity is not None else None))
+        return self
+
+    def close(self):
+        if not self.closed and lib is not None:
+            lib.fbs_table_free(self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
 def debug_gauss(words, sigma):
     """The host's rounded Gaussian (sampler 1) of windows of six uint64 words [count][6] at standard deviation sigma -> int64 [count]
     (fbs_debug_gauss: no context, no GPU)."""
@@ -651,7 +763,7 @@ class Context(ClientContext):
         device_keys=True: the evaluation keys are made -- and a server key is expanded -- on the GPU (knob "keys_on_device",
         include/fbs_exec.h) instead of on the host and uploaded; the same words either way (`stat("keys_made_on_device")`)."""
         self.device = device
-        self._states = weakref.WeakSet()   # its DeviceStates: closed with it
+        self._states = weakref.WeakSet()   # its DeviceStates and DeviceTables: closed with it
         self._create(params, seed, device)
         if device_keys:
             self.tune(keys_on_device=1)
@@ -660,7 +772,7 @@ class Context(ClientContext):
 
     def close(self):
         if getattr(self, "_h", None) and lib is not None:      # `lib` is None while the interpreter shuts down
-            for st in list(getattr(self, "_states", ())):      # fbs_ctx_destroy frees the states still alive
+            for st in list(getattr(self, "_states", ())):      # fbs_ctx_destroy frees the states and tables still alive
                 st._h = None
             lib.fbs_ctx_destroy(self._h)
             self._h = None
@@ -755,6 +867,10 @@ class Context(ClientContext):
         """A `DeviceState` of [rows][T][D+1] ciphertexts in this context's device memory (fbs_state_create)."""
         return DeviceState(self, rows, T)
 
+    def table(self, state, rows, spread=2):
+        """A `DeviceTable` of rows of `state` ([planes][len] row numbers), `spread` boxes an entry (fbs_table_create)."""
+        return DeviceTable(state, rows, spread)
+
     # ---- compact outputs: key-switched to the small key, rounded to `bits` bits a field, bit-packed (include/fbs_exec.h) ----
     def compact_dev(self, d_cts, count, d_words, bits=None, stream=0):
         """fbs_compact_dev: `count` big-key ciphertexts at d_cts -> [count][W] words at d_words, asynchronous on `stream`; needs
@@ -843,6 +959,25 @@ class Context(ClientContext):
         """fbs_lookup_compact_dev: the same lookup with the indices as compact ciphertexts [count][W] at width `bits`"""
         self._check(lib.fbs_lookup_compact_dev(self._h, d_tables or None, int(n_tables), d_table_of or None, d_words or None, int(count),
                                                self.default_compact_bits if bits is None else int(bits), d_cts_out or None, stream or None))
+
+    # ---- encrypted tables: the rotated sample itself, and sums of samples (include/fbs_exec.h, "encrypted tables") ----
+    def rotate_dev(self, d_tables, n_tables, d_table_of, d_cts_index, count, d_glwe_out, negate=False, stream=0):
+        """fbs_rotate_dev: `lookup_dev` without the sample extraction -- the whole rotated sample of every index at d_glwe_out
+        ([count][k+1][N]); negate: by the negated amounts, X^{+r} instead of X^{-r}"""
+        self._check(lib.fbs_rotate_dev(self._h, d_tables or None, int(n_tables), d_table_of or None, d_cts_index or None, int(count),
+                                       ROTATE_NEGATE if negate else 0, d_glwe_out or None, stream or None))
+
+    def rotate_compact_dev(self, d_tables, n_tables, d_table_of, d_words, count, d_glwe_out, bits=None, negate=False, stream=0):
+        """fbs_rotate_compact_dev: the same with the indices as compact ciphertexts [count][W] at width `bits`"""
+        self._check(lib.fbs_rotate_compact_dev(self._h, d_tables or None, int(n_tables), d_table_of or None, d_words or None, int(count),
+                                               self.default_compact_bits if bits is None else int(bits), ROTATE_NEGATE if negate else 0,
+                                               d_glwe_out or None, stream or None))
+
+    def glwe_add_dev(self, d_dst, n_dst, dst_of, d_src, stream=0):
+        """fbs_glwe_add_dev: sample dst_of[f] of the `n_dst` at d_dst += sample f of d_src, modulo q; dst_of is a host array, checked
+        (in range, no target twice)"""
+        dst_of = _c(dst_of, np.uint32).reshape(-1)
+        self._check(lib.fbs_glwe_add_dev(self._h, d_dst or None, int(n_dst), _ptr(dst_of), d_src or None, dst_of.size, stream or None))
 
     def debug_fold_front_dev(self, d_cts, count, cols, tg, d_fields, stream=0):
         """fbs_debug_fold_front_dev (a test hook): the fold's front kernel alone"""

@@ -677,8 +677,14 @@ int dev_blind_rotate(fbs_ctx *ctx, const fbs_tvset *tv, const GateView &gv, cons
     BrArgs a{};
     if (start) {
         // a fused rotation leaves its whole accumulator for several tables to extract from: that has no meaning for a table that
-        // is itself the accumulator
-        if (gv.acc_rows || gv.row_words) return set_error(ctx, FBS_E_INVALID, "a rotation of an encrypted table cannot be a fused one");
+        // is itself the accumulator.  One caller wants the rotated sample itself (encrypted tables, fbs_rotate_dev): it names rows of
+        // whole accumulators and a dst_slot whose entries carry the accumulator bit, and nothing of a fused program
+        if (start->whole) {
+            if (gv.acc_rows || !gv.out_rows || !gv.dst_slot || gv.row_words != (p.k + 1) * ctx->N)
+                return set_error(ctx, FBS_E_INVALID, "a rotated sample goes into rows of (k + 1) N words");
+        } else if (gv.acc_rows || gv.row_words) {
+            return set_error(ctx, FBS_E_INVALID, "a rotation of an encrypted table cannot be a fused one");
+        }
         if (!start->d_acc0 || start->n_acc == 0) return set_error(ctx, FBS_E_INVALID, "no encrypted table to rotate");
         a.acc0 = start->d_acc0;
         a.n_acc = start->n_acc;

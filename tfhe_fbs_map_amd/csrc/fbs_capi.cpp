@@ -259,6 +259,8 @@ int fbs_ctx_stat(const fbs_ctx *ctx, const char *name, int64_t *value) try {
     else if (k == "bsk_upload_bytes") *value = ctx->bsk_upload_bytes;
     else if (k == "lookup_tables") *value = ctx->lookup_tables;
     else if (k == "lookup_scratch_words") *value = (int64_t)ctx->lookup_tables_capacity;
+    else if (k == "tables_alive") *value = (int64_t)ctx->tables.size();
+    else if (k == "table_scratch_words") *value = (int64_t)ctx->table_scratch_capacity;
     else return set_error(ctx, FBS_E_INVALID, "unknown statistic '" + k + "'");
     return FBS_OK;
 } FBS_API_CATCH(ctx)
@@ -280,7 +282,7 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     if (ctx->scratch_used) (void)hipStreamSynchronize(ctx->scratch_stream);
     for (void *p : {(void *)ctx->d_bsk_hat, (void *)ctx->d_bsk_hat_small, (void *)ctx->d_ksk, (void *)ctx->d_ksk_f, (void *)ctx->d_ks_corr, (void *)ctx->d_ks_a, (void *)ctx->d_ks_b, (void *)ctx->d_ks_c, (void *)ctx->d_tw_fwd, (void *)ctx->d_tw_inv, (void *)ctx->d_psi_pow, (void *)ctx->d_ms, (void *)ctx->d_ms_eps, (void *)ctx->d_ms_body, (void *)ctx->d_acc, (void *)ctx->d_stage_in, (void *)ctx->d_stage_out, (void *)ctx->d_stage_ids,
                     (void *)ctx->d_idx, (void *)ctx->d_wires, (void *)ctx->d_sk_bits, (void *)ctx->d_sk_lwe_bits, (void *)ctx->d_io_msgs,
-                    (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc, (void *)ctx->d_pub, (void *)ctx->d_lookup_tables, (void *)ctx->d_lookup_idx, (void *)ctx->d_audit_err, (void *)ctx->d_audit_stats})
+                    (void *)ctx->d_compact, (void *)ctx->d_links, (void *)ctx->d_pack_fields, (void *)ctx->d_pack_acc, (void *)ctx->d_pub, (void *)ctx->d_lookup_tables, (void *)ctx->d_lookup_idx, (void *)ctx->d_acc_flags, (void *)ctx->d_add_idx, (void *)ctx->d_table_scratch, (void *)ctx->d_audit_err, (void *)ctx->d_audit_stats})
         if (p) (void)hipFree(p);
     for (auto &key : ctx->gadget_dev)
         for (void *p : {(void *)key.d_key, (void *)key.d_out})
@@ -288,6 +290,11 @@ void fbs_ctx_destroy(fbs_ctx *ctx) try {
     for (fbs_state *st : ctx->states) {   // the states still alive
         (void)hipFree(st->d);
         delete st;
+    }
+    for (fbs_table *tab : ctx->tables) {   // ... and the tables
+        (void)hipFree(tab->d);
+        (void)hipFree(tab->d_unit_maps);
+        delete tab;
     }
     if (ctx->inputs_event) (void)hipEventDestroy(ctx->inputs_event);
     fbs_tvset_destroy(ctx->tv_identity);
@@ -1540,6 +1547,339 @@ int fbs_state_lookup(fbs_ctx *ctx, const fbs_state *table_state, const uint32_t 
         if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) return rc;
         return dev_blind_rotate(ctx, nullptr, gv, ctx->d_ms, s, &start);
     });
+} FBS_API_CATCH(ctx)
+
+// ---- encrypted tables (include/fbs_exec.h): the wide-box map, the rotation that returns the rotated sample, the sum of samples ------
+int fbs_table_map(uint32_t p, uint32_t N, uint32_t spread, uint32_t len, uint32_t base, uint32_t stride, uint32_t *map_out) try {
+    return host_table_map(p, N, spread, len, base, stride, map_out);
+} FBS_API_CATCH(nullptr)
+
+// the dst_slot array of a rotation that leaves whole accumulators: the accumulator bit for every bootstrap of a pass, written when
+// the array grows and never again
+static int ensure_acc_flags(fbs_ctx *ctx, size_t count) {
+    if (count <= ctx->acc_flags_capacity) return FBS_OK;
+    if (int rc = grow(ctx, ctx->d_acc_flags, ctx->acc_flags_capacity, count, 4, false)) return rc;
+    FBS_HIP(ctx, hipMemsetD32(ctx->d_acc_flags, (int)0x80000000u, count));
+    FBS_HIP(ctx, hipDeviceSynchronize());
+    return FBS_OK;
+}
+
+// what both rotations check once the lookups' checks are through: the flags and the output samples
+static int check_rotate_out(const fbs_ctx *ctx, uint32_t flags, const uint64_t *d_glwe_out, size_t count) {
+    if (flags & ~1u) return set_error(ctx, FBS_E_INVALID, "unknown flag: bit 0 (negate the amounts) is the only one");
+    if (count && !d_glwe_out) return set_error(ctx, FBS_E_INVALID, "null argument");
+    if ((uintptr_t)d_glwe_out & 15u) return set_error(ctx, FBS_E_INVALID, "rotated samples are GLWE samples: d_glwe_out must be 16-byte aligned");
+    if (count > SIZE_MAX / 8 / ((size_t)(ctx->p.k + 1) * ctx->N)) return set_error(ctx, FBS_E_INVALID, "count * (k + 1) N words overflow");
+    return FBS_OK;
+}
+
+// rows [f0, f0 + rows) of a rotation call once their amounts are in d_ms: negated where asked, then turned, whole accumulators out
+static int rotate_rows(fbs_ctx *ctx, const BrStart &tables, size_t f0, size_t rows, uint32_t flags, uint64_t *d_glwe_out, hipStream_t s) {
+    const uint32_t acc_words = (ctx->p.k + 1) * ctx->N;
+    if ((flags & 1u))
+        if (int rc = dev_ms_negate(ctx, ctx->d_ms, rows, s)) return rc;
+    GateView gv = batch_view(nullptr, nullptr, nullptr, rows);
+    gv.out_rows = d_glwe_out + f0 * acc_words;
+    gv.row_words = acc_words;
+    gv.dst_slot = ctx->d_acc_flags;
+    BrStart start = tables;
+    start.first = f0;
+    start.whole = true;
+    return dev_blind_rotate(ctx, nullptr, gv, ctx->d_ms, s, &start);
+}
+
+// (needs neither a secret nor a fold key)
+int fbs_rotate_dev(fbs_ctx *ctx, const uint64_t *d_tables, uint32_t n_tables, const uint32_t *d_table_of, const uint64_t *d_cts_index,
+                   size_t count, uint32_t flags, uint64_t *d_glwe_out, void *stream) try {
+    if (int rc = io_prologue(ctx, d_cts_index, d_glwe_out, count, IO_CT_WORDS, nullptr)) return rc;
+    if (int rc = check_lookup_tables(ctx, d_tables, n_tables, count)) return rc;
+    if (int rc = check_rotate_out(ctx, flags, d_glwe_out, count)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure_ms(ctx, count)) return rc;
+    if (int rc = ensure_acc_flags(ctx, count)) return rc;
+    const GateView gv = batch_view(d_cts_index, nullptr, nullptr, count);
+    hipStream_t s = pick(ctx, stream);
+    return scratch_section(ctx, s, [&]() -> int {
+        if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) return rc;
+        return rotate_rows(ctx, BrStart{d_tables, n_tables, d_table_of, 0}, 0, count, flags, d_glwe_out, s);
+    });
+} FBS_API_CATCH(ctx)
+
+// fbs_lookup_compact_dev's passes and unpack, the rotated sample out
+int fbs_rotate_compact_dev(fbs_ctx *ctx, const uint64_t *d_tables, uint32_t n_tables, const uint32_t *d_table_of, const uint64_t *d_words,
+                           size_t count, uint32_t bits, uint32_t flags, uint64_t *d_glwe_out, void *stream) try {
+    if (int rc = io_prologue(ctx, d_words, d_glwe_out, count, IO_CT_WORDS, nullptr)) return rc;
+    if (int rc = check_bits(ctx, bits)) return rc;
+    if (int rc = check_compact_words(ctx, count, bits)) return rc;
+    if (int rc = check_lookup_tables(ctx, d_tables, n_tables, count)) return rc;
+    if (int rc = check_rotate_out(ctx, flags, d_glwe_out, count)) return rc;
+    if (count == 0) return FBS_OK;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure_acc_flags(ctx, ms_pass_size(ctx, count))) return rc;
+    const size_t W = compact_words(ctx->p.n, bits);
+    hipStream_t s = pick(ctx, stream);
+    return ms_passes(ctx, count, s, [&](size_t f0, size_t rows) {
+        if (int rc = dev_compact_unpack(ctx, d_words + f0 * W, rows, bits, ctx->d_ms, s)) return rc;
+        return rotate_rows(ctx, BrStart{d_tables, n_tables, d_table_of, 0}, f0, rows, flags, d_glwe_out, s);
+    });
+} FBS_API_CATCH(ctx)
+
+// dst_of is host memory: checked here, then uploaded (which blocks, as the index arrays of fbs_state_lookup do)
+int fbs_glwe_add_dev(fbs_ctx *ctx, uint64_t *d_dst, size_t n_dst, const uint32_t *dst_of, const uint64_t *d_src, size_t count, void *stream) try {
+    if (!ctx || (count && (!d_dst || !dst_of || !d_src))) return FBS_E_INVALID;
+    if (((uintptr_t)d_dst | (uintptr_t)d_src) & 15u) return set_error(ctx, FBS_E_INVALID, "GLWE samples: d_dst and d_src must be 16-byte aligned");
+    if (count > n_dst) return set_error(ctx, FBS_E_INVALID, "more sources than targets: a target would be written twice");
+    if (n_dst > 0x7FFFFFFFull) return set_error(ctx, FBS_E_INVALID, "batch too large");
+    if (count == 0) return FBS_OK;
+    {   // the kernel reads a source word and writes a target word in no order between samples: the two arrays are disjoint
+        const size_t acc_bytes = (size_t)(ctx->p.k + 1) * ctx->N * 8;
+        const uintptr_t d0 = (uintptr_t)d_dst, d1 = d0 + n_dst * acc_bytes, s0 = (uintptr_t)d_src, s1 = s0 + count * acc_bytes;
+        if (d0 < s1 && s0 < d1) return set_error(ctx, FBS_E_INVALID, "d_dst and d_src overlap");
+    }
+    for (size_t f = 0; f < count; f++)
+        if (dst_of[f] >= n_dst)
+            return set_error(ctx, FBS_E_INVALID, "target " + std::to_string(dst_of[f]) + " of source " + std::to_string(f) + " is past the " + std::to_string(n_dst) + " samples");
+    std::vector<uint32_t> sorted(dst_of, dst_of + count);
+    std::sort(sorted.begin(), sorted.end());
+    const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+    if (twice != sorted.end()) return set_error(ctx, FBS_E_INVALID, "target " + std::to_string(*twice) + " is written twice in one call");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = grow(ctx, ctx->d_add_idx, ctx->add_idx_capacity, count, 4, false)) return rc;
+    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));   // (an earlier call may still read the targets)
+    FBS_HIP(ctx, hipMemcpy(ctx->d_add_idx, dst_of, count * 4, hipMemcpyHostToDevice));
+    hipStream_t s = pick(ctx, stream);
+    return scratch_section(ctx, s, [&]() -> int { return dev_glwe_add(ctx, d_dst, d_src, ctx->d_add_idx, count, s); });
+} FBS_API_CATCH(ctx)
+
+// ---- resident tables: folded samples that persist, read by rotation and written by rotation ---------------------------------------
+static bool table_of_ctx(const fbs_ctx *ctx, const fbs_table *t) {   // (by address, as state_of)
+    return t && std::find(ctx->tables.begin(), ctx->tables.end(), t) != ctx->tables.end();
+}
+
+// the maps of n_tab tables from one wide-box layout `box` (entry numbers: host_table_map at base 0, stride 1): table t's entry x
+// is source src(t, x)
+static void table_maps(uint32_t *maps, const std::vector<uint32_t> &box, size_t n_tab, const std::function<uint32_t(size_t, uint32_t)> &src) {
+    const size_t N = box.size();
+    for (size_t t = 0; t < n_tab; t++)
+        for (size_t j = 0; j < N; j++)
+            maps[t * N + j] = box[j] == FOLD_MAP_NONE ? FOLD_MAP_NONE : src(t, box[j] & ~FOLD_MAP_NEG) | (box[j] & FOLD_MAP_NEG);
+}
+
+// the index arrays of a table call, uploaded once (which blocks: an earlier call may still read them)
+static int upload_table_idx(fbs_ctx *ctx, const std::vector<uint32_t> &idx) {
+    if (int rc = grow(ctx, ctx->d_lookup_idx, ctx->lookup_idx_capacity, idx.size(), 4, false)) return rc;
+    if (ctx->scratch_used) FBS_HIP(ctx, hipStreamSynchronize(ctx->scratch_stream));
+    FBS_HIP(ctx, hipMemcpy(ctx->d_lookup_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+    return FBS_OK;
+}
+
+int fbs_table_create(fbs_ctx *ctx, const fbs_state *state, const uint32_t *rows, uint32_t n_planes, uint32_t len, uint32_t spread,
+                     fbs_table **out) try {
+    if (!ctx || !out) return FBS_E_INVALID;
+    *out = nullptr;
+    if (!state_of(ctx, state)) return set_error(ctx, FBS_E_INVALID, "not a live state of this context");
+    if (!rows || n_planes == 0) return set_error(ctx, FBS_E_INVALID, "a table set has at least one plane");
+    const uint32_t N = ctx->N, p = ctx->p.p_msg, k1 = ctx->p.k + 1;
+    if (spread < 1) return set_error(ctx, FBS_E_INVALID, "an entry takes at least one box");
+    if (len == 0) return set_error(ctx, FBS_E_INVALID, "a table has at least one entry");
+    if (len > p / spread) return set_error(ctx, FBS_E_INVALID, "a table has at most floor(p / spread) entries");
+    const size_t T = state->T, n_tab = (size_t)n_planes * T, n_src = state->rows * T;
+    for (size_t i = 0; i < (size_t)n_planes * len; i++)
+        if (rows[i] >= state->rows) return set_error(ctx, FBS_E_INVALID, "rows past the end of the state");
+    if (n_src >= FOLD_MAP_NEG || n_tab > 0x7FFFFFFFull / N) return set_error(ctx, FBS_E_INVALID, "batch too large");
+    if (int rc = gadget_prologue(ctx, GK_FOLD, n_tab * N, 0)) return rc;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> box(N), idx(n_tab * N);
+    if (int rc = host_table_map(p, N, spread, len, 0, 1, box.data())) return rc;
+    table_maps(idx.data(), box, n_tab, [&](size_t t, uint32_t x) { return (uint32_t)((size_t)rows[t / T * len + x] * T + t % T); });
+    std::unique_ptr<fbs_table> tab(new fbs_table);
+    ctx->tables.reserve(ctx->tables.size() + 1);
+    const size_t bytes = n_tab * k1 * N * 8;
+    const hipError_t e = hipMalloc(&tab->d, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return set_error(ctx, FBS_E_DEVICE, "tables of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e));
+    }
+    int rc = upload_table_idx(ctx, idx);
+    if (rc == FBS_OK) rc = gadget_passes(ctx, GK_FOLD, state->d, n_tab * N, 0, tab->d, nullptr, ctx->stream, ctx->d_lookup_idx, n_src);
+    if (rc == FBS_OK) {   // the unit boxes of the writes to come, made and uploaded once: unit t holds ciphertext t of a write's scratch
+        if ((rc = host_table_map(p, N, spread, 1, 0, 1, box.data())) == FBS_OK) {
+            table_maps(idx.data(), box, n_tab, [](size_t t, uint32_t) { return (uint32_t)t; });
+            if (hipMalloc(&tab->d_unit_maps, idx.size() * 4) != hipSuccess ||
+                hipMemcpy(tab->d_unit_maps, idx.data(), idx.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+                (void)hipGetLastError();
+                rc = set_error(ctx, FBS_E_DEVICE, "the unit-box maps of " + std::to_string(idx.size() * 4) + " bytes could not be placed");
+            }
+        }
+    }
+    if (rc != FBS_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(tab->d);
+        if (tab->d_unit_maps) (void)hipFree(tab->d_unit_maps);
+        return rc;
+    }
+    tab->ctx = ctx, tab->n_tab = n_tab, tab->T = T, tab->n_planes = n_planes, tab->len = len, tab->spread = spread;
+    ctx->tables.push_back(tab.get());
+    *out = tab.release();
+    return FBS_OK;
+} FBS_API_CATCH(ctx)
+
+void fbs_table_free(fbs_table *table) try {
+    if (!table) return;
+    fbs_ctx *ctx = table->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);   // queued reads and writes may still use it
+    if (ctx->scratch_used) (void)hipStreamSynchronize(ctx->scratch_stream);
+    ctx->tables.erase(std::remove(ctx->tables.begin(), ctx->tables.end(), table), ctx->tables.end());
+    (void)hipFree(table->d);
+    (void)hipFree(table->d_unit_maps);
+    delete table;
+} catch (...) {
+}
+
+int fbs_table_stat(const fbs_table *table, const char *name, int64_t *value) try {
+    if (!table || !name || !value) return FBS_E_INVALID;
+    const std::string k(name);
+    if (k == "tables") *value = (int64_t)table->n_tab;
+    else if (k == "planes") *value = table->n_planes;
+    else if (k == "samples") *value = (int64_t)table->T;
+    else if (k == "len") *value = table->len;
+    else if (k == "spread") *value = table->spread;
+    else if (k == "writes") *value = table->writes;
+    else if (k == "words") *value = (int64_t)(table->n_tab * (table->ctx->p.k + 1) * table->ctx->N);
+    else return set_error(table->ctx, FBS_E_INVALID, "unknown statistic '" + k + "'");
+    return FBS_OK;
+} FBS_API_CATCH(table ? table->ctx : nullptr)
+
+int fbs_table_words(fbs_ctx *ctx, const fbs_table *table, uint64_t *out) try {
+    if (!ctx || !out) return FBS_E_INVALID;
+    if (!table_of_ctx(ctx, table)) return set_error(ctx, FBS_E_INVALID, "not a live table of this context");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    FBS_HIP(ctx, hipMemcpyAsync(out, table->d, table->n_tab * (ctx->p.k + 1) * ctx->N * 8, hipMemcpyDeviceToHost, ctx->stream));
+    return sync_stream(ctx, ctx->stream);
+} FBS_API_CATCH(ctx)
+
+// what a read and a write check of the index: its state and row, and that its samples are the table's (or, shared, any -- a write: one)
+static int check_table_index(const fbs_ctx *ctx, const fbs_table *table, const fbs_state *index_state, size_t index_row, bool writing) {
+    if (!table_of_ctx(ctx, table)) return set_error(ctx, FBS_E_INVALID, "not a live table of this context");
+    if (!state_of(ctx, index_state)) return set_error(ctx, FBS_E_INVALID, "not a live state of this context");
+    if (index_row >= index_state->rows) return set_error(ctx, FBS_E_INVALID, "rows past the end of the state");
+    if (table->T != 1 && index_state->T != table->T) return set_error(ctx, FBS_E_INVALID, "the index state has not the tables' samples");
+    if (writing && table->T == 1 && index_state->T != 1)
+        return set_error(ctx, FBS_E_INVALID, "a shared table is written by an index state of one sample: several samples writing one table in one call have no order");
+    if ((size_t)table->n_planes * index_state->T > 0x7FFFFFFFull) return set_error(ctx, FBS_E_INVALID, "batch too large");
+    return FBS_OK;
+}
+
+// the view in which the planes of an index share its one key switch: bootstrap f = m T + s, source_of all zero
+static GateView table_view(const fbs_ctx *ctx, const fbs_table *table, const fbs_state *index_state, size_t index_row, const uint32_t *d_zeros) {
+    const size_t T = index_state->T;
+    GateView gv{};
+    gv.in_base = index_state->d + index_row * T * (ctx->D + 1);
+    gv.source_of = d_zeros;
+    gv.T = T, gv.s_count = T, gv.count = (size_t)table->n_planes * T, gv.ks_count = T, gv.n_gates = table->n_planes;
+    return gv;
+}
+
+// fbs_state_lookup's rotation without its fold
+int fbs_table_read(fbs_ctx *ctx, const fbs_table *table, const fbs_state *index_state, size_t index_row, fbs_state *out_state,
+                   size_t out_row0) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (int rc = check_table_index(ctx, table, index_state, index_row, false)) return rc;
+    if (!state_of(ctx, out_state)) return set_error(ctx, FBS_E_INVALID, "not a live state of this context");
+    if (out_state == index_state) return set_error(ctx, FBS_E_INVALID, "the output state must be another state");
+    const size_t T = index_state->T, count = (size_t)table->n_planes * T;
+    if (out_state->T != T || out_row0 > out_state->rows || table->n_planes > out_state->rows - out_row0)
+        return set_error(ctx, FBS_E_INVALID, "the output state holds n_planes rows of the index state's samples from out_row0 on");
+    if (!ctx->have_keys) return set_error(ctx, FBS_E_STATE, "fbs_keygen has not run");
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> idx(count + table->n_planes, 0u);   // which table a bootstrap reads, then the planes' shared source
+    for (size_t f = 0; f < count; f++) idx[f] = (uint32_t)(table->T == 1 ? f / T : f);
+    if (int rc = ensure_ms(ctx, T)) return rc;
+    if (int rc = upload_table_idx(ctx, idx)) return rc;
+    GateView gv = table_view(ctx, table, index_state, index_row, ctx->d_lookup_idx + count);
+    gv.out_base = out_state->d + out_row0 * T * (ctx->D + 1);
+    const BrStart start{table->d, (uint32_t)table->n_tab, ctx->d_lookup_idx, 0};
+    hipStream_t s = ctx->stream;
+    return scratch_section(ctx, s, [&]() -> int {
+        if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, ctx->p.log_n_poly + 1, s)) return rc;
+        return dev_blind_rotate(ctx, nullptr, gv, ctx->d_ms, s, &start);
+    });
+} FBS_API_CATCH(ctx)
+
+// ADD: the values folded into unit boxes, turned by the index's negated amounts, added.  SET: first the old entries read by the same
+// amounts, refreshed, and taken off the values; then the add steps on the differences.  Bootstrap f = m T + s writes table f.
+int fbs_table_write(fbs_ctx *ctx, fbs_table *table, const fbs_state *index_state, size_t index_row, const fbs_state *value_state,
+                    const uint32_t *value_rows, uint32_t mode, const fbs_tvset *identity) try {
+    if (!ctx) return FBS_E_INVALID;
+    if (mode > 1) return set_error(ctx, FBS_E_INVALID, "mode is 0 (add) or 1 (set)");
+    if (int rc = check_table_index(ctx, table, index_state, index_row, true)) return rc;
+    if (!state_of(ctx, value_state)) return set_error(ctx, FBS_E_INVALID, "not a live state of this context");
+    if (!value_rows) return set_error(ctx, FBS_E_INVALID, "null argument");
+    const size_t T = index_state->T, count = table->n_tab, n_planes = table->n_planes;
+    const uint32_t N = ctx->N, acc_words = (ctx->p.k + 1) * N;
+    const size_t ctw = ctx->D + 1;
+    if (value_state->T != T) return set_error(ctx, FBS_E_INVALID, "the value state has not the index state's samples");
+    for (size_t m = 0; m < n_planes; m++)
+        if (value_rows[m] >= value_state->rows) return set_error(ctx, FBS_E_INVALID, "rows past the end of the state");
+    const size_t n_values = value_state->rows * T;
+    if (n_values >= FOLD_MAP_NEG) return set_error(ctx, FBS_E_INVALID, "batch too large");
+    if (int rc = gadget_prologue(ctx, GK_FOLD, count * N, 0)) return rc;
+    FBS_HIP(ctx, hipSetDevice(ctx->device));
+    fbs_tvset *tv = nullptr;
+    if (mode == 1) {
+        if (identity && identity->ctx != ctx) return set_error(ctx, FBS_E_INVALID, "test-vector set belongs to another context");
+        if (!identity)
+            if (int rc = identity_tv(ctx, &tv)) return rc;
+    }
+    const fbs_tvset *refresh = identity ? identity : tv;
+    // the index arrays of the call, a few words a table: the value of table f [count], 0 .. count - 1 [count], zeros [n_planes].  The
+    // unit-box maps, N words a table, are the table object's own (made once by fbs_table_create): unit f folds ciphertext f of the
+    // scratch, where an add gathers its values and a set leaves its differences, in the tables' order
+    std::vector<uint32_t> idx(2 * count + n_planes, 0u);
+    uint32_t *value_of = idx.data(), *ident = value_of + count;
+    for (size_t f = 0; f < count; f++) value_of[f] = (uint32_t)((size_t)value_rows[f / T] * T + f % T), ident[f] = (uint32_t)f;
+    const size_t units = 0, turned = count * acc_words, olds = 2 * count * acc_words;   // offsets into the scratch, in words
+    if (int rc = grow(ctx, ctx->d_table_scratch, ctx->table_scratch_capacity, olds + count * ctw, 8, true)) return rc;
+    if (int rc = ensure_ms(ctx, mode == 1 ? std::max(T, count) : T)) return rc;
+    if (int rc = ensure_acc_flags(ctx, n_planes)) return rc;
+    if (int rc = upload_table_idx(ctx, idx)) return rc;
+    const uint32_t *d_value_of = ctx->d_lookup_idx, *d_ident = d_value_of + count, *d_zeros = d_ident + count;
+    uint64_t *d_units = ctx->d_table_scratch + units, *d_turned = ctx->d_table_scratch + turned, *d_old = ctx->d_table_scratch + olds;
+    const GateView gv = table_view(ctx, table, index_state, index_row, d_zeros);
+    const uint32_t log2_mod = ctx->p.log_n_poly + 1;
+    hipStream_t s = ctx->stream;
+    {
+        int rc = scratch_section(ctx, s, [&]() -> int {
+            if (mode == 0) return dev_ct_sub(ctx, value_state->d, d_value_of, nullptr, d_old, count, s);   // (nothing taken off: a gather)
+            if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, log2_mod, s)) return rc;
+            GateView read = gv;
+            read.out_rows = d_old;   // (rows of D + 1 words: table f's old entry is ciphertext f)
+            const BrStart start{table->d, (uint32_t)count, nullptr, 0};
+            if (int rc = dev_blind_rotate(ctx, nullptr, read, ctx->d_ms, s, &start)) return rc;
+            // refreshed: a written box would otherwise carry the table's noise twice over after every set
+            if (int rc = dev_keyswitch(ctx, batch_view(d_old, nullptr, nullptr, count), ctx->d_ms, log2_mod, s)) return rc;
+            if (int rc = dev_blind_rotate(ctx, refresh, batch_view(nullptr, d_old, nullptr, count), ctx->d_ms, s)) return rc;
+            return dev_ct_sub(ctx, value_state->d, d_value_of, d_old, d_old, count, s);
+        });
+        if (rc != FBS_OK) return rc;
+    }
+    if (int rc = gadget_passes(ctx, GK_FOLD, d_old, count * N, 0, d_units, nullptr, s, table->d_unit_maps, count)) return rc;
+    int rc = scratch_section(ctx, s, [&]() -> int {
+        if (int rc = dev_keyswitch(ctx, gv, ctx->d_ms, log2_mod, s)) return rc;   // (a set's refresh has used the amounts' rows)
+        if (int rc = dev_ms_negate(ctx, ctx->d_ms, T, s)) return rc;
+        GateView turn = gv;
+        turn.out_rows = d_turned;
+        turn.row_words = acc_words;
+        turn.dst_slot = ctx->d_acc_flags;
+        BrStart start{d_units, (uint32_t)count, nullptr, 0};
+        start.whole = true;
+        if (int rc = dev_blind_rotate(ctx, nullptr, turn, ctx->d_ms, s, &start)) return rc;
+        return dev_glwe_add(ctx, table->d, d_turned, d_ident, count, s);
+    });
+    if (rc == FBS_OK) table->writes++;
+    return rc;
 } FBS_API_CATCH(ctx)
 
 int fbs_state_fold(fbs_ctx *ctx, const fbs_state *st, size_t row0, size_t rows, uint64_t *out) try {

@@ -559,6 +559,26 @@ int host_lookup_map(uint32_t p, uint32_t N, uint32_t len, uint32_t base, uint32_
     return FBS_OK;
 }
 
+// The map of a WRITABLE table (fbs_table_map of include/fbs_exec.h, "encrypted tables"): an entry takes `spread` ordinary boxes, the
+// wide slot of a signed position c in (-N, N) being W(c) = floor((2 p c + s N) / (2 s N)).  Coefficient j takes source
+// base + W(j) stride for W(j) < len, source `base` negated where W(j - N) == 0 (2 p (N - j) <= s N: the half box of entry 0 below
+// X^N), nothing elsewhere.  The two cases never meet: below X^N, W(j) >= floor(p / s) >= len.  spread = 1 is host_lookup_map.
+int host_table_map(uint32_t p, uint32_t N, uint32_t spread, uint32_t len, uint32_t base, uint32_t stride, uint32_t *map_out) {
+    if (!map_out) return FBS_E_INVALID;
+    if (p < 2) return set_error(nullptr, FBS_E_INVALID, "a table needs p >= 2");
+    if (N < 2 || N > (1u << 16) || (N & (N - 1))) return set_error(nullptr, FBS_E_INVALID, "N must be a power of two in [2, 2^16]");
+    if (spread < 1) return set_error(nullptr, FBS_E_INVALID, "an entry takes at least one box");
+    if (len == 0) return set_error(nullptr, FBS_E_INVALID, "a table has at least one entry");
+    if (len > p / spread) return set_error(nullptr, FBS_E_INVALID, "a table has at most floor(p / spread) entries");
+    if ((uint64_t)base + (uint64_t)(len - 1) * stride >= FOLD_MAP_NEG) return set_error(nullptr, FBS_E_INVALID, "a source index must stay below 2^31");
+    const uint64_t sN = (uint64_t)spread * N;
+    for (uint32_t j = 0; j < N; j++) {
+        const uint64_t w = ((uint64_t)j * 2 * p + sN) / (2 * sN);
+        map_out[j] = w < len ? base + (uint32_t)w * stride : (uint64_t)(N - j) * 2 * p <= sN ? base | FOLD_MAP_NEG : FOLD_MAP_NONE;
+    }
+    return FBS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Several tables on one blind rotation (multi-value bootstrap; Carpov, Izabachene, Mollimard, CT-RSA 2019).  The test
 // vector above is delta_half * G(X) with G_j = +-(2 f - c), and (1 + X + .. + X^(N-1)) (1 - X) = 2 in Z[X]/(X^N + 1), so

@@ -292,6 +292,17 @@ struct fbs_ctx : fbs::HostState {
     uint32_t *d_lookup_idx = nullptr;
     size_t lookup_idx_capacity = 0;      // in words
     int64_t lookup_tables = 0;           // tables the last fbs_state_lookup folded (fbs_ctx_stat)
+    // encrypted tables: the accumulator bit for every bootstrap of a pass of fbs_rotate_dev (a dst_slot array, filled when it
+    // grows), and the targets of an fbs_glwe_add_dev call
+    uint32_t *d_acc_flags = nullptr;
+    size_t acc_flags_capacity = 0;       // in words
+    uint32_t *d_add_idx = nullptr;
+    size_t add_idx_capacity = 0;         // in words
+    // resident tables: the tables alive (fbs_ctx_destroy frees them), and the scratch of a write, grown like d_lookup_tables -- the
+    // unit boxes and the turned samples, (k + 1) N words each, and the refreshed old entries of a set, D + 1 words each, a table
+    std::vector<fbs_table *> tables;
+    uint64_t *d_table_scratch = nullptr;
+    size_t table_scratch_capacity = 0;   // in words
     uint64_t *d_pub = nullptr;       // staging of fbs_state_put_public's GLWE samples
     size_t pub_capacity = 0;         // in words
     fbs_tvset *tv_identity = nullptr;   // the identity table [0, 1, .., p - 1], made on first use: what refreshes a compact input
@@ -325,6 +336,17 @@ struct fbs_state {
     fbs_ctx *ctx = nullptr;
     uint64_t *d = nullptr;
     size_t rows = 0, T = 0;
+};
+
+// context-owned folded tables [n_tab][k + 1][N] that stay where they are until freed: table (m, s) of plane m and sample s is
+// number m T + s, or m where one table per plane is shared by every sample (T = 1)
+struct fbs_table {
+    fbs_ctx *ctx = nullptr;
+    uint64_t *d = nullptr;
+    uint32_t *d_unit_maps = nullptr;  // [n_tab][N]: the unit-box map of every table's writes, unit t taking ciphertext t of the write scratch
+    size_t n_tab = 0, T = 0;          // T: samples a plane has tables for (1: shared)
+    uint32_t n_planes = 0, len = 0, spread = 0;
+    int64_t writes = 0;
 };
 
 struct fbs_tvset {
@@ -474,6 +496,8 @@ void host_decrypt_packed(const fbs_ctx *ctx, const uint64_t *words, size_t count
 int host_build_tv(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint64_t *tv, uint64_t *post_add);
 // the same box rule as the map of a mapped fold: what fbs_lookup_map answers (map_out [N])
 int host_lookup_map(uint32_t p, uint32_t N, uint32_t len, uint32_t base, uint32_t stride, uint32_t *map_out);
+// the map of a writable table, `spread` boxes an entry: what fbs_table_map answers (map_out [N]); spread = 1 is host_lookup_map
+int host_table_map(uint32_t p, uint32_t N, uint32_t spread, uint32_t len, uint32_t base, uint32_t stride, uint32_t *map_out);
 // D_F with TV_F = TV_0 * D_F as (position, value) pairs of its non-zero coefficients, at most p + 1 of them (`pos`, `val`
 // sized for that); *norm2 = |D_F|^2, *g_norm2 = |G_F|^2 (TV_F = delta_half G_F), *abs_sum = sum |d|.  Errors as host_build_tv.
 int host_build_tv_diff(const fbs_ctx *ctx, const int32_t *table, uint32_t len, uint32_t *pos, int32_t *val, uint32_t *count,
@@ -516,6 +540,9 @@ struct BrStart {
     uint32_t n_acc;
     const uint32_t *d_acc_of;   // [first + gv.count] device memory, or null: bootstrap i starts from sample first + i
     size_t first;               // the pass's first bootstrap, counted within the entry's call (an entry may run in passes)
+    // encrypted tables (fbs_rotate_dev): the rotated sample itself is wanted, not an entry of it -- the view names out_rows of
+    // (k + 1) N words and a dst_slot whose entries carry the accumulator bit, and every bootstrap leaves its whole accumulator there
+    bool whole = false;
 };
 int dev_blind_rotate(fbs_ctx *ctx, const fbs_tvset *tv, const GateView &gv, const uint32_t *d_ms, hipStream_t stream,
                      const BrStart *start = nullptr);
@@ -579,6 +606,15 @@ int dev_pack_accumulate(const fbs_ctx *ctx, const PackArgs &a, size_t samples, h
 int dev_fold(fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint64_t *d_glwe, hipStream_t stream, const uint32_t *d_map = nullptr,
              size_t n_src = 0);
 int dev_fold_front(const fbs_ctx *ctx, const uint64_t *d_cts, size_t count, uint32_t cols, uint32_t tg, uint32_t *d_fields, hipStream_t stream);
+
+// encrypted tables (fbs_table.hip).  dev_ms_negate: every amount of `rows` modulus-switched rows [n + 1] -> (2N - a) mod 2N.
+// dev_glwe_add: sample d_dst_of[f] of d_dst += sample f of d_src mod q, f < count, (k + 1) N words a sample; d_dst_of (device) holds
+// what the host checked: targets in range, none twice
+int dev_ms_negate(const fbs_ctx *ctx, uint32_t *d_ms, size_t rows, hipStream_t stream);
+int dev_glwe_add(const fbs_ctx *ctx, uint64_t *d_dst, const uint64_t *d_src, const uint32_t *d_dst_of, size_t count, hipStream_t stream);
+// dev_ct_sub: ciphertext f of d_out = ciphertext d_a_of[f] of d_a - ciphertext f of d_b mod q, f < count, D + 1 words each (d_out may
+// be d_b; d_b null: nothing is taken off, a gather); d_a_of (device) holds what the host checked
+int dev_ct_sub(const fbs_ctx *ctx, const uint64_t *d_a, const uint32_t *d_a_of, const uint64_t *d_b, uint64_t *d_out, size_t count, hipStream_t stream);
 
 // audited evaluation (fbs_audit.hip): errors of the big-key ciphertexts in slots d_row_slot[rows], samples [s_begin, s_begin + s_count),
 // against d_expected [rows][s_count] -> d_err [rows][s_count] (wire units); of the switched fields d_ms [rows * s_count][n + 1] at

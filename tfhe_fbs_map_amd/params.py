@@ -298,6 +298,25 @@ def lookup_index_margin(prm: Params, index_out_norm2: float = 1.0) -> float:
     return refresh_margin(prm, None, index_out_norm2)
 
 
+# ---- encrypted tables (include/fbs_exec.h, "encrypted tables") ------------------------------------------------------------------------
+TABLE_ADD, TABLE_SET = 0, 1
+
+
+def table_write_norm2(table_norm2: float, value_norm2: float, fold_factor: float, mode: int = TABLE_ADD) -> float:
+    """What a resident table carries after a write, in units of one blind rotation's output variance: what it carried, the value's own
+    noise, the fold that laid the value out as a unit box and the rotation that turned it; a set adds the refreshed copy of the old
+    entry that is taken off, a bootstrap output.  The fold is counted whole.  A unit box has only about spread N / p sources, but
+    fold_factor x that share is NOT what its fold adds where the value lies: of `folded_state_variance`'s two terms only the key
+    noise is a sum over the sources; the rounding of a ciphertext's own mask words stays whole at its own coefficient.  Measured on
+    unit boxes alone, the filled coefficients carry 0.73 of the whole fold and 5.4 times the share (profiles/tables/README.md)."""
+    return table_norm2 + value_norm2 + fold_factor + 1.0 + (1.0 if mode == TABLE_SET else 0.0)
+
+
+def table_read_norm2(table_norm2: float) -> float:
+    """What a read of a resident table returns: the table's noise and the rotation that read it"""
+    return table_norm2 + 1.0
+
+
 def p_error(margin: float) -> float:
     """Probability that a Gaussian leaves +-margin standard deviations (one bootstrap)."""
     return math.erfc(margin / math.sqrt(2.0))

@@ -675,6 +675,183 @@ def plan_lookup(params, fold_factor, p, T_table, T_index, n_entries, digits, tab
     return [-(-n_entries // p ** (r + 1)) for r in range(digits)], out_norm2
 
 
+def plan_table(params, fold_factor, op, spread, n_entries, T_table, T_index=None, table_norm2=1.0, index_out_norm2=1.0, written=False,
+               value_norm2=1.0, table_max=None, value_max=None, min_margin=None):
+    """The pure part of a resident table (include/fbs_exec.h, "encrypted tables"): -> dict(norm2, max_value, out_norm2) or ValueError.
+    op "create": `table_norm2` is the entries' own, and the table carries that and the fold.  op "read": out_norm2 =
+    `params.table_read_norm2`.  op "add" / "set": norm2 = `params.table_write_norm2`, max_value the entries' new bound.
+    Refused: no fold key; spread < 1, no entry, more than floor(p / spread); an index state that has not the tables' samples, or
+    more than one sample writing a shared table; an index read with too little margin -- `params.lookup_index_margin` times spread
+    on a table never written, times spread / 2 on a written one and for every write (half of an entry's wide box is what the
+    other side's noise may use), against `params.refresh_margin_needed(params, 1)`; an add whose sum could leave [0, p); a write
+    after which a read would refresh below `params.SET_MARGIN`.  `min_margin`, when given, stands in for both margins."""
+    from .params import (SET_MARGIN, TABLE_ADD, TABLE_SET, lookup_index_margin, refresh_margin, refresh_margin_needed, table_read_norm2,
+                         table_write_norm2)
+    p, spread, n_entries, T_table = int(params.p_msg), int(spread), int(n_entries), int(T_table)
+    if op not in ("create", "read", "add", "set"):
+        raise ValueError("op %r is none of 'create', 'read', 'add', 'set'" % (op,))
+    if fold_factor is None:
+        raise ValueError("the server key has no fold key: a resident table is a fold, and so is every value written")
+    if spread < 1:
+        raise ValueError("an entry takes at least one box")
+    if n_entries < 1:
+        raise ValueError("a table has at least one entry")
+    if n_entries > p // spread:
+        raise ValueError("%d entries of %d boxes each are more than p = %d boxes hold (%d)" % (n_entries, spread, p, p // spread))
+    table_norm2 = float(np.max(table_norm2))
+    if op == "create":
+        return dict(norm2=table_norm2 + float(fold_factor), max_value=table_max, out_norm2=None)
+    T_index = int(T_index)
+    writing = op != "read"
+    if T_table != 1 and T_index != T_table:
+        raise ValueError("an index of %d samples for tables of %d" % (T_index, T_table))
+    if writing and T_table == 1 and T_index != 1:
+        raise ValueError("a shared table is written by an index of one sample, not %d: their writes would have no order" % T_index)
+    need = refresh_margin_needed(params, 1.0) if min_margin is None else float(min_margin)
+    need_out = SET_MARGIN if min_margin is None else float(min_margin)
+    margin = lookup_index_margin(params, float(np.max(index_out_norm2))) * (spread / 2.0 if writing or written else spread)
+    if margin < need:
+        raise ValueError("the index would be read at %.2f standard deviations, below the %.2f needed: refresh it first" % (margin, need))
+    if not writing:
+        out_norm2 = table_read_norm2(table_norm2)
+        if refresh_margin(params, None, out_norm2) < need_out:
+            raise ValueError("the entry read would refresh at %.2f standard deviations, below the %.2f needed: refresh the table first"
+                             % (refresh_margin(params, None, out_norm2), need_out))
+        return dict(norm2=table_norm2, max_value=table_max, out_norm2=out_norm2)
+    if value_max is None or table_max is None:
+        raise ValueError("a write needs the bounds of the table's entries and of the values")
+    table_max, value_max = int(table_max), int(value_max)
+    if value_max < 0:
+        raise ValueError("max_value %d is negative" % value_max)
+    new_max = value_max if op == "set" else table_max + value_max
+    if new_max > p - 1:
+        raise ValueError("a sum of entries up to %d and values up to %d reaches %d, above p - 1 = %d: it would not decrypt"
+                         % (0 if op == "set" else table_max, value_max, new_max, p - 1))
+    norm2 = table_write_norm2(table_norm2, float(np.max(value_norm2)), float(fold_factor), TABLE_SET if op == "set" else TABLE_ADD)
+    after = refresh_margin(params, None, table_read_norm2(norm2))
+    if after < need_out:
+        raise ValueError("a read after this write would refresh at %.2f standard deviations, below the %.2f needed: the table's noise "
+                         "budget is spent -- make a new server.table(...) of the refreshed entries()" % (after, need_out))
+    return dict(norm2=norm2, max_value=new_max, out_norm2=None)
+
+
+class ResidentTable:
+    """Encrypted tables that stay folded on the server's GPU (`Server.table`; include/fbs_exec.h, "encrypted tables"): one table per
+    plane and sample -- or one per plane, shared, where they were made of a state of one sample --, `n_entries` entries each, an entry
+    taking `spread` boxes: an index holds spread * i.  `read` returns entries by an encrypted index, `add` and `set` write by one;
+    `out_norm2`, `max_value` and `writes`, one figure a table (table (m, s) is number m T + s), follow the tables through their
+    writes (`plan_table`): planes written with noisier or larger values age faster than the others."""
+
+    def __init__(self, server, table, planes, n_entries, spread, T, out_norm2, max_value):
+        self.server, self.table, self.planes = server, table, list(planes)
+        self.n_entries, self.spread, self.T = int(n_entries), int(spread), int(T)
+        per_plane = lambda x, dtype: np.repeat(np.broadcast_to(np.asarray(x, dtype), (len(self.planes),)), self.T)   # noqa: E731
+        self.out_norm2, self.max_value = per_plane(out_norm2, np.float64), per_plane(max_value, np.int64)
+        self.writes = np.zeros(len(self.planes) * self.T, np.int64)
+        self.fingerprint = server.key.fingerprint
+
+    def _of(self, m):
+        """the tables of plane m"""
+        return slice(m * self.T, (m + 1) * self.T)
+
+    @property
+    def closed(self):
+        return self.table is None or bool(self.table.closed)
+
+    def _index(self, index, index_name):
+        if self.closed:
+            raise ValueError("the resident table is closed")
+        if not isinstance(index, ResidentOutputs) or index.closed:
+            raise ValueError("the index is not an open ResidentOutputs")
+        if index.server is not self.server or index.fingerprint != self.fingerprint:
+            raise ValueError("the index is resident on another server")
+        if index_name not in index.output_names:
+            raise ValueError("no row named %s" % index_name)
+        row = index.output_names.index(index_name)
+        return row, 1.0 if index.out_norm2 is None else float(index.out_norm2[row])
+
+    def _plan(self, op, m, T_index, index_norm2, **kw):
+        """plane m's tables through `plan_table`"""
+        key = self.server.key
+        at = self._of(m)
+        return plan_table(key.params, None if key.fold_bodies is None else key.fold_factor, op, self.spread, self.n_entries, self.T, T_index,
+                          self.out_norm2[at], index_norm2, bool(self.writes[at].any()), table_max=int(self.max_value[at].max()), **kw)
+
+    def read(self, index, index_name, out_names=None) -> "ResidentOutputs":
+        """-> a `ResidentOutputs` of one row per plane (`out_names`, or the planes' names): at every sample the entry i of the plane's
+        table, spread * i being the encrypted value of row `index_name` of `index` there"""
+        row, i2 = self._index(index, index_name)
+        out_norm2 = [self._plan("read", m, index.T, i2)["out_norm2"] for m in range(len(self.planes))]
+        names = list(self.planes) if out_names is None else list(out_names)
+        if len(names) != len(self.planes):
+            raise ValueError("%d output names for %d planes" % (len(names), len(self.planes)))
+        return ResidentOutputs(names, index.T, self.fingerprint, out_norm2, self.table.read(index.state, row), self.server)
+
+    def _write(self, op, index, index_name, values, value_names, max_value):
+        row, i2 = self._index(index, index_name)
+        if not isinstance(values, ResidentOutputs) or values.closed or values.server is not self.server:
+            raise ValueError("the values are not an open ResidentOutputs of this server")
+        value_names = [value_names] if isinstance(value_names, str) else list(value_names)
+        missing = [n for n in value_names if n not in values.output_names]
+        if missing or len(value_names) != len(self.planes):
+            raise ValueError("one value row a plane; no row named %s" % ", ".join(map(str, missing)) if missing else "one value row a plane")
+        rows = [values.output_names.index(n) for n in value_names]
+        v2 = np.ones(len(rows)) if values.out_norm2 is None else values.out_norm2[rows]
+        bounds = np.broadcast_to(np.asarray(max_value, np.int64), (len(rows),))      # one bound, or one a plane
+        plans = [self._plan(op, m, index.T, i2, value_norm2=float(v2[m]), value_max=int(bounds[m])) for m in range(len(rows))]
+        if values.T != index.T:
+            raise ValueError("values of %d samples for an index of %d" % (values.T, index.T))
+        self.table.write(index.state, row, values.state, rows, mode=self.table.SET if op == "set" else self.table.ADD)
+        for m, plan in enumerate(plans):                                             # (every plane was admitted before any was written)
+            self.out_norm2[self._of(m)], self.max_value[self._of(m)] = plan["norm2"], plan["max_value"]
+        self.writes += 1
+        return self
+
+    def add(self, index, index_name, values, value_names, max_value):
+        """entry[i] += value in every table, i named by row `index_name` of `index` as for `read`; plane m's values are row
+        value_names[m] of `values`, each at most `max_value` (an int, or one a plane).  Plain integer addition: refused when a sum could reach p."""
+        return self._write("add", index, index_name, values, value_names, max_value)
+
+    def set(self, index, index_name, values, value_names, max_value):
+        """entry[i] = value: the old entry is read, refreshed and taken off the value, and the difference added"""
+        return self._write("set", index, index_name, values, value_names, max_value)
+
+    def entries(self):
+        """-> a list of n_entries `ResidentOutputs` (the caller closes them), entry e of every table read out by a trivial index of
+        spread * e -- no noise on the index: exact whatever the tables' writes were.  Each has the tables' samples."""
+        if self.closed:
+            raise ValueError("the resident table is closed")
+        from .security import MODULUS
+        prm = self.server.key.params
+        delta = 2 * ((MODULUS + 2 * prm.p_msg) // (4 * prm.p_msg))
+        out = []
+        with self.server.ctx.state(1, self.T) as index:
+            cts = np.zeros((1, self.T, prm.ct_words), np.uint64)
+            for e in range(self.n_entries):
+                cts[..., -1] = self.spread * e * delta % MODULUS
+                index.put(cts)
+                out.append(ResidentOutputs(["%s[%d]" % (pl, e) for pl in self.planes], self.T, self.fingerprint,
+                                           [float(self.out_norm2[self._of(m)].max()) + 1.0 for m in range(len(self.planes))],
+                                           self.table.read(index, 0), self.server))
+        return out
+
+    def fetch(self):
+        """the tables' words, uint64 [tables][k+1][N] (table (m, s) is number m T + s)"""
+        if self.closed:
+            raise ValueError("the resident table is closed")
+        return self.table.words()
+
+    def close(self):
+        if self.table is not None:
+            self.table.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class SampleView:
     """The rows of a `ResidentOutputs` read through a sample map (`ResidentOutputs.samples`): T = len(index) samples, sample s the
     state's sample index[s], or a trivial ciphertext of `fill` where index[s] == SAMPLE_NONE.  A source of `Server.run_chain`
@@ -1131,6 +1308,52 @@ class Server:
         finally:
             for st in temps:
                 st.close()
+
+    def table(self, state, entries, spread=2, max_value=None, names=None) -> "ResidentTable":
+        """Writable encrypted tables of rows of `state` (include/fbs_exec.h, "encrypted tables"; fbs_table_create): `entries` is a list
+        of planes, each a list of row names (entry e = name e), as at `lookup`'s axis "rows" -- a table per plane and sample, or one
+        shared table per plane where `state` has one sample.  `state` is a `ResidentOutputs` of this server, or `PlainInputs`: the
+        server's own cleartext bits (a histogram's zeros), laid out as trivial ciphertexts -- no client ciphertext, no noise; T None
+        there is one sample, a shared table.  Folded ONCE, the tables stay on the GPU until the `ResidentTable` is closed; `state`
+        itself is not needed afterwards.  An entry takes `spread` boxes (2: a write by a noisy index is safe, `plan_table`), so an
+        index holds spread * i and a table floor(p / spread) entries.  max_value: the bound of the entries (None: p - 1, or the
+        largest plain value), which `add` holds its sums to.  names: one per plane (plane0, plane1, ..)."""
+        plain = isinstance(state, PlainInputs)
+        if not plain:
+            if not isinstance(state, ResidentOutputs) or state.closed:
+                raise ValueError("the table is not an open ResidentOutputs")
+            if state.server is not self or state.state.ctx is not self.ctx or state.fingerprint != self.key.fingerprint:
+                raise ValueError("the table is resident on another server")
+        row_names = state.input_names if plain else state.output_names
+        T = (state.T or 1) if plain else state.T
+        planes = [list(pl) for pl in entries]
+        if not planes or any(len(pl) != len(planes[0]) for pl in planes):
+            raise ValueError("every plane has the same number of entries, and there is at least one plane")
+        missing = [n for pl in planes for n in pl if n not in row_names]
+        if missing:
+            raise ValueError("no row named %s" % ", ".join(map(str, missing)))
+        rows = [[row_names.index(n) for n in pl] for pl in planes]
+        t2 = np.zeros(len(row_names)) if plain else np.ones(len(row_names)) if state.out_norm2 is None else state.out_norm2
+        prm = self.key.params
+        if max_value is None:
+            max_value = int(state.values.max()) if plain and state.values.size else prm.p_msg - 1
+        if not 0 <= int(max_value) <= prm.p_msg - 1:
+            raise ValueError("max_value %d outside [0, p - 1]" % max_value)
+        fold_factor = None if self.key.fold_bodies is None else self.key.fold_factor
+        norm2 = [plan_table(prm, fold_factor, "create", spread, len(pl), T, table_norm2=t2[pl], table_max=int(max_value))["norm2"] for pl in rows]
+        names = ["plane%d" % m for m in range(len(planes))] if names is None else list(names)
+        if len(names) != len(planes):
+            raise ValueError("%d names for %d planes" % (len(names), len(planes)))
+        if not plain:
+            return ResidentTable(self, self.ctx.table(state.state, rows, spread), names, len(planes[0]), spread, T, norm2, max_value)
+        from .security import MODULUS
+        delta = 2 * ((MODULUS + 2 * prm.p_msg) // (4 * prm.p_msg))
+        cts = np.zeros((len(row_names), T, prm.ct_words), np.uint64)   # trivial ciphertexts (0, .., 0, m Delta)
+        for j in range(len(row_names)):
+            cts[j, :, -1] = np.asarray(state.row(j), np.int64) * delta % MODULUS
+        with self.ctx.state(len(row_names), T) as made:
+            made.put(cts)
+            return ResidentTable(self, self.ctx.table(made, rows, spread), names, len(planes[0]), spread, T, norm2, max_value)
 
     def fold(self, env, state: "ResidentOutputs", left, right, back=None, fill=0) -> "ResidentOutputs":
         """A tree reduction of the T samples of `state` to one, on the GPU: `env` combines two samples into one, and each round
